@@ -83,6 +83,9 @@ def parse_args():
     ap.add_argument("--skip-cpu", action="store_true", help="no oracle parity / cpu_baseline legs")
     ap.add_argument("--parity-frac", type=float, default=1.0, help="fraction of every leg's output compared with the oracle")
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline leg, write what its last step returned (records + operations "
+                         "of a fixed sample of the pairs) to DIR/*.npy (see dump_sw_outputs)")
     return ap.parse_args()
 
 
@@ -412,6 +415,47 @@ def sw_parity(orc, osc, mode, x, y, L, d_out, d_ops, stride, n_check, threads, c
     return bool(ok), t_cpu
 
 
+DUMP_RECORD_COLUMNS = ("score", "xstart", "xend", "ystart", "yend", "xlen", "ylen", "n_ops", "ops_off",
+                       "clip_len0", "clip_len1", "clip_len2", "clip_len3", "n_clips", "mode", "status")
+DUMP_MAX_PAIRS = 1 << 17        # records: 131072 x 16 float64 = 16.8 MB
+DUMP_MAX_OPS_BYTES = 24 << 20   # operation slots as float32
+DUMP_SEED = 20240917
+
+
+def dump_sw_outputs(out_dir, d_out, d_ops, n_pairs, stride):
+    """--dump-outputs: what the headline step handed its caller in its last timed step (rank 0's pairs), for comparing two
+    builds output for output.  Integers stored as float64 / float32 (exact), 45 MB at most:
+      sw_pairs.npy      float64 (k,): the pairs sampled — all of them up to DUMP_MAX_PAIRS, else a fixed seeded sample, ascending
+      sw_records.npy    float64 (k, 16): their bg_alignment_t records, columns DUMP_RECORD_COLUMNS
+      sw_ops_pairs.npy  float64 (j,): every ceil(k / j)-th sampled pair, j bounded by DUMP_MAX_OPS_BYTES
+      sw_ops.npy        float32 (j, stride): their operation slots; the bytes outside [ops_off, ops_off + n_ops) are not
+                        written by the library and are stored as -1"""
+    idx = np.arange(n_pairs, dtype=np.int64)
+    if n_pairs > DUMP_MAX_PAIRS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pairs, DUMP_MAX_PAIRS, replace=False))
+    k = len(idx)
+    dev = d_out.device
+    torch.cuda.synchronize()
+    rec = d_out.view(n_pairs, 64).index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy().view(_lib.ALN_DTYPE).reshape(k)
+    cols = [rec[c] for c in DUMP_RECORD_COLUMNS[:9]] + [rec["clip_len"][:, i] for i in range(4)] + \
+           [rec[c] for c in DUMP_RECORD_COLUMNS[13:]]
+    records = np.stack([c.astype(np.float64) for c in cols], axis=1)
+    j = max(1, min(k, DUMP_MAX_OPS_BYTES // (4 * stride)))
+    step = -(-k // j)
+    oidx = idx[::step]
+    slots = d_ops.view(n_pairs, stride).index_select(0, torch.from_numpy(oidx).to(dev)).cpu().numpy()
+    orec = rec[::step]
+    start = orec["ops_off"].astype(np.int64) - oidx * stride  # first operation byte within the pair's slot
+    col = np.arange(stride)[None, :]
+    valid = (col >= start[:, None]) & (col < (start + orec["n_ops"].astype(np.int64))[:, None])
+    ops = np.where(valid, slots.astype(np.float32), np.float32(-1))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"sw_pairs": idx.astype(np.float64), "sw_records": records, "sw_ops_pairs": oidx.astype(np.float64), "sw_ops": ops}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def sw_roofline(kernel, fill_ms, tb_ms, pairs_per_launch, L, n_ops_mean, note, shape_key="sw_pairs_per_launch"):
     # algorithmic bytes per pair (SURVEY.md §8d, traceback spilled to HBM):
     #   m + n + 24 + n_ops + 2 B x (m+1)(n+1) reference traceback cells
@@ -461,6 +505,8 @@ def main():
             GATHER.gather(rec, [n_pairs] * world)
 
     sw_t = timed_steps(sw_step, args.steps, args.warmup, dev)
+    if args.dump_outputs and rank == 0:
+        dump_sw_outputs(args.dump_outputs, d_out, d_ops, n_pairs, stride)
     gcups = world * float(n_pairs) * L * L * args.steps / sw_t / 1e9
     tm = kernel_timing(ctx, sw_step)
     fill_ms = tm["fill_ms"] / max(1, tm["fill_launches"])

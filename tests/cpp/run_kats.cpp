@@ -3,7 +3,9 @@
 // Needs a gfx950 device (the engine has no CPU fallback).  Usage: run_kats [filter-substring]
 #include <cstdio>
 #include <cstring>
+#include <filesystem>
 #include <sstream>
+#include <unistd.h>
 
 #include "biogpu.hpp"
 
@@ -305,7 +307,9 @@ static void kat_fmindex_save_and_load() {
     fmindex::FMIndex fm(b, bwt::less(b, alphabet), bwt::Occ(b, 3, alphabet));
     fm.attach(sa);
     fm.attach_text(t);
-    const std::string path = "/tmp/biogpu_kat_index.bgfm";
+    // a name of this process's own in the temporary directory: concurrent or earlier runs cannot collide with it
+    const std::string path = (std::filesystem::temp_directory_path() /
+                              ("biogpu_kat_index_" + std::to_string(getpid()) + ".bgfm")).string();
     fm.save(path);
     const auto fm2 = fmindex::FMIndex::load(path);
     std::vector<Text> pats;
@@ -329,7 +333,7 @@ static void kat_fmindex_save_and_load() {
     const auto h1 = fm.seed_extend_batch(scoring, {r0}), h2 = fm2->seed_extend_batch(scoring, {r0});
     CHECK(h2[0].alignment && h1[0].alignment && h2[0].alignment->score == h1[0].alignment->score);
     CHECK_EQ(h2[0].ref_start, (size_t)2000);
-    CHECK(panics([] { fmindex::FMIndex::load("/tmp/biogpu_kat_index.missing"); }));
+    CHECK(panics([&] { fmindex::FMIndex::load(path + ".missing"); }));
     // the loaded handle knows its length and its BWT (bg_fm_len / bg_fm_bwt): FMDIndex::from works on it when the text is
     // DNA + '$' (fmindex.rs:311-329)
     CHECK_EQ(fm2->len(), fm.len());

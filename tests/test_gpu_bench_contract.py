@@ -48,3 +48,43 @@ def test_bench_line_has_the_contract_fields_and_green_parity():
     assert d["fm"]["roofline"]["requested_lines_per_launch"] > 0
     flags = {k: v for k, v in d["parity"].items() if isinstance(v, bool)}
     assert len(flags) >= 10 and all(flags.values()), flags
+
+
+def test_dump_outputs_hold_the_headline_results(tmp_path):
+    """--dump-outputs DIR: after `--steps` timed steps, DIR holds the headline step's records and operations as float .npy
+    files, and they are the oracle's for the bench's own pairs (below 65536 pairs synth_gpu.sw_pairs_big makes exactly
+    synth.sw_pairs(n, L, seed=2); every pair is dumped below 131072)."""
+    import numpy as np
+
+    import oracle_py as orc
+    from rust_bio_amd import synth
+
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    n, L, dump = 3000, 150, tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", str(n),
+           "--read-len", str(L), "--skip-cpu", "--skip-packed", "--skip-k1", "--skip-semiglobal", "--skip-fm", "--fm-big-genome", "0",
+           "--skip-fmd", "--skip-banded", "--skip-ingest", "--skip-pipeline", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    d = json.loads([ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    a = {nm: np.load(dump / (nm + ".npy")) for nm in ("sw_pairs", "sw_records", "sw_ops_pairs", "sw_ops")}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert (a["sw_pairs"] == np.arange(n)).all() and (a["sw_ops_pairs"] == np.arange(n)).all()
+    rec, ops = a["sw_records"], a["sw_ops"]
+    stride = 2 * L + 4
+    assert rec.shape == (n, 16) and ops.shape == (n, stride)
+    x, xo, y, yo = synth.sw_pairs(n, L, seed=2)
+    oout, oops, ostride = orc.align_batch(orc.make_scoring(-5, -1, 1, -1), "local", x, xo, y, yo)
+    # columns: score xstart xend ystart yend xlen ylen n_ops ops_off clip_len[4] n_clips mode status
+    for col, f in ((0, "score"), (1, "xstart"), (2, "xend"), (3, "ystart"), (4, "yend"), (7, "n_ops")):
+        assert (rec[:, col] == oout[f].astype(np.float64)).all(), f
+    kq = rec[:, 7].astype(np.int64)
+    assert (rec[:, 8] == (np.arange(n) + 1) * stride - kq).all()
+    assert ((ops >= 0).sum(axis=1) == kq).all()
+    kind = (oops.reshape(n, ostride) & np.uint64(0xFF)).astype(np.float32)
+    for p in range(n):
+        assert (ops[p, stride - kq[p]:] == kind[p, :kq[p]]).all(), p
