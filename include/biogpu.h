@@ -631,6 +631,23 @@ int bg_get_timing(bg_ctx* ctx, bg_timing_t* out);
 /* Pairs of the last banded call on this ctx that the packed-int16 fill flagged (a band cell below the floor of its strip's
  * 16-bit range) and the int32 kernels recomputed.  Waits for the call's kernels. */
 int bg_band_redo_pairs(bg_ctx* ctx, uint64_t* out);
+/* Fill kernel families, one bit each, for bg_last_fill_kernels. */
+enum {
+    BG_FILL_K1_WIDE = 0x1,       /* K1, int32 values (sw_fill.inc) */
+    BG_FILL_K1_NARROW = 0x2,     /* K1, scaled int32 keys */
+    BG_FILL_K1_LF = 0x4,         /* K1's local flavour (scaled keys, no clip machinery) */
+    BG_FILL_K1P = 0x8,           /* K1p, two pairs per lane in int16 halves (sw_fill_pk16.inc) */
+    BG_FILL_K1P_LF = 0x10,       /* K1p's local flavour */
+    BG_FILL_K3 = 0x20,           /* banded, one pair per wavefront (banded_fill.hip) */
+    BG_FILL_K3V2_WIDE = 0x40,    /* banded, eight pairs per wavefront, int32 values (banded_fill2.inc) */
+    BG_FILL_K3V2_NARROW = 0x80,  /* ... scaled int32 keys */
+    BG_FILL_K3I = 0x100,         /* banded interior runs, scaled int32 keys (banded_fill2i.hip) */
+    BG_FILL_K3P = 0x200          /* banded interior runs, uint16 keys per strip (banded_fill2p.hip) */
+};
+/* The fill kernel families the last bg_align_batch* or bg_align_banded_* call on this ctx launched, OR-ed over its
+ * sub-batches (BG_FILL_* bits; 0 before the first such call).  A family counts when it was launched, even if it found
+ * nothing to do (K3i behind K3p only recomputes the pairs K3p flagged). */
+int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask);
 int bg_enable_timing(bg_ctx* ctx, int on);
 
 #ifdef __cplusplus

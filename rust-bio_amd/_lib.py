@@ -15,6 +15,9 @@ ERRORS = {-1: "INVALID_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -5: "SENTINE
           -6: "POSITIVE_PENALTY", -7: "OUT_OF_ALPHABET", -8: "TOO_LARGE", -9: "OPS_CAP",
           -10: "TRACEBACK", -11: "UNSUPPORTED", -12: "IO"}
 MIN_SCORE = -858993459
+# BG_FILL_* (include/biogpu.h): fill kernel families, as Context.last_fill_kernels() reports them
+FILL = {"K1_WIDE": 0x1, "K1_NARROW": 0x2, "K1_LF": 0x4, "K1P": 0x8, "K1P_LF": 0x10, "K3": 0x20, "K3V2_WIDE": 0x40,
+        "K3V2_NARROW": 0x80, "K3I": 0x100, "K3P": 0x200}
 
 
 class BiogpuError(RuntimeError):
@@ -90,7 +93,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_align_batch", "bg_align_batch_dev", "bg_align_banded_batch", "bg_align_banded_batch_dev", "bg_band_create_batch",
            "bg_align_banded_bands_batch", "bg_band_from_matches_batch", "bg_sparse_find_kmer_matches", "bg_sparse_sdpkpp",
            "bg_sparse_lcskpp", "bg_sparse_sdpkpp_union_lcskpp_path", "bg_sparse_expand_kmer_matches", "bg_fastq_parse",
-           "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_pack2_host",
+           "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_pack2_host",
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -211,6 +214,7 @@ def lib():
         L.bg_get_timing.argtypes = [vp, C.POINTER(TimingC)]
         L.bg_enable_timing.argtypes = [vp, i32]
         L.bg_band_redo_pairs.argtypes = [vp, C.POINTER(u64)]
+        L.bg_last_fill_kernels.argtypes = [vp, C.POINTER(u32)]
         L.bg_pack2_host.argtypes = [vp, u64, vp, vp]
         for s in SYMBOLS:
             if getattr(L, s).restype is C.c_int or s.startswith("bg_") and getattr(L, s).restype is None:
@@ -242,6 +246,12 @@ class Context:
         """pairs of the last banded call that the packed fill flagged and the int32 kernels recomputed"""
         v = C.c_uint64(0)
         check(lib().bg_band_redo_pairs(self.h, C.byref(v)))
+        return int(v.value)
+
+    def last_fill_kernels(self):
+        """BG_FILL_* bits (FILL) of the fill kernel families the last align call on this ctx launched"""
+        v = C.c_uint32(0)
+        check(lib().bg_last_fill_kernels(self.h, C.byref(v)))
         return int(v.value)
 
     def close(self):

@@ -324,6 +324,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
                              uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used, uint64_t* band_cells,
                              const BandMaker& make_band, const uint32_t* dev_kw = nullptr, const BandDevIO* dio = nullptr) {
     if (!ctx || !sc || mode < BG_MODE_CUSTOM || mode > BG_MODE_LOCAL) return BG_ERR_INVALID_ARG;
+    ctx->fill_mask = 0;
     int rc = check_scoring(sc);
     if (rc) return rc;
     if (ops_used) *ops_used = 0;
@@ -377,7 +378,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
     // every reachable score within 24 bits: the scaled-key variant of K3v2 applies (same bound as sw_api.hip)
     const int64_t mag = std::max<int64_t>({std::abs((int64_t)cs.gap_open), std::abs((int64_t)cs.gap_extend),
                                            std::abs((int64_t)sc->match_score), std::abs((int64_t)sc->mismatch_score), 1});
-    auto clip_ok = [](int32_t c) { return c <= BG_MIN_SCORE / 2 || c >= -(1 << 22); };  // 'minus infinity' or small
+    auto clip_ok = [](int32_t c) { return c <= kNarrowNegClip || c >= -(1 << 22); };  // 'minus infinity' or small (banded_kernels.h)
     const bool narrow = !ctx->force_wide && mag * ((int64_t)max_x + (int64_t)max_y + 8) < (1 << 24) && clip_ok(cs.xclip_prefix) &&
                         clip_ok(cs.xclip_suffix) && clip_ok(cs.yclip_prefix) && clip_ok(cs.yclip_suffix);
 
@@ -879,8 +880,8 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             a.tb_flip = kTbFlip;
             // interior runs (band_split): scaled keys, x kept whole, a real y-prefix clip — semiglobal-like scorings
             a.ring32 = ctx->band_window ? 0 : 1;
-            a.split = (narrow && !ctx->band_interior_off && cs.xclip_prefix <= BG_MIN_SCORE / 2 && cs.xclip_suffix <= BG_MIN_SCORE / 2 &&
-                       cs.yclip_prefix > BG_MIN_SCORE / 2) ? 1 : 0;
+            a.split = (narrow && !ctx->band_interior_off && cs.xclip_prefix <= kNarrowNegClip && cs.xclip_suffix <= kNarrowNegClip &&
+                       cs.yclip_prefix > kNarrowNegClip) ? 1 : 0;
             // ... and, where the scoring and the lengths fit its 16-bit strip-relative keys, K3p takes the runs first
             // (banded_fill2p.hip: target / threshold as computed there; at least 2^14 key units == 1024 score units of room)
             {
@@ -897,7 +898,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             if (on_device) B.started_target += band_fill2_blocks(a.n_pairs);
             // K3v2 / K3p (K3i): eight pairs per wavefront; the epilogue goes to the traceback stream, ahead of K4 — the fill
             // stream goes straight on with the next sub-batch (event timing keeps everything on one stream)
-            launch_band_fill2(a, narrow, st, S.fill_gone, ctx->timing || ctx->band_window ? nullptr : st_tb, sp != st ? sp : nullptr, S.pre_done);
+            ctx->fill_mask |= launch_band_fill2(a, narrow, st, S.fill_gone, ctx->timing || ctx->band_window ? nullptr : st_tb, sp != st ? sp : nullptr, S.pre_done);
             S.fill_gone_valid = true;
         }
         else {
@@ -908,6 +909,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
                 BG_HIP(hipStreamWaitEvent(st, S.pre_done, 0));
             }
             fill<<<dim3((unsigned)((take + 3) / 4)), dim3(256), 0, st>>>(a);
+            ctx->fill_mask |= BG_FILL_K3;
             S.fill_gone_valid = false;
         }
         BG_HIP(hipGetLastError());

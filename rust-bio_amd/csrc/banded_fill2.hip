@@ -304,8 +304,8 @@ uint32_t band_fill2_blocks(uint32_t n_pairs) {
     return (jobs + 3) / 4;
 }
 
-bool launch_band_fill2(const BandArgs& a0, bool narrow, hipStream_t st, hipEvent_t after_fill, hipStream_t epi, hipStream_t pre,
-                       hipEvent_t pre_done) {
+uint32_t launch_band_fill2(const BandArgs& a0, bool narrow, hipStream_t st, hipEvent_t after_fill, hipStream_t epi, hipStream_t pre,
+                           hipEvent_t pre_done) {
     // epi: the epilogue runs there, behind after_fill (so that `st` can go on with the fill of the next sub-batch); null: on st
     // pre: the stream that prepared this sub-batch (banded_api.hip); phase 1 of a split fill runs there too — under the tail
     //      of the previous sub-batch's long kernel instead of behind it — and `st` takes over behind pre_done; null: all on st
@@ -319,17 +319,19 @@ bool launch_band_fill2(const BandArgs& a0, bool narrow, hipStream_t st, hipEvent
     BandArgs a = a0;
     const uint32_t jobs = (a.n_pairs + PW - 1) / PW;
     const dim3 grid((jobs + 3) / 4);
+    uint32_t launched = 0;  // BG_FILL_* families
     if (narrow) {
         // scorings that admit interior runs (band_split, banded_kernels.h): K3v2 on the strips before them, K3i on the runs,
         // K3v2 on the strips behind them — three launches, the first and the last a few strips per pair
-        const bool split = a.split && a.sc.xp <= NEG / 2;
+        const bool split = a.split && a.sc.xp <= kNarrowNegClip;
         uint32_t* const started = a.started;
         if (!split) {
             join_pre();
             a.phase = 0;
             a.split = 0;
-            if (a.sc.xp > NEG / 2) launch_fill2_narrow_xp(a, grid, st);
+            if (a.sc.xp > kNarrowNegClip) launch_fill2_narrow_xp(a, grid, st);
             else launch_fill2_narrow(a, grid, st);
+            launched = BG_FILL_K3V2_NARROW;
         } else {
             a.started = nullptr;  // whoever waits for "the fill is resident" means the long launch
             a.phase = 1;
@@ -348,9 +350,11 @@ bool launch_band_fill2(const BandArgs& a0, bool narrow, hipStream_t st, hipEvent
                 launch_fill2_narrow(a, grid, st);
                 launch_fill2i(a, grid, st);
                 a.redo = 0;
+                launched |= BG_FILL_K3P;
             } else {
                 launch_fill2i(a, grid, st);
             }
+            launched |= BG_FILL_K3V2_NARROW | BG_FILL_K3I;
             a.started = nullptr;
             a.phase = 2;
             launch_fill2_narrow(a, grid, st);
@@ -363,11 +367,12 @@ bool launch_band_fill2(const BandArgs& a0, bool narrow, hipStream_t st, hipEvent
         a.phase = 0;
         a.split = 0;
         launch_fill2_wide(a, grid, st);
+        launched = BG_FILL_K3V2_WIDE;
         if (after_fill) (void)hipEventRecord(after_fill, st);
         if (epi && after_fill) (void)hipStreamWaitEvent(epi, after_fill, 0);
         banded_epilogue_kernel<2, false><<<dim3((a.n_pairs + 3) / 4), dim3(256), 0, epi && after_fill ? epi : st>>>(a);
     }
-    return true;
+    return launched;
 }
 
 }  // namespace bgband_dev

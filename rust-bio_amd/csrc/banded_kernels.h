@@ -26,6 +26,12 @@ namespace bgband_dev {
 using namespace bgsw;
 
 enum : uint32_t { BP_OK = 0, BP_TOO_MANY_CELLS = 1, BP_UNSUPPORTED = 2 };
+// The narrow banded kernels (K3v2 narrow, K3i, K3p) map the reference's integers below NEG / 2 to the scaled domain
+// relative to NEG (banded_fill2.inc: to_s, from_scaled).  That map is exact while a value stays within 2^25 of NEG, and
+// everything derived from a clip moves it by less than 2^24 (the admission bound, banded_api.hip), so a clip at or below
+// this is 'minus infinity' to them.  A clip above it must be a small real score (>= -2^22); anything between the two
+// takes the wide kernels: to_s(-700 000 000) >> 4 would be +91 884 595.
+constexpr int32_t kNarrowNegClip = NEG + (1 << 20);
 // Traceback bytes of a pair (one per band cell, rows 1..m; row 0 is a closed form): a row's cells cf..cl in groups of
 // 16 — K3v2 hands them over in complete 16-byte groups (banded_fill2.hip) — and the groups of eight consecutive rows
 // interleaved: group g of row i sits at row_off[i] + g * 128, row_off[i] = (base of the rows (i-1)/8*8+1 ..) +
@@ -127,9 +133,9 @@ __device__ __forceinline__ uint32_t tb_cell_norm(uint32_t b) { return ((b >> 1) 
 typedef void (*band_fill_fn)(const BandArgs);
 band_fill_fn get_band_fill(int sm);
 // K3v2 (banded_fill2.hip): LP lanes per pair, R rows per lane, MatchParams scoring; the last-column
-// epilogue runs in its own kernel.  Returns false if the geometry is not instantiated.
-bool launch_band_fill2(const BandArgs& a, bool narrow, hipStream_t st, hipEvent_t after_fill = nullptr, hipStream_t epi = nullptr,
-                       hipStream_t pre = nullptr, hipEvent_t pre_done = nullptr);
+// epilogue runs in its own kernel.  Returns the BG_FILL_* families it launched.
+uint32_t launch_band_fill2(const BandArgs& a, bool narrow, hipStream_t st, hipEvent_t after_fill = nullptr, hipStream_t epi = nullptr,
+                           hipStream_t pre = nullptr, hipEvent_t pre_done = nullptr);
 void launch_fill2i(const BandArgs& a, dim3 grid, hipStream_t st);  // banded_fill2i.hip: the interior runs
 void launch_fill2p(const BandArgs& a, hipStream_t st);             // banded_fill2p.hip: the same, two pairs per lane group
 uint32_t band_fill2_blocks(uint32_t n_pairs);  // thread blocks launch_band_fill2 starts for n_pairs

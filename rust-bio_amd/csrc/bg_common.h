@@ -100,6 +100,7 @@ struct bg_ctx {
     bool timing = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
     bg_timing_t last = {};
+    uint32_t fill_mask = 0;  // BG_FILL_* families the last align call launched (bg_last_fill_kernels)
 };
 
 // grow-only device scratch

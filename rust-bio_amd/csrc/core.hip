@@ -318,6 +318,12 @@ extern "C" int bg_enable_timing(bg_ctx* ctx, int on) {
     return BG_OK;
 }
 
+extern "C" int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask) {
+    if (!ctx || !mask) return BG_ERR_INVALID_ARG;
+    *mask = ctx->fill_mask;
+    return BG_OK;
+}
+
 extern "C" int bg_get_timing(bg_ctx* ctx, bg_timing_t* out) {
     if (!ctx || !out) return BG_ERR_INVALID_ARG;
     *out = ctx->last;

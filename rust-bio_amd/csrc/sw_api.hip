@@ -369,6 +369,8 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
         }
     }
     if (!fill) return BG_ERR_UNSUPPORTED;
+    ctx->fill_mask |= pk16 ? (a.g.tb_fmt == 2 ? BG_FILL_K1P_LF : BG_FILL_K1P)
+                           : a.g.tb_fmt == 3 ? BG_FILL_K1_LF : narrow ? BG_FILL_K1_NARROW : BG_FILL_K1_WIDE;
     if (packed_codes) {
         if (pk16) {
             a.packed = 1;  // K1p reads the 2-bit streams as they are
@@ -499,6 +501,7 @@ extern "C" int bg_align_batch_dev(bg_ctx* ctx, const bg_scoring_t* sc, int mode,
                                   const uint64_t* d_y_off, uint32_t max_xlen, uint32_t max_ylen,
                                   bg_alignment_t* d_out, uint8_t* d_ops, uint64_t ops_stride,
                                   void* stream) {
+    if (ctx) ctx->fill_mask = 0;
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, d_x, d_x_off, d_y, d_y_off, max_xlen, max_ylen, d_out, d_ops, ops_stride, stream, -1);
 }
 
@@ -513,6 +516,7 @@ extern "C" int bg_align_batch_packed_dev(bg_ctx* ctx, const bg_scoring_t* sc, in
     for (int a = 0; a < 4; a++)
         for (int b = a + 1; b < 4; b++)
             if (codes[a] == codes[b]) return BG_ERR_INVALID_ARG;
+    if (ctx) ctx->fill_mask = 0;
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, (const uint8_t*)d_x, d_x_off, (const uint8_t*)d_y, d_y_off, max_xlen, max_ylen,
                                 d_out, d_ops, ops_stride, stream, -1, codes);
 }
@@ -829,6 +833,7 @@ extern "C" int bg_align_batch(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uin
                               const uint64_t* y_off, bg_alignment_t* out, uint8_t* ops_buf,
                               uint64_t ops_cap, uint64_t* ops_used) {
     if (!ctx || !sc) return BG_ERR_INVALID_ARG;
+    ctx->fill_mask = 0;
     int rc = check_scoring(sc);
     if (rc) return rc;
     if (ops_used) *ops_used = 0;

@@ -35,7 +35,22 @@ def as_dict(a):
             "xlen": a.xlen, "ylen": a.ylen, "ops": a.operations}
 
 
-def differential(kw, some, mode, k, w, xs, ys, opts=None):
+def oracle_banded(kw, some, mode, k, w, xs, ys):
+    """the oracle's record of every pair (band_cells included), None where the reference itself panics / loops"""
+    okw = dict(kw)
+    okw["match_scores_some"] = 1 if some else 0
+    osc = orc.make_scoring(**okw)
+    wants = []
+    for p in range(len(xs)):
+        try:
+            wants.append(orc.banded_align(osc, mode, k, w, xs[p], ys[p]))
+        except RuntimeError:
+            wants.append(None)
+    return wants
+
+
+def differential(kw, some, mode, k, w, xs, ys, opts=None, wants=None):
+    """wants: oracle_banded(...) of the same arguments, when the caller compares several runs with one oracle pass"""
     al = Aligner.with_scoring(engine_scoring(kw, some), k, w)
     for k_, v_ in (opts or {}).items():
         al.ctx.set_option(k_, v_)
@@ -51,14 +66,12 @@ def differential(kw, some, mode, k, w, xs, ys, opts=None):
         engine_failed = True
     for k_ in (opts or {}):
         al.ctx.set_option(k_, 0)  # (the default ctx is shared between Aligners)
-    okw = dict(kw)
-    okw["match_scores_some"] = 1 if some else 0
-    osc = orc.make_scoring(**okw)
+    if wants is None:
+        wants = oracle_banded(kw, some, mode, k, w, xs, ys)
     n_bad = 0
     for p in range(len(xs)):
-        try:
-            want = orc.banded_align(osc, mode, k, w, xs[p], ys[p])
-        except RuntimeError:
+        want = dict(wants[p]) if wants[p] is not None else None
+        if want is None:
             # the reference itself panics / loops forever on this pair: the engine must say so
             assert out["status"][p] != 0, (mode, k, w, kw, p, xs[p], ys[p])
             n_bad += 1

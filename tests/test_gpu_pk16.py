@@ -40,14 +40,22 @@ def related_pairs(rng, n_pairs, m_of, n_of, alpha=ALPHA):
 MODES = {"custom": 0, "global": 1, "semiglobal": 2, "local": 3}
 
 
-def local_vs_oracle(kw, xs, ys, mode="local", clips=None):
+def local_vs_oracle(kw, xs, ys, mode="local", clips=None, opts=None):
+    """every record and operation against the oracle; opts: ctx options for this call.  Returns (records, operations,
+    ctx) — ctx.last_fill_kernels() tells which fill ran."""
     sc = Scoring.from_scores(kw["gap_open"], kw["gap_extend"], kw["match"], kw["mismatch"])
     for c, v in (clips or {}).items():
         setattr(sc, c, v)
     al = Aligner.with_scoring(sc)
     x, xo = _lib.concat(xs)
     y, yo = _lib.concat(ys)
-    out, ops = al.align_arrays(MODES[mode], x, xo, y, yo)
+    for k_, v_ in (opts or {}).items():
+        al.ctx.set_option(k_, v_)
+    try:
+        out, ops = al.align_arrays(MODES[mode], x, xo, y, yo)
+    finally:
+        for k_ in (opts or {}):
+            al.ctx.set_option(k_, 0)  # (the default ctx is shared between Aligners)
     oout, oops, stride = orc.align_batch(orc.make_scoring(**kw, **dict(CLIPS, **(clips or {}))), mode, x, xo, y, yo, threads=8)
     for f in ("score", "xstart", "xend", "ystart", "yend", "xlen", "ylen", "n_ops"):
         bad = np.nonzero(out[f].astype(np.int64) != oout[f].astype(np.int64))[0]
@@ -56,6 +64,7 @@ def local_vs_oracle(kw, xs, ys, mode="local", clips=None):
     for p in range(len(xs)):
         want = orc.decode_ops(oops[p * stride:p * stride + int(oout["n_ops"][p])])
         assert decode_ops(out[p], ops) == want, (mode, clips, kw, p, xs[p], ys[p])
+    return out, ops, al.ctx
 
 
 BASE = dict(gap_open=-5, gap_extend=-1, match=1, mismatch=-1)
