@@ -99,16 +99,9 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *   band_packed_off = 1    interior runs on the int32 kernel (K3i) only: no packed-int16 kernel (K3p) in front of it
  *   band_packed_thresh     K3p's detect-and-recompute threshold in key units (score * 16); 0 = derived from the scoring,
  *                          65535 = every pair is flagged and recomputed by the int32 kernels (tests)
- *   band_tail_last / band_window / band_raster_late = 1  A/B switches of the banded pipeline's order (round-3 behaviour)
- *   band_join_serial = 1   the k-mer join of a sub-batch on the builder's stream instead of its own (A/B)
- *   band_pre_serial = 1    a banded fill's preparation (pair table, waits, first strips) on the fill stream instead of its own (A/B)
  *   band_chain_global  chaining tree placement: 0 LDS, 1 global scratch, -1 by batch size (default)
  *   band_join_global = 1  k-mer join with its table in global memory even where the LDS flavour applies
- *   band_join_late = 1    the k-mer join of a sub-batch waits for the chaining of the one before it (A/B: measured slower)
- *   band_p_block512 = 1   K3p in blocks of eight wavefronts compiled for 168 VGPRs instead of four at 187 (A/B: measured slower)
  *   band_chain_rows    global-tree chaining with four pairs per wavefront (chain_rows_kernel; default 1) or one (0: A/B, tests)
- *   band_host_sync = 1 the chaining of a sub-batch is launched after a host wait for K4 of two sub-batches ago (rounds 2-4)
- *                      instead of a stream wait (A/B)
  *   fm_wide_from       texts of this many symbols or more get the 64-bit index layout (default 2^32 - 1; tests lower it so
  *                      that small texts exercise csrc/fm_wide.hip); 0 restores the default
  *   fm_wide_sb_shift   log2 of the rank blocks per superblock of the 64-bit layout (default 17; 0 .. 24; tests use small

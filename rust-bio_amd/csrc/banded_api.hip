@@ -154,19 +154,15 @@ struct bg_band_scratch {
         hipEvent_t copied = nullptr, filled = nullptr, traced = nullptr, built = nullptr, matched = nullptr;
         bool built_valid = false;  // `built` has been recorded in this call
         hipEvent_t fill_gone = nullptr;  // the fill kernel itself is off the device (its epilogue may still run)
-        hipEvent_t pre_done = nullptr;   // ... and what pre_stream did for it is done
+        hipEvent_t pre_done = nullptr;   // ... and what its preparation stream (aux_stream) did for it is done
         hipEvent_t cleared = nullptr;    // the aux block has been zeroed (on aux_stream)
-        bool busy = false, fill_gone_valid = false;
+        bool busy = false;
     } set[2];
     // device band builder (band_device.hip): scratch slices per pair + its per-pair state
     void* db[2][17] = {};  // the builder's own arrays, one set per sub-batch parity (the join of c + 2 runs next to the chaining of c + 1)
     size_t db_cap[2][17] = {};
     hipStream_t build_stream = nullptr;
-    hipStream_t join_stream = nullptr;  // k-mer join + chain preparation of the sub-batch after next
-    hipStream_t pre_stream = nullptr;   // what a fill needs before its long kernel: the pair table, the waits, K3v2's first strips
     hipEvent_t seq_ready = nullptr;
-    hipEvent_t chained = nullptr;  // the chaining's event loop of the sub-batch being built has left the device
-    bool chained_valid = false;    // ... recorded in this call, under a running fill
     void* h_state = nullptr;  // pinned copy of the builder's BandDevPair array
     size_t h_state_cap = 0;
     void* io[6] = {};  // x, y, x_off, y_off, out, ops on the device
@@ -180,7 +176,7 @@ struct bg_band_scratch {
     hipStream_t dl_stream = nullptr;            // ... which a few blocks on this high-priority stream bring to h_ops meanwhile
     static constexpr uint64_t kDlSlots = 1024;
     hipStream_t tb_stream = nullptr;
-    hipStream_t aux_stream = nullptr;   // clears the aux block of the next sub-batch under the running fill
+    hipStream_t aux_stream = nullptr;   // clears the aux block of the next sub-batch under the running fill, and prepares that fill
     hipStream_t copy_stream = nullptr;  // host-buffer flavour: sequence slices go up here
     uint32_t* d_started = nullptr;  // blocks of the K3v2 launches of the current call that have started (see banded_fill2.hip)
     uint32_t started_target = 0;    // ... and how many have been launched
@@ -222,8 +218,6 @@ void bg_band_scratch_free(bg_band_scratch* b) {
     if (b->dl_stream) hipStreamDestroy(b->dl_stream);
     for (auto& set : b->db)
         for (void* p : set) hipFree(p);
-    if (b->join_stream) hipStreamDestroy(b->join_stream);
-    if (b->pre_stream) hipStreamDestroy(b->pre_stream);
     hipHostFree(b->h_state);
     hipHostFree(b->h_ops);
     if (b->tb_stream) hipStreamDestroy(b->tb_stream);
@@ -231,7 +225,6 @@ void bg_band_scratch_free(bg_band_scratch* b) {
     if (b->copy_stream) hipStreamDestroy(b->copy_stream);
     if (b->build_stream) hipStreamDestroy(b->build_stream);
     if (b->seq_ready) hipEventDestroy(b->seq_ready);
-    if (b->chained) hipEventDestroy(b->chained);
     delete b;
 }
 
@@ -300,11 +293,9 @@ using BandMaker = std::function<bool(uint64_t, bgband::Band&, bgband::Workspace&
 // ones, and neither can sit in front of the other or of the fill: the gap between two fills drops from 10.8 to 1.9 ms
 // (profiles/r05_banded_timeline_prio.txt) — and the call gains nothing, because the join that used to run in that gap now
 // starves under two fills in a row and the chaining behind it starts late (profiles/r05_banded_pipeline_experiments.txt).
-// BG_BAND_STREAM_PRIO=0: all normal (rounds 2-4).
 int band_stream_create(hipStream_t* s, int level) {
-    static const int on = [] { const char* e = getenv("BG_BAND_STREAM_PRIO"); return e ? atoi(e) : 1; }();
     int lo = 0, hi = 0;
-    if (!on || level == 0 || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi)
+    if (level == 0 || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi)
         return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess ? BG_OK : BG_ERR_HIP;
     return hipStreamCreateWithPriority(s, hipStreamNonBlocking, level > 0 ? hi : lo) == hipSuccess ? BG_OK : BG_ERR_HIP;
 }
@@ -460,8 +451,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
         }
     } slices;
     const uint64_t n_slices = dio ? 0 : (n_pairs + chunk_pairs - 1) / chunk_pairs;
-    uint64_t slices_up = 0, waited_fill = 0, waited_build = 0;
-    (void)waited_build;
+    uint64_t slices_up = 0, waited_fill = 0;
     if (n_slices && !B.copy_stream && (rc = band_stream_create(&B.copy_stream, -1))) return rc;
     auto upload_slices = [&](uint64_t upto) -> int {  // slices [slices_up, upto)
         for (; slices_up < std::min(upto, n_slices); slices_up++) {
@@ -519,7 +509,6 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
     if (!B.build_stream) {
         BG_HIP(hipStreamCreateWithFlags(&B.build_stream, hipStreamNonBlocking));
         BG_HIP(hipEventCreateWithFlags(&B.seq_ready, hipEventDisableTiming));
-        BG_HIP(hipEventCreateWithFlags(&B.chained, hipEventDisableTiming));
         for (auto& s : B.set) {
             BG_HIP(hipEventCreateWithFlags(&s.built, hipEventDisableTiming));
             BG_HIP(hipEventCreateWithFlags(&s.matched, hipEventDisableTiming));
@@ -527,34 +516,33 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
         }
     }
     hipStream_t st_build = B.build_stream;
-    // The join (and the chain preparation behind it) of a sub-batch on a stream of its own: the builder's kernels are one
+    // The join (and the chain preparation behind it) of a sub-batch runs off the builder's stream: the builder's kernels are one
     // chain per sub-batch — join, preparation, chaining, raster, row ranges — and under the fill that chain, not the fill,
     // was the cycle (44 ms per 16 384 pairs, 14 of them the join).  With the builder's arrays twice the join of c + 2 runs
-    // next to the chaining of c + 1 (`band_join_serial` = 1: one stream, as before).
+    // next to the chaining of c + 1.
     // (no stream of its own: the process maps its streams onto a handful of hardware queues, and two more of them cost the
     //  full bench — a dozen streams by then — 12 % of this leg where the leg alone gained 3 %; the join shares the stream of
     //  the host-buffer flavour's sequence uploads, which it waits for anyway)
     if (!B.copy_stream && (rc = band_stream_create(&B.copy_stream, -1))) return rc;
-    hipStream_t st_join = ctx->band_join_serial ? st_build : B.copy_stream;
+    hipStream_t st_join = B.copy_stream;
     for (auto& s : B.set) s.built_valid = false;
-    B.chained_valid = false;
     uint64_t waited_join = 0;
     // The preparation of a fill — the pair table's upload, the waits for the band, the cleared aux block and the sequences,
     // and K3v2's phase 1 (the strips before the interior runs) — does not depend on the fill before it, but on the fill
     // stream it queued behind it: 2 ms between two long kernels, every cycle.  On a stream of its own it runs under the
-    // previous fill's tail (`band_pre_serial` = 1: on the fill stream as before; event timing keeps one stream).
+    // previous fill's tail (event timing keeps one stream).
     // (it shares the stream that clears the aux block: the clear is one of the things it waits for)
     if (!B.aux_stream && (rc = band_stream_create(&B.aux_stream, 1))) return rc;
     for (auto& s : B.set)
         if (!s.pre_done) BG_HIP(hipEventCreateWithFlags(&s.pre_done, hipEventDisableTiming));
-    const bool use_pre = dev_kw != nullptr && !ctx->band_on_host && !ctx->timing && !ctx->band_window && !ctx->band_pre_serial;
+    const bool use_pre = dev_kw != nullptr && !ctx->band_on_host && !ctx->timing;
     uint64_t waited_pre = 0;
     if (!B.d_started) BG_HIP(hipMalloc((void**)&B.d_started, 64));
     BG_HIP(hipMemsetAsync(B.d_started, 0, 8, st));  // [0] blocks started, [1] pairs K3p flagged
     B.started_target = 0;
     BG_HIP(hipEventRecord(B.seq_ready, st));
     BG_HIP(hipStreamWaitEvent(st_build, B.seq_ready, 0));
-    if (st_join != st_build) BG_HIP(hipStreamWaitEvent(st_join, B.seq_ready, 0));
+    BG_HIP(hipStreamWaitEvent(st_join, B.seq_ready, 0));
 
     const bool build_on_device = dev_kw != nullptr && !ctx->band_on_host;
     // First half of the device builder for the sub-batch that starts at p0: the k-mer join (B1) and the event
@@ -568,7 +556,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
     // of resident wavefronts that lasts as long as its slowest pair whatever the sub-batch size, so a short sub-batch at
     // the end costs a full fill with the device idle around it (100 000 pairs = 6 x 16 384 + 1 696: 30 ms of 345); up
     // front it runs under the band construction of the first full sub-batch, which nothing else would overlap.
-    const uint64_t first_want = (n_pairs > chunk_pairs && n_pairs % chunk_pairs && !ctx->band_tail_last) ? n_pairs % chunk_pairs : 0;
+    const uint64_t first_want = (n_pairs > chunk_pairs && n_pairs % chunk_pairs) ? n_pairs % chunk_pairs : 0;
     auto want_at = [&](uint64_t p0) -> uint64_t {
         if (p0 == 0 && first_want) return first_want;
         return std::min<uint64_t>(chunk_pairs, n_pairs - p0);
@@ -581,13 +569,12 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
         const uint64_t want = want_at(p0);
         if ((rc = need_seq(st_join, waited_join, p0 + want))) return rc;
         // this parity's arrays were last read by the raster of two sub-batches ago
-        if (st_join != st_build && n_chunk >= 2 && B.set[n_chunk & 1].built_valid) BG_HIP(hipStreamWaitEvent(st_join, B.set[n_chunk & 1].built, 0));
-        // `band_join_late` = 1 (A/B, round 5): this join starts when the chaining of the sub-batch before it has left the
-        // device.  Under a running fill the registers two fill wavefronts per SIMD leave hold EITHER that chaining OR this
-        // join plus a part of it, and whichever is dispatched first keeps the other one in rounds.  Measured: ordering them
-        // costs more than the race (279 against 265 ms per 100 000 pairs: the join then starves behind the raster and K4
-        // instead, and the next chaining starts late) — the default leaves the dispatch order to the hardware.
-        if (st_join != st_build && B.chained_valid && ctx->band_join_late) BG_HIP(hipStreamWaitEvent(st_join, B.chained, 0));
+        if (n_chunk >= 2 && B.set[n_chunk & 1].built_valid) BG_HIP(hipStreamWaitEvent(st_join, B.set[n_chunk & 1].built, 0));
+        // This join does not wait for the chaining of the sub-batch before it.  Under a running fill the registers two fill
+        // wavefronts per SIMD leave hold EITHER that chaining OR this join plus a part of it, and whichever is dispatched
+        // first keeps the other one in rounds.  Measured in round 5: ordering them costs more than the race (279 against
+        // 265 ms per 100 000 pairs: the join then starves behind the raster and K4 instead, and the next chaining starts
+        // late), so the dispatch order is left to the hardware.
         void** db = B.db[n_chunk & 1];
         size_t* db_cap = B.db_cap[n_chunk & 1];
         uint32_t max_m = 0, max_n = 0;
@@ -689,7 +676,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             const size_t need_rc = std::max<size_t>(row0[want] * sizeof(int2), 64), need_ro = std::max<size_t>(row0[want] * 4, 64);
             const bool grows = S.hc_rowc < need_rc || S.hc_roff < need_ro || S.hc_pairs < want * sizeof(BandPair) || S.dc_rowc < need_rc ||
                                S.dc_roff < need_ro || B.h_state_cap < want * sizeof(BandDevPair);
-            if (grows || !build_on_device || ctx->band_host_sync)
+            if (grows || !build_on_device)
                 if ((rc = set_idle())) return rc;
         }
         if ((rc = pinned_reserve(&S.h_rowc, &S.hc_rowc, std::max<size_t>(row0[want] * sizeof(int2), 64)))) return rc;
@@ -709,7 +696,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             d.rowc = (int2*)S.d_rowc;
             d.row_off = (uint32_t*)S.d_roff;
             if ((rc = pinned_reserve(&B.h_state, &B.h_state_cap, want * sizeof(BandDevPair)))) return rc;
-            if (st_join != st_build) BG_HIP(hipStreamWaitEvent(st_build, S.matched, 0));
+            BG_HIP(hipStreamWaitEvent(st_build, S.matched, 0));
             BG_HIP(hipMemcpyAsync((void*)d.row0, row0.data(), (want + 1) * 8, hipMemcpyHostToDevice, st_build));
             // The chaining of sub-batch c + 1 runs UNDER the fill of c: it mostly waits on memory and fits the registers
             // the fill leaves free — provided it starts after every block of the fill is resident
@@ -718,14 +705,6 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             // overlap K4 of sub-batch c.
             if (B.started_target) launch_band_wait_started(B.d_started, B.started_target, st_build);
             if ((rc = launch_band_chain(d, st_build, 2))) return rc;
-            if (B.started_target) {
-                BG_HIP(hipEventRecord(B.chained, st_build));
-                B.chained_valid = true;
-            }
-            if (ctx->band_raster_late && n_chunk >= 1 && B.set[(n_chunk - 1) & 1].busy) {  // (the raster does not have to wait for the fill's epilogue)
-                bg_band_scratch::Set& prev = B.set[(n_chunk - 1) & 1];
-                BG_HIP(hipStreamWaitEvent(st_build, prev.fill_gone_valid ? prev.fill_gone : prev.filled, 0));
-            }
             if (S.busy) BG_HIP(hipStreamWaitEvent(st_build, S.traced, 0));  // the raster writes the set's row ranges: K4 of c - 2 has read them
             if ((rc = launch_band_raster(d, st_build))) return rc;
             BG_HIP(hipMemcpyAsync(B.h_state, d.state, want * sizeof(BandDevPair), hipMemcpyDeviceToHost, st_build));
@@ -735,7 +714,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             // behind, without waiting for the host to learn this one's sizes (finish() used to issue them: 2 ms of round trip
             // on the builder's path, and they landed in the gap between two fills).  Speculative in one respect: the next
             // sub-batch starts at p0 + want only if the scratch budget takes all of this one — otherwise finish() re-issues.
-            if (p0 + want < n_pairs && !ctx->band_window)
+            if (p0 + want < n_pairs)
                 if ((rc = issue_match(p0 + want, n_chunk + 1))) return rc;
         } else {
         std::atomic<bool> bad_input{false};
@@ -863,10 +842,9 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             const Plan& N = plan[(n_chunk + 1) & 1];
             if (!(N.matched && N.p0 == p0 + take))
                 if ((rc = issue_match(p0 + take, n_chunk + 1))) return rc;
-            // Round 3: the fill waited for the join (124 KB of LDS per block: it could only run in a window between two
-            // fills).  With K3i / K3p on 32-byte rings (two blocks = 66 KB per CU) the join (91 KB) and the chaining's
-            // preparation (16 KB per wavefront) fit NEXT to a fill: no window, fills back to back.
-            if (ctx->band_window) BG_HIP(hipStreamWaitEvent(st, B.set[(n_chunk + 1) & 1].matched, 0));
+            // The fill does not wait for that join: with K3i / K3p on 32-byte rings (two blocks = 66 KB per CU) the join
+            // (91 KB) and the chaining's preparation (16 KB per wavefront) fit NEXT to a fill, so fills run back to back
+            // (round 3's 64-byte rings, 124 KB of LDS per block, left the join only a window between two fills).
         }
         if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
         // Geometry by sub-batch size: K3v2 binds a pair to 8 lanes for ~30 ms whatever the batch (throughput comes from the
@@ -879,7 +857,6 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             a.started = on_device ? B.d_started : nullptr;
             a.tb_flip = kTbFlip;
             // interior runs (band_split): scaled keys, x kept whole, a real y-prefix clip — semiglobal-like scorings
-            a.ring32 = ctx->band_window ? 0 : 1;
             a.split = (narrow && !ctx->band_interior_off && cs.xclip_prefix <= kNarrowNegClip && cs.xclip_suffix <= kNarrowNegClip &&
                        cs.yclip_prefix > kNarrowNegClip) ? 1 : 0;
             // ... and, where the scoring and the lengths fit its 16-bit strip-relative keys, K3p takes the runs first
@@ -893,13 +870,11 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
                             max_y < 65536 && target - thresh >= (1 << 14)) ? 1 : 0;
                 a.pk_thresh = (int32_t)ctx->band_packed_thresh;
                 a.redo_count = B.d_started + 1;
-                a.p_block512 = ctx->band_p_block512 ? 1 : 0;
             }
             if (on_device) B.started_target += band_fill2_blocks(a.n_pairs);
             // K3v2 / K3p (K3i): eight pairs per wavefront; the epilogue goes to the traceback stream, ahead of K4 — the fill
             // stream goes straight on with the next sub-batch (event timing keeps everything on one stream)
-            ctx->fill_mask |= launch_band_fill2(a, narrow, st, S.fill_gone, ctx->timing || ctx->band_window ? nullptr : st_tb, sp != st ? sp : nullptr, S.pre_done);
-            S.fill_gone_valid = true;
+            ctx->fill_mask |= launch_band_fill2(a, narrow, st, S.fill_gone, ctx->timing ? nullptr : st_tb, sp != st ? sp : nullptr, S.pre_done);
         }
         else {
             a.tb_flip = 0;
@@ -910,7 +885,6 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
             }
             fill<<<dim3((unsigned)((take + 3) / 4)), dim3(256), 0, st>>>(a);
             ctx->fill_mask |= BG_FILL_K3;
-            S.fill_gone_valid = false;
         }
         BG_HIP(hipGetLastError());
         if (ctx->timing) {

@@ -63,16 +63,12 @@ __device__ __forceinline__ pk row_shr1_first(pk first, pk v) {
 // 0xffff in every half that is non-zero
 __device__ __forceinline__ pk nz_mask(pk v, pk one) { return pk_sub(pk_subs(one, v), one); }
 
-// WB: wavefronts per block.  4: round 4's launch (187 VGPRs, two blocks per CU) — the default.  8 (`band_p_block512`): ONE
-// block per CU compiled for 168 VGPRs (the compiler parks 14 values of the strip prologue in scratch; the step loops are
-// the same instructions), so that two fill wavefronts per SIMD leave 176 VGPRs and the chaining of the next sub-batch
-// (chain_rows_kernel: 40 VGPRs, four wavefronts per SIMD for 16 384 pairs) is resident as a whole next to the fill instead
-// of three wavefronts in four.  Measured in round 5 (profiles/r05_banded_pipeline_experiments.txt): the chaining does
-// drop from 22 to 16 ms under the fill, the fill itself runs 3 % longer, and the call does not gain — what runs next to a
-// fill (chaining, raster, join, K4: ~7 900 VGPR-ms per SIMD and sub-batch) does not fit the registers a fill leaves
-// (176 x 30 ms) whatever the order; the rest runs in the gap between two fills, which is what the cycle already does.
-template <int R, int LP, int WB>
-__global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(WB == 8 ? 3 : 2, WB == 8 ? 3 : 2))) void banded_fill2p_kernel(const BandArgs a) {
+// Four wavefronts per block at 187 VGPRs, two blocks per CU: eight wavefronts per block compiled for 168 VGPRs made the
+// chaining next to the fill faster but the fill itself 3 % slower, and the call gained nothing (round 5,
+// profiles/r05_banded_pipeline_experiments.txt).
+constexpr int WB = 4;
+template <int R, int LP>
+__global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(2, 2))) void banded_fill2p_kernel(const BandArgs a) {
     constexpr int RING = 32;   // bytes of LDS per row and pair, indexed by step (banded_fill2i.hip)
     constexpr int FLUSH = 16;  // steps between two hand-overs of complete 16-byte groups == the blocks of the Sn / Ly merge
     static_assert(LP == 16, "a block of 16 steps is one chunk: lane ll prepares / hands over step t0 + ll");
@@ -508,13 +504,8 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(WB == 8
 
 void launch_fill2p(const BandArgs& a, hipStream_t st) {
     // 16 lanes x 2 rows per pair couple: 8 pairs per wavefront, K3i's grid (two wavefronts per SIMD at 16 384 pairs)
-    if (a.p_block512) {
-        constexpr uint32_t per_block = 8 * 2 * (64 / 16);
-        banded_fill2p_kernel<2, 16, 8><<<dim3((a.n_pairs + per_block - 1) / per_block), dim3(512), 0, st>>>(a);
-    } else {
-        constexpr uint32_t per_block = 4 * 2 * (64 / 16);
-        banded_fill2p_kernel<2, 16, 4><<<dim3((a.n_pairs + per_block - 1) / per_block), dim3(256), 0, st>>>(a);
-    }
+    constexpr uint32_t per_block = WB * 2 * (64 / 16);
+    banded_fill2p_kernel<2, 16><<<dim3((a.n_pairs + per_block - 1) / per_block), dim3(64 * WB), 0, st>>>(a);
 }
 
 }  // namespace bgband_dev

@@ -97,13 +97,11 @@ struct BandArgs {
     uint32_t tb_flip;   // XORed onto every traceback byte K4 reads (kTbFlip after K3v2, 0 after K3)
     uint32_t* started;  // K3v2: every block counts itself in when it starts (nullptr: nobody is waiting for that)
     int32_t phase;  // K3v2: 0 all strips of every pair; 1 / 2: the strips before / behind the interior run (band_split)
-    int32_t ring32; // K3i with 32-byte rings (33 KB of LDS per block instead of 65)
     int32_t split;  // the scoring admits interior runs (host decision, banded_api.hip): band_split may say yes
     int32_t packed;     // the interior runs go to K3p (banded_fill2p.hip) first; K3i redoes what it flags
     int32_t redo;       // K3v2 phase 1 / K3i: only the pairs K3p flagged (aux[5] != 0)
     int32_t pk_thresh;  // K3p: the threshold a band cell's key has to exceed (0: derived from the scoring; tests raise it)
     uint32_t* redo_count;  // K3p counts the pairs it flags here (nullptr: nobody asks)
-    int32_t p_block512;    // K3p in blocks of eight wavefronts at 168 VGPRs (banded_fill2p.hip) instead of four at 187
 };
 
 // Interior run of a pair: the strips [s_a, s_b) of RS rows each that banded_fill2i_kernel takes with its reduced cell.

@@ -73,7 +73,6 @@ struct bg_ctx {
     bool no_local_fast = false;  // tests: Aligner::local on the general K1p (no LF flavour)
     bool no_couples = false;  // tests: K1p without the (m, n) slot order on ragged batches
     int band_chain_global = -1;  // chain_kernel tree placement: -1 by batch size, 0 LDS, 1 global scratch
-    bool band_host_sync = false;  // A/B: issue() waits on the host for K4 of two sub-batches ago before launching the chaining (rounds 2-4)
     bool fq_no_fused = false;  // tests, A/B: bg_fastq_parse_dev through F1 .. F6 only (no one-pass kernel in front)
     int64_t sa_chunk_symbols = 0;  // tests: suffixes per pass of round 0 of the device suffix-array builder (0: by free memory)
     bool band_chain_rows = true;  // global-tree chaining: four pairs per wavefront (chain_rows_kernel); false: one (A/B, tests)
@@ -82,13 +81,6 @@ struct bg_ctx {
     bool band_interior_off = false;  // tests: K3v2 takes its general step in every strip (no reduced step in interior strips)
     bool band_packed_off = false;    // tests, A/B: interior runs on K3i (int32) only, no packed-int16 K3p in front of it
     int64_t band_packed_thresh = 0;  // tests: K3p's redo threshold in key units (0: derived from the scoring; 0xffff: every pair is redone)
-    bool band_pre_serial = false;    // A/B: a fill's preparation (pair table, waits, K3v2 phase 1) on the fill stream, behind the previous fill
-    bool band_join_serial = false;   // A/B: the k-mer join of a sub-batch on the builder's stream, behind the previous sub-batch's row ranges (one chain)
-    bool band_tail_last = false;   // A/B: the remainder sub-batch of a large banded call runs last (round 3) instead of first
-    bool band_window = false;      // A/B: K3i on 64-byte rings, and the fill waits for the next sub-batch's join + preparation (round 3's window between two fills)
-    bool band_raster_late = false; // A/B: the raster of sub-batch c + 1 waits for fill c to leave the device (round 3)
-    bool band_join_late = false;  // A/B: the k-mer join of sub-batch c + 2 waits for the chaining of c + 1 to leave the device (round 5: measured slower)
-    bool band_p_block512 = false;  // A/B: K3p in blocks of eight wavefronts compiled for 168 VGPRs instead of four at 187 (round 5: measured 3 % slower)
     int64_t band_budget_gb = 0;  // traceback + aux bytes per scratch set of the banded pipeline, in GB (0: 40)
     bool band_on_host = false;  // build bands with the host builder (band_host.cpp) instead of band_device.hip
     // the scratch above is one set per ctx: a *_dev call arriving on another stream than the previous one first

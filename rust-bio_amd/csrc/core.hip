@@ -218,10 +218,6 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
         ctx->sa_chunk_symbols = value;
         return BG_OK;
     }
-    if (!strcmp(key, "band_host_sync")) {
-        ctx->band_host_sync = value != 0;
-        return BG_OK;
-    }
     if (!strcmp(key, "band_chain_rows")) {
         ctx->band_chain_rows = value != 0;
         return BG_OK;
@@ -245,34 +241,6 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "band_packed_thresh")) {
         if (value < 0 || value > 0xffff) return BG_ERR_INVALID_ARG;
         ctx->band_packed_thresh = value;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_pre_serial")) {
-        ctx->band_pre_serial = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_join_serial")) {
-        ctx->band_join_serial = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_tail_last")) {
-        ctx->band_tail_last = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_window")) {
-        ctx->band_window = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_raster_late")) {
-        ctx->band_raster_late = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_join_late")) {
-        ctx->band_join_late = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "band_p_block512")) {
-        ctx->band_p_block512 = value != 0;
         return BG_OK;
     }
     if (!strcmp(key, "band_budget_gb")) {
