@@ -85,7 +85,8 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
 /* Tunables (0 keeps the default) and the switches the tests use to reach every kernel variant:
  *   chunk_pairs        pairs per sub-batch of bg_align_batch_dev (default 2^20) and of the banded pipeline (16384)
  *   host_chunk_pairs   pairs per stage of bg_align_batch's pipelined host path (122880)
- *   seed_chunk_reads   reads per pass of bg_seed_extend_batch[_dev] (0: equal passes of at most 2^21 reads)
+ *   seed_chunk_reads   reads per pass of bg_seed_extend[_strands]_batch[_dev] (0: equal passes of at most 2^21 reads,
+ *                      2^20 with both strands)
  *   force_wide = 1     scores kept as plain int32 even where they fit the 24-bit keys of the fast kernels
  *   no_pk16 = 1        no packed-int16 fill (K1p): the int32 kernel K1 runs for every batch
  *   no_couples = 1     K1p without the (m, n) slot order on ragged batches
@@ -512,6 +513,34 @@ int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_pa
                              const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                              bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals,
                              void* stream);
+/* Both strands.  Sequencers read both strands of the DNA: against an index of the forward text, a read from the other
+ * strand maps as its reverse complement.  revcomp(read) is rust-bio's dna::revcomp (alphabets/dna.rs): the bytes
+ * reversed, AGCTYRWSKMDVHBN -> TCGARYWSMKHBDVN and the same in lower case, every other byte (N, $, ...) itself.
+ *   forward strand   the composition above on `read`;
+ *   reverse strand   the composition above on revcomp(read) — seeds, votes, proposals, merge, windows and extension apply
+ *                    to each strand on its own;
+ *   best hit         with both strands the highest score wins, the forward strand on an equal score, the smallest s
+ *                    within one strand.
+ * A reverse-strand winner's aln (x coordinates, xlen, operations) refers to revcomp(read) against the forward text (the
+ * SAM convention: bg_cigar_batch gives the SAM CIGAR directly); window_start / ref_start / ref_end are forward-text
+ * coordinates.  n_candidates, n_seed_hits and totals are sums over the strands that ran.  strand[r] (optional): BG_HIT_*
+ * of read r's winner.  `strands` outside BG_STRAND_FORWARD ..= BG_STRAND_BOTH: BG_ERR_INVALID_ARG; every other limit,
+ * argument check and the out-of-alphabet rule are those of bg_seed_extend_batch[_dev], per strand.  strands =
+ * BG_STRAND_FORWARD computes exactly what bg_seed_extend_batch[_dev] computes. */
+enum { BG_STRAND_FORWARD = 1, BG_STRAND_REVERSE = 2, BG_STRAND_BOTH = 3 };   /* which strands to map */
+enum { BG_HIT_FORWARD = 0, BG_HIT_REVERSE = 1, BG_HIT_NONE = 255 };          /* strand[r] of the winner */
+int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
+                                 uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                 uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour (operation slots, totals and passes as bg_seed_extend_batch_dev; seed_chunk_reads counts the caller's
+ * reads, and with both strands a pass takes at most 2^20 of them). */
+int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
+                                     uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
+                                     uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
+                                     uint64_t ops_stride, uint64_t* totals, void* stream);
+/* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
+ * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
+int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);
 
 /* ---- FASTQ ingest and CIGAR emission --------------------------------------
  * bio::io::fastq::Reader::read / Records on a text that is in memory (io/fastq.rs:266-303, 508-527: header

@@ -650,6 +650,41 @@ public:
         }
         return res;
     }
+    // The same on both strands (bg_seed_extend_strands_batch): each read and its dna::revcomp, the better one wins (the forward
+    // strand on an equal score).  A reverse hit's alignment is of revcomp(read) against the forward text (the SAM convention).
+    struct StrandedSeedHit : SeedHit {
+        bool reverse = false;  // the winner is on the reverse strand
+    };
+    std::vector<StrandedSeedHit> seed_extend_batch_strands(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                           uint32_t strands = BG_STRAND_BOTH, uint32_t seed_len = 20, uint32_t stride = 10,
+                                                           uint32_t max_occ = 16, uint32_t pad = 25) const {
+        std::vector<int32_t> table;
+        const bg_scoring_t sc = scoring.to_c(table);
+        const bg_seed_params_t prm = {seed_len, stride, max_occ, pad};
+        Text buf;
+        std::vector<uint64_t> off{0};
+        for (auto& r : reads) {
+            buf.insert(buf.end(), r.begin(), r.end());
+            off.push_back(buf.size());
+        }
+        std::vector<bg_seed_hit_t> hits(reads.size());
+        std::vector<uint8_t> strand(reads.size());
+        std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4) * reads.size() + 8);
+        uint64_t used = 0;
+        const int rc = bg_seed_extend_strands_batch(h_, &sc, &prm, strands, reads.size(), buf.data(), off.data(), hits.data(),
+                                                    strand.data(), ops.data(), ops.size(), &used);
+        if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
+        check(rc, "bg_seed_extend_strands_batch");
+        std::vector<StrandedSeedHit> res(reads.size());
+        for (size_t r = 0; r < reads.size(); r++) {
+            if (hits[r].aln.score != BG_MIN_SCORE) res[r].alignment = alignment::pairwise::detail::to_alignment(hits[r].aln, ops.data());
+            res[r].ref_start = (size_t)hits[r].ref_start;
+            res[r].ref_end = (size_t)hits[r].ref_end;
+            res[r].n_candidates = hits[r].n_candidates;
+            res[r].reverse = strand[r] == BG_HIT_REVERSE;
+        }
+        return res;
+    }
     bg_fm* raw() const { return h_; }
     size_t len() const { return n_; }
 

@@ -15,6 +15,9 @@ ERRORS = {-1: "INVALID_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -5: "SENTINE
           -6: "POSITIVE_PENALTY", -7: "OUT_OF_ALPHABET", -8: "TOO_LARGE", -9: "OPS_CAP",
           -10: "TRACEBACK", -11: "UNSUPPORTED", -12: "IO"}
 MIN_SCORE = -858993459
+# BG_STRAND_* (which strands bg_seed_extend_strands_batch[_dev] maps) and BG_HIT_* (the strand of a read's winner)
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 1, 2, 3
+HIT_FORWARD, HIT_REVERSE, HIT_NONE = 0, 1, 255
 # BG_FILL_* (include/biogpu.h): fill kernel families, as Context.last_fill_kernels() reports them
 FILL = {"K1_WIDE": 0x1, "K1_NARROW": 0x2, "K1_LF": 0x4, "K1P": 0x8, "K1P_LF": 0x10, "K3": 0x20, "K3V2_WIDE": 0x40,
         "K3V2_NARROW": 0x80, "K3I": 0x100, "K3P": 0x200}
@@ -95,6 +98,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_sparse_lcskpp", "bg_sparse_sdpkpp_union_lcskpp_path", "bg_sparse_expand_kmer_matches", "bg_fastq_parse",
            "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_pack2_host",
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
+           "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
@@ -205,6 +209,11 @@ def lib():
         L.bg_fm_set_text_dev.argtypes = [vp, vp, u64]
         L.bg_seed_extend_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u64, vp, vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u64, vp, vp, u32, vp, vp, u64, vp, vp]
+        L.bg_seed_extend_strands_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u32, u64, vp, vp, vp, vp, vp, u64,
+                                                   C.POINTER(u64)]
+        L.bg_seed_extend_strands_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u32, u64, vp, vp, u32, vp, vp,
+                                                       vp, u64, vp, vp]
+        L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

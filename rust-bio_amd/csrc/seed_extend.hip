@@ -10,7 +10,9 @@
 // best-hit reduction that hands back one alignment (with its operations) per read.  Definition of the
 // composition: include/biogpu.h (the tests hold a CPU statement of the same thing).
 //
-// Per batch of reads (S = seed slots per read):
+// Per batch of reads (S = seed slots per read; with both strands (bg_seed_extend_strands_batch[_dev]) the stages run on
+// "virtual reads", each read followed by its revcomp, and S7 picks the better strand of each read):
+//   S0 strands          one wavefront per read: read + revcomp -> scratch (stranded call only)
 //   S1 K5<SEEDS>        n_reads * S backward searches                                  -> tag, lower, upper
 //   S2 votes            cnt[q] = interval size if Complete and 1 <= size <= max_occ     -> scan -> hit offsets
 //   S3 K6               Interval::occ of every voting interval                          -> text positions
@@ -219,19 +221,94 @@ __global__ __launch_bounds__(64) void se_gather_kernel(SeedPrm prm, uint64_t n_r
     }
 }
 
+// dna::complement (rust-bio alphabets/dna.rs): AGCTYRWSKMDVHBN -> TCGARYWSMKHBDVN, the same in lower case, every other
+// byte (N, $, ...) itself
+struct alignas(16) ComplementTable {
+    uint8_t v[256];
+};
+constexpr ComplementTable make_complement() {
+    ComplementTable t{};
+    for (int i = 0; i < 256; i++) t.v[i] = (uint8_t)i;
+    const char* a = "AGCTYRWSKMDVHBN";
+    const char* b = "TCGARYWSMKHBDVN";
+    for (int i = 0; a[i]; i++) {
+        t.v[(uint8_t)a[i]] = (uint8_t)b[i];
+        t.v[(uint8_t)a[i] + 32] = (uint8_t)(b[i] + 32);
+    }
+    return t;
+}
+__constant__ ComplementTable kComplement = make_complement();
+
+// the block's copy of the table: 64 dwords, one per lane of the first wavefront
+__device__ __forceinline__ void load_complement(uint8_t* s_comp) {
+    if (threadIdx.x < 64) ((uint32_t*)s_comp)[threadIdx.x] = ((const uint32_t*)kComplement.v)[threadIdx.x];
+    __syncthreads();
+}
+
+// dst[0 .. L) = revcomp(src[0 .. L)) by the 64 lanes of one wavefront
+__device__ __forceinline__ void revcomp_wave(const uint8_t* s_comp, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                             uint64_t L, uint32_t lane) {
+    for (uint64_t i = lane; i < L; i += 64) dst[i] = s_comp[src[L - 1 - i]];
+}
+
+// bg_revcomp_batch_dev: one wavefront per sequence, four per block
+__global__ __launch_bounds__(256) void se_revcomp_kernel(uint64_t n, const uint8_t* __restrict__ in, const uint64_t* __restrict__ off,
+                                                         uint8_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(4))) uint8_t s_comp[256];
+    load_complement(s_comp);
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const uint64_t o = off[r];
+    revcomp_wave(s_comp, in + o, out + o, off[r + 1] - o, threadIdx.x & 63);
+}
+
+// S0 of the stranded call: the pass's virtual reads, one wavefront per read of the caller, four per block.  G = 2: virtual
+// read 2r is read r, 2r + 1 its revcomp, back to back at 2 (off[r] - off[0]); G = 1: the revcomp alone at off[r] - off[0].
+// Offsets relative to the pass's first read, G * nr + 1 of them.  `cap` = G * nr * max_read_len bytes of scratch: a read
+// longer than max_read_len (the caller's error) sets bit 1 of *flags, and offsets and bytes stay inside the scratch.
+template <int G>
+__global__ __launch_bounds__(256) void se_strands_kernel(uint64_t nr, const uint8_t* __restrict__ reads, const uint64_t* __restrict__ read_off,
+                                                         uint64_t cap, uint8_t* __restrict__ vreads, uint64_t* __restrict__ voff,
+                                                         uint32_t* __restrict__ flags) {
+    __shared__ __attribute__((aligned(4))) uint8_t s_comp[256];
+    load_complement(s_comp);
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= nr) return;
+    const uint64_t base = read_off[0], ro = read_off[r], L = read_off[r + 1] - ro;
+    const uint64_t vo = G * (ro - base);
+    if (lane == 0) {
+        voff[G * r] = min(vo, cap);
+        if (G == 2) voff[2 * r + 1] = min(vo + L, cap);
+        if (r + 1 == nr) voff[G * nr] = min(G * (read_off[nr] - base), cap);
+    }
+    if (vo + G * L > cap) {
+        if (lane == 0) atomicOr(flags, 2u);
+        return;
+    }
+    if (G == 2)
+        for (uint64_t i = lane; i < L; i += 64) vreads[vo + i] = reads[ro + i];
+    revcomp_wave(s_comp, reads + ro, vreads + vo + (G - 1) * L, L, lane);
+}
+
 // S7: 16 lanes per read: best candidate (highest score, first = smallest start among equals), record + operations
 // `hits` / `ops` are the caller's whole arrays, `r0` the first read of this pass: read r0 + r of the call owns
-// ops[(r0 + r) * ops_stride, (r0 + r + 1) * ops_stride) and its ops_off is relative to the caller's `ops`
+// ops[(r0 + r) * ops_stride, (r0 + r + 1) * ops_stride) and its ops_off is relative to the caller's `ops`.
+// Read r's candidates are those of its G virtual reads, coff[G r] .. coff[G r + G): with G = 2 the forward strand's come
+// first, so the same key makes it win a tie.  `strand` (optional): BG_HIT_* of the winner; with G = 1 every winner is on
+// strand `strand1`.
+template <int G>
 __global__ __launch_bounds__(256) void se_best_kernel(uint64_t n_reads, uint64_t r0, const uint64_t* __restrict__ coff,
                                                       const uint32_t* __restrict__ n_hits,
                                                       const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ c_ops,
                                                       const uint64_t* __restrict__ w_lo, bg_seed_hit_t* __restrict__ hits,
-                                                      uint8_t* __restrict__ ops, uint64_t ops_stride) {
+                                                      uint8_t* __restrict__ ops, uint64_t ops_stride, uint8_t* __restrict__ strand,
+                                                      uint8_t strand1) {
     const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t l16 = threadIdx.x & 15;
     if (r >= n_reads) return;  // uniform per group of 16
-    const uint64_t c0 = coff[r];
-    const uint32_t nc = (uint32_t)(coff[r + 1] - c0);
+    const uint64_t c0 = coff[G * r];
+    const uint32_t nc = (uint32_t)(coff[G * r + G] - c0);
     // key: score (biased to unsigned) in the high word, ~candidate index in the low one: max = best score, first wins
     uint64_t best = 0;
     for (uint32_t c = l16; c < nc; c += 16) {
@@ -249,10 +326,12 @@ __global__ __launch_bounds__(256) void se_best_kernel(uint64_t n_reads, uint64_t
     h.aln.score = BG_MIN_SCORE;
     h.window_start = h.ref_start = h.ref_end = ~0ull;
     h.n_candidates = nc;
-    h.n_seed_hits = n_hits[r];
+    h.n_seed_hits = G == 2 ? n_hits[2 * r] + n_hits[2 * r + 1] : n_hits[r];
     h.aln.ops_off = (r0 + r + 1) * ops_stride;
+    uint8_t won = BG_HIT_NONE;
     if (nc) {
         const uint32_t c = ~(uint32_t)best;
+        won = G == 2 ? (c >= coff[2 * r + 1] - c0 ? BG_HIT_REVERSE : BG_HIT_FORWARD) : strand1;
         const bg_alignment_t a = aln[c0 + c];
         h.aln = a;
         h.aln.ops_off = (r0 + r + 1) * ops_stride - a.n_ops;
@@ -262,7 +341,10 @@ __global__ __launch_bounds__(256) void se_best_kernel(uint64_t n_reads, uint64_t
         if (ops && c_ops)
             for (uint32_t i = l16; i < a.n_ops; i += 16) ops[h.aln.ops_off + i] = c_ops[a.ops_off + i];
     }
-    if (l16 == 0) hits[r0 + r] = h;
+    if (l16 == 0) {
+        hits[r0 + r] = h;
+        if (strand) strand[r0 + r] = won;
+    }
 }
 
 }  // namespace
@@ -291,10 +373,15 @@ extern "C" int bg_fm_set_text_dev(bg_fm* fm, const uint8_t* d_text, uint64_t n) 
     return BG_OK;
 }
 
-extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint64_t n_reads,
-                                        const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
-                                        bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals,
-                                        void* stream) {
+namespace {
+
+// The passes of bg_seed_extend_batch_dev over "virtual reads", G of them per read of the caller.  strands = 0: the caller's
+// reads as they are, G = 1, no strand array (bg_seed_extend_batch_dev).  BG_STRAND_FORWARD: the same, with the strand array.
+// BG_STRAND_REVERSE: G = 1 on the revcomps, BG_STRAND_BOTH: G = 2 on read and revcomp, materialised per pass by
+// se_strands_kernel.  Stages S1-S6 run unchanged on the virtual reads; S7 picks each caller read's best over its G.
+int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
+           const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
+           uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
     if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
     if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
@@ -321,17 +408,22 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
     int rc;
     auto need = [&](int i, size_t bytes) -> int { return bg_reserve(&W.p[i], &W.cap[i], std::max<size_t>(bytes, 64)); };
 
+    const uint32_t G = strands == BG_STRAND_BOTH ? 2 : 1;
+    const bool virt = strands == BG_STRAND_REVERSE || strands == BG_STRAND_BOTH;  // reads to materialise (S0)
     uint64_t done_hits = 0, done_cand = 0;
     bool any_panic = false;
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
-    // (default: up to 2^21 reads per pass, the passes of a call of equal size — 1.25 M reads went as 2^20 + 0.2 M until round 6:
-    //  two host round trips and a set of under-filled launches for a sixth of the reads)
-    const uint64_t chunk_cap = ctx->seed_chunk_reads > 0 ? (uint64_t)ctx->seed_chunk_reads : (1u << 21);
+    // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size — 1.25 M reads went as 2^20 + 0.2 M until
+    //  round 6: two host round trips and a set of under-filled launches for a sixth of the reads).  The option counts the
+    //  caller's reads.
+    const uint64_t chunk_cap = ctx->seed_chunk_reads > 0 ? (uint64_t)ctx->seed_chunk_reads : (1u << 21) / G;
     const uint64_t n_pass = (n_reads + chunk_cap - 1) / chunk_cap;
     const uint64_t chunk = ctx->seed_chunk_reads > 0 ? chunk_cap : (n_reads + n_pass - 1) / n_pass;
     for (uint64_t r0 = 0; r0 < n_reads; r0 += chunk) {
         const uint64_t nr = std::min(chunk, n_reads - r0);
-        const uint64_t nq = nr * std::max<uint32_t>(prm.S, 1);
+        const uint64_t nv = G * nr;  // virtual reads of this pass
+        const uint64_t nq = nv * std::max<uint32_t>(prm.S, 1);
+        const uint8_t* vreads = d_reads;
         const uint64_t* roff = d_read_off + r0;
         // ---- S1/S2: seeds -> votes -> hit offsets
         if ((rc = need(0, nq))) return rc;              // tag
@@ -344,10 +436,26 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
         uint8_t* d_tag = (uint8_t*)W.p[0];
         uint64_t *d_lo = (uint64_t*)W.p[1], *d_hi = (uint64_t*)W.p[2], *d_hoff = (uint64_t*)W.p[4], *d_sums = (uint64_t*)W.p[5];
         uint32_t* d_cnt = (uint32_t*)W.p[3];
+        uint32_t* d_flags = (uint32_t*)(d_sums + 2 * (nq / 2048 + 2));  // bit 0: a seed out of the alphabet, bit 1: a read > max_read_len
+        // ---- S0 (stranded call): the virtual reads and their offsets, relative to the pass's first read
+        if (virt) {
+            const uint64_t voff_bytes = (nv + 1) * 8, cap = nv * (uint64_t)max_read_len;
+            if ((rc = need(15, voff_bytes + cap))) return rc;
+            uint64_t* d_voff = (uint64_t*)W.p[15];
+            uint8_t* d_vreads = (uint8_t*)W.p[15] + voff_bytes;
+            const dim3 grid((unsigned)((nr + 3) / 4)), block(256);
+            if (G == 2)
+                se_strands_kernel<2><<<grid, block, 0, st>>>(nr, d_reads, roff, cap, d_vreads, d_voff, d_flags);
+            else
+                se_strands_kernel<1><<<grid, block, 0, st>>>(nr, d_reads, roff, cap, d_vreads, d_voff, d_flags);
+            BG_HIP(hipGetLastError());
+            vreads = d_vreads;
+            roff = d_voff;
+        }
         if (prm.S) {
-            if ((rc = bg_fm_search_seeds_dev(fm, nr, d_reads, roff, prm.S, prm.stride, prm.seed_len, d_tag, d_lo, d_hi, d_cnt, st))) return rc;
+            if ((rc = bg_fm_search_seeds_dev(fm, nv, vreads, roff, prm.S, prm.stride, prm.seed_len, d_tag, d_lo, d_hi, d_cnt, st))) return rc;
             se_votes_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(nq, d_tag, d_lo, d_hi, prm.max_occ, d_cnt,
-                                                                                      (uint32_t*)(d_sums + 2 * (nq / 2048 + 2)));
+                                                                                      d_flags);
         } else {
             BG_HIP(hipMemsetAsync(d_cnt, 0, nq * 4, st));
         }
@@ -357,28 +465,29 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
         BG_HIP(hipStreamSynchronize(st));  // sizes the position array
         const uint64_t n_hits = W.h_tot[0];
         if (W.h_tot[4] & 1) any_panic = true;
+        if (W.h_tot[4] & 2) return BG_ERR_INVALID_ARG;  // a read longer than max_read_len (S0 kept within its scratch)
         // ---- S3: Interval::occ of the voting intervals
         if ((rc = need(6, n_hits * 8))) return rc;
         uint64_t* d_pos = (uint64_t*)W.p[6];
         if (n_hits && (rc = bg_interval_occ_batch_dev(fm, nq, d_lo, d_hoff, n_hits, d_pos, st))) return rc;
         // ---- S4: proposals -> sorted unique candidates per read, scans of the per-read counts
-        if ((rc = need(7, 4 * nr * 4))) return rc;           // n_cand | n_hits | x_bytes | y_bytes
-        if ((rc = need(8, 3 * (nr + 1) * 8))) return rc;      // coff | xoff | yoff
+        if ((rc = need(7, 4 * nv * 4))) return rc;           // n_cand | n_hits | x_bytes | y_bytes
+        if ((rc = need(8, 3 * (nv + 1) * 8))) return rc;      // coff | xoff | yoff
         uint32_t* d_nc = (uint32_t*)W.p[7];
-        uint32_t *d_nh = d_nc + nr, *d_xb = d_nh + nr, *d_yb = d_xb + nr;
+        uint32_t *d_nh = d_nc + nv, *d_xb = d_nh + nv, *d_yb = d_xb + nv;
         uint64_t* d_coff = (uint64_t*)W.p[8];
-        uint64_t *d_xoff = d_coff + (nr + 1), *d_yoff = d_xoff + (nr + 1);
+        uint64_t *d_xoff = d_coff + (nv + 1), *d_yoff = d_xoff + (nv + 1);
         if (fm->wide)
-            se_propose_kernel<uint64_t><<<dim3((unsigned)nr), dim3(64), 0, st>>>(prm, nr, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
+            se_propose_kernel<uint64_t><<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
         else
-            se_propose_kernel<uint32_t><<<dim3((unsigned)nr), dim3(64), 0, st>>>(prm, nr, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
+            se_propose_kernel<uint32_t><<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
         BG_HIP(hipGetLastError());
-        if ((rc = bg_scan_u32(d_nc, nr, d_coff, d_sums, st))) return rc;
-        if ((rc = bg_scan_u32(d_xb, nr, d_xoff, d_sums, st))) return rc;
-        if ((rc = bg_scan_u32(d_yb, nr, d_yoff, d_sums, st))) return rc;
-        BG_HIP(hipMemcpyAsync(&W.h_tot[1], d_coff + nr, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(&W.h_tot[2], d_xoff + nr, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(&W.h_tot[3], d_yoff + nr, 8, hipMemcpyDeviceToHost, st));
+        if ((rc = bg_scan_u32(d_nc, nv, d_coff, d_sums, st))) return rc;
+        if ((rc = bg_scan_u32(d_xb, nv, d_xoff, d_sums, st))) return rc;
+        if ((rc = bg_scan_u32(d_yb, nv, d_yoff, d_sums, st))) return rc;
+        BG_HIP(hipMemcpyAsync(&W.h_tot[1], d_coff + nv, 8, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipMemcpyAsync(&W.h_tot[2], d_xoff + nv, 8, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipMemcpyAsync(&W.h_tot[3], d_yoff + nv, 8, hipMemcpyDeviceToHost, st));
         BG_HIP(hipStreamSynchronize(st));  // sizes the candidate pairs
         const uint64_t C = W.h_tot[1], X = W.h_tot[2], Y = W.h_tot[3];
         // ---- S5: the pairs
@@ -394,7 +503,7 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
         uint64_t* d_cyoff = d_cxoff + (C + 1);
         uint64_t* d_wlo = (uint64_t*)W.p[12];
         bg_alignment_t* d_aln = (bg_alignment_t*)W.p[13];
-        se_gather_kernel<<<dim3((unsigned)nr), dim3(64), 0, st>>>(prm, nr, d_reads, roff, (const uint8_t*)fm->d_text, d_hoff, d_pos, d_coff,
+        se_gather_kernel<<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, vreads, roff, (const uint8_t*)fm->d_text, d_hoff, d_pos, d_coff,
                                                                   d_xoff, d_yoff, d_x, d_cxoff, d_y, d_cyoff, d_wlo);
         BG_HIP(hipGetLastError());
         // ---- S6: Aligner::semiglobal on every candidate
@@ -402,8 +511,13 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
                                                d_cops, cstride, st, -1)))
             return rc;
         // ---- S7: best hit per read
-        se_best_kernel<<<dim3((unsigned)((nr * 16 + 255) / 256)), dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits,
-                                                                                      d_ops, ops_stride);
+        const dim3 best_grid((unsigned)((nr * 16 + 255) / 256));
+        if (G == 2)
+            se_best_kernel<2><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
+                                                               d_strand, 0);
+        else
+            se_best_kernel<1><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
+                                                               d_strand, strands == BG_STRAND_REVERSE ? BG_HIT_REVERSE : BG_HIT_FORWARD);
         BG_HIP(hipGetLastError());
         done_hits += n_hits;
         done_cand += C;
@@ -417,9 +531,38 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
     return any_panic ? BG_ERR_OUT_OF_ALPHABET : BG_OK;
 }
 
-extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint64_t n_reads,
-                                    const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* ops_buf,
-                                    uint64_t ops_cap, uint64_t* ops_used) {
+}  // namespace
+
+extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint64_t n_reads,
+                                        const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                        bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals,
+                                        void* stream) {
+    return se_run(fm, sc, prm, 0, n_reads, d_reads, d_read_off, max_read_len, d_hits, nullptr, d_ops, ops_stride, totals, stream);
+}
+
+extern "C" int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
+                                                uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
+                                                uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
+                                                uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    return se_run(fm, sc, prm, strands, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals, stream);
+}
+
+extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream) {
+    if (!ctx || (n && (!d_in || !d_off || !d_out))) return BG_ERR_INVALID_ARG;
+    if (n == 0) return BG_OK;
+    BG_HIP(hipSetDevice(ctx->device));
+    se_revcomp_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(n, d_in, d_off, d_out);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+namespace {
+
+// the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order
+int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
+                const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
+                uint64_t ops_cap, uint64_t* ops_used) {
     if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (n_reads == 0) return BG_OK;
@@ -432,6 +575,7 @@ extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_
     const uint64_t bytes = read_off[n_reads];
     uint8_t *d_reads = nullptr, *d_ops = nullptr;
     uint64_t* d_off = nullptr;
+    uint8_t* d_strand = nullptr;
     bg_seed_hit_t* d_hits = nullptr;
     std::vector<uint8_t> h_ops;
     int panic_rc = BG_OK;
@@ -441,12 +585,14 @@ extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_
         BG_HIP(hipMalloc((void**)&d_off, (n_reads + 1) * 8));
         BG_HIP(hipMalloc((void**)&d_hits, n_reads * sizeof(bg_seed_hit_t)));
         if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_reads * stride));
+        if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_reads));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-        int rc = bg_seed_extend_batch_dev(fm, sc, prm, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_ops, stride, nullptr, st);
+        int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(hits, d_hits, n_reads * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
+        if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_reads, hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_reads * stride);
             BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_reads * stride, hipMemcpyDeviceToHost, st));
@@ -459,6 +605,7 @@ extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_
     hipFree(d_off);
     hipFree(d_hits);
     hipFree(d_ops);
+    hipFree(d_strand);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
     uint64_t used = 0;
@@ -477,4 +624,19 @@ extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_
     }
     if (ops_used) *ops_used = used;
     return status ? status : panic_rc;
+}
+
+}  // namespace
+
+extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint64_t n_reads,
+                                    const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* ops_buf,
+                                    uint64_t ops_cap, uint64_t* ops_used) {
+    return se_run_host(fm, sc, prm, 0, n_reads, reads, read_off, hits, nullptr, ops_buf, ops_cap, ops_used);
+}
+
+extern "C" int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
+                                            uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                            uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used);
 }

@@ -4,7 +4,8 @@ The reference has no such function; callers compose it from `FMIndex::backward_s
 `Aligner::semiglobal` (/root/reference/src/lib.rs:129-165, benches/fmindex.rs:20-38).  The composition — which
 seeds vote, hit -> proposed read start, per-read dedup, window gather, best-hit reduction, the winners'
 operations — runs in HIP kernels behind the C ABI (rust-bio_amd/csrc/seed_extend.hip); its definition is in
-include/biogpu.h (the tests hold a CPU statement of it).  This module only marshals arguments."""
+include/biogpu.h (the tests hold a CPU statement of it).  The `_strands` calls map each read on the forward strand, on
+the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -61,3 +62,45 @@ def seed_extend_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_h
     _lib.check(_lib.lib().bg_seed_extend_batch_dev(fm.h, C.byref(sc), C.byref(pc), n_reads, d_reads, d_read_off, max_read_len,
                                                    d_hits, d_ops, ops_stride, totals.ctypes.data if totals is not None else None,
                                                    stream), "bg_seed_extend_batch_dev")
+
+
+def seed_extend_strands_arrays(fm, scoring, reads, read_off, params=None, strands=_lib.STRAND_BOTH, want_ops=True,
+                               allow_out_of_alphabet=False):
+    """bg_seed_extend_strands_batch, host buffers: returns (hits: SEED_HIT_DTYPE[n], strand: uint8[n] of HIT_FORWARD /
+    HIT_REVERSE / HIT_NONE, ops: the winners' operations back to back).  A reverse-strand winner's alignment and operations
+    refer to revcomp(read) against the forward text.  Errors as seed_extend_arrays."""
+    params = params or SeedParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n, 1), dtype=np.uint8)
+    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc = scoring.to_c(), params.to_c()
+    rc = _lib.lib().bg_seed_extend_strands_batch(fm.h, C.byref(sc), C.byref(pc), strands, n, rd.ctypes.data, off.ctypes.data,
+                                                 hits.ctypes.data, strand.ctypes.data, ops.ctypes.data if want_ops else None, cap,
+                                                 C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_strands_batch")
+    return hits, strand[:n], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_strands_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand=0, d_ops=0, ops_stride=0,
+                            params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
+    """bg_seed_extend_strands_batch_dev (pointers are ints; d_strand / d_ops may be 0); `totals` as seed_extend_dev, summed
+    over the strands that ran."""
+    params = params or SeedParams()
+    sc, pc = scoring.to_c(), params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_strands_batch_dev(fm.h, C.byref(sc), C.byref(pc), strands, n_reads, d_reads, d_read_off,
+                                                           max_read_len, d_hits, d_strand or None, d_ops or None, ops_stride,
+                                                           totals.ctypes.data if totals is not None else None, stream),
+               "bg_seed_extend_strands_batch_dev")
+
+
+def revcomp_dev(n, d_in, d_off, d_out, ctx=None, stream=0):
+    """bg_revcomp_batch_dev: d_out[d_off[i] .. d_off[i + 1]) = dna::revcomp of the same range of d_in, for i < n (pointers
+    are ints; asynchronous on `stream`)."""
+    ctx = ctx or _lib.default_context()
+    _lib.check(_lib.lib().bg_revcomp_batch_dev(ctx.h, n, d_in, d_off, d_out, stream), "bg_revcomp_batch_dev")

@@ -1,5 +1,6 @@
 //! Seed-and-extend in one call (`bg_seed_extend_batch`): the composition rust-bio's callers write by hand from
-//! `backward_search`, `Interval::occ` and `Aligner::semiglobal` (src/lib.rs:129-165, benches/fmindex.rs:20-38).
+//! `backward_search`, `Interval::occ` and `Aligner::semiglobal` (src/lib.rs:129-165, benches/fmindex.rs:20-38), on the
+//! forward strand or on both (`bg_seed_extend_strands_batch`: the `dna::revcomp` of each read as well).
 use crate::fmindex::GpuFMIndex;
 use crate::pairwise::{scoring_to_c, tabulate};
 use crate::{concat, strerror, sys, to_alignment, zero_alignment};
@@ -12,6 +13,8 @@ pub struct Hit {
     pub ref_start: usize,
     pub ref_end: usize,
     pub n_candidates: u32,
+    /// the winner is on the reverse strand: `alignment` is of `dna::revcomp(read)` against the forward text (SAM's convention)
+    pub reverse: bool,
 }
 
 impl GpuFMIndex<'_> {
@@ -42,6 +45,37 @@ impl GpuFMIndex<'_> {
                 ref_start: h.ref_start as usize,
                 ref_end: h.ref_end as usize,
                 n_candidates: h.n_candidates,
+                reverse: false,
+            })
+            .collect()
+    }
+
+    /// `strands`: `sys::BG_STRAND_FORWARD`, `_REVERSE` or `_BOTH` (as u32).  The reads go in as given; the library builds the reverse
+    /// complements itself.  With both strands the higher score wins, the forward strand on an equal score.
+    pub fn seed_extend_batch_strands<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], strands: u32, seed_len: u32,
+                                                   stride: u32, max_occ: u32, pad: u32) -> Vec<Hit> {
+        let table = tabulate(scoring);
+        let sc = scoring_to_c(scoring, &table);
+        let prm = sys::bg_seed_params_t { seed_len, stride, max_occ, pad };
+        let (buf, off) = concat(reads);
+        let zero = sys::bg_seed_hit_t { aln: zero_alignment(), window_start: 0, ref_start: 0, ref_end: 0, n_candidates: 0, n_seed_hits: 0 };
+        let mut hits = vec![zero; reads.len()];
+        let mut strand = vec![0u8; reads.len()];
+        let mut ops = vec![0u8; 2 * buf.len() + (2 * pad as usize + 4) * reads.len() + 8];
+        let mut used = 0u64;
+        let rc = unsafe {
+            sys::bg_seed_extend_strands_batch(self.h, &sc, &prm, strands, reads.len() as u64, buf.as_ptr(), off.as_ptr(),
+                                              hits.as_mut_ptr(), strand.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used)
+        };
+        assert!(rc == 0, "{}", strerror(rc));
+        hits.iter()
+            .zip(strand.iter())
+            .map(|(h, &s)| Hit {
+                alignment: if h.aln.score == sys::BG_MIN_SCORE { None } else { Some(to_alignment(&h.aln, &ops)) },
+                ref_start: h.ref_start as usize,
+                ref_end: h.ref_end as usize,
+                n_candidates: h.n_candidates,
+                reverse: s as i32 == sys::BG_HIT_REVERSE,
             })
             .collect()
     }
