@@ -47,12 +47,6 @@ using namespace bgfm;
 
 namespace {
 
-// `jump` (optional): the state of the search after the LAST kJumpK symbols of a pattern, for every
-// kJumpK-mer over the four coded symbols — {l, r, depth}: depth < kJumpK means the search ends there
-// (the next symbol empties the interval).  A pattern whose last kJumpK symbols are all coded starts from
-// that entry: one table read instead of kJumpK LF steps (2 block reads each).  The table is filled by
-// this very kernel (run without it: JUMP == false, which also keeps the two apart in profiles), so the
-// results cannot differ.
 // SEEDS: the patterns are the seed windows of a batch of reads (seed-and-extend, seed_extend.hip) — query q is
 // seed q % S of read q / S: pat[pat_off[r] + k * stride ..+ seed_len) while it fits in the read (else an empty
 // pattern: Absent), so overlapping windows need no copy of the reads.
@@ -64,13 +58,12 @@ namespace {
 // tools/microbench/ub_gather64.hip); the results are the same.
 // (the DEFER launch reads every tag once — n_q bytes, ~10 us per 10 M queries — and the fast kernel writes every tag it
 //  owns, deferred or answered, so a caller's stale tag buffer cannot fake a deferral)
-// DEFER: only the queries whose tag is kTagDeferred are searched (second launch behind fm_search_fast_kernel)
-template <bool JUMP, bool SEEDS, bool PACKED = false, bool COUNT = false, bool DEFER = false>
+// DEFER: only the queries whose tag is kTagDeferred are searched (second launch behind a fast kernel)
+template <bool SEEDS, bool PACKED, bool COUNT, bool DEFER>
 __global__ __launch_bounds__(256) void fm_backward_search_kernel(
     FmDev fm, uint64_t n_q, const uint8_t* __restrict__ pat, const uint64_t* __restrict__ pat_off,
     uint8_t* __restrict__ tag, uint64_t* __restrict__ lower, uint64_t* __restrict__ upper,
-    uint32_t* __restrict__ matched_len, const uint4* __restrict__ jump, const SeedSrc seeds) {
-    static_assert(!(PACKED && JUMP), "packed patterns: no jump table");
+    uint32_t* __restrict__ matched_len, const SeedSrc seeds) {
     __shared__ uint16_t s_class[256];
     __shared__ uint32_t s_less[256];
     __shared__ uint32_t s_exc[kMaxExcLds];
@@ -127,35 +120,6 @@ __global__ __launch_bounds__(256) void fm_backward_search_kernel(
                 l = 0;
                 r = fm.n - 1;  // fmindex.rs:148
                 matched = 0;
-                if (JUMP && len >= kJumpK) {
-                    uint32_t idx = 0;
-                    bool coded = true;
-                    for (uint32_t u = 0; u < kJumpK; u++) {  // u-th symbol from the end
-                        const uint32_t c = s_class[pat[off + len - 1 - u]];
-                        coded = coded && c < 4;
-                        idx = idx << 2 | (c & 3u);
-                    }
-                    if (coded) {
-                        const uint4 e = jump[idx];
-                        l = e.x;
-                        r = e.y;
-                        matched = e.z;
-                        pos = len - e.z;
-                        if (e.z < kJumpK) {  // the search ends inside the last kJumpK symbols
-                            if (e.z)
-                                emit(BG_FM_PARTIAL, l, r + 1, e.z);
-                            else
-                                emit(BG_FM_ABSENT, 0, 0, 0);
-                            q += n_quads;
-                            continue;
-                        }
-                        if (pos == 0) {
-                            emit(BG_FM_COMPLETE, l, r + 1, matched);
-                            q += n_quads;
-                            continue;
-                        }
-                    }
-                }
                 if (PACKED) {
                     const uint64_t gs = off + pos - 1;
                     pk_cur = pk[gs >> 4];
@@ -282,28 +246,23 @@ __global__ __launch_bounds__(256) void fm_backward_search_kernel(
 // (tests/test_gpu_fm.py, test_gpu_pack2.py); 466 -> ~560 M queries/s on the 100 Mbp index.
 // PACKED: `pat` is a 2-bit stream already (pack2.hip, the index's codes; offsets in symbols): taking a query is a funnel
 // shift of up to 16 dwords into the slot, nothing can be "bad".
-// STEP2: the LF loop takes two pattern symbols per block access from the index's 2-step rank blocks (fm_kernels.h:
-// Fm2Dev; f2.blocks2 != null), single steps — the last symbol of an odd-length pattern, and the two steps of a double
-// step that found nothing — from the same blocks: half the requests of a query against a request-rate limit.
-template <bool SEEDS, bool COUNT, bool PACKED = false, bool STEP2 = false>
+// Single LF steps on the 1-step blocks: what answers an index without 2-step rank blocks, and searches with "no_step2"
+// set; fm_search_fast2x_kernel is the same search on the 2-step blocks.
+template <bool SEEDS, bool COUNT, bool PACKED>
 __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t n_q, const uint8_t* __restrict__ pat,
                                                              const uint64_t* __restrict__ pat_off, uint8_t* __restrict__ tag,
                                                              uint64_t* __restrict__ lower, uint64_t* __restrict__ upper,
-                                                             uint32_t* __restrict__ matched_len, const SeedSrc seeds, const Fm2Dev f2) {
+                                                             uint32_t* __restrict__ matched_len, const SeedSrc seeds) {
     __shared__ uint16_t s_class[256];
     __shared__ uint32_t s_less4[4];
     __shared__ uint32_t s_exc[kMaxExcLds];
-    __shared__ uint32_t s_pk[64 * (kFastSyms / 16) + 1];  // (+1: the 2-step funnel reads one dword past a slot's last)
+    // (+1 and its zero store: no code here reads that dword, but without them the prologue compiles differently — 45
+    //  VGPRs instead of 43; with them the kernel keeps the instructions it had when a 2-step branch still read it)
+    __shared__ uint32_t s_pk[64 * (kFastSyms / 16) + 1];
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) s_class[i] = fm.sym_class[i];
     if (threadIdx.x < 4) s_less4[threadIdx.x] = fm.less[(seeds.code_bytes >> (8 * threadIdx.x)) & 0xFFu];
     for (uint32_t i = threadIdx.x; i < fm.n_exc; i += blockDim.x) s_exc[i] = fm.exc_pos[i];
     if (threadIdx.x == 0) s_pk[64 * (kFastSyms / 16)] = 0;
-    __shared__ uint32_t s_c2[16], s_e2pos[kMaxExc2], s_e2nib[kMaxExc2];
-    if (STEP2 && threadIdx.x < 16) s_c2[threadIdx.x] = f2.c2[threadIdx.x];
-    if (STEP2 && threadIdx.x < kMaxExc2) {
-        s_e2pos[threadIdx.x] = f2.exc_pos[threadIdx.x];
-        s_e2nib[threadIdx.x] = f2.exc_nib[threadIdx.x];
-    }
     __syncthreads();
 
     const uint32_t t = threadIdx.x & 3;
@@ -312,7 +271,7 @@ __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t 
     uint32_t* const wave_slots = s_pk + (threadIdx.x >> 6) * 16 * (kFastSyms / 16);  // the 16 slots of this wavefront
     const uint64_t n_quads = (uint64_t)gridDim.x * (blockDim.x >> 2);
     uint64_t q = (uint64_t)blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);
-    bool active = false, need = true, force1 = false;
+    bool active = false, need = true;
     uint32_t pos = 0, l = 0, r = 0, matched = 0, n_lines = 0;
 
     // Taking the next query is a job of the WHOLE wavefront, one waiting quad at a time (round 3; a quad packing its own
@@ -397,7 +356,6 @@ __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t 
                 matched = 0;
                 active = true;
                 need = false;
-                force1 = false;
             }
             waiting &= waiting - 1;
         }
@@ -413,76 +371,7 @@ __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t 
     for (;;) {
         if (__any(need)) fetch_all();
         if (!__any(active)) break;
-        if (STEP2 && active) {
-            // two iterations of the loop at fmindex.rs:160-182 per block access (fm_kernels.h), or one (`single`: the last
-            // symbol of an odd length, and the two symbols of a pair that no row of the interval has in front).  One code
-            // path for both: k symbols, a 4-bit code whose low half is masked off for a single step, and ONE end
-            // condition — Occ(r) == Occ(l - 1) is "the pair does not occur" for a double step and, for a single one, both
-            // of the reference's (occ_r == 0 implies it; l > r is it), which report the same (pl, pr, matched_len)
-            const bool single = force1 || pos == 1;
-            const uint32_t k = single ? 1u : 2u;
-            const uint32_t p2 = pos - k, ix = p2 >> 4;
-            // symbols pos-2 (second: low bits) and pos-1 (first) as one nibble; a single step reads its symbol into the high half
-            uint32_t c = __builtin_amdgcn_alignbit(slot[ix + 1], slot[ix], 2 * (p2 & 15u));
-            c = single ? (c & 3u) << 2 : (c & 15u);
-            const uint32_t base = single ? s_less4[c >> 2] : s_c2[c];
-            const uint32_t lm1 = l ? l - 1 : 0u;
-            const uint32_t br = r / kSym2PerBlock, orr = r % kSym2PerBlock, bl = lm1 / kSym2PerBlock, ol = lm1 % kSym2PerBlock;
-            const uint4 rc = f2.blocks2[(uint64_t)br * 8 + t], rs = f2.blocks2[(uint64_t)br * 8 + 4 + t];
-            uint4 lc = rc, ls = rs;
-            if (bl != br) {
-                lc = f2.blocks2[(uint64_t)bl * 8 + t];
-                ls = f2.blocks2[(uint64_t)bl * 8 + 4 + t];
-                if (COUNT) n_lines += 1;
-            }
-            if (COUNT) n_lines += 1;
-            const Pair2Key key2 = pair2_key(c, single);
-            uint32_t occ_r = quad_sum(block2_part(rc, rs, t, orr, c, single, key2));
-            uint32_t occ_l = quad_sum(block2_part(lc, ls, t, ol, c, single, key2));
-            // positions that hold a 0 for a symbol without a code: the first two inline (one sentinel: exactly two; unused
-            // entries sit at position 2^32 - 1, which no rank reaches), more of them (several sentinels) in a loop
-            {
-                const uint32_t key = single ? 16u : c;  // what an entry must say to have been counted: "first component" / this nibble
-                const uint32_t e0 = f2.exc_pos[0], n0 = single ? (f2.exc_nib[0] & 16u) | (c ? 32u : 0u) : (f2.exc_nib[0] & 15u);
-                const uint32_t e1 = f2.exc_pos[1], n1 = single ? (f2.exc_nib[1] & 16u) | (c ? 32u : 0u) : (f2.exc_nib[1] & 15u);
-                occ_r -= (n0 == key && e0 <= r) ? 1u : 0u;
-                occ_l -= (n0 == key && e0 <= lm1) ? 1u : 0u;
-                occ_r -= (n1 == key && e1 <= r) ? 1u : 0u;
-                occ_l -= (n1 == key && e1 <= lm1) ? 1u : 0u;
-                for (uint32_t e = 2; e < f2.n_exc; e++) {  // (uniform)
-                    const uint32_t pe = s_e2pos[e], ne = s_e2nib[e];
-                    const uint32_t nk = single ? (ne & 16u) | (c ? 32u : 0u) : (ne & 15u);
-                    occ_r -= (nk == key && pe <= r) ? 1u : 0u;
-                    occ_l -= (nk == key && pe <= lm1) ? 1u : 0u;
-                }
-            }
-            occ_l = l ? occ_l : 0u;
-            const bool empty = occ_r == occ_l;
-            if (empty && !single) {
-                force1 = true;  // nothing changes: the two single steps that follow say how the query ends
-            } else if (empty) {
-                if (matched)
-                    emit(BG_FM_PARTIAL, l, r + 1, matched);
-                else
-                    emit(BG_FM_ABSENT, 0, 0, 0);
-                need = true;
-            } else {
-                l = base + occ_l;  // fmindex.rs:171 (twice for a double step)
-                r = base + occ_r - 1;
-                pos = p2;
-                matched += k;
-                if (pos == 0) {
-                    emit(BG_FM_COMPLETE, l, r + 1, matched);
-                    need = true;
-                }
-            }
-            if (need) {
-                q += n_quads;
-                active = false;
-                force1 = false;
-            }
-        }
-        if (!STEP2 && active) {
+        if (active) {
             // one iteration of the loop at fmindex.rs:160-182; the symbol is a code already
             pos -= 1;
             const uint32_t a = (slot[pos >> 4] >> (2 * (pos & 15u))) & 3u;
@@ -538,15 +427,21 @@ __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t 
     if (COUNT && t == 0 && n_lines) atomicAdd(seeds.lines, (unsigned long long)n_lines);
 }
 
-// K5x — fm_search_fast2x_kernel: fm_search_fast_kernel<STEP2> with TWO queries per quad (round 5).  With its requests
-// halved the search waits neither for memory throughput nor for the vector unit (0.60 of the 128-byte gather rate at
-// 3 Gbp, VALU 31 % busy, eight wavefronts per SIMD — the most the hardware holds): it waits for the latency of one block
-// access per step, and the only parallelism left to add is inside a wavefront.  Every quad walks two independent queries:
+// K5x — fm_search_fast2x_kernel: the fast kernel's search on the index's 2-step rank blocks (fm_kernels.h: Fm2Dev;
+// f2.blocks2 != null), TWO queries per quad.  The LF loop takes two pattern symbols per block access — half the requests of
+// a query against a request-rate limit (round 4) — and single steps (the last symbol of an odd-length pattern, and the two
+// symbols of a pair that no row of the interval has in front) from the same blocks.  One code path for both: k symbols, a
+// 4-bit code whose low half is masked off for a single step, and ONE end condition — Occ(r) == Occ(l - 1) is "the pair
+// does not occur" for a double step and, for a single one, both of the reference's (occ_r == 0 implies it; l > r is it),
+// which report the same (pl, pr, matched_len).
+// Two queries per quad (round 5): with its requests halved the search waits neither for memory throughput nor for the
+// vector unit (0.60 of the 128-byte gather rate at 3 Gbp, VALU 31 % busy, eight wavefronts per SIMD — the most the hardware
+// holds): it waits for the latency of one block access per step, and the only parallelism left to add is inside a wavefront.  Every quad walks two independent queries:
 // phase A computes the block addresses of both and issues their loads — all of them unconditional and in one basic block,
 // so that the second query's requests leave before the first one's data is waited for (the line of l - 1 is requested even
 // where it is the line of r: a hit in the vector cache) — phase B ranks and updates both.  Stream (quad, u) takes queries
 // (quad * 2 + u) + k * (quads * 2); results, deferral and LDS pattern slots as in fm_search_fast_kernel.
-// Measured (profiles/r05_fm_ilp.txt, 10 M x 100 bp): 846 -> 1076 M queries/s on the 100 Mbp index, 608 -> 794 M at 3 Gbp
+// Measured against one query per quad (profiles/r05_fm_ilp.txt, 10 M x 100 bp): 846 -> 1076 M queries/s on the 100 Mbp index, 608 -> 794 M at 3 Gbp
 // (packed patterns 908 -> 1121 and 657 -> 860).  86 VGPRs: five wavefronts per SIMD, ten queries in flight per SIMD-slot
 // against eight.  More is not better: three queries per quad (116 VGPRs, four wavefronts: twelve) reach 988 / 752, four
 // (147: three wavefronts) 838 / 673, and the same two queries compiled for six wavefronts (80 VGPRs, three values in
@@ -554,13 +449,14 @@ __global__ __launch_bounds__(256) void fm_search_fast_kernel(FmDev fm, uint64_t 
 // WIDE (round 6): the same kernel on 64-bit positions (FmLayout<true>: l, r, less, C2 and the exception positions are
 // uint64; the blocks' counters are relative to a superblock whose absolute base — sixteen pair codes + four single-step sums —
 // is one more load per rank, issued in phase A next to the block's).  The narrow instantiation compiles to the code it was.
-template <bool SEEDS, bool COUNT, bool PACKED, int U, bool WIDE = false>
+template <bool SEEDS, bool COUNT, bool PACKED, bool WIDE>
 __global__ __launch_bounds__(256) void fm_search_fast2x_kernel(typename FmLayout<WIDE>::Dev fm, uint64_t n_q, const uint8_t* __restrict__ pat,
                                                                const uint64_t* __restrict__ pat_off, uint8_t* __restrict__ tag,
                                                                uint64_t* __restrict__ lower, uint64_t* __restrict__ upper,
                                                                uint32_t* __restrict__ matched_len, const SeedSrc seeds,
                                                                const typename FmLayout<WIDE>::Dev2 f2) {
     using P = typename FmLayout<WIDE>::Pos;
+    constexpr int U = 2;                       // queries per quad
     constexpr uint32_t SLOT = kFastSyms / 16;  // dwords per pattern slot
     __shared__ uint16_t s_class[256];
     __shared__ P s_less4[4];
@@ -708,6 +604,7 @@ __global__ __launch_bounds__(256) void fm_search_fast2x_kernel(typename FmLayout
             p2[u] = s.active ? s.pos - (single[u] ? 1u : 2u) : 0u;
             const uint32_t* const slot = s_pk + ((threadIdx.x >> 2) * U + u) * SLOT;
             const uint32_t ix = p2[u] >> 4;
+            // symbols pos-2 (second: low bits) and pos-1 (first) as one nibble; a single step reads its symbol into the high half
             const uint32_t cc = __builtin_amdgcn_alignbit(slot[ix + 1], slot[ix], 2 * (p2[u] & 15u));
             c[u] = single[u] ? (cc & 3u) << 2 : (cc & 15u);
             lm1[u] = s.l ? s.l - 1 : 0u;
@@ -728,7 +625,7 @@ __global__ __launch_bounds__(256) void fm_search_fast2x_kernel(typename FmLayout
             }
             if (COUNT && s.active) n_lines += bl != br ? 2u : 1u;
         }
-        // ---- phase B: fmindex.rs:160-182, twice per block access (see fm_search_fast_kernel<STEP2>)
+        // ---- phase B: fmindex.rs:160-182, twice per block access (or once: `single`)
 #pragma unroll
         for (int u = 0; u < U; u++) {
             St& s = S[u];
@@ -742,6 +639,8 @@ __global__ __launch_bounds__(256) void fm_search_fast2x_kernel(typename FmLayout
                 occ_r += sbr[u];
                 occ_l += sbl[u];
             }
+            // positions that hold a 0 for a symbol without a code: the first two inline (one sentinel: exactly two; unused
+            // entries sit at the largest position, which no rank reaches), more of them (several sentinels) in a loop
             {
                 const uint32_t key = single[u] ? 16u : c[u];
                 const P e0 = f2.exc_pos[0];
@@ -788,26 +687,6 @@ __global__ __launch_bounds__(256) void fm_search_fast2x_kernel(typename FmLayout
         }
     }
     if (COUNT && t == 0 && n_lines) atomicAdd(seeds.lines, (unsigned long long)n_lines);
-}
-
-// jump-table construction: every kJumpK-mer over the four coded bytes as a pattern ...
-__global__ __launch_bounds__(256) void fm_jump_patterns_kernel(uint32_t code_byte, uint8_t* pat, uint64_t* pat_off) {
-    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t n = 1ull << (2 * kJumpK);
-    if (idx > n) return;
-    pat_off[idx] = idx * kJumpK;
-    if (idx == n) return;
-    for (uint32_t j = 0; j < kJumpK; j++) pat[idx * kJumpK + j] = (uint8_t)(code_byte >> (8 * ((idx >> (2 * j)) & 3u)));
-}
-// ... and its search result as a table entry {l, r, depth, 0}
-__global__ __launch_bounds__(256) void fm_jump_pack_kernel(const uint8_t* tag, const uint64_t* lower, const uint64_t* upper,
-                                                           const uint32_t* matched, uint4* jump) {
-    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (1ull << (2 * kJumpK))) return;
-    const uint32_t tg = tag[idx];
-    uint4 e = make_uint4(0, 0, 0, 0);
-    if (tg == BG_FM_COMPLETE || tg == BG_FM_PARTIAL) e = make_uint4((uint32_t)lower[idx], (uint32_t)upper[idx] - 1u, matched[idx], 0);
-    jump[idx] = e;
 }
 
 }  // namespace
@@ -1344,7 +1223,6 @@ extern "C" int bg_fm_free(bg_fm* fm) {
     hipFree(fm->d_bitvecs);
     hipFree(fm->d_bwt_raw);
     if (fm->text_owned) hipFree(fm->d_text);
-    hipFree(fm->d_jump);
     hipFree(fm->d_sa);
     hipFree(fm->d_extra_row);
     hipFree(fm->d_extra_pos);
@@ -1358,42 +1236,76 @@ extern "C" uint64_t bg_fm_step2_bytes(const bg_fm* fm) {
     return fm && fm->dev2.blocks2 && !fm->no_step2 ? ((uint64_t)fm->dev.n + kSym2PerBlock - 1) / kSym2PerBlock * 128 : 0;
 }
 
-// the four 2-bit codes all stand for symbols and no symbol is ranked by a bit vector: the packed / fast kernels apply
-static bool fm_fast_ok(const bg_fm* fm) { return !fm->dev.n_dense && fm->n_codes == 4 && !fm->no_fast; }
-// ... and the index has 2-step rank blocks (fm_step2.hip): the fast kernels take two symbols per block access
-static bool fm_step2_ok(const bg_fm* fm) { return fm->dev2.blocks2 != nullptr && !fm->no_step2; }
-// grid of fm_search_fast2x_kernel: persistent blocks, as many as are resident (its registers decide), 128 queries each
-template <typename K>
-static uint64_t fm_2x_blocks(K kernel, uint64_t n_q, int u) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    return std::min<uint64_t>((n_q + 64 * (uint64_t)u - 1) / (64 * (uint64_t)u), 256ull * (uint64_t)per_cu);
-}
-#define FM_LAUNCH_2X(SEEDS, COUNT, PACKED, ...)                                                                                  \
-    fm_search_fast2x_kernel<SEEDS, COUNT, PACKED, 2><<<dim3((unsigned)fm_2x_blocks(fm_search_fast2x_kernel<SEEDS, COUNT, PACKED, 2>, n_q, 2)), \
-                                                       dim3(256), 0, st>>>(__VA_ARGS__)
-#define FM_LAUNCH_2XW(SEEDS, PACKED, ...)                                                                                                    \
-    fm_search_fast2x_kernel<SEEDS, false, PACKED, 2, true><<<dim3((unsigned)fm_2x_blocks(fm_search_fast2x_kernel<SEEDS, false, PACKED, 2, true>, n_q, 2)), \
-                                                            dim3(256), 0, st>>>(__VA_ARGS__)
 static SeedSrc fm_codes(const bg_fm* fm) {
     SeedSrc ex{};
     ex.code_bytes = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
                     (uint32_t)fm->code_byte[3] << 24;
     return ex;
 }
+// grid of fm_search_fast2x_kernel: persistent blocks, as many as are resident (its registers decide), 128 queries each
+template <typename K>
+static uint64_t fm_2x_blocks(K kernel, uint64_t n_q) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+    return std::min<uint64_t>((n_q + 127) / 128, 256ull * (uint64_t)per_cu);
+}
 
-// the 2x fast kernel on 64-bit positions (fm_wide.hip decides when; queries it cannot hold are left tagged kTagDeferred)
-int fm_wide_fast2x_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
-                          uint64_t* d_upper, uint32_t* d_matched_len, hipStream_t st, const SeedSrc* seeds, bool packed) {
-    SeedSrc src = fm_codes(fm);
-    if (seeds) src.S = seeds->S, src.stride = seeds->stride, src.seed_len = seeds->seed_len;
-    if (seeds)
-        FM_LAUNCH_2XW(true, false, fm->wdev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, fm->wdev2);
-    else if (packed)
-        FM_LAUNCH_2XW(false, true, fm->wdev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, fm->wdev2);
-    else
-        FM_LAUNCH_2XW(false, false, fm->wdev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, fm->wdev2);
+// Every backward search, on either layout and in every flavour (SEEDS: the seed windows of src; PACKED: 2-bit patterns,
+// offsets in symbols; COUNT: the block loads counted into src.lines, narrow index only).  The fast kernels apply when the
+// four 2-bit codes all stand for symbols (no dense symbols), the patterns may fit their LDS slots, no test option says
+// otherwise and, on a wide index, the index has 2-step blocks (no single-step fast kernel there).  They answer what their
+// slots hold and tag the rest (a byte outside the codes, more than kFastSyms symbols) kTagDeferred for the generic kernel
+// launched behind them; otherwise the generic kernel answers every query.
+template <bool SEEDS, bool PACKED, bool COUNT>
+static int fm_search(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
+                     uint64_t* d_upper, uint32_t* d_matched_len, const SeedSrc& src, hipStream_t st) {
+    const bool step2 = (fm->wide ? fm->wdev2.blocks2 : fm->dev2.blocks2) && !fm->no_step2;
+    const bool fast = fm->n_codes == 4 && (fm->wide ? step2 : !fm->dev.n_dense) && !fm->no_fast && (!SEEDS || src.seed_len <= kFastSyms);
+    if (fm->wide) {
+        if constexpr (COUNT) {
+            return BG_ERR_UNSUPPORTED;
+        } else {
+            if (!fast) return fm_wide_search_launch<SEEDS, PACKED, false>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
+            auto kernel = fm_search_fast2x_kernel<SEEDS, false, PACKED, true>;
+            kernel<<<dim3((unsigned)fm_2x_blocks(kernel, n_q)), dim3(256), 0, st>>>(fm->wdev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper,
+                                                                                    d_matched_len, src, fm->wdev2);
+            BG_HIP(hipGetLastError());
+            return fm_wide_search_launch<SEEDS, PACKED, true>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
+        }
+    }
+    const dim3 grid((unsigned)std::min<uint64_t>((n_q + 63) / 64, 256 * 8));  // 8 resident 256-thread blocks per CU
+    if (!fast) {
+        fm_backward_search_kernel<SEEDS, PACKED, COUNT, false><<<grid, dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower,
+                                                                                        d_upper, d_matched_len, src);
+    } else {
+        if (step2) {
+            auto kernel = fm_search_fast2x_kernel<SEEDS, COUNT, PACKED, false>;
+            kernel<<<dim3((unsigned)fm_2x_blocks(kernel, n_q)), dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper,
+                                                                                    d_matched_len, src, fm->dev2);
+        } else {
+            fm_search_fast_kernel<SEEDS, COUNT, PACKED><<<grid, dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper,
+                                                                                   d_matched_len, src);
+        }
+        fm_backward_search_kernel<SEEDS, PACKED, COUNT, true><<<grid, dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower,
+                                                                                       d_upper, d_matched_len, src);
+    }
     BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+// `search` under the ctx's timing events: with ctx->timing, its span on `st` counts as one launch in ctx->last.fm_ms
+template <typename F>
+static int fm_timed(bg_ctx* ctx, hipStream_t st, F&& search) {
+    const bool timed = ctx && ctx->timing;
+    if (timed) BG_HIP(hipEventRecord(ctx->ev[0], st));
+    const int rc = search();
+    if (rc || !timed) return rc;
+    BG_HIP(hipEventRecord(ctx->ev[1], st));
+    BG_HIP(hipEventSynchronize(ctx->ev[1]));
+    float ms = 0;
+    BG_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->last.fm_ms += ms;
+    ctx->last.fm_launches += 1;
     return BG_OK;
 }
 
@@ -1401,21 +1313,6 @@ extern "C" int bg_fm_set_option(bg_fm* fm, const char* key, int64_t value) {
     if (!fm || !key) return BG_ERR_INVALID_ARG;
     if (!strcmp(key, "no_step2")) {  // searches take single steps only, whether the index has 2-step blocks or not (tests, A/B)
         fm->no_step2 = value != 0;
-        return BG_OK;
-    }
-    if (!strcmp(key, "ilp")) {  // queries per quad of the 2-step search: 1 fm_search_fast_kernel, 2 fm_search_fast2x_kernel (A/B)
-        if (value != 1 && value != 2) return BG_ERR_INVALID_ARG;
-        fm->ilp = (int)value;
-        return BG_OK;
-    }
-    if (!strcmp(key, "jump_min_queries")) {  // batch size from which K5 builds / uses its jump table; < 0: never (default)
-        std::lock_guard<std::mutex> lk(fm->jump_mu);
-        fm->no_jump = value < 0;
-        fm->jump_min_queries = value < 0 ? ~0ull : (uint64_t)value;
-        if (fm->no_jump && fm->d_jump) {
-            hipFree(fm->d_jump);
-            fm->d_jump = nullptr;
-        }
         return BG_OK;
     }
     if (!strcmp(key, "no_fast")) {  // tests: every search through the generic kernel
@@ -1432,155 +1329,24 @@ extern "C" int bg_fm_backward_search_batch_dev(bg_fm* fm, uint64_t n_q, const ui
     if (!fm || (n_q && (!d_pat_off || !d_tag || !d_lower || !d_upper || !d_matched_len)))
         return BG_ERR_INVALID_ARG;
     if (n_q == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
     hipStream_t st = (hipStream_t)stream;
-    if (fm->wide) {  // 64-bit positions: fm_wide.hip
-        if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
-        const int rcw = fm_wide_search_dev(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, st);
-        if (rcw) return rcw;
-        if (ctx->timing) {
-            BG_HIP(hipEventRecord(ctx->ev[1], st));
-            BG_HIP(hipEventSynchronize(ctx->ev[1]));
-            float ms = 0;
-            BG_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-            ctx->last.fm_ms += ms;
-            ctx->last.fm_launches += 1;
-        }
-        return BG_OK;
-    }
-    const uint64_t quads_per_block = 64;
-    uint64_t blocks = (n_q + quads_per_block - 1) / quads_per_block;
-    blocks = std::min<uint64_t>(blocks, 256 * 8);  // 8 resident 256-thread blocks per CU
-    // the jump table pays off from a few million LF steps on; it is built once per index, by the search itself
-    const uint4* jump = nullptr;
-    if (!fm->no_jump && n_q >= fm->jump_min_queries && fm->n_codes == 4) {
-      std::lock_guard<std::mutex> lk(fm->jump_mu);
-      if (!fm->d_jump && !fm->no_jump) {
-        const uint64_t nk = 1ull << (2 * kJumpK);
-        void* d_table = nullptr;
-        uint8_t *t_pat = nullptr, *t_tag = nullptr;
-        uint64_t *t_off = nullptr, *t_lo = nullptr, *t_hi = nullptr;
-        uint32_t* t_ml = nullptr;
-        auto build = [&]() -> int {
-            BG_HIP(hipMalloc((void**)&t_pat, nk * kJumpK));
-            BG_HIP(hipMalloc((void**)&t_off, (nk + 1) * 8));
-            BG_HIP(hipMalloc((void**)&t_tag, nk));
-            BG_HIP(hipMalloc((void**)&t_lo, nk * 8));
-            BG_HIP(hipMalloc((void**)&t_hi, nk * 8));
-            BG_HIP(hipMalloc((void**)&t_ml, nk * 4));
-            BG_HIP(hipMalloc(&d_table, nk * sizeof(uint4)));
-            const uint32_t cb = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
-                                (uint32_t)fm->code_byte[3] << 24;
-            fm_jump_patterns_kernel<<<dim3((unsigned)((nk + 256) / 256)), dim3(256), 0, st>>>(cb, t_pat, t_off);
-            fm_backward_search_kernel<false, false><<<dim3(256 * 8), dim3(256), 0, st>>>(fm->dev, nk, t_pat, t_off, t_tag, t_lo, t_hi, t_ml, nullptr, SeedSrc{});
-            fm_jump_pack_kernel<<<dim3((unsigned)(nk / 256)), dim3(256), 0, st>>>(t_tag, t_lo, t_hi, t_ml, (uint4*)d_table);
-            BG_HIP(hipGetLastError());
-            BG_HIP(hipStreamSynchronize(st));
-            fm->bytes += nk * sizeof(uint4);
-            return BG_OK;
-        };
-        const int rcj = build();
-        hipFree(t_pat);
-        hipFree(t_off);
-        hipFree(t_tag);
-        hipFree(t_lo);
-        hipFree(t_hi);
-        hipFree(t_ml);
-        if (rcj) {  // no memory for the table: search without it
-            hipFree(d_table);
-            fm->no_jump = true;
-        } else {
-            fm->d_jump = d_table;  // published complete
-        }
-      }
-      jump = (const uint4*)fm->d_jump;
-    }
-    if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
-    if (jump) {
-        fm_backward_search_kernel<true, false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, jump, SeedSrc{});
-    } else if (fm_fast_ok(fm)) {
-        // DNA-like index: patterns become 2-bit codes in LDS when a quad takes them; what that path cannot hold (a byte
-        // outside the four codes, more than kFastSyms symbols) is left to the generic kernel behind it
-        if (fm_step2_ok(fm) && fm->ilp >= 2)
-            FM_LAUNCH_2X(false, false, false, fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, fm_codes(fm), fm->dev2);
-        else if (fm_step2_ok(fm))
-            fm_search_fast_kernel<false, false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, fm_codes(fm), fm->dev2);
-        else
-            fm_search_fast_kernel<false, false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, fm_codes(fm), fm->dev2);
-        fm_backward_search_kernel<false, false, false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, SeedSrc{});
-    } else {
-        fm_backward_search_kernel<false, false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, SeedSrc{});
-    }
-    BG_HIP(hipGetLastError());
-    if (ctx->timing) {
-        BG_HIP(hipEventRecord(ctx->ev[1], st));
-        BG_HIP(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        BG_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->last.fm_ms += ms;
-        ctx->last.fm_launches += 1;
-    }
-    return BG_OK;
+    return fm_timed(fm->ctx, st, [&] {
+        return fm_search<false, false, false>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, fm_codes(fm), st);
+    });
 }
 
 // the seed windows of a batch of reads as patterns (see SeedSrc): n_reads * S queries, results indexed [read * S + seed]
+// (timed: the seed search inside bg_seed_extend_batch_dev, kernel_ms.seed_search of bench.py)
 int bg_fm_search_seeds_dev(bg_fm* fm, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t S,
                            uint32_t stride, uint32_t seed_len, uint8_t* d_tag, uint64_t* d_lower, uint64_t* d_upper,
                            uint32_t* d_matched_len, hipStream_t st) {
     const uint64_t n_q = n_reads * S;
     if (n_q == 0) return BG_OK;
-    if (fm->wide) {  // 64-bit positions: fm_wide.hip
-        SeedSrc src{};
-        src.S = S, src.stride = stride, src.seed_len = seed_len;
-        bg_ctx* cx = fm->ctx;
-        if (cx && cx->timing) BG_HIP(hipEventRecord(cx->ev[0], st));
-        const int rcw = fm_wide_search_dev(fm, n_q, d_reads, d_read_off, d_tag, d_lower, d_upper, d_matched_len, st, &src, false);
-        if (rcw) return rcw;
-        if (cx && cx->timing) {
-            BG_HIP(hipEventRecord(cx->ev[1], st));
-            BG_HIP(hipEventSynchronize(cx->ev[1]));
-            float ms = 0;
-            BG_HIP(hipEventElapsedTime(&ms, cx->ev[0], cx->ev[1]));
-            cx->last.fm_ms += ms;
-            cx->last.fm_launches += 1;
-        }
-        return BG_OK;
-    }
-    const uint64_t blocks = std::min<uint64_t>((n_q + 63) / 64, 256 * 8);
     SeedSrc src = fm_codes(fm);
     src.S = S, src.stride = stride, src.seed_len = seed_len;
-    bg_ctx* ctx = fm->ctx;
-    if (ctx && ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
-    if (fm_fast_ok(fm) && seed_len <= kFastSyms) {
-        if (fm_step2_ok(fm) && fm->ilp >= 2)
-            FM_LAUNCH_2X(true, false, false, fm->dev, n_q, d_reads, d_read_off, d_tag, d_lower, d_upper, d_matched_len, src, fm->dev2);
-        else if (fm_step2_ok(fm))
-            fm_search_fast_kernel<true, false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->dev, n_q, d_reads, d_read_off, d_tag,
-                                                                                                         d_lower, d_upper, d_matched_len, src, fm->dev2);
-        else
-            fm_search_fast_kernel<true, false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->dev, n_q, d_reads, d_read_off, d_tag, d_lower,
-                                                                                            d_upper, d_matched_len, src, fm->dev2);
-        fm_backward_search_kernel<false, true, false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, d_reads, d_read_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, src);
-    } else {
-        fm_backward_search_kernel<false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, d_reads, d_read_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, src);
-    }
-    BG_HIP(hipGetLastError());
-    if (ctx && ctx->timing) {  // (the seed search inside bg_seed_extend_batch_dev: kernel_ms.seed_search of bench.py)
-        BG_HIP(hipEventRecord(ctx->ev[1], st));
-        BG_HIP(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        BG_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->last.fm_ms += ms;
-        ctx->last.fm_launches += 1;
-    }
-    return BG_OK;
+    return fm_timed(fm->ctx, st, [&] {
+        return fm_search<true, false, false>(fm, n_q, d_reads, d_read_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
+    });
 }
 
 // ---- 2-bit packed patterns (north_star: "coalesced HBM loads of packed 2-bit reads") -------------------------------
@@ -1599,39 +1365,10 @@ extern "C" int bg_fm_backward_search_packed_dev(bg_fm* fm, uint64_t n_q, const u
     if (!fm || (n_q && (!d_packed || !d_sym_off || !d_tag || !d_lower || !d_upper || !d_matched_len))) return BG_ERR_INVALID_ARG;
     if ((!fm->wide && fm->dev.n_dense) || fm->n_codes != 4) return BG_ERR_UNSUPPORTED;
     if (n_q == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t blocks = std::min<uint64_t>((n_q + 63) / 64, 256 * 8);
-    const SeedSrc ex = fm_codes(fm);
-    if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
-    if (fm->wide) {  // 64-bit positions: fm_wide.hip
-        const int rcw = fm_wide_search_dev(fm, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, st, nullptr, true);
-        if (rcw) return rcw;
-    } else if (!fm->no_fast) {  // the LDS-slot kernel; patterns beyond its 256 symbols are left to the generic packed kernel
-        if (fm_step2_ok(fm) && fm->ilp >= 2)
-            FM_LAUNCH_2X(false, false, true, fm->dev, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, ex, fm->dev2);
-        else if (fm_step2_ok(fm))
-            fm_search_fast_kernel<false, false, true, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, ex, fm->dev2);
-        else
-            fm_search_fast_kernel<false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, ex, fm->dev2);
-        fm_backward_search_kernel<false, false, true, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, ex);
-    } else {
-        fm_backward_search_kernel<false, false, true, false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-            fm->dev, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, ex);
-    }
-    BG_HIP(hipGetLastError());
-    if (ctx->timing) {
-        BG_HIP(hipEventRecord(ctx->ev[1], st));
-        BG_HIP(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        BG_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->last.fm_ms += ms;
-        ctx->last.fm_launches += 1;
-    }
-    return BG_OK;
+    return fm_timed(fm->ctx, st, [&] {
+        return fm_search<false, true, false>(fm, n_q, (const uint8_t*)d_packed, d_sym_off, d_tag, d_lower, d_upper, d_matched_len, fm_codes(fm), st);
+    });
 }
 
 // measurement aid: the same search with its 64-byte block loads counted (synchronous; *lines_out on the host)
@@ -1646,33 +1383,17 @@ extern "C" int bg_fm_backward_search_count_lines_dev(bg_fm* fm, uint64_t n_q, co
     BG_HIP(hipSetDevice(fm->ctx->device));
     unsigned long long* d_cnt = nullptr;
     BG_HIP(hipMalloc((void**)&d_cnt, 8));
-    int rc = BG_OK;
     auto run = [&]() -> int {
         BG_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
-        const uint64_t blocks = std::min<uint64_t>((n_q + 63) / 64, 256 * 8);
         SeedSrc ex = fm_codes(fm);
         ex.lines = d_cnt;
-        if (fm_fast_ok(fm)) {
-            if (fm_step2_ok(fm) && fm->ilp >= 2)
-            FM_LAUNCH_2X(false, true, false, fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, ex, fm->dev2);
-            else if (fm_step2_ok(fm))
-                fm_search_fast_kernel<false, true, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag,
-                                                                                                            d_lower, d_upper, d_matched_len, ex, fm->dev2);
-            else
-                fm_search_fast_kernel<false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->dev, n_q, d_pat, d_pat_off, d_tag,
-                                                                                               d_lower, d_upper, d_matched_len, ex, fm->dev2);
-            fm_backward_search_kernel<false, false, false, true, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, ex);
-        } else {
-            fm_backward_search_kernel<false, false, false, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-                fm->dev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, nullptr, ex);
-        }
-        BG_HIP(hipGetLastError());
+        const int rc = fm_search<false, false, true>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, ex, st);
+        if (rc) return rc;
         BG_HIP(hipMemcpyAsync(lines_out, d_cnt, 8, hipMemcpyDeviceToHost, st));
         BG_HIP(hipStreamSynchronize(st));
         return BG_OK;
     };
-    rc = run();
+    const int rc = run();
     hipFree(d_cnt);
     return rc;
 }

@@ -2,7 +2,6 @@
 // the 2-bit block layout, the quad rank helper and the index handle.  Layout notes: fm_index.hip.
 #ifndef BG_FM_KERNELS_H
 #define BG_FM_KERNELS_H
-#include <mutex>
 #include <vector>
 
 #include "bg_common.h"
@@ -12,7 +11,6 @@ namespace bgfm {
 constexpr uint32_t kSymPerBlock = 192;
 constexpr uint32_t kBvBits = 480;       // bits per 64-byte block of a dense symbol's rank bit vector (+ a 32-bit counter)
 constexpr uint32_t kMaxExcLds = 1024;   // sparse exception positions (all of them fit in LDS)
-constexpr uint32_t kJumpK = 12;  // symbols covered by the jump table of K5 (4^12 entries x 16 bytes = 256 MB)
 // symbol classes (uint16 per byte value): how Occ::get(r, a) is answered for byte a
 constexpr uint16_t kClsZero = 4;        // in the alphabet, never occurs in the BWT: 0
 constexpr uint16_t kClsSparse = 0x100;  // + e: sparse exception symbol e — sorted position list
@@ -276,7 +274,6 @@ struct bg_fm {
     bgfm::Fm2Dev dev2 = {};      // 2-step rank blocks (fm_kernels.h), built behind the index by fm_build_step2
     void* d_blocks2 = nullptr;
     bool no_step2 = false;       // option "no_step2": searches take single steps only (tests, A/B)
-    int ilp = 2;                 // option "ilp": queries per quad of the search (1: fm_search_fast_kernel / fmw_search_kernel; 2: the 2x kernels)
     void* d_blocks = nullptr;
     void* d_exc_pos = nullptr;
     void* d_exc_sym_pos = nullptr;
@@ -299,14 +296,7 @@ struct bg_fm {
     uint32_t sa_rate = 0;
     uint8_t sa_sentinel = 0;
     uint8_t code_byte[4] = {0, 0, 0, 0};  // byte value of each 2-bit code
-    // K5's optional jump table (opt-in through bg_fm_set_option "jump_min_queries"; +2.5 % on a cache-resident
-    // index, nothing on an HBM-resident one): built once, under jump_mu, and published only after the build
-    // stream has synchronised — concurrent searches either see the finished table or none
-    void* d_jump = nullptr;
-    std::mutex jump_mu;
-    uint64_t jump_min_queries = ~0ull;
-    bool no_jump = true;
-    bool no_fast = false;    // tests: never the pack-at-fetch kernel (fm_search_fast_kernel)
+    bool no_fast = false;    // option "no_fast": every search through the generic kernel alone (tests)
     int n_codes = 0;         // distinct bytes with a 2-bit code (<= 4)
     uint32_t less_len = 0;
     bool fmd_ok = false;  // the BWT is a word over dna::n_alphabet() + '$' (FMDIndex::from, fmindex.rs:323-327)
@@ -328,12 +318,11 @@ void fm_remember_inputs(bg_fm* fm, const uint8_t* alphabet, uint32_t n_sym, uint
 // fm_wide.hip: the index with 64-bit positions (built from a BWT in HBM; `less` null: the BWT's own cumulative counts)
 int fm_wide_build_dev(bg_ctx* ctx, const uint8_t* d_bwt, uint64_t n, const uint8_t* alphabet, uint32_t n_sym, const uint64_t* less,
                       uint32_t less_len, uint64_t* less_out, bg_fm** out, hipStream_t st);
-// `seeds` non-null: the SEEDS flavour (n_q = reads * S; S, stride, seed_len set); `packed`: pat is a 2-bit stream, offsets in symbols
-int fm_wide_search_dev(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
-                       uint64_t* d_upper, uint32_t* d_matched_len, hipStream_t st, const bgfm::SeedSrc* seeds = nullptr, bool packed = false);
-// fm_index.hip: the 2x fast kernel instantiated for 64-bit positions (needs fm->wdev2.blocks2); deferred queries are left tagged
-int fm_wide_fast2x_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
-                          uint64_t* d_upper, uint32_t* d_matched_len, hipStream_t st, const bgfm::SeedSrc* seeds, bool packed);
+// fm_wide.hip: fmw_search2x_kernel, the generic search on 64-bit positions, for one flavour (SeedSrc; DEFER: only the
+// queries tagged kTagDeferred).  fm_index.hip's fm_search decides when it runs.
+template <bool SEEDS, bool PACKED, bool DEFER>
+int fm_wide_search_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
+                          uint64_t* d_upper, uint32_t* d_matched_len, const bgfm::SeedSrc& src, hipStream_t st);
 // fm_step2.hip: the 2-step blocks behind a finished 64-bit index (best effort; synchronises the stream)
 void fm_build_step2_wide(bg_fm* fm, hipStream_t st);
 int fm_wide_sa_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st);

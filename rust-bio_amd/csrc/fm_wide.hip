@@ -9,14 +9,16 @@
 //   fm_wide_build_dev   the index from a BWT in HBM (bg_fm_build_dev, and bg_fm_build after an upload): the block kernels
 //                       of fm_index.hip's device builder, a 64-bit scan of the per-block counts, heads relative to the
 //                       superblock's first block
-//   fmw_search_kernel   FMIndexable::backward_search (fmindex.rs:144-208) for byte patterns: a quad per query like K5's
-//                       generic kernel, l and r 64-bit, Occ::get = base[superblock][code] + cnt[code] + popcount
+//   fmw_search2x_kernel FMIndexable::backward_search (fmindex.rs:144-208), the generic search: two queries per quad, l and r
+//                       64-bit, Occ::get = base[superblock][code] + cnt[code] + popcount; byte, packed and seed-window
+//                       patterns.  fm_index.hip's fm_search decides when it runs: alone, or behind the 2x fast kernel
+//                       (fm_search_fast2x_kernel<WIDE>, on the 2-step blocks fm_step2.hip builds) for what that defers
 //   fmw_sampled_get_kernel / fmw_raw_get_kernel   Interval::occ over a SampledSuffixArray / a raw one (suffix_array.rs:
 //                       134-184) with 64-bit samples
-// Narrow indexes (n < 2^32 - 1) never come here: their kernels, layouts and speed are those of rounds 1-4.  What is NOT
-// offered on a wide index (BG_ERR_UNSUPPORTED, stated in biogpu.h): the 2-bit packed pattern entry points and the 2-step
-// rank blocks (speed, not function: the byte entry points answer the same queries), seed-and-extend, the FMD-index
-// kernels (their interval records are uint32 in the C ABI), and alphabets that need rank bit vectors.
+// Narrow indexes (n < 2^32 - 1) never come here: their kernels, layouts and speed are those of rounds 1-4.  A wide
+// index takes packed patterns, 2-step rank blocks, seed-and-extend and the FMD-index kernels (fmd_smems.hip,
+// through the entry points with 64-bit records).  What is NOT offered on one (BG_ERR_UNSUPPORTED): alphabets that need
+// rank bit vectors, the FMD entry points with 32-bit records, and the counted search (bg_fm_backward_search_count_lines_dev).
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -105,130 +107,13 @@ __device__ __forceinline__ uint64_t wide_rank(const FmWideDev& fm, const uint4 v
     return fm.sb[(blk >> fm.sb_shift) * 4 + code] + (uint64_t)quad_sum(block_part(v, t, o, code));
 }
 
-// K5 on 64-bit positions: FMIndexable::backward_search (fmindex.rs:144-208).  A quad of four lanes per query; both ranks of a
-// step are issued together, one line when they fall into the same block.
-__global__ __launch_bounds__(256) void fmw_search_kernel(FmWideDev fm, uint64_t n_q, const uint8_t* __restrict__ pat,
-                                                         const uint64_t* __restrict__ pat_off, uint8_t* __restrict__ tag,
-                                                         uint64_t* __restrict__ lower, uint64_t* __restrict__ upper,
-                                                         uint32_t* __restrict__ matched_len) {
-    __shared__ uint16_t s_class[256];
-    __shared__ uint64_t s_less[256];
-    __shared__ uint64_t s_exc[kWideMaxExc];
-    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
-        s_class[i] = fm.sym_class[i];
-        s_less[i] = fm.less[i];
-    }
-    for (uint32_t i = threadIdx.x; i < fm.n_exc; i += blockDim.x) s_exc[i] = fm.exc_pos[i];
-    __syncthreads();
-    const uint32_t t = threadIdx.x & 3;
-    const uint64_t n_quads = (uint64_t)gridDim.x * (blockDim.x >> 2);
-    uint64_t q = (uint64_t)blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);
-    bool active = false;
-    uint64_t off = 0, l = 0, r = 0;
-    uint32_t len = 0, pos = 0, matched = 0, a_next = 0;
-    auto emit = [&](uint32_t tg, uint64_t lo, uint64_t hi, uint32_t ml) {
-        if (t == 0) {
-            tag[q] = (uint8_t)tg;
-            lower[q] = lo;
-            upper[q] = hi;
-            matched_len[q] = ml;
-        }
-    };
-    auto fetch = [&]() {  // the next non-empty query; empty patterns are Absent at once (fmindex.rs:185-207)
-        active = false;
-        while (q < n_q) {
-            off = pat_off[q];
-            len = (uint32_t)(pat_off[q + 1] - off);
-            if (len) {
-                pos = len;
-                l = 0;
-                r = fm.n - 1;  // fmindex.rs:148
-                matched = 0;
-                a_next = pat[off + pos - 1];
-                active = true;
-                return;
-            }
-            emit(BG_FM_ABSENT, 0, 0, 0);
-            q += n_quads;
-        }
-    };
-    fetch();
-    while (__any(active)) {
-        if (active) {
-            // one iteration of the loop at fmindex.rs:160-182
-            const uint32_t a = a_next;
-            pos -= 1;
-            if (pos) a_next = pat[off + pos - 1];  // (address independent of the ranks)
-            const uint32_t cls = s_class[a];
-            const uint64_t less_a = s_less[a];
-            uint64_t occ_r = 0, occ_l = 0;
-            bool stop = false;
-            uint32_t stop_tag = BG_FM_PARTIAL;
-            if (cls == kClsPanic) {
-                stop = true;
-                stop_tag = BG_FM_PANIC;
-            } else if (cls < 4) {
-                const uint64_t br = r / kSymPerBlock;
-                const uint32_t orr = (uint32_t)(r - br * kSymPerBlock);
-                const uint4 vr = fm.blocks[br * 4 + t];
-                uint4 vl = vr;
-                uint64_t bl = br;
-                uint32_t ol = 0;
-                if (l > 0) {
-                    bl = (l - 1) / kSymPerBlock;
-                    ol = (uint32_t)((l - 1) - bl * kSymPerBlock);
-                    if (bl != br) vl = fm.blocks[bl * 4 + t];
-                }
-                occ_r = wide_rank(fm, vr, t, br, orr, cls);
-                if (l > 0) occ_l = wide_rank(fm, vl, t, bl, ol, cls);
-                if (cls == 0 && fm.n_exc) {  // sparse exceptions sit in the stream as code 0
-                    occ_r -= count_le64(s_exc, 0u, fm.n_exc, r);
-                    if (l > 0) occ_l -= count_le64(s_exc, 0u, fm.n_exc, l - 1);
-                }
-            } else if (cls >= kClsSparse) {  // (no dense symbols on a wide index)
-                const uint32_t e = cls - kClsSparse;
-                const uint32_t lo = fm.sparse_off[e], hi = fm.sparse_off[e + 1];
-                occ_r = count_le64(fm.exc_sym_pos, lo, hi, r) - lo;
-                if (l > 0) occ_l = count_le64(fm.exc_sym_pos, lo, hi, l - 1) - lo;
-            }  // kClsZero: both stay 0
-            const uint64_t pl = l, pr = r;
-            if (!stop) {
-                if (occ_r == 0) {  // fmindex.rs:167-170
-                    stop = true;
-                } else {
-                    l = less_a + occ_l;  // fmindex.rs:171
-                    r = less_a + occ_r - 1;
-                    if (l > r)  // fmindex.rs:177-180
-                        stop = true;
-                    else
-                        matched += 1;
-                }
-            }
-            if (stop) {
-                if (stop_tag == BG_FM_PANIC)
-                    emit(BG_FM_PANIC, 0, 0, matched);
-                else if (matched)
-                    emit(BG_FM_PARTIAL, pl, pr + 1, matched);
-                else
-                    emit(BG_FM_ABSENT, 0, 0, 0);
-                q += n_quads;
-                fetch();
-            } else if (pos == 0) {
-                emit(BG_FM_COMPLETE, l, r + 1, matched);
-                q += n_quads;
-                fetch();
-            }
-        }
-    }
-}
-
-// The same search with TWO queries per quad (round 5; what fm_search_fast2x_kernel is to the narrow index, fm_index.hip):
-// a step is one dependent block access, eight wavefronts per SIMD are all the hardware holds, and the parallelism left to
-// add is a second independent query inside the wavefront.  Phase A reads both streams' symbols and classes and issues
-// their block loads and superblock bases — unconditional, in one basic block (a stream without a coded symbol reads
-// block 0; the line of l - 1 is requested even where it is the line of r) — phase B ranks and updates both.  Stream
-// (quad, u) takes queries (2 quad + u) + k * 2 quads.  bg_fm_set_option("ilp", 1): the kernel above.  On the 4.4 G-symbol
-// index: 302 -> 404 M queries/s (profiles/r05_fm_wide_4g4.json), same arrays.
+// K5 on 64-bit positions: FMIndexable::backward_search (fmindex.rs:144-208) with TWO queries per quad (round 5; what
+// fm_search_fast2x_kernel is to the narrow index, fm_index.hip): a step is one dependent block access, eight wavefronts per
+// SIMD are all the hardware holds, and the parallelism left to add is a second independent query inside the wavefront.
+// Phase A reads both streams' symbols and classes and issues their block loads and superblock bases — unconditional, in one
+// basic block (a stream without a coded symbol reads block 0; the line of l - 1 is requested even where it is the line of
+// r) — phase B ranks and updates both.  Stream (quad, u) takes queries (2 quad + u) + k * 2 quads.  On the 4.4 G-symbol
+// index: 302 M queries/s with one query per quad, 404 M with two (profiles/r05_fm_wide_4g4.json), same arrays.
 // Round 6: the flavours the narrow generic kernel has — SEEDS (the seed windows of a batch of reads: query q is seed q % S of
 // read q / S, fm_kernels.h SeedSrc), PACKED (`pat` is a 2-bit stream in the index's codes, offsets in symbols: the class of a
 // symbol is its code) and DEFER (only the queries the 2x fast kernel in front left tagged kTagDeferred).
@@ -685,10 +570,9 @@ int fm_wide_build_dev(bg_ctx* ctx, const uint8_t* d_bwt, uint64_t n, const uint8
     return BG_OK;
 }
 
-namespace {
 template <bool SEEDS, bool PACKED, bool DEFER>
-int launch_2x(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower, uint64_t* d_upper,
-              uint32_t* d_matched_len, const SeedSrc& src, hipStream_t st) {
+int fm_wide_search_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
+                          uint64_t* d_upper, uint32_t* d_matched_len, const SeedSrc& src, hipStream_t st) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fmw_search2x_kernel<SEEDS, PACKED, DEFER>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
     const uint64_t blocks = std::min<uint64_t>((n_q + 127) / 128, 256ull * (uint64_t)per_cu);
@@ -697,34 +581,17 @@ int launch_2x(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_p
     BG_HIP(hipGetLastError());
     return BG_OK;
 }
-}  // namespace
-
-// Which kernel answers a search on 64-bit positions:
-//   * the index has 2-step blocks (a DNA-like text with at most a handful of positions outside its four letters — T$R$ of a
-//     genome without N) and neither "no_step2", "no_fast" nor "ilp" = 1 is set: fm_search_fast2x_kernel<WIDE> (fm_index.hip),
-//     then this file's generic kernel for the queries it deferred (a byte outside the codes, more than 256 symbols);
-//   * otherwise the generic kernels here: two queries per quad (every flavour), or one ("ilp" = 1, byte patterns).
-int fm_wide_search_dev(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,
-                       uint64_t* d_upper, uint32_t* d_matched_len, hipStream_t st, const SeedSrc* seeds, bool packed) {
-    SeedSrc src{};
-    if (seeds) src = *seeds;
-    src.code_bytes = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 | (uint32_t)fm->code_byte[3] << 24;
-    const bool fast = fm->wdev2.blocks2 && !fm->no_step2 && !fm->no_fast && fm->ilp >= 2 && fm->n_codes == 4 && (!seeds || seeds->seed_len <= kFastSyms);
-    int rc;
-    if (fast) {
-        if ((rc = fm_wide_fast2x_launch(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, st, seeds, packed))) return rc;
-        if (seeds) return launch_2x<true, false, true>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-        if (packed) return launch_2x<false, true, true>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-        return launch_2x<false, false, true>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-    }
-    if (seeds) return launch_2x<true, false, false>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-    if (packed) return launch_2x<false, true, false>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-    if (fm->ilp >= 2) return launch_2x<false, false, false>(fm, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len, src, st);
-    const uint64_t blocks = std::min<uint64_t>((n_q + 63) / 64, 256 * 8);
-    fmw_search_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->wdev, n_q, d_pat, d_pat_off, d_tag, d_lower, d_upper, d_matched_len);
-    BG_HIP(hipGetLastError());
-    return BG_OK;
-}
+// the flavours fm_search (fm_index.hip) launches
+#define FMW_SEARCH_LAUNCH(SEEDS, PACKED, DEFER)                                                                                       \
+    template int fm_wide_search_launch<SEEDS, PACKED, DEFER>(bg_fm*, uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint64_t*, \
+                                                             uint64_t*, uint32_t*, const SeedSrc&, hipStream_t);
+FMW_SEARCH_LAUNCH(false, false, false)
+FMW_SEARCH_LAUNCH(false, false, true)
+FMW_SEARCH_LAUNCH(true, false, false)
+FMW_SEARCH_LAUNCH(true, false, true)
+FMW_SEARCH_LAUNCH(false, true, false)
+FMW_SEARCH_LAUNCH(false, true, true)
+#undef FMW_SEARCH_LAUNCH
 
 int fm_wide_sa_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st) {
     if (n == 0) return BG_OK;

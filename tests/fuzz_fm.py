@@ -8,7 +8,7 @@ Round 3 (final K5: wave-cooperative fetch, straight-line step): seeds 31 and 32,
 configurations, 993 311 of them also as packed streams, 0 mismatches.
 Round 3, final: seed 74: 3 790 678 queries (922 101 also packed), 0 mismatches.
 Round 6: `python tests/fuzz_fm.py SEED SECONDS wide` — every index on the 64-bit layout (ctx option fm_wide_from = 1, a random
-fm_wide_sb_shift so that short texts span many superblocks): fmw_search_kernel (ilp 1), fmw_search2x_kernel (ilp 2), the
+fm_wide_sb_shift so that short texts span many superblocks): fmw_search2x_kernel, the
 2-step blocks on 64-bit positions with byte and packed patterns (where the text has them), single steps (no_step2), and
 Interval::occ through 64-bit samples against the suffix array's rows."""
 import os
@@ -109,15 +109,8 @@ while time.time() - t0 < budget and n_fail == 0:
     variants["generic"] = search(fm, d_pat, d_off, n_q)
     fm.set_option("no_fast", 0)
     if WIDE:
-        fm.set_option("ilp", 1)
-        variants["wide_ilp1"] = search(fm, d_pat, d_off, n_q)
-        fm.set_option("no_fast", 1)
-        variants["wide_generic_ilp1"] = search(fm, d_pat, d_off, n_q)
-        fm.set_option("no_fast", 0)
         fm.set_option("no_step2", 1)
-        variants["wide_ilp1_single_steps"] = search(fm, d_pat, d_off, n_q)
-        fm.set_option("ilp", 2)
-        variants["wide_ilp2_single_steps"] = search(fm, d_pat, d_off, n_q)
+        variants["wide_single_steps"] = search(fm, d_pat, d_off, n_q)
         fm.set_option("no_step2", 0)
         # Interval::occ through 64-bit samples (fmw_sampled_get_kernel) / the raw array against the suffix array's rows
         from rust_bio_amd.suffix_array import RawSuffixArray, SampledSuffixArray

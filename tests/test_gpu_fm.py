@@ -120,36 +120,6 @@ def test_genome_1m_sample_bit_exact():
             assert bytes(g[s:s + len(p)]) == p
 
 
-def test_jump_table_does_not_change_results():
-    """K5's table of the search state after the last 12 symbols (built by the search itself) against the
-    plain LF loop: patterns shorter than, equal to and longer than 12, with N's, partial and absent ones."""
-    g = synth.genome(300_000, 9)
-    sa, b, ls, fm = build(g, b"ACGTNacgtn", 64)
-    rng = np.random.default_rng(2)
-    pats = []
-    gb = g.tobytes()
-    for _ in range(30_000):
-        ln = int(rng.integers(1, 40))
-        s = int(rng.integers(0, len(gb) - 50))
-        p = bytearray(gb[s:s + ln])
-        r = rng.random()
-        if r < 0.3:
-            p[int(rng.integers(0, ln))] = b"ACGT"[int(rng.integers(0, 4))]
-        elif r < 0.35:
-            p[int(rng.integers(0, ln))] = ord("N")
-        elif r < 0.4:
-            p = bytearray(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=ln)].tobytes())
-        pats.append(bytes(p))
-    buf, off = _lib.concat(pats)
-    fm.set_option("jump_min_queries", -1)
-    plain = fm.backward_search_arrays(buf, off)
-    fm.set_option("jump_min_queries", 0)
-    fast = fm.backward_search_arrays(buf, off)
-    assert fm.device_bytes() > 200_000_000  # the table exists
-    for a_, b_ in zip(plain, fast):
-        assert (a_ == b_).all()
-
-
 def test_one_index_searched_from_several_threads():
     """`bg_fm` is immutable after construction: bg_fm_backward_search_batch_dev uses no shared scratch, so several host
     threads may search one handle at once, each on its own stream (include/biogpu.h, "Streams and threads")."""
@@ -306,24 +276,19 @@ def test_two_step_rank_blocks_equal_single_steps_and_the_oracle(text_kind):
     d_off = torch.from_numpy(off.astype(np.int64)).to("cuda:0")
     n_q = len(pats)
 
-    def run(no_step2, ilp=1):
+    def run(no_step2):
         fm.set_option("no_step2", no_step2)
-        fm.set_option("ilp", ilp)
         tag = torch.full((n_q,), 77, dtype=torch.uint8, device="cuda:0")
         lo, hi = torch.zeros(n_q, dtype=torch.int64, device="cuda:0"), torch.zeros(n_q, dtype=torch.int64, device="cuda:0")
         ml = torch.zeros(n_q, dtype=torch.int32, device="cuda:0")
         fm.backward_search_dev(n_q, d_pat.data_ptr(), d_off.data_ptr(), tag.data_ptr(), lo.data_ptr(), hi.data_ptr(), ml.data_ptr())
         torch.cuda.synchronize()
         fm.set_option("no_step2", 0)
-        fm.set_option("ilp", 2)
         return tag.cpu().numpy(), lo.cpu().numpy(), hi.cpu().numpy(), ml.cpu().numpy()
 
-    two, one = run(0), run(1)
+    two, one = run(0), run(1)  # fm_search_fast2x_kernel (the default) / fm_search_fast_kernel
     for a, c in zip(two, one):
         assert (a == c).all()
-    for ilp in (2,):  # two queries per quad (fm_search_fast2x_kernel; the default)
-        for a, e in zip(two, run(0, ilp=ilp)):
-            assert (a == e).all(), ilp
     otag, olo, ohi, oml = orc.backward_search_batch(b, ls, orc.Occ(b, 64, alpha), pat, off, threads=8)
     tag, lo, hi, ml = two
     assert (tag == otag).all() and (lo == olo.astype(np.int64)).all() and (hi == ohi.astype(np.int64)).all()

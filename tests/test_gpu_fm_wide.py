@@ -71,12 +71,12 @@ def check_search(fm, b, ls, alphabet, pats):
     torch.cuda.synchronize()
     assert (d_tag.cpu().numpy() == otag).all()
     assert (d_lo.cpu().numpy().astype(np.uint64)[ok] == olo[ok]).all() and (d_hi.cpu().numpy().astype(np.uint64)[ok] == ohi[ok]).all()
-    # ... which runs two queries per quad by default (fmw_search2x_kernel): the one-query kernel answers the same
-    fm.set_option("ilp", 1)
+    # ... and the generic kernel alone (fmw_search2x_kernel, with 2-step blocks otherwise behind the fast kernel) the same
+    fm.set_option("no_fast", 1)
     d_tag1, d_lo1, d_hi1, d_ml1 = torch.zeros_like(d_tag), torch.zeros_like(d_lo), torch.zeros_like(d_hi), torch.zeros_like(d_ml)
     fm.backward_search_dev(nq, d_pat.data_ptr(), d_off.data_ptr(), d_tag1.data_ptr(), d_lo1.data_ptr(), d_hi1.data_ptr(), d_ml1.data_ptr())
     torch.cuda.synchronize()
-    fm.set_option("ilp", 2)
+    fm.set_option("no_fast", 0)
     assert torch.equal(d_tag, d_tag1) and torch.equal(d_ml, d_ml1)
     okd = torch.from_numpy(ok).to(DEV)
     assert torch.equal(d_lo[okd], d_lo1[okd]) and torch.equal(d_hi[okd], d_hi1[okd])
@@ -153,7 +153,7 @@ def test_wide_two_step_blocks_packed_patterns_and_seeds(sb_shift):
     fm = FMIndex(b, ls, Occ(b, 3, N_ALPHABET), ctx=ctx)
     assert fm.step2_bytes() > 0
     pats = patterns(text, rng, 6000, foreign=b"X") + [text[100:500].tobytes(), text[7:7 + 256].tobytes(), text[9:9 + 257].tobytes()]
-    tag, lo, hi = check_search(fm, b, ls, N_ALPHABET, pats)  # (also compares ilp 2 with ilp 1 = the generic kernel)
+    tag, lo, hi = check_search(fm, b, ls, N_ALPHABET, pats)  # (also compares the fast kernel with the generic one alone)
     assert (tag == 0).sum() > 1000 and (tag == 1).sum() > 400
     fm.set_option("no_step2", 1)
     assert fm.step2_bytes() == 0
