@@ -85,8 +85,8 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
 /* Tunables (0 keeps the default) and the switches the tests use to reach every kernel variant:
  *   chunk_pairs        pairs per sub-batch of bg_align_batch_dev (default 2^20) and of the banded pipeline (16384)
  *   host_chunk_pairs   pairs per stage of bg_align_batch's pipelined host path (122880)
- *   seed_chunk_reads   reads per pass of bg_seed_extend[_strands]_batch[_dev] (0: equal passes of at most 2^21 reads,
- *                      2^20 with both strands)
+ *   seed_chunk_reads   reads per pass of bg_seed_extend[_strands|_pairs]_batch[_dev] (0: equal passes of at most 2^21
+ *                      reads, 2^20 with both strands and with pairs; pairs round it down to an even count, at least 2)
  *   force_wide = 1     scores kept as plain int32 even where they fit the 24-bit keys of the fast kernels
  *   no_pk16 = 1        no packed-int16 fill (K1p): the int32 kernel K1 runs for every batch
  *   no_couples = 1     K1p without the (m, n) slot order on ragged batches
@@ -532,6 +532,44 @@ int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg
                                      uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
                                      uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
                                      uint64_t ops_stride, uint64_t* totals, void* stream);
+/* Read pairs.  Paired-end reads come as two mates per DNA fragment, read towards each other from opposite strands.  The
+ * reads are interleaved mates: read 2p is mate 1 of pair p, read 2p + 1 its mate 2 (2 n_pairs + 1 offsets; an interleaved
+ * FASTQ parsed by bg_fastq_parse[_dev] gives this layout).
+ *   candidates       each mate is mapped on both strands exactly as bg_seed_extend_strands_batch with BG_STRAND_BOTH maps a
+ *                    read; a candidate's ref_start / ref_end are forward-text coordinates; the candidates of one (mate,
+ *                    strand) are numbered in ascending proposed start;
+ *   proper           a candidate a of one mate on the forward strand with a candidate b of the other mate on the reverse
+ *                    strand — orientation A: m1 forward, m2 reverse; orientation B: m2 forward, m1 reverse — with
+ *                    a.ref_start <= b.ref_start and min_span <= span <= max_span, span = max(a.ref_end, b.ref_end) -
+ *                    a.ref_start (FR only: RF, FF and RR are never proper);
+ *   best proper      the highest a.score + b.score (64-bit); on a tie orientation A, then the smaller candidate index of the
+ *                    forward mate, then that of the reverse mate;
+ *   paired or not    best1, best2: each mate's own best under the strands rule.  If a proper combination exists and
+ *                    pair_sum + pen_unpaired >= best1 + best2, the pair is proper: hits[2p], hits[2p + 1] are that
+ *                    combination's two candidates (operations and strands with them).  Otherwise each mate reports exactly
+ *                    what bg_seed_extend_strands_batch reports for it (BG_HIT_NONE included) and the pair is not proper.
+ * n_candidates, n_seed_hits and totals mean what they mean in the strands call, per mate.  strand[r] (optional): BG_HIT_*
+ * of each reported hit.  Operation slots, ops_stride, host compaction, the out-of-alphabet rule and every limit are those of
+ * the strands call.  BG_ERR_INVALID_ARG: min_span > max_span, pen_unpaired < 0, a null pairs, a null hits with n_pairs > 0.
+ * A pass never splits a pair: seed_chunk_reads counts the caller's reads, rounded down to an even count (at least 2). */
+typedef struct {
+    uint32_t min_span, max_span; /* a proper pair's span (SAM |TLEN|), both inclusive */
+    int32_t  pen_unpaired;       /* >= 0; the score a proper pair may give up against the two mates' own bests */
+} bg_pair_params_t;
+typedef struct {
+    uint64_t span;      /* of the reported proper pair; 0 when not proper */
+    uint32_t n_proper;  /* proper combinations among the pair's candidates, both orientations */
+    uint8_t  proper;    /* 1: hits[2p], hits[2p + 1] are the chosen proper pair */
+    uint8_t  reserved[3];
+} bg_pair_hit_t;        /* 16 bytes */
+int bg_seed_extend_pairs_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                               uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                               uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour (operation slots of the 2 n_pairs reads, totals and passes as bg_seed_extend_strands_batch_dev). */
+int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                   uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                   bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_ops,
+                                   uint64_t ops_stride, uint64_t* totals, void* stream);
 /* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
  * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
 int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);

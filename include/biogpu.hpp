@@ -685,6 +685,57 @@ public:
         }
         return res;
     }
+    // Read pairs (bg_seed_extend_pairs_batch): reads[2p], reads[2p + 1] are the two mates of pair p.  Each mate is mapped on both
+    // strands; where the best proper FR combination (span in min_span ..= max_span) gives up at most pen_unpaired of score
+    // against the mates' own bests, both mates report it and `proper` is set; otherwise each mate reports its strands-call hit.
+    struct PairedSeedHit {
+        StrandedSeedHit mate[2];
+        bool proper = false;
+        uint64_t span = 0;      // of the proper pair (SAM |TLEN|); 0 when not proper
+        uint32_t n_proper = 0;  // proper combinations among the pair's candidates
+    };
+    std::vector<PairedSeedHit> seed_extend_batch_pairs(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                       uint32_t min_span = 0, uint32_t max_span = 1000, int32_t pen_unpaired = 17,
+                                                       uint32_t seed_len = 20, uint32_t stride = 10, uint32_t max_occ = 16,
+                                                       uint32_t pad = 25) const {
+        if (reads.size() % 2) throw std::invalid_argument("seed_extend_batch_pairs: an odd number of reads (mates come in pairs)");
+        std::vector<int32_t> table;
+        const bg_scoring_t sc = scoring.to_c(table);
+        const bg_seed_params_t prm = {seed_len, stride, max_occ, pad};
+        const bg_pair_params_t pp = {min_span, max_span, pen_unpaired};
+        Text buf;
+        std::vector<uint64_t> off{0};
+        for (auto& r : reads) {
+            buf.insert(buf.end(), r.begin(), r.end());
+            off.push_back(buf.size());
+        }
+        const size_t n_pairs = reads.size() / 2;
+        std::vector<bg_seed_hit_t> hits(reads.size());
+        std::vector<uint8_t> strand(reads.size());
+        std::vector<bg_pair_hit_t> pairs(std::max<size_t>(n_pairs, 1));
+        std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4) * reads.size() + 8);
+        uint64_t used = 0;
+        const int rc = bg_seed_extend_pairs_batch(h_, &sc, &prm, &pp, n_pairs, buf.data(), off.data(), hits.data(), strand.data(),
+                                                  pairs.data(), ops.data(), ops.size(), &used);
+        if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
+        check(rc, "bg_seed_extend_pairs_batch");
+        std::vector<PairedSeedHit> res(n_pairs);
+        for (size_t p = 0; p < n_pairs; p++) {
+            for (int m = 0; m < 2; m++) {
+                const bg_seed_hit_t& h = hits[2 * p + m];
+                StrandedSeedHit& o = res[p].mate[m];
+                if (h.aln.score != BG_MIN_SCORE) o.alignment = alignment::pairwise::detail::to_alignment(h.aln, ops.data());
+                o.ref_start = (size_t)h.ref_start;
+                o.ref_end = (size_t)h.ref_end;
+                o.n_candidates = h.n_candidates;
+                o.reverse = strand[2 * p + m] == BG_HIT_REVERSE;
+            }
+            res[p].proper = pairs[p].proper != 0;
+            res[p].span = pairs[p].span;
+            res[p].n_proper = pairs[p].n_proper;
+        }
+        return res;
+    }
     bg_fm* raw() const { return h_; }
     size_t len() const { return n_; }
 

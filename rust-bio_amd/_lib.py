@@ -82,6 +82,17 @@ class SeedParamsC(C.Structure):
     _fields_ = [("seed_len", C.c_uint32), ("stride", C.c_uint32), ("max_occ", C.c_uint32), ("pad", C.c_uint32)]
 
 
+# bg_pair_params_t (bg_seed_extend_pairs_batch[_dev])
+class PAIR_PARAMS(C.Structure):
+    _fields_ = [("min_span", C.c_uint32), ("max_span", C.c_uint32), ("pen_unpaired", C.c_int32)]
+
+
+assert C.sizeof(PAIR_PARAMS) == 12, C.sizeof(PAIR_PARAMS)
+# bg_pair_hit_t
+PAIR_HIT_DTYPE = np.dtype([("span", "<u8"), ("n_proper", "<u4"), ("proper", "u1"), ("reserved", "u1", (3,))])
+assert PAIR_HIT_DTYPE.itemsize == 16, PAIR_HIT_DTYPE.itemsize
+
+
 # bg_fastq_record_t
 FQREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"),
                         ("id_len", "<u4"), ("desc_len", "<u4"), ("seq_len", "<u4"), ("qual_len", "<u4"),
@@ -99,6 +110,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_pack2_host",
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
+           "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
@@ -213,6 +225,10 @@ def lib():
                                                    C.POINTER(u64)]
         L.bg_seed_extend_strands_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u32, u64, vp, vp, u32, vp, vp,
                                                        vp, u64, vp, vp]
+        L.bg_seed_extend_pairs_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp, vp,
+                                                 vp, vp, vp, u64, C.POINTER(u64)]
+        L.bg_seed_extend_pairs_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp,
+                                                     u32, vp, vp, vp, vp, u64, vp, vp]
         L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]

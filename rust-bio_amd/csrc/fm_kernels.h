@@ -335,5 +335,11 @@ void fm_build_step2(bg_fm* fm, hipStream_t st);
 int bg_fm_search_seeds_dev(bg_fm* fm, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t S,
                            uint32_t stride, uint32_t seed_len, uint8_t* d_tag, uint64_t* d_lower, uint64_t* d_upper,
                            uint32_t* d_matched_len, hipStream_t st);
+// seed_pairs.hip: S7 of bg_seed_extend_pairs_batch_dev over one pass (n_pairs pairs from caller read r0 on), on the pass
+// scratch of seed_extend.hip (candidate offsets of the 4 n_pairs virtual reads, their alignments, operations, windows).
+// max_cand bounds the candidates of one virtual read.
+int bg_seed_pairs_launch(const bg_pair_params_t* pp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff, const uint32_t* d_n_hits,
+                         const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits,
+                         uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint32_t max_cand, hipStream_t st);
 
 #endif

@@ -21,6 +21,8 @@
 //   S5 gather           (read, text window) pairs, offsets                              -> x, x_off, y, y_off
 //   S6 align            Aligner::semiglobal on every candidate (bg_align_batch_dev)      -> records + operations
 //   S7 best             per read: highest score, smallest start among equals           -> bg_seed_hit_t + its ops
+//      (pair mode, bg_seed_extend_pairs_batch[_dev]: per pair of interleaved mates, the best proper FR combination of their
+//       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t)
 #include <algorithm>
 
 #include "fm_kernels.h"
@@ -379,9 +381,12 @@ namespace {
 // reads as they are, G = 1, no strand array (bg_seed_extend_batch_dev).  BG_STRAND_FORWARD: the same, with the strand array.
 // BG_STRAND_REVERSE: G = 1 on the revcomps, BG_STRAND_BOTH: G = 2 on read and revcomp, materialised per pass by
 // se_strands_kernel.  Stages S1-S6 run unchanged on the virtual reads; S7 picks each caller read's best over its G.
+// Pair mode (`pair` set, strands = BG_STRAND_BOTH, n_reads = 2 n_pairs interleaved mates): passes hold whole pairs and
+// se_pair_kernel replaces S7, writing d_pairs as well.
 int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
            const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
-           uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream) {
+           uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
+           bg_pair_hit_t* d_pairs = nullptr) {
     if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
     if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
     if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
@@ -415,10 +420,11 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
     // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size — 1.25 M reads went as 2^20 + 0.2 M until
     //  round 6: two host round trips and a set of under-filled launches for a sixth of the reads).  The option counts the
-    //  caller's reads.
-    const uint64_t chunk_cap = ctx->seed_chunk_reads > 0 ? (uint64_t)ctx->seed_chunk_reads : (1u << 21) / G;
-    const uint64_t n_pass = (n_reads + chunk_cap - 1) / chunk_cap;
-    const uint64_t chunk = ctx->seed_chunk_reads > 0 ? chunk_cap : (n_reads + n_pass - 1) / n_pass;
+    //  caller's reads; in pair mode it is rounded down to whole pairs (at least one), and so are the equal passes.
+    const uint64_t unit = pair ? 2 : 1, n_units = n_reads / unit;
+    const uint64_t chunk_cap = std::max<uint64_t>(ctx->seed_chunk_reads > 0 ? (uint64_t)ctx->seed_chunk_reads / unit : (1u << 21) / G / unit, 1);
+    const uint64_t n_pass = (n_units + chunk_cap - 1) / chunk_cap;
+    const uint64_t chunk = unit * (ctx->seed_chunk_reads > 0 ? chunk_cap : (n_units + n_pass - 1) / n_pass);
     for (uint64_t r0 = 0; r0 < n_reads; r0 += chunk) {
         const uint64_t nr = std::min(chunk, n_reads - r0);
         const uint64_t nv = G * nr;  // virtual reads of this pass
@@ -510,9 +516,13 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
         if (C && (rc = bg_align_batch_dev_hint(ctx, sc, BG_MODE_SEMIGLOBAL, C, d_x, d_cxoff, d_y, d_cyoff, max_read_len, win_max, d_aln,
                                                d_cops, cstride, st, -1)))
             return rc;
-        // ---- S7: best hit per read
+        // ---- S7: best hit per read (pair mode: per pair)
         const dim3 best_grid((unsigned)((nr * 16 + 255) / 256));
-        if (G == 2)
+        if (pair) {
+            if ((rc = bg_seed_pairs_launch(pair, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_pairs,
+                                           kMaxProposals, st)))
+                return rc;
+        } else if (G == 2)
             se_best_kernel<2><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
                                                                d_strand, 0);
         else
@@ -548,6 +558,26 @@ extern "C" int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* s
     return se_run(fm, sc, prm, strands, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals, stream);
 }
 
+namespace {
+
+// the pair calls' own argument checks; every other one is se_run's
+int pair_args(const bg_pair_params_t* pp, const void* pairs, uint64_t n_pairs, const void* hits) {
+    if (!pp || !pairs || pp->min_span > pp->max_span || pp->pen_unpaired < 0 || (n_pairs && !hits) || n_pairs > (UINT64_MAX >> 2))
+        return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                              uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                              bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_ops,
+                                              uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
+    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
+                  stream, pp, d_pairs);
+}
+
 extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream) {
     if (!ctx || (n && (!d_in || !d_off || !d_out))) return BG_ERR_INVALID_ARG;
     if (n == 0) return BG_OK;
@@ -562,7 +592,7 @@ namespace {
 // the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order
 int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
                 const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
-                uint64_t ops_cap, uint64_t* ops_used) {
+                uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr) {
     if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (n_reads == 0) return BG_OK;
@@ -577,6 +607,7 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     uint64_t* d_off = nullptr;
     uint8_t* d_strand = nullptr;
     bg_seed_hit_t* d_hits = nullptr;
+    bg_pair_hit_t* d_pairs = nullptr;
     std::vector<uint8_t> h_ops;
     int panic_rc = BG_OK;
     auto run = [&]() -> int {
@@ -586,13 +617,16 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
         BG_HIP(hipMalloc((void**)&d_hits, n_reads * sizeof(bg_seed_hit_t)));
         if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_reads * stride));
         if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_reads));
+        if (pair) BG_HIP(hipMalloc((void**)&d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t)));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-        int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st);
+        int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st,
+                        pair, d_pairs);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(hits, d_hits, n_reads * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
         if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_reads, hipMemcpyDeviceToHost, st));
+        if (pair) BG_HIP(hipMemcpyAsync(pairs, d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_reads * stride);
             BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_reads * stride, hipMemcpyDeviceToHost, st));
@@ -606,6 +640,7 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     hipFree(d_hits);
     hipFree(d_ops);
     hipFree(d_strand);
+    hipFree(d_pairs);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
     uint64_t used = 0;
@@ -639,4 +674,11 @@ extern "C" int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, c
                                             uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
     return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used);
+}
+
+extern "C" int bg_seed_extend_pairs_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                          uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                          uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
+    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs);
 }

@@ -5,7 +5,8 @@ The reference has no such function; callers compose it from `FMIndex::backward_s
 seeds vote, hit -> proposed read start, per-read dedup, window gather, best-hit reduction, the winners'
 operations — runs in HIP kernels behind the C ABI (rust-bio_amd/csrc/seed_extend.hip); its definition is in
 include/biogpu.h (the tests hold a CPU statement of it).  The `_strands` calls map each read on the forward strand, on
-the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  This module only marshals arguments."""
+the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  The `_pairs` calls map interleaved mates of
+paired-end reads and report the best proper FR pair where there is one.  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +21,17 @@ class SeedParams:
 
     def to_c(self):
         return _lib.SeedParamsC(self.seed_len, self.stride, self.max_occ, self.pad)
+
+
+class PairParams:
+    """bg_pair_params_t: a proper pair's span (SAM |TLEN|) lies in min_span ..= max_span; it may give up pen_unpaired (>= 0)
+    of score against the two mates' own bests."""
+
+    def __init__(self, min_span=0, max_span=1000, pen_unpaired=17):
+        self.min_span, self.max_span, self.pen_unpaired = min_span, max_span, pen_unpaired
+
+    def to_c(self):
+        return _lib.PAIR_PARAMS(self.min_span, self.max_span, self.pen_unpaired)
 
 
 def attach_text(fm, text=None, d_text=None):
@@ -97,6 +109,45 @@ def seed_extend_strands_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_
                                                            max_read_len, d_hits, d_strand or None, d_ops or None, ops_stride,
                                                            totals.ctypes.data if totals is not None else None, stream),
                "bg_seed_extend_strands_batch_dev")
+
+
+def seed_extend_pairs_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, want_ops=True, allow_out_of_alphabet=False):
+    """bg_seed_extend_pairs_batch, host buffers.  The reads are interleaved mates: read 2p is mate 1 of pair p, read 2p + 1 its
+    mate 2 (an even count).  Returns (hits: SEED_HIT_DTYPE[2n], strand: uint8[2n], pairs: PAIR_HIT_DTYPE[n], ops: the reported
+    hits' operations back to back).  Errors as seed_extend_arrays."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    if n % 2:
+        raise ValueError("seed_extend_pairs_arrays: an odd number of reads")
+    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n, 1), dtype=np.uint8)
+    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
+    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc, pp = scoring.to_c(), params.to_c(), pair_params.to_c()
+    rc = _lib.lib().bg_seed_extend_pairs_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), n // 2, rd.ctypes.data, off.ctypes.data,
+                                               hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
+                                               ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_pairs_batch")
+    return hits, strand[:n], pairs[:n // 2], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_pairs_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_strand=0, d_ops=0, ops_stride=0,
+                          params=None, pair_params=None, stream=0, totals=None):
+    """bg_seed_extend_pairs_batch_dev (pointers are ints; 2 n_pairs interleaved mates, d_pairs: n_pairs bg_pair_hit_t; d_strand /
+    d_ops may be 0); `totals` as seed_extend_dev, over both strands of every mate."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    sc, pc, pp = scoring.to_c(), params.to_c(), pair_params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_pairs_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), n_pairs, d_reads, d_read_off,
+                                                         max_read_len, d_hits, d_strand or None, d_pairs or None, d_ops or None,
+                                                         ops_stride, totals.ctypes.data if totals is not None else None, stream),
+               "bg_seed_extend_pairs_batch_dev")
 
 
 def revcomp_dev(n, d_in, d_off, d_out, ctx=None, stream=0):

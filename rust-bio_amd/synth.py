@@ -151,3 +151,32 @@ def fastq_text(n_reads, length, seed):
     out[:, o2:o2 + length] = rng.integers(33, 74, size=(n_reads, length), dtype=np.uint8)
     out[:, o2 + length] = 10
     return out.reshape(-1)
+
+
+_COMP = np.arange(256, dtype=np.uint8)
+_COMP[list(b"ACGT")] = list(b"TGCA")
+
+
+def read_pairs(text, n_pairs, length, seed, min_frag=300, max_frag=500, sub=0.05, ins=0.01, dele=0.01, chunk=1 << 16):
+    """Paired-end reads of `length` bases from fragments of the genome (`text` ends in '$'; ACGT).  Per pair: a fragment of
+    SplitMix64 length in [min_frag, max_frag] at a SplitMix64 start; mate 1 is its first `length` bases, mate 2 the reverse
+    complement of its last `length` bases; in a seeded half of the pairs the two are swapped.  Each read is then mutated
+    like the cfg 5 reads (mutate_fixed, the bench's model), `chunk` reads per mutation seed.  Reads are interleaved (read 2p,
+    2p + 1 = pair p).  Returns (reads uint8[2 n_pairs * length], origin int64[2 n_pairs]: forward-text start of each read's
+    source, rev bool[2 n_pairs]: the read is from the reverse strand)."""
+    n = len(text) - 1
+    frag = min_frag + (splitmix64(seed, n_pairs) >> np.uint64(1)) % np.uint64(max_frag - min_frag + 1)
+    start = (splitmix64(seed ^ 0x2545F491, n_pairs) >> np.uint64(1)) % (np.uint64(n + 1) - frag)
+    swap = (splitmix64(seed ^ 0x6C8E9CF5, n_pairs) >> np.uint64(63)).astype(bool)
+    frag, start = frag.astype(np.int64), start.astype(np.int64)
+    org = np.stack([start, start + frag - length], axis=1)
+    rev = np.zeros((n_pairs, 2), dtype=bool)
+    rev[:, 1] = True
+    org[swap] = org[swap][:, ::-1]
+    rev[swap] = rev[swap][:, ::-1]
+    org, rev = org.reshape(-1), rev.reshape(-1)
+    refs = np.asarray(text)[org[:, None] + np.arange(length)[None, :]]
+    refs[rev] = _COMP[refs[rev][:, ::-1]]
+    out = [mutate_fixed(refs[c0:c0 + chunk], seed + 1000003 + 7919 * (c0 // chunk), sub, ins, dele)[0].reshape(-1)
+           for c0 in range(0, 2 * n_pairs, chunk)]
+    return (np.concatenate(out) if out else np.zeros(0, np.uint8)), org, rev

@@ -190,3 +190,29 @@ def protein_pairs(n_pairs, length, seed, device, sub=0.15, chunk=1 << 16):
         ys.append(aa[y].reshape(-1))
     off = torch.arange(n_pairs + 1, dtype=torch.int64, device=device) * length
     return torch.cat(xs), off, torch.cat(ys), off.clone()
+
+
+def read_pairs_from_genome(text, n_pairs, length, seed, min_frag=300, max_frag=500, sub=0.05, ins=0.01, dele=0.01, chunk=1 << 16):
+    """Mirror of synth.read_pairs on a uint8 device tensor ending in '$' (the same draws, the same reads).  Returns (reads
+    uint8[2 n_pairs * length], origin int64[2 n_pairs], rev bool[2 n_pairs]) on the device."""
+    dev = text.device
+    n = text.numel() - 1
+    frag = min_frag + _lsr(splitmix64(seed, n_pairs, dev), 1) % (max_frag - min_frag + 1)
+    start = _lsr(splitmix64(seed ^ 0x2545F491, n_pairs, dev), 1) % (n + 1 - frag)
+    swap = _lsr(splitmix64(seed ^ 0x6C8E9CF5, n_pairs, dev), 63).to(torch.bool)
+    org = torch.stack([start, start + frag - length], dim=1)
+    rev = torch.zeros((n_pairs, 2), dtype=torch.bool, device=dev)
+    rev[:, 1] = True
+    org = torch.where(swap[:, None], org.flip(1), org).reshape(-1)
+    rev = torch.where(swap[:, None], rev.flip(1), rev).reshape(-1)
+    comp = torch.arange(256, dtype=torch.uint8, device=dev)
+    comp[torch.tensor(list(b"ACGT"), device=dev).long()] = torch.tensor(list(b"TGCA"), dtype=torch.uint8, device=dev)
+    ar = torch.arange(length, dtype=torch.int64, device=dev)
+    out = []
+    for c0 in range(0, 2 * n_pairs, chunk):
+        o, rv = org[c0:c0 + chunk], rev[c0:c0 + chunk]
+        refs = text[(o[:, None] + ar[None, :]).reshape(-1)].view(-1, length)
+        refs = torch.where(rv[:, None], comp[refs.flip(1).long()], refs)
+        x, _ = mutate_fixed(refs, seed + 1000003 + 7919 * (c0 // chunk), sub, ins, dele)
+        out.append(x.reshape(-1))
+    return (torch.cat(out) if out else torch.zeros(0, dtype=torch.uint8, device=dev)), org, rev

@@ -1,6 +1,7 @@
 //! Seed-and-extend in one call (`bg_seed_extend_batch`): the composition rust-bio's callers write by hand from
 //! `backward_search`, `Interval::occ` and `Aligner::semiglobal` (src/lib.rs:129-165, benches/fmindex.rs:20-38), on the
-//! forward strand or on both (`bg_seed_extend_strands_batch`: the `dna::revcomp` of each read as well).
+//! forward strand or on both (`bg_seed_extend_strands_batch`: the `dna::revcomp` of each read as well), or as read pairs
+//! (`bg_seed_extend_pairs_batch`: interleaved mates, the best proper FR pair where there is one).
 use crate::fmindex::GpuFMIndex;
 use crate::pairwise::{scoring_to_c, tabulate};
 use crate::{concat, strerror, sys, to_alignment, zero_alignment};
@@ -15,6 +16,17 @@ pub struct Hit {
     pub n_candidates: u32,
     /// the winner is on the reverse strand: `alignment` is of `dna::revcomp(read)` against the forward text (SAM's convention)
     pub reverse: bool,
+}
+
+pub struct PairHit {
+    /// mate 1, mate 2
+    pub mates: [Hit; 2],
+    /// both mates report the chosen proper FR pair (SAM FLAG 0x2)
+    pub proper: bool,
+    /// of the proper pair (SAM |TLEN|); 0 when not proper
+    pub span: u64,
+    /// proper combinations among the pair's candidates, both orientations
+    pub n_proper: u32,
 }
 
 impl GpuFMIndex<'_> {
@@ -77,6 +89,42 @@ impl GpuFMIndex<'_> {
                 n_candidates: h.n_candidates,
                 reverse: s as i32 == sys::BG_HIT_REVERSE,
             })
+            .collect()
+    }
+
+    /// Read pairs: `reads[2p]`, `reads[2p + 1]` are the mates of pair p, each mapped on both strands.  Where the best proper FR
+    /// combination (span in `min_span ..= max_span`) gives up at most `pen_unpaired` of score against the mates' own bests, both
+    /// mates report it and the pair is proper; otherwise each mate reports what `seed_extend_batch_strands` reports for it.
+    pub fn seed_extend_batch_pairs<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], min_span: u32, max_span: u32,
+                                                 pen_unpaired: i32, seed_len: u32, stride: u32, max_occ: u32, pad: u32)
+                                                 -> Vec<PairHit> {
+        assert!(reads.len() % 2 == 0, "mates come in pairs: an odd number of reads");
+        let table = tabulate(scoring);
+        let sc = scoring_to_c(scoring, &table);
+        let prm = sys::bg_seed_params_t { seed_len, stride, max_occ, pad };
+        let pp = sys::bg_pair_params_t { min_span, max_span, pen_unpaired };
+        let (buf, off) = concat(reads);
+        let n_pairs = reads.len() / 2;
+        let zero = sys::bg_seed_hit_t { aln: zero_alignment(), window_start: 0, ref_start: 0, ref_end: 0, n_candidates: 0, n_seed_hits: 0 };
+        let mut hits = vec![zero; reads.len()];
+        let mut strand = vec![0u8; reads.len()];
+        let mut pairs = vec![sys::bg_pair_hit_t { span: 0, n_proper: 0, proper: 0, reserved: [0; 3] }; n_pairs.max(1)];
+        let mut ops = vec![0u8; 2 * buf.len() + (2 * pad as usize + 4) * reads.len() + 8];
+        let mut used = 0u64;
+        let rc = unsafe {
+            sys::bg_seed_extend_pairs_batch(self.h, &sc, &prm, &pp, n_pairs as u64, buf.as_ptr(), off.as_ptr(), hits.as_mut_ptr(),
+                                            strand.as_mut_ptr(), pairs.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used)
+        };
+        assert!(rc == 0, "{}", strerror(rc));
+        let hit = |r: usize| Hit {
+            alignment: if hits[r].aln.score == sys::BG_MIN_SCORE { None } else { Some(to_alignment(&hits[r].aln, &ops)) },
+            ref_start: hits[r].ref_start as usize,
+            ref_end: hits[r].ref_end as usize,
+            n_candidates: hits[r].n_candidates,
+            reverse: strand[r] as i32 == sys::BG_HIT_REVERSE,
+        };
+        (0..n_pairs)
+            .map(|p| PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper })
             .collect()
     }
 }
