@@ -6,6 +6,12 @@
         --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU (RCCL over xGMI).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
         (what the driver does): RANK / LOCAL_RANK / WORLD_SIZE come from the environment.
+    python bench.py --full ...
+        every leg below, not only the headline.
+
+A plain run measures the headline alone: it sets up its pairs, runs the warm-up and timed steps, writes --dump-outputs and
+prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything else — the other legs, the headline's roofline
+and per-kernel times, the oracle parity and CPU baselines, the collective's proof — runs with `--full` only.
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
   * headline (`value`): BASELINE configs[1] — 1 M x 150 bp synthetic read pairs per GPU through `Aligner::local`
@@ -23,7 +29,7 @@ One "step" = one pass of the hot path over one batch of synthetic input that is 
   * `ingest` (FASTQ text -> records).
 Units (pairs / queries / reads) shard across ranks; every rank builds its own replica of the index on its GPU
 (suffix array, BWT and SA samples on the device).  Rank 0 prints ONE JSON line.  The CPU legs (oracle parity over the whole workload +
-`cpu_baseline`, median of 3) run on rank 0 of the single-GPU run only.
+`cpu_baseline`, median of 3) run on rank 0 of the single-GPU `--full` run only.
 """
 import argparse
 import json
@@ -47,6 +53,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg, not only the headline: its roofline and per-kernel times, its packed / int32 / semiglobal "
+                         "flavours, the other BASELINE configs with their strong variants, oracle parity and CPU baselines; "
+                         "the --skip-* and --quick options below shape this run")
     ap.add_argument("--pairs", type=int, default=1_000_000, help="read pairs per GPU (configs[1]: 1M)")
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--genome", type=int, default=100_000_000, help="FM leg: genome length (configs[2]: 100 Mbp)")
@@ -65,7 +75,7 @@ def parse_args():
     ap.add_argument("--banded-pairs", type=int, default=100_000,
                     help="banded leg: 10 kb pairs per GPU, and in total for banded.strong (configs[3]: 100k, split over the GPUs)")
     ap.add_argument("--banded-parity-pairs", type=int, default=5120,
-                    help="banded leg: pairs compared with the oracle (5 % of configs[3]; ~13 s of the 16-thread oracle)")
+                    help="banded leg: pairs compared with the oracle (5 %% of configs[3]; ~13 s of the 16-thread oracle)")
     ap.add_argument("--banded-chunk", type=int, default=0, help="banded leg: pairs per sub-batch (0 = the library's default)")
     ap.add_argument("--skip-pipeline", action="store_true")
     ap.add_argument("--pipeline-reads", type=int, default=1_250_000,
@@ -78,7 +88,7 @@ def parse_args():
     ap.add_argument("--fmd-genome", type=int, default=100_000_000, help="SMEM leg: genome length T (the index is over T$R$: 2 T + 2 symbols)")
     ap.add_argument("--fmd-reads", type=int, default=500_000, help="SMEM leg: 150 bp reads per GPU")
     ap.add_argument("--quick", action="store_true",
-                    help="A/B work: no CPU legs (parity, cpu_baseline), no 3 Gbp index, no packed / strong / host-API side legs, one "
+                    help="A/B work with --full: no CPU legs (parity, cpu_baseline), no 3 Gbp index, no packed / strong / host-API side legs, one "
                          "sub-batch of the banded workload — every kernel still runs on its full-size shape; NOT the measured configuration")
     ap.add_argument("--skip-cpu", action="store_true", help="no oracle parity / cpu_baseline legs")
     ap.add_argument("--parity-frac", type=float, default=1.0, help="fraction of every leg's output compared with the oracle")
@@ -483,7 +493,7 @@ def main():
     GATHER = Gatherer(ctx, rank, world, stream)
     L = args.read_len
     n_pairs = args.pairs
-    do_cpu = rank == 0 and world == 1 and not args.skip_cpu
+    do_cpu = args.full and rank == 0 and world == 1 and not args.skip_cpu
     threads = args.cpu_threads or host_cores()
     parity = {} if do_cpu else None
     orc = None
@@ -508,6 +518,18 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_sw_outputs(args.dump_outputs, d_out, d_ops, n_pairs, stride)
     gcups = world * float(n_pairs) * L * L * args.steps / sw_t / 1e9
+    result = {"metric": "GCUPS (SW) + FM-index queries/sec", "value": round(gcups, 3), "unit": "GCUPS",
+              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+              "ms_per_step": round(sw_t / args.steps * 1e3, 3), "higher_is_better": True,
+              "scaling": "weak", "vs_baseline": None, "dtype": "int16" if L <= 192 else "int32", "data": "synthetic",
+              "config": {"workload": f"{n_pairs} x {L} bp synthetic read pairs per GPU, Aligner::local "
+                                     "affine-gap (-5,-1,+1,-1), score+coords+traceback ops (BASELINE configs[1])",
+                         "pairs_per_gpu": n_pairs, "read_len": L, "parallelism": f"shard{world}"}}
+    if world > 1:
+        result["collective"] = GATHER.kind
+    if not args.full:
+        emit(result, rank, world)
+        return
     tm = kernel_timing(ctx, sw_step)
     fill_ms = tm["fill_ms"] / max(1, tm["fill_launches"])
     tb_ms = tm["traceback_ms"] / max(1, tm["traceback_launches"])
@@ -515,9 +537,9 @@ def main():
     rec = d_out.view(torch.int32).view(n_pairs, 16)
     n_ops_mean = float(rec[:, 7].to(torch.int64).sum().item()) / n_pairs
     fill_kernel = "sw_fill_pk16_kernel" if L <= 192 else "sw_fill_kernel"  # K1p: two pairs per lane (short reads)
-    roofline = sw_roofline(fill_kernel, fill_ms, tb_ms, pairs_per_launch, L, n_ops_mean,
-                           "VALU-bound integer DP: `frac` is the required HBM figure on the reference's 2 B/cell "
-                           "traceback, `valu_frac` the issue-rate utilisation that actually bounds it (DESIGN.md §4)")
+    result["roofline"] = sw_roofline(fill_kernel, fill_ms, tb_ms, pairs_per_launch, L, n_ops_mean,
+                                     "VALU-bound integer DP: `frac` is the required HBM figure on the reference's 2 B/cell "
+                                     "traceback, `valu_frac` the issue-rate utilisation that actually bounds it (DESIGN.md §4)")
 
     cpu_baseline = None
     host_api = None
@@ -550,17 +572,8 @@ def main():
                             "operations brought back by a small kernel on a high-priority stream, all overlapped with the next stages' kernels"}
         del hout, hopsb, hxa, hya
 
-    result = {"metric": "GCUPS (SW) + FM-index queries/sec", "value": round(gcups, 3), "unit": "GCUPS",
-              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-              "ms_per_step": round(sw_t / args.steps * 1e3, 3), "higher_is_better": True,
-              "scaling": "weak", "vs_baseline": None, "dtype": "int16" if L <= 192 else "int32", "data": "synthetic",
-              "config": {"workload": f"{n_pairs} x {L} bp synthetic read pairs per GPU, Aligner::local "
-                                     "affine-gap (-5,-1,+1,-1), score+coords+traceback ops (BASELINE configs[1])",
-                         "pairs_per_gpu": n_pairs, "read_len": L, "parallelism": f"shard{world}"},
-              "roofline": roofline}
     if world > 1:  # the headline step's collective, proven from the library's side (bg_comm_world) and timed alone
         rec5 = d_out.view(torch.int32).view(n_pairs, 16)[:, :5].contiguous()
-        result["collective"] = GATHER.kind
         result["collective_proof"] = GATHER.proof(rec5, [n_pairs] * world)
         del rec5
     if host_api:
@@ -688,11 +701,15 @@ def main():
     if not args.skip_ingest:
         result["ingest"] = ingest_leg(args, ctx, dev, stream, rank, world, do_cpu, orc, parity)
 
+    if cpu_baseline is not None:
+        result["cpu_baseline"] = cpu_baseline
+    if parity is not None:
+        result["parity"] = parity
+    emit(result, rank, world)
+
+
+def emit(result, rank, world):
     if rank == 0:
-        if cpu_baseline is not None:
-            result["cpu_baseline"] = cpu_baseline
-        if parity is not None:
-            result["parity"] = parity
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

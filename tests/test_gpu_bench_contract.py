@@ -1,7 +1,7 @@
 """bench.py's one JSON line on a scaled-down workload: the driver's contract (metric / value / unit / n_gpus / steps /
-warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload), the `roofline` and
-`cpu_baseline` objects of the tier brief, a leg for every BASELINE config (configs[1] headline, [2] fm, [3] banded, [4]
-seed_extend — each with its strong variant where the config is multi-GPU), and every parity flag true."""
+warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full also the
+`roofline` and `cpu_baseline` objects of the tier brief, a leg for every BASELINE config (configs[1] headline, [2] fm, [3]
+banded, [4] seed_extend — each with its strong variant where the config is multi-GPU), and every parity flag true."""
 import json
 import os
 import subprocess
@@ -13,11 +13,37 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def assert_contract_fields(d, steps, warmup):
+    for k, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                   ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str)):
+        assert isinstance(d[k], typ), k
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["vs_baseline"] is None
+    assert d["scaling"] == "weak" and "workload" in d["config"] and "model" not in d["config"]
+
+
+def test_plain_line_is_the_headline_alone():
+    """Without --full the run times the headline and prints its line: no other leg, no roofline, no CPU leg."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--pairs", "20000"]
+    out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    lines = [ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, "rank 0 prints ONE JSON line"
+    d = json.loads(lines[0])
+    assert_contract_fields(d, steps=3, warmup=2)
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GCUPS" and d["dtype"] == "int16"
+    assert d["config"]["pairs_per_gpu"] == 20000
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                      "vs_baseline", "dtype", "data", "config"}, sorted(d)
+
+
 def test_bench_line_has_the_contract_fields_and_green_parity():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "20000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--pairs", "20000",
            "--k1-pairs", "4096", "--genome", "300000", "--fm-big-genome", "400000", "--queries", "20000", "--banded-pairs", "70",
            "--banded-parity-pairs", "70", "--pipeline-reads", "3000", "--pipeline-reads-total", "4001", "--ingest-reads", "3000",
            "--fmd-genome", "200000", "--fmd-reads", "2000"]
@@ -26,11 +52,7 @@ def test_bench_line_has_the_contract_fields_and_green_parity():
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "rank 0 prints ONE JSON line"
     d = json.loads(lines[0])
-    for k, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
-                   ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str)):
-        assert isinstance(d[k], typ), k
-    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["vs_baseline"] is None and d["scaling"] == "weak"
-    assert "workload" in d["config"] and "model" not in d["config"]
+    assert_contract_fields(d, steps=2, warmup=1)
     r = d["roofline"]
     assert r["bound"] in ("hbm", "mfma") and r["unit"] in ("GB/s", "TFLOP/s") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert "traffic" in r and r["peak"] == 8000.0

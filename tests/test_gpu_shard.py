@@ -127,7 +127,7 @@ def test_bench_launches_its_own_ranks():
     import json
     env = dict(os.environ, BENCH_SINGLE_GPU="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--pairs", "20000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--pairs", "20000",
            "--genome", "300000", "--fm-big-genome", "0", "--queries", "40000", "--banded-pairs", "97", "--pipeline-reads", "3000",
            "--pipeline-reads-total", "5001", "--skip-ingest", "--skip-k1"]
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)

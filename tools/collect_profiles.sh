@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the profiles/ artefacts of one round on the GPU box (run through gpurun):
 #   tools/collect_profiles.sh <tag>        e.g. r02
-# 1. rocprofv3 --kernel-trace --stats of the default bench.py command (all legs)   -> <tag>_bench_kernel_stats.csv
+# 1. rocprofv3 --kernel-trace --stats of bench.py --full (all legs)                -> <tag>_bench_kernel_stats.csv
 # 2. separate PMC passes, kernel-trace only (never combined with other trace domains):
 #      FETCH_SIZE, WRITE_SIZE                                                      -> <tag>_pmc_traffic.json
 #      SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES                   -> <tag>_sq_counters.json
@@ -14,7 +14,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --skip-cpu"
+BENCH="python $R/bench.py --full --skip-cpu"
 # the counter passes keep one launch shape per kernel: the seed-and-extend leg reuses K2 / K5 on other batch sizes
 PMCBENCH="$BENCH --skip-fmd --skip-pipeline --skip-packed --fm-big-genome 0 --banded-pairs 98304 --pipeline-reads-total 0 --steps 2 --warmup 0"
 # ... and the FM kernel on the 3 Gbp index gets passes of its own (same kernel name as the 100 Mbp leg)

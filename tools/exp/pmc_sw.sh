@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 for C in WRITE_SIZE FETCH_SIZE; do
-rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/pmcsw_$C -o x -- python $R/bench.py --skip-cpu --skip-fm --skip-banded --skip-pipeline --steps 2 --warmup 0 > /tmp/pmcsw_$C.log 2>&1
+rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/pmcsw_$C -o x -- python $R/bench.py --full --skip-cpu --skip-fm --skip-banded --skip-pipeline --steps 2 --warmup 0 > /tmp/pmcsw_$C.log 2>&1
 python - $C <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float))

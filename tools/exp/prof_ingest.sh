@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ing
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ing -o x -- python $R/bench.py --skip-cpu --skip-fm --skip-banded --skip-pipeline --skip-k1 --skip-semiglobal --skip-packed --fm-big-genome 0 --pairs 65536 --steps 3 --warmup 1 > /tmp/ing.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ing -o x -- python $R/bench.py --full --skip-cpu --skip-fm --skip-banded --skip-pipeline --skip-k1 --skip-semiglobal --skip-packed --fm-big-genome 0 --pairs 65536 --steps 3 --warmup 1 > /tmp/ing.log 2>&1
 python - <<'PY'
 import csv, glob, json
 for f in glob.glob("/tmp/ing/**/*kernel_stats.csv", recursive=True):

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pl
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pl -o x -- python $R/bench.py --skip-cpu --skip-banded --skip-k1 --skip-semiglobal --skip-packed --skip-ingest --skip-fmd --fm-big-genome 0 --pairs 65536 --queries 100000 --steps 2 --warmup 1 > /tmp/pl.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pl -o x -- python $R/bench.py --full --skip-cpu --skip-banded --skip-k1 --skip-semiglobal --skip-packed --skip-ingest --skip-fmd --fm-big-genome 0 --pairs 65536 --queries 100000 --steps 2 --warmup 1 > /tmp/pl.log 2>&1
 python - <<'PY'
 import csv, glob, json
 for f in glob.glob("/tmp/pl/**/*kernel_stats.csv", recursive=True):

@@ -9,7 +9,7 @@
 #   fuzz_fm:<seed>:<s>    tests/fuzz_fm.py            fuzz_fm_wide:<seed>:<s>   the same on the forced 64-bit layout
 #   fuzz_banded:<seed>:<s>[:k3p]   fuzz_banded_long:<seed>:<s>:<len>   fuzz_pairwise:<seed>:<s>   fuzz_pk16:<seed>:<s>   fuzz_fastq:<seed>:<s>   fuzz_pipeline:<seed>:<s>
 #   bench[:args]          python bench.py [args ...] (args separated by ',')  -> <tag>/bench.json
-#   profiles              tools/collect_profiles.sh <tag>  (kernel stats + PMC passes of the default bench command)
+#   profiles              tools/collect_profiles.sh <tag>  (kernel stats + PMC passes of bench.py --full)
 #   py:<script>[:args]    python <script> [args ...] (args separated by ',')  -> <tag>/<script basename>.json (stdout)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:?tag}; shift

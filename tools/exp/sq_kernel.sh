@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for G in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_INSTS_LDS" "SQ_WAVES SQ_INSTS_BRANCH SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SMEM SQ_ACTIVE_INST_MISC"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $G --output-format csv -d "$OUT/p$i" -o sq -- python $R/bench.py --skip-cpu --steps 2 --warmup 0 "$@" > "$OUT/p$i.log" 2>&1
+  rocprofv3 --kernel-trace --pmc $G --output-format csv -d "$OUT/p$i" -o sq -- python $R/bench.py --full --skip-cpu --steps 2 --warmup 0 "$@" > "$OUT/p$i.log" 2>&1
 done
 python - "$OUT" "$K" <<'PY'
 import csv, glob, sys, collections
