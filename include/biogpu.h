@@ -702,6 +702,9 @@ enum {
  * sub-batches (BG_FILL_* bits; 0 before the first such call).  A family counts when it was launched, even if it found
  * nothing to do (K3i behind K3p only recomputes the pairs K3p flagged). */
 int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask);
+/* 1 when the last bg_align_batch* call ran K1p's local flavour (BG_FILL_K1P_LF) with its keys in the offset frame (the cell
+ * taken where every key fits it; the option "no_pk16_frame" turns it off), else 0. */
+int bg_last_fill_framed(bg_ctx* ctx, int* framed);
 int bg_enable_timing(bg_ctx* ctx, int on);
 
 #ifdef __cplusplus

@@ -316,6 +316,7 @@ static int banded_batch_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint
                              const BandMaker& make_band, const uint32_t* dev_kw = nullptr, const BandDevIO* dio = nullptr) {
     if (!ctx || !sc || mode < BG_MODE_CUSTOM || mode > BG_MODE_LOCAL) return BG_ERR_INVALID_ARG;
     ctx->fill_mask = 0;
+    ctx->fill_framed = false;
     int rc = check_scoring(sc);
     if (rc) return rc;
     if (ops_used) *ops_used = 0;

@@ -268,6 +268,10 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
         ctx->no_local_fast = value != 0;
         return BG_OK;
     }
+    if (!strcmp(key, "no_pk16_frame")) {
+        ctx->no_pk16_frame = value != 0;
+        return BG_OK;
+    }
     if (!strcmp(key, "no_pk16")) {
         ctx->no_pk16 = value != 0;
         return BG_OK;
@@ -289,6 +293,12 @@ extern "C" int bg_enable_timing(bg_ctx* ctx, int on) {
 extern "C" int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask) {
     if (!ctx || !mask) return BG_ERR_INVALID_ARG;
     *mask = ctx->fill_mask;
+    return BG_OK;
+}
+
+extern "C" int bg_last_fill_framed(bg_ctx* ctx, int* framed) {
+    if (!ctx || !framed) return BG_ERR_INVALID_ARG;
+    *framed = ctx->fill_framed ? 1 : 0;
     return BG_OK;
 }
 

@@ -22,6 +22,7 @@ sw_fill_fn get_fill_params_lf(int lp, int r);
 sw_fill_fn get_fill_matrix(int lp, int r, int sm, bool narrow, bool local);
 sw_fill_fn get_fill_pk16_local(int lp, int r, int which);
 sw_fill_fn get_fill_pk16_localfast(int lp, int r, int which);
+sw_fill_fn get_fill_pk16_localframe(int lp, int r, int which);
 sw_fill_fn get_fill_pk16_semiglobal(int lp, int r, int which);
 sw_fill_fn get_fill_pk16_global(int lp, int r, int which);
 sw_fill_fn get_fill_pk16_custom(int lp, int r, int which);
@@ -362,6 +363,11 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
             pk16 = false;  // no K1p instantiation for this shape: the general kernel K1 picked above runs
         } else {
             cfg.r = r_pick;
+            // LF keys in the offset frame (its cell does without the clamped gap adds) wherever they fit 15 bits there
+            if (local_fast && !ctx->no_pk16_frame && pk16_frame_fits(c, max_ylen, cfg.r, cfg.lp)) {
+                getter = get_fill_pk16_localframe;
+                ctx->fill_framed = true;
+            }
             fill = getter(cfg.lp, cfg.r, 0);
             fill_rest = local_fast ? nullptr : getter(cfg.lp, cfg.r, 1);  // LF: the first launch takes every wavefront
             fill_second = getter(cfg.lp, cfg.r, 2);
@@ -501,7 +507,10 @@ extern "C" int bg_align_batch_dev(bg_ctx* ctx, const bg_scoring_t* sc, int mode,
                                   const uint64_t* d_y_off, uint32_t max_xlen, uint32_t max_ylen,
                                   bg_alignment_t* d_out, uint8_t* d_ops, uint64_t ops_stride,
                                   void* stream) {
-    if (ctx) ctx->fill_mask = 0;
+    if (ctx) {
+        ctx->fill_mask = 0;
+        ctx->fill_framed = false;
+    }
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, d_x, d_x_off, d_y, d_y_off, max_xlen, max_ylen, d_out, d_ops, ops_stride, stream, -1);
 }
 
@@ -516,7 +525,10 @@ extern "C" int bg_align_batch_packed_dev(bg_ctx* ctx, const bg_scoring_t* sc, in
     for (int a = 0; a < 4; a++)
         for (int b = a + 1; b < 4; b++)
             if (codes[a] == codes[b]) return BG_ERR_INVALID_ARG;
-    if (ctx) ctx->fill_mask = 0;
+    if (ctx) {
+        ctx->fill_mask = 0;
+        ctx->fill_framed = false;
+    }
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, (const uint8_t*)d_x, d_x_off, (const uint8_t*)d_y, d_y_off, max_xlen, max_ylen,
                                 d_out, d_ops, ops_stride, stream, -1, codes);
 }
@@ -834,6 +846,7 @@ extern "C" int bg_align_batch(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uin
                               uint64_t ops_cap, uint64_t* ops_used) {
     if (!ctx || !sc) return BG_ERR_INVALID_ARG;
     ctx->fill_mask = 0;
+    ctx->fill_framed = false;
     int rc = check_scoring(sc);
     if (rc) return rc;
     if (ops_used) *ops_used = 0;

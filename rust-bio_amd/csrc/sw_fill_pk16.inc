@@ -79,7 +79,16 @@ enum { CZ = 0, CF = 1, CI = 2 };
 // launch).  The local floor 0 (the x-prefix-clip candidate, mod.rs:765-768) comes out of the unsigned saturation of the
 // substitution score instead of one more maximum — the move code of such a cell is 0, which K2 and the epilogue read as
 // C_XP (SwGeom::tb_fmt == 2).
-template <int R, int LP, int MODE, int XP, int XS, int YP, int YS, bool LF = false>
+// FR (LF only, where pk16_frame_fits): the keys live in an offset frame, K^ = K + B + g (r + s) with r the row within the
+// lane, s the step, g = 16 |ge| and B = pk16_frame_bias (sw_kernels.h).  A gap extension is then no instruction at all
+// (I^(r, s) = I^(r - 1, s), D^(r, s) = D^(r, s - 1)), the opens and the diagonal differ from their sources by constants,
+// and since every key of the frame lies in [0, 0x7fff] those constants go on with full-rate 32-bit adds, one per cell
+// for both pairs (no half ever carries into the other): four v_pk_add_i16 clamp per cell become two v_add_u32.  The
+// local floor 0 becomes the per-(row, step) constant F(r, s) = B + g (r + s), one more maximum; the row maxima SnB leave
+// the frame as they are taken (best^ - F + priority, one subtract instead of the or), and so do Sl / Il when they are
+// parked: the epilogue, the traceback cells and K2 see what the plain LF cell gives them.  The values crossing to the lane
+// below (row R - 1 there, row -1 here) are re-based by g (R - 1), and 0 is 'minus infinity' of I and D.
+template <int R, int LP, int MODE, int XP, int XS, int YP, int YS, bool LF = false, bool FR = false>
 __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     constexpr bool FAST = MODE == 0;
     constexpr int PW = 64 / LP;
@@ -93,6 +102,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     static_assert(LP == 16 || LP == 32, "lanes per pair");
     static_assert(R >= 1 && R <= 12, "rows per lane");
     static_assert(!LF || LOCAL, "LF is a flavour of the local kernel");
+    static_assert(!FR || LF, "the frame is a cell of the LF flavour");
     (void)NARROW;
     (void)LOCAL;
     // LDS, two uses that never overlap in time: during the fill, the traceback words of the current tile (a
@@ -136,6 +146,14 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     // -(mismatch | K_SUBST) as an unsigned amount (LF: mismatch <= -1)
     const pk MISC = dup16(-((sc.mismatch * 16) | K_SUBST));
     (void)MISC;
+    // FR: fr(c) adds c to both halves with one 32-bit add (exact while each half stays inside [0, 0xffff]; any c)
+    auto fr = [](int32_t c) -> pk { return (uint32_t)c * 0x10001u; };
+    const int32_t gF = -16 * sc.ge, BF = pk16_frame_bias(sc);
+    const pk GF = fr(gF);
+    const pk KGOI = fr(sc.go * 16 + K_INS + 1 + gF), KGOD = fr(sc.go * 16 + K_DEL + 1 + gF);  // opens: one row / step on
+    const pk KSUB = fr(((sc.mismatch * 16) | K_SUBST) + 2 * gF);                                // diagonal: both
+    const pk KREB = fr(gF * (R - 1));  // row R - 1 of the lane above at step s -> row -1 here at step s + 1
+    (void)GF; (void)KGOI; (void)KGOD; (void)KSUB; (void)KREB;
     // the traceback cells are put together with v_pk_mad_u16; the factors are hidden from the compiler, which
     // otherwise rewrites every multiply-add by a power of two into a shift and an add (two instructions for one)
     pk C16 = dup16(16), C32 = dup16(32), C1024 = dup16(1024);
@@ -265,6 +283,20 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
             }
         }
         pk diag0 = dup16((pair_ok && rb < m) ? scl(col0_S(sc, rb, m, fold0)) : NEGS);  // S(rb, 0)
+        if (FR) {
+            // into the frame: column 0 is step ll - 1 of this lane, its diagonal step ll - 2 of row -1.  Exact modular adds, undone
+            // when the rows are parked (a lane that computes nothing gets back what it started with); rows past m start at
+            // score 0 and stay garbage nobody reads, as without the frame
+            const int32_t off0 = BF + gF * ((int32_t)ll - 1);
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const pk o = fr(off0 + gF * r);
+                Sl[r] = (pair_ok && rb + r + 1 <= m) ? Sl[r] + o : o;
+                Il[r] += o;
+                Dl[r] = 0;
+            }
+            diag0 = fr(off0 - gF) + ((pair_ok && rb < m) ? dup16(scl(col0_S(sc, rb, m, fold0))) : 0u);
+        }
 
         pk S_out = FLOORK, I_out = FLOORK, cm_out = FLOORK, ca_out = 0, q_out = 0;
         pk ychunk = 0, ychunk_nx = 0;
@@ -331,6 +363,10 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
             }
             // lane 0 of the wavefront keeps its own value ("old" == source): it is a row-0 lane and overrides it
             pk S_up = (pk)wave_shr1((int)S_out, (int)S_out), I_up = (pk)wave_shr1((int)I_out, (int)I_out);
+            if (FR) {  // into this lane's frame (re-based here rather than before the shift: S_out / I_out stay the last row's registers)
+                S_up -= KREB;
+                I_up -= KREB;
+            }
             pk cm = FLOORK, ca = 0;
             if (FOLD) {
                 cm = (pk)wave_shr1((int)cm_out, (int)cm_out);
@@ -339,10 +375,12 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
             pk q = (pk)wave_shr1((int)q_out, (int)q_out);
             const uint32_t j = s + 1 - (uint32_t)ll;
             const bool col_ok = ALLON || (pair_ok && (j - 1) < n);  // 1 <= j <= n
+            const pk F0 = fr(BF + gF * (int32_t)s);  // FR: the frame of row 0 at this step (wave-uniform)
+            (void)F0;
             if (ll == 0) {  // row 0 of the matrix (mod.rs:678-721)
                 q = ychunk;
-                S_up = 0;
-                I_up = FLOORK;  // mod.rs:681
+                S_up = FR ? F0 - GF : 0u;  // row -1
+                I_up = FR ? 0u : FLOORK;   // mod.rs:681
                 cm = FLOORK;    // S[curr][1..=m] reset, mod.rs:719-721 (both dead without FOLD)
                 ca = 0;         // Lx[j] starts at 0
                 if (!ROW0_ZERO && col_ok) {
@@ -384,10 +422,14 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                         // mod.rs:733-755: substitution score with the MATCH/SUBST move code in its low bits
                         const pk e = pk_subs_u16(ONE, px[r] ^ q);  // 1 where the characters agree
                         // LF: diag >= 0, the sum saturates at key 0 = (score 0, code 0) where the reference's S falls back on
-                        // the x-prefix clip
-                        const pk m_key = LF ? pk_subs_u16(pk_mad_u16(e, DELTA, diag), MISC) : pk_adds(diag, pk_mad_u16(e, DELTA, MISK));
-                        const pk Iv_t = pk_max(pk_adds(I_up, GE), pk_adds(S_up, GOT_I));
-                        const pk Dv_t = pk_max(pk_adds(Dl[r], GE), pk_adds(Sl[r], GOT_D));
+                        // the x-prefix clip; FR: the floor is that key in the frame, F(r, s)
+                        const pk Fr = F0 + (uint32_t)r * GF;
+                        (void)Fr;
+                        const pk m_key = FR   ? pk_max(pk_mad_u16(e, DELTA, diag) + KSUB, Fr)
+                                         : LF ? pk_subs_u16(pk_mad_u16(e, DELTA, diag), MISC)
+                                              : pk_adds(diag, pk_mad_u16(e, DELTA, MISK));
+                        const pk Iv_t = FR ? pk_max(I_up, S_up + KGOI) : pk_max(pk_adds(I_up, GE), pk_adds(S_up, GOT_I));
+                        const pk Dv_t = FR ? pk_max(Dl[r], Sl[r] + KGOD) : pk_max(pk_adds(Dl[r], GE), pk_adds(Sl[r], GOT_D));
                         const pk Iv = Iv_t & NOFLAG, Dv = Dv_t & NOFLAG;
                         // mod.rs:757-786: first maximum wins == max over (score | priority)
                         pk kb = pk_max(m_key, Dv_t);
@@ -409,7 +451,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                         }
                         if (YS != CI) {  // mod.rs:799-802
                             const pk t1 = YS == CZ ? best : pk_min(pk_adds(best, YS16), YSCAP);
-                            SnB[r] = pk_max(SnB[r], t1 | sprio);
+                            SnB[r] = pk_max(SnB[r], FR ? best - (Fr - sprio) : t1 | sprio);  // FR: out of the frame
                         }
                         // packed cell: I opens | 3-bit move << 1 | D opens << 4 (flipped to "extends" below)
                         const pk c5 = pk_mad_u16(Dv_t & ONE, C16, (kb & 0x000e000eu) | (Iv_t & ONE));
@@ -502,10 +544,12 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
         // The packed rows are parked in LDS (thread-private slots, stride 64: conflict-free) so that the
         // epilogue's 64-bit scans do not have to share the register file with them.
         pk* park = wave_lds + lane;
+        // FR: out of the frame of the lane's last column, step n - 1 + ll (n == 0: the frame of column 0 it started in)
+        const pk offl = FR ? fr(BF + gF * ((int32_t)ll + (int32_t)n - 1)) : 0u;
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            park[(0 * R + r) * 64] = Sl[r];
-            park[(1 * R + r) * 64] = Il[r];
+            park[(0 * R + r) * 64] = FR ? Sl[r] - (offl + (uint32_t)r * GF) : Sl[r];
+            park[(1 * R + r) * 64] = FR ? Il[r] - (offl + (uint32_t)r * GF) : Il[r];
             park[(2 * R + r) * 64] = SnR[r];
             park[(3 * R + r) * 64] = Ly[r];
         }
@@ -565,17 +609,17 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
 
 // the fast launch is tuned for three wavefronts per SIMD up to R = 10 (168 VGPRs, 46 KB of LDS per block); the two
 // others take what the generic row-m handling needs, two per SIMD at least
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_kernel(const SwArgs a) {
-    sw_fill_pk16_body<R, LP, 0, XP, XS, YP, YS, LF>(a);
+    sw_fill_pk16_body<R, LP, 0, XP, XS, YP, YS, LF, FR>(a);
 }
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_rest_kernel(const SwArgs a) {
-    sw_fill_pk16_body<R, LP, 1, XP, XS, YP, YS, LF>(a);
+    sw_fill_pk16_body<R, LP, 1, XP, XS, YP, YS, LF, FR>(a);
 }
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_second_kernel(const SwArgs a) {
-    sw_fill_pk16_body<R, LP, 2, XP, XS, YP, YS, LF>(a);
+    sw_fill_pk16_body<R, LP, 2, XP, XS, YP, YS, LF, FR>(a);
 }
 
 }  // namespace pk16
@@ -584,6 +628,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3
 // one instantiation unit per clip pattern: BG_PK16_GETTER(name, XP, XS, YP, YS, cases)
 #define BG_PK16_CASE(LP_, R_)                                                                          \
     if (lp == LP_ && r == R_)                                                                         \
-        return which == 0   ? pk16::sw_fill_pk16_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_>             \
-               : which == 1 ? pk16::sw_fill_pk16_rest_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_>        \
-                            : pk16::sw_fill_pk16_second_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_>;
+        return which == 0   ? pk16::sw_fill_pk16_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_, FR_>        \
+               : which == 1 ? pk16::sw_fill_pk16_rest_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_, FR_>   \
+                            : pk16::sw_fill_pk16_second_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_, FR_>;

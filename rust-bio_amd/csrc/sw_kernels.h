@@ -56,6 +56,26 @@ struct SwScoring {
     int32_t match, mismatch;
 };
 
+// K1p's framed LF cell (sw_fill_pk16.inc): keys kept as K + B + g (r + s), r = row within the lane, s = step, g = 16 |ge|.
+// The bias B (a multiple of 16) keeps every value the cell forms at or above 0, and every gap open at or above 1 (0 is the
+// frame's 'minus infinity'): a diagonal two frames back (B >= 2g), a mismatch on it (B >= -mismatch key) and an open out
+// of the row above the lane (B >= 1 - open key).
+__host__ __device__ inline int32_t pk16_frame_bias(const SwScoring& sc) {
+    const int32_t g = -16 * sc.ge;
+    int32_t b = 2 * g;
+    const int32_t lows[3] = {-((sc.mismatch * 16) | (int32_t)(C_SUBST << 1)), -(sc.go * 16 + (int32_t)(C_INS << 1)),
+                             -(sc.go * 16 + (int32_t)(C_DEL << 1))};
+    for (int32_t v : lows) b = b > v ? b : v;
+    return (b + 15) & ~15;
+}
+// ... and whether every key of a fill of reads up to max_ylen columns, r rows per lane, lp lanes per pair stays inside
+// [0, 0x7fff] there: local scores are at most match * min(i, j) <= match * max_ylen (rows past m included)
+inline bool pk16_frame_fits(const SwScoring& sc, uint32_t max_ylen, int r, int lp) {
+    if (sc.ge > 0 || sc.match < 0) return false;
+    const int64_t g = -16ll * sc.ge, nsteps = (int64_t)max_ylen + lp - 1;
+    return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x8000;
+}
+
 // aux record of one pair (int32 words):
 //   [0] S nibble of (m,0)   [1] score = S[n%2][m] after the epilogue   [2] Lx[n] after the epilogue
 //   Ly[m_cap+1]  Lx[n_cap+1]  colBits[m_cap+1 bytes]: (S nibble | I nibble << 4) of column n
