@@ -16,34 +16,112 @@
 #include "sw_kernels.h"
 
 namespace bgsw {
-sw_fill_fn get_fill_params_narrow(int lp, int r, bool local);
-sw_fill_fn get_fill_params_wide(int lp, int r, bool local);
-sw_fill_fn get_fill_params_lf(int lp, int r);
-sw_fill_fn get_fill_matrix(int lp, int r, int sm, bool narrow, bool local);
-sw_fill_fn get_fill_pk16_local(int lp, int r, int which);
-sw_fill_fn get_fill_pk16_localfast(int lp, int r, int which);
-sw_fill_fn get_fill_pk16_localframe(int lp, int r, int which);
-sw_fill_fn get_fill_pk16_semiglobal(int lp, int r, int which);
-sw_fill_fn get_fill_pk16_global(int lp, int r, int which);
-sw_fill_fn get_fill_pk16_custom(int lp, int r, int which);
 void launch_traceback(const SwArgs& a, int nw, hipStream_t st);
+
+static sw_fill_fn sw_fill_get(SwFill f, bool narrow, int lp, int r, int which = 0) {
+    static sw_fill_fn (*const get[])(bool, int, int, int) = {
+#define BG_X(F) sw_fill_get_##F,
+        BG_SW_FILLS(BG_X)
+#undef BG_X
+    };
+    return get[f](narrow, lp, r, which);
+}
+// the smallest r >= r0 (that divides m, if m != 0) family f has instantiated; 0 if none
+static int instantiated_r(SwFill f, bool narrow, int lp, int r0, uint32_t m = 0) {
+    for (int r = r0; r <= 12; r++)
+        if ((!m || m % r == 0) && sw_fill_get(f, narrow, lp, r)) return r;
+    return 0;
+}
 
 struct Config {
     int lp, r;
 };
-// rows of x covered per strip = lp * r; short reads pack several pairs into one wavefront
-static Config pick_config(uint32_t m_cap, int sm) {
-    if (sm == SCORE_PARAMS) {
-        if (m_cap <= 192) return {16, std::max(2, 2 * (int)((m_cap + 31) / 32))};
-        if (m_cap <= 384) return {32, std::max(8, 2 * (int)((m_cap + 63) / 64))};
-        return {64, 8};
-    }
-    if (m_cap <= 96) return {16, 6};
-    if (m_cap <= 128) return {16, 8};
-    if (m_cap <= 160) return {16, 10};
-    if (m_cap <= 192) return {16, 12};
-    if (m_cap <= 384) return {32, 12};
+// rows of x covered per strip = lp * r; short reads pack several pairs into one wavefront.  A family runs the smallest r
+// at or above this one it has instantiated.
+static Config pick_config(uint32_t m_cap) {
+    if (m_cap <= 192) return {16, std::max(2, 2 * (int)((m_cap + 31) / 32))};
+    if (m_cap <= 384) return {32, std::max(8, 2 * (int)((m_cap + 63) / 64))};
     return {64, 8};
+}
+
+// NARROW kernels need every reachable score inside +-2^25 (sw_kernels.h), K1p every real value inside +-2040: both are
+// bounded by (longest path) x (largest finite magnitude in the scoring)
+static int64_t score_magnitude(const SwScoring& c, const int32_t* matrix) {
+    int64_t mag = std::max<int64_t>(std::abs((int64_t)c.go), std::abs((int64_t)c.ge));
+    for (int32_t v : {c.xp, c.xs, c.yp, c.ys})
+        if (v != BG_MIN_SCORE) mag = std::max<int64_t>(mag, std::abs((int64_t)v));
+    if (matrix) {
+        for (size_t t = 0; t < 65536; t++) mag = std::max<int64_t>(mag, std::abs((int64_t)matrix[t]));
+    } else {
+        mag = std::max<int64_t>(mag, std::max(std::abs((int64_t)c.match), std::abs((int64_t)c.mismatch)));
+    }
+    return mag;
+}
+
+// What a call runs: the fill kernels, their shape, the traceback cell format K2 decodes and the BG_FILL_* bit the call
+// reports.  fill == nullptr: nothing is instantiated for this scoring and these lengths.
+struct FillPlan {
+    int lp = 0, r = 0;
+    sw_fill_fn fill = nullptr, fill_rest = nullptr, fill_second = nullptr;  // K1p: the fast launch, the rest, the second pairs
+    uint32_t tb_fmt = TBF_K1;
+    uint32_t fill_bit = 0;
+    bool k1p = false, framed = false;
+};
+// the one place that chooses a fill: K1p where admitted and shaped, else K1's LF flavour where admitted, else K1 by score
+// source.  `c` carries the clip penalties of the mode.
+static FillPlan plan_fill(const bg_ctx& ctx, const SwScoring& c, int sm, int64_t mag, uint32_t max_xlen, uint32_t max_ylen) {
+    const Config cfg = pick_config(max_xlen);
+    const bool local = c.xp == 0 && c.xs == 0 && c.yp == 0 && c.ys == 0;
+    // local alignments whose gaps and mismatches cost something take the LF flavours (sw_fill.inc, sw_fill_pk16.inc)
+    // (match >= 0: K1p's LF cell's unsigned mad needs matchkey - mismatchkey >= 0; MatchParams::new asserts it,
+    //  mod.rs:199-200, but nothing in the C API does)
+    const bool lf = local && c.go < 0 && c.mismatch < 0 && c.match >= 0 && !ctx.no_local_fast;
+    FillPlan p;
+    p.lp = cfg.lp;
+    // K1p: short reads whose scores fit 12 bits (sw_fill_pk16.inc) — two pairs per lane, one instantiation unit per
+    // clip pattern.  Bound: no real DP value, nor the epilogue's go * i terms, may leave +-2040.
+    if (!ctx.no_pk16 && sm == SCORE_PARAMS && cfg.lp <= 32 && max_xlen >= 1 && mag * ((int64_t)std::max(max_xlen, max_ylen) + 2) <= 2040) {
+        const int32_t M = BG_MIN_SCORE;
+        SwFill f = lf      ? FILL_K1P_LF
+                   : local ? FILL_K1P_LOCAL
+                   : (c.xp == M && c.xs == M && c.yp == 0 && c.ys == 0) ? FILL_K1P_SEMIGLOBAL
+                   : (c.xp == M && c.xs == M && c.yp == M && c.ys == M) ? FILL_K1P_GLOBAL
+                                                                        : FILL_K1P_CUSTOM;
+        // rows per lane: the fast launch wants row m on the last row of a lane (m % R == 0); reads of a
+        // batch usually share one length, so prefer an instantiated R that divides the longest
+        const int r0 = (int)((max_xlen + cfg.lp - 1) / cfg.lp);
+        int r = instantiated_r(f, true, cfg.lp, r0, max_xlen);
+        if (!r) r = instantiated_r(f, true, cfg.lp, r0);
+        if (r) {  // (else no K1p instantiation for this shape: K1 runs)
+            // LF keys in the offset frame (its cell does without the clamped gap adds) wherever they fit 15 bits there
+            p.framed = lf && !ctx.no_pk16_frame && pk16_frame_fits(c, max_ylen, r, cfg.lp);
+            if (p.framed) f = FILL_K1P_LF_FRAMED;
+            p.r = r;
+            p.fill = sw_fill_get(f, true, cfg.lp, r, 0);
+            p.fill_rest = lf ? nullptr : sw_fill_get(f, true, cfg.lp, r, 1);  // LF: the first launch takes every wavefront
+            p.fill_second = sw_fill_get(f, true, cfg.lp, r, 2);
+            p.tb_fmt = lf ? TBF_K1P_LF : TBF_K1P;
+            p.fill_bit = lf ? BG_FILL_K1P_LF : BG_FILL_K1P;
+            p.k1p = true;
+            return p;
+        }
+    }
+    const bool narrow = !ctx.force_wide && mag * ((int64_t)max_xlen + max_ylen + 8) < (1 << 24);
+    // K1's LF flavour (sw_fill.inc): Aligner::local under MatchParams, scaled keys, reads of one strip — the
+    // reference-width (int32) kernel without the clip machinery such alignments never use
+    if (sm == SCORE_PARAMS && narrow && lf && max_xlen <= (uint32_t)(cfg.lp * cfg.r) && (p.fill = sw_fill_get(FILL_K1_LF, true, cfg.lp, cfg.r))) {
+        p.r = cfg.r;
+        p.tb_fmt = TBF_K1_LF;
+        p.fill_bit = BG_FILL_K1_LF;
+        return p;
+    }
+    const SwFill f = sm == SCORE_PARAMS ? (local ? FILL_K1_LOCAL : FILL_K1)
+                     : sm == SCORE_LDS  ? (local && narrow ? FILL_K1_LDS_LOCAL : FILL_K1_LDS)
+                                        : FILL_K1_GLOBAL;
+    p.r = instantiated_r(f, narrow, cfg.lp, cfg.r);
+    p.fill = sw_fill_get(f, narrow, cfg.lp, p.r);
+    p.fill_bit = narrow ? BG_FILL_K1_NARROW : BG_FILL_K1_WIDE;
+    return p;
 }
 
 // Bytes with identical rows and columns in the 256x256 table are interchangeable: compact the
@@ -222,6 +300,14 @@ static int check_scoring(const bg_scoring_t* sc) {
     return BG_OK;
 }
 
+// a call of the C ABI reports afresh which fills it launched (bg_last_fill_kernels, bg_last_fill_framed); the sub-batches
+// and stages of one call accumulate
+static void reset_fill_report(bg_ctx* ctx) {
+    if (!ctx) return;
+    ctx->fill_mask = 0;
+    ctx->fill_framed = false;
+}
+
 // len_hint: what the caller knows about the lengths of the batch — 1 every pair has the same (m, n), 0 they differ,
 // -1 unknown (a reduction on the device + one stream synchronisation per sub-batch finds out)
 static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint64_t n_pairs,
@@ -302,83 +388,12 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
         a.alpha = A;
     }
 
-    Config cfg = pick_config(max_xlen, sm);
-    const bool all_zero_clips = a.sc.xp == 0 && a.sc.xs == 0 && a.sc.yp == 0 && a.sc.ys == 0;
-    // NARROW kernels need every reachable score inside +-2^25 (sw_kernels.h): bound it by
-    // (longest path) x (largest finite magnitude in the scoring)
-    int64_t mag = std::max<int64_t>(std::abs((int64_t)a.sc.go), std::abs((int64_t)a.sc.ge));
-    for (int32_t c : {a.sc.xp, a.sc.xs, a.sc.yp, a.sc.ys})
-        if (c != BG_MIN_SCORE) mag = std::max<int64_t>(mag, std::abs((int64_t)c));
-    if (sc->matrix) {
-        for (size_t t = 0; t < 65536; t++) mag = std::max<int64_t>(mag, std::abs((int64_t)sc->matrix[t]));
-    } else {
-        mag = std::max<int64_t>(mag, std::max(std::abs((int64_t)a.sc.match), std::abs((int64_t)a.sc.mismatch)));
-    }
-    const bool narrow = !ctx->force_wide && mag * ((int64_t)max_xlen + max_ylen + 8) < (1 << 24);
-    sw_fill_fn fill = sm == SCORE_PARAMS
-                          ? (narrow ? get_fill_params_narrow(cfg.lp, cfg.r, all_zero_clips)
-                                    : get_fill_params_wide(cfg.lp, cfg.r, all_zero_clips))
-                          : get_fill_matrix(cfg.lp, cfg.r, sm, narrow, all_zero_clips);
-    if (!fill && sm != SCORE_PARAMS && cfg.lp == 16 && cfg.r < 12) {
-        // 8 and 10 rows per lane exist for the LDS table with narrow scores only (the protein case they were measured
-        // on); a table beyond 64 classes or wide scores take the 12-row geometry that is instantiated for everything
-        cfg.r = 12;
-        fill = get_fill_matrix(cfg.lp, cfg.r, sm, narrow, all_zero_clips);
-    }
-    // K1's LF flavour (sw_fill.inc): Aligner::local under MatchParams whose gaps and mismatches cost something, scaled
-    // keys, reads of one strip — the reference-width (int32) kernel without the clip machinery such alignments never use
-    a.g.tb_fmt = 0;
-    if (fill && sm == SCORE_PARAMS && narrow && all_zero_clips && a.sc.go < 0 && a.sc.mismatch < 0 && a.sc.match >= 0 &&
-        !ctx->no_local_fast && max_xlen <= (uint32_t)(cfg.lp * cfg.r)) {
-        if (sw_fill_fn lf = get_fill_params_lf(cfg.lp, cfg.r)) {
-            fill = lf;
-            a.g.tb_fmt = 3;
-        }
-    }
-    // K1p: short reads whose scores fit 12 bits (sw_fill_pk16.inc) — two pairs per lane, one instantiation
-    // unit per clip pattern.  Bound: no real DP value, nor the epilogue's go * i terms, may leave +-2040.
-    sw_fill_fn fill_rest = nullptr, fill_second = nullptr;
-    bool pk16 = !ctx->no_pk16 && sm == SCORE_PARAMS && cfg.lp <= 32 && max_xlen >= 1 &&
-                      mag * ((int64_t)std::max(max_xlen, max_ylen) + 2) <= 2040;
-    if (pk16) {
-        const SwScoring& c = a.sc;
-        const int32_t M = BG_MIN_SCORE;
-        // local alignments whose gaps and mismatches cost something take the LF flavour (sw_fill_pk16.inc)
-        // (match >= 0: the LF cell's unsigned mad needs matchkey - mismatchkey >= 0; MatchParams::new asserts it, mod.rs:199-200,
-        //  but nothing in the C API does)
-        const bool local_fast = all_zero_clips && c.go < 0 && c.mismatch < 0 && c.match >= 0 && !ctx->no_local_fast;
-        auto getter = local_fast ? get_fill_pk16_localfast
-                      : all_zero_clips ? get_fill_pk16_local
-                      : (c.xp == M && c.xs == M && c.yp == 0 && c.ys == 0) ? get_fill_pk16_semiglobal
-                      : (c.xp == M && c.xs == M && c.yp == M && c.ys == M) ? get_fill_pk16_global
-                                                                           : get_fill_pk16_custom;
-        // rows per lane: the fast launch wants row m on the last row of a lane (m % R == 0); reads of a
-        // batch usually share one length, so prefer an instantiated R that divides the longest
-        int r_pick = 0;
-        for (int r = (int)((max_xlen + cfg.lp - 1) / cfg.lp); r <= 12 && !r_pick; r++)
-            if (max_xlen % r == 0 && getter(cfg.lp, r, 0)) r_pick = r;
-        for (int r = (int)((max_xlen + cfg.lp - 1) / cfg.lp); r <= 12 && !r_pick; r++)
-            if (getter(cfg.lp, r, 0)) r_pick = r;
-        if (!r_pick) {
-            pk16 = false;  // no K1p instantiation for this shape: the general kernel K1 picked above runs
-        } else {
-            cfg.r = r_pick;
-            // LF keys in the offset frame (its cell does without the clamped gap adds) wherever they fit 15 bits there
-            if (local_fast && !ctx->no_pk16_frame && pk16_frame_fits(c, max_ylen, cfg.r, cfg.lp)) {
-                getter = get_fill_pk16_localframe;
-                ctx->fill_framed = true;
-            }
-            fill = getter(cfg.lp, cfg.r, 0);
-            fill_rest = local_fast ? nullptr : getter(cfg.lp, cfg.r, 1);  // LF: the first launch takes every wavefront
-            fill_second = getter(cfg.lp, cfg.r, 2);
-            a.g.tb_fmt = local_fast ? 2 : 1;
-        }
-    }
-    if (!fill) return BG_ERR_UNSUPPORTED;
-    ctx->fill_mask |= pk16 ? (a.g.tb_fmt == 2 ? BG_FILL_K1P_LF : BG_FILL_K1P)
-                           : a.g.tb_fmt == 3 ? BG_FILL_K1_LF : narrow ? BG_FILL_K1_NARROW : BG_FILL_K1_WIDE;
+    const FillPlan plan = plan_fill(*ctx, a.sc, sm, score_magnitude(a.sc, sc->matrix), max_xlen, max_ylen);
+    if (!plan.fill) return BG_ERR_UNSUPPORTED;
+    ctx->fill_mask |= plan.fill_bit;
+    if (plan.framed) ctx->fill_framed = true;
     if (packed_codes) {
-        if (pk16) {
+        if (plan.k1p) {
             a.packed = 1;  // K1p reads the 2-bit streams as they are
         } else {
             // every other kernel takes bytes: the streams are unpacked into ctx scratch (two totals come back to the host)
@@ -394,17 +409,18 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
             a.y = (const uint8_t*)ctx->unpk[1];
         }
     }
-    const int nw = tb_words(cfg.r);
-    const uint32_t pw = 64 / cfg.lp;
+    const int nw = tb_words(plan.r);
+    const uint32_t pw = 64 / plan.lp;
     SwGeom& g = a.g;
-    g.lp = cfg.lp;
-    g.r = cfg.r;
-    g.r_inv = (uint32_t)(((1ull << 32) + cfg.r - 1) / cfg.r);
-    g.lp_shift = cfg.lp == 16 ? 4 : cfg.lp == 32 ? 5 : 6;
+    g.lp = plan.lp;
+    g.r = plan.r;
+    g.tb_fmt = plan.tb_fmt;
+    g.r_inv = (uint32_t)(((1ull << 32) + plan.r - 1) / plan.r);
+    g.lp_shift = plan.lp == 16 ? 4 : plan.lp == 32 ? 5 : 6;
     g.m_cap = max_xlen;
     g.n_cap = max_ylen;
-    g.nsteps = max_ylen ? max_ylen + cfg.lp - 1 : 0;
-    g.nstrips = std::max<uint32_t>(1, (max_xlen + cfg.lp * cfg.r - 1) / (cfg.lp * cfg.r));
+    g.nsteps = max_ylen ? max_ylen + plan.lp - 1 : 0;
+    g.nstrips = std::max<uint32_t>(1, (max_xlen + plan.lp * plan.r - 1) / (plan.lp * plan.r));
     g.aux_stride = SwGeom::stride_for(max_xlen, max_ylen);
 
     // scratch per wavefront job / per pair
@@ -426,7 +442,7 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
     a.bnd = (int4*)ctx->bnd;
     // K1p on a ragged batch: slots in (m, n) order (the strip buffer is free: K1p has one strip)
     uint32_t *d_keycnt = nullptr, *d_keysum = nullptr, *d_perm = nullptr, *d_lenst = nullptr;
-    if (pk16 && !ctx->no_couples) {
+    if (plan.k1p && !ctx->no_couples) {
         const size_t need = (size_t)kLenKeys * 4 + 1024 * 4 + 64 + chunk * 4;
         if ((rc = bg_reserve(&ctx->bnd, &ctx->bnd_bytes, need))) return rc;
         a.bnd = (int4*)ctx->bnd;
@@ -464,13 +480,13 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
             a.n_eff = d_lenst + 4;
         }
         if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[0], st));
-        const uint32_t nwaves = pk16 ? (njobs + 1) / 2 : njobs;  // a K1p wavefront takes two jobs
-        fill<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);
+        const uint32_t nwaves = plan.k1p ? (njobs + 1) / 2 : njobs;  // a K1p wavefront takes two jobs
+        plan.fill<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);
         BG_HIP(hipGetLastError());
         if (ctx->timing) BG_HIP(hipEventRecord(ctx->ev[1], st));
         // what the fast launch skipped: wavefronts with other read lengths, then the second pairs of unequal couples
-        if (fill_rest) fill_rest<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);
-        if (fill_second && len_hint != 1) fill_second<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);  // (1: the caller knows the lengths agree)
+        if (plan.fill_rest) plan.fill_rest<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);
+        if (plan.fill_second && len_hint != 1) plan.fill_second<<<dim3((nwaves + 3) / 4), dim3(256), 0, st>>>(a);  // (1: the caller knows the lengths agree)
         BG_HIP(hipGetLastError());
         if (ctx->timing) {
             BG_HIP(hipEventSynchronize(ctx->ev[1]));
@@ -507,10 +523,7 @@ extern "C" int bg_align_batch_dev(bg_ctx* ctx, const bg_scoring_t* sc, int mode,
                                   const uint64_t* d_y_off, uint32_t max_xlen, uint32_t max_ylen,
                                   bg_alignment_t* d_out, uint8_t* d_ops, uint64_t ops_stride,
                                   void* stream) {
-    if (ctx) {
-        ctx->fill_mask = 0;
-        ctx->fill_framed = false;
-    }
+    reset_fill_report(ctx);
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, d_x, d_x_off, d_y, d_y_off, max_xlen, max_ylen, d_out, d_ops, ops_stride, stream, -1);
 }
 
@@ -525,10 +538,7 @@ extern "C" int bg_align_batch_packed_dev(bg_ctx* ctx, const bg_scoring_t* sc, in
     for (int a = 0; a < 4; a++)
         for (int b = a + 1; b < 4; b++)
             if (codes[a] == codes[b]) return BG_ERR_INVALID_ARG;
-    if (ctx) {
-        ctx->fill_mask = 0;
-        ctx->fill_framed = false;
-    }
+    reset_fill_report(ctx);
     return align_batch_dev_impl(ctx, sc, mode, n_pairs, (const uint8_t*)d_x, d_x_off, (const uint8_t*)d_y, d_y_off, max_xlen, max_ylen,
                                 d_out, d_ops, ops_stride, stream, -1, codes);
 }
@@ -845,8 +855,7 @@ extern "C" int bg_align_batch(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uin
                               const uint64_t* y_off, bg_alignment_t* out, uint8_t* ops_buf,
                               uint64_t ops_cap, uint64_t* ops_used) {
     if (!ctx || !sc) return BG_ERR_INVALID_ARG;
-    ctx->fill_mask = 0;
-    ctx->fill_framed = false;
+    reset_fill_report(ctx);
     int rc = check_scoring(sc);
     if (rc) return rc;
     if (ops_used) *ops_used = 0;

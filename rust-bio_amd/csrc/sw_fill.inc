@@ -1,4 +1,4 @@
-// K1 — sw_fill_kernel<R, LP, SM>.  Included by the sw_fill_*.hip instantiation units.
+// K1 — sw_fill_kernel<R, LP, SM>.  Included by its instantiation unit, sw_fill_k1.hip.
 // Design notes: sw_kernels.h.  Reference: pairwise/mod.rs:597-843.
 #include <type_traits>
 
@@ -42,10 +42,10 @@ __device__ __forceinline__ void scan_first_max(int ll, int64_t& v, uint32_t& idx
 // Lx[j < n] (K2 fails loudly should a path ever ask for one), column n's fold is one more scan of the epilogue
 // (EPI_FOLD_PRE).  I and D values carry their candidate priority with them (score << 4 | priority << 1 | opened: K3i's
 // keys, banded_fill2i.hip) — no clearing and or-ing per cell — and Sn / Ly are kept per block of 16 steps (one or and
-// one max per cell).  Traceback cells: tb_fmt 3 — six 5-bit cells per word like tb_fmt 0, each I opened | move << 1 |
+// one max per cell).  Traceback cells: TBF_K1_LF — six 5-bit cells per word like TBF_K1, each I opened | move << 1 |
 // D opened << 4.
 #ifndef K1_WAVES  // wavefronts per SIMD K1 is compiled for (0: the compiler's choice — 233 VGPRs, two wavefronts, for R = 10; variant
-#define K1_WAVES 0  // builds: tools/exp/ko_build.sh sw_fill_params_lf.hip k1w3 -DK1_WAVES=3)
+#define K1_WAVES 0  // builds: tools/exp/ko_build.sh sw_fill_k1.hip k1w3 -DK1_WAVES=3)
 #endif
 #if K1_WAVES
 #define K1_OCC __attribute__((amdgpu_waves_per_eu(K1_WAVES, K1_WAVES)))
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) K1_OCC void sw_fill_kernel(const SwArgs a) {
             for (int r = 0; r < R; r++) Il[r] &= ~15;
         }
         {
-            // the packed cell of row r in column n, in tb_fmt 0's layout (move | I extended << 3 | D extended << 4)
+            // the packed cell of row r in column n, in TBF_K1's layout (move | I extended << 3 | D extended << 4)
             auto cell_of = [&](int r) -> uint32_t {
                 const uint32_t v = (wlast[r / 6] >> (5 * (r % 6))) & 31u;
                 return LF ? (((v >> 1) & 7u) | ((~v & 1u) << 3) | (~v & 16u)) : v;

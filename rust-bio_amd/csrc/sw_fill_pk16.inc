@@ -13,7 +13,7 @@
 // batches the slots hold the pairs in (m, n) order (SwArgs::perm, built in sw_api.hip), so that couples of
 // equal lengths are the rule.
 // Traceback words: 3 cells x 5 bits (I extends | move << 1 | D extends << 4) per 16-bit half
-// (SwGeom::tb_fmt == 1), same tiles as K1.
+// (SwGeom::tb_fmt == TBF_K1P), same tiles as K1.
 #include <type_traits>
 
 #include "sw_kernels.h"
@@ -78,7 +78,7 @@ enum { CZ = 0, CF = 1, CI = 2 };
 // of row m out of every step, and makes every wavefront a "fast" one (row m is nothing special during the fill: one
 // launch).  The local floor 0 (the x-prefix-clip candidate, mod.rs:765-768) comes out of the unsigned saturation of the
 // substitution score instead of one more maximum — the move code of such a cell is 0, which K2 and the epilogue read as
-// C_XP (SwGeom::tb_fmt == 2).
+// C_XP (SwGeom::tb_fmt == TBF_K1P_LF).
 // FR (LF only, where pk16_frame_fits): the keys live in an offset frame, K^ = K + B + g (r + s) with r the row within the
 // lane, s the step, g = 16 |ge| and B = pk16_frame_bias (sw_kernels.h).  A gap extension is then no instruction at all
 // (I^(r, s) = I^(r - 1, s), D^(r, s) = D^(r, s - 1)), the opens and the diagonal differ from their sources by constants,
@@ -625,7 +625,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3
 }  // namespace pk16
 }  // namespace bgsw
 
-// one instantiation unit per clip pattern: BG_PK16_GETTER(name, XP, XS, YP, YS, cases)
+// shape (LP_, R_) of a unit's getter (sw_fill_get_K1P_*, one unit per clip pattern), expanded over a shape list of
+// sw_kernels.h with the unit's clips XP_ .. YS_ and flavour LF_, FR_ in scope
 #define BG_PK16_CASE(LP_, R_)                                                                          \
     if (lp == LP_ && r == R_)                                                                         \
         return which == 0   ? pk16::sw_fill_pk16_kernel<R_, LP_, XP_, XS_, YP_, YS_, LF_, FR_>        \

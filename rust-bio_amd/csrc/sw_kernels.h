@@ -76,12 +76,20 @@ inline bool pk16_frame_fits(const SwScoring& sc, uint32_t max_ylen, int r, int l
     return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x8000;
 }
 
+// traceback cell formats (SwGeom::tb_fmt): what the fill writes and K2 decodes
+enum : uint32_t {
+    TBF_K1 = 0,      // K1: six 5-bit cells per word, each move | I extends << 3 | D extends << 4
+    TBF_K1P = 1,     // K1p (sw_fill_pk16.inc): three cells per 16-bit half, each I extends | move << 1 | D extends << 4
+    TBF_K1P_LF = 2,  // K1p's LF flavour: as TBF_K1P, and move code 0 stands for C_XP (the floor of a local alignment)
+    TBF_K1_LF = 3    // K1's LF flavour (sw_fill.inc): TBF_K1's packing, each cell I opened | move << 1 | D opened << 4
+};
+
 // aux record of one pair (int32 words):
 //   [0] S nibble of (m,0)   [1] score = S[n%2][m] after the epilogue   [2] Lx[n] after the epilogue
 //   Ly[m_cap+1]  Lx[n_cap+1]  colBits[m_cap+1 bytes]: (S nibble | I nibble << 4) of column n
 struct SwGeom {
     uint32_t lp, r, nsteps, nstrips, m_cap, n_cap, aux_stride;
-    uint32_t tb_fmt;  // 0: six 5-bit cells per word (K1); 1: three per 16-bit half (K1p, sw_fill_pk16.inc); 2: as 1, move code 0 == C_XP (K1p LF)
+    uint32_t tb_fmt;    // TBF_*
     uint32_t r_inv;     // ceil(2^32 / r): (row * r_inv) >> 32 == row / r for row < 2^24 (K2 divides per traceback step)
     uint32_t lp_shift;  // log2(lp)
     __host__ __device__ uint32_t off_Ly() const { return 4; }
@@ -258,6 +266,35 @@ __device__ __forceinline__ uint32_t s_nibble_of_code(uint32_t code) {
 }
 
 typedef void (*sw_fill_fn)(const SwArgs);
+
+// ---- the instantiated fill kernels ------------------------------------------------------------------------------
+// Shape sets (lanes per pair, rows per lane), each written once; the instantiation units expand them.
+#define BG_K1_SHAPES(X) X(16, 2) X(16, 4) X(16, 6) X(16, 8) X(16, 10) X(16, 12) X(32, 8) X(32, 10) X(32, 12) X(64, 8)
+// tabulated match functions: 8 and 10 rows per lane exist for the LDS table with narrow keys only (the protein case
+// they were measured on)
+#define BG_K1_TABLE_SHAPES(X) X(16, 6) X(16, 12) X(32, 12) X(64, 8)
+#define BG_K1_TABLE_LDS_NARROW_SHAPES(X) BG_K1_TABLE_SHAPES(X) X(16, 8) X(16, 10)
+// K1p with a fixed clip pattern (custom, global, semiglobal), and Aligner::local (plain, LF, framed LF)
+#define BG_K1P_SHAPES(X) X(16, 2) X(16, 4) X(16, 5) X(16, 6) X(16, 8) X(16, 10) X(16, 12) X(32, 8) X(32, 10) X(32, 12)
+#define BG_K1P_LOCAL_SHAPES(X)                                                                                    \
+    X(16, 2) X(16, 3) X(16, 4) X(16, 5) X(16, 6) X(16, 7) X(16, 8) X(16, 9) X(16, 10) X(16, 11) X(16, 12) \
+    X(32, 7) X(32, 8) X(32, 9) X(32, 10) X(32, 11) X(32, 12)
+
+// Fill families: the template flavours of K1 (sw_fill_k1.hip) and K1p (sw_fill_pk16_*.hip).  LOCAL: Aligner::local's
+// cell; LDS / GLOBAL: a tabulated match function in LDS / read from HBM.  sw_fill_get_<family>(narrow, lp, r, which)
+// returns the family's kernel for narrow or wide keys (K1; K1_LF and K1_LDS_LOCAL exist narrow only, K1p ignores it),
+// lp lanes per pair, r rows per lane and launch `which` (K1p: 0 the fast launch, 1 the rest, 2 the second pairs), or
+// nullptr where that is not instantiated.  plan_fill (sw_api.hip) is the one place that chooses among them.
+#define BG_SW_FILLS(X) \
+    X(K1) X(K1_LOCAL) X(K1_LF) X(K1_LDS) X(K1_LDS_LOCAL) X(K1_GLOBAL) X(K1P_CUSTOM) X(K1P_GLOBAL) X(K1P_SEMIGLOBAL) X(K1P_LOCAL) X(K1P_LF) X(K1P_LF_FRAMED)
+enum SwFill {
+#define BG_X(F) FILL_##F,
+    BG_SW_FILLS(BG_X)
+#undef BG_X
+};
+#define BG_X(F) sw_fill_fn sw_fill_get_##F(bool narrow, int lp, int r, int which);
+BG_SW_FILLS(BG_X)
+#undef BG_X
 
 }  // namespace bgsw
 #endif

@@ -54,7 +54,8 @@ def local_flavour(kw, clips4):  # sw_api.hip: the LF flavours (Aligner::local wi
 
 
 def sw_fill(kw, mode, clips, max_x, max_y, opts=None):
-    """the one fill family an Aligner call launches"""
+    """the one fill family an Aligner call launches: plan_fill (sw_api.hip) in the same order — K1p if admitted, K1's
+    LF flavour if admitted and x fits one strip, else K1 by its keys"""
     opts = opts or {}
     c4 = mode_clips(mode, clips)
     mag = magnitude(kw, c4)
