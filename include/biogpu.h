@@ -85,7 +85,7 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
 /* Tunables (0 keeps the default) and the switches the tests use to reach every kernel variant:
  *   chunk_pairs        pairs per sub-batch of bg_align_batch_dev (default 2^20) and of the banded pipeline (16384)
  *   host_chunk_pairs   pairs per stage of bg_align_batch's pipelined host path (122880)
- *   seed_chunk_reads   reads per pass of bg_seed_extend[_strands|_pairs]_batch[_dev] (0: equal passes of at most 2^21
+ *   seed_chunk_reads   reads per pass of bg_seed_extend[_strands|_pairs|_multi]_batch[_dev] (0: equal passes of at most 2^21
  *                      reads, 2^20 with both strands and with pairs; pairs round it down to an even count, at least 2)
  *   force_wide = 1     scores kept as plain int32 even where they fit the 24-bit keys of the fast kernels
  *   no_pk16 = 1        no packed-int16 fill (K1p): the int32 kernel K1 runs for every batch
@@ -570,6 +570,53 @@ int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_s
                                    uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                    bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_ops,
                                    uint64_t ops_stride, uint64_t* totals, void* stream);
+/* Runner-up loci and a mapping quality.  The strands call reports one alignment per read, so a read inside a two-copy repeat and
+ * a read that maps uniquely look the same.  The multi call reports up to K = max_hits loci per read and a MAPQ: hits / strand
+ * have K slots per read (hits[K r + k]), multi one record per read.
+ *   candidates       those of bg_seed_extend_strands_batch with the same `strands`, numbered with the forward strand first and
+ *                    in ascending proposed start within a strand; ref_start / ref_end are forward-text coordinates;
+ *   rank             by score, the highest first; among equal scores the smaller candidate number (the strands call's best
+ *                    hit is rank 0);
+ *   loci             walk the candidates in rank order.  A candidate is kept as the next locus unless its text interval
+ *                    touches or overlaps that of a locus already kept: a.ref_start <= b.ref_end && b.ref_start <= a.ref_end,
+ *                    whatever the two strands (candidates that were not kept suppress nothing).  A candidate that scores below
+ *                    min_score is never kept.  The walk stops after max(K, 2) loci;
+ *   reported         loci 0 .. min(n_loci, K) - 1 fill the read's slots in that order, each a complete bg_seed_hit_t with its
+ *                    strand and operations exactly as the strands call would write that candidate.  An unused slot is written
+ *                    like an unmapped read (score BG_MIN_SCORE, positions UINT64_MAX, n_ops 0, strand BG_HIT_NONE).
+ *                    n_candidates / n_seed_hits are the read's, repeated in every slot;
+ *   MAPQ             in integers: s1 = the score of locus 0, s2 = the score of locus 1, or 0 if there is none.  mapq = 0 if there
+ *                    is no locus, s1 <= 0 or s2 >= s1; otherwise min(mapq_cap, mapq_cap * (s1 - max(s2, 0)) / s1), 64-bit, the
+ *                    division truncating.  The runner-up is found even when K = 1.
+ * With min_score = INT32_MIN, slot 0 of every read is what bg_seed_extend_strands_batch[_dev] reports for it with the same
+ * `strands`, field by field and operation by operation.  Device operation slots: slot K r + k ends at d_ops + (K r + k + 1) *
+ * ops_stride (the same minimum stride); the host flavour compacts operations in slot order.  BG_ERR_INVALID_ARG: max_hits 0 or
+ * above BG_SEED_MAX_HITS, mapq_cap above 254, a null mp or multi; every other check, limit, the out-of-alphabet rule, totals,
+ * passes and seed_chunk_reads are the strands call's.
+ * Known limit: inside a tandem repeat whose period is shorter than the read, the shifted copies overlap and count as one
+ * locus, so MAPQ there is optimistic. */
+enum { BG_SEED_MAX_HITS = 8 };
+typedef struct {
+    uint32_t max_hits;   /* K: hits reported per read, 1 ..= BG_SEED_MAX_HITS */
+    int32_t  min_score;  /* a candidate scoring below this is neither reported nor counted as a runner-up */
+    uint32_t mapq_cap;   /* MAPQ of a read without a runner-up; 0 ..= 254 (255 means "unavailable" in SAM) */
+} bg_multi_params_t;
+typedef struct {
+    int32_t  sub_score;  /* score of the runner-up locus (locus 1), BG_MIN_SCORE if there is none */
+    uint32_t n_loci;     /* loci found by the rule above, counted up to max(K, 2) */
+    uint8_t  n_reported; /* min(n_loci, K): how many of the read's K slots are filled */
+    uint8_t  mapq;
+    uint8_t  reserved[6];
+} bg_multi_hit_t;        /* 16 bytes */
+int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
+                               uint32_t strands, uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off,
+                               bg_seed_hit_t* hits, uint8_t* strand, bg_multi_hit_t* multi, uint8_t* ops_buf, uint64_t ops_cap,
+                               uint64_t* ops_used);
+/* Device flavour (totals and passes as bg_seed_extend_strands_batch_dev). */
+int bg_seed_extend_multi_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
+                                   uint32_t strands, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
+                                   uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_multi_hit_t* d_multi,
+                                   uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream);
 /* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
  * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
 int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);

@@ -736,6 +736,59 @@ public:
         }
         return res;
     }
+    // Runner-up loci and MAPQ (bg_seed_extend_multi_batch): up to max_hits loci per read whose text intervals do not touch, the best
+    // first (hits[0] is what seed_extend_batch_strands reports), the runner-up's score and a MAPQ in 0 ..= mapq_cap: 0 where the
+    // runner-up scores as much as the best, mapq_cap where there is none.  A candidate below min_score is neither reported nor a
+    // runner-up.
+    struct MultiSeedHit {
+        std::vector<StrandedSeedHit> hits;  // the read's loci in rank order (empty: unmapped)
+        uint8_t mapq = 0;
+        int32_t sub_score = BG_MIN_SCORE;   // of the runner-up locus; BG_MIN_SCORE if there is none
+        uint32_t n_loci = 0;                // loci found, counted up to max(max_hits, 2)
+    };
+    std::vector<MultiSeedHit> seed_extend_batch_multi(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                      uint32_t max_hits = 1, int32_t min_score = INT32_MIN, uint32_t mapq_cap = 60,
+                                                      uint32_t strands = BG_STRAND_BOTH, uint32_t seed_len = 20, uint32_t stride = 10,
+                                                      uint32_t max_occ = 16, uint32_t pad = 25) const {
+        if (max_hits == 0 || max_hits > BG_SEED_MAX_HITS) throw std::invalid_argument("seed_extend_batch_multi: max_hits outside 1 ..= 8");
+        std::vector<int32_t> table;
+        const bg_scoring_t sc = scoring.to_c(table);
+        const bg_seed_params_t prm = {seed_len, stride, max_occ, pad};
+        const bg_multi_params_t mp = {max_hits, min_score, mapq_cap};
+        Text buf;
+        std::vector<uint64_t> off{0};
+        for (auto& r : reads) {
+            buf.insert(buf.end(), r.begin(), r.end());
+            off.push_back(buf.size());
+        }
+        const size_t K = max_hits;
+        std::vector<bg_seed_hit_t> hits(reads.size() * K);
+        std::vector<uint8_t> strand(reads.size() * K);
+        std::vector<bg_multi_hit_t> multi(std::max<size_t>(reads.size(), 1));
+        std::vector<uint8_t> ops(K * (2 * buf.size() + (2 * (size_t)pad + 4) * reads.size() + 8));
+        uint64_t used = 0;
+        const int rc = bg_seed_extend_multi_batch(h_, &sc, &prm, &mp, strands, reads.size(), buf.data(), off.data(), hits.data(),
+                                                  strand.data(), multi.data(), ops.data(), ops.size(), &used);
+        if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
+        check(rc, "bg_seed_extend_multi_batch");
+        std::vector<MultiSeedHit> res(reads.size());
+        for (size_t r = 0; r < reads.size(); r++) {
+            res[r].mapq = multi[r].mapq;
+            res[r].sub_score = multi[r].sub_score;
+            res[r].n_loci = multi[r].n_loci;
+            res[r].hits.resize(multi[r].n_reported);
+            for (size_t k = 0; k < multi[r].n_reported; k++) {
+                const bg_seed_hit_t& h = hits[r * K + k];
+                StrandedSeedHit& o = res[r].hits[k];
+                o.alignment = alignment::pairwise::detail::to_alignment(h.aln, ops.data());
+                o.ref_start = (size_t)h.ref_start;
+                o.ref_end = (size_t)h.ref_end;
+                o.n_candidates = h.n_candidates;
+                o.reverse = strand[r * K + k] == BG_HIT_REVERSE;
+            }
+        }
+        return res;
+    }
     bg_fm* raw() const { return h_; }
     size_t len() const { return n_; }
 

@@ -93,6 +93,20 @@ PAIR_HIT_DTYPE = np.dtype([("span", "<u8"), ("n_proper", "<u4"), ("proper", "u1"
 assert PAIR_HIT_DTYPE.itemsize == 16, PAIR_HIT_DTYPE.itemsize
 
 
+# bg_multi_params_t (bg_seed_extend_multi_batch[_dev])
+SEED_MAX_HITS = 8
+
+
+class MULTI_PARAMS(C.Structure):
+    _fields_ = [("max_hits", C.c_uint32), ("min_score", C.c_int32), ("mapq_cap", C.c_uint32)]
+
+
+assert C.sizeof(MULTI_PARAMS) == 12, C.sizeof(MULTI_PARAMS)
+# bg_multi_hit_t
+MULTI_HIT_DTYPE = np.dtype([("sub_score", "<i4"), ("n_loci", "<u4"), ("n_reported", "u1"), ("mapq", "u1"), ("reserved", "u1", (6,))])
+assert MULTI_HIT_DTYPE.itemsize == 16, MULTI_HIT_DTYPE.itemsize
+
+
 # bg_fastq_record_t
 FQREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"),
                         ("id_len", "<u4"), ("desc_len", "<u4"), ("seq_len", "<u4"), ("qual_len", "<u4"),
@@ -111,6 +125,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
+           "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
@@ -229,6 +244,10 @@ def lib():
                                                  vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_pairs_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp,
                                                      u32, vp, vp, vp, vp, u64, vp, vp]
+        L.bg_seed_extend_multi_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp, vp,
+                                                 vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.bg_seed_extend_multi_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp,
+                                                     vp, u32, vp, vp, vp, vp, u64, vp, vp]
         L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]

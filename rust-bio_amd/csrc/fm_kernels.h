@@ -341,5 +341,13 @@ int bg_fm_search_seeds_dev(bg_fm* fm, uint64_t n_reads, const uint8_t* d_reads, 
 int bg_seed_pairs_launch(const bg_pair_params_t* pp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff, const uint32_t* d_n_hits,
                          const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits,
                          uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint32_t max_cand, hipStream_t st);
+// seed_multi.hip: S7 of bg_seed_extend_multi_batch_dev over one pass (n_reads reads from caller read r0 on, G virtual reads
+// each; strand1: the strand of every hit when G = 1), on the same pass scratch.  Read r0 + r owns slots K (r0 + r) ..
+// K (r0 + r) + K - 1 of d_hits / d_strand / d_ops and record r0 + r of d_multi.  max_cand bounds the candidates of one
+// virtual read.
+int bg_seed_multi_launch(const bg_multi_params_t* mp, uint32_t G, uint8_t strand1, uint64_t n_reads, uint64_t r0, const uint64_t* d_coff,
+                         const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
+                         bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_multi_hit_t* d_multi,
+                         uint32_t max_cand, hipStream_t st);
 
 #endif

@@ -22,7 +22,9 @@
 //   S6 align            Aligner::semiglobal on every candidate (bg_align_batch_dev)      -> records + operations
 //   S7 best             per read: highest score, smallest start among equals           -> bg_seed_hit_t + its ops
 //      (pair mode, bg_seed_extend_pairs_batch[_dev]: per pair of interleaved mates, the best proper FR combination of their
-//       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t)
+//       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t;
+//       multi mode, bg_seed_extend_multi_batch[_dev]: per read up to K loci that do not touch, in rank order -> K bg_seed_hit_t +
+//       their ops, bg_multi_hit_t with the runner-up's score and MAPQ)
 #include <algorithm>
 
 #include "fm_kernels.h"
@@ -383,10 +385,12 @@ namespace {
 // se_strands_kernel.  Stages S1-S6 run unchanged on the virtual reads; S7 picks each caller read's best over its G.
 // Pair mode (`pair` set, strands = BG_STRAND_BOTH, n_reads = 2 n_pairs interleaved mates): passes hold whole pairs and
 // se_pair_kernel replaces S7, writing d_pairs as well.
+// Multi mode (`multi` set): se_multi_kernel replaces S7; d_hits / d_strand / d_ops hold multi->max_hits slots per read, d_multi one
+// record per read.
 int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
            const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
            uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
-           bg_pair_hit_t* d_pairs = nullptr) {
+           bg_pair_hit_t* d_pairs = nullptr, const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* d_multi = nullptr) {
     if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
     if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
     if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
@@ -522,6 +526,10 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
             if ((rc = bg_seed_pairs_launch(pair, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_pairs,
                                            kMaxProposals, st)))
                 return rc;
+        } else if (multi) {
+            if ((rc = bg_seed_multi_launch(multi, G, strands == BG_STRAND_REVERSE ? BG_HIT_REVERSE : BG_HIT_FORWARD, nr, r0, d_coff, d_nh,
+                                           d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_multi, kMaxProposals, st)))
+                return rc;
         } else if (G == 2)
             se_best_kernel<2><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
                                                                d_strand, 0);
@@ -578,6 +586,27 @@ extern "C" int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc,
                   stream, pp, d_pairs);
 }
 
+namespace {
+
+// the multi calls' own argument checks; every other one is se_run's
+int multi_args(const bg_multi_params_t* mp, const void* multi, uint32_t strands, uint64_t n_reads) {
+    if (!mp || !multi || mp->max_hits == 0 || mp->max_hits > BG_SEED_MAX_HITS || mp->mapq_cap > 254 || strands < BG_STRAND_FORWARD ||
+        strands > BG_STRAND_BOTH || n_reads > (UINT64_MAX >> 8))
+        return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_seed_extend_multi_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
+                                              uint32_t strands, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
+                                              uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_multi_hit_t* d_multi,
+                                              uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (int rc = multi_args(mp, d_multi, strands, n_reads)) return rc;
+    return se_run(fm, sc, prm, strands, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals, stream,
+                  nullptr, nullptr, mp, d_multi);
+}
+
 extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream) {
     if (!ctx || (n && (!d_in || !d_off || !d_out))) return BG_ERR_INVALID_ARG;
     if (n == 0) return BG_OK;
@@ -589,10 +618,12 @@ extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in
 
 namespace {
 
-// the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order
+// the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order (multi mode:
+// multi->max_hits slots per read in hits / strand, compacted in slot order)
 int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
                 const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
-                uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr) {
+                uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr,
+                const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* multis = nullptr) {
     if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (n_reads == 0) return BG_OK;
@@ -608,28 +639,32 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     uint8_t* d_strand = nullptr;
     bg_seed_hit_t* d_hits = nullptr;
     bg_pair_hit_t* d_pairs = nullptr;
+    bg_multi_hit_t* d_multi = nullptr;
+    const uint64_t n_slots = n_reads * (multi ? multi->max_hits : 1);
     std::vector<uint8_t> h_ops;
     int panic_rc = BG_OK;
     auto run = [&]() -> int {
         hipStream_t st = ctx->stream;
         BG_HIP(hipMalloc((void**)&d_reads, std::max<uint64_t>(bytes, 16)));
         BG_HIP(hipMalloc((void**)&d_off, (n_reads + 1) * 8));
-        BG_HIP(hipMalloc((void**)&d_hits, n_reads * sizeof(bg_seed_hit_t)));
-        if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_reads * stride));
-        if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_reads));
+        BG_HIP(hipMalloc((void**)&d_hits, n_slots * sizeof(bg_seed_hit_t)));
+        if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_slots * stride));
+        if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_slots));
         if (pair) BG_HIP(hipMalloc((void**)&d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t)));
+        if (multi) BG_HIP(hipMalloc((void**)&d_multi, n_reads * sizeof(bg_multi_hit_t)));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st,
-                        pair, d_pairs);
+                        pair, d_pairs, multi, d_multi);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
-        BG_HIP(hipMemcpyAsync(hits, d_hits, n_reads * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
-        if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_reads, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipMemcpyAsync(hits, d_hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
+        if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_slots, hipMemcpyDeviceToHost, st));
         if (pair) BG_HIP(hipMemcpyAsync(pairs, d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
+        if (multi) BG_HIP(hipMemcpyAsync(multis, d_multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
         if (stride) {
-            h_ops.resize(n_reads * stride);
-            BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_reads * stride, hipMemcpyDeviceToHost, st));
+            h_ops.resize(n_slots * stride);
+            BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_slots * stride, hipMemcpyDeviceToHost, st));
         }
         BG_HIP(hipStreamSynchronize(st));
         return BG_OK;
@@ -641,11 +676,12 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     hipFree(d_ops);
     hipFree(d_strand);
     hipFree(d_pairs);
+    hipFree(d_multi);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
     uint64_t used = 0;
     int status = BG_OK;
-    for (uint64_t r = 0; r < n_reads; r++) {
+    for (uint64_t r = 0; r < n_slots; r++) {
         bg_alignment_t& a = hits[r].aln;
         if (a.status) status = a.status;
         if (ops_buf) {
@@ -681,4 +717,12 @@ extern "C" int bg_seed_extend_pairs_batch(bg_fm* fm, const bg_scoring_t* sc, con
                                           uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
     return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs);
+}
+
+extern "C" int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
+                                          uint32_t strands, uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off,
+                                          bg_seed_hit_t* hits, uint8_t* strand, bg_multi_hit_t* multi, uint8_t* ops_buf, uint64_t ops_cap,
+                                          uint64_t* ops_used) {
+    if (int rc = multi_args(mp, multi, strands, n_reads)) return rc;
+    return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, nullptr, nullptr, mp, multi);
 }

@@ -6,7 +6,8 @@ seeds vote, hit -> proposed read start, per-read dedup, window gather, best-hit 
 operations — runs in HIP kernels behind the C ABI (rust-bio_amd/csrc/seed_extend.hip); its definition is in
 include/biogpu.h (the tests hold a CPU statement of it).  The `_strands` calls map each read on the forward strand, on
 the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  The `_pairs` calls map interleaved mates of
-paired-end reads and report the best proper FR pair where there is one.  This module only marshals arguments."""
+paired-end reads and report the best proper FR pair where there is one.  The `_multi` calls report up to K loci per read that
+do not touch, the runner-up's score and a MAPQ.  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -32,6 +33,17 @@ class PairParams:
 
     def to_c(self):
         return _lib.PAIR_PARAMS(self.min_span, self.max_span, self.pen_unpaired)
+
+
+class MultiParams:
+    """bg_multi_params_t: max_hits (K, 1 ..= 8) loci reported per read; a candidate scoring below min_score is neither reported
+    nor counted as a runner-up; mapq_cap (0 ..= 254) is the MAPQ of a read without a runner-up."""
+
+    def __init__(self, max_hits=1, min_score=-2**31, mapq_cap=60):
+        self.max_hits, self.min_score, self.mapq_cap = max_hits, min_score, mapq_cap
+
+    def to_c(self):
+        return _lib.MULTI_PARAMS(self.max_hits, self.min_score, self.mapq_cap)
 
 
 def attach_text(fm, text=None, d_text=None):
@@ -148,6 +160,46 @@ def seed_extend_pairs_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_le
                                                          max_read_len, d_hits, d_strand or None, d_pairs or None, d_ops or None,
                                                          ops_stride, totals.ctypes.data if totals is not None else None, stream),
                "bg_seed_extend_pairs_batch_dev")
+
+
+def seed_extend_multi_arrays(fm, scoring, reads, read_off, params=None, multi_params=None, strands=_lib.STRAND_BOTH, want_ops=True,
+                             allow_out_of_alphabet=False):
+    """bg_seed_extend_multi_batch, host buffers.  With K = multi_params.max_hits, returns (hits: SEED_HIT_DTYPE[n, K], strand:
+    uint8[n, K], multi: MULTI_HIT_DTYPE[n], ops: the reported hits' operations back to back in slot order): read r's loci are
+    hits[r, :multi["n_reported"][r]], the best first; the other slots read like an unmapped read.  Errors as seed_extend_arrays."""
+    params = params or SeedParams()
+    multi_params = multi_params or MultiParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    K = max(int(multi_params.max_hits), 1) if 0 < multi_params.max_hits <= _lib.SEED_MAX_HITS else 1  # (the call rejects the rest)
+    hits = np.zeros((n, K), dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n * K, 1), dtype=np.uint8)
+    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
+    cap = K * (int(2 * off[-1] + (2 * params.pad + 4) * n) + 8) if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc, mp = scoring.to_c(), params.to_c(), multi_params.to_c()
+    rc = _lib.lib().bg_seed_extend_multi_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(mp), strands, n, rd.ctypes.data, off.ctypes.data,
+                                               hits.ctypes.data, strand.ctypes.data, multi.ctypes.data,
+                                               ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_multi_batch")
+    return hits, strand[:n * K].reshape(n, K), multi[:n], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_multi_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_multi, d_strand=0, d_ops=0, ops_stride=0,
+                          params=None, multi_params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
+    """bg_seed_extend_multi_batch_dev (pointers are ints; d_hits / d_strand / d_ops hold max_hits slots per read, slot K r + k,
+    d_multi n_reads bg_multi_hit_t; d_strand / d_ops may be 0); `totals` as seed_extend_strands_dev."""
+    params = params or SeedParams()
+    multi_params = multi_params or MultiParams()
+    sc, pc, mp = scoring.to_c(), params.to_c(), multi_params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_multi_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(mp), strands, n_reads, d_reads,
+                                                         d_read_off, max_read_len, d_hits, d_strand or None, d_multi or None,
+                                                         d_ops or None, ops_stride, totals.ctypes.data if totals is not None else None,
+                                                         stream),
+               "bg_seed_extend_multi_batch_dev")
 
 
 def revcomp_dev(n, d_in, d_off, d_out, ctx=None, stream=0):

@@ -1,7 +1,8 @@
 //! Seed-and-extend in one call (`bg_seed_extend_batch`): the composition rust-bio's callers write by hand from
 //! `backward_search`, `Interval::occ` and `Aligner::semiglobal` (src/lib.rs:129-165, benches/fmindex.rs:20-38), on the
 //! forward strand or on both (`bg_seed_extend_strands_batch`: the `dna::revcomp` of each read as well), or as read pairs
-//! (`bg_seed_extend_pairs_batch`: interleaved mates, the best proper FR pair where there is one).
+//! (`bg_seed_extend_pairs_batch`: interleaved mates, the best proper FR pair where there is one), or with runner-up loci and a
+//! MAPQ per read (`bg_seed_extend_multi_batch`).
 use crate::fmindex::GpuFMIndex;
 use crate::pairwise::{scoring_to_c, tabulate};
 use crate::{concat, strerror, sys, to_alignment, zero_alignment};
@@ -27,6 +28,17 @@ pub struct PairHit {
     pub span: u64,
     /// proper combinations among the pair's candidates, both orientations
     pub n_proper: u32,
+}
+
+pub struct MultiHit {
+    /// the read's loci in rank order, the best first (empty: unmapped); their text intervals do not touch
+    pub hits: Vec<Hit>,
+    /// 0 where the runner-up scores as much as the best, `mapq_cap` where there is none
+    pub mapq: u8,
+    /// score of the runner-up locus; `BG_MIN_SCORE` if there is none
+    pub sub_score: i32,
+    /// loci found, counted up to max(max_hits, 2)
+    pub n_loci: u32,
 }
 
 impl GpuFMIndex<'_> {
@@ -125,6 +137,47 @@ impl GpuFMIndex<'_> {
         };
         (0..n_pairs)
             .map(|p| PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper })
+            .collect()
+    }
+
+    /// Runner-up loci and MAPQ: up to `max_hits` (1 ..= 8) loci per read on both strands, the best first (`hits[0]` is what
+    /// `seed_extend_batch_strands` reports).  A candidate below `min_score` is neither reported nor counted as a runner-up.
+    pub fn seed_extend_batch_multi<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], max_hits: u32, min_score: i32, mapq_cap: u32,
+                                                 seed_len: u32, stride: u32, max_occ: u32, pad: u32)
+                                                 -> Vec<MultiHit> {
+        assert!(max_hits >= 1 && max_hits as i32 <= sys::BG_SEED_MAX_HITS, "max_hits outside 1 ..= 8");
+        let table = tabulate(scoring);
+        let sc = scoring_to_c(scoring, &table);
+        let prm = sys::bg_seed_params_t { seed_len, stride, max_occ, pad };
+        let mp = sys::bg_multi_params_t { max_hits, min_score, mapq_cap };
+        let (buf, off) = concat(reads);
+        let k = max_hits as usize;
+        let zero = sys::bg_seed_hit_t { aln: zero_alignment(), window_start: 0, ref_start: 0, ref_end: 0, n_candidates: 0, n_seed_hits: 0 };
+        let mut hits = vec![zero; reads.len() * k];
+        let mut strand = vec![0u8; reads.len() * k];
+        let mut multi = vec![sys::bg_multi_hit_t { sub_score: 0, n_loci: 0, n_reported: 0, mapq: 0, reserved: [0; 6] }; reads.len().max(1)];
+        let mut ops = vec![0u8; k * (2 * buf.len() + (2 * pad as usize + 4) * reads.len() + 8)];
+        let mut used = 0u64;
+        let rc = unsafe {
+            sys::bg_seed_extend_multi_batch(self.h, &sc, &prm, &mp, sys::BG_STRAND_BOTH as u32, reads.len() as u64, buf.as_ptr(), off.as_ptr(),
+                                            hits.as_mut_ptr(), strand.as_mut_ptr(), multi.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64,
+                                            &mut used)
+        };
+        assert!(rc == 0, "{}", strerror(rc));
+        let hit = |s: usize| Hit {
+            alignment: Some(to_alignment(&hits[s].aln, &ops)),
+            ref_start: hits[s].ref_start as usize,
+            ref_end: hits[s].ref_end as usize,
+            n_candidates: hits[s].n_candidates,
+            reverse: strand[s] as i32 == sys::BG_HIT_REVERSE,
+        };
+        (0..reads.len())
+            .map(|r| MultiHit {
+                hits: (0..multi[r].n_reported as usize).map(|j| hit(r * k + j)).collect(),
+                mapq: multi[r].mapq,
+                sub_score: multi[r].sub_score,
+                n_loci: multi[r].n_loci,
+            })
             .collect()
     }
 }
