@@ -109,6 +109,8 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *                      values so that short texts span many superblocks)
  *   fq_no_fused = 1    bg_fastq_parse[_dev] through its general multi-pass kernels only, without the one-pass kernel that serves
  *                      four-line ASCII records in front (tests, A/B)
+ *   sam_lanes          lanes that format one line in bg_sam_emit_batch_dev's write pass: 16 or 32 (0 = default; tests, A/B: the
+ *                      text does not depend on it)
  *   sa_chunk_symbols   suffixes sorted per pass of round 0 of bg_suffix_array_dev[64] (0 = derived from free device memory;
  *                      tests use small values so that short texts take several passes)
  *   band_budget_gb     traceback + aux bytes per scratch set of the banded pipeline, in GB (0 = default: 40, and never more
@@ -670,6 +672,87 @@ int bg_cigar_batch_dev(bg_ctx* ctx, uint64_t n, const bg_alignment_t* d_aln, con
 int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const uint8_t* ops, uint64_t ops_bytes,
                     const uint8_t* x, const uint64_t* x_off, const uint8_t* y, const uint64_t* y_off, uint32_t ncol,
                     char* out, uint64_t out_cap, uint64_t* out_off);
+
+/* ---- SAM records from seed-and-extend hits (sam_emit.hip) -----------------------------------------------
+ * The output half of "wire format in, format out": one SAM line (SAM v1.6, section 1.4) per hit slot, formatted in HBM
+ * from exactly what bg_fastq_parse_dev and bg_seed_extend_strands / _pairs / _multi_batch_dev leave there; nothing is
+ * repacked in between.  rust-bio has no SAM writer: the record is defined here from the SAM specification, the way the
+ * pair and multi rules are defined above.  fm supplies the ctx and the attached text (bg_fm_set_text[_dev]), which MD needs.
+ * Read r is FASTQ record r (recs[r]; its sequence and qualities at seq + seq_off, qual + qual_off, its id in the FASTQ
+ * text), slot K r + k is hits / strand [K r + k] with K = max_hits (1 after the strands and pairs calls), operations at
+ * ops + aln.ops_off.  multi (optional): one record per read; pairs (with BG_SAM_PAIRED): one per pair, reads 2p, 2p + 1.
+ *
+ * Output is one contiguous buffer: slot K r + k occupies out[out_off[K r + k] .. out_off[K r + k + 1]); a slot that writes
+ * no line has length 0; the lines are in slot order, so the buffer is a valid SAM body as it stands.  The call computes every
+ * length and the offsets first, reads the total back with one stream synchronisation (like the counters of the seed-extend
+ * calls) and stores it in *out_bytes whatever happens next.  out == NULL with out_cap == 0 is a sizing call (out_off is
+ * filled) and returns BG_OK; a total above out_cap returns BG_ERR_OPS_CAP before one byte of text is written.
+ * BG_ERR_INVALID_ARG: max_hits 0 or above BG_SEED_MAX_HITS; n_contigs 0; BG_SAM_PAIRED with an odd n_reads, with
+ * max_hits != 1 or without pairs; BG_SAM_TAG_MD on an index without text; unknown flag bits; a null fm, sp, out_off or
+ * out_bytes, or (n_reads > 0) a null contigs, names, fastq text, recs, seq, qual, hits, strand or ops.
+ *
+ * The record.  A slot is PLACED if its hit has a score (score != BG_MIN_SCORE and strand != BG_HIT_NONE) and
+ * [ref_start, ref_end) lies inside one contig, found by binary search of ref_start in `start`: a hit that falls between
+ * contigs or runs over a contig's end is not placed and is treated as unmapped everywhere below.  pos = ref_start -
+ * contig.start + 1.  Slot k = 0 always writes a line; a slot k > 0 writes a line only with BG_SAM_SECONDARY, and only if
+ * it is placed and slot 0 is placed.  The line has eleven TAB-separated fields, then tags, then '\n':
+ *    1 QNAME   the FASTQ id bytes, or "*" if id_len == 0.  With BG_SAM_PAIRED a trailing "/1" on mate 1 or "/2" on mate 2
+ *              is dropped when id_len > 2.
+ *    2 FLAG    in decimal.  0x4 not placed; 0x10 reverse strand and placed; 0x100 for k > 0.  With BG_SAM_PAIRED: 0x1; 0x40
+ *              for even r, 0x80 for odd r; 0x8 mate not placed; 0x20 mate placed on the reverse strand; 0x2 when
+ *              pairs[p].proper and both mates are placed on one contig.
+ *    3 RNAME   the contig's name, or "*".
+ *    4 POS     pos, or 0.  A mate that is not placed takes RNAME and POS from a placed mate (SAM 1.4).
+ *    5 MAPQ    0 if not placed or k > 0; otherwise multi[r].mapq if multi is given, else 255.
+ *    6 CIGAR   byte for byte what bg_cigar_batch_dev(hard_clip = 0) writes for hits[slot].aln, or "*" if not placed (or
+ *              without operations).
+ *    7 RNEXT   "*" when not paired or neither mate is placed; "=" when this line's RNAME is the mate's contig; otherwise
+ *              the mate's contig name.
+ *    8 PNEXT   the mate's POS field, or 0.
+ *    9 TLEN    0 unless both mates are placed on one contig; otherwise max(ref_end) - min(ref_start), positive for the
+ *              mate with the smaller ref_start (mate 1 on a tie) and negative for the other.  For a proper pair |TLEN| is
+ *              pairs[p].span.
+ *   10 SEQ     the read for a forward or unplaced slot, dna::revcomp(read) for a reverse one (the bytes of
+ *              bg_revcomp_batch_dev); "*" if the read is empty or k > 0.
+ *   11 QUAL    the quality bytes, reversed on the reverse strand; "*" if qual_len != seq_len, if empty, or if k > 0.
+ * Tags, on placed lines only, in this order: AS:i:<score>; XS:i:<multi[r].sub_score> with multi, k == 0 and a runner-up
+ * (sub_score != BG_MIN_SCORE); NM:i:<number of SUBST + INS + DEL operations> with BG_SAM_TAG_NM; MD:Z:<md> with
+ * BG_SAM_TAG_MD.  The MD string is built by walking the operations from ref_start with a counter c = 0.  MATCH: c += 1
+ * and the text advances.  SUBST: write c, write the text byte, set c = 0; the text advances.  A run of consecutive DEL:
+ * write c, '^' and the run's text bytes, set c = 0.  INS: nothing.  At the end write c.  (This yields the specification's
+ * 10A5^AC0T3 forms without special cases.)
+ * bg_sam_header (host only, no GPU) writes "@HD\tVN:1.6\tSO:unsorted\n", one "@SQ\tSN:<name>\tLN:<len>\n" per contig and
+ * "@PG\tID:biogpu\tPN:biogpu\n"; *out_bytes receives the length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if
+ * out_cap is too small (nothing written).
+ * Not covered: BAM / BGZF, sorting, supplementary (chimeric) records, read groups, mate rescue.  Known limit: the
+ * seed-and-extend windows know nothing of contig boundaries, so a read whose best alignment crosses one is reported
+ * unmapped here (not clipped to the contig) even where a slightly worse alignment inside one contig exists. */
+typedef struct {            /* one reference sequence inside the indexed text; 32 bytes */
+    uint64_t start, len;    /* text[start .. start + len): contigs ascending in start, not overlapping, inside the text without its final sentinel */
+    uint64_t name_off;      /* into `names` */
+    uint32_t name_len, reserved;
+} bg_sam_contig_t;
+enum { BG_SAM_PAIRED = 1, BG_SAM_SECONDARY = 2, BG_SAM_TAG_NM = 4, BG_SAM_TAG_MD = 8 };
+typedef struct {
+    uint32_t flags;         /* BG_SAM_* */
+    uint32_t max_hits;      /* K: slots per read in hits / strand (1 after the strands and pairs calls) */
+} bg_sam_params_t;
+int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, char* out, uint64_t out_cap,
+                  uint64_t* out_bytes);
+/* Device flavour: every d_* pointer in HBM, d_out_off n_reads * K + 1 entries, out_bytes a host pointer; the text pass is
+ * asynchronous on `stream`.  Goes through the handle's ctx (scratch): the ctx's single-thread rule applies. */
+int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                          uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                          const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                          const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, char* d_out,
+                          uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream);
+/* The same with host pointers; ops as the host seed-extend calls return them (aln.ops_off into ops).  The sizes of the
+ * FASTQ text, seq, qual, ops and names are taken from the records that point into them. */
+int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs,
+                      uint64_t n_contigs, const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs,
+                      const uint8_t* seq, const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand,
+                      const uint8_t* ops, const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap,
+                      uint64_t* out_off, uint64_t* out_bytes);
 
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI

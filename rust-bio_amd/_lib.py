@@ -113,6 +113,18 @@ FQREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8
                         ("has_desc", "<i4"), ("check", "<i4")])
 assert FQREC_DTYPE.itemsize == 56, FQREC_DTYPE.itemsize
 
+# bg_sam_contig_t, BG_SAM_* and bg_sam_params_t (bg_sam_header, bg_sam_emit_batch[_dev])
+SAM_CONTIG_DTYPE = np.dtype([("start", "<u8"), ("len", "<u8"), ("name_off", "<u8"), ("name_len", "<u4"), ("reserved", "<u4")])
+assert SAM_CONTIG_DTYPE.itemsize == 32, SAM_CONTIG_DTYPE.itemsize
+SAM_PAIRED, SAM_SECONDARY, SAM_TAG_NM, SAM_TAG_MD = 1, 2, 4, 8
+
+
+class SAM_PARAMS(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_hits", C.c_uint32)]
+
+
+assert C.sizeof(SAM_PARAMS) == 8, C.sizeof(SAM_PARAMS)
+
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
            "bg_set_option", "bg_suffix_array", "bg_bwt", "bg_less", "bg_fm_build", "bg_fm_free",
            "bg_fm_device_bytes", "bg_fm_set_option", "bg_fm_backward_search_batch", "bg_fm_backward_search_batch_dev",
@@ -126,6 +138,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
+           "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
@@ -249,6 +262,11 @@ def lib():
         L.bg_seed_extend_multi_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp,
                                                      vp, u32, vp, vp, vp, vp, u64, vp, vp]
         L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
+        L.bg_sam_header.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
+        L.bg_sam_emit_batch_dev.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                            C.POINTER(u64), vp]
+        L.bg_sam_emit_batch.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                        C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

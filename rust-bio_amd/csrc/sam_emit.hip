@@ -1,0 +1,553 @@
+// SAM records from seed-and-extend hits (bg_sam_emit_batch[_dev], bg_sam_header): the record is defined in include/biogpu.h.
+// Two passes over the hit slots.  The length pass (one lane per slot) decides what each line holds, walks the slot's
+// operations for the CIGAR, NM and MD lengths and writes the line length; a scan turns the lengths into offsets.  The write
+// pass gives every line a fixed group of 16 or 32 lanes: the group stages the line in LDS at the same offset inside a 16-byte
+// granule that it has in the output buffer, so that everything but the line's unaligned head and tail leaves with 16-byte
+// stores.  A line that is longer than the staging area (reads go up to 65 535 bases) is formatted by the same code straight
+// into global memory.  The group leaves the CIGAR and MD strings blank: walking a slot's operations is serial, and with one
+// walking lane per group a wavefront spent its time there (measured: 20.8 ms of a 22.6 ms call for 1.25 M lines, against
+// 1.8 ms for the whole length pass, which does the same two walks with every lane busy).  So a third kernel, one lane per
+// slot like the length pass, writes the two strings into the finished lines.  All passes derive the line from one function
+// (sam_line), so they cannot disagree about a length.
+#include <algorithm>
+
+#include "fm_kernels.h"
+
+namespace {
+
+constexpr uint32_t kStage = 1024;             // bytes of a staged line
+constexpr uint32_t kStageBuf = kStage + 16;   // ... plus its offset inside the 16-byte granule of the output
+
+struct SamArgs {
+    uint64_t n_slots;
+    uint32_t K, flags;
+    const bg_sam_contig_t* contigs;
+    uint64_t n_contigs;
+    const char* names;
+    const uint8_t* fq;
+    const bg_fastq_record_t* recs;
+    const uint8_t* seq;
+    const uint8_t* qual;
+    const bg_seed_hit_t* hits;
+    const uint8_t* strand;
+    const uint8_t* ops;
+    const bg_multi_hit_t* multi;
+    const bg_pair_hit_t* pairs;
+    const uint8_t* text;
+    uint64_t n_text;
+};
+
+struct SamDesc {  // what the length pass learned from a slot's operations, and where the two strings go in the line
+    uint32_t cigar_len, md_len, nm;
+    uint32_t cigar_at, md_at;  // 0: no such string (a line never starts with either)
+    uint32_t reserved;
+};
+
+// dna::complement, as seed_extend.hip tabulates it for bg_revcomp_batch_dev
+struct alignas(16) ComplementTable {
+    uint8_t v[256];
+};
+constexpr ComplementTable make_complement() {
+    ComplementTable t{};
+    for (int i = 0; i < 256; i++) t.v[i] = (uint8_t)i;
+    const char* a = "AGCTYRWSKMDVHBN";
+    const char* b = "TCGARYWSMKHBDVN";
+    for (int i = 0; a[i]; i++) {
+        t.v[(uint8_t)a[i]] = (uint8_t)b[i];
+        t.v[(uint8_t)a[i] + 32] = (uint8_t)(b[i] + 32);
+    }
+    return t;
+}
+__constant__ ComplementTable kSamComplement = make_complement();
+
+__device__ __forceinline__ uint32_t ndig(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 10) {
+        v /= 10;
+        n++;
+    }
+    return n;
+}
+__device__ __forceinline__ uint32_t ndig_signed(int64_t v) { return v < 0 ? 1 + ndig((uint64_t)(-v)) : ndig((uint64_t)v); }
+// v in n = ndig(v) decimal digits
+__device__ __forceinline__ void put_dec(char* d, uint64_t v, uint32_t n) {
+    for (uint32_t i = n; i-- > 0;) {
+        d[i] = (char)('0' + v % 10);
+        v /= 10;
+    }
+}
+__device__ __forceinline__ uint32_t put_signed(char* d, int64_t v) {
+    uint32_t w = 0;
+    if (v < 0) d[w++] = '-';
+    const uint64_t m = v < 0 ? (uint64_t)(-v) : (uint64_t)v;
+    const uint32_t n = ndig(m);
+    put_dec(d + w, m, n);
+    return w + n;
+}
+
+// the contig a slot is placed on, -1 if it is not placed
+__device__ int64_t sam_place(const SamArgs& a, uint64_t slot) {
+    const bg_seed_hit_t& h = a.hits[slot];
+    if (h.aln.score == BG_MIN_SCORE || a.strand[slot] == BG_HIT_NONE) return -1;
+    const uint64_t s = h.ref_start, e = h.ref_end;
+    uint64_t lo = 0, hi = a.n_contigs;  // the first contig that starts behind s
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (a.contigs[mid].start <= s) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return -1;
+    const uint64_t end = a.contigs[lo - 1].start + a.contigs[lo - 1].len;
+    return s < end && s <= e && e <= end ? (int64_t)(lo - 1) : -1;
+}
+
+struct SamLine {
+    bool writes, placed, rev, seq_star, qual_star, has_xs;
+    uint32_t flag, mapq, qname_len, seq_len;
+    int64_t contig;  // RNAME: a contig, or -1 for "*"
+    int64_t next;    // RNEXT: a contig, -1 for "*", -2 for "="
+    uint64_t pos, pnext;
+    int64_t tlen;
+    int32_t score, xs;
+};
+
+// every field of a slot's line but the three that need the operations
+__device__ SamLine sam_line(const SamArgs& a, uint64_t slot) {
+    SamLine L = {};
+    const uint64_t r = slot / a.K;
+    const uint32_t k = (uint32_t)(slot - r * a.K);
+    const int64_t own = sam_place(a, slot);
+    L.placed = own >= 0;
+    L.writes = k == 0 || ((a.flags & BG_SAM_SECONDARY) && L.placed && sam_place(a, r * a.K) >= 0);
+    if (!L.writes) return L;
+    const bg_seed_hit_t& h = a.hits[slot];
+    const bg_fastq_record_t& rec = a.recs[r];
+    L.rev = L.placed && a.strand[slot] == BG_HIT_REVERSE;
+    L.flag = (L.placed ? 0u : 0x4u) | (L.rev ? 0x10u : 0u) | (k ? 0x100u : 0u);
+    L.contig = own;
+    L.pos = L.placed ? h.ref_start - a.contigs[own].start + 1 : 0;
+    L.next = -1;
+    L.qname_len = rec.id_len;
+    if (a.flags & BG_SAM_PAIRED) {  // K == 1: the mate's slot is the neighbouring read's
+        const uint64_t m = slot ^ 1;
+        const int64_t mate = sam_place(a, m);
+        const bg_seed_hit_t& hm = a.hits[m];
+        const bool first = !(r & 1);
+        L.flag |= 0x1u | (first ? 0x40u : 0x80u) | (mate < 0 ? 0x8u : 0u) | (mate >= 0 && a.strand[m] == BG_HIT_REVERSE ? 0x20u : 0u);
+        const uint64_t mpos = mate >= 0 ? hm.ref_start - a.contigs[mate].start + 1 : 0;
+        if (L.placed && own == mate) {
+            if (a.pairs[r >> 1].proper) L.flag |= 0x2u;
+            const uint64_t span = max(h.ref_end, hm.ref_end) - min(h.ref_start, hm.ref_start);
+            const bool left = h.ref_start < hm.ref_start || (h.ref_start == hm.ref_start && first);
+            L.tlen = left ? (int64_t)span : -(int64_t)span;
+        }
+        if (!L.placed && mate >= 0) {
+            L.contig = mate;
+            L.pos = mpos;
+        }
+        if (L.placed || mate >= 0) {
+            const int64_t mate_rname = mate >= 0 ? mate : own;  // the mate's RNAME and POS fields, borrowed ones included
+            L.next = mate_rname == L.contig ? -2 : mate_rname;
+            L.pnext = mate >= 0 ? mpos : L.pos;
+        }
+        if (rec.id_len > 2) {
+            const uint8_t* q = a.fq + rec.id_off + rec.id_len - 2;
+            if (q[0] == '/' && q[1] == (first ? '1' : '2')) L.qname_len -= 2;
+        }
+    }
+    L.mapq = !L.placed || k ? 0u : (a.multi ? a.multi[r].mapq : 255u);
+    L.seq_len = rec.seq_len;
+    L.seq_star = k > 0 || rec.seq_len == 0;
+    L.qual_star = k > 0 || rec.qual_len == 0 || rec.qual_len != rec.seq_len;
+    L.score = h.aln.score;
+    L.has_xs = L.placed && a.multi && k == 0 && a.multi[r].sub_score != BG_MIN_SCORE;
+    L.xs = L.has_xs ? a.multi[r].sub_score : 0;
+    return L;
+}
+
+// The CIGAR of cigar_kernel (fastq_ingest.hip) with soft clips; o == nullptr: only its length.
+__device__ uint32_t sam_cigar(const bg_alignment_t& al, const uint8_t* __restrict__ q, char* o) {
+    if (!al.n_ops) return 0;
+    uint32_t w = 0;
+    auto emit = [&](uint32_t n, char c) {
+        const uint32_t d = ndig(n);
+        if (o) {
+            put_dec(o + w, n, d);
+            o[w + d] = c;
+        }
+        w += d + 1;
+    };
+    auto add = [&](uint32_t kind, uint32_t n) {
+        if (kind <= BG_OP_INS) emit(n, kind == BG_OP_MATCH ? '=' : kind == BG_OP_SUBST ? 'X' : kind == BG_OP_DEL ? 'D' : 'I');
+    };
+    if (al.xstart > 0) emit(al.xstart, 'S');
+    uint32_t last = q[0], run = 1;
+    for (uint32_t i = 1; i < al.n_ops; i++) {
+        const uint32_t op = q[i];
+        if (op == last) {
+            run++;
+        } else {
+            add(last, run);
+            run = 1;
+        }
+        last = op;
+    }
+    add(last, run);
+    if (al.xlen > al.xend) emit(al.xlen - al.xend, 'S');
+    return w;
+}
+
+// The MD string and NM of a hit (rule in include/biogpu.h); o == nullptr: only the length (the text is not read then).
+__device__ uint32_t sam_md(const SamArgs& a, const bg_seed_hit_t& h, const uint8_t* __restrict__ q, char* o, uint32_t* nm) {
+    uint32_t w = 0, c = 0, n = 0;
+    uint64_t t = h.ref_start;
+    bool in_del = false;
+    auto count = [&]() {
+        const uint32_t d = ndig(c);
+        if (o) put_dec(o + w, c, d);
+        w += d;
+        c = 0;
+    };
+    auto ref = [&]() {
+        if (o) o[w] = t < a.n_text ? (char)a.text[t] : '?';
+        w++;
+        t++;
+    };
+    for (uint32_t i = 0; i < h.aln.n_ops; i++) {
+        const uint32_t op = q[i];
+        if (op == BG_OP_DEL) {
+            if (!in_del) {
+                count();
+                if (o) o[w] = '^';
+                w++;
+            }
+            ref();
+            n++;
+        } else if (op == BG_OP_MATCH) {
+            c++;
+            t++;
+        } else if (op == BG_OP_SUBST) {
+            count();
+            ref();
+            n++;
+        } else if (op == BG_OP_INS) {
+            n++;
+        }
+        in_del = op == BG_OP_DEL;
+    }
+    count();
+    *nm = n;
+    return w;
+}
+
+// where the fields of a line start; [11] is the first byte of the tags (or the final newline), len the whole line
+struct SamLayout {
+    uint32_t at[12];
+    uint32_t len;
+};
+__device__ SamLayout sam_layout(const SamArgs& a, const SamLine& L, const SamDesc& d) {
+    SamLayout y;
+    uint32_t w = 0;
+    auto field = [&](int i, uint32_t n) {
+        y.at[i] = w;
+        w += n + 1;  // and its TAB (the newline behind QUAL when there are no tags)
+    };
+    field(0, L.qname_len ? L.qname_len : 1);
+    field(1, ndig(L.flag));
+    field(2, L.contig >= 0 ? a.contigs[L.contig].name_len : 1);
+    field(3, ndig(L.pos));
+    field(4, ndig(L.mapq));
+    field(5, L.placed && d.cigar_len ? d.cigar_len : 1);
+    field(6, L.next >= 0 ? a.contigs[L.next].name_len : 1);
+    field(7, ndig(L.pnext));
+    field(8, ndig_signed(L.tlen));
+    field(9, L.seq_star ? 1 : L.seq_len);
+    field(10, L.qual_star ? 1 : L.seq_len);
+    y.at[11] = w - 1;
+    if (L.placed) {
+        w += 5 + ndig_signed(L.score) + 1;
+        if (L.has_xs) w += 5 + ndig_signed(L.xs) + 1;
+        if (a.flags & BG_SAM_TAG_NM) w += 5 + ndig(d.nm) + 1;
+        if (a.flags & BG_SAM_TAG_MD) w += 5 + d.md_len + 1;
+    }
+    y.len = w;
+    return y;
+}
+
+// length pass: one lane per slot
+__global__ __launch_bounds__(256) void sam_length_kernel(const SamArgs a, uint32_t* __restrict__ len, SamDesc* __restrict__ desc) {
+    const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= a.n_slots) return;
+    const SamLine L = sam_line(a, slot);
+    SamDesc d = {};
+    if (!L.writes) {
+        len[slot] = 0;
+        desc[slot] = d;
+        return;
+    }
+    if (L.placed) {
+        const bg_seed_hit_t& h = a.hits[slot];
+        const uint8_t* q = a.ops + h.aln.ops_off;
+        d.cigar_len = sam_cigar(h.aln, q, nullptr);
+        if (a.flags & (BG_SAM_TAG_NM | BG_SAM_TAG_MD)) d.md_len = sam_md(a, h, q, nullptr, &d.nm);
+    }
+    const SamLayout y = sam_layout(a, L, d);
+    if (L.placed && d.cigar_len) d.cigar_at = y.at[5];
+    if (L.placed && (a.flags & BG_SAM_TAG_MD)) d.md_at = y.len - 1 - d.md_len;  // the last tag: the newline follows it
+    len[slot] = y.len;
+    desc[slot] = d;
+}
+
+// third pass: one lane per slot writes the CIGAR and MD strings into the line the write pass left
+__global__ __launch_bounds__(256) void sam_ops_kernel(const SamArgs a, const SamDesc* __restrict__ desc, const uint64_t* __restrict__ off,
+                                                      char* __restrict__ out) {
+    const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= a.n_slots) return;
+    const SamDesc d = desc[slot];
+    if (!d.cigar_at && !d.md_at) return;
+    const bg_seed_hit_t& h = a.hits[slot];
+    const uint8_t* q = a.ops + h.aln.ops_off;
+    char* line = out + off[slot];
+    if (d.cigar_at) sam_cigar(h.aln, q, line + d.cigar_at);
+    if (d.md_at) {
+        uint32_t nm;
+        sam_md(a, h, q, line + d.md_at, &nm);
+    }
+}
+
+// One line by the G lanes of its group into dst (LDS or global memory): lane 0 the short fields, lane 1 the tags, all of them
+// the names, SEQ and QUAL; the CIGAR and MD strings stay blank for sam_ops_kernel.
+template <int G>
+__device__ void sam_format(const SamArgs& a, uint64_t slot, const SamDesc& d, char* dst, uint32_t lane, const uint8_t* s_comp) {
+    const SamLine L = sam_line(a, slot);
+    const SamLayout y = sam_layout(a, L, d);
+    const uint64_t r = slot / a.K;
+    const bg_fastq_record_t& rec = a.recs[r];
+    auto copy = [&](uint32_t at, const void* src, uint32_t n) {
+        for (uint32_t i = lane; i < n; i += G) dst[at + i] = ((const char*)src)[i];
+    };
+    auto name = [&](uint32_t at, int64_t contig) {
+        if (contig >= 0) copy(at, a.names + a.contigs[contig].name_off, a.contigs[contig].name_len);
+        else if (lane == 0) dst[at] = contig == -2 ? '=' : '*';
+    };
+    if (L.qname_len) copy(y.at[0], a.fq + rec.id_off, L.qname_len);
+    name(y.at[2], L.contig);
+    name(y.at[6], L.next);
+    if (!L.seq_star) {
+        const uint8_t* s = a.seq + rec.seq_off;
+        const uint32_t n = L.seq_len;
+        if (L.rev)
+            for (uint32_t i = lane; i < n; i += G) dst[y.at[9] + i] = (char)s_comp[s[n - 1 - i]];
+        else
+            copy(y.at[9], s, n);
+    }
+    if (!L.qual_star) {
+        const uint8_t* s = a.qual + rec.qual_off;
+        const uint32_t n = L.seq_len;
+        if (L.rev)
+            for (uint32_t i = lane; i < n; i += G) dst[y.at[10] + i] = (char)s[n - 1 - i];
+        else
+            copy(y.at[10], s, n);
+    }
+    if (lane == 0) {
+        if (!L.qname_len) dst[y.at[0]] = '*';
+        put_dec(dst + y.at[1], L.flag, ndig(L.flag));
+        put_dec(dst + y.at[3], L.pos, ndig(L.pos));
+        put_dec(dst + y.at[4], L.mapq, ndig(L.mapq));
+        if (!d.cigar_at) dst[y.at[5]] = '*';
+        put_dec(dst + y.at[7], L.pnext, ndig(L.pnext));
+        put_signed(dst + y.at[8], L.tlen);
+        if (L.seq_star) dst[y.at[9]] = '*';
+        if (L.qual_star) dst[y.at[10]] = '*';
+        for (int i = 1; i < 11; i++) dst[y.at[i] - 1] = '\t';
+        dst[y.len - 1] = '\n';
+    }
+    if (lane == 1 && L.placed) {
+        uint32_t w = y.at[11];
+        auto tag = [&](char c0, char c1, char type) {
+            dst[w] = '\t';
+            dst[w + 1] = c0;
+            dst[w + 2] = c1;
+            dst[w + 3] = ':';
+            dst[w + 4] = type;
+            dst[w + 5] = ':';
+            w += 6;
+        };
+        tag('A', 'S', 'i');
+        w += put_signed(dst + w, L.score);
+        if (L.has_xs) {
+            tag('X', 'S', 'i');
+            w += put_signed(dst + w, L.xs);
+        }
+        if (a.flags & BG_SAM_TAG_NM) {
+            tag('N', 'M', 'i');
+            w += put_signed(dst + w, d.nm);
+        }
+        if (a.flags & BG_SAM_TAG_MD) tag('M', 'D', 'Z');
+    }
+}
+
+// write pass: G lanes per slot, 256 / G slots per block
+template <int G>
+__global__ __launch_bounds__(256) void sam_write_kernel(const SamArgs a, const SamDesc* __restrict__ desc, const uint64_t* __restrict__ off,
+                                                        char* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) char s_stage[(256 / G) * kStageBuf];
+    __shared__ __attribute__((aligned(4))) uint8_t s_comp[256];
+    if (threadIdx.x < 64) ((uint32_t*)s_comp)[threadIdx.x] = ((const uint32_t*)kSamComplement.v)[threadIdx.x];
+    __syncthreads();
+    const uint32_t g = threadIdx.x / G, lane = threadIdx.x % G;
+    const uint64_t slot = (uint64_t)blockIdx.x * (256 / G) + g;
+    uint64_t o0 = 0;
+    uint32_t len = 0;
+    if (slot < a.n_slots) {
+        o0 = off[slot];
+        len = (uint32_t)(off[slot + 1] - o0);
+    }
+    char* line = out + o0;
+    const uint32_t mis = (uint32_t)((uintptr_t)line & 15);
+    const bool staged = len && mis + len <= kStageBuf;
+    char* stage = s_stage + g * kStageBuf + mis;
+    if (len) sam_format<G>(a, slot, desc[slot], staged ? stage : line, lane, s_comp);
+    __syncthreads();
+    if (!staged) return;
+    // head up to the first 16-byte boundary and tail behind the last one byte by byte, everything between as 16-byte stores
+    const uint32_t head = min(len, (16 - mis) & 15);
+    const uint32_t body = (len - head) >> 4, tail = (len - head) & 15;
+    if (lane < head) line[lane] = stage[lane];
+    for (uint32_t i = lane; i < body; i += G) *(uint4*)(line + head + 16 * i) = *(const uint4*)(stage + head + 16 * i);
+    if (lane < tail) line[head + 16 * body + lane] = stage[head + 16 * body + lane];
+}
+
+int sam_check(const bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, uint64_t n_contigs, const void* pairs) {
+    if (!fm || !sp) return BG_ERR_INVALID_ARG;
+    if (sp->flags & ~(uint32_t)(BG_SAM_PAIRED | BG_SAM_SECONDARY | BG_SAM_TAG_NM | BG_SAM_TAG_MD)) return BG_ERR_INVALID_ARG;
+    if (sp->max_hits == 0 || sp->max_hits > BG_SEED_MAX_HITS || n_contigs == 0) return BG_ERR_INVALID_ARG;
+    if ((sp->flags & BG_SAM_PAIRED) && ((n_reads & 1) || sp->max_hits != 1 || !pairs)) return BG_ERR_INVALID_ARG;
+    if ((sp->flags & BG_SAM_TAG_MD) && !fm->d_text) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, char* out, uint64_t out_cap,
+                             uint64_t* out_bytes) {
+    if (!out_bytes || (n_contigs && (!contigs || !names)) || (!out && out_cap)) return BG_ERR_INVALID_ARG;
+    std::string s = "@HD\tVN:1.6\tSO:unsorted\n";
+    for (uint64_t c = 0; c < n_contigs; c++) {
+        s += "@SQ\tSN:";
+        s.append(names + contigs[c].name_off, contigs[c].name_len);
+        s += "\tLN:" + std::to_string(contigs[c].len) + "\n";
+    }
+    s += "@PG\tID:biogpu\tPN:biogpu\n";
+    *out_bytes = s.size();
+    if (!out) return BG_OK;
+    if (s.size() > out_cap) return BG_ERR_OPS_CAP;
+    memcpy(out, s.data(), s.size());
+    return BG_OK;
+}
+
+extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                                     uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                                     const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                                     const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, char* d_out,
+                                     uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream) {
+    if (!d_out_off || !out_bytes) return BG_ERR_INVALID_ARG;
+    *out_bytes = 0;
+    int rc = sam_check(fm, sp, n_reads, n_contigs, d_pairs);
+    if (rc) return rc;
+    if (!d_out && out_cap) return BG_ERR_INVALID_ARG;
+    if (n_reads && (!d_contigs || !d_names || !d_fastq_text || !d_recs || !d_seq || !d_qual || !d_hits || !d_strand || !d_ops))
+        return BG_ERR_INVALID_ARG;
+    bg_ctx* ctx = fm->ctx;
+    hipStream_t st = (hipStream_t)stream;
+    BG_HIP(hipSetDevice(ctx->device));
+    if (n_reads == 0) {
+        const uint64_t z = 0;
+        BG_HIP(hipMemcpyAsync(d_out_off, &z, 8, hipMemcpyHostToDevice, st));
+        BG_HIP(hipStreamSynchronize(st));
+        return BG_OK;
+    }
+    bg_scratch_guard guard(ctx, st);
+    const uint64_t n_slots = n_reads * sp->max_hits;
+    const size_t len_bytes = (n_slots * 4 + 15) & ~(size_t)15, desc_bytes = n_slots * sizeof(SamDesc);
+    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, len_bytes + desc_bytes + 2 * (n_slots / 2048 + 1) * 8))) return rc;
+    uint32_t* d_len = (uint32_t*)ctx->aux;
+    SamDesc* d_desc = (SamDesc*)((uint8_t*)ctx->aux + len_bytes);
+    uint64_t* d_sums = (uint64_t*)((uint8_t*)ctx->aux + len_bytes + desc_bytes);
+    const SamArgs a = {n_slots, sp->max_hits, sp->flags, d_contigs, n_contigs, d_names, d_fastq_text, d_recs, d_seq, d_qual, d_hits,
+                       d_strand, d_ops, d_multi, (sp->flags & BG_SAM_PAIRED) ? d_pairs : nullptr, (const uint8_t*)fm->d_text, fm->n_text};
+    sam_length_kernel<<<dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, st>>>(a, d_len, d_desc);
+    BG_HIP(hipGetLastError());
+    if ((rc = bg_scan_u32(d_len, n_slots, d_out_off, d_sums, st))) return rc;
+    uint64_t total = 0;
+    BG_HIP(hipMemcpyAsync(&total, d_out_off + n_slots, 8, hipMemcpyDeviceToHost, st));
+    BG_HIP(hipStreamSynchronize(st));
+    *out_bytes = total;
+    if (!d_out) return BG_OK;
+    if (total > out_cap) return BG_ERR_OPS_CAP;
+    if (ctx->sam_lanes == 32)
+        sam_write_kernel<32><<<dim3((uint32_t)((n_slots + 7) / 8)), dim3(256), 0, st>>>(a, d_desc, d_out_off, d_out);
+    else
+        sam_write_kernel<16><<<dim3((uint32_t)((n_slots + 15) / 16)), dim3(256), 0, st>>>(a, d_desc, d_out_off, d_out);
+    sam_ops_kernel<<<dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, st>>>(a, d_desc, d_out_off, d_out);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
+                                 const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
+                                 const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
+                                 const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap, uint64_t* out_off,
+                                 uint64_t* out_bytes) {
+    if (!out_off || !out_bytes) return BG_ERR_INVALID_ARG;
+    *out_bytes = 0;
+    int rc = sam_check(fm, sp, n_reads, n_contigs, pairs);
+    if (rc) return rc;
+    if (!out && out_cap) return BG_ERR_INVALID_ARG;
+    if (n_reads && (!contigs || !names || !fastq_text || !recs || !seq || !qual || !hits || !strand || !ops)) return BG_ERR_INVALID_ARG;
+    out_off[0] = 0;
+    if (n_reads == 0) return BG_OK;
+    bg_ctx* ctx = fm->ctx;
+    BG_HIP(hipSetDevice(ctx->device));
+    const uint64_t n_slots = n_reads * sp->max_hits;
+    // the buffers the records point into end where their last record ends
+    uint64_t fq_bytes = 0, seq_bytes = 0, qual_bytes = 0, ops_bytes = 0, name_bytes = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        fq_bytes = std::max<uint64_t>(fq_bytes, recs[r].id_off + recs[r].id_len);
+        seq_bytes = std::max<uint64_t>(seq_bytes, recs[r].seq_off + recs[r].seq_len);
+        qual_bytes = std::max<uint64_t>(qual_bytes, recs[r].qual_off + recs[r].qual_len);
+    }
+    for (uint64_t s = 0; s < n_slots; s++)
+        if (hits[s].aln.score != BG_MIN_SCORE) ops_bytes = std::max<uint64_t>(ops_bytes, hits[s].aln.ops_off + hits[s].aln.n_ops);
+    for (uint64_t c = 0; c < n_contigs; c++) name_bytes = std::max<uint64_t>(name_bytes, contigs[c].name_off + contigs[c].name_len);
+    enum { CONTIGS, NAMES, FQ, RECS, SEQ, QUAL, HITS, STRAND, OPS, MULTI, PAIRS, OFF, OUT, N };
+    const void* src[N] = {contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi, pairs, nullptr, nullptr};
+    const size_t bytes[N] = {(size_t)(n_contigs * sizeof(bg_sam_contig_t)), (size_t)name_bytes, (size_t)fq_bytes,
+                             (size_t)(n_reads * sizeof(bg_fastq_record_t)), (size_t)seq_bytes, (size_t)qual_bytes,
+                             (size_t)(n_slots * sizeof(bg_seed_hit_t)), (size_t)n_slots, (size_t)ops_bytes,
+                             multi ? (size_t)(n_reads * sizeof(bg_multi_hit_t)) : 0, pairs ? (size_t)(n_reads / 2 * sizeof(bg_pair_hit_t)) : 0,
+                             (size_t)((n_slots + 1) * 8), (size_t)out_cap};
+    void* d[N] = {};
+    auto run = [&]() -> int {
+        hipStream_t st = ctx->stream;
+        for (int i = 0; i < N; i++) {
+            if (!src[i] && i < OFF) continue;  // multi / pairs not given
+            if (i == OUT && !out) continue;    // a sizing call
+            BG_HIP(hipMalloc(&d[i], std::max<size_t>(bytes[i], 16)));
+            if (src[i] && bytes[i]) BG_HIP(hipMemcpyAsync(d[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
+        }
+        const int rc2 = bg_sam_emit_batch_dev(fm, sp, n_reads, (const bg_sam_contig_t*)d[CONTIGS], n_contigs, (const char*)d[NAMES],
+                                              (const uint8_t*)d[FQ], (const bg_fastq_record_t*)d[RECS], (const uint8_t*)d[SEQ],
+                                              (const uint8_t*)d[QUAL], (const bg_seed_hit_t*)d[HITS], (const uint8_t*)d[STRAND],
+                                              (const uint8_t*)d[OPS], (const bg_multi_hit_t*)d[MULTI], (const bg_pair_hit_t*)d[PAIRS],
+                                              (char*)d[OUT], out_cap, (uint64_t*)d[OFF], out_bytes, st);
+        if (rc2 && rc2 != BG_ERR_OPS_CAP) return rc2;
+        BG_HIP(hipMemcpyAsync(out_off, d[OFF], bytes[OFF], hipMemcpyDeviceToHost, st));
+        if (!rc2 && out && *out_bytes) BG_HIP(hipMemcpyAsync(out, d[OUT], *out_bytes, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipStreamSynchronize(st));
+        return rc2;
+    };
+    rc = run();
+    for (void* p : d) hipFree(p);
+    return rc;
+}
