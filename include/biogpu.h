@@ -572,6 +572,64 @@ int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_s
                                    uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                    bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_ops,
                                    uint64_t ops_stride, uint64_t* totals, void* stream);
+/* Mate rescue.  The paired call makes a pair proper only if BOTH mates produced a seeded candidate at the right locus.  A mate
+ * whose every seed window holds a mismatch, or whose seeds all fall in intervals above max_occ (a mate inside a repeat), has no
+ * candidate there.  Its partner already says where it must lie: within max_span, on the opposite strand.  The rescue call is
+ * the paired call plus one more batch of semiglobal alignments in those insert windows.  Per pair p (m1 = read 2p, m2 = read
+ * 2p + 1):
+ *   candidates, pair rule   exactly those of bg_seed_extend_pairs_batch.  If the pair rule finds a proper combination
+ *                    (n_proper > 0, whatever "paired or not" then decides), or neither mate has a candidate, the pair's outputs
+ *                    are exactly the paired call's and rescued[p] = 0;
+ *   anchors          otherwise, for each mate that has candidates: its candidates over both strands in the multi call's rank order
+ *                    (score descending, then candidate number: forward strand first, ascending proposed start); the first A =
+ *                    max_anchors of them are its anchors, of anchor rank 0 .. A - 1.  An anchor with ref_end - ref_start >
+ *                    max_span is skipped (it keeps its rank and gives no rescue alignment);
+ *   rescue window    of anchor c (text = the indexed text without its final sentinel, n_text bytes):
+ *                    forward anchor: [c.ref_start, min(n_text, c.ref_start + max_span)), the other mate is sought on the reverse
+ *                    strand; reverse anchor: [c.ref_end - max_span (0 if that is negative), c.ref_end), the other mate is sought
+ *                    on the forward strand;
+ *   rescue alignment Aligner::semiglobal(x, y = text[window)), x = the other mate as read (forward strand sought) or revcomp of
+ *                    it (reverse strand sought).  An empty window or an x of length 0 gives no alignment.  Its hit is a complete
+ *                    bg_seed_hit_t: aln the aligner's record (operations with it), window_start the window's first text offset,
+ *                    ref_start / ref_end = window_start + ystart / yend, n_candidates / n_seed_hits the mate's own seeded counts
+ *                    (possibly 0);
+ *   accepted         if its score >= min_score and (anchor, rescued) passes the pair rule's own "proper" test (the forward one is
+ *                    a, the reverse one b: a.ref_start <= b.ref_start, min_span <= span <= max_span);
+ *   choice           among a pair's accepted rescues the highest anchor.score + rescued.score (64-bit); on a tie orientation A (m1
+ *                    forward), then the rescue anchored on m1, then the smaller anchor rank;
+ *   paired or not    own(m) = mate m's own best score under the strands rule, 0 for a mate without candidates.  If sum +
+ *                    pen_unpaired >= own(m1) + own(m2): the anchor's mate reports the anchor candidate exactly as the paired call
+ *                    writes a candidate, the other mate reports the rescued hit with its strand, pairs[p].proper = 1,
+ *                    pairs[p].span the span, pairs[p].n_proper stays the seeded count (0), rescued[p] = 1 or 2: which mate was
+ *                    rescued.  Otherwise the paired call's output and rescued[p] = 0.
+ * A rescued hit is an ordinary hit to every consumer (bg_sam_emit_batch[_dev] writes it as it writes a seeded one).
+ * Limits and errors of the rescue calls (everything else is the paired call's): max_span > 65535: BG_ERR_TOO_LARGE; max_anchors 0
+ * or above BG_RESCUE_MAX_ANCHORS, a null rp or rescued: BG_ERR_INVALID_ARG; device operation slots need ops_stride >=
+ * max_read_len + max(max_read_len + 2 pad, max_span) + 4, else BG_ERR_OPS_CAP.  totals (optional, host) has 4 entries:
+ * suffix-array rows resolved, seeded candidates aligned, rescue alignments run, pairs rescued.  A pass waits once more than
+ * a pass of the paired call, for the counters that size the rescue batch; a call given totals waits once more at its end, for
+ * the fourth.  Passes never split a pair and the result does not depend on seed_chunk_reads.  The out-of-alphabet rule is
+ * unchanged (the rescue alignment itself needs no alphabet).
+ * max_span also sizes the window: with max_span one below a fragment's length the mate is still found, aligned without its last
+ * base, and the accepted span is then at most max_span.
+ * Known limits: a forward mate that ends beyond its reverse partner's end is outside the window (dovetailed mates); a better
+ * rescued pair is not sought when a proper seeded combination exists; a rescue window may cross a contig boundary; MAPQ is not
+ * recomputed for a rescued mate. */
+enum { BG_RESCUE_MAX_ANCHORS = 4 };
+typedef struct {
+    uint32_t max_anchors;  /* A: anchors tried per mate, 1 ..= BG_RESCUE_MAX_ANCHORS */
+    int32_t  min_score;    /* a rescued alignment scoring below this is discarded */
+} bg_rescue_params_t;
+int bg_seed_extend_pairs_rescue_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                      const bg_rescue_params_t* rp, uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off,
+                                      bg_seed_hit_t* hits, uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* rescued, uint8_t* ops_buf,
+                                      uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour (operation slots of the 2 n_pairs reads and passes as bg_seed_extend_pairs_batch_dev). */
+int bg_seed_extend_pairs_rescue_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                          const bg_rescue_params_t* rp, uint64_t n_pairs, const uint8_t* d_reads,
+                                          const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
+                                          bg_pair_hit_t* d_pairs, uint8_t* d_rescued, uint8_t* d_ops, uint64_t ops_stride,
+                                          uint64_t* totals, void* stream);
 /* Runner-up loci and a mapping quality.  The strands call reports one alignment per read, so a read inside a two-copy repeat and
  * a read that maps uniquely look the same.  The multi call reports up to K = max_hits loci per read and a MAPQ: hits / strand
  * have K slots per read (hits[K r + k]), multi one record per read.
@@ -724,7 +782,8 @@ int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const ui
  * bg_sam_header (host only, no GPU) writes "@HD\tVN:1.6\tSO:unsorted\n", one "@SQ\tSN:<name>\tLN:<len>\n" per contig and
  * "@PG\tID:biogpu\tPN:biogpu\n"; *out_bytes receives the length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if
  * out_cap is too small (nothing written).
- * Not covered: BAM / BGZF, sorting, supplementary (chimeric) records, read groups, mate rescue.  Known limit: the
+ * Not covered: BAM / BGZF, sorting, supplementary (chimeric) records, read groups.  (Mate rescue happens before this call:
+ * bg_seed_extend_pairs_rescue_batch[_dev]; a rescued hit is written like any other.)  Known limit: the
  * seed-and-extend windows know nothing of contig boundaries, so a read whose best alignment crosses one is reported
  * unmapped here (not clipped to the contig) even where a slightly worse alignment inside one contig exists. */
 typedef struct {            /* one reference sequence inside the indexed text; 32 bytes */

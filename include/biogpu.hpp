@@ -693,11 +693,29 @@ public:
         bool proper = false;
         uint64_t span = 0;      // of the proper pair (SAM |TLEN|); 0 when not proper
         uint32_t n_proper = 0;  // proper combinations among the pair's candidates
+        uint8_t rescued = 0;    // seed_extend_batch_pairs_rescue: 1 / 2 = the mate placed inside its partner's insert window
     };
     std::vector<PairedSeedHit> seed_extend_batch_pairs(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
                                                        uint32_t min_span = 0, uint32_t max_span = 1000, int32_t pen_unpaired = 17,
                                                        uint32_t seed_len = 20, uint32_t stride = 10, uint32_t max_occ = 16,
                                                        uint32_t pad = 25) const {
+        return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, nullptr);
+    }
+    // Mate rescue (bg_seed_extend_pairs_rescue_batch): seed_extend_batch_pairs, and where a pair's seeded candidates hold no proper
+    // combination, the other mate is aligned inside the insert window of each of a mate's best max_anchors (1 ..= 4) candidates; a
+    // rescued alignment below min_score is discarded.
+    std::vector<PairedSeedHit> seed_extend_batch_pairs_rescue(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                              uint32_t max_anchors = 2, int32_t min_score = 0, uint32_t min_span = 0,
+                                                              uint32_t max_span = 1000, int32_t pen_unpaired = 17, uint32_t seed_len = 20,
+                                                              uint32_t stride = 10, uint32_t max_occ = 16, uint32_t pad = 25) const {
+        const bg_rescue_params_t rp = {max_anchors, min_score};
+        return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, &rp);
+    }
+
+private:
+    std::vector<PairedSeedHit> pairs_impl(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads, uint32_t min_span,
+                                          uint32_t max_span, int32_t pen_unpaired, uint32_t seed_len, uint32_t stride, uint32_t max_occ,
+                                          uint32_t pad, const bg_rescue_params_t* rp) const {
         if (reads.size() % 2) throw std::invalid_argument("seed_extend_batch_pairs: an odd number of reads (mates come in pairs)");
         std::vector<int32_t> table;
         const bg_scoring_t sc = scoring.to_c(table);
@@ -713,12 +731,16 @@ public:
         std::vector<bg_seed_hit_t> hits(reads.size());
         std::vector<uint8_t> strand(reads.size());
         std::vector<bg_pair_hit_t> pairs(std::max<size_t>(n_pairs, 1));
-        std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4) * reads.size() + 8);
+        std::vector<uint8_t> rescued(std::max<size_t>(n_pairs, 1));
+        // (a rescued hit has up to read + max_span operations)
+        std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4 + (rp ? max_span : 0)) * reads.size() + 8);
         uint64_t used = 0;
-        const int rc = bg_seed_extend_pairs_batch(h_, &sc, &prm, &pp, n_pairs, buf.data(), off.data(), hits.data(), strand.data(),
-                                                  pairs.data(), ops.data(), ops.size(), &used);
+        const int rc = rp ? bg_seed_extend_pairs_rescue_batch(h_, &sc, &prm, &pp, rp, n_pairs, buf.data(), off.data(), hits.data(),
+                                                              strand.data(), pairs.data(), rescued.data(), ops.data(), ops.size(), &used)
+                          : bg_seed_extend_pairs_batch(h_, &sc, &prm, &pp, n_pairs, buf.data(), off.data(), hits.data(), strand.data(),
+                                                       pairs.data(), ops.data(), ops.size(), &used);
         if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
-        check(rc, "bg_seed_extend_pairs_batch");
+        check(rc, rp ? "bg_seed_extend_pairs_rescue_batch" : "bg_seed_extend_pairs_batch");
         std::vector<PairedSeedHit> res(n_pairs);
         for (size_t p = 0; p < n_pairs; p++) {
             for (int m = 0; m < 2; m++) {
@@ -733,9 +755,12 @@ public:
             res[p].proper = pairs[p].proper != 0;
             res[p].span = pairs[p].span;
             res[p].n_proper = pairs[p].n_proper;
+            res[p].rescued = rp ? rescued[p] : 0;
         }
         return res;
     }
+
+public:
     // Runner-up loci and MAPQ (bg_seed_extend_multi_batch): up to max_hits loci per read whose text intervals do not touch, the best
     // first (hits[0] is what seed_extend_batch_strands reports), the runner-up's score and a MAPQ in 0 ..= mapq_cap: 0 where the
     // runner-up scores as much as the best, mapq_cap where there is none.  A candidate below min_score is neither reported nor a

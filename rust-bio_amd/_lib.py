@@ -93,6 +93,15 @@ PAIR_HIT_DTYPE = np.dtype([("span", "<u8"), ("n_proper", "<u4"), ("proper", "u1"
 assert PAIR_HIT_DTYPE.itemsize == 16, PAIR_HIT_DTYPE.itemsize
 
 
+# bg_rescue_params_t (bg_seed_extend_pairs_rescue_batch[_dev])
+class RESCUE_PARAMS(C.Structure):
+    _fields_ = [("max_anchors", C.c_uint32), ("min_score", C.c_int32)]
+
+
+assert C.sizeof(RESCUE_PARAMS) == 8, C.sizeof(RESCUE_PARAMS)
+RESCUE_MAX_ANCHORS = 4
+
+
 # bg_multi_params_t (bg_seed_extend_multi_batch[_dev])
 SEED_MAX_HITS = 8
 
@@ -137,6 +146,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
+           "bg_seed_extend_pairs_rescue_batch", "bg_seed_extend_pairs_rescue_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
@@ -257,6 +267,10 @@ def lib():
                                                  vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_pairs_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp,
                                                      u32, vp, vp, vp, vp, u64, vp, vp]
+        L.bg_seed_extend_pairs_rescue_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                        C.POINTER(RESCUE_PARAMS), u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.bg_seed_extend_pairs_rescue_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                            C.POINTER(RESCUE_PARAMS), u64, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp]
         L.bg_seed_extend_multi_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp, vp,
                                                  vp, vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_multi_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp,

@@ -24,15 +24,17 @@
 //      (pair mode, bg_seed_extend_pairs_batch[_dev]: per pair of interleaved mates, the best proper FR combination of their
 //       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t;
 //       multi mode, bg_seed_extend_multi_batch[_dev]: per read up to K loci that do not touch, in rank order -> K bg_seed_hit_t +
-//       their ops, bg_multi_hit_t with the runner-up's score and MAPQ)
+//       their ops, bg_multi_hit_t with the runner-up's score and MAPQ;
+//       rescue mode, bg_seed_extend_pairs_rescue_batch[_dev]: pair mode, then for the pairs without a proper combination the stages
+//       R1-R4 of seed_rescue.hip: anchors -> one more batch of semiglobal alignments in their insert windows -> rescued pairs)
 #include <algorithm>
 
 #include "fm_kernels.h"
 
 struct bg_seed_scratch {
-    void* p[16] = {};
-    size_t cap[16] = {};
-    uint64_t* h_tot = nullptr;  // pinned: totals read back between S4 and S5
+    void* p[24] = {};  // 16 .. 23: the rescue stages' plan, counts, offsets, pairs, records and operations
+    size_t cap[24] = {};
+    uint64_t* h_tot = nullptr;  // pinned: totals read back between S4 and S5 (and, rescue call, between R1 and R2)
 };
 void bg_seed_scratch_free(bg_seed_scratch* s) {
     if (!s) return;
@@ -387,17 +389,22 @@ namespace {
 // se_pair_kernel replaces S7, writing d_pairs as well.
 // Multi mode (`multi` set): se_multi_kernel replaces S7; d_hits / d_strand / d_ops hold multi->max_hits slots per read, d_multi one
 // record per read.
+// Rescue mode (`rescue` set, pair mode): R1-R4 of seed_rescue.hip replace S7; d_rescued one byte per pair, totals 4 entries.
 int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
            const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
            uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
-           bg_pair_hit_t* d_pairs = nullptr, const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* d_multi = nullptr) {
+           bg_pair_hit_t* d_pairs = nullptr, const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* d_multi = nullptr,
+           const bg_rescue_params_t* rescue = nullptr, uint8_t* d_rescued = nullptr) {
     if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
     if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
     if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
     if (max_read_len > 65535 || prm_in->pad > 65535) return BG_ERR_TOO_LARGE;
+    if (rescue && pair->max_span > 65535) return BG_ERR_TOO_LARGE;
     const uint32_t win_max = max_read_len + 2 * prm_in->pad;
-    if (d_ops && ops_stride < (uint64_t)max_read_len + win_max + 4) return BG_ERR_OPS_CAP;
+    const uint32_t rwin_max = rescue ? pair->max_span : 0;  // the longest rescue window
+    if (d_ops && ops_stride < (uint64_t)max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
     if (totals) totals[0] = totals[1] = 0;
+    if (totals && rescue) totals[2] = totals[3] = 0;
     if (n_reads == 0) return BG_OK;
     bg_ctx* ctx = fm->ctx;
     hipStream_t st = (hipStream_t)stream;
@@ -419,7 +426,7 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
 
     const uint32_t G = strands == BG_STRAND_BOTH ? 2 : 1;
     const bool virt = strands == BG_STRAND_REVERSE || strands == BG_STRAND_BOTH;  // reads to materialise (S0)
-    uint64_t done_hits = 0, done_cand = 0;
+    uint64_t done_hits = 0, done_cand = 0, done_rescue = 0;
     bool any_panic = false;
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
     // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size — 1.25 M reads went as 2^20 + 0.2 M until
@@ -522,7 +529,55 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
             return rc;
         // ---- S7: best hit per read (pair mode: per pair)
         const dim3 best_grid((unsigned)((nr * 16 + 255) / 256));
-        if (pair) {
+        if (rescue) {
+            // ---- R1: the paired call's answer for every pair + the rescue plan of those without a proper combination
+            const uint64_t np = nr / 2;
+            const uint64_t rstride = d_ops ? (uint64_t)max_read_len + rwin_max + 4 : 0;
+            if ((rc = need(16, bg_seed_rescue_plan_bytes(np)))) return rc;
+            if ((rc = need(17, np * 8 + 3 * np * 4))) return rc;       // own_sum | n_res | x_bytes | y_bytes
+            if ((rc = need(18, 3 * (np + 1) * 8))) return rc;          // roff | rxoff | ryoff
+            int64_t* d_own = (int64_t*)W.p[17];
+            uint32_t* d_rn = (uint32_t*)(d_own + np);
+            uint32_t *d_rxb = d_rn + np, *d_ryb = d_rxb + np;
+            uint64_t* d_roff = (uint64_t*)W.p[18];
+            uint64_t *d_rxoff = d_roff + (np + 1), *d_ryoff = d_rxoff + (np + 1);
+            if ((rc = bg_seed_rescue_plan_launch(pair, rescue, prm.n_text, np, r0, roff, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops,
+                                                 ops_stride, d_strand, d_pairs, d_rescued, W.p[16], d_own, d_rn, d_rxb, d_ryb, kMaxProposals,
+                                                 st)))
+                return rc;
+            if ((rc = bg_scan_u32(d_rn, np, d_roff, d_sums, st))) return rc;
+            if ((rc = bg_scan_u32(d_rxb, np, d_rxoff, d_sums, st))) return rc;
+            if ((rc = bg_scan_u32(d_ryb, np, d_ryoff, d_sums, st))) return rc;
+            BG_HIP(hipMemcpyAsync(&W.h_tot[5], d_roff + np, 8, hipMemcpyDeviceToHost, st));
+            BG_HIP(hipMemcpyAsync(&W.h_tot[6], d_rxoff + np, 8, hipMemcpyDeviceToHost, st));
+            BG_HIP(hipMemcpyAsync(&W.h_tot[7], d_ryoff + np, 8, hipMemcpyDeviceToHost, st));
+            BG_HIP(hipStreamSynchronize(st));  // sizes the rescue pairs: the one extra round trip of a pass
+            const uint64_t RC = W.h_tot[5], RX = W.h_tot[6], RY = W.h_tot[7];
+            if (RC) {
+                // ---- R2: the (other mate, insert window) pairs
+                if ((rc = need(19, RX))) return rc;
+                if ((rc = need(20, RY))) return rc;
+                if ((rc = need(21, 2 * (RC + 1) * 8))) return rc;
+                if ((rc = need(22, RC * sizeof(bg_alignment_t)))) return rc;
+                if ((rc = need(23, RC * rstride))) return rc;
+                uint64_t* d_rcxoff = (uint64_t*)W.p[21];
+                uint64_t* d_rcyoff = d_rcxoff + (RC + 1);
+                bg_alignment_t* d_raln = (bg_alignment_t*)W.p[22];
+                uint8_t* d_rops = d_ops ? (uint8_t*)W.p[23] : nullptr;
+                if ((rc = bg_seed_rescue_gather_launch(np, vreads, roff, (const uint8_t*)fm->d_text, W.p[16], d_roff, d_rxoff, d_ryoff,
+                                                       (uint8_t*)W.p[19], d_rcxoff, (uint8_t*)W.p[20], d_rcyoff, st)))
+                    return rc;
+                // ---- R3: Aligner::semiglobal on every rescue pair
+                if ((rc = bg_align_batch_dev_hint(ctx, sc, BG_MODE_SEMIGLOBAL, RC, (const uint8_t*)W.p[19], d_rcxoff, (const uint8_t*)W.p[20],
+                                                  d_rcyoff, max_read_len, rwin_max, d_raln, d_rops, rstride, st, -1)))
+                    return rc;
+                // ---- R4: the rescued pairs
+                if ((rc = bg_seed_rescue_pick_launch(pair, rescue, np, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, W.p[16], d_own, d_roff, d_raln,
+                                                     d_rops, d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued, st)))
+                    return rc;
+            }
+            done_rescue += RC;
+        } else if (pair) {
             if ((rc = bg_seed_pairs_launch(pair, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_pairs,
                                            kMaxProposals, st)))
                 return rc;
@@ -543,6 +598,16 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
     if (totals) {
         totals[0] = done_hits;
         totals[1] = done_cand;
+    }
+    if (totals && rescue) {
+        // pairs rescued: counted on the device from the bytes R1 / R4 wrote (the call's last wait, outside the passes)
+        totals[2] = done_rescue;
+        uint64_t* d_count = (uint64_t*)W.p[18];  // (the rescue offsets of the last pass are no longer needed)
+        BG_HIP(hipMemsetAsync(d_count, 0, 8, st));
+        if ((rc = bg_seed_rescue_count_launch(n_reads / 2, d_rescued, d_count, st))) return rc;
+        BG_HIP(hipMemcpyAsync(&W.h_tot[5], d_count, 8, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipStreamSynchronize(st));
+        totals[3] = W.h_tot[5];
     }
     // a seed that reaches a byte outside the alphabet makes the reference's backward_search panic; here it does not
     // vote, every read is still answered, and the call says so
@@ -588,6 +653,27 @@ extern "C" int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc,
 
 namespace {
 
+// the rescue calls' own argument checks; every other one is the pair calls' and se_run's
+int rescue_args(const bg_rescue_params_t* rp, const void* rescued) {
+    if (!rp || !rescued || rp->max_anchors == 0 || rp->max_anchors > BG_RESCUE_MAX_ANCHORS) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_seed_extend_pairs_rescue_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                                     const bg_rescue_params_t* rp, uint64_t n_pairs, const uint8_t* d_reads,
+                                                     const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits,
+                                                     uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_rescued, uint8_t* d_ops,
+                                                     uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
+    if (int rc = rescue_args(rp, d_rescued)) return rc;
+    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
+                  stream, pp, d_pairs, nullptr, nullptr, rp, d_rescued);
+}
+
+namespace {
+
 // the multi calls' own argument checks; every other one is se_run's
 int multi_args(const bg_multi_params_t* mp, const void* multi, uint32_t strands, uint64_t n_reads) {
     if (!mp || !multi || mp->max_hits == 0 || mp->max_hits > BG_SEED_MAX_HITS || mp->mapq_cap > 254 || strands < BG_STRAND_FORWARD ||
@@ -623,7 +709,8 @@ namespace {
 int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
                 const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
                 uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr,
-                const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* multis = nullptr) {
+                const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* multis = nullptr, const bg_rescue_params_t* rescue = nullptr,
+                uint8_t* rescued = nullptr) {
     if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (n_reads == 0) return BG_OK;
@@ -632,11 +719,13 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     uint64_t max_len = 0;
     for (uint64_t r = 0; r < n_reads; r++) max_len = std::max(max_len, read_off[r + 1] - read_off[r]);
     if (max_len > 65535) return BG_ERR_TOO_LARGE;
-    const uint64_t stride = ops_buf ? 2 * max_len + 2 * (uint64_t)prm->pad + 4 : 0;
+    if (rescue && pair->max_span > 65535) return BG_ERR_TOO_LARGE;
+    // (rescue call: a slot also holds the operations of a read against a rescue window of max_span bytes)
+    const uint64_t stride = ops_buf ? max_len + std::max<uint64_t>(max_len + 2 * (uint64_t)prm->pad, rescue ? pair->max_span : 0) + 4 : 0;
     const uint64_t bytes = read_off[n_reads];
     uint8_t *d_reads = nullptr, *d_ops = nullptr;
     uint64_t* d_off = nullptr;
-    uint8_t* d_strand = nullptr;
+    uint8_t *d_strand = nullptr, *d_rescued = nullptr;
     bg_seed_hit_t* d_hits = nullptr;
     bg_pair_hit_t* d_pairs = nullptr;
     bg_multi_hit_t* d_multi = nullptr;
@@ -651,16 +740,18 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
         if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_slots * stride));
         if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_slots));
         if (pair) BG_HIP(hipMalloc((void**)&d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t)));
+        if (rescue) BG_HIP(hipMalloc((void**)&d_rescued, std::max<uint64_t>(n_reads / 2, 16)));
         if (multi) BG_HIP(hipMalloc((void**)&d_multi, n_reads * sizeof(bg_multi_hit_t)));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st,
-                        pair, d_pairs, multi, d_multi);
+                        pair, d_pairs, multi, d_multi, rescue, d_rescued);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(hits, d_hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
         if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_slots, hipMemcpyDeviceToHost, st));
         if (pair) BG_HIP(hipMemcpyAsync(pairs, d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
+        if (rescue) BG_HIP(hipMemcpyAsync(rescued, d_rescued, n_reads / 2, hipMemcpyDeviceToHost, st));
         if (multi) BG_HIP(hipMemcpyAsync(multis, d_multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_slots * stride);
@@ -676,6 +767,7 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
     hipFree(d_ops);
     hipFree(d_strand);
     hipFree(d_pairs);
+    hipFree(d_rescued);
     hipFree(d_multi);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
@@ -717,6 +809,16 @@ extern "C" int bg_seed_extend_pairs_batch(bg_fm* fm, const bg_scoring_t* sc, con
                                           uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
     return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs);
+}
+
+extern "C" int bg_seed_extend_pairs_rescue_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                                 const bg_rescue_params_t* rp, uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off,
+                                                 bg_seed_hit_t* hits, uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* rescued, uint8_t* ops_buf,
+                                                 uint64_t ops_cap, uint64_t* ops_used) {
+    if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
+    if (int rc = rescue_args(rp, rescued)) return rc;
+    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
+                       nullptr, rp, rescued);
 }
 
 extern "C" int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,

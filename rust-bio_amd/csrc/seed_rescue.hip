@@ -1,0 +1,279 @@
+// Mate rescue in seed-and-extend (bg_seed_extend_pairs_rescue_batch[_dev]): the stages that replace S7 of seed_extend.hip in
+// pair mode when rescue is asked for.  A pair whose seeded candidates hold no proper combination is given a second chance:
+// each mate's best candidates ("anchors") say where the other mate must lie, and that mate is aligned semiglobally against
+// the anchor's insert window (definition in include/biogpu.h, "Mate rescue").
+//   R1 plan     per pair: the pair rule and the paired call's own writes (seed_pair_rule.h, shared with se_pair_kernel); for a
+//               pair without a proper combination the anchors of each mate -> rescue plan entries + per-pair counts
+//      (scan of the per-pair rescue / x-byte / y-byte counts; the three totals are the ONE extra host round trip of a pass)
+//   R2 gather   (other mate on the sought strand, anchor window) pairs, offsets         -> x, x_off, y, y_off
+//   R3 align    Aligner::semiglobal on every rescue pair (bg_align_batch_dev_hint, by seed_extend.hip)
+//   R4 pick     per pair: acceptance, choice, "paired or not"; a rescued pair's two hits, strands, operations, pair record
+//               and rescued byte overwrite what R1 wrote for it
+// A pass without a single rescue alignment stops after R1's read-back.
+#include <algorithm>
+
+#include "seed_pair_rule.h"
+
+namespace {
+
+using namespace bgpair;
+
+constexpr uint32_t kSlots = 2 * BG_RESCUE_MAX_ANCHORS;  // rescue alignments of one pair: up to A per anchoring mate
+
+// one planned rescue alignment; entry k of pair p is plan[kSlots * p + k]
+struct RescuePlan {
+    uint64_t lo;    // the window's first text offset
+    uint32_t len;   // its length, 1 ..= max_span
+    uint32_t info;  // anchor candidate relative to cb[0] (bits 0-12) | x's virtual read within the pair << 16 | rank << 18 |
+                    // anchor on the forward strand << 20 | anchoring mate << 21
+};
+
+struct RescuePrm {
+    uint32_t max_anchors;
+    int32_t min_score;
+    uint64_t n_text;
+};
+
+// R1: 16 lanes per pair.  Every pair is first answered as the paired call answers it (rescued = 0).  The anchors of a mate are
+// its first A candidates in rank order: A rounds of the own-best key's max over the keys below the last one found.
+__global__ __launch_bounds__(256) void se_rescue_plan_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, RescuePrm rp,
+                                                             const uint64_t* __restrict__ voff, const uint64_t* __restrict__ coff,
+                                                             const uint32_t* __restrict__ n_hits, const bg_alignment_t* __restrict__ aln,
+                                                             const uint8_t* __restrict__ c_ops, const uint64_t* __restrict__ w_lo,
+                                                             bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
+                                                             uint8_t* __restrict__ strand, bg_pair_hit_t* __restrict__ pairs,
+                                                             uint8_t* __restrict__ rescued, RescuePlan* __restrict__ plan,
+                                                             int64_t* __restrict__ own_sum, uint32_t* __restrict__ n_res,
+                                                             uint32_t* __restrict__ x_bytes, uint32_t* __restrict__ y_bytes) {
+    const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t l16 = threadIdx.x & 15;
+    if (p >= n_pairs) return;  // uniform per group of 16
+    const PairRule R = pair_rule(p, l16, pp, coff, aln, w_lo);
+    pair_write(p, l16, r0, pp, R, n_hits, aln, c_ops, w_lo, hits, ops, ops_stride, strand, pairs);
+    uint32_t nr = 0, xb = 0, yb = 0;
+    if (R.n_proper == 0) {
+#pragma unroll
+        for (int m = 0; m < 2; m++) {
+            const uint64_t c0 = R.cb[2 * m];
+            const uint32_t nc = (uint32_t)(R.cb[2 * m + 2] - c0), n_fwd = (uint32_t)(R.cb[2 * m + 1] - c0);
+            if (!nc) continue;
+            const int other = 1 - m;
+            const uint32_t Lo = (uint32_t)(voff[4 * p + 2 * other + 1] - voff[4 * p + 2 * other]);  // the sought mate's length
+            uint64_t prev = ~0ull;
+            for (uint32_t k = 0; k < rp.max_anchors; k++) {
+                uint64_t best = 0;
+                for (uint32_t c = l16; c < nc; c += 16) {
+                    const uint32_t sc = (uint32_t)aln[c0 + c].score ^ 0x80000000u;
+                    const uint64_t key = ((uint64_t)sc << 32) | (uint32_t)~c;
+                    if (key < prev) best = max(best, key);
+                }
+                best = max16(best);
+                if (!best) break;  // fewer than A candidates (a candidate's key is never 0: c < 2 kMaxCand)
+                prev = best;
+                const uint32_t c = ~(uint32_t)best;
+                const bool fwd = c < n_fwd;
+                const bg_alignment_t& a = aln[c0 + c];
+                const uint64_t rs = w_lo[c0 + c] + a.ystart, re = w_lo[c0 + c] + a.yend;
+                if (re - rs > pp.max_span) continue;
+                const uint64_t lo = fwd ? rs : (re > pp.max_span ? re - pp.max_span : 0u);
+                const uint64_t hi = fwd ? min(rp.n_text, rs + pp.max_span) : re;
+                if (hi <= lo || Lo == 0) continue;
+                if (l16 == 0) {
+                    RescuePlan e;
+                    e.lo = lo;
+                    e.len = (uint32_t)(hi - lo);
+                    // the forward anchor's mate is sought on the reverse strand: its revcomp, virtual read 2 other + 1
+                    e.info = (uint32_t)(c0 + c - R.cb[0]) | (uint32_t)(2 * other + (fwd ? 1 : 0)) << 16 | k << 18 | (fwd ? 1u : 0u) << 20 |
+                             (uint32_t)m << 21;
+                    plan[kSlots * p + nr] = e;
+                }
+                nr++;
+                xb += Lo;
+                yb += (uint32_t)(hi - lo);
+            }
+        }
+    }
+    if (l16 == 0) {
+        rescued[r0 / 2 + p] = 0;
+        n_res[p] = nr;
+        x_bytes[p] = xb;
+        y_bytes[p] = yb;
+        // own(m): 0 for a mate without candidates
+        own_sum[p] = (int64_t)(R.cb[2] > R.cb[0] ? key_score(R.own[0]) : 0) + (R.cb[4] > R.cb[2] ? key_score(R.own[1]) : 0);
+    }
+}
+
+// R2: one wavefront per pair, four per block: the (x, window) pairs of its planned rescues + their offsets.  x is read from the
+// pass's virtual reads, which hold both strands of every mate.
+__global__ __launch_bounds__(256) void se_rescue_gather_kernel(uint64_t n_pairs, const uint8_t* __restrict__ vreads,
+                                                               const uint64_t* __restrict__ voff, const uint8_t* __restrict__ text,
+                                                               const RescuePlan* __restrict__ plan, const uint64_t* __restrict__ roff,
+                                                               const uint64_t* __restrict__ xoff, const uint64_t* __restrict__ yoff,
+                                                               uint8_t* __restrict__ x, uint64_t* __restrict__ x_off,
+                                                               uint8_t* __restrict__ y, uint64_t* __restrict__ y_off) {
+    const uint64_t p = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (p >= n_pairs) return;
+    if (p + 1 == n_pairs && lane == 0) {  // closing offsets
+        x_off[roff[n_pairs]] = xoff[n_pairs];
+        y_off[roff[n_pairs]] = yoff[n_pairs];
+    }
+    const uint64_t j0 = roff[p];
+    const uint32_t n = (uint32_t)(roff[p + 1] - j0);
+    uint64_t xo = xoff[p], yo = yoff[p];
+    for (uint32_t k = 0; k < n; k++) {
+        const RescuePlan e = plan[kSlots * p + k];
+        const uint64_t v = 4 * p + ((e.info >> 16) & 3);
+        const uint64_t ro = voff[v];
+        const uint32_t L = (uint32_t)(voff[v + 1] - ro);
+        if (lane == 0) {
+            x_off[j0 + k] = xo;
+            y_off[j0 + k] = yo;
+        }
+        for (uint32_t i = lane; i < L; i += 64) x[xo + i] = vreads[ro + i];
+        for (uint32_t i = lane; i < e.len; i += 64) y[yo + i] = text[e.lo + i];
+        xo += L;
+        yo += e.len;
+    }
+}
+
+// R4: 16 lanes per pair, one lane per planned rescue (kSlots <= 16).  Key of an accepted rescue: the score sum biased to
+// unsigned (33 bits), 1 for orientation A, 1 for the rescue anchored on m1, ~rank (2 bits), so the max is the rule's choice.
+__global__ __launch_bounds__(256) void se_rescue_pick_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, RescuePrm rp,
+                                                             const uint64_t* __restrict__ coff, const uint32_t* __restrict__ n_hits,
+                                                             const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ c_ops,
+                                                             const uint64_t* __restrict__ w_lo, const RescuePlan* __restrict__ plan,
+                                                             const int64_t* __restrict__ own_sum, const uint64_t* __restrict__ roff,
+                                                             const bg_alignment_t* __restrict__ r_aln, const uint8_t* __restrict__ r_ops,
+                                                             bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
+                                                             uint8_t* __restrict__ strand, bg_pair_hit_t* __restrict__ pairs,
+                                                             uint8_t* __restrict__ rescued) {
+    static_assert(kSlots <= 16, "one lane per planned rescue");
+    const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t l16 = threadIdx.x & 15;
+    if (p >= n_pairs) return;  // uniform per group of 16
+    const uint64_t j0 = roff[p];
+    const uint32_t n = (uint32_t)(roff[p + 1] - j0);
+    if (!n) return;
+    PairRule R;
+#pragma unroll
+    for (int v = 0; v < 5; v++) R.cb[v] = coff[4 * p + v];
+    uint64_t key = 0;
+    if (l16 < n) {
+        const RescuePlan e = plan[kSlots * p + l16];
+        const bg_alignment_t& q = r_aln[j0 + l16];
+        const uint64_t ca = R.cb[0] + (e.info & 0x1FFF);
+        const bool fwd = (e.info >> 20) & 1;
+        const uint32_t m = (e.info >> 21) & 1;
+        const uint64_t as = w_lo[ca] + aln[ca].ystart, ae = w_lo[ca] + aln[ca].yend;
+        const uint64_t qs = e.lo + q.ystart, qe = e.lo + q.yend;
+        const uint64_t f_start = fwd ? as : qs, b_start = fwd ? qs : as;  // the forward one is `a`, the reverse one `b`
+        const uint64_t span = max(ae, qe) - f_start;
+        if (q.score >= rp.min_score && f_start <= b_start && span >= pp.min_span && span <= pp.max_span) {
+            const uint64_t sum = (uint64_t)((int64_t)aln[ca].score + q.score + (1ll << 32));
+            const bool orient_a = fwd == (m == 0);  // m1 forward: m1 anchors forward, or m2 anchors in reverse
+            key = sum << 8 | (uint64_t)orient_a << 7 | (uint64_t)(m == 0) << 6 | (3u - ((e.info >> 18) & 3)) << 4 | l16;
+        }
+    }
+    key = max16(key);
+    if (!key) return;
+    const int64_t sum = (int64_t)(key >> 8) - (1ll << 32);
+    if (sum + pp.pen_unpaired < own_sum[p]) return;
+    const uint32_t k = (uint32_t)key & 15;
+    const RescuePlan e = plan[kSlots * p + k];
+    const bg_alignment_t q = r_aln[j0 + k];
+    const bool fwd = (e.info >> 20) & 1;
+    const int m = (e.info >> 21) & 1, other = 1 - m;
+    const uint64_t ca = R.cb[0] + (e.info & 0x1FFF);
+    // the anchor's mate reports the anchor candidate exactly as the paired call writes a candidate ...
+    write_mate(p, m, l16, r0, R, ca - R.cb[2 * m], n_hits, aln, c_ops, w_lo, hits, ops, ops_stride, strand);
+    // ... the other mate the rescued hit on the opposite strand
+    const uint64_t r = 2 * p + other;
+    bg_seed_hit_t h;
+    memset(&h, 0, sizeof(h));
+    h.aln = q;
+    h.aln.ops_off = (r0 + r + 1) * ops_stride - q.n_ops;
+    h.window_start = e.lo;
+    h.ref_start = e.lo + q.ystart;
+    h.ref_end = e.lo + q.yend;
+    h.n_candidates = (uint32_t)(R.cb[2 * other + 2] - R.cb[2 * other]);
+    h.n_seed_hits = n_hits[4 * p + 2 * other] + n_hits[4 * p + 2 * other + 1];
+    if (ops && r_ops)
+        for (uint32_t i = l16; i < q.n_ops; i += 16) ops[h.aln.ops_off + i] = r_ops[q.ops_off + i];
+    if (l16 == 0) {
+        hits[r0 + r] = h;
+        if (strand) strand[r0 + r] = fwd ? BG_HIT_REVERSE : BG_HIT_FORWARD;
+        const uint64_t as = w_lo[ca] + aln[ca].ystart, ae = w_lo[ca] + aln[ca].yend;
+        bg_pair_hit_t ph;
+        memset(&ph, 0, sizeof(ph));
+        ph.span = max(ae, h.ref_end) - (fwd ? as : h.ref_start);
+        ph.n_proper = 0;  // the seeded count: a pair with a proper seeded combination is not rescued
+        ph.proper = 1;
+        pairs[r0 / 2 + p] = ph;
+        rescued[r0 / 2 + p] = (uint8_t)(other + 1);
+    }
+}
+
+// totals[3]: the rescued pairs of the whole call, one add per wavefront
+__global__ __launch_bounds__(256) void se_rescue_count_kernel(uint64_t n_pairs, const uint8_t* __restrict__ rescued,
+                                                              unsigned long long* __restrict__ count) {
+    uint32_t n = 0;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_pairs; p += (uint64_t)gridDim.x * blockDim.x) n += rescued[p] != 0;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+}  // namespace
+
+int bg_seed_rescue_count_launch(uint64_t n_pairs, const uint8_t* d_rescued, uint64_t* d_count, hipStream_t st) {
+    if (n_pairs == 0) return BG_OK;
+    const unsigned grid = (unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 2048);
+    se_rescue_count_kernel<<<dim3(grid), dim3(256), 0, st>>>(n_pairs, d_rescued, (unsigned long long*)d_count);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+size_t bg_seed_rescue_plan_bytes(uint64_t n_pairs) { return n_pairs * kSlots * sizeof(RescuePlan); }
+
+int bg_seed_rescue_plan_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_text, uint64_t n_pairs, uint64_t r0,
+                               const uint64_t* d_voff, const uint64_t* d_coff, const uint32_t* d_n_hits, const bg_alignment_t* d_aln,
+                               const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride,
+                               uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_rescued, void* d_plan, int64_t* d_own_sum,
+                               uint32_t* d_n_res, uint32_t* d_x_bytes, uint32_t* d_y_bytes, uint32_t max_cand, hipStream_t st) {
+    if (max_cand > kMaxCand) return BG_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return BG_OK;
+    const PairPrm prm{pp->min_span, pp->max_span, pp->pen_unpaired};
+    const RescuePrm rprm{rp->max_anchors, rp->min_score, n_text};
+    se_rescue_plan_kernel<<<dim3((unsigned)((n_pairs * 16 + 255) / 256)), dim3(256), 0, st>>>(
+        n_pairs, r0, prm, rprm, d_voff, d_coff, d_n_hits, d_aln, d_c_ops, d_w_lo, d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued,
+        (RescuePlan*)d_plan, d_own_sum, d_n_res, d_x_bytes, d_y_bytes);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+int bg_seed_rescue_gather_launch(uint64_t n_pairs, const uint8_t* d_vreads, const uint64_t* d_voff, const uint8_t* d_text, const void* d_plan,
+                                 const uint64_t* d_roff, const uint64_t* d_xoff, const uint64_t* d_yoff, uint8_t* d_x, uint64_t* d_x_off,
+                                 uint8_t* d_y, uint64_t* d_y_off, hipStream_t st) {
+    if (n_pairs == 0) return BG_OK;
+    se_rescue_gather_kernel<<<dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, st>>>(n_pairs, d_vreads, d_voff, d_text,
+                                                                                        (const RescuePlan*)d_plan, d_roff, d_xoff, d_yoff, d_x,
+                                                                                        d_x_off, d_y, d_y_off);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+int bg_seed_rescue_pick_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff,
+                               const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
+                               const void* d_plan, const int64_t* d_own_sum, const uint64_t* d_roff, const bg_alignment_t* d_r_aln,
+                               const uint8_t* d_r_ops, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand,
+                               bg_pair_hit_t* d_pairs, uint8_t* d_rescued, hipStream_t st) {
+    if (n_pairs == 0) return BG_OK;
+    const PairPrm prm{pp->min_span, pp->max_span, pp->pen_unpaired};
+    const RescuePrm rprm{rp->max_anchors, rp->min_score, 0};
+    se_rescue_pick_kernel<<<dim3((unsigned)((n_pairs * 16 + 255) / 256)), dim3(256), 0, st>>>(
+        n_pairs, r0, prm, rprm, d_coff, d_n_hits, d_aln, d_c_ops, d_w_lo, (const RescuePlan*)d_plan, d_own_sum, d_roff, d_r_aln, d_r_ops,
+        d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}

@@ -6,7 +6,8 @@ seeds vote, hit -> proposed read start, per-read dedup, window gather, best-hit 
 operations — runs in HIP kernels behind the C ABI (rust-bio_amd/csrc/seed_extend.hip); its definition is in
 include/biogpu.h (the tests hold a CPU statement of it).  The `_strands` calls map each read on the forward strand, on
 the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  The `_pairs` calls map interleaved mates of
-paired-end reads and report the best proper FR pair where there is one.  The `_multi` calls report up to K loci per read that
+paired-end reads and report the best proper FR pair where there is one; the `_pairs_rescue` calls also look for a mate without a
+seeded candidate inside its partner's insert window.  The `_multi` calls report up to K loci per read that
 do not touch, the runner-up's score and a MAPQ.  This module only marshals arguments."""
 import ctypes as C
 
@@ -33,6 +34,17 @@ class PairParams:
 
     def to_c(self):
         return _lib.PAIR_PARAMS(self.min_span, self.max_span, self.pen_unpaired)
+
+
+class RescueParams:
+    """bg_rescue_params_t: max_anchors (A, 1 ..= 4) candidates of a mate, best first, in whose insert windows the other mate is
+    sought; a rescued alignment scoring below min_score is discarded."""
+
+    def __init__(self, max_anchors=2, min_score=0):
+        self.max_anchors, self.min_score = max_anchors, min_score
+
+    def to_c(self):
+        return _lib.RESCUE_PARAMS(self.max_anchors, self.min_score)
 
 
 class MultiParams:
@@ -160,6 +172,51 @@ def seed_extend_pairs_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_le
                                                          max_read_len, d_hits, d_strand or None, d_pairs or None, d_ops or None,
                                                          ops_stride, totals.ctypes.data if totals is not None else None, stream),
                "bg_seed_extend_pairs_batch_dev")
+
+
+def seed_extend_pairs_rescue_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, rescue_params=None, want_ops=True,
+                                    allow_out_of_alphabet=False):
+    """bg_seed_extend_pairs_rescue_batch, host buffers: seed_extend_pairs_arrays plus mate rescue.  Returns (hits, strand, pairs,
+    rescued: uint8[n] — 0, or 1 / 2: the mate that was placed inside its partner's insert window —, ops)."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    rescue_params = rescue_params or RescueParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    if n % 2:
+        raise ValueError("seed_extend_pairs_rescue_arrays: an odd number of reads")
+    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n, 1), dtype=np.uint8)
+    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
+    rescued = np.zeros(max(n // 2, 1), dtype=np.uint8)
+    # a reported hit has at most read + window operations; a rescue window is up to max_span bytes
+    cap = int(off[-1] + (max(int(np.diff(off).max(initial=0)) + 2 * params.pad, pair_params.max_span) + 4) * n) + 8 if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc, pp, rp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c()
+    rc = _lib.lib().bg_seed_extend_pairs_rescue_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), n // 2, rd.ctypes.data,
+                                                      off.ctypes.data, hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
+                                                      rescued.ctypes.data, ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_pairs_rescue_batch")
+    return hits, strand[:n], pairs[:n // 2], rescued[:n // 2], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_pairs_rescue_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_rescued, d_strand=0, d_ops=0,
+                                 ops_stride=0, params=None, pair_params=None, rescue_params=None, stream=0, totals=None):
+    """bg_seed_extend_pairs_rescue_batch_dev (pointers are ints; as seed_extend_pairs_dev, plus d_rescued: n_pairs bytes;
+    ops_stride >= max_read_len + max(max_read_len + 2 pad, max_span) + 4); `totals`, if given, is a uint64[4] numpy array that
+    receives (suffix-array rows resolved, seeded candidates aligned, rescue alignments run, pairs rescued)."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    rescue_params = rescue_params or RescueParams()
+    sc, pc, pp, rp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_pairs_rescue_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), n_pairs, d_reads,
+                                                                d_read_off, max_read_len, d_hits, d_strand or None, d_pairs or None,
+                                                                d_rescued or None, d_ops or None, ops_stride,
+                                                                totals.ctypes.data if totals is not None else None, stream),
+               "bg_seed_extend_pairs_rescue_batch_dev")
 
 
 def seed_extend_multi_arrays(fm, scoring, reads, read_off, params=None, multi_params=None, strands=_lib.STRAND_BOTH, want_ops=True,

@@ -28,6 +28,8 @@ pub struct PairHit {
     pub span: u64,
     /// proper combinations among the pair's candidates, both orientations
     pub n_proper: u32,
+    /// `seed_extend_batch_pairs_rescue`: 1 / 2 = the mate that was placed inside its partner's insert window, 0 otherwise
+    pub rescued: u8,
 }
 
 pub struct MultiHit {
@@ -110,6 +112,23 @@ impl GpuFMIndex<'_> {
     pub fn seed_extend_batch_pairs<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], min_span: u32, max_span: u32,
                                                  pen_unpaired: i32, seed_len: u32, stride: u32, max_occ: u32, pad: u32)
                                                  -> Vec<PairHit> {
+        self.pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, None)
+    }
+
+    /// Mate rescue (`bg_seed_extend_pairs_rescue_batch`): `seed_extend_batch_pairs`, and where a pair's seeded candidates hold no
+    /// proper combination, the other mate is aligned inside the insert window of each of a mate's best `max_anchors` (1 ..= 4)
+    /// candidates; a rescued alignment below `min_score` is discarded.  `PairHit::rescued` says which mate was placed that way.
+    pub fn seed_extend_batch_pairs_rescue<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], max_anchors: u32, min_score: i32,
+                                                        min_span: u32, max_span: u32, pen_unpaired: i32, seed_len: u32, stride: u32,
+                                                        max_occ: u32, pad: u32)
+                                                        -> Vec<PairHit> {
+        let rp = sys::bg_rescue_params_t { max_anchors, min_score };
+        self.pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, Some(rp))
+    }
+
+    fn pairs_impl<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], min_span: u32, max_span: u32, pen_unpaired: i32,
+                                seed_len: u32, stride: u32, max_occ: u32, pad: u32, rp: Option<sys::bg_rescue_params_t>)
+                                -> Vec<PairHit> {
         assert!(reads.len() % 2 == 0, "mates come in pairs: an odd number of reads");
         let table = tabulate(scoring);
         let sc = scoring_to_c(scoring, &table);
@@ -121,11 +140,19 @@ impl GpuFMIndex<'_> {
         let mut hits = vec![zero; reads.len()];
         let mut strand = vec![0u8; reads.len()];
         let mut pairs = vec![sys::bg_pair_hit_t { span: 0, n_proper: 0, proper: 0, reserved: [0; 3] }; n_pairs.max(1)];
-        let mut ops = vec![0u8; 2 * buf.len() + (2 * pad as usize + 4) * reads.len() + 8];
+        let mut rescued = vec![0u8; n_pairs.max(1)];
+        // (a rescued hit has up to read + max_span operations)
+        let window = 2 * pad as usize + 4 + if rp.is_some() { max_span as usize } else { 0 };
+        let mut ops = vec![0u8; 2 * buf.len() + window * reads.len() + 8];
         let mut used = 0u64;
         let rc = unsafe {
-            sys::bg_seed_extend_pairs_batch(self.h, &sc, &prm, &pp, n_pairs as u64, buf.as_ptr(), off.as_ptr(), hits.as_mut_ptr(),
-                                            strand.as_mut_ptr(), pairs.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used)
+            match &rp {
+                Some(rp) => sys::bg_seed_extend_pairs_rescue_batch(self.h, &sc, &prm, &pp, rp, n_pairs as u64, buf.as_ptr(), off.as_ptr(),
+                                                                   hits.as_mut_ptr(), strand.as_mut_ptr(), pairs.as_mut_ptr(),
+                                                                   rescued.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used),
+                None => sys::bg_seed_extend_pairs_batch(self.h, &sc, &prm, &pp, n_pairs as u64, buf.as_ptr(), off.as_ptr(), hits.as_mut_ptr(),
+                                                        strand.as_mut_ptr(), pairs.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used),
+            }
         };
         assert!(rc == 0, "{}", strerror(rc));
         let hit = |r: usize| Hit {
@@ -136,7 +163,8 @@ impl GpuFMIndex<'_> {
             reverse: strand[r] as i32 == sys::BG_HIT_REVERSE,
         };
         (0..n_pairs)
-            .map(|p| PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper })
+            .map(|p| PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper,
+                               rescued: if rp.is_some() { rescued[p] } else { 0 } })
             .collect()
     }
 
