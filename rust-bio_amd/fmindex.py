@@ -231,7 +231,9 @@ class FMDIndex:
         self.fm = fmindex
         self.records32 = records32
 
-    def smems_arrays(self, pat, pat_off, i_pos, l, all_=False, cap=None):
+    def smems_arrays(self, pat, pat_off, i_pos, l, all_=False, cap=None, keep_panics=False):
+        """-> (count per pattern, records [n, cap, 6]).  A pattern the reference panics on fails the whole call (AlphabetError);
+        with keep_panics=True it comes back as count 0xFFFFFFFF next to the other patterns' answers."""
         p = _lib.as_u8(pat)
         off = np.ascontiguousarray(pat_off, dtype=np.uint64)
         n = len(off) - 1
@@ -249,7 +251,8 @@ class FMDIndex:
             fn = _lib.lib().bg_fmd_smems_batch64
         rc = fn(self.fm.h, 1 if all_ else 0, n, p.ctypes.data, off.ctypes.data,
                 ip.ctypes.data if ip is not None else None, l, cap, cnt.ctypes.data, out.ctypes.data)
-        _lib.check(rc, "FMDIndex::smems")
+        if not (keep_panics and rc == -7):  # BG_ERR_OUT_OF_ALPHABET: every other pattern is still answered
+            _lib.check(rc, "FMDIndex::smems")
         return cnt, out
 
     @staticmethod
