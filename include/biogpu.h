@@ -677,6 +677,50 @@ int bg_seed_extend_multi_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_s
                                    uint32_t strands, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
                                    uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_multi_hit_t* d_multi,
                                    uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream);
+/* Mapping quality of read pairs.  The paired call reports one placement per mate and does not say how unique it is; the multi
+ * call scores single reads and knows nothing of the partner.  The pairs-mapq call is the paired call plus one bg_multi_hit_t
+ * per read: multi[2p], multi[2p + 1] belong to the mates of pair p.  A mate inside a repeat whose partner is unique gets a high
+ * MAPQ when the partner settles which copy it is, and 0 when it does not.  Like the pair and multi rules this is this library's
+ * own definition (rust-bio has no mapper).
+ *   outputs          candidates, the pair rule, "paired or not", hits, strand, pairs, operation slots, totals, passes and limits
+ *                    are exactly those of bg_seed_extend_pairs_batch[_dev]: those outputs are written byte for byte as the
+ *                    paired call writes them;
+ *   touches(a, b)    the multi rule's test in forward-text coordinates, whatever the strands: a.ref_start <= b.ref_end &&
+ *                    b.ref_start <= a.ref_end;
+ *   not proper       (pairs[p].proper == 0) each mate's record is exactly what bg_seed_extend_multi_batch with BG_STRAND_BOTH,
+ *                    max_hits = 1 and the same min_score / mapq_cap writes for that read: sub_score, n_loci (counted up to 2),
+ *                    n_reported and mapq.  hits stay the paired call's even where the mate's best scores below min_score; the
+ *                    record then says n_reported = 0, mapq = 0;
+ *   proper           with the chosen combination (c1, c2), S1 = c1.score + c2.score (64-bit).  For mate i with partner j:
+ *                    alternatives of mate i: every candidate x of mate i, on either strand, with x.score >= min_score and
+ *                    !touches(x, c_i).  sub_score = the highest x.score among them, or BG_MIN_SCORE if there are none; n_loci =
+ *                    2 or 1 accordingly; n_reported = 1.
+ *                    S2_i = the maximum over (a) every proper combination (the pair rule's test, both orientations) whose
+ *                    mate-i member is an alternative of mate i: the sum of its two scores; (b) every alternative x: x.score +
+ *                    c_j.score - pen_unpaired, the mate placed elsewhere and unpaired.
+ *                    mapq = 0 if c_i.score <= 0; mapq_cap if mate i has no alternative; otherwise min(mapq_cap, mapq_cap *
+ *                    min(S1 - S2_i, c_i.score) / c_i.score), 64-bit, the division truncating.
+ * S1 >= S2_i always holds: S1 is the maximum over all proper combinations, which covers (a); and "paired or not" made the pair
+ * proper because S1 + pen_unpaired >= best1 + best2 >= x.score + c_j.score, which covers (b).  When the partner is the same in
+ * both sums (S2_i = x.score + c_j.score through a proper combination) the formula is the multi rule's on mate i's scores, so a
+ * pair and a single read agree where they should.
+ * BG_ERR_INVALID_ARG: a null qp or multi, mapq_cap above 254; everything else is the paired call's.
+ * Known limits: no MAPQ for rescued pairs (bg_seed_extend_pairs_rescue_batch[_dev] keeps reporting none); inside a tandem repeat
+ * whose period is shorter than the read the shifted copies touch and are no alternatives (the multi rule's limit). */
+typedef struct {
+    int32_t  min_score;  /* a candidate scoring below this is no alternative and no runner-up */
+    uint32_t mapq_cap;   /* MAPQ of a mate without an alternative; 0 ..= 254 */
+} bg_pairq_params_t;
+int bg_seed_extend_pairs_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                    const bg_pairq_params_t* qp, uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off,
+                                    bg_seed_hit_t* hits, uint8_t* strand, bg_pair_hit_t* pairs, bg_multi_hit_t* multi,
+                                    uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour (operation slots, totals and passes as bg_seed_extend_pairs_batch_dev; d_multi: 2 n_pairs records). */
+int bg_seed_extend_pairs_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                        const bg_pairq_params_t* qp, uint64_t n_pairs, const uint8_t* d_reads,
+                                        const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
+                                        bg_pair_hit_t* d_pairs, bg_multi_hit_t* d_multi, uint8_t* d_ops, uint64_t ops_stride,
+                                        uint64_t* totals, void* stream);
 /* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
  * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
 int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);
@@ -733,7 +777,7 @@ int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const ui
 
 /* ---- SAM records from seed-and-extend hits (sam_emit.hip) -----------------------------------------------
  * The output half of "wire format in, format out": one SAM line (SAM v1.6, section 1.4) per hit slot, formatted in HBM
- * from exactly what bg_fastq_parse_dev and bg_seed_extend_strands / _pairs / _multi_batch_dev leave there; nothing is
+ * from exactly what bg_fastq_parse_dev and bg_seed_extend_strands / _pairs / _pairs_mapq / _multi_batch_dev leave there; nothing is
  * repacked in between.  rust-bio has no SAM writer: the record is defined here from the SAM specification, the way the
  * pair and multi rules are defined above.  fm supplies the ctx and the attached text (bg_fm_set_text[_dev]), which MD needs.
  * Read r is FASTQ record r (recs[r]; its sequence and qualities at seq + seq_off, qual + qual_off, its id in the FASTQ
@@ -761,7 +805,8 @@ int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const ui
  *              pairs[p].proper and both mates are placed on one contig.
  *    3 RNAME   the contig's name, or "*".
  *    4 POS     pos, or 0.  A mate that is not placed takes RNAME and POS from a placed mate (SAM 1.4).
- *    5 MAPQ    0 if not placed or k > 0; otherwise multi[r].mapq if multi is given, else 255.
+ *    5 MAPQ    0 if not placed or k > 0; otherwise multi[r].mapq if multi is given, else 255.  With BG_SAM_PAIRED the records
+ *              of bg_seed_extend_pairs_mapq_batch[_dev] go in as multi: each mate's MAPQ, judged against the pair.
  *    6 CIGAR   byte for byte what bg_cigar_batch_dev(hard_clip = 0) writes for hits[slot].aln, or "*" if not placed (or
  *              without operations).
  *    7 RNEXT   "*" when not paired or neither mate is placed; "=" when this line's RNAME is the mate's contig; otherwise
@@ -774,7 +819,7 @@ int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const ui
  *              bg_revcomp_batch_dev); "*" if the read is empty or k > 0.
  *   11 QUAL    the quality bytes, reversed on the reverse strand; "*" if qual_len != seq_len, if empty, or if k > 0.
  * Tags, on placed lines only, in this order: AS:i:<score>; XS:i:<multi[r].sub_score> with multi, k == 0 and a runner-up
- * (sub_score != BG_MIN_SCORE); NM:i:<number of SUBST + INS + DEL operations> with BG_SAM_TAG_NM; MD:Z:<md> with
+ * (sub_score != BG_MIN_SCORE; with the pairs-mapq records: the mate's best alternative); NM:i:<number of SUBST + INS + DEL operations> with BG_SAM_TAG_NM; MD:Z:<md> with
  * BG_SAM_TAG_MD.  The MD string is built by walking the operations from ref_start with a counter c = 0.  MATCH: c += 1
  * and the text advances.  SUBST: write c, write the text byte, set c = 0; the text advances.  A run of consecutive DEL:
  * write c, '^' and the run's text bytes, set c = 0.  INS: nothing.  At the end write c.  (This yields the specification's

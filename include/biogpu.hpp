@@ -694,6 +694,10 @@ public:
         uint64_t span = 0;      // of the proper pair (SAM |TLEN|); 0 when not proper
         uint32_t n_proper = 0;  // proper combinations among the pair's candidates
         uint8_t rescued = 0;    // seed_extend_batch_pairs_rescue: 1 / 2 = the mate placed inside its partner's insert window
+        // seed_extend_batch_pairs_mapq only, per mate: MAPQ (255: not computed), the best alternative placement's score, 1 or 2 loci
+        uint8_t mapq[2] = {255, 255};
+        int32_t sub_score[2] = {BG_MIN_SCORE, BG_MIN_SCORE};
+        uint32_t n_loci[2] = {0, 0};
     };
     std::vector<PairedSeedHit> seed_extend_batch_pairs(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
                                                        uint32_t min_span = 0, uint32_t max_span = 1000, int32_t pen_unpaired = 17,
@@ -711,11 +715,22 @@ public:
         const bg_rescue_params_t rp = {max_anchors, min_score};
         return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, &rp);
     }
+    // Mapping quality of read pairs (bg_seed_extend_pairs_mapq_batch): seed_extend_batch_pairs, and per mate a MAPQ in 0 ..= mapq_cap
+    // judged against the pair where it is proper (0: another placement of the mate serves the pair as well; mapq_cap: there is no
+    // other placement) and as seed_extend_batch_multi judges a single read where it is not.  A candidate below min_score is no
+    // alternative.
+    std::vector<PairedSeedHit> seed_extend_batch_pairs_mapq(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                            int32_t min_score = INT32_MIN, uint32_t mapq_cap = 60, uint32_t min_span = 0,
+                                                            uint32_t max_span = 1000, int32_t pen_unpaired = 17, uint32_t seed_len = 20,
+                                                            uint32_t stride = 10, uint32_t max_occ = 16, uint32_t pad = 25) const {
+        const bg_pairq_params_t qp = {min_score, mapq_cap};
+        return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, nullptr, &qp);
+    }
 
 private:
     std::vector<PairedSeedHit> pairs_impl(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads, uint32_t min_span,
                                           uint32_t max_span, int32_t pen_unpaired, uint32_t seed_len, uint32_t stride, uint32_t max_occ,
-                                          uint32_t pad, const bg_rescue_params_t* rp) const {
+                                          uint32_t pad, const bg_rescue_params_t* rp, const bg_pairq_params_t* qp = nullptr) const {
         if (reads.size() % 2) throw std::invalid_argument("seed_extend_batch_pairs: an odd number of reads (mates come in pairs)");
         std::vector<int32_t> table;
         const bg_scoring_t sc = scoring.to_c(table);
@@ -732,15 +747,18 @@ private:
         std::vector<uint8_t> strand(reads.size());
         std::vector<bg_pair_hit_t> pairs(std::max<size_t>(n_pairs, 1));
         std::vector<uint8_t> rescued(std::max<size_t>(n_pairs, 1));
+        std::vector<bg_multi_hit_t> multi(qp ? std::max<size_t>(reads.size(), 1) : 0);
         // (a rescued hit has up to read + max_span operations)
         std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4 + (rp ? max_span : 0)) * reads.size() + 8);
         uint64_t used = 0;
         const int rc = rp ? bg_seed_extend_pairs_rescue_batch(h_, &sc, &prm, &pp, rp, n_pairs, buf.data(), off.data(), hits.data(),
                                                               strand.data(), pairs.data(), rescued.data(), ops.data(), ops.size(), &used)
+                       : qp ? bg_seed_extend_pairs_mapq_batch(h_, &sc, &prm, &pp, qp, n_pairs, buf.data(), off.data(), hits.data(),
+                                                              strand.data(), pairs.data(), multi.data(), ops.data(), ops.size(), &used)
                           : bg_seed_extend_pairs_batch(h_, &sc, &prm, &pp, n_pairs, buf.data(), off.data(), hits.data(), strand.data(),
                                                        pairs.data(), ops.data(), ops.size(), &used);
         if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
-        check(rc, rp ? "bg_seed_extend_pairs_rescue_batch" : "bg_seed_extend_pairs_batch");
+        check(rc, rp ? "bg_seed_extend_pairs_rescue_batch" : qp ? "bg_seed_extend_pairs_mapq_batch" : "bg_seed_extend_pairs_batch");
         std::vector<PairedSeedHit> res(n_pairs);
         for (size_t p = 0; p < n_pairs; p++) {
             for (int m = 0; m < 2; m++) {
@@ -751,6 +769,11 @@ private:
                 o.ref_end = (size_t)h.ref_end;
                 o.n_candidates = h.n_candidates;
                 o.reverse = strand[2 * p + m] == BG_HIT_REVERSE;
+                if (qp) {
+                    res[p].mapq[m] = multi[2 * p + m].mapq;
+                    res[p].sub_score[m] = multi[2 * p + m].sub_score;
+                    res[p].n_loci[m] = multi[2 * p + m].n_loci;
+                }
             }
             res[p].proper = pairs[p].proper != 0;
             res[p].span = pairs[p].span;

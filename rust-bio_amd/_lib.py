@@ -116,6 +116,14 @@ MULTI_HIT_DTYPE = np.dtype([("sub_score", "<i4"), ("n_loci", "<u4"), ("n_reporte
 assert MULTI_HIT_DTYPE.itemsize == 16, MULTI_HIT_DTYPE.itemsize
 
 
+# bg_pairq_params_t (bg_seed_extend_pairs_mapq_batch[_dev])
+class PAIRQ_PARAMS(C.Structure):
+    _fields_ = [("min_score", C.c_int32), ("mapq_cap", C.c_uint32)]
+
+
+assert C.sizeof(PAIRQ_PARAMS) == 8, C.sizeof(PAIRQ_PARAMS)
+
+
 # bg_fastq_record_t
 FQREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"),
                         ("id_len", "<u4"), ("desc_len", "<u4"), ("seq_len", "<u4"), ("qual_len", "<u4"),
@@ -148,6 +156,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
            "bg_seed_extend_pairs_rescue_batch", "bg_seed_extend_pairs_rescue_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
+           "bg_seed_extend_pairs_mapq_batch", "bg_seed_extend_pairs_mapq_batch_dev",
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -275,6 +284,10 @@ def lib():
                                                  vp, vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_multi_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(MULTI_PARAMS), u32, u64, vp,
                                                      vp, u32, vp, vp, vp, vp, u64, vp, vp]
+        L.bg_seed_extend_pairs_mapq_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                      C.POINTER(PAIRQ_PARAMS), u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.bg_seed_extend_pairs_mapq_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                          C.POINTER(PAIRQ_PARAMS), u64, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp]
         L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
         L.bg_sam_header.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
         L.bg_sam_emit_batch_dev.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,

@@ -341,6 +341,12 @@ int bg_fm_search_seeds_dev(bg_fm* fm, uint64_t n_reads, const uint8_t* d_reads, 
 int bg_seed_pairs_launch(const bg_pair_params_t* pp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff, const uint32_t* d_n_hits,
                          const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits,
                          uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint32_t max_cand, hipStream_t st);
+// seed_pairq.hip: S7 of bg_seed_extend_pairs_mapq_batch_dev over one pass: what bg_seed_pairs_launch writes, plus records
+// r0 + 2p, r0 + 2p + 1 of d_multi for the mates of pair p.
+int bg_seed_pairq_launch(const bg_pair_params_t* pp, const bg_pairq_params_t* qp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff,
+                         const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
+                         bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs,
+                         bg_multi_hit_t* d_multi, uint32_t max_cand, hipStream_t st);
 // seed_rescue.hip: stages R1, R2, R4 of bg_seed_extend_pairs_rescue_batch_dev over one pass, on the same pass scratch (d_voff: the
 // offsets of the pass's 4 n_pairs virtual reads).  R1 answers every pair as bg_seed_pairs_launch does and plans the rescue
 // alignments (d_plan: bg_seed_rescue_plan_bytes(n_pairs) bytes; per pair the mates' own score sum and the counts of rescue

@@ -23,6 +23,8 @@
 //   S7 best             per read: highest score, smallest start among equals           -> bg_seed_hit_t + its ops
 //      (pair mode, bg_seed_extend_pairs_batch[_dev]: per pair of interleaved mates, the best proper FR combination of their
 //       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t;
+//       pairs-mapq mode, bg_seed_extend_pairs_mapq_batch[_dev]: pair mode plus a bg_multi_hit_t per mate, its MAPQ judged against the
+//       pair (seed_pairq.hip);
 //       multi mode, bg_seed_extend_multi_batch[_dev]: per read up to K loci that do not touch, in rank order -> K bg_seed_hit_t +
 //       their ops, bg_multi_hit_t with the runner-up's score and MAPQ;
 //       rescue mode, bg_seed_extend_pairs_rescue_batch[_dev]: pair mode, then for the pairs without a proper combination the stages
@@ -390,11 +392,12 @@ namespace {
 // Multi mode (`multi` set): se_multi_kernel replaces S7; d_hits / d_strand / d_ops hold multi->max_hits slots per read, d_multi one
 // record per read.
 // Rescue mode (`rescue` set, pair mode): R1-R4 of seed_rescue.hip replace S7; d_rescued one byte per pair, totals 4 entries.
+// Pairs-mapq mode (`pairq` set, pair mode): se_pairq_kernel replaces S7, writing d_pairs and one d_multi record per mate.
 int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
            const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
            uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
            bg_pair_hit_t* d_pairs = nullptr, const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* d_multi = nullptr,
-           const bg_rescue_params_t* rescue = nullptr, uint8_t* d_rescued = nullptr) {
+           const bg_rescue_params_t* rescue = nullptr, uint8_t* d_rescued = nullptr, const bg_pairq_params_t* pairq = nullptr) {
     if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
     if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
     if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
@@ -577,6 +580,10 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
                     return rc;
             }
             done_rescue += RC;
+        } else if (pairq) {
+            if ((rc = bg_seed_pairq_launch(pair, pairq, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand,
+                                           d_pairs, d_multi, kMaxProposals, st)))
+                return rc;
         } else if (pair) {
             if ((rc = bg_seed_pairs_launch(pair, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_pairs,
                                            kMaxProposals, st)))
@@ -653,6 +660,27 @@ extern "C" int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc,
 
 namespace {
 
+// the pairs-mapq calls' own argument checks; every other one is the pair calls' and se_run's
+int pairq_args(const bg_pairq_params_t* qp, const void* multi) {
+    if (!qp || !multi || qp->mapq_cap > 254) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_seed_extend_pairs_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                                   const bg_pairq_params_t* qp, uint64_t n_pairs, const uint8_t* d_reads,
+                                                   const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits,
+                                                   uint8_t* d_strand, bg_pair_hit_t* d_pairs, bg_multi_hit_t* d_multi, uint8_t* d_ops,
+                                                   uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
+    if (int rc = pairq_args(qp, d_multi)) return rc;
+    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
+                  stream, pp, d_pairs, nullptr, d_multi, nullptr, nullptr, qp);
+}
+
+namespace {
+
 // the rescue calls' own argument checks; every other one is the pair calls' and se_run's
 int rescue_args(const bg_rescue_params_t* rp, const void* rescued) {
     if (!rp || !rescued || rp->max_anchors == 0 || rp->max_anchors > BG_RESCUE_MAX_ANCHORS) return BG_ERR_INVALID_ARG;
@@ -705,12 +733,12 @@ extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in
 namespace {
 
 // the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order (multi mode:
-// multi->max_hits slots per read in hits / strand, compacted in slot order)
+// multi->max_hits slots per read in hits / strand, compacted in slot order; pairs-mapq mode: one `multis` record per read)
 int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
                 const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
                 uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr,
                 const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* multis = nullptr, const bg_rescue_params_t* rescue = nullptr,
-                uint8_t* rescued = nullptr) {
+                uint8_t* rescued = nullptr, const bg_pairq_params_t* pairq = nullptr) {
     if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (n_reads == 0) return BG_OK;
@@ -741,18 +769,18 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
         if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_slots));
         if (pair) BG_HIP(hipMalloc((void**)&d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t)));
         if (rescue) BG_HIP(hipMalloc((void**)&d_rescued, std::max<uint64_t>(n_reads / 2, 16)));
-        if (multi) BG_HIP(hipMalloc((void**)&d_multi, n_reads * sizeof(bg_multi_hit_t)));
+        if (multi || pairq) BG_HIP(hipMalloc((void**)&d_multi, n_reads * sizeof(bg_multi_hit_t)));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st,
-                        pair, d_pairs, multi, d_multi, rescue, d_rescued);
+                        pair, d_pairs, multi, d_multi, rescue, d_rescued, pairq);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(hits, d_hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
         if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_slots, hipMemcpyDeviceToHost, st));
         if (pair) BG_HIP(hipMemcpyAsync(pairs, d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
         if (rescue) BG_HIP(hipMemcpyAsync(rescued, d_rescued, n_reads / 2, hipMemcpyDeviceToHost, st));
-        if (multi) BG_HIP(hipMemcpyAsync(multis, d_multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
+        if (multi || pairq) BG_HIP(hipMemcpyAsync(multis, d_multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_slots * stride);
             BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_slots * stride, hipMemcpyDeviceToHost, st));
@@ -827,4 +855,14 @@ extern "C" int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, con
                                           uint64_t* ops_used) {
     if (int rc = multi_args(mp, multi, strands, n_reads)) return rc;
     return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, nullptr, nullptr, mp, multi);
+}
+
+extern "C" int bg_seed_extend_pairs_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                               const bg_pairq_params_t* qp, uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off,
+                                               bg_seed_hit_t* hits, uint8_t* strand, bg_pair_hit_t* pairs, bg_multi_hit_t* multi,
+                                               uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
+    if (int rc = pairq_args(qp, multi)) return rc;
+    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
+                       multi, nullptr, nullptr, qp);
 }

@@ -7,7 +7,8 @@ operations — runs in HIP kernels behind the C ABI (rust-bio_amd/csrc/seed_exte
 include/biogpu.h (the tests hold a CPU statement of it).  The `_strands` calls map each read on the forward strand, on
 the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  The `_pairs` calls map interleaved mates of
 paired-end reads and report the best proper FR pair where there is one; the `_pairs_rescue` calls also look for a mate without a
-seeded candidate inside its partner's insert window.  The `_multi` calls report up to K loci per read that
+seeded candidate inside its partner's insert window; the `_pairs_mapq` calls add a MAPQ per mate, judged against the pair.  The
+`_multi` calls report up to K loci per read that
 do not touch, the runner-up's score and a MAPQ.  This module only marshals arguments."""
 import ctypes as C
 
@@ -56,6 +57,17 @@ class MultiParams:
 
     def to_c(self):
         return _lib.MULTI_PARAMS(self.max_hits, self.min_score, self.mapq_cap)
+
+
+class PairQualityParams:
+    """bg_pairq_params_t: a candidate scoring below min_score is no alternative placement of a mate (and no runner-up); mapq_cap
+    (0 ..= 254) is the MAPQ of a mate without an alternative."""
+
+    def __init__(self, min_score=-2**31, mapq_cap=60):
+        self.min_score, self.mapq_cap = min_score, mapq_cap
+
+    def to_c(self):
+        return _lib.PAIRQ_PARAMS(self.min_score, self.mapq_cap)
 
 
 def attach_text(fm, text=None, d_text=None):
@@ -172,6 +184,49 @@ def seed_extend_pairs_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_le
                                                          max_read_len, d_hits, d_strand or None, d_pairs or None, d_ops or None,
                                                          ops_stride, totals.ctypes.data if totals is not None else None, stream),
                "bg_seed_extend_pairs_batch_dev")
+
+
+def seed_extend_pairs_mapq_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, quality_params=None, want_ops=True,
+                                  allow_out_of_alphabet=False):
+    """bg_seed_extend_pairs_mapq_batch, host buffers: seed_extend_pairs_arrays plus a mapping quality per mate.  Returns (hits,
+    strand, pairs, multi: MULTI_HIT_DTYPE[2n] — read r's MAPQ, its best alternative's score and n_loci —, ops)."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    quality_params = quality_params or PairQualityParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    if n % 2:
+        raise ValueError("seed_extend_pairs_mapq_arrays: an odd number of reads")
+    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n, 1), dtype=np.uint8)
+    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
+    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
+    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc, pp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), quality_params.to_c()
+    rc = _lib.lib().bg_seed_extend_pairs_mapq_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(qp), n // 2, rd.ctypes.data,
+                                                    off.ctypes.data, hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
+                                                    multi.ctypes.data, ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_pairs_mapq_batch")
+    return hits, strand[:n], pairs[:n // 2], multi[:n], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_pairs_mapq_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_multi, d_strand=0, d_ops=0,
+                               ops_stride=0, params=None, pair_params=None, quality_params=None, stream=0, totals=None):
+    """bg_seed_extend_pairs_mapq_batch_dev (pointers are ints; as seed_extend_pairs_dev, plus d_multi: 2 n_pairs bg_multi_hit_t,
+    which bg_sam_emit_batch_dev takes as its d_multi together with SAM_PAIRED)."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    quality_params = quality_params or PairQualityParams()
+    sc, pc, pp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), quality_params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_pairs_mapq_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(qp), n_pairs, d_reads,
+                                                              d_read_off, max_read_len, d_hits, d_strand or None, d_pairs or None,
+                                                              d_multi or None, d_ops or None, ops_stride,
+                                                              totals.ctypes.data if totals is not None else None, stream),
+               "bg_seed_extend_pairs_mapq_batch_dev")
 
 
 def seed_extend_pairs_rescue_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, rescue_params=None, want_ops=True,
