@@ -613,8 +613,8 @@ int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_s
  * max_span also sizes the window: with max_span one below a fragment's length the mate is still found, aligned without its last
  * base, and the accepted span is then at most max_span.
  * Known limits: a forward mate that ends beyond its reverse partner's end is outside the window (dovetailed mates); a better
- * rescued pair is not sought when a proper seeded combination exists; a rescue window may cross a contig boundary; MAPQ is not
- * recomputed for a rescued mate. */
+ * rescued pair is not sought when a proper seeded combination exists; a rescue window may cross a contig boundary.  (A MAPQ for
+ * the mates of a rescued pair: bg_seed_extend_pairs_rescue_mapq_batch[_dev] below.) */
 enum { BG_RESCUE_MAX_ANCHORS = 4 };
 typedef struct {
     uint32_t max_anchors;  /* A: anchors tried per mate, 1 ..= BG_RESCUE_MAX_ANCHORS */
@@ -705,8 +705,8 @@ int bg_seed_extend_multi_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_s
  * both sums (S2_i = x.score + c_j.score through a proper combination) the formula is the multi rule's on mate i's scores, so a
  * pair and a single read agree where they should.
  * BG_ERR_INVALID_ARG: a null qp or multi, mapq_cap above 254; everything else is the paired call's.
- * Known limits: no MAPQ for rescued pairs (bg_seed_extend_pairs_rescue_batch[_dev] keeps reporting none); inside a tandem repeat
- * whose period is shorter than the read the shifted copies touch and are no alternatives (the multi rule's limit). */
+ * Known limit: inside a tandem repeat whose period is shorter than the read the shifted copies touch and are no alternatives (the
+ * multi rule's limit).  (This call never rescues; bg_seed_extend_pairs_rescue_mapq_batch[_dev] below rescues and judges.) */
 typedef struct {
     int32_t  min_score;  /* a candidate scoring below this is no alternative and no runner-up */
     uint32_t mapq_cap;   /* MAPQ of a mate without an alternative; 0 ..= 254 */
@@ -721,6 +721,52 @@ int bg_seed_extend_pairs_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
                                         const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
                                         bg_pair_hit_t* d_pairs, bg_multi_hit_t* d_multi, uint8_t* d_ops, uint64_t ops_stride,
                                         uint64_t* totals, void* stream);
+/* Mapping quality of rescued read pairs.  The rescue call places a mate inside its partner's insert window and says nothing of
+ * how unique either placement is; the pairs-mapq call judges every mate and never rescues.  The rescue-mapq call is the rescue
+ * call plus one bg_multi_hit_t per read (multi[2p], multi[2p + 1]: the mates of pair p).  rp is the rescue call's, qp the
+ * pairs-mapq call's.  This is this library's own definition (rust-bio has no mapper).
+ *   outputs          hits, strand, pairs, rescued, operation slots and totals (4 entries) are byte for byte what
+ *                    bg_seed_extend_pairs_rescue_batch[_dev] writes for the same arguments;
+ *   rescued[p] == 0  multi[2p] and multi[2p + 1] are exactly what bg_seed_extend_pairs_mapq_batch[_dev] writes for that pair: the
+ *                    pairs-mapq rule with a proper seeded combination, the multi rule at K = 1 otherwise, also where rescue
+ *                    alignments were run and none was accepted or "paired or not" turned the choice down;
+ *   rescued[p] != 0  the chosen rescue is (anchor candidate c_a of mate a, rescued hit h of mate r); c_i is mate i's reported hit
+ *                    (c_a or h); S1 = c_a.score + h.score (64-bit); touches is the multi rule's test.  An accepted rescue is any
+ *                    planned rescue alignment of the pair that passes the rescue rule's acceptance, chosen or not; its two
+ *                    members are its anchor (a seeded candidate of the anchoring mate) and its hit (a placement of the other
+ *                    mate).  For mate i with partner j:
+ *                    alternatives of mate i: every seeded candidate x of mate i, on either strand, with x.score >= qp.min_score
+ *                    and !touches(x, c_i); and the mate-i member y of every accepted rescue with y.score >= qp.min_score and
+ *                    !touches(y, c_i).  sub_score = the highest score among the alternatives, or BG_MIN_SCORE if there are none;
+ *                    n_loci = 2 or 1 accordingly; n_reported = 1.
+ *                    S2_i = the maximum over (a) every accepted rescue whose mate-i member is an alternative: its anchor's score
+ *                    plus its hit's score; (b) every seeded alternative x: x.score + c_j.score - pen_unpaired.
+ *                    mapq = 0 if c_i.score <= 0; mapq_cap if mate i has no alternative; otherwise min(mapq_cap, mapq_cap *
+ *                    clamp(S1 - S2_i, 0, c_i.score) / c_i.score), in 64-bit signed integers, the division truncating.
+ * Unlike the seeded rule, S1 >= S2_i does not always hold here: the chosen anchor is one of its mate's first A candidates by rank
+ * and need not be that mate's best (the best one's own rescue may have failed), and the rescued hit may score above own(j); a
+ * better-scoring seeded candidate of the anchor's mate then gives S2_i > S1 through (b).  Hence the clamp at 0: such a mate gets
+ * mapq 0.
+ * What the rule gives: an anchor inside a far two-copy repeat costs the anchor's mate pen_unpaired (mapq = mapq_cap *
+ * pen_unpaired / score) and the rescued mate gets mapq_cap; two anchors that rescue the same placement give the anchor's mate 0
+ * and the rescued mate mapq_cap (the two hits touch); a fragment wholly inside a two-copy repeat gives both mates 0; a rescued
+ * mate with an exact seeded copy elsewhere is judged through (b).
+ * Argument checks, limits, the ops_stride minimum, totals, passes and the extra waits are the rescue call's; in addition a null
+ * qp or multi, or mapq_cap above 254: BG_ERR_INVALID_ARG.  An error writes nothing.
+ * Known limits: those of the rescue rule (dovetailed mates, no rescue where a proper seeded combination exists, windows that
+ * cross a contig boundary) and the multi rule's tandem-repeat limit. */
+int bg_seed_extend_pairs_rescue_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                           const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs,
+                                           const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand,
+                                           bg_pair_hit_t* pairs, uint8_t* rescued, bg_multi_hit_t* multi, uint8_t* ops_buf,
+                                           uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour (operation slots, totals and passes as bg_seed_extend_pairs_rescue_batch_dev; d_multi: 2 n_pairs records). */
+int bg_seed_extend_pairs_rescue_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                               const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs,
+                                               const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                               bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_rescued,
+                                               bg_multi_hit_t* d_multi, uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals,
+                                               void* stream);
 /* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
  * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
 int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);

@@ -694,7 +694,7 @@ public:
         uint64_t span = 0;      // of the proper pair (SAM |TLEN|); 0 when not proper
         uint32_t n_proper = 0;  // proper combinations among the pair's candidates
         uint8_t rescued = 0;    // seed_extend_batch_pairs_rescue: 1 / 2 = the mate placed inside its partner's insert window
-        // seed_extend_batch_pairs_mapq only, per mate: MAPQ (255: not computed), the best alternative placement's score, 1 or 2 loci
+        // seed_extend_batch_pairs_mapq and seed_extend_batch_pairs_rescue_mapq only, per mate: MAPQ (255: not computed), the best alternative placement's score, 1 or 2 loci
         uint8_t mapq[2] = {255, 255};
         int32_t sub_score[2] = {BG_MIN_SCORE, BG_MIN_SCORE};
         uint32_t n_loci[2] = {0, 0};
@@ -726,6 +726,19 @@ public:
         const bg_pairq_params_t qp = {min_score, mapq_cap};
         return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, nullptr, &qp);
     }
+    // Mapping quality of rescued read pairs (bg_seed_extend_pairs_rescue_mapq_batch): seed_extend_batch_pairs_rescue, and per mate the
+    // MAPQ of seed_extend_batch_pairs_mapq; the mates of a rescued pair are judged against the pair's other accepted rescues and
+    // the mates' seeded candidates elsewhere.  rescue_min_score discards a rescued alignment, min_score an alternative.
+    std::vector<PairedSeedHit> seed_extend_batch_pairs_rescue_mapq(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                                   uint32_t max_anchors = 2, int32_t rescue_min_score = 0,
+                                                                   int32_t min_score = INT32_MIN, uint32_t mapq_cap = 60,
+                                                                   uint32_t min_span = 0, uint32_t max_span = 1000, int32_t pen_unpaired = 17,
+                                                                   uint32_t seed_len = 20, uint32_t stride = 10, uint32_t max_occ = 16,
+                                                                   uint32_t pad = 25) const {
+        const bg_rescue_params_t rp = {max_anchors, rescue_min_score};
+        const bg_pairq_params_t qp = {min_score, mapq_cap};
+        return pairs_impl(scoring, reads, min_span, max_span, pen_unpaired, seed_len, stride, max_occ, pad, &rp, &qp);
+    }
 
 private:
     std::vector<PairedSeedHit> pairs_impl(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads, uint32_t min_span,
@@ -751,14 +764,20 @@ private:
         // (a rescued hit has up to read + max_span operations)
         std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4 + (rp ? max_span : 0)) * reads.size() + 8);
         uint64_t used = 0;
-        const int rc = rp ? bg_seed_extend_pairs_rescue_batch(h_, &sc, &prm, &pp, rp, n_pairs, buf.data(), off.data(), hits.data(),
+        const int rc = rp && qp ? bg_seed_extend_pairs_rescue_mapq_batch(h_, &sc, &prm, &pp, rp, qp, n_pairs, buf.data(), off.data(),
+                                                                         hits.data(), strand.data(), pairs.data(), rescued.data(),
+                                                                         multi.data(), ops.data(), ops.size(), &used)
+                       : rp ? bg_seed_extend_pairs_rescue_batch(h_, &sc, &prm, &pp, rp, n_pairs, buf.data(), off.data(), hits.data(),
                                                               strand.data(), pairs.data(), rescued.data(), ops.data(), ops.size(), &used)
                        : qp ? bg_seed_extend_pairs_mapq_batch(h_, &sc, &prm, &pp, qp, n_pairs, buf.data(), off.data(), hits.data(),
                                                               strand.data(), pairs.data(), multi.data(), ops.data(), ops.size(), &used)
                           : bg_seed_extend_pairs_batch(h_, &sc, &prm, &pp, n_pairs, buf.data(), off.data(), hits.data(), strand.data(),
                                                        pairs.data(), ops.data(), ops.size(), &used);
         if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a seed holds a byte outside the index's alphabet");
-        check(rc, rp ? "bg_seed_extend_pairs_rescue_batch" : qp ? "bg_seed_extend_pairs_mapq_batch" : "bg_seed_extend_pairs_batch");
+        check(rc, rp && qp ? "bg_seed_extend_pairs_rescue_mapq_batch"
+                  : rp   ? "bg_seed_extend_pairs_rescue_batch"
+                  : qp   ? "bg_seed_extend_pairs_mapq_batch"
+                         : "bg_seed_extend_pairs_batch");
         std::vector<PairedSeedHit> res(n_pairs);
         for (size_t p = 0; p < n_pairs; p++) {
             for (int m = 0; m < 2; m++) {

@@ -157,6 +157,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_seed_extend_pairs_rescue_batch", "bg_seed_extend_pairs_rescue_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
            "bg_seed_extend_pairs_mapq_batch", "bg_seed_extend_pairs_mapq_batch_dev",
+           "bg_seed_extend_pairs_rescue_mapq_batch", "bg_seed_extend_pairs_rescue_mapq_batch_dev",
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -288,6 +289,12 @@ def lib():
                                                       C.POINTER(PAIRQ_PARAMS), u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_pairs_mapq_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
                                                           C.POINTER(PAIRQ_PARAMS), u64, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp]
+        L.bg_seed_extend_pairs_rescue_mapq_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                             C.POINTER(RESCUE_PARAMS), C.POINTER(PAIRQ_PARAMS), u64, vp, vp, vp, vp, vp,
+                                                             vp, vp, vp, u64, C.POINTER(u64)]
+        L.bg_seed_extend_pairs_rescue_mapq_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS),
+                                                                 C.POINTER(RESCUE_PARAMS), C.POINTER(PAIRQ_PARAMS), u64, vp, vp, u32, vp,
+                                                                 vp, vp, vp, vp, vp, u64, vp, vp]
         L.bg_revcomp_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp]
         L.bg_sam_header.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
         L.bg_sam_emit_batch_dev.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,

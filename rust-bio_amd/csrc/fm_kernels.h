@@ -367,6 +367,13 @@ int bg_seed_rescue_pick_launch(const bg_pair_params_t* pp, const bg_rescue_param
                                bg_pair_hit_t* d_pairs, uint8_t* d_rescued, hipStream_t st);
 // *d_count += the pairs of the call with a non-zero rescued byte (totals[3])
 int bg_seed_rescue_count_launch(uint64_t n_pairs, const uint8_t* d_rescued, uint64_t* d_count, hipStream_t st);
+// seed_rescueq.hip: the stage after R4 of bg_seed_extend_pairs_rescue_mapq_batch_dev over one pass: records r0 + 2p, r0 + 2p + 1 of
+// d_multi for the mates of every pair p of the pass with a non-zero rescued byte, from the plan and the rescue alignments that
+// R1-R4 left in the pass scratch.  The other pairs' records are written before R1 (bg_seed_pairq_launch) and stay.
+int bg_seed_rescueq_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs, uint64_t r0,
+                           const uint64_t* d_coff, const bg_alignment_t* d_aln, const uint64_t* d_w_lo, const void* d_plan,
+                           const uint64_t* d_roff, const bg_alignment_t* d_r_aln, const uint8_t* d_rescued, bg_multi_hit_t* d_multi,
+                           hipStream_t st);
 // seed_multi.hip: S7 of bg_seed_extend_multi_batch_dev over one pass (n_reads reads from caller read r0 on, G virtual reads
 // each; strand1: the strand of every hit when G = 1), on the same pass scratch.  Read r0 + r owns slots K (r0 + r) ..
 // K (r0 + r) + K - 1 of d_hits / d_strand / d_ops and record r0 + r of d_multi.  max_cand bounds the candidates of one

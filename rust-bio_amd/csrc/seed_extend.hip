@@ -393,6 +393,8 @@ namespace {
 // record per read.
 // Rescue mode (`rescue` set, pair mode): R1-R4 of seed_rescue.hip replace S7; d_rescued one byte per pair, totals 4 entries.
 // Pairs-mapq mode (`pairq` set, pair mode): se_pairq_kernel replaces S7, writing d_pairs and one d_multi record per mate.
+// Both (`rescue` and `pairq` set): se_pairq_kernel writes every pair's records before R1, which rewrites the same hits; after R4
+// se_rescue_mapq_kernel (seed_rescueq.hip) rewrites the records of the rescued pairs.
 int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
            const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
            uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
@@ -544,6 +546,10 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
             uint32_t *d_rxb = d_rn + np, *d_ryb = d_rxb + np;
             uint64_t* d_roff = (uint64_t*)W.p[18];
             uint64_t *d_rxoff = d_roff + (np + 1), *d_ryoff = d_rxoff + (np + 1);
+            // (rescue-mapq call: every pair's records first, as the pairs-mapq call writes them; a pass may end after R1)
+            if (pairq && (rc = bg_seed_pairq_launch(pair, pairq, np, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
+                                                    d_strand, d_pairs, d_multi, kMaxProposals, st)))
+                return rc;
             if ((rc = bg_seed_rescue_plan_launch(pair, rescue, prm.n_text, np, r0, roff, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops,
                                                  ops_stride, d_strand, d_pairs, d_rescued, W.p[16], d_own, d_rn, d_rxb, d_ryb, kMaxProposals,
                                                  st)))
@@ -577,6 +583,10 @@ int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, ui
                 // ---- R4: the rescued pairs
                 if ((rc = bg_seed_rescue_pick_launch(pair, rescue, np, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, W.p[16], d_own, d_roff, d_raln,
                                                      d_rops, d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued, st)))
+                    return rc;
+                // ---- the records of the rescued pairs (the plan and d_raln are still live)
+                if (pairq && (rc = bg_seed_rescueq_launch(pair, rescue, pairq, np, r0, d_coff, d_aln, d_wlo, W.p[16], d_roff, d_raln, d_rescued,
+                                                          d_multi, st)))
                     return rc;
             }
             done_rescue += RC;
@@ -700,6 +710,19 @@ extern "C" int bg_seed_extend_pairs_rescue_batch_dev(bg_fm* fm, const bg_scoring
                   stream, pp, d_pairs, nullptr, nullptr, rp, d_rescued);
 }
 
+extern "C" int bg_seed_extend_pairs_rescue_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm,
+                                                          const bg_pair_params_t* pp, const bg_rescue_params_t* rp, const bg_pairq_params_t* qp,
+                                                          uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off,
+                                                          uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs,
+                                                          uint8_t* d_rescued, bg_multi_hit_t* d_multi, uint8_t* d_ops, uint64_t ops_stride,
+                                                          uint64_t* totals, void* stream) {
+    if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
+    if (int rc = rescue_args(rp, d_rescued)) return rc;
+    if (int rc = pairq_args(qp, d_multi)) return rc;
+    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
+                  stream, pp, d_pairs, nullptr, d_multi, rp, d_rescued, qp);
+}
+
 namespace {
 
 // the multi calls' own argument checks; every other one is se_run's
@@ -733,7 +756,8 @@ extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in
 namespace {
 
 // the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order (multi mode:
-// multi->max_hits slots per read in hits / strand, compacted in slot order; pairs-mapq mode: one `multis` record per read)
+// multi->max_hits slots per read in hits / strand, compacted in slot order; pairs-mapq and rescue-mapq mode: one `multis` record
+// per read)
 int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
                 const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
                 uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr,
@@ -865,4 +889,16 @@ extern "C" int bg_seed_extend_pairs_mapq_batch(bg_fm* fm, const bg_scoring_t* sc
     if (int rc = pairq_args(qp, multi)) return rc;
     return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
                        multi, nullptr, nullptr, qp);
+}
+
+extern "C" int bg_seed_extend_pairs_rescue_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
+                                                      const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs,
+                                                      const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand,
+                                                      bg_pair_hit_t* pairs, uint8_t* rescued, bg_multi_hit_t* multi, uint8_t* ops_buf,
+                                                      uint64_t ops_cap, uint64_t* ops_used) {
+    if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
+    if (int rc = rescue_args(rp, rescued)) return rc;
+    if (int rc = pairq_args(qp, multi)) return rc;
+    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
+                       multi, rp, rescued, qp);
 }

@@ -12,27 +12,11 @@
 // A pass without a single rescue alignment stops after R1's read-back.
 #include <algorithm>
 
-#include "seed_pair_rule.h"
+#include "seed_rescue_rule.h"
 
 namespace {
 
 using namespace bgpair;
-
-constexpr uint32_t kSlots = 2 * BG_RESCUE_MAX_ANCHORS;  // rescue alignments of one pair: up to A per anchoring mate
-
-// one planned rescue alignment; entry k of pair p is plan[kSlots * p + k]
-struct RescuePlan {
-    uint64_t lo;    // the window's first text offset
-    uint32_t len;   // its length, 1 ..= max_span
-    uint32_t info;  // anchor candidate relative to cb[0] (bits 0-12) | x's virtual read within the pair << 16 | rank << 18 |
-                    // anchor on the forward strand << 20 | anchoring mate << 21
-};
-
-struct RescuePrm {
-    uint32_t max_anchors;
-    int32_t min_score;
-    uint64_t n_text;
-};
 
 // R1: 16 lanes per pair.  Every pair is first answered as the paired call answers it (rescued = 0).  The anchors of a mate are
 // its first A candidates in rank order: A rounds of the own-best key's max over the keys below the last one found.
@@ -137,8 +121,8 @@ __global__ __launch_bounds__(256) void se_rescue_gather_kernel(uint64_t n_pairs,
     }
 }
 
-// R4: 16 lanes per pair, one lane per planned rescue (kSlots <= 16).  Key of an accepted rescue: the score sum biased to
-// unsigned (33 bits), 1 for orientation A, 1 for the rescue anchored on m1, ~rank (2 bits), so the max is the rule's choice.
+// R4: 16 lanes per pair, one lane per planned rescue (kSlots <= 16).  The max of the accepted rescues' keys (rescue_key of
+// seed_rescue_rule.h) is the rule's choice.
 __global__ __launch_bounds__(256) void se_rescue_pick_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, RescuePrm rp,
                                                              const uint64_t* __restrict__ coff, const uint32_t* __restrict__ n_hits,
                                                              const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ c_ops,
@@ -161,23 +145,11 @@ __global__ __launch_bounds__(256) void se_rescue_pick_kernel(uint64_t n_pairs, u
     uint64_t key = 0;
     if (l16 < n) {
         const RescuePlan e = plan[kSlots * p + l16];
-        const bg_alignment_t& q = r_aln[j0 + l16];
-        const uint64_t ca = R.cb[0] + (e.info & 0x1FFF);
-        const bool fwd = (e.info >> 20) & 1;
-        const uint32_t m = (e.info >> 21) & 1;
-        const uint64_t as = w_lo[ca] + aln[ca].ystart, ae = w_lo[ca] + aln[ca].yend;
-        const uint64_t qs = e.lo + q.ystart, qe = e.lo + q.yend;
-        const uint64_t f_start = fwd ? as : qs, b_start = fwd ? qs : as;  // the forward one is `a`, the reverse one `b`
-        const uint64_t span = max(ae, qe) - f_start;
-        if (q.score >= rp.min_score && f_start <= b_start && span >= pp.min_span && span <= pp.max_span) {
-            const uint64_t sum = (uint64_t)((int64_t)aln[ca].score + q.score + (1ll << 32));
-            const bool orient_a = fwd == (m == 0);  // m1 forward: m1 anchors forward, or m2 anchors in reverse
-            key = sum << 8 | (uint64_t)orient_a << 7 | (uint64_t)(m == 0) << 6 | (3u - ((e.info >> 18) & 3)) << 4 | l16;
-        }
+        key = rescue_key(e, r_aln[j0 + l16], l16, R.cb[0], pp, rp.min_score, aln, w_lo);
     }
     key = max16(key);
     if (!key) return;
-    const int64_t sum = (int64_t)(key >> 8) - (1ll << 32);
+    const int64_t sum = rescue_key_sum(key);
     if (sum + pp.pen_unpaired < own_sum[p]) return;
     const uint32_t k = (uint32_t)key & 15;
     const RescuePlan e = plan[kSlots * p + k];

@@ -274,6 +274,57 @@ def seed_extend_pairs_rescue_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_
                "bg_seed_extend_pairs_rescue_batch_dev")
 
 
+def seed_extend_pairs_rescue_mapq_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, rescue_params=None,
+                                         quality_params=None, want_ops=True, allow_out_of_alphabet=False):
+    """bg_seed_extend_pairs_rescue_mapq_batch, host buffers: seed_extend_pairs_rescue_arrays plus a mapping quality per mate, the
+    mates of rescued pairs included.  Returns (hits, strand, pairs, rescued, multi: MULTI_HIT_DTYPE[2n], ops)."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    rescue_params = rescue_params or RescueParams()
+    quality_params = quality_params or PairQualityParams()
+    rd = _lib.as_u8(reads)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    if n % 2:
+        raise ValueError("seed_extend_pairs_rescue_mapq_arrays: an odd number of reads")
+    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
+    strand = np.zeros(max(n, 1), dtype=np.uint8)
+    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
+    rescued = np.zeros(max(n // 2, 1), dtype=np.uint8)
+    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
+    # a reported hit has at most read + window operations; a rescue window is up to max_span bytes
+    cap = int(off[-1] + (max(int(np.diff(off).max(initial=0)) + 2 * params.pad, pair_params.max_span) + 4) * n) + 8 if want_ops else 0
+    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
+    used = C.c_uint64(0)
+    sc, pc, pp, rp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c(), quality_params.to_c()
+    rc = _lib.lib().bg_seed_extend_pairs_rescue_mapq_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), C.byref(qp), n // 2,
+                                                           rd.ctypes.data, off.ctypes.data, hits.ctypes.data, strand.ctypes.data,
+                                                           pairs.ctypes.data, rescued.ctypes.data, multi.ctypes.data,
+                                                           ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    if not (rc == -7 and allow_out_of_alphabet):
+        _lib.check(rc, "bg_seed_extend_pairs_rescue_mapq_batch")
+    return hits, strand[:n], pairs[:n // 2], rescued[:n // 2], multi[:n], (ops[:used.value] if want_ops else None)
+
+
+def seed_extend_pairs_rescue_mapq_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_rescued, d_multi,
+                                      d_strand=0, d_ops=0, ops_stride=0, params=None, pair_params=None, rescue_params=None,
+                                      quality_params=None, stream=0, totals=None):
+    """bg_seed_extend_pairs_rescue_mapq_batch_dev (pointers are ints; as seed_extend_pairs_rescue_dev, plus d_multi: 2 n_pairs
+    bg_multi_hit_t, which bg_sam_emit_batch_dev takes as its d_multi together with SAM_PAIRED); `totals` as
+    seed_extend_pairs_rescue_dev."""
+    params = params or SeedParams()
+    pair_params = pair_params or PairParams()
+    rescue_params = rescue_params or RescueParams()
+    quality_params = quality_params or PairQualityParams()
+    sc, pc, pp, rp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c(), quality_params.to_c()
+    _lib.check(_lib.lib().bg_seed_extend_pairs_rescue_mapq_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), C.byref(qp),
+                                                                     n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand or None,
+                                                                     d_pairs or None, d_rescued or None, d_multi or None, d_ops or None,
+                                                                     ops_stride, totals.ctypes.data if totals is not None else None,
+                                                                     stream),
+               "bg_seed_extend_pairs_rescue_mapq_batch_dev")
+
+
 def seed_extend_multi_arrays(fm, scoring, reads, read_off, params=None, multi_params=None, strands=_lib.STRAND_BOTH, want_ops=True,
                              allow_out_of_alphabet=False):
     """bg_seed_extend_multi_batch, host buffers.  With K = multi_params.max_hits, returns (hits: SEED_HIT_DTYPE[n, K], strand:

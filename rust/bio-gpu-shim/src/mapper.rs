@@ -2,7 +2,8 @@
 //! `backward_search`, `Interval::occ` and `Aligner::semiglobal` (src/lib.rs:129-165, benches/fmindex.rs:20-38), on the
 //! forward strand or on both (`bg_seed_extend_strands_batch`: the `dna::revcomp` of each read as well), or as read pairs
 //! (`bg_seed_extend_pairs_batch`: interleaved mates, the best proper FR pair where there is one), or with runner-up loci and a
-//! MAPQ per read (`bg_seed_extend_multi_batch`), or as read pairs with a MAPQ per mate (`bg_seed_extend_pairs_mapq_batch`).
+//! MAPQ per read (`bg_seed_extend_multi_batch`), or as read pairs with a MAPQ per mate (`bg_seed_extend_pairs_mapq_batch`; with mate
+//! rescue as well: `bg_seed_extend_pairs_rescue_mapq_batch`).
 use crate::fmindex::GpuFMIndex;
 use crate::pairwise::{scoring_to_c, tabulate};
 use crate::{concat, strerror, sys, to_alignment, zero_alignment};
@@ -32,7 +33,7 @@ pub struct PairHit {
     pub rescued: u8,
 }
 
-/// `seed_extend_batch_pairs_mapq`: how unique each mate's placement is, mate 1 and mate 2
+/// `seed_extend_batch_pairs_mapq` / `seed_extend_batch_pairs_rescue_mapq`: how unique each mate's placement is, mate 1 and mate 2
 pub struct PairQuality {
     /// judged against the pair where it is proper (0: another placement of the mate serves the pair as well; `mapq_cap`: the mate has
     /// no other placement), as `seed_extend_batch_multi` judges a single read where it is not
@@ -177,6 +178,56 @@ impl GpuFMIndex<'_> {
                 let (a, b) = (&multi[2 * p], &multi[2 * p + 1]);
                 (PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper,
                            rescued: 0 },
+                 PairQuality { mapq: [a.mapq, b.mapq], sub_score: [a.sub_score, b.sub_score], n_loci: [a.n_loci, b.n_loci] })
+            })
+            .collect()
+    }
+
+    /// Mate rescue with a mapping quality per mate (`bg_seed_extend_pairs_rescue_mapq_batch`): what `seed_extend_batch_pairs_rescue`
+    /// returns, and for every pair a `PairQuality`; the mates of a rescued pair are judged against the pair's other accepted rescues
+    /// and the mates' seeded candidates elsewhere.  `rescue_min_score` discards a rescued alignment, `min_score` an alternative.
+    pub fn seed_extend_batch_pairs_rescue_mapq<F: MatchFunc>(&self, scoring: &Scoring<F>, reads: &[&[u8]], max_anchors: u32,
+                                                             rescue_min_score: i32, min_score: i32, mapq_cap: u32, min_span: u32,
+                                                             max_span: u32, pen_unpaired: i32, seed_len: u32, stride: u32, max_occ: u32,
+                                                             pad: u32)
+                                                             -> Vec<(PairHit, PairQuality)> {
+        assert!(reads.len() % 2 == 0, "mates come in pairs: an odd number of reads");
+        assert!(mapq_cap <= 254, "mapq_cap outside 0 ..= 254");
+        let table = tabulate(scoring);
+        let sc = scoring_to_c(scoring, &table);
+        let prm = sys::bg_seed_params_t { seed_len, stride, max_occ, pad };
+        let pp = sys::bg_pair_params_t { min_span, max_span, pen_unpaired };
+        let rp = sys::bg_rescue_params_t { max_anchors, min_score: rescue_min_score };
+        let qp = sys::bg_pairq_params_t { min_score, mapq_cap };
+        let (buf, off) = concat(reads);
+        let n_pairs = reads.len() / 2;
+        let zero = sys::bg_seed_hit_t { aln: zero_alignment(), window_start: 0, ref_start: 0, ref_end: 0, n_candidates: 0, n_seed_hits: 0 };
+        let mut hits = vec![zero; reads.len()];
+        let mut strand = vec![0u8; reads.len()];
+        let mut pairs = vec![sys::bg_pair_hit_t { span: 0, n_proper: 0, proper: 0, reserved: [0; 3] }; n_pairs.max(1)];
+        let mut rescued = vec![0u8; n_pairs.max(1)];
+        let mut multi = vec![sys::bg_multi_hit_t { sub_score: 0, n_loci: 0, n_reported: 0, mapq: 0, reserved: [0; 6] }; reads.len().max(1)];
+        // (a rescued hit has up to read + max_span operations)
+        let mut ops = vec![0u8; 2 * buf.len() + (2 * pad as usize + 4 + max_span as usize) * reads.len() + 8];
+        let mut used = 0u64;
+        let rc = unsafe {
+            sys::bg_seed_extend_pairs_rescue_mapq_batch(self.h, &sc, &prm, &pp, &rp, &qp, n_pairs as u64, buf.as_ptr(), off.as_ptr(),
+                                                        hits.as_mut_ptr(), strand.as_mut_ptr(), pairs.as_mut_ptr(), rescued.as_mut_ptr(),
+                                                        multi.as_mut_ptr(), ops.as_mut_ptr(), ops.len() as u64, &mut used)
+        };
+        assert!(rc == 0, "{}", strerror(rc));
+        let hit = |r: usize| Hit {
+            alignment: if hits[r].aln.score == sys::BG_MIN_SCORE { None } else { Some(to_alignment(&hits[r].aln, &ops)) },
+            ref_start: hits[r].ref_start as usize,
+            ref_end: hits[r].ref_end as usize,
+            n_candidates: hits[r].n_candidates,
+            reverse: strand[r] as i32 == sys::BG_HIT_REVERSE,
+        };
+        (0..n_pairs)
+            .map(|p| {
+                let (a, b) = (&multi[2 * p], &multi[2 * p + 1]);
+                (PairHit { mates: [hit(2 * p), hit(2 * p + 1)], proper: pairs[p].proper != 0, span: pairs[p].span, n_proper: pairs[p].n_proper,
+                           rescued: rescued[p] },
                  PairQuality { mapq: [a.mapq, b.mapq], sub_score: [a.sub_score, b.sub_score], n_loci: [a.n_loci, b.n_loci] })
             })
             .collect()
