@@ -335,52 +335,6 @@ void fm_build_step2(bg_fm* fm, hipStream_t st);
 int bg_fm_search_seeds_dev(bg_fm* fm, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t S,
                            uint32_t stride, uint32_t seed_len, uint8_t* d_tag, uint64_t* d_lower, uint64_t* d_upper,
                            uint32_t* d_matched_len, hipStream_t st);
-// seed_pairs.hip: S7 of bg_seed_extend_pairs_batch_dev over one pass (n_pairs pairs from caller read r0 on), on the pass
-// scratch of seed_extend.hip (candidate offsets of the 4 n_pairs virtual reads, their alignments, operations, windows).
-// max_cand bounds the candidates of one virtual read.
-int bg_seed_pairs_launch(const bg_pair_params_t* pp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff, const uint32_t* d_n_hits,
-                         const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits,
-                         uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint32_t max_cand, hipStream_t st);
-// seed_pairq.hip: S7 of bg_seed_extend_pairs_mapq_batch_dev over one pass: what bg_seed_pairs_launch writes, plus records
-// r0 + 2p, r0 + 2p + 1 of d_multi for the mates of pair p.
-int bg_seed_pairq_launch(const bg_pair_params_t* pp, const bg_pairq_params_t* qp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff,
-                         const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
-                         bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_pair_hit_t* d_pairs,
-                         bg_multi_hit_t* d_multi, uint32_t max_cand, hipStream_t st);
-// seed_rescue.hip: stages R1, R2, R4 of bg_seed_extend_pairs_rescue_batch_dev over one pass, on the same pass scratch (d_voff: the
-// offsets of the pass's 4 n_pairs virtual reads).  R1 answers every pair as bg_seed_pairs_launch does and plans the rescue
-// alignments (d_plan: bg_seed_rescue_plan_bytes(n_pairs) bytes; per pair the mates' own score sum and the counts of rescue
-// alignments / x bytes / y bytes); R2 gathers their (x, window) pairs at the scanned offsets; R4 rewrites the rescued pairs.
-size_t bg_seed_rescue_plan_bytes(uint64_t n_pairs);
-int bg_seed_rescue_plan_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_text, uint64_t n_pairs, uint64_t r0,
-                               const uint64_t* d_voff, const uint64_t* d_coff, const uint32_t* d_n_hits, const bg_alignment_t* d_aln,
-                               const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride,
-                               uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_rescued, void* d_plan, int64_t* d_own_sum,
-                               uint32_t* d_n_res, uint32_t* d_x_bytes, uint32_t* d_y_bytes, uint32_t max_cand, hipStream_t st);
-int bg_seed_rescue_gather_launch(uint64_t n_pairs, const uint8_t* d_vreads, const uint64_t* d_voff, const uint8_t* d_text, const void* d_plan,
-                                 const uint64_t* d_roff, const uint64_t* d_xoff, const uint64_t* d_yoff, uint8_t* d_x, uint64_t* d_x_off,
-                                 uint8_t* d_y, uint64_t* d_y_off, hipStream_t st);
-int bg_seed_rescue_pick_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff,
-                               const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
-                               const void* d_plan, const int64_t* d_own_sum, const uint64_t* d_roff, const bg_alignment_t* d_r_aln,
-                               const uint8_t* d_r_ops, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand,
-                               bg_pair_hit_t* d_pairs, uint8_t* d_rescued, hipStream_t st);
-// *d_count += the pairs of the call with a non-zero rescued byte (totals[3])
-int bg_seed_rescue_count_launch(uint64_t n_pairs, const uint8_t* d_rescued, uint64_t* d_count, hipStream_t st);
-// seed_rescueq.hip: the stage after R4 of bg_seed_extend_pairs_rescue_mapq_batch_dev over one pass: records r0 + 2p, r0 + 2p + 1 of
-// d_multi for the mates of every pair p of the pass with a non-zero rescued byte, from the plan and the rescue alignments that
-// R1-R4 left in the pass scratch.  The other pairs' records are written before R1 (bg_seed_pairq_launch) and stay.
-int bg_seed_rescueq_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs, uint64_t r0,
-                           const uint64_t* d_coff, const bg_alignment_t* d_aln, const uint64_t* d_w_lo, const void* d_plan,
-                           const uint64_t* d_roff, const bg_alignment_t* d_r_aln, const uint8_t* d_rescued, bg_multi_hit_t* d_multi,
-                           hipStream_t st);
-// seed_multi.hip: S7 of bg_seed_extend_multi_batch_dev over one pass (n_reads reads from caller read r0 on, G virtual reads
-// each; strand1: the strand of every hit when G = 1), on the same pass scratch.  Read r0 + r owns slots K (r0 + r) ..
-// K (r0 + r) + K - 1 of d_hits / d_strand / d_ops and record r0 + r of d_multi.  max_cand bounds the candidates of one
-// virtual read.
-int bg_seed_multi_launch(const bg_multi_params_t* mp, uint32_t G, uint8_t strand1, uint64_t n_reads, uint64_t r0, const uint64_t* d_coff,
-                         const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
-                         bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand, bg_multi_hit_t* d_multi,
-                         uint32_t max_cand, hipStream_t st);
+// (the seed-and-extend stages and their pass view: seed_pass.h)
 
 #endif

@@ -10,33 +10,61 @@
 // best-hit reduction that hands back one alignment (with its operations) per read.  Definition of the
 // composition: include/biogpu.h (the tests hold a CPU statement of the same thing).
 //
-// Per batch of reads (S = seed slots per read; with both strands (bg_seed_extend_strands_batch[_dev]) the stages run on
-// "virtual reads", each read followed by its revcomp, and S7 picks the better strand of each read):
-//   S0 strands          one wavefront per read: read + revcomp -> scratch (stranded call only)
+// Every entry point describes its call in one SeedCall (absent outputs and mode parameters are null) and hands it to se_run,
+// which cuts it into passes; a pass is the four functions below, in this order, on the named buffers of bg_seed_scratch.
+// Per pass (S = seed slots per read; the stages run on "virtual reads": each read as it is, or its revcomp, or both, the
+// read followed by its revcomp):
+//   se_candidates
+//   S0 strands          one wavefront per read: read + revcomp -> scratch (virtual reads other than the reads themselves)
 //   S1 K5<SEEDS>        n_reads * S backward searches                                  -> tag, lower, upper
 //   S2 votes            cnt[q] = interval size if Complete and 1 <= size <= max_occ     -> scan -> hit offsets
+//      (the total and the flag word are the FIRST host round trip)
 //   S3 K6               Interval::occ of every voting interval                          -> text positions
 //   S4 propose          one wavefront per read: s = pos - seed offset, sort, dedup      -> per-read candidate lists
-//      (scan of the per-read candidate / x-byte / y-byte counts; the three totals are the ONE host round trip)
+//      (scan of the per-read candidate / x-byte / y-byte counts; the three totals are the SECOND host round trip)
+//   se_align
 //   S5 gather           (read, text window) pairs, offsets                              -> x, x_off, y, y_off
 //   S6 align            Aligner::semiglobal on every candidate (bg_align_batch_dev)      -> records + operations
+//   se_reduce           on the pass view of seed_pass.h (SeedPass, SeedOut), by mode:
 //   S7 best             per read: highest score, smallest start among equals           -> bg_seed_hit_t + its ops
-//      (pair mode, bg_seed_extend_pairs_batch[_dev]: per pair of interleaved mates, the best proper FR combination of their
-//       candidates or each mate's own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t;
-//       pairs-mapq mode, bg_seed_extend_pairs_mapq_batch[_dev]: pair mode plus a bg_multi_hit_t per mate, its MAPQ judged against the
-//       pair (seed_pairq.hip);
-//       multi mode, bg_seed_extend_multi_batch[_dev]: per read up to K loci that do not touch, in rank order -> K bg_seed_hit_t +
-//       their ops, bg_multi_hit_t with the runner-up's score and MAPQ;
-//       rescue mode, bg_seed_extend_pairs_rescue_batch[_dev]: pair mode, then for the pairs without a proper combination the stages
-//       R1-R4 of seed_rescue.hip: anchors -> one more batch of semiglobal alignments in their insert windows -> rescued pairs)
+//      pair mode        per pair of interleaved mates the best proper FR combination of their candidates, or each mate's
+//                       own best -> two bg_seed_hit_t + their ops, bg_pair_hit_t (seed_pairs.hip)
+//      pairs-mapq mode  pair mode plus a bg_multi_hit_t per mate, its MAPQ judged against the pair (seed_pairq.hip)
+//      multi mode       per read up to K loci that do not touch, in rank order -> K bg_seed_hit_t + their ops, bg_multi_hit_t
+//                       with the runner-up's score and MAPQ (seed_multi.hip)
+//   se_rescue           rescue modes, instead of se_reduce: (pairs-mapq records of every pair,) R1 plan, one more host
+//                       round trip, R2 gather, R3 align, R4 pick (seed_rescue.hip), (records of the rescued pairs,
+//                       seed_rescueq.hip)
+// The rules the reduction kernels share are device functions in seed_rule.h, seed_pair_rule.h and seed_rescue_rule.h.
 #include <algorithm>
 
-#include "fm_kernels.h"
+#include "seed_rule.h"
 
+// The pass scratch: one growing device buffer per name (bg_reserve), kept by the context between calls.
+enum SeedBuf {
+    kTag, kLower, kUpper,  // S1: per seed slot
+    kVotes,                // S1 writes the seeds' matched lengths here (not read), S2 the votes over them
+    kHitOff,               // S2: scan of the votes
+    kScanPartials,         // bg_scan_u32's own scratch, every scan of a pass
+    kFlags,                // 64 bytes: bit 0 a seed out of the alphabet, bit 1 a read longer than max_read_len
+    kPos,                  // S3: text positions; S4 leaves each read's candidate starts at the front of its slice
+    kPerReadCounts,        // S4: n_cand | n_hits | x_bytes | y_bytes per virtual read
+    kPerReadOffsets,       // their scans: coff | xoff | yoff
+    kX, kY, kCandOff,      // S5: the aligner's input; kCandOff: x_off | y_off per candidate
+    kWLo,                  // S5: the window's first text offset per candidate
+    kAln, kCandOps,        // S6: the candidates' alignments and operations
+    kVreads,               // S0: voff | the virtual reads' bytes
+    kRescuePlan,           // R1: plan entries
+    kPerPairCounts,        // R1: own_sum | n_res | x_bytes | y_bytes per pair
+    kPerPairOffsets,       // their scans: roff | xoff | yoff
+    kRescueX, kRescueY, kRescueOff, kRescueAln, kRescueOps,  // R2, R3: as kX .. kCandOps, for the rescue alignments
+    kRescuedCount,         // 64 bytes: the call's rescued pairs (totals[3])
+    kSeedBufs
+};
 struct bg_seed_scratch {
-    void* p[24] = {};  // 16 .. 23: the rescue stages' plan, counts, offsets, pairs, records and operations
-    size_t cap[24] = {};
-    uint64_t* h_tot = nullptr;  // pinned: totals read back between S4 and S5 (and, rescue call, between R1 and R2)
+    void* p[kSeedBufs] = {};
+    size_t cap[kSeedBufs] = {};
+    uint64_t* h_tot = nullptr;  // pinned: totals read back in the host round trips of a pass
 };
 void bg_seed_scratch_free(bg_seed_scratch* s) {
     if (!s) return;
@@ -47,7 +75,9 @@ void bg_seed_scratch_free(bg_seed_scratch* s) {
 
 namespace {
 
-constexpr uint32_t kMaxProposals = 1024;  // seed slots x max_occ per read (sorted in LDS by one wavefront)
+using namespace bgseed;
+
+constexpr uint32_t kMaxProposals = kMaxCand;  // seed slots x max_occ per read (sorted in LDS by one wavefront)
 // proposals are sorted as uint32 on an index with 32-bit positions and as uint64 on one with 64-bit positions (round 6:
 // the kernels below are templates over that type; ~P(0) marks a dropped proposal)
 struct SeedPrm {
@@ -299,60 +329,21 @@ __global__ __launch_bounds__(256) void se_strands_kernel(uint64_t nr, const uint
     revcomp_wave(s_comp, reads + ro, vreads + vo + (G - 1) * L, L, lane);
 }
 
-// S7: 16 lanes per read: best candidate (highest score, first = smallest start among equals), record + operations
-// `hits` / `ops` are the caller's whole arrays, `r0` the first read of this pass: read r0 + r of the call owns
-// ops[(r0 + r) * ops_stride, (r0 + r + 1) * ops_stride) and its ops_off is relative to the caller's `ops`.
-// Read r's candidates are those of its G virtual reads, coff[G r] .. coff[G r + G): with G = 2 the forward strand's come
-// first, so the same key makes it win a tie.  `strand` (optional): BG_HIT_* of the winner; with G = 1 every winner is on
-// strand `strand1`.
+// S7: 16 lanes per read: best candidate (highest score, first = smallest start among equals), record + operations.
+// Read r0 + r of the call owns slot r0 + r.  Read r's candidates are those of its G virtual reads, coff[G r] .. coff[G r + G):
+// with G = 2 the forward strand's come first, so the same key makes it win a tie; with G = 1 every winner is on strand `strand1`.
 template <int G>
-__global__ __launch_bounds__(256) void se_best_kernel(uint64_t n_reads, uint64_t r0, const uint64_t* __restrict__ coff,
-                                                      const uint32_t* __restrict__ n_hits,
-                                                      const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ c_ops,
-                                                      const uint64_t* __restrict__ w_lo, bg_seed_hit_t* __restrict__ hits,
-                                                      uint8_t* __restrict__ ops, uint64_t ops_stride, uint8_t* __restrict__ strand,
-                                                      uint8_t strand1) {
+__global__ __launch_bounds__(256) void se_best_kernel(SeedPass P, SeedOut O, uint8_t strand1) {
     const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t l16 = threadIdx.x & 15;
-    if (r >= n_reads) return;  // uniform per group of 16
-    const uint64_t c0 = coff[G * r];
-    const uint32_t nc = (uint32_t)(coff[G * r + G] - c0);
-    // key: score (biased to unsigned) in the high word, ~candidate index in the low one: max = best score, first wins
+    if (r >= P.n) return;  // uniform per group of 16
+    const uint64_t c0 = P.coff[G * r];
+    const uint32_t nc = (uint32_t)(P.coff[G * r + G] - c0);
     uint64_t best = 0;
-    for (uint32_t c = l16; c < nc; c += 16) {
-        const uint32_t sc = (uint32_t)aln[c0 + c].score ^ 0x80000000u;
-        const uint64_t key = ((uint64_t)sc << 32) | (uint32_t)~c;
-        best = max(best, key);
-    }
-#pragma unroll
-    for (int o = 8; o; o >>= 1) {
-        const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(best >> 32), o, 16) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)best, o, 16);
-        best = max(best, other);
-    }
-    bg_seed_hit_t h;
-    memset(&h, 0, sizeof(h));
-    h.aln.score = BG_MIN_SCORE;
-    h.window_start = h.ref_start = h.ref_end = ~0ull;
-    h.n_candidates = nc;
-    h.n_seed_hits = G == 2 ? n_hits[2 * r] + n_hits[2 * r + 1] : n_hits[r];
-    h.aln.ops_off = (r0 + r + 1) * ops_stride;
-    uint8_t won = BG_HIT_NONE;
-    if (nc) {
-        const uint32_t c = ~(uint32_t)best;
-        won = G == 2 ? (c >= coff[2 * r + 1] - c0 ? BG_HIT_REVERSE : BG_HIT_FORWARD) : strand1;
-        const bg_alignment_t a = aln[c0 + c];
-        h.aln = a;
-        h.aln.ops_off = (r0 + r + 1) * ops_stride - a.n_ops;
-        h.window_start = w_lo[c0 + c];
-        h.ref_start = w_lo[c0 + c] + a.ystart;
-        h.ref_end = w_lo[c0 + c] + a.yend;
-        if (ops && c_ops)
-            for (uint32_t i = l16; i < a.n_ops; i += 16) ops[h.aln.ops_off + i] = c_ops[a.ops_off + i];
-    }
-    if (l16 == 0) {
-        hits[r0 + r] = h;
-        if (strand) strand[r0 + r] = won;
-    }
+    for (uint32_t c = l16; c < nc; c += 16) best = max(best, own_key(P.aln[c0 + c].score, c));
+    const uint32_t c = key_cand(max16(best));
+    const uint8_t won = !nc ? BG_HIT_NONE : G == 2 ? (c >= P.coff[2 * r + 1] - c0 ? BG_HIT_REVERSE : BG_HIT_FORWARD) : strand1;
+    write_cand(P, O, P.r0 + r, l16, c0 + c, won, nc, G == 2 ? P.n_hits[2 * r] + P.n_hits[2 * r + 1] : P.n_hits[r]);
 }
 
 }  // namespace
@@ -383,252 +374,359 @@ extern "C" int bg_fm_set_text_dev(bg_fm* fm, const uint8_t* d_text, uint64_t n) 
 
 namespace {
 
-// The passes of bg_seed_extend_batch_dev over "virtual reads", G of them per read of the caller.  strands = 0: the caller's
-// reads as they are, G = 1, no strand array (bg_seed_extend_batch_dev).  BG_STRAND_FORWARD: the same, with the strand array.
-// BG_STRAND_REVERSE: G = 1 on the revcomps, BG_STRAND_BOTH: G = 2 on read and revcomp, materialised per pass by
-// se_strands_kernel.  Stages S1-S6 run unchanged on the virtual reads; S7 picks each caller read's best over its G.
-// Pair mode (`pair` set, strands = BG_STRAND_BOTH, n_reads = 2 n_pairs interleaved mates): passes hold whole pairs and
-// se_pair_kernel replaces S7, writing d_pairs as well.
-// Multi mode (`multi` set): se_multi_kernel replaces S7; d_hits / d_strand / d_ops hold multi->max_hits slots per read, d_multi one
-// record per read.
-// Rescue mode (`rescue` set, pair mode): R1-R4 of seed_rescue.hip replace S7; d_rescued one byte per pair, totals 4 entries.
-// Pairs-mapq mode (`pairq` set, pair mode): se_pairq_kernel replaces S7, writing d_pairs and one d_multi record per mate.
-// Both (`rescue` and `pairq` set): se_pairq_kernel writes every pair's records before R1, which rewrites the same hits; after R4
-// se_rescue_mapq_kernel (seed_rescueq.hip) rewrites the records of the rescued pairs.
-int se_run(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm_in, uint32_t strands, uint64_t n_reads,
-           const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand,
-           uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream, const bg_pair_params_t* pair = nullptr,
-           bg_pair_hit_t* d_pairs = nullptr, const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* d_multi = nullptr,
-           const bg_rescue_params_t* rescue = nullptr, uint8_t* d_rescued = nullptr, const bg_pairq_params_t* pairq = nullptr) {
-    if (!fm || !sc || !prm_in || (n_reads && (!d_read_off || !d_hits))) return BG_ERR_INVALID_ARG;
-    if (!fm->d_text || fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
-    if (prm_in->seed_len == 0 || prm_in->stride == 0 || prm_in->max_occ == 0) return BG_ERR_INVALID_ARG;
-    if (max_read_len > 65535 || prm_in->pad > 65535) return BG_ERR_TOO_LARGE;
-    if (rescue && pair->max_span > 65535) return BG_ERR_TOO_LARGE;
-    const uint32_t win_max = max_read_len + 2 * prm_in->pad;
-    const uint32_t rwin_max = rescue ? pair->max_span : 0;  // the longest rescue window
-    if (d_ops && ops_stride < (uint64_t)max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
-    if (totals) totals[0] = totals[1] = 0;
-    if (totals && rescue) totals[2] = totals[3] = 0;
-    if (n_reads == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
-    hipStream_t st = (hipStream_t)stream;
+// One call of any flavour: absent outputs and mode parameters are null.
+//   strands      0: the caller's reads as they are, no strand array; BG_STRAND_FORWARD: the same, with the strand array;
+//                BG_STRAND_REVERSE: the revcomps; BG_STRAND_BOTH: read and revcomp (G = 2 virtual reads per read)
+//   pair         pair mode (strands = BG_STRAND_BOTH, n_reads = 2 n_pairs interleaved mates): passes hold whole pairs; `pairs`
+//   pairq        with pair: one `multi` record per mate
+//   rescue       with pair: `rescued` one byte per pair, `totals` 4 entries (otherwise 2)
+//   multi_prm    multi mode: hits / strand / ops hold max_hits slots per read, `multi` one record per read
+struct SeedCall {
+    bg_fm* fm = nullptr;
+    const bg_scoring_t* sc = nullptr;
+    const bg_seed_params_t* prm = nullptr;
+    uint32_t strands = 0;
+    uint64_t n_reads = 0;
+    const uint8_t* reads = nullptr;
+    const uint64_t* read_off = nullptr;
+    uint32_t max_read_len = 0;
+    bg_seed_hit_t* hits = nullptr;
+    uint8_t* strand = nullptr;
+    uint8_t* ops = nullptr;
+    uint64_t ops_stride = 0;
+    bg_pair_hit_t* pairs = nullptr;
+    bg_multi_hit_t* multi = nullptr;
+    uint8_t* rescued = nullptr;
+    uint64_t* totals = nullptr;
+    const bg_pair_params_t* pair = nullptr;
+    const bg_multi_params_t* multi_prm = nullptr;
+    const bg_rescue_params_t* rescue = nullptr;
+    const bg_pairq_params_t* pairq = nullptr;
+    void* stream = nullptr;
+};
+
+// consecutive arrays out of one scratch buffer
+struct Carve {
+    uint8_t* at;
+    template <typename T>
+    T* take(size_t n) {
+        T* q = (T*)at;
+        at += n * sizeof(T);
+        return q;
+    }
+};
+
+// what a call's passes share
+struct SeedRun {
+    const SeedCall& call;
+    bg_seed_scratch& W;
+    bg_ctx* ctx = nullptr;
+    hipStream_t st = nullptr;
+    SeedPrm prm = {};
+    uint32_t G = 1;         // virtual reads per read
+    bool virt = false;      // the virtual reads are materialised (S0)
+    uint32_t win_max = 0;   // the longest candidate window
+    uint32_t rwin_max = 0;  // the longest rescue window
+    SeedOut out = {};
+
+    int need(SeedBuf b, size_t bytes) { return bg_reserve(&W.p[b], &W.cap[b], std::max<size_t>(bytes, 64)); }
+    template <typename T>
+    T* buf(SeedBuf b) const {
+        return (T*)W.p[b];
+    }
+    uint8_t strand1() const { return call.strands == BG_STRAND_REVERSE ? BG_HIT_REVERSE : BG_HIT_FORWARD; }
+};
+
+// one pass: reads r0 .. r0 + nr of the call, and what its stages hand on
+struct SeedPassRun {
+    uint64_t r0, nr, nv, nq;  // caller reads, virtual reads, seed slots
+    const uint8_t* vreads;    // the virtual reads and their nv + 1 offsets
+    const uint64_t* roff;
+    uint64_t* hoff;           // S2
+    uint64_t* pos;            // S3, S4
+    uint32_t* n_hits;         // S4: per virtual read, and the scans of its other counts
+    SeedXYOff off;
+    uint64_t n_sa_rows, C, X, Y;  // the host round trips: suffix-array rows, candidates, their x and y bytes
+    SeedPass view;                // S5, S6: what the reduction reads
+    uint64_t n_rescue;            // R1: rescue alignments
+};
+
+// S0-S4: seeds -> votes -> text positions -> per-read candidate lists.  Two host round trips: the hit total with the flag word
+// (sizes the position array), then the candidate / x-byte / y-byte totals (size the aligner's input).
+int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
+    int rc;
+    const SeedCall& c = R.call;
+    const uint64_t nv = p.nv, nq = p.nq;
+    if ((rc = R.need(kTag, nq))) return rc;
+    if ((rc = R.need(kLower, nq * 8))) return rc;
+    if ((rc = R.need(kUpper, nq * 8))) return rc;
+    if ((rc = R.need(kVotes, nq * 4))) return rc;
+    if ((rc = R.need(kHitOff, (nq + 1) * 8))) return rc;
+    if ((rc = R.need(kScanPartials, 2 * (nq / 2048 + 2) * 8))) return rc;
+    if ((rc = R.need(kFlags, 64))) return rc;
+    uint8_t* d_tag = R.buf<uint8_t>(kTag);
+    uint64_t *d_lo = R.buf<uint64_t>(kLower), *d_hi = R.buf<uint64_t>(kUpper), *d_sums = R.buf<uint64_t>(kScanPartials);
+    uint32_t* d_votes = R.buf<uint32_t>(kVotes);
+    uint32_t* d_matched_len = d_votes;  // the search must write them somewhere; S2 overwrites them
+    uint32_t* d_flags = R.buf<uint32_t>(kFlags);
+    p.hoff = R.buf<uint64_t>(kHitOff);
+    BG_HIP(hipMemsetAsync(d_flags, 0, 8, R.st));
+    // ---- S0: the virtual reads and their offsets, relative to the pass's first read
+    p.vreads = c.reads;
+    p.roff = c.read_off + p.r0;
+    if (R.virt) {
+        const uint64_t cap = nv * (uint64_t)c.max_read_len;
+        if ((rc = R.need(kVreads, (nv + 1) * 8 + cap))) return rc;
+        Carve v{R.buf<uint8_t>(kVreads)};
+        uint64_t* d_voff = v.take<uint64_t>(nv + 1);
+        uint8_t* d_vreads = v.take<uint8_t>(cap);
+        const dim3 grid((unsigned)((p.nr + 3) / 4)), block(256);
+        if (R.G == 2)
+            se_strands_kernel<2><<<grid, block, 0, R.st>>>(p.nr, c.reads, p.roff, cap, d_vreads, d_voff, d_flags);
+        else
+            se_strands_kernel<1><<<grid, block, 0, R.st>>>(p.nr, c.reads, p.roff, cap, d_vreads, d_voff, d_flags);
+        BG_HIP(hipGetLastError());
+        p.vreads = d_vreads;
+        p.roff = d_voff;
+    }
+    // ---- S1/S2: seeds -> votes -> hit offsets
+    if (R.prm.S) {
+        if ((rc = bg_fm_search_seeds_dev(c.fm, nv, p.vreads, p.roff, R.prm.S, R.prm.stride, R.prm.seed_len, d_tag, d_lo, d_hi, d_matched_len,
+                                         R.st)))
+            return rc;
+        se_votes_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, R.st>>>(nq, d_tag, d_lo, d_hi, R.prm.max_occ, d_votes, d_flags);
+    } else {
+        BG_HIP(hipMemsetAsync(d_votes, 0, nq * 4, R.st));
+    }
+    if ((rc = bg_scan_u32(d_votes, nq, p.hoff, d_sums, R.st))) return rc;
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[0], p.hoff + nq, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[4], d_flags, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipStreamSynchronize(R.st));  // sizes the position array
+    p.n_sa_rows = R.W.h_tot[0];
+    if (R.W.h_tot[4] & 1) *any_panic = true;
+    if (R.W.h_tot[4] & 2) return BG_ERR_INVALID_ARG;  // a read longer than max_read_len (S0 kept within its scratch)
+    // ---- S3: Interval::occ of the voting intervals
+    if ((rc = R.need(kPos, p.n_sa_rows * 8))) return rc;
+    p.pos = R.buf<uint64_t>(kPos);
+    if (p.n_sa_rows && (rc = bg_interval_occ_batch_dev(c.fm, nq, d_lo, p.hoff, p.n_sa_rows, p.pos, R.st))) return rc;
+    // ---- S4: proposals -> sorted unique candidates per read, scans of the per-read counts
+    if ((rc = R.need(kPerReadCounts, 4 * nv * 4))) return rc;
+    if ((rc = R.need(kPerReadOffsets, 3 * (nv + 1) * 8))) return rc;
+    Carve counts{R.buf<uint8_t>(kPerReadCounts)}, offsets{R.buf<uint8_t>(kPerReadOffsets)};
+    uint32_t* d_nc = counts.take<uint32_t>(nv);
+    p.n_hits = counts.take<uint32_t>(nv);
+    uint32_t *d_xb = counts.take<uint32_t>(nv), *d_yb = counts.take<uint32_t>(nv);
+    uint64_t *d_coff = offsets.take<uint64_t>(nv + 1), *d_xoff = offsets.take<uint64_t>(nv + 1), *d_yoff = offsets.take<uint64_t>(nv + 1);
+    p.off = SeedXYOff{d_coff, d_xoff, d_yoff};
+    if (c.fm->wide)
+        se_propose_kernel<uint64_t><<<dim3((unsigned)nv), dim3(64), 0, R.st>>>(R.prm, nv, p.roff, p.hoff, p.pos, d_nc, p.n_hits, d_xb, d_yb);
+    else
+        se_propose_kernel<uint32_t><<<dim3((unsigned)nv), dim3(64), 0, R.st>>>(R.prm, nv, p.roff, p.hoff, p.pos, d_nc, p.n_hits, d_xb, d_yb);
+    BG_HIP(hipGetLastError());
+    if ((rc = bg_scan_u32(d_nc, nv, d_coff, d_sums, R.st))) return rc;
+    if ((rc = bg_scan_u32(d_xb, nv, d_xoff, d_sums, R.st))) return rc;
+    if ((rc = bg_scan_u32(d_yb, nv, d_yoff, d_sums, R.st))) return rc;
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[1], d_coff + nv, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[2], d_xoff + nv, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[3], d_yoff + nv, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipStreamSynchronize(R.st));  // sizes the candidate pairs
+    p.C = R.W.h_tot[1], p.X = R.W.h_tot[2], p.Y = R.W.h_tot[3];
+    return BG_OK;
+}
+
+// S5-S6: the (read, window) pairs of every candidate, and Aligner::semiglobal on them -> the pass view
+int se_align(SeedRun& R, SeedPassRun& p) {
+    int rc;
+    const SeedCall& c = R.call;
+    const uint64_t cstride = c.ops ? (uint64_t)c.max_read_len + R.win_max + 4 : 0;
+    if ((rc = R.need(kX, p.X))) return rc;
+    if ((rc = R.need(kY, p.Y))) return rc;
+    if ((rc = R.need(kCandOff, 2 * (p.C + 1) * 8))) return rc;
+    if ((rc = R.need(kWLo, p.C * 8))) return rc;
+    if ((rc = R.need(kAln, p.C * sizeof(bg_alignment_t)))) return rc;
+    if ((rc = R.need(kCandOps, p.C * cstride))) return rc;
+    Carve o{R.buf<uint8_t>(kCandOff)};
+    const SeedPairsXY xy{R.buf<uint8_t>(kX), o.take<uint64_t>(p.C + 1), R.buf<uint8_t>(kY), o.take<uint64_t>(p.C + 1)};
+    uint64_t* d_wlo = R.buf<uint64_t>(kWLo);
+    bg_alignment_t* d_aln = R.buf<bg_alignment_t>(kAln);
+    uint8_t* d_cops = c.ops ? R.buf<uint8_t>(kCandOps) : nullptr;
+    se_gather_kernel<<<dim3((unsigned)p.nv), dim3(64), 0, R.st>>>(R.prm, p.nv, p.vreads, p.roff, (const uint8_t*)c.fm->d_text, p.hoff, p.pos,
+                                                                  p.off.roff, p.off.xoff, p.off.yoff, xy.x, xy.x_off, xy.y, xy.y_off, d_wlo);
+    BG_HIP(hipGetLastError());
+    if (p.C && (rc = bg_align_batch_dev_hint(R.ctx, c.sc, BG_MODE_SEMIGLOBAL, p.C, xy.x, xy.x_off, xy.y, xy.y_off, c.max_read_len, R.win_max,
+                                             d_aln, d_cops, cstride, R.st, -1)))
+        return rc;
+    p.view = SeedPass{p.r0, c.pair ? p.nr / 2 : p.nr, p.off.roff, p.n_hits, d_aln, d_cops, d_wlo, p.roff};
+    return BG_OK;
+}
+
+// S7: one answer per read, per pair in the pair modes
+int se_reduce(SeedRun& R, SeedPassRun& p) {
+    const SeedCall& c = R.call;
+    if (c.pairq) return bg_seed_pairq_launch(p.view, R.out, c.pair, c.pairq, R.st);
+    if (c.pair) return bg_seed_pairs_launch(p.view, R.out, c.pair, R.st);
+    if (c.multi_prm) return bg_seed_multi_launch(p.view, R.out, c.multi_prm, R.G, R.strand1(), R.st);
+    const dim3 grid((unsigned)((p.nr * 16 + 255) / 256));
+    if (R.G == 2)
+        se_best_kernel<2><<<grid, dim3(256), 0, R.st>>>(p.view, R.out, 0);
+    else
+        se_best_kernel<1><<<grid, dim3(256), 0, R.st>>>(p.view, R.out, R.strand1());
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+// The rescue modes' reduction: R1-R4 of seed_rescue.hip.  With pairq, se_pairq_kernel writes every pair's records before R1,
+// which rewrites the same hits, and se_rescue_mapq_kernel rewrites the records of the rescued pairs after R4.  A pass without
+// a rescue alignment ends after R1's read-back, the one extra host round trip.
+int se_rescue(SeedRun& R, SeedPassRun& p) {
+    int rc;
+    const SeedCall& c = R.call;
+    const uint64_t np = p.view.n;
+    const uint64_t rstride = c.ops ? (uint64_t)c.max_read_len + R.rwin_max + 4 : 0;
+    if ((rc = R.need(kRescuePlan, bg_seed_rescue_plan_bytes(np)))) return rc;
+    if ((rc = R.need(kPerPairCounts, np * 8 + 3 * np * 4))) return rc;
+    if ((rc = R.need(kPerPairOffsets, 3 * (np + 1) * 8))) return rc;
+    Carve counts{R.buf<uint8_t>(kPerPairCounts)}, offsets{R.buf<uint8_t>(kPerPairOffsets)};
+    SeedRescuePlan plan;
+    plan.plan = R.buf<void>(kRescuePlan);
+    plan.own_sum = counts.take<int64_t>(np);
+    plan.n_res = counts.take<uint32_t>(np), plan.x_bytes = counts.take<uint32_t>(np), plan.y_bytes = counts.take<uint32_t>(np);
+    uint64_t *d_roff = offsets.take<uint64_t>(np + 1), *d_rxoff = offsets.take<uint64_t>(np + 1), *d_ryoff = offsets.take<uint64_t>(np + 1);
+    uint64_t* d_sums = R.buf<uint64_t>(kScanPartials);
+    if (c.pairq && (rc = bg_seed_pairq_launch(p.view, R.out, c.pair, c.pairq, R.st))) return rc;
+    // ---- R1: the paired call's answer for every pair + the rescue plan of those without a proper combination
+    if ((rc = bg_seed_rescue_plan_launch(p.view, R.out, c.pair, c.rescue, R.prm.n_text, plan, R.st))) return rc;
+    if ((rc = bg_scan_u32(plan.n_res, np, d_roff, d_sums, R.st))) return rc;
+    if ((rc = bg_scan_u32(plan.x_bytes, np, d_rxoff, d_sums, R.st))) return rc;
+    if ((rc = bg_scan_u32(plan.y_bytes, np, d_ryoff, d_sums, R.st))) return rc;
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[5], d_roff + np, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[6], d_rxoff + np, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[7], d_ryoff + np, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipStreamSynchronize(R.st));  // sizes the rescue pairs
+    const uint64_t RC = R.W.h_tot[5], RX = R.W.h_tot[6], RY = R.W.h_tot[7];
+    p.n_rescue = RC;
+    if (!RC) return BG_OK;
+    // ---- R2: the (other mate, insert window) pairs
+    if ((rc = R.need(kRescueX, RX))) return rc;
+    if ((rc = R.need(kRescueY, RY))) return rc;
+    if ((rc = R.need(kRescueOff, 2 * (RC + 1) * 8))) return rc;
+    if ((rc = R.need(kRescueAln, RC * sizeof(bg_alignment_t)))) return rc;
+    if ((rc = R.need(kRescueOps, RC * rstride))) return rc;
+    Carve o{R.buf<uint8_t>(kRescueOff)};
+    const SeedPairsXY xy{R.buf<uint8_t>(kRescueX), o.take<uint64_t>(RC + 1), R.buf<uint8_t>(kRescueY), o.take<uint64_t>(RC + 1)};
+    bg_alignment_t* d_raln = R.buf<bg_alignment_t>(kRescueAln);
+    uint8_t* d_rops = c.ops ? R.buf<uint8_t>(kRescueOps) : nullptr;
+    if ((rc = bg_seed_rescue_gather_launch(p.view, p.vreads, (const uint8_t*)c.fm->d_text, plan.plan, SeedXYOff{d_roff, d_rxoff, d_ryoff}, xy,
+                                           R.st)))
+        return rc;
+    // ---- R3: Aligner::semiglobal on every rescue pair
+    if ((rc = bg_align_batch_dev_hint(R.ctx, c.sc, BG_MODE_SEMIGLOBAL, RC, xy.x, xy.x_off, xy.y, xy.y_off, c.max_read_len, R.rwin_max, d_raln,
+                                      d_rops, rstride, R.st, -1)))
+        return rc;
+    const SeedRescueAln res{d_roff, d_raln, d_rops};
+    // ---- R4: the rescued pairs
+    if ((rc = bg_seed_rescue_pick_launch(p.view, R.out, c.pair, c.rescue, plan, res, R.st))) return rc;
+    // ---- the records of the rescued pairs (the plan and the rescue alignments are still live)
+    if (c.pairq && (rc = bg_seed_rescueq_launch(p.view, R.out, c.pair, c.rescue, c.pairq, plan.plan, res, R.st))) return rc;
+    return BG_OK;
+}
+
+// The call's checks, its passes, its totals.
+int se_run(const SeedCall& c) {
+    if (!c.fm || !c.sc || !c.prm || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
+    if (!c.fm->d_text || c.fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
+    if (c.prm->seed_len == 0 || c.prm->stride == 0 || c.prm->max_occ == 0) return BG_ERR_INVALID_ARG;
+    if (c.max_read_len > 65535 || c.prm->pad > 65535) return BG_ERR_TOO_LARGE;
+    if (c.rescue && c.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
+    const uint32_t win_max = c.max_read_len + 2 * c.prm->pad;
+    const uint32_t rwin_max = c.rescue ? c.pair->max_span : 0;
+    if (c.ops && c.ops_stride < (uint64_t)c.max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
+    if (c.totals) c.totals[0] = c.totals[1] = 0;
+    if (c.totals && c.rescue) c.totals[2] = c.totals[3] = 0;
+    if (c.n_reads == 0) return BG_OK;
+    bg_ctx* ctx = c.fm->ctx;
+    hipStream_t st = (hipStream_t)c.stream;
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);  // ctx->seed is one scratch set: calls on other streams wait for this one's last kernel
     SeedPrm prm;
-    prm.S = max_read_len >= prm_in->seed_len ? (max_read_len - prm_in->seed_len) / prm_in->stride + 1 : 0;
-    prm.stride = prm_in->stride;
-    prm.seed_len = prm_in->seed_len;
-    prm.max_occ = prm_in->max_occ;
-    prm.pad = prm_in->pad;
-    prm.n_text = fm->n_text;
+    prm.S = c.max_read_len >= c.prm->seed_len ? (c.max_read_len - c.prm->seed_len) / c.prm->stride + 1 : 0;
+    prm.stride = c.prm->stride;
+    prm.seed_len = c.prm->seed_len;
+    prm.max_occ = c.prm->max_occ;
+    prm.pad = c.prm->pad;
+    prm.n_text = c.fm->n_text;
     if (prm.S > 64 || (uint64_t)prm.S * prm.max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
     if (!ctx->seed) ctx->seed = new bg_seed_scratch();
     bg_seed_scratch& W = *ctx->seed;
     if (!W.h_tot) BG_HIP(hipHostMalloc((void**)&W.h_tot, 64, hipHostMallocDefault));
+    const uint32_t G = c.strands == BG_STRAND_BOTH ? 2 : 1;
+    SeedRun R{c, W};
+    R.ctx = ctx, R.st = st, R.prm = prm, R.G = G, R.win_max = win_max, R.rwin_max = rwin_max;
+    R.virt = c.strands == BG_STRAND_REVERSE || c.strands == BG_STRAND_BOTH;
+    R.out.hits = c.hits, R.out.ops = c.ops, R.out.ops_stride = c.ops_stride, R.out.strand = c.strand;
+    R.out.pairs = c.pairs, R.out.multi = c.multi, R.out.rescued = c.rescued;
     int rc;
-    auto need = [&](int i, size_t bytes) -> int { return bg_reserve(&W.p[i], &W.cap[i], std::max<size_t>(bytes, 64)); };
-
-    const uint32_t G = strands == BG_STRAND_BOTH ? 2 : 1;
-    const bool virt = strands == BG_STRAND_REVERSE || strands == BG_STRAND_BOTH;  // reads to materialise (S0)
     uint64_t done_hits = 0, done_cand = 0, done_rescue = 0;
     bool any_panic = false;
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
-    // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size — 1.25 M reads went as 2^20 + 0.2 M until
-    //  round 6: two host round trips and a set of under-filled launches for a sixth of the reads).  The option counts the
-    //  caller's reads; in pair mode it is rounded down to whole pairs (at least one), and so are the equal passes.
-    const uint64_t unit = pair ? 2 : 1, n_units = n_reads / unit;
+    // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size).  The option counts the caller's reads;
+    // in pair mode it is rounded down to whole pairs (at least one), and so are the equal passes.
+    const uint64_t unit = c.pair ? 2 : 1, n_units = c.n_reads / unit;
     const uint64_t chunk_cap = std::max<uint64_t>(ctx->seed_chunk_reads > 0 ? (uint64_t)ctx->seed_chunk_reads / unit : (1u << 21) / G / unit, 1);
     const uint64_t n_pass = (n_units + chunk_cap - 1) / chunk_cap;
     const uint64_t chunk = unit * (ctx->seed_chunk_reads > 0 ? chunk_cap : (n_units + n_pass - 1) / n_pass);
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += chunk) {
-        const uint64_t nr = std::min(chunk, n_reads - r0);
-        const uint64_t nv = G * nr;  // virtual reads of this pass
-        const uint64_t nq = nv * std::max<uint32_t>(prm.S, 1);
-        const uint8_t* vreads = d_reads;
-        const uint64_t* roff = d_read_off + r0;
-        // ---- S1/S2: seeds -> votes -> hit offsets
-        if ((rc = need(0, nq))) return rc;              // tag
-        if ((rc = need(1, nq * 8))) return rc;          // lower
-        if ((rc = need(2, nq * 8))) return rc;          // upper
-        if ((rc = need(3, nq * 4))) return rc;          // matched_len, then votes
-        if ((rc = need(4, (nq + 1) * 8))) return rc;    // hit offsets
-        if ((rc = need(5, 2 * (nq / 2048 + 2) * 8 + 64))) return rc;  // scan partials (+ the panic flag behind them)
-        BG_HIP(hipMemsetAsync((uint8_t*)W.p[5] + 2 * (nq / 2048 + 2) * 8, 0, 8, st));
-        uint8_t* d_tag = (uint8_t*)W.p[0];
-        uint64_t *d_lo = (uint64_t*)W.p[1], *d_hi = (uint64_t*)W.p[2], *d_hoff = (uint64_t*)W.p[4], *d_sums = (uint64_t*)W.p[5];
-        uint32_t* d_cnt = (uint32_t*)W.p[3];
-        uint32_t* d_flags = (uint32_t*)(d_sums + 2 * (nq / 2048 + 2));  // bit 0: a seed out of the alphabet, bit 1: a read > max_read_len
-        // ---- S0 (stranded call): the virtual reads and their offsets, relative to the pass's first read
-        if (virt) {
-            const uint64_t voff_bytes = (nv + 1) * 8, cap = nv * (uint64_t)max_read_len;
-            if ((rc = need(15, voff_bytes + cap))) return rc;
-            uint64_t* d_voff = (uint64_t*)W.p[15];
-            uint8_t* d_vreads = (uint8_t*)W.p[15] + voff_bytes;
-            const dim3 grid((unsigned)((nr + 3) / 4)), block(256);
-            if (G == 2)
-                se_strands_kernel<2><<<grid, block, 0, st>>>(nr, d_reads, roff, cap, d_vreads, d_voff, d_flags);
-            else
-                se_strands_kernel<1><<<grid, block, 0, st>>>(nr, d_reads, roff, cap, d_vreads, d_voff, d_flags);
-            BG_HIP(hipGetLastError());
-            vreads = d_vreads;
-            roff = d_voff;
-        }
-        if (prm.S) {
-            if ((rc = bg_fm_search_seeds_dev(fm, nv, vreads, roff, prm.S, prm.stride, prm.seed_len, d_tag, d_lo, d_hi, d_cnt, st))) return rc;
-            se_votes_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(nq, d_tag, d_lo, d_hi, prm.max_occ, d_cnt,
-                                                                                      d_flags);
-        } else {
-            BG_HIP(hipMemsetAsync(d_cnt, 0, nq * 4, st));
-        }
-        if ((rc = bg_scan_u32(d_cnt, nq, d_hoff, d_sums, st))) return rc;
-        BG_HIP(hipMemcpyAsync(&W.h_tot[0], d_hoff + nq, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(&W.h_tot[4], d_sums + 2 * (nq / 2048 + 2), 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));  // sizes the position array
-        const uint64_t n_hits = W.h_tot[0];
-        if (W.h_tot[4] & 1) any_panic = true;
-        if (W.h_tot[4] & 2) return BG_ERR_INVALID_ARG;  // a read longer than max_read_len (S0 kept within its scratch)
-        // ---- S3: Interval::occ of the voting intervals
-        if ((rc = need(6, n_hits * 8))) return rc;
-        uint64_t* d_pos = (uint64_t*)W.p[6];
-        if (n_hits && (rc = bg_interval_occ_batch_dev(fm, nq, d_lo, d_hoff, n_hits, d_pos, st))) return rc;
-        // ---- S4: proposals -> sorted unique candidates per read, scans of the per-read counts
-        if ((rc = need(7, 4 * nv * 4))) return rc;           // n_cand | n_hits | x_bytes | y_bytes
-        if ((rc = need(8, 3 * (nv + 1) * 8))) return rc;      // coff | xoff | yoff
-        uint32_t* d_nc = (uint32_t*)W.p[7];
-        uint32_t *d_nh = d_nc + nv, *d_xb = d_nh + nv, *d_yb = d_xb + nv;
-        uint64_t* d_coff = (uint64_t*)W.p[8];
-        uint64_t *d_xoff = d_coff + (nv + 1), *d_yoff = d_xoff + (nv + 1);
-        if (fm->wide)
-            se_propose_kernel<uint64_t><<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
-        else
-            se_propose_kernel<uint32_t><<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, roff, d_hoff, d_pos, d_nc, d_nh, d_xb, d_yb);
-        BG_HIP(hipGetLastError());
-        if ((rc = bg_scan_u32(d_nc, nv, d_coff, d_sums, st))) return rc;
-        if ((rc = bg_scan_u32(d_xb, nv, d_xoff, d_sums, st))) return rc;
-        if ((rc = bg_scan_u32(d_yb, nv, d_yoff, d_sums, st))) return rc;
-        BG_HIP(hipMemcpyAsync(&W.h_tot[1], d_coff + nv, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(&W.h_tot[2], d_xoff + nv, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(&W.h_tot[3], d_yoff + nv, 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));  // sizes the candidate pairs
-        const uint64_t C = W.h_tot[1], X = W.h_tot[2], Y = W.h_tot[3];
-        // ---- S5: the pairs
-        const uint64_t cstride = d_ops ? (uint64_t)max_read_len + win_max + 4 : 0;
-        if ((rc = need(9, X))) return rc;
-        if ((rc = need(10, Y))) return rc;
-        if ((rc = need(11, 2 * (C + 1) * 8))) return rc;
-        if ((rc = need(12, C * 8))) return rc;
-        if ((rc = need(13, C * sizeof(bg_alignment_t)))) return rc;
-        if ((rc = need(14, C * cstride))) return rc;
-        uint8_t *d_x = (uint8_t*)W.p[9], *d_y = (uint8_t*)W.p[10], *d_cops = d_ops ? (uint8_t*)W.p[14] : nullptr;
-        uint64_t* d_cxoff = (uint64_t*)W.p[11];
-        uint64_t* d_cyoff = d_cxoff + (C + 1);
-        uint64_t* d_wlo = (uint64_t*)W.p[12];
-        bg_alignment_t* d_aln = (bg_alignment_t*)W.p[13];
-        se_gather_kernel<<<dim3((unsigned)nv), dim3(64), 0, st>>>(prm, nv, vreads, roff, (const uint8_t*)fm->d_text, d_hoff, d_pos, d_coff,
-                                                                  d_xoff, d_yoff, d_x, d_cxoff, d_y, d_cyoff, d_wlo);
-        BG_HIP(hipGetLastError());
-        // ---- S6: Aligner::semiglobal on every candidate
-        if (C && (rc = bg_align_batch_dev_hint(ctx, sc, BG_MODE_SEMIGLOBAL, C, d_x, d_cxoff, d_y, d_cyoff, max_read_len, win_max, d_aln,
-                                               d_cops, cstride, st, -1)))
-            return rc;
-        // ---- S7: best hit per read (pair mode: per pair)
-        const dim3 best_grid((unsigned)((nr * 16 + 255) / 256));
-        if (rescue) {
-            // ---- R1: the paired call's answer for every pair + the rescue plan of those without a proper combination
-            const uint64_t np = nr / 2;
-            const uint64_t rstride = d_ops ? (uint64_t)max_read_len + rwin_max + 4 : 0;
-            if ((rc = need(16, bg_seed_rescue_plan_bytes(np)))) return rc;
-            if ((rc = need(17, np * 8 + 3 * np * 4))) return rc;       // own_sum | n_res | x_bytes | y_bytes
-            if ((rc = need(18, 3 * (np + 1) * 8))) return rc;          // roff | rxoff | ryoff
-            int64_t* d_own = (int64_t*)W.p[17];
-            uint32_t* d_rn = (uint32_t*)(d_own + np);
-            uint32_t *d_rxb = d_rn + np, *d_ryb = d_rxb + np;
-            uint64_t* d_roff = (uint64_t*)W.p[18];
-            uint64_t *d_rxoff = d_roff + (np + 1), *d_ryoff = d_rxoff + (np + 1);
-            // (rescue-mapq call: every pair's records first, as the pairs-mapq call writes them; a pass may end after R1)
-            if (pairq && (rc = bg_seed_pairq_launch(pair, pairq, np, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
-                                                    d_strand, d_pairs, d_multi, kMaxProposals, st)))
-                return rc;
-            if ((rc = bg_seed_rescue_plan_launch(pair, rescue, prm.n_text, np, r0, roff, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops,
-                                                 ops_stride, d_strand, d_pairs, d_rescued, W.p[16], d_own, d_rn, d_rxb, d_ryb, kMaxProposals,
-                                                 st)))
-                return rc;
-            if ((rc = bg_scan_u32(d_rn, np, d_roff, d_sums, st))) return rc;
-            if ((rc = bg_scan_u32(d_rxb, np, d_rxoff, d_sums, st))) return rc;
-            if ((rc = bg_scan_u32(d_ryb, np, d_ryoff, d_sums, st))) return rc;
-            BG_HIP(hipMemcpyAsync(&W.h_tot[5], d_roff + np, 8, hipMemcpyDeviceToHost, st));
-            BG_HIP(hipMemcpyAsync(&W.h_tot[6], d_rxoff + np, 8, hipMemcpyDeviceToHost, st));
-            BG_HIP(hipMemcpyAsync(&W.h_tot[7], d_ryoff + np, 8, hipMemcpyDeviceToHost, st));
-            BG_HIP(hipStreamSynchronize(st));  // sizes the rescue pairs: the one extra round trip of a pass
-            const uint64_t RC = W.h_tot[5], RX = W.h_tot[6], RY = W.h_tot[7];
-            if (RC) {
-                // ---- R2: the (other mate, insert window) pairs
-                if ((rc = need(19, RX))) return rc;
-                if ((rc = need(20, RY))) return rc;
-                if ((rc = need(21, 2 * (RC + 1) * 8))) return rc;
-                if ((rc = need(22, RC * sizeof(bg_alignment_t)))) return rc;
-                if ((rc = need(23, RC * rstride))) return rc;
-                uint64_t* d_rcxoff = (uint64_t*)W.p[21];
-                uint64_t* d_rcyoff = d_rcxoff + (RC + 1);
-                bg_alignment_t* d_raln = (bg_alignment_t*)W.p[22];
-                uint8_t* d_rops = d_ops ? (uint8_t*)W.p[23] : nullptr;
-                if ((rc = bg_seed_rescue_gather_launch(np, vreads, roff, (const uint8_t*)fm->d_text, W.p[16], d_roff, d_rxoff, d_ryoff,
-                                                       (uint8_t*)W.p[19], d_rcxoff, (uint8_t*)W.p[20], d_rcyoff, st)))
-                    return rc;
-                // ---- R3: Aligner::semiglobal on every rescue pair
-                if ((rc = bg_align_batch_dev_hint(ctx, sc, BG_MODE_SEMIGLOBAL, RC, (const uint8_t*)W.p[19], d_rcxoff, (const uint8_t*)W.p[20],
-                                                  d_rcyoff, max_read_len, rwin_max, d_raln, d_rops, rstride, st, -1)))
-                    return rc;
-                // ---- R4: the rescued pairs
-                if ((rc = bg_seed_rescue_pick_launch(pair, rescue, np, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, W.p[16], d_own, d_roff, d_raln,
-                                                     d_rops, d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued, st)))
-                    return rc;
-                // ---- the records of the rescued pairs (the plan and d_raln are still live)
-                if (pairq && (rc = bg_seed_rescueq_launch(pair, rescue, pairq, np, r0, d_coff, d_aln, d_wlo, W.p[16], d_roff, d_raln, d_rescued,
-                                                          d_multi, st)))
-                    return rc;
-            }
-            done_rescue += RC;
-        } else if (pairq) {
-            if ((rc = bg_seed_pairq_launch(pair, pairq, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand,
-                                           d_pairs, d_multi, kMaxProposals, st)))
-                return rc;
-        } else if (pair) {
-            if ((rc = bg_seed_pairs_launch(pair, nr / 2, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_pairs,
-                                           kMaxProposals, st)))
-                return rc;
-        } else if (multi) {
-            if ((rc = bg_seed_multi_launch(multi, G, strands == BG_STRAND_REVERSE ? BG_HIT_REVERSE : BG_HIT_FORWARD, nr, r0, d_coff, d_nh,
-                                           d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride, d_strand, d_multi, kMaxProposals, st)))
-                return rc;
-        } else if (G == 2)
-            se_best_kernel<2><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
-                                                               d_strand, 0);
-        else
-            se_best_kernel<1><<<best_grid, dim3(256), 0, st>>>(nr, r0, d_coff, d_nh, d_aln, d_cops, d_wlo, d_hits, d_ops, ops_stride,
-                                                               d_strand, strands == BG_STRAND_REVERSE ? BG_HIT_REVERSE : BG_HIT_FORWARD);
-        BG_HIP(hipGetLastError());
-        done_hits += n_hits;
-        done_cand += C;
+    for (uint64_t r0 = 0; r0 < c.n_reads; r0 += chunk) {
+        SeedPassRun p{};
+        p.r0 = r0;
+        p.nr = std::min(chunk, c.n_reads - r0);
+        p.nv = G * p.nr;
+        p.nq = p.nv * std::max<uint32_t>(prm.S, 1);
+        if ((rc = se_candidates(R, p, &any_panic))) return rc;
+        if ((rc = se_align(R, p))) return rc;
+        if ((rc = c.rescue ? se_rescue(R, p) : se_reduce(R, p))) return rc;
+        done_hits += p.n_sa_rows;
+        done_cand += p.C;
+        done_rescue += p.n_rescue;
     }
-    if (totals) {
-        totals[0] = done_hits;
-        totals[1] = done_cand;
+    if (c.totals) {
+        c.totals[0] = done_hits;
+        c.totals[1] = done_cand;
     }
-    if (totals && rescue) {
+    if (c.totals && c.rescue) {
         // pairs rescued: counted on the device from the bytes R1 / R4 wrote (the call's last wait, outside the passes)
-        totals[2] = done_rescue;
-        uint64_t* d_count = (uint64_t*)W.p[18];  // (the rescue offsets of the last pass are no longer needed)
+        c.totals[2] = done_rescue;
+        if ((rc = R.need(kRescuedCount, 64))) return rc;
+        uint64_t* d_count = R.buf<uint64_t>(kRescuedCount);
         BG_HIP(hipMemsetAsync(d_count, 0, 8, st));
-        if ((rc = bg_seed_rescue_count_launch(n_reads / 2, d_rescued, d_count, st))) return rc;
+        if ((rc = bg_seed_rescue_count_launch(c.n_reads / 2, c.rescued, d_count, st))) return rc;
         BG_HIP(hipMemcpyAsync(&W.h_tot[5], d_count, 8, hipMemcpyDeviceToHost, st));
         BG_HIP(hipStreamSynchronize(st));
-        totals[3] = W.h_tot[5];
+        c.totals[3] = W.h_tot[5];
     }
     // a seed that reaches a byte outside the alphabet makes the reference's backward_search panic; here it does not
     // vote, every read is still answered, and the call says so
     return any_panic ? BG_ERR_OUT_OF_ALPHABET : BG_OK;
+}
+
+// the mode calls' own argument checks; every other one is se_run's
+int pair_args(const bg_pair_params_t* pp, const void* pairs, uint64_t n_pairs, const void* hits) {
+    if (!pp || !pairs || pp->min_span > pp->max_span || pp->pen_unpaired < 0 || (n_pairs && !hits) || n_pairs > (UINT64_MAX >> 2))
+        return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+int pairq_args(const bg_pairq_params_t* qp, const void* multi) {
+    if (!qp || !multi || qp->mapq_cap > 254) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+int rescue_args(const bg_rescue_params_t* rp, const void* rescued) {
+    if (!rp || !rescued || rp->max_anchors == 0 || rp->max_anchors > BG_RESCUE_MAX_ANCHORS) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
+int multi_args(const bg_multi_params_t* mp, const void* multi, uint32_t strands, uint64_t n_reads) {
+    if (!mp || !multi || mp->max_hits == 0 || mp->max_hits > BG_SEED_MAX_HITS || mp->mapq_cap > 254 || strands < BG_STRAND_FORWARD ||
+        strands > BG_STRAND_BOTH || n_reads > (UINT64_MAX >> 8))
+        return BG_ERR_INVALID_ARG;
+    return BG_OK;
 }
 
 }  // namespace
@@ -637,7 +735,10 @@ extern "C" int bg_seed_extend_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const
                                         const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                         bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals,
                                         void* stream) {
-    return se_run(fm, sc, prm, 0, n_reads, d_reads, d_read_off, max_read_len, d_hits, nullptr, d_ops, ops_stride, totals, stream);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    return se_run(c);
 }
 
 extern "C" int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
@@ -645,38 +746,24 @@ extern "C" int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* s
                                                 uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
                                                 uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
-    return se_run(fm, sc, prm, strands, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals, stream);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand;
+    return se_run(c);
 }
-
-namespace {
-
-// the pair calls' own argument checks; every other one is se_run's
-int pair_args(const bg_pair_params_t* pp, const void* pairs, uint64_t n_pairs, const void* hits) {
-    if (!pp || !pairs || pp->min_span > pp->max_span || pp->pen_unpaired < 0 || (n_pairs && !hits) || n_pairs > (UINT64_MAX >> 2))
-        return BG_ERR_INVALID_ARG;
-    return BG_OK;
-}
-
-}  // namespace
 
 extern "C" int bg_seed_extend_pairs_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
                                               uint64_t n_pairs, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                               bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_ops,
                                               uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
-    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
-                  stream, pp, d_pairs);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.pair = pp, c.pairs = d_pairs;
+    return se_run(c);
 }
-
-namespace {
-
-// the pairs-mapq calls' own argument checks; every other one is the pair calls' and se_run's
-int pairq_args(const bg_pairq_params_t* qp, const void* multi) {
-    if (!qp || !multi || qp->mapq_cap > 254) return BG_ERR_INVALID_ARG;
-    return BG_OK;
-}
-
-}  // namespace
 
 extern "C" int bg_seed_extend_pairs_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
                                                    const bg_pairq_params_t* qp, uint64_t n_pairs, const uint8_t* d_reads,
@@ -685,19 +772,12 @@ extern "C" int bg_seed_extend_pairs_mapq_batch_dev(bg_fm* fm, const bg_scoring_t
                                                    uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
     if (int rc = pairq_args(qp, d_multi)) return rc;
-    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
-                  stream, pp, d_pairs, nullptr, d_multi, nullptr, nullptr, qp);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.pair = pp, c.pairs = d_pairs, c.pairq = qp, c.multi = d_multi;
+    return se_run(c);
 }
-
-namespace {
-
-// the rescue calls' own argument checks; every other one is the pair calls' and se_run's
-int rescue_args(const bg_rescue_params_t* rp, const void* rescued) {
-    if (!rp || !rescued || rp->max_anchors == 0 || rp->max_anchors > BG_RESCUE_MAX_ANCHORS) return BG_ERR_INVALID_ARG;
-    return BG_OK;
-}
-
-}  // namespace
 
 extern "C" int bg_seed_extend_pairs_rescue_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
                                                      const bg_rescue_params_t* rp, uint64_t n_pairs, const uint8_t* d_reads,
@@ -706,8 +786,11 @@ extern "C" int bg_seed_extend_pairs_rescue_batch_dev(bg_fm* fm, const bg_scoring
                                                      uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
     if (int rc = rescue_args(rp, d_rescued)) return rc;
-    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
-                  stream, pp, d_pairs, nullptr, nullptr, rp, d_rescued);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.pair = pp, c.pairs = d_pairs, c.rescue = rp, c.rescued = d_rescued;
+    return se_run(c);
 }
 
 extern "C" int bg_seed_extend_pairs_rescue_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm,
@@ -719,29 +802,23 @@ extern "C" int bg_seed_extend_pairs_rescue_mapq_batch_dev(bg_fm* fm, const bg_sc
     if (int rc = pair_args(pp, d_pairs, n_pairs, d_hits)) return rc;
     if (int rc = rescue_args(rp, d_rescued)) return rc;
     if (int rc = pairq_args(qp, d_multi)) return rc;
-    return se_run(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals,
-                  stream, pp, d_pairs, nullptr, d_multi, rp, d_rescued, qp);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.pair = pp, c.pairs = d_pairs, c.rescue = rp, c.rescued = d_rescued, c.pairq = qp, c.multi = d_multi;
+    return se_run(c);
 }
-
-namespace {
-
-// the multi calls' own argument checks; every other one is se_run's
-int multi_args(const bg_multi_params_t* mp, const void* multi, uint32_t strands, uint64_t n_reads) {
-    if (!mp || !multi || mp->max_hits == 0 || mp->max_hits > BG_SEED_MAX_HITS || mp->mapq_cap > 254 || strands < BG_STRAND_FORWARD ||
-        strands > BG_STRAND_BOTH || n_reads > (UINT64_MAX >> 8))
-        return BG_ERR_INVALID_ARG;
-    return BG_OK;
-}
-
-}  // namespace
 
 extern "C" int bg_seed_extend_multi_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
                                               uint32_t strands, uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
                                               uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, bg_multi_hit_t* d_multi,
                                               uint8_t* d_ops, uint64_t ops_stride, uint64_t* totals, void* stream) {
     if (int rc = multi_args(mp, d_multi, strands, n_reads)) return rc;
-    return se_run(fm, sc, prm, strands, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand, d_ops, ops_stride, totals, stream,
-                  nullptr, nullptr, mp, d_multi);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.multi_prm = mp, c.multi = d_multi;
+    return se_run(c);
 }
 
 extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream) {
@@ -755,74 +832,65 @@ extern "C" int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in
 
 namespace {
 
-// the host-buffer flavours: se_run on copies of the reads, then the winners' operations compacted in read order (multi mode:
-// multi->max_hits slots per read in hits / strand, compacted in slot order; pairs-mapq and rescue-mapq mode: one `multis` record
-// per read)
-int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands, uint64_t n_reads,
-                const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* strand, uint8_t* ops_buf,
-                uint64_t ops_cap, uint64_t* ops_used, const bg_pair_params_t* pair = nullptr, bg_pair_hit_t* pairs = nullptr,
-                const bg_multi_params_t* multi = nullptr, bg_multi_hit_t* multis = nullptr, const bg_rescue_params_t* rescue = nullptr,
-                uint8_t* rescued = nullptr, const bg_pairq_params_t* pairq = nullptr) {
-    if (!fm || !sc || !prm || (n_reads && (!read_off || !hits))) return BG_ERR_INVALID_ARG;
+// The host-buffer flavours: `h` describes the call on the caller's host arrays (its max_read_len, ops, ops_stride, totals and
+// stream are not set).  The same call runs on device copies; then the reported hits' operations are compacted into ops_buf in
+// slot order (multi mode: max_hits slots per read).
+int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (!h.fm || !h.sc || !h.prm || (h.n_reads && (!h.read_off || !h.hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
-    if (n_reads == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
+    if (h.n_reads == 0) return BG_OK;
+    bg_ctx* ctx = h.fm->ctx;
     BG_HIP(hipSetDevice(ctx->device));
+    const uint64_t n_reads = h.n_reads;
     uint64_t max_len = 0;
-    for (uint64_t r = 0; r < n_reads; r++) max_len = std::max(max_len, read_off[r + 1] - read_off[r]);
+    for (uint64_t r = 0; r < n_reads; r++) max_len = std::max(max_len, h.read_off[r + 1] - h.read_off[r]);
     if (max_len > 65535) return BG_ERR_TOO_LARGE;
-    if (rescue && pair->max_span > 65535) return BG_ERR_TOO_LARGE;
+    if (h.rescue && h.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
     // (rescue call: a slot also holds the operations of a read against a rescue window of max_span bytes)
-    const uint64_t stride = ops_buf ? max_len + std::max<uint64_t>(max_len + 2 * (uint64_t)prm->pad, rescue ? pair->max_span : 0) + 4 : 0;
-    const uint64_t bytes = read_off[n_reads];
-    uint8_t *d_reads = nullptr, *d_ops = nullptr;
-    uint64_t* d_off = nullptr;
-    uint8_t *d_strand = nullptr, *d_rescued = nullptr;
-    bg_seed_hit_t* d_hits = nullptr;
-    bg_pair_hit_t* d_pairs = nullptr;
-    bg_multi_hit_t* d_multi = nullptr;
-    const uint64_t n_slots = n_reads * (multi ? multi->max_hits : 1);
+    const uint64_t stride = ops_buf ? max_len + std::max<uint64_t>(max_len + 2 * (uint64_t)h.prm->pad, h.rescue ? h.pair->max_span : 0) + 4 : 0;
+    const uint64_t n_slots = n_reads * (h.multi_prm ? h.multi_prm->max_hits : 1);
+    const uint64_t bytes = h.read_off[n_reads], n_pairs = n_reads / 2;
     std::vector<uint8_t> h_ops;
+    SeedCall d = h;  // the same call on device copies; an output the call does not have stays null
+    uint8_t* d_reads = nullptr;
+    uint64_t* d_off = nullptr;
+    d.hits = nullptr, d.strand = nullptr, d.pairs = nullptr, d.rescued = nullptr, d.multi = nullptr;
+    d.max_read_len = (uint32_t)max_len, d.ops_stride = stride, d.stream = ctx->stream;
     int panic_rc = BG_OK;
     auto run = [&]() -> int {
         hipStream_t st = ctx->stream;
         BG_HIP(hipMalloc((void**)&d_reads, std::max<uint64_t>(bytes, 16)));
         BG_HIP(hipMalloc((void**)&d_off, (n_reads + 1) * 8));
-        BG_HIP(hipMalloc((void**)&d_hits, n_slots * sizeof(bg_seed_hit_t)));
-        if (stride) BG_HIP(hipMalloc((void**)&d_ops, n_slots * stride));
-        if (strand) BG_HIP(hipMalloc((void**)&d_strand, n_slots));
-        if (pair) BG_HIP(hipMalloc((void**)&d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t)));
-        if (rescue) BG_HIP(hipMalloc((void**)&d_rescued, std::max<uint64_t>(n_reads / 2, 16)));
-        if (multi || pairq) BG_HIP(hipMalloc((void**)&d_multi, n_reads * sizeof(bg_multi_hit_t)));
-        if (bytes) BG_HIP(hipMemcpyAsync(d_reads, reads, bytes, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-        int rc = se_run(fm, sc, prm, strands, n_reads, d_reads, d_off, (uint32_t)max_len, d_hits, d_strand, d_ops, stride, nullptr, st,
-                        pair, d_pairs, multi, d_multi, rescue, d_rescued, pairq);
+        BG_HIP(hipMalloc((void**)&d.hits, n_slots * sizeof(bg_seed_hit_t)));
+        if (stride) BG_HIP(hipMalloc((void**)&d.ops, n_slots * stride));
+        if (h.strand) BG_HIP(hipMalloc((void**)&d.strand, n_slots));
+        if (h.pairs) BG_HIP(hipMalloc((void**)&d.pairs, n_pairs * sizeof(bg_pair_hit_t)));
+        if (h.rescued) BG_HIP(hipMalloc((void**)&d.rescued, std::max<uint64_t>(n_pairs, 16)));
+        if (h.multi) BG_HIP(hipMalloc((void**)&d.multi, n_reads * sizeof(bg_multi_hit_t)));
+        if (bytes) BG_HIP(hipMemcpyAsync(d_reads, h.reads, bytes, hipMemcpyHostToDevice, st));
+        BG_HIP(hipMemcpyAsync(d_off, h.read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+        d.reads = d_reads, d.read_off = d_off;
+        int rc = se_run(d);
         if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
         panic_rc = rc;
-        BG_HIP(hipMemcpyAsync(hits, d_hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
-        if (strand) BG_HIP(hipMemcpyAsync(strand, d_strand, n_slots, hipMemcpyDeviceToHost, st));
-        if (pair) BG_HIP(hipMemcpyAsync(pairs, d_pairs, n_reads / 2 * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
-        if (rescue) BG_HIP(hipMemcpyAsync(rescued, d_rescued, n_reads / 2, hipMemcpyDeviceToHost, st));
-        if (multi || pairq) BG_HIP(hipMemcpyAsync(multis, d_multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
+        BG_HIP(hipMemcpyAsync(h.hits, d.hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
+        if (h.strand) BG_HIP(hipMemcpyAsync(h.strand, d.strand, n_slots, hipMemcpyDeviceToHost, st));
+        if (h.pairs) BG_HIP(hipMemcpyAsync(h.pairs, d.pairs, n_pairs * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
+        if (h.rescued) BG_HIP(hipMemcpyAsync(h.rescued, d.rescued, n_pairs, hipMemcpyDeviceToHost, st));
+        if (h.multi) BG_HIP(hipMemcpyAsync(h.multi, d.multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_slots * stride);
-            BG_HIP(hipMemcpyAsync(h_ops.data(), d_ops, n_slots * stride, hipMemcpyDeviceToHost, st));
+            BG_HIP(hipMemcpyAsync(h_ops.data(), d.ops, n_slots * stride, hipMemcpyDeviceToHost, st));
         }
         BG_HIP(hipStreamSynchronize(st));
         return BG_OK;
     };
     int rc = run();
-    hipFree(d_reads);
-    hipFree(d_off);
-    hipFree(d_hits);
-    hipFree(d_ops);
-    hipFree(d_strand);
-    hipFree(d_pairs);
-    hipFree(d_rescued);
-    hipFree(d_multi);
+    for (void* q : {(void*)d_reads, (void*)d_off, (void*)d.hits, (void*)d.ops, (void*)d.strand, (void*)d.pairs, (void*)d.rescued, (void*)d.multi})
+        hipFree(q);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
+    bg_seed_hit_t* hits = h.hits;
     uint64_t used = 0;
     int status = BG_OK;
     for (uint64_t r = 0; r < n_slots; r++) {
@@ -846,21 +914,30 @@ int se_run_host(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, 
 extern "C" int bg_seed_extend_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint64_t n_reads,
                                     const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits, uint8_t* ops_buf,
                                     uint64_t ops_cap, uint64_t* ops_used) {
-    return se_run_host(fm, sc, prm, 0, n_reads, reads, read_off, hits, nullptr, ops_buf, ops_cap, ops_used);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = 0, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
+    c.hits = hits;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
                                             uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
                                             uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
-    return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_pairs_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
                                           uint64_t n_pairs, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
                                           uint8_t* strand, bg_pair_hit_t* pairs, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
-    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.pair = pp, c.pairs = pairs;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_pairs_rescue_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
@@ -869,8 +946,10 @@ extern "C" int bg_seed_extend_pairs_rescue_batch(bg_fm* fm, const bg_scoring_t* 
                                                  uint64_t ops_cap, uint64_t* ops_used) {
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
     if (int rc = rescue_args(rp, rescued)) return rc;
-    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
-                       nullptr, rp, rescued);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.pair = pp, c.pairs = pairs, c.rescue = rp, c.rescued = rescued;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_multi_params_t* mp,
@@ -878,7 +957,10 @@ extern "C" int bg_seed_extend_multi_batch(bg_fm* fm, const bg_scoring_t* sc, con
                                           bg_seed_hit_t* hits, uint8_t* strand, bg_multi_hit_t* multi, uint8_t* ops_buf, uint64_t ops_cap,
                                           uint64_t* ops_used) {
     if (int rc = multi_args(mp, multi, strands, n_reads)) return rc;
-    return se_run_host(fm, sc, prm, strands, n_reads, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, nullptr, nullptr, mp, multi);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.multi_prm = mp, c.multi = multi;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_pairs_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
@@ -887,8 +969,10 @@ extern "C" int bg_seed_extend_pairs_mapq_batch(bg_fm* fm, const bg_scoring_t* sc
                                                uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
     if (int rc = pairq_args(qp, multi)) return rc;
-    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
-                       multi, nullptr, nullptr, qp);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.pair = pp, c.pairs = pairs, c.pairq = qp, c.multi = multi;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 
 extern "C" int bg_seed_extend_pairs_rescue_mapq_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, const bg_pair_params_t* pp,
@@ -899,6 +983,8 @@ extern "C" int bg_seed_extend_pairs_rescue_mapq_batch(bg_fm* fm, const bg_scorin
     if (int rc = pair_args(pp, pairs, n_pairs, hits)) return rc;
     if (int rc = rescue_args(rp, rescued)) return rc;
     if (int rc = pairq_args(qp, multi)) return rc;
-    return se_run_host(fm, sc, prm, BG_STRAND_BOTH, 2 * n_pairs, reads, read_off, hits, strand, ops_buf, ops_cap, ops_used, pp, pairs, nullptr,
-                       multi, rp, rescued, qp);
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.prm = prm, c.strands = BG_STRAND_BOTH, c.n_reads = 2 * n_pairs, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.pair = pp, c.pairs = pairs, c.rescue = rp, c.rescued = rescued, c.pairq = qp, c.multi = multi;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
 }

@@ -1,84 +1,85 @@
 // The pair rule of bg_seed_extend_pairs_batch[_dev] (include/biogpu.h, "Read pairs") as device functions, shared by the pair
-// stage (seed_pairs.hip) and the rescue stages (seed_rescue.hip): one pair per group of 16 lanes, on the pass scratch of
-// seed_extend.hip (candidate offsets of the 4 n_pairs virtual reads m1, rc(m1), m2, rc(m2), their alignments, windows).
+// stages (seed_pairs.hip, seed_pairq.hip) and the rescue stages (seed_rescue.hip, seed_rescueq.hip): one pair per group of 16
+// lanes, on the pass view of seed_pass.h (pair p: virtual reads 4p .. 4p + 3 = m1, rc(m1), m2, rc(m2)).
 #ifndef BG_SEED_PAIR_RULE_H
 #define BG_SEED_PAIR_RULE_H
-#include "fm_kernels.h"
+#include "seed_rule.h"
 
 namespace bgpair {
 
-constexpr uint32_t kMaxCand = 1024;  // candidates of one virtual read are below this: a candidate index fits in 10 key bits
+using namespace bgseed;
 
 struct PairPrm {
     uint64_t min_span, max_span;
     int64_t pen_unpaired;
 };
-
-// max of a 64-bit key over the 16 lanes of a group
-__device__ __forceinline__ uint64_t max16(uint64_t v) {
-#pragma unroll
-    for (int o = 8; o; o >>= 1) {
-        const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o, 16) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o, 16);
-        v = max(v, other);
-    }
-    return v;
-}
-
-// the score of an own-best key (se_best_kernel<2>'s key: score biased to unsigned in the high word, ~candidate in the low one)
-__device__ __forceinline__ int32_t key_score(uint64_t key) { return (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u); }
+inline PairPrm pair_prm(const bg_pair_params_t* pp) { return PairPrm{pp->min_span, pp->max_span, pp->pen_unpaired}; }
 
 // What the rule finds for one pair, the same in every lane of its group.
 struct PairRule {
     uint64_t cb[5];   // candidate offsets of the pair's four virtual reads, and their end
-    uint64_t own[2];  // each mate's own best over both strands (own-best key; 0: the mate has no candidate)
+    uint64_t own[2];  // each mate's own best over both strands (own_key; 0: the mate has no candidate)
     uint64_t best;    // key of the best proper combination: score sum biased to unsigned (33 bits), 1 for orientation A, ~i, ~j
     uint32_t n_proper;
 };
 
+// A proper combination: candidate i of the forward list `a` with candidate j of the reverse list `b` of orientation o
+// (0: A, a is m1's; 1: B, a is m2's), their scores and text intervals.
+struct ProperCombo {
+    int o;
+    uint32_t i, j;
+    int32_t a_score, b_score;
+    uint64_t a_start, a_end, b_start, b_end;
+};
+
 // Orientation A pairs m1's forward candidates (v = 0) with m2's reverse ones (v = 3), orientation B m2's forward ones (v = 2)
-// with m1's reverse ones (v = 1).  The lanes walk each orientation's product, strided over the longer list, with one key per
-// combination (10 bits per candidate index: both below kMaxCand), so the max is the rule's best.
-__device__ __forceinline__ PairRule pair_rule(uint64_t p, uint32_t l16, const PairPrm& pp, const uint64_t* __restrict__ coff,
-                                              const bg_alignment_t* __restrict__ aln, const uint64_t* __restrict__ w_lo) {
+// with m1's reverse ones (v = 1).  The lanes of the group walk each orientation's product, strided over the longer list, and
+// f sees every proper combination once, in one lane.  `on` false: nothing is walked.
+template <typename F>
+__device__ __forceinline__ void for_proper(const SeedPass& P, const uint64_t (&cb)[5], bool on, uint32_t l16, const PairPrm& pp, F&& f) {
+#pragma unroll
+    for (int o = 0; o < 2; o++) {
+        const uint64_t fa = cb[o == 0 ? 0 : 2], fb = cb[o == 0 ? 3 : 1];
+        const uint32_t na = on ? (uint32_t)(cb[o == 0 ? 1 : 3] - fa) : 0, nb = on ? (uint32_t)(cb[o == 0 ? 4 : 2] - fb) : 0;
+        const bool lanes_on_a = na > nb;
+        const uint32_t n_out = lanes_on_a ? nb : na, n_in = lanes_on_a ? na : nb;
+        for (uint32_t u = 0; u < n_out; u++) {
+            for (uint32_t w = l16; w < n_in; w += 16) {
+                const uint32_t i = lanes_on_a ? w : u, j = lanes_on_a ? u : w;
+                const bg_alignment_t& A = P.aln[fa + i];
+                const bg_alignment_t& B = P.aln[fb + j];
+                const uint64_t a_start = P.w_lo[fa + i] + A.ystart, b_start = P.w_lo[fb + j] + B.ystart;
+                if (a_start > b_start) continue;
+                const uint64_t a_end = P.w_lo[fa + i] + A.yend, b_end = P.w_lo[fb + j] + B.yend;
+                const uint64_t span = max(a_end, b_end) - a_start;
+                if (span < pp.min_span || span > pp.max_span) continue;
+                f(ProperCombo{o, i, j, A.score, B.score, a_start, a_end, b_start, b_end});
+            }
+        }
+    }
+}
+
+// One key per proper combination (10 bits per candidate index: both below kMaxCand), so the max is the rule's best.
+__device__ __forceinline__ PairRule pair_rule(const SeedPass& P, uint64_t p, uint32_t l16, const PairPrm& pp) {
     PairRule R;
 #pragma unroll
-    for (int v = 0; v < 5; v++) R.cb[v] = coff[4 * p + v];
+    for (int v = 0; v < 5; v++) R.cb[v] = P.coff[4 * p + v];
     // each mate's own best over both strands: highest score, forward strand on a tie, smallest start
 #pragma unroll
     for (int m = 0; m < 2; m++) {
         const uint64_t c0 = R.cb[2 * m];
         const uint32_t nc = (uint32_t)(R.cb[2 * m + 2] - c0);
         uint64_t best = 0;
-        for (uint32_t c = l16; c < nc; c += 16) {
-            const uint32_t sc = (uint32_t)aln[c0 + c].score ^ 0x80000000u;
-            best = max(best, ((uint64_t)sc << 32) | (uint32_t)~c);
-        }
+        for (uint32_t c = l16; c < nc; c += 16) best = max(best, own_key(P.aln[c0 + c].score, c));
         R.own[m] = max16(best);
     }
-    // proper combinations of both orientations
     uint64_t best = 0;
     uint32_t n_proper = 0;
-#pragma unroll
-    for (int o = 0; o < 2; o++) {
-        const uint64_t fa = R.cb[o == 0 ? 0 : 2], fb = R.cb[o == 0 ? 3 : 1];
-        const uint32_t na = (uint32_t)(R.cb[o == 0 ? 1 : 3] - fa), nb = (uint32_t)(R.cb[o == 0 ? 4 : 2] - fb);
-        const bool lanes_on_a = na > nb;
-        const uint32_t n_out = lanes_on_a ? nb : na, n_in = lanes_on_a ? na : nb;
-        for (uint32_t u = 0; u < n_out; u++) {
-            for (uint32_t w = l16; w < n_in; w += 16) {
-                const uint32_t i = lanes_on_a ? w : u, j = lanes_on_a ? u : w;
-                const bg_alignment_t& A = aln[fa + i];
-                const bg_alignment_t& B = aln[fb + j];
-                const uint64_t a_start = w_lo[fa + i] + A.ystart, b_start = w_lo[fb + j] + B.ystart;
-                if (a_start > b_start) continue;
-                const uint64_t span = max(w_lo[fa + i] + A.yend, w_lo[fb + j] + B.yend) - a_start;
-                if (span < pp.min_span || span > pp.max_span) continue;
-                n_proper++;
-                const uint64_t sum = (uint64_t)((int64_t)A.score + B.score + (1ll << 32));
-                best = max(best, sum << 21 | (uint64_t)(o == 0) << 20 | (uint64_t)(kMaxCand - 1 - i) << 10 | (kMaxCand - 1 - j));
-            }
-        }
-    }
+    for_proper(P, R.cb, true, l16, pp, [&](const ProperCombo& k) {
+        n_proper++;
+        const uint64_t sum = (uint64_t)((int64_t)k.a_score + k.b_score + (1ll << 32));
+        best = max(best, sum << 21 | (uint64_t)(k.o == 0) << 20 | (uint64_t)(kMaxCand - 1 - k.i) << 10 | (kMaxCand - 1 - k.j));
+    });
     R.best = max16(best);
 #pragma unroll
     for (int o = 8; o; o >>= 1) n_proper += (uint32_t)__shfl_xor((int)n_proper, o, 16);
@@ -86,77 +87,54 @@ __device__ __forceinline__ PairRule pair_rule(uint64_t p, uint32_t l16, const Pa
     return R;
 }
 
-// Mate m of pair p (caller read r0 + 2p + m) reports candidate `pick` of its own (relative to cb[2m]; ignored when the mate
-// has none: it is then written like an unmapped read) exactly as se_best_kernel<2> writes a winner: record, window,
-// operations right-aligned in the read's slot, strand.
-__device__ __forceinline__ void write_mate(uint64_t p, int m, uint32_t l16, uint64_t r0, const PairRule& R, uint64_t pick,
-                                           const uint32_t* __restrict__ n_hits, const bg_alignment_t* __restrict__ aln,
-                                           const uint8_t* __restrict__ c_ops, const uint64_t* __restrict__ w_lo,
-                                           bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
-                                           uint8_t* __restrict__ strand) {
-    const uint64_t r = 2 * p + m;
-    const uint64_t c0 = R.cb[2 * m];
-    const uint32_t nc = (uint32_t)(R.cb[2 * m + 2] - c0);
-    bg_seed_hit_t h;
-    memset(&h, 0, sizeof(h));
-    h.aln.score = BG_MIN_SCORE;
-    h.window_start = h.ref_start = h.ref_end = ~0ull;
-    h.n_candidates = nc;
-    h.n_seed_hits = n_hits[4 * p + 2 * m] + n_hits[4 * p + 2 * m + 1];
-    h.aln.ops_off = (r0 + r + 1) * ops_stride;
-    uint8_t won = BG_HIT_NONE;
-    if (nc) {
-        const uint64_t c = pick;
-        won = c >= R.cb[2 * m + 1] - c0 ? BG_HIT_REVERSE : BG_HIT_FORWARD;
-        const bg_alignment_t a = aln[c0 + c];
-        h.aln = a;
-        h.aln.ops_off = (r0 + r + 1) * ops_stride - a.n_ops;
-        h.window_start = w_lo[c0 + c];
-        h.ref_start = w_lo[c0 + c] + a.ystart;
-        h.ref_end = w_lo[c0 + c] + a.yend;
-        if (ops && c_ops)
-            for (uint32_t k = l16; k < a.n_ops; k += 16) ops[h.aln.ops_off + k] = c_ops[a.ops_off + k];
-    }
-    if (l16 == 0) {
-        hits[r0 + r] = h;
-        if (strand) strand[r0 + r] = won;
-    }
-}
-
-// Rule 4 and the writes of the paired call: the best proper pair, if it gives up at most pen_unpaired against the mates' own
-// bests; a mate that is not part of a proper pair reports exactly what se_best_kernel<2> writes for it.
-__device__ __forceinline__ void pair_write(uint64_t p, uint32_t l16, uint64_t r0, const PairPrm& pp, const PairRule& R,
-                                           const uint32_t* __restrict__ n_hits, const bg_alignment_t* __restrict__ aln,
-                                           const uint8_t* __restrict__ c_ops, const uint64_t* __restrict__ w_lo,
-                                           bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
-                                           uint8_t* __restrict__ strand, bg_pair_hit_t* __restrict__ pairs) {
-    bool proper = false;
-    uint64_t pick[2] = {~(uint32_t)R.own[0], ~(uint32_t)R.own[1]};  // candidate per mate, relative to cb[2m]
-    uint64_t span = 0;
+// "Paired or not" (rule 4): the best proper combination, if it gives up at most pen_unpaired against the mates' own bests.
+struct PairChoice {
+    bool proper;
+    uint32_t pick[2];  // the candidate each mate reports, relative to cb[2m]: the combination's member, or the mate's own best
+    int64_t pair_sum;  // proper: the combination's score sum
+    uint64_t span;     // proper: its span
+};
+__device__ __forceinline__ PairChoice pair_choice(const SeedPass& P, const PairRule& R, const PairPrm& pp) {
+    PairChoice ch{false, {key_cand(R.own[0]), key_cand(R.own[1])}, 0, 0};
     if (R.n_proper) {
         const int64_t pair_sum = (int64_t)(R.best >> 21) - (1ll << 32);
-        const int64_t own_sum = (int64_t)key_score(R.own[0]) + key_score(R.own[1]);
-        if (pair_sum + pp.pen_unpaired >= own_sum) {
-            proper = true;
+        if (pair_sum + pp.pen_unpaired >= (int64_t)key_score(R.own[0]) + key_score(R.own[1])) {
+            ch.proper = true;
+            ch.pair_sum = pair_sum;
             const bool orient_a = (R.best >> 20) & 1;
             const uint32_t i = kMaxCand - 1 - (uint32_t)((R.best >> 10) & (kMaxCand - 1));
             const uint32_t j = kMaxCand - 1 - (uint32_t)(R.best & (kMaxCand - 1));
             const uint64_t ca = (orient_a ? R.cb[0] : R.cb[2]) + i, cr = (orient_a ? R.cb[3] : R.cb[1]) + j;  // forward, reverse
-            const uint64_t a_start = w_lo[ca] + aln[ca].ystart;
-            span = max(w_lo[ca] + aln[ca].yend, w_lo[cr] + aln[cr].yend) - a_start;
-            pick[0] = (orient_a ? ca : cr) - R.cb[0];
-            pick[1] = (orient_a ? cr : ca) - R.cb[2];
+            ch.span = max(P.w_lo[ca] + P.aln[ca].yend, P.w_lo[cr] + P.aln[cr].yend) - (P.w_lo[ca] + P.aln[ca].ystart);
+            ch.pick[0] = (uint32_t)((orient_a ? ca : cr) - R.cb[0]);
+            ch.pick[1] = (uint32_t)((orient_a ? cr : ca) - R.cb[2]);
         }
     }
+    return ch;
+}
+
+// Mate m of pair p (caller read r0 + 2p + m) reports candidate `pick` of its own (relative to cb[2m]; a mate without
+// candidates is written like an unmapped read) exactly as se_best_kernel<2> writes a winner.
+__device__ __forceinline__ void write_mate(const SeedPass& P, const SeedOut& O, uint64_t p, int m, uint32_t l16, const PairRule& R,
+                                           uint32_t pick) {
+    const uint64_t c0 = R.cb[2 * m];
+    const uint32_t nc = (uint32_t)(R.cb[2 * m + 2] - c0);
+    const uint8_t won = !nc ? BG_HIT_NONE : pick >= R.cb[2 * m + 1] - c0 ? BG_HIT_REVERSE : BG_HIT_FORWARD;
+    write_cand(P, O, P.r0 + 2 * p + m, l16, c0 + pick, won, nc, P.n_hits[4 * p + 2 * m] + P.n_hits[4 * p + 2 * m + 1]);
+}
+
+// The writes of the paired call: a mate that is not part of a proper pair reports exactly what se_best_kernel<2> writes for it.
+__device__ __forceinline__ void pair_write(const SeedPass& P, const SeedOut& O, uint64_t p, uint32_t l16, const PairRule& R,
+                                           const PairChoice& ch) {
 #pragma unroll
-    for (int m = 0; m < 2; m++) write_mate(p, m, l16, r0, R, pick[m], n_hits, aln, c_ops, w_lo, hits, ops, ops_stride, strand);
+    for (int m = 0; m < 2; m++) write_mate(P, O, p, m, l16, R, ch.pick[m]);
     if (l16 == 0) {
         bg_pair_hit_t ph;
         memset(&ph, 0, sizeof(ph));
-        ph.span = span;
+        ph.span = ch.span;
         ph.n_proper = R.n_proper;
-        ph.proper = proper ? 1 : 0;
-        pairs[r0 / 2 + p] = ph;
+        ph.proper = ch.proper ? 1 : 0;
+        O.pairs[P.r0 / 2 + p] = ph;
     }
 }
 

@@ -1,0 +1,95 @@
+// One pass of seed-and-extend as its reduction stages see it (seed_pairs.hip, seed_pairq.hip, seed_multi.hip, seed_rescue.hip,
+// seed_rescueq.hip, and se_best_kernel of seed_extend.hip): what stages S0-S6 of seed_extend.hip left in the pass scratch
+// (SeedPass), where the answers go (SeedOut), and the launchers of the stages, which take these two plus what is their own.
+#ifndef BG_SEED_PASS_H
+#define BG_SEED_PASS_H
+#include "fm_kernels.h"
+
+namespace bgseed {
+
+// Candidates of one virtual read are at most this (its proposals: seed slots x max_occ, sorted in LDS by one wavefront).
+constexpr uint32_t kMaxCand = 1024;
+constexpr uint32_t kMaskWords = 4;  // se_multi_kernel: one "out" bit per candidate in four dwords per lane
+static_assert(kMaxCand <= 1u << 10, "a candidate index is a 10-bit field of the pair rule's key");
+static_assert(4 * kMaxCand <= 1u << 13, "a candidate of a pair, relative to the pair's first, is a 13-bit field of a rescue plan entry");
+static_assert(2 * kMaxCand <= 16 * 32 * kMaskWords, "the multi stage keeps one bit per candidate of both strands of a read");
+
+// The pass: `n` units (reads; in the pair modes pairs of interleaved mates) from caller read r0 on.  A read has G virtual
+// reads (itself, or itself and its revcomp), a pair the four m1, rc(m1), m2, rc(m2); virtual read v owns candidates
+// coff[v] .. coff[v + 1) of aln / w_lo (the candidate's alignment with operations at c_ops + aln.ops_off, its window's
+// first text offset) and resolved n_hits[v] suffix-array rows.  voff: the virtual reads' byte offsets (rescue stages).
+struct SeedPass {
+    uint64_t r0, n;
+    const uint64_t* coff;
+    const uint32_t* n_hits;
+    const bg_alignment_t* aln;
+    const uint8_t* c_ops;
+    const uint64_t* w_lo;
+    const uint64_t* voff;
+};
+
+// The caller's whole arrays (absent: null).  Slot s of hits / strand ends its operations at ops + (s + 1) * ops_stride.
+struct SeedOut {
+    bg_seed_hit_t* hits;
+    uint8_t* ops;
+    uint64_t ops_stride;
+    uint8_t* strand;
+    bg_pair_hit_t* pairs;
+    bg_multi_hit_t* multi;
+    uint8_t* rescued;
+};
+
+// What R1 leaves per pair of the pass: the plan entries (bg_seed_rescue_plan_bytes), the mates' own score sum, and the counts
+// of rescue alignments / x bytes / y bytes.
+struct SeedRescuePlan {
+    void* plan;
+    int64_t* own_sum;
+    uint32_t *n_res, *x_bytes, *y_bytes;
+};
+// The scans of per-unit counts of alignments / x bytes / y bytes (n + 1 entries each): unit u's alignments are roff[u] ..
+// roff[u + 1), their sequences start at x + xoff[u] and y + yoff[u].
+struct SeedXYOff {
+    const uint64_t *roff, *xoff, *yoff;
+};
+// the input of a batch of alignments: sequences back to back and their offsets
+struct SeedPairsXY {
+    uint8_t* x;
+    uint64_t* x_off;
+    uint8_t* y;
+    uint64_t* y_off;
+};
+// R3's answer: rescue alignment j of pair p is aln[roff[p] + j], its operations at ops + aln.ops_off
+struct SeedRescueAln {
+    const uint64_t* roff;
+    const bg_alignment_t* aln;
+    const uint8_t* ops;
+};
+
+}  // namespace bgseed
+
+// seed_pairs.hip: S7 of the paired call: hits, strand and operations of reads r0 + 2p, r0 + 2p + 1 and pairs[r0 / 2 + p].
+int bg_seed_pairs_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, hipStream_t st);
+// seed_pairq.hip: S7 of the pairs-mapq call: what bg_seed_pairs_launch writes, plus multi[r0 + 2p], multi[r0 + 2p + 1].
+int bg_seed_pairq_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, const bg_pairq_params_t* qp,
+                         hipStream_t st);
+// seed_multi.hip: S7 of the multi call (G virtual reads per read; strand1: the strand of every hit when G = 1).  Read r0 + r
+// owns slots K (r0 + r) .. K (r0 + r) + K - 1 of hits / strand / ops and multi[r0 + r].
+int bg_seed_multi_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_multi_params_t* mp, uint32_t G, uint8_t strand1,
+                         hipStream_t st);
+// seed_rescue.hip: stages R1, R2, R4 of the rescue call.  R1 answers every pair as bg_seed_pairs_launch does and plans the rescue
+// alignments; R2 gathers their (x, window) pairs at the scanned offsets; R4 rewrites the rescued pairs.
+size_t bg_seed_rescue_plan_bytes(uint64_t n_pairs);
+int bg_seed_rescue_plan_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp,
+                               uint64_t n_text, const bgseed::SeedRescuePlan& plan, hipStream_t st);
+int bg_seed_rescue_gather_launch(const bgseed::SeedPass& P, const uint8_t* d_vreads, const uint8_t* d_text, const void* d_plan,
+                                 const bgseed::SeedXYOff& off, const bgseed::SeedPairsXY& xy, hipStream_t st);
+int bg_seed_rescue_pick_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp,
+                               const bgseed::SeedRescuePlan& plan, const bgseed::SeedRescueAln& res, hipStream_t st);
+// *d_count += the pairs of the call with a non-zero rescued byte (totals[3])
+int bg_seed_rescue_count_launch(uint64_t n_pairs, const uint8_t* d_rescued, uint64_t* d_count, hipStream_t st);
+// seed_rescueq.hip: the stage after R4 of the rescue-mapq call: multi[r0 + 2p], multi[r0 + 2p + 1] of every pair p of the pass with
+// a non-zero rescued byte.  The other pairs' records are written before R1 (bg_seed_pairq_launch) and stay.
+int bg_seed_rescueq_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp,
+                           const bg_pairq_params_t* qp, const void* d_plan, const bgseed::SeedRescueAln& res, hipStream_t st);
+
+#endif

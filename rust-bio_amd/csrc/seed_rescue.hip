@@ -20,20 +20,13 @@ using namespace bgpair;
 
 // R1: 16 lanes per pair.  Every pair is first answered as the paired call answers it (rescued = 0).  The anchors of a mate are
 // its first A candidates in rank order: A rounds of the own-best key's max over the keys below the last one found.
-__global__ __launch_bounds__(256) void se_rescue_plan_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, RescuePrm rp,
-                                                             const uint64_t* __restrict__ voff, const uint64_t* __restrict__ coff,
-                                                             const uint32_t* __restrict__ n_hits, const bg_alignment_t* __restrict__ aln,
-                                                             const uint8_t* __restrict__ c_ops, const uint64_t* __restrict__ w_lo,
-                                                             bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
-                                                             uint8_t* __restrict__ strand, bg_pair_hit_t* __restrict__ pairs,
-                                                             uint8_t* __restrict__ rescued, RescuePlan* __restrict__ plan,
-                                                             int64_t* __restrict__ own_sum, uint32_t* __restrict__ n_res,
-                                                             uint32_t* __restrict__ x_bytes, uint32_t* __restrict__ y_bytes) {
+__global__ __launch_bounds__(256) void se_rescue_plan_kernel(SeedPass P, SeedOut O, PairPrm pp, RescuePrm rp, SeedRescuePlan out) {
     const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t l16 = threadIdx.x & 15;
-    if (p >= n_pairs) return;  // uniform per group of 16
-    const PairRule R = pair_rule(p, l16, pp, coff, aln, w_lo);
-    pair_write(p, l16, r0, pp, R, n_hits, aln, c_ops, w_lo, hits, ops, ops_stride, strand, pairs);
+    if (p >= P.n) return;  // uniform per group of 16
+    const PairRule R = pair_rule(P, p, l16, pp);
+    pair_write(P, O, p, l16, R, pair_choice(P, R, pp));
+    RescuePlan* plan = (RescuePlan*)out.plan;
     uint32_t nr = 0, xb = 0, yb = 0;
     if (R.n_proper == 0) {
 #pragma unroll
@@ -42,22 +35,21 @@ __global__ __launch_bounds__(256) void se_rescue_plan_kernel(uint64_t n_pairs, u
             const uint32_t nc = (uint32_t)(R.cb[2 * m + 2] - c0), n_fwd = (uint32_t)(R.cb[2 * m + 1] - c0);
             if (!nc) continue;
             const int other = 1 - m;
-            const uint32_t Lo = (uint32_t)(voff[4 * p + 2 * other + 1] - voff[4 * p + 2 * other]);  // the sought mate's length
+            const uint32_t Lo = (uint32_t)(P.voff[4 * p + 2 * other + 1] - P.voff[4 * p + 2 * other]);  // the sought mate's length
             uint64_t prev = ~0ull;
             for (uint32_t k = 0; k < rp.max_anchors; k++) {
                 uint64_t best = 0;
                 for (uint32_t c = l16; c < nc; c += 16) {
-                    const uint32_t sc = (uint32_t)aln[c0 + c].score ^ 0x80000000u;
-                    const uint64_t key = ((uint64_t)sc << 32) | (uint32_t)~c;
+                    const uint64_t key = own_key(P.aln[c0 + c].score, c);
                     if (key < prev) best = max(best, key);
                 }
                 best = max16(best);
-                if (!best) break;  // fewer than A candidates (a candidate's key is never 0: c < 2 kMaxCand)
+                if (!best) break;  // fewer than A candidates (a candidate's key is never 0)
                 prev = best;
-                const uint32_t c = ~(uint32_t)best;
+                const uint32_t c = key_cand(best);
                 const bool fwd = c < n_fwd;
-                const bg_alignment_t& a = aln[c0 + c];
-                const uint64_t rs = w_lo[c0 + c] + a.ystart, re = w_lo[c0 + c] + a.yend;
+                const bg_alignment_t& a = P.aln[c0 + c];
+                const uint64_t rs = P.w_lo[c0 + c] + a.ystart, re = P.w_lo[c0 + c] + a.yend;
                 if (re - rs > pp.max_span) continue;
                 const uint64_t lo = fwd ? rs : (re > pp.max_span ? re - pp.max_span : 0u);
                 const uint64_t hi = fwd ? min(rp.n_text, rs + pp.max_span) : re;
@@ -78,44 +70,40 @@ __global__ __launch_bounds__(256) void se_rescue_plan_kernel(uint64_t n_pairs, u
         }
     }
     if (l16 == 0) {
-        rescued[r0 / 2 + p] = 0;
-        n_res[p] = nr;
-        x_bytes[p] = xb;
-        y_bytes[p] = yb;
+        O.rescued[P.r0 / 2 + p] = 0;
+        out.n_res[p] = nr;
+        out.x_bytes[p] = xb;
+        out.y_bytes[p] = yb;
         // own(m): 0 for a mate without candidates
-        own_sum[p] = (int64_t)(R.cb[2] > R.cb[0] ? key_score(R.own[0]) : 0) + (R.cb[4] > R.cb[2] ? key_score(R.own[1]) : 0);
+        out.own_sum[p] = (int64_t)(R.cb[2] > R.cb[0] ? key_score(R.own[0]) : 0) + (R.cb[4] > R.cb[2] ? key_score(R.own[1]) : 0);
     }
 }
 
 // R2: one wavefront per pair, four per block: the (x, window) pairs of its planned rescues + their offsets.  x is read from the
 // pass's virtual reads, which hold both strands of every mate.
-__global__ __launch_bounds__(256) void se_rescue_gather_kernel(uint64_t n_pairs, const uint8_t* __restrict__ vreads,
-                                                               const uint64_t* __restrict__ voff, const uint8_t* __restrict__ text,
-                                                               const RescuePlan* __restrict__ plan, const uint64_t* __restrict__ roff,
-                                                               const uint64_t* __restrict__ xoff, const uint64_t* __restrict__ yoff,
-                                                               uint8_t* __restrict__ x, uint64_t* __restrict__ x_off,
-                                                               uint8_t* __restrict__ y, uint64_t* __restrict__ y_off) {
+__global__ __launch_bounds__(256) void se_rescue_gather_kernel(SeedPass P, const uint8_t* __restrict__ vreads, const uint8_t* __restrict__ text,
+                                                               const RescuePlan* __restrict__ plan, SeedXYOff off, SeedPairsXY xy) {
     const uint64_t p = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
-    if (p >= n_pairs) return;
-    if (p + 1 == n_pairs && lane == 0) {  // closing offsets
-        x_off[roff[n_pairs]] = xoff[n_pairs];
-        y_off[roff[n_pairs]] = yoff[n_pairs];
+    if (p >= P.n) return;
+    if (p + 1 == P.n && lane == 0) {  // closing offsets
+        xy.x_off[off.roff[P.n]] = off.xoff[P.n];
+        xy.y_off[off.roff[P.n]] = off.yoff[P.n];
     }
-    const uint64_t j0 = roff[p];
-    const uint32_t n = (uint32_t)(roff[p + 1] - j0);
-    uint64_t xo = xoff[p], yo = yoff[p];
+    const uint64_t j0 = off.roff[p];
+    const uint32_t n = (uint32_t)(off.roff[p + 1] - j0);
+    uint64_t xo = off.xoff[p], yo = off.yoff[p];
     for (uint32_t k = 0; k < n; k++) {
         const RescuePlan e = plan[kSlots * p + k];
         const uint64_t v = 4 * p + ((e.info >> 16) & 3);
-        const uint64_t ro = voff[v];
-        const uint32_t L = (uint32_t)(voff[v + 1] - ro);
+        const uint64_t ro = P.voff[v];
+        const uint32_t L = (uint32_t)(P.voff[v + 1] - ro);
         if (lane == 0) {
-            x_off[j0 + k] = xo;
-            y_off[j0 + k] = yo;
+            xy.x_off[j0 + k] = xo;
+            xy.y_off[j0 + k] = yo;
         }
-        for (uint32_t i = lane; i < L; i += 64) x[xo + i] = vreads[ro + i];
-        for (uint32_t i = lane; i < e.len; i += 64) y[yo + i] = text[e.lo + i];
+        for (uint32_t i = lane; i < L; i += 64) xy.x[xo + i] = vreads[ro + i];
+        for (uint32_t i = lane; i < e.len; i += 64) xy.y[yo + i] = text[e.lo + i];
         xo += L;
         yo += e.len;
     }
@@ -123,66 +111,50 @@ __global__ __launch_bounds__(256) void se_rescue_gather_kernel(uint64_t n_pairs,
 
 // R4: 16 lanes per pair, one lane per planned rescue (kSlots <= 16).  The max of the accepted rescues' keys (rescue_key of
 // seed_rescue_rule.h) is the rule's choice.
-__global__ __launch_bounds__(256) void se_rescue_pick_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, RescuePrm rp,
-                                                             const uint64_t* __restrict__ coff, const uint32_t* __restrict__ n_hits,
-                                                             const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ c_ops,
-                                                             const uint64_t* __restrict__ w_lo, const RescuePlan* __restrict__ plan,
-                                                             const int64_t* __restrict__ own_sum, const uint64_t* __restrict__ roff,
-                                                             const bg_alignment_t* __restrict__ r_aln, const uint8_t* __restrict__ r_ops,
-                                                             bg_seed_hit_t* __restrict__ hits, uint8_t* __restrict__ ops, uint64_t ops_stride,
-                                                             uint8_t* __restrict__ strand, bg_pair_hit_t* __restrict__ pairs,
-                                                             uint8_t* __restrict__ rescued) {
+__global__ __launch_bounds__(256) void se_rescue_pick_kernel(SeedPass P, SeedOut O, PairPrm pp, RescuePrm rp, SeedRescuePlan in,
+                                                             SeedRescueAln res) {
     static_assert(kSlots <= 16, "one lane per planned rescue");
     const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t l16 = threadIdx.x & 15;
-    if (p >= n_pairs) return;  // uniform per group of 16
-    const uint64_t j0 = roff[p];
-    const uint32_t n = (uint32_t)(roff[p + 1] - j0);
+    if (p >= P.n) return;  // uniform per group of 16
+    const RescuePlan* plan = (const RescuePlan*)in.plan;
+    const uint64_t j0 = res.roff[p];
+    const uint32_t n = (uint32_t)(res.roff[p + 1] - j0);
     if (!n) return;
     PairRule R;
 #pragma unroll
-    for (int v = 0; v < 5; v++) R.cb[v] = coff[4 * p + v];
+    for (int v = 0; v < 5; v++) R.cb[v] = P.coff[4 * p + v];
     uint64_t key = 0;
     if (l16 < n) {
         const RescuePlan e = plan[kSlots * p + l16];
-        key = rescue_key(e, r_aln[j0 + l16], l16, R.cb[0], pp, rp.min_score, aln, w_lo);
+        key = rescue_key(P, e, res.aln[j0 + l16], l16, R.cb[0], pp, rp.min_score);
     }
     key = max16(key);
     if (!key) return;
     const int64_t sum = rescue_key_sum(key);
-    if (sum + pp.pen_unpaired < own_sum[p]) return;
+    if (sum + pp.pen_unpaired < in.own_sum[p]) return;
     const uint32_t k = (uint32_t)key & 15;
     const RescuePlan e = plan[kSlots * p + k];
-    const bg_alignment_t q = r_aln[j0 + k];
+    const bg_alignment_t q = res.aln[j0 + k];
     const bool fwd = (e.info >> 20) & 1;
     const int m = (e.info >> 21) & 1, other = 1 - m;
     const uint64_t ca = R.cb[0] + (e.info & 0x1FFF);
     // the anchor's mate reports the anchor candidate exactly as the paired call writes a candidate ...
-    write_mate(p, m, l16, r0, R, ca - R.cb[2 * m], n_hits, aln, c_ops, w_lo, hits, ops, ops_stride, strand);
+    write_mate(P, O, p, m, l16, R, (uint32_t)(ca - R.cb[2 * m]));
     // ... the other mate the rescued hit on the opposite strand
     const uint64_t r = 2 * p + other;
-    bg_seed_hit_t h;
-    memset(&h, 0, sizeof(h));
-    h.aln = q;
-    h.aln.ops_off = (r0 + r + 1) * ops_stride - q.n_ops;
-    h.window_start = e.lo;
-    h.ref_start = e.lo + q.ystart;
-    h.ref_end = e.lo + q.yend;
-    h.n_candidates = (uint32_t)(R.cb[2 * other + 2] - R.cb[2 * other]);
-    h.n_seed_hits = n_hits[4 * p + 2 * other] + n_hits[4 * p + 2 * other + 1];
-    if (ops && r_ops)
-        for (uint32_t i = l16; i < q.n_ops; i += 16) ops[h.aln.ops_off + i] = r_ops[q.ops_off + i];
+    write_hit(O, P.r0 + r, l16, &q, e.lo, res.ops, fwd ? BG_HIT_REVERSE : BG_HIT_FORWARD,
+              ReadCounts{(uint32_t)(R.cb[2 * other + 2] - R.cb[2 * other]), P.n_hits[4 * p + 2 * other] + P.n_hits[4 * p + 2 * other + 1]});
     if (l16 == 0) {
-        hits[r0 + r] = h;
-        if (strand) strand[r0 + r] = fwd ? BG_HIT_REVERSE : BG_HIT_FORWARD;
-        const uint64_t as = w_lo[ca] + aln[ca].ystart, ae = w_lo[ca] + aln[ca].yend;
+        const uint64_t as = P.w_lo[ca] + P.aln[ca].ystart, ae = P.w_lo[ca] + P.aln[ca].yend;
+        const uint64_t qs = e.lo + q.ystart, qe = e.lo + q.yend;
         bg_pair_hit_t ph;
         memset(&ph, 0, sizeof(ph));
-        ph.span = max(ae, h.ref_end) - (fwd ? as : h.ref_start);
+        ph.span = max(ae, qe) - (fwd ? as : qs);
         ph.n_proper = 0;  // the seeded count: a pair with a proper seeded combination is not rescued
         ph.proper = 1;
-        pairs[r0 / 2 + p] = ph;
-        rescued[r0 / 2 + p] = (uint8_t)(other + 1);
+        O.pairs[P.r0 / 2 + p] = ph;
+        O.rescued[P.r0 / 2 + p] = (uint8_t)(other + 1);
     }
 }
 
@@ -208,44 +180,28 @@ int bg_seed_rescue_count_launch(uint64_t n_pairs, const uint8_t* d_rescued, uint
 
 size_t bg_seed_rescue_plan_bytes(uint64_t n_pairs) { return n_pairs * kSlots * sizeof(RescuePlan); }
 
-int bg_seed_rescue_plan_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_text, uint64_t n_pairs, uint64_t r0,
-                               const uint64_t* d_voff, const uint64_t* d_coff, const uint32_t* d_n_hits, const bg_alignment_t* d_aln,
-                               const uint8_t* d_c_ops, const uint64_t* d_w_lo, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride,
-                               uint8_t* d_strand, bg_pair_hit_t* d_pairs, uint8_t* d_rescued, void* d_plan, int64_t* d_own_sum,
-                               uint32_t* d_n_res, uint32_t* d_x_bytes, uint32_t* d_y_bytes, uint32_t max_cand, hipStream_t st) {
-    if (max_cand > kMaxCand) return BG_ERR_UNSUPPORTED;
-    if (n_pairs == 0) return BG_OK;
-    const PairPrm prm{pp->min_span, pp->max_span, pp->pen_unpaired};
+int bg_seed_rescue_plan_launch(const SeedPass& P, const SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_text,
+                               const SeedRescuePlan& plan, hipStream_t st) {
+    if (P.n == 0) return BG_OK;
     const RescuePrm rprm{rp->max_anchors, rp->min_score, n_text};
-    se_rescue_plan_kernel<<<dim3((unsigned)((n_pairs * 16 + 255) / 256)), dim3(256), 0, st>>>(
-        n_pairs, r0, prm, rprm, d_voff, d_coff, d_n_hits, d_aln, d_c_ops, d_w_lo, d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued,
-        (RescuePlan*)d_plan, d_own_sum, d_n_res, d_x_bytes, d_y_bytes);
+    se_rescue_plan_kernel<<<dim3((unsigned)((P.n * 16 + 255) / 256)), dim3(256), 0, st>>>(P, O, pair_prm(pp), rprm, plan);
     BG_HIP(hipGetLastError());
     return BG_OK;
 }
 
-int bg_seed_rescue_gather_launch(uint64_t n_pairs, const uint8_t* d_vreads, const uint64_t* d_voff, const uint8_t* d_text, const void* d_plan,
-                                 const uint64_t* d_roff, const uint64_t* d_xoff, const uint64_t* d_yoff, uint8_t* d_x, uint64_t* d_x_off,
-                                 uint8_t* d_y, uint64_t* d_y_off, hipStream_t st) {
-    if (n_pairs == 0) return BG_OK;
-    se_rescue_gather_kernel<<<dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, st>>>(n_pairs, d_vreads, d_voff, d_text,
-                                                                                        (const RescuePlan*)d_plan, d_roff, d_xoff, d_yoff, d_x,
-                                                                                        d_x_off, d_y, d_y_off);
+int bg_seed_rescue_gather_launch(const SeedPass& P, const uint8_t* d_vreads, const uint8_t* d_text, const void* d_plan, const SeedXYOff& off,
+                                 const SeedPairsXY& xy, hipStream_t st) {
+    if (P.n == 0) return BG_OK;
+    se_rescue_gather_kernel<<<dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, st>>>(P, d_vreads, d_text, (const RescuePlan*)d_plan, off, xy);
     BG_HIP(hipGetLastError());
     return BG_OK;
 }
 
-int bg_seed_rescue_pick_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, uint64_t n_pairs, uint64_t r0, const uint64_t* d_coff,
-                               const uint32_t* d_n_hits, const bg_alignment_t* d_aln, const uint8_t* d_c_ops, const uint64_t* d_w_lo,
-                               const void* d_plan, const int64_t* d_own_sum, const uint64_t* d_roff, const bg_alignment_t* d_r_aln,
-                               const uint8_t* d_r_ops, bg_seed_hit_t* d_hits, uint8_t* d_ops, uint64_t ops_stride, uint8_t* d_strand,
-                               bg_pair_hit_t* d_pairs, uint8_t* d_rescued, hipStream_t st) {
-    if (n_pairs == 0) return BG_OK;
-    const PairPrm prm{pp->min_span, pp->max_span, pp->pen_unpaired};
+int bg_seed_rescue_pick_launch(const SeedPass& P, const SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp,
+                               const SeedRescuePlan& plan, const SeedRescueAln& res, hipStream_t st) {
+    if (P.n == 0) return BG_OK;
     const RescuePrm rprm{rp->max_anchors, rp->min_score, 0};
-    se_rescue_pick_kernel<<<dim3((unsigned)((n_pairs * 16 + 255) / 256)), dim3(256), 0, st>>>(
-        n_pairs, r0, prm, rprm, d_coff, d_n_hits, d_aln, d_c_ops, d_w_lo, (const RescuePlan*)d_plan, d_own_sum, d_roff, d_r_aln, d_r_ops,
-        d_hits, d_ops, ops_stride, d_strand, d_pairs, d_rescued);
+    se_rescue_pick_kernel<<<dim3((unsigned)((P.n * 16 + 255) / 256)), dim3(256), 0, st>>>(P, O, pair_prm(pp), rprm, plan, res);
     BG_HIP(hipGetLastError());
     return BG_OK;
 }

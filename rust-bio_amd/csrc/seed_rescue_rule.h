@@ -26,18 +26,17 @@ struct RescuePrm {
 // Planned rescue `slot` of a pair (plan entry e, its alignment q, the pair's first candidate cb0): 0 if it is not accepted,
 // otherwise the key whose maximum over the pair's slots is the rule's choice: the score sum biased to unsigned (33 bits), 1 for
 // orientation A, 1 for the rescue anchored on m1, ~rank (2 bits), the slot.
-__device__ __forceinline__ uint64_t rescue_key(const RescuePlan& e, const bg_alignment_t& q, uint32_t slot, uint64_t cb0, const PairPrm& pp,
-                                               int32_t min_score, const bg_alignment_t* __restrict__ aln,
-                                               const uint64_t* __restrict__ w_lo) {
+__device__ __forceinline__ uint64_t rescue_key(const SeedPass& P, const RescuePlan& e, const bg_alignment_t& q, uint32_t slot, uint64_t cb0,
+                                               const PairPrm& pp, int32_t min_score) {
     const uint64_t ca = cb0 + (e.info & 0x1FFF);
     const bool fwd = (e.info >> 20) & 1;
     const uint32_t m = (e.info >> 21) & 1;
-    const uint64_t as = w_lo[ca] + aln[ca].ystart, ae = w_lo[ca] + aln[ca].yend;
+    const uint64_t as = P.w_lo[ca] + P.aln[ca].ystart, ae = P.w_lo[ca] + P.aln[ca].yend;
     const uint64_t qs = e.lo + q.ystart, qe = e.lo + q.yend;
     const uint64_t f_start = fwd ? as : qs, b_start = fwd ? qs : as;  // the forward one is `a`, the reverse one `b`
     const uint64_t span = max(ae, qe) - f_start;
     if (!(q.score >= min_score && f_start <= b_start && span >= pp.min_span && span <= pp.max_span)) return 0;
-    const uint64_t sum = (uint64_t)((int64_t)aln[ca].score + q.score + (1ll << 32));
+    const uint64_t sum = (uint64_t)((int64_t)P.aln[ca].score + q.score + (1ll << 32));
     const bool orient_a = fwd == (m == 0);  // m1 forward: m1 anchors forward, or m2 anchors in reverse
     return sum << 8 | (uint64_t)orient_a << 7 | (uint64_t)(m == 0) << 6 | (3u - ((e.info >> 18) & 3)) << 4 | slot;
 }

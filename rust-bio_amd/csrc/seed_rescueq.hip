@@ -9,20 +9,6 @@ namespace {
 
 using namespace bgpair;
 
-struct PairqPrm {
-    int32_t min_score;
-    uint32_t mapq_cap;
-};
-
-// score (biased to unsigned) as a key of max16; 0: none
-__device__ __forceinline__ uint64_t score_key(int32_t s) { return (uint64_t)((uint32_t)s ^ 0x80000000u) | 1ull << 32; }
-__device__ __forceinline__ int32_t score_of(uint64_t key) { return (int32_t)((uint32_t)key ^ 0x80000000u); }
-
-// lane `src` of the group's value
-__device__ __forceinline__ uint64_t bcast16(uint64_t v, uint32_t src) {
-    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), (int)src, 16) << 32) | (uint32_t)__shfl((int)(uint32_t)v, (int)src, 16);
-}
-
 // 16 lanes per pair, pairs with rescued != 0 only (the others keep the records written before R1).
 //   1. lane k < n holds planned rescue k of the pair: its key (rescue_key: 0 unless accepted), its anchor (a seeded candidate of
 //      the anchoring mate) and its hit (a placement of the other mate).  The maximum key is R4's choice: anchor c_a, hit h,
@@ -35,34 +21,31 @@ __device__ __forceinline__ uint64_t bcast16(uint64_t v, uint32_t src) {
 //   4. lane 0 writes the two records; S1 - S2_i is clamped at 0 in signed arithmetic (a better seeded candidate of the anchor's
 //      mate whose own rescue failed gives S2_i > S1 through (b)).
 // No LDS, no atomics; every reduction is a max16 on a 64-bit key.
-__global__ __launch_bounds__(256) void se_rescue_mapq_kernel(uint64_t n_pairs, uint64_t r0, PairPrm pp, int32_t rescue_min_score, PairqPrm qp,
-                                                             const uint64_t* __restrict__ coff, const bg_alignment_t* __restrict__ aln,
-                                                             const uint64_t* __restrict__ w_lo, const RescuePlan* __restrict__ plan,
-                                                             const uint64_t* __restrict__ roff, const bg_alignment_t* __restrict__ r_aln,
-                                                             const uint8_t* __restrict__ rescued, bg_multi_hit_t* __restrict__ multi) {
+__global__ __launch_bounds__(256) void se_rescue_mapq_kernel(SeedPass P, SeedOut O, PairPrm pp, int32_t rescue_min_score, PairqPrm qp,
+                                                             const RescuePlan* __restrict__ plan, SeedRescueAln res) {
     static_assert(kSlots <= 16, "one lane per planned rescue");
     const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t l16 = threadIdx.x & 15;
-    if (p >= n_pairs) return;            // uniform per group of 16
-    if (!rescued[r0 / 2 + p]) return;    // the same
-    const uint64_t j0 = roff[p];
-    const uint32_t n = (uint32_t)(roff[p + 1] - j0);
+    if (p >= P.n) return;                // uniform per group of 16
+    if (!O.rescued[P.r0 / 2 + p]) return;  // the same
+    const uint64_t j0 = res.roff[p];
+    const uint32_t n = (uint32_t)(res.roff[p + 1] - j0);
     uint64_t cb[5];
 #pragma unroll
-    for (int v = 0; v < 5; v++) cb[v] = coff[4 * p + v];
+    for (int v = 0; v < 5; v++) cb[v] = P.coff[4 * p + v];
     // 1. this lane's rescue (without one: not accepted, and intervals that nothing reads)
     uint64_t key = 0, a_lo = 0, a_hi = 0, h_lo = 0, h_hi = 0;
     int32_t a_score = 0, h_score = 0;
     uint32_t am = 0;  // the anchoring mate
     if (l16 < n) {
         const RescuePlan e = plan[kSlots * p + l16];
-        const bg_alignment_t& q = r_aln[j0 + l16];
-        key = rescue_key(e, q, l16, cb[0], pp, rescue_min_score, aln, w_lo);
+        const bg_alignment_t& q = res.aln[j0 + l16];
+        key = rescue_key(P, e, q, l16, cb[0], pp, rescue_min_score);
         const uint64_t ca = cb[0] + (e.info & 0x1FFF);
         am = (e.info >> 21) & 1;
-        a_score = aln[ca].score;
-        a_lo = w_lo[ca] + aln[ca].ystart;
-        a_hi = w_lo[ca] + aln[ca].yend;
+        a_score = P.aln[ca].score;
+        a_lo = P.w_lo[ca] + P.aln[ca].ystart;
+        a_hi = P.w_lo[ca] + P.aln[ca].yend;
         h_score = q.score;
         h_lo = e.lo + q.ystart;
         h_hi = e.lo + q.yend;
@@ -81,17 +64,7 @@ __global__ __launch_bounds__(256) void se_rescue_mapq_kernel(uint64_t n_pairs, u
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         // 2. the mate's seeded candidates elsewhere
-        const uint64_t c0 = cb[2 * i];
-        const uint32_t nc = (uint32_t)(cb[2 * i + 2] - c0);
-        uint64_t best = 0;
-        for (uint32_t c = l16; c < nc; c += 16) {
-            const bg_alignment_t& a = aln[c0 + c];
-            const int32_t score = a.score;
-            const uint64_t x_lo = w_lo[c0 + c] + a.ystart, x_hi = w_lo[c0 + c] + a.yend;
-            if (score < qp.min_score || (x_lo <= hi[i] && lo[i] <= x_hi)) continue;
-            best = max(best, score_key(score));
-        }
-        seeded[i] = max16(best);
+        seeded[i] = best_elsewhere(P, l16, cb[2 * i], (uint32_t)(cb[2 * i + 2] - cb[2 * i]), lo[i], hi[i], qp.min_score);
         // 3. the mate-i member of this lane's rescue
         const bool is_anchor = am == (uint32_t)i;
         const int32_t y_score = is_anchor ? a_score : h_score;
@@ -111,32 +84,26 @@ __global__ __launch_bounds__(256) void se_rescue_mapq_kernel(uint64_t n_pairs, u
         mh.n_loci = other ? 2 : 1;
         mh.n_reported = 1;
         const int64_t s1 = cs[i];
-        if (s1 > 0) {
-            int64_t num = s1;  // the score this mate's placement is ahead by, 0 ..= s1
-            if (other) {
-                // S2: the pair's best total with this mate elsewhere, through an accepted rescue or unpaired; one of the two exists
-                int64_t s2 = INT64_MIN;
-                if (seeded[i]) s2 = (int64_t)score_of(seeded[i]) + cs[1 - i] - pp.pen_unpaired;
-                if (through[i]) s2 = max(s2, (int64_t)(through[i] - 1) - (1ll << 32));
-                num = min(max(S1 - s2, (int64_t)0), s1);  // (S2 > S1 happens: include/biogpu.h)
-            }
-            mh.mapq = (uint8_t)min((int64_t)qp.mapq_cap, (int64_t)qp.mapq_cap * num / s1);
+        int64_t num = s1;  // the score this mate's placement is ahead by, 0 ..= s1
+        if (s1 > 0 && other) {
+            // S2: the pair's best total with this mate elsewhere, through an accepted rescue or unpaired; one of the two exists
+            int64_t s2 = INT64_MIN;
+            if (seeded[i]) s2 = (int64_t)score_of(seeded[i]) + cs[1 - i] - pp.pen_unpaired;
+            if (through[i]) s2 = max(s2, (int64_t)(through[i] - 1) - (1ll << 32));
+            num = min(max(S1 - s2, (int64_t)0), s1);  // (S2 > S1 happens: include/biogpu.h)
         }
-        multi[r0 + 2 * p + i] = mh;
+        mh.mapq = mapq_of(qp.mapq_cap, (uint64_t)num, s1);
+        O.multi[P.r0 + 2 * p + i] = mh;
     }
 }
 
 }  // namespace
 
-int bg_seed_rescueq_launch(const bg_pair_params_t* pp, const bg_rescue_params_t* rp, const bg_pairq_params_t* qp, uint64_t n_pairs, uint64_t r0,
-                           const uint64_t* d_coff, const bg_alignment_t* d_aln, const uint64_t* d_w_lo, const void* d_plan,
-                           const uint64_t* d_roff, const bg_alignment_t* d_r_aln, const uint8_t* d_rescued, bg_multi_hit_t* d_multi,
-                           hipStream_t st) {
-    if (n_pairs == 0) return BG_OK;
-    const PairPrm prm{pp->min_span, pp->max_span, pp->pen_unpaired};
-    const PairqPrm qprm{qp->min_score, qp->mapq_cap};
-    se_rescue_mapq_kernel<<<dim3((unsigned)((n_pairs * 16 + 255) / 256)), dim3(256), 0, st>>>(
-        n_pairs, r0, prm, rp->min_score, qprm, d_coff, d_aln, d_w_lo, (const RescuePlan*)d_plan, d_roff, d_r_aln, d_rescued, d_multi);
+int bg_seed_rescueq_launch(const SeedPass& P, const SeedOut& O, const bg_pair_params_t* pp, const bg_rescue_params_t* rp,
+                           const bg_pairq_params_t* qp, const void* d_plan, const SeedRescueAln& res, hipStream_t st) {
+    if (P.n == 0) return BG_OK;
+    se_rescue_mapq_kernel<<<dim3((unsigned)((P.n * 16 + 255) / 256)), dim3(256), 0, st>>>(
+        P, O, pair_prm(pp), rp->min_score, PairqPrm{qp->min_score, qp->mapq_cap}, (const RescuePlan*)d_plan, res);
     BG_HIP(hipGetLastError());
     return BG_OK;
 }

@@ -81,35 +81,69 @@ def attach_text(fm, text=None, d_text=None):
         _lib.check(_lib.lib().bg_fm_set_text(fm.h, t.ctypes.data, len(t)), "bg_fm_set_text")
 
 
-def seed_extend_arrays(fm, scoring, reads, read_off, params=None, want_ops=True, allow_out_of_alphabet=False):
-    """Host-buffer batch: returns (hits: SEED_HIT_DTYPE[n], ops: uint8[], winners' operations back to back).
-    A seed that reaches a byte outside the index's alphabet raises AlphabetError (the reference's backward_search
-    panics there) unless allow_out_of_alphabet: such seeds simply do not vote."""
+_OUT_DTYPE = {"strand": np.uint8, "pairs": _lib.PAIR_HIT_DTYPE, "rescued": np.uint8, "multi": _lib.MULTI_HIT_DTYPE}
+
+
+def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_out_of_alphabet, modes=(), outs=(), strands=None, K=None,
+               max_span=None):
+    """The host-buffer call bg_<stem>_batch, behind the public function <stem>_arrays.  modes: the mode's parameter objects in the call's order; outs: the
+    names of its output arrays after `hits`, in the call's order (keys of _OUT_DTYPE); strands: None for a call without that
+    argument; K: slots per read of the multi call; max_span: of a rescue call, whose operation slots also hold a rescue window.
+    Returns (hits, *outs, ops)."""
+    name = f"bg_{stem}_batch"
     params = params or SeedParams()
     rd = _lib.as_u8(reads)
     off = np.ascontiguousarray(read_off, dtype=np.uint64)
     n = len(off) - 1
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
+    if "pairs" in outs and n % 2:
+        raise ValueError(f"{stem}_arrays: an odd number of reads")
+    hits = np.zeros(n if K is None else (n, K), dtype=_lib.SEED_HIT_DTYPE)
+    K = K or 1
+    size = {"strand": n * K, "pairs": n // 2, "rescued": n // 2, "multi": n}
+    arrays = [np.zeros(max(size[o], 1), dtype=_OUT_DTYPE[o]) for o in outs]
+    if not want_ops:
+        cap = 0
+    elif max_span is None:
+        cap = K * (int(2 * off[-1] + (2 * params.pad + 4) * n) + 8)
+    else:
+        # a reported hit has at most read + window operations; a rescue window is up to max_span bytes
+        cap = int(off[-1] + (max(int(np.diff(off).max(initial=0)) + 2 * params.pad, max_span) + 4) * n) + 8
     ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
     used = C.c_uint64(0)
-    sc, pc = scoring.to_c(), params.to_c()
-    rc = _lib.lib().bg_seed_extend_batch(fm.h, C.byref(sc), C.byref(pc), n, rd.ctypes.data, off.ctypes.data,
-                                         hits.ctypes.data, ops.ctypes.data if want_ops else None, cap, C.byref(used))
+    structs = [scoring.to_c(), params.to_c()] + [m.to_c() for m in modes]
+    rc = getattr(_lib.lib(), name)(fm.h, *map(C.byref, structs), *([] if strands is None else [strands]), n // 2 if "pairs" in outs else n,
+                                   rd.ctypes.data, off.ctypes.data, hits.ctypes.data, *[a.ctypes.data for a in arrays],
+                                   ops.ctypes.data if want_ops else None, cap, C.byref(used))
     if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_batch")
-    return hits, (ops[:used.value] if want_ops else None)
+        _lib.check(rc, name)
+    return (hits, *[a[:size[o]] for a, o in zip(arrays, outs)], ops[:used.value] if want_ops else None)
+
+
+def _dev_call(stem, fm, scoring, n, d_reads, d_read_off, max_read_len, *, d_hits, d_outs, d_ops, ops_stride, params, stream, totals,
+              modes=(), strands=None):
+    """The device-resident call bg_<stem>_batch_dev (pointers are ints, 0: absent); modes, strands as _host_call,
+    d_outs: the output pointers after d_hits in the call's order."""
+    name = f"bg_{stem}_batch_dev"
+    structs = [scoring.to_c(), (params or SeedParams()).to_c()] + [m.to_c() for m in modes]
+    _lib.check(getattr(_lib.lib(), name)(fm.h, *map(C.byref, structs), *([] if strands is None else [strands]), n, d_reads, d_read_off,
+                                         max_read_len, d_hits, *[d or None for d in d_outs], d_ops or None, ops_stride,
+                                         totals.ctypes.data if totals is not None else None, stream), name)
+
+
+def seed_extend_arrays(fm, scoring, reads, read_off, params=None, want_ops=True, allow_out_of_alphabet=False):
+    """Host-buffer batch: returns (hits: SEED_HIT_DTYPE[n], ops: uint8[], winners' operations back to back).
+    A seed that reaches a byte outside the index's alphabet raises AlphabetError (the reference's backward_search
+    panics there) unless allow_out_of_alphabet: such seeds simply do not vote."""
+    return _host_call("seed_extend", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet)
 
 
 def seed_extend_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_ops=0, ops_stride=0, params=None,
                     stream=0, totals=None):
     """Device-resident batch (pointers are ints); `totals`, if given, is a uint64[2] numpy array that receives
     (suffix-array rows resolved, candidates aligned)."""
-    params = params or SeedParams()
-    sc, pc = scoring.to_c(), params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_batch_dev(fm.h, C.byref(sc), C.byref(pc), n_reads, d_reads, d_read_off, max_read_len,
-                                                   d_hits, d_ops, ops_stride, totals.ctypes.data if totals is not None else None,
-                                                   stream), "bg_seed_extend_batch_dev")
+    _dev_call("seed_extend", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals)
 
 
 def seed_extend_strands_arrays(fm, scoring, reads, read_off, params=None, strands=_lib.STRAND_BOTH, want_ops=True,
@@ -117,145 +151,62 @@ def seed_extend_strands_arrays(fm, scoring, reads, read_off, params=None, strand
     """bg_seed_extend_strands_batch, host buffers: returns (hits: SEED_HIT_DTYPE[n], strand: uint8[n] of HIT_FORWARD /
     HIT_REVERSE / HIT_NONE, ops: the winners' operations back to back).  A reverse-strand winner's alignment and operations
     refer to revcomp(read) against the forward text.  Errors as seed_extend_arrays."""
-    params = params or SeedParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n, 1), dtype=np.uint8)
-    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc = scoring.to_c(), params.to_c()
-    rc = _lib.lib().bg_seed_extend_strands_batch(fm.h, C.byref(sc), C.byref(pc), strands, n, rd.ctypes.data, off.ctypes.data,
-                                                 hits.ctypes.data, strand.ctypes.data, ops.ctypes.data if want_ops else None, cap,
-                                                 C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_strands_batch")
-    return hits, strand[:n], (ops[:used.value] if want_ops else None)
+    return _host_call("seed_extend_strands", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet, outs=["strand"], strands=strands)
 
 
 def seed_extend_strands_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand=0, d_ops=0, ops_stride=0,
                             params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
     """bg_seed_extend_strands_batch_dev (pointers are ints; d_strand / d_ops may be 0); `totals` as seed_extend_dev, summed
     over the strands that ran."""
-    params = params or SeedParams()
-    sc, pc = scoring.to_c(), params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_strands_batch_dev(fm.h, C.byref(sc), C.byref(pc), strands, n_reads, d_reads, d_read_off,
-                                                           max_read_len, d_hits, d_strand or None, d_ops or None, ops_stride,
-                                                           totals.ctypes.data if totals is not None else None, stream),
-               "bg_seed_extend_strands_batch_dev")
+    _dev_call("seed_extend_strands", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals, strands=strands)
 
 
 def seed_extend_pairs_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, want_ops=True, allow_out_of_alphabet=False):
     """bg_seed_extend_pairs_batch, host buffers.  The reads are interleaved mates: read 2p is mate 1 of pair p, read 2p + 1 its
     mate 2 (an even count).  Returns (hits: SEED_HIT_DTYPE[2n], strand: uint8[2n], pairs: PAIR_HIT_DTYPE[n], ops: the reported
     hits' operations back to back).  Errors as seed_extend_arrays."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
-    if n % 2:
-        raise ValueError("seed_extend_pairs_arrays: an odd number of reads")
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n, 1), dtype=np.uint8)
-    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
-    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc, pp = scoring.to_c(), params.to_c(), pair_params.to_c()
-    rc = _lib.lib().bg_seed_extend_pairs_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), n // 2, rd.ctypes.data, off.ctypes.data,
-                                               hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
-                                               ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_pairs_batch")
-    return hits, strand[:n], pairs[:n // 2], (ops[:used.value] if want_ops else None)
+    return _host_call("seed_extend_pairs", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet,
+                      modes=[pair_params or PairParams()], outs=["strand", "pairs"])
 
 
 def seed_extend_pairs_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_strand=0, d_ops=0, ops_stride=0,
                           params=None, pair_params=None, stream=0, totals=None):
     """bg_seed_extend_pairs_batch_dev (pointers are ints; 2 n_pairs interleaved mates, d_pairs: n_pairs bg_pair_hit_t; d_strand /
     d_ops may be 0); `totals` as seed_extend_dev, over both strands of every mate."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    sc, pc, pp = scoring.to_c(), params.to_c(), pair_params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_pairs_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), n_pairs, d_reads, d_read_off,
-                                                         max_read_len, d_hits, d_strand or None, d_pairs or None, d_ops or None,
-                                                         ops_stride, totals.ctypes.data if totals is not None else None, stream),
-               "bg_seed_extend_pairs_batch_dev")
+    _dev_call("seed_extend_pairs", fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand, d_pairs], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals, modes=[pair_params or PairParams()])
 
 
 def seed_extend_pairs_mapq_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, quality_params=None, want_ops=True,
                                   allow_out_of_alphabet=False):
     """bg_seed_extend_pairs_mapq_batch, host buffers: seed_extend_pairs_arrays plus a mapping quality per mate.  Returns (hits,
     strand, pairs, multi: MULTI_HIT_DTYPE[2n] — read r's MAPQ, its best alternative's score and n_loci —, ops)."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    quality_params = quality_params or PairQualityParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
-    if n % 2:
-        raise ValueError("seed_extend_pairs_mapq_arrays: an odd number of reads")
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n, 1), dtype=np.uint8)
-    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
-    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
-    cap = int(2 * off[-1] + (2 * params.pad + 4) * n) + 8 if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc, pp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), quality_params.to_c()
-    rc = _lib.lib().bg_seed_extend_pairs_mapq_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(qp), n // 2, rd.ctypes.data,
-                                                    off.ctypes.data, hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
-                                                    multi.ctypes.data, ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_pairs_mapq_batch")
-    return hits, strand[:n], pairs[:n // 2], multi[:n], (ops[:used.value] if want_ops else None)
+    return _host_call("seed_extend_pairs_mapq", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet,
+                      modes=[pair_params or PairParams(), quality_params or PairQualityParams()], outs=["strand", "pairs", "multi"])
 
 
 def seed_extend_pairs_mapq_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_multi, d_strand=0, d_ops=0,
                                ops_stride=0, params=None, pair_params=None, quality_params=None, stream=0, totals=None):
     """bg_seed_extend_pairs_mapq_batch_dev (pointers are ints; as seed_extend_pairs_dev, plus d_multi: 2 n_pairs bg_multi_hit_t,
     which bg_sam_emit_batch_dev takes as its d_multi together with SAM_PAIRED)."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    quality_params = quality_params or PairQualityParams()
-    sc, pc, pp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), quality_params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_pairs_mapq_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(qp), n_pairs, d_reads,
-                                                              d_read_off, max_read_len, d_hits, d_strand or None, d_pairs or None,
-                                                              d_multi or None, d_ops or None, ops_stride,
-                                                              totals.ctypes.data if totals is not None else None, stream),
-               "bg_seed_extend_pairs_mapq_batch_dev")
+    _dev_call("seed_extend_pairs_mapq", fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits=d_hits,
+              d_outs=[d_strand, d_pairs, d_multi], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals, modes=[pair_params or PairParams(), quality_params or PairQualityParams()])
 
 
 def seed_extend_pairs_rescue_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, rescue_params=None, want_ops=True,
                                     allow_out_of_alphabet=False):
     """bg_seed_extend_pairs_rescue_batch, host buffers: seed_extend_pairs_arrays plus mate rescue.  Returns (hits, strand, pairs,
     rescued: uint8[n] — 0, or 1 / 2: the mate that was placed inside its partner's insert window —, ops)."""
-    params = params or SeedParams()
     pair_params = pair_params or PairParams()
-    rescue_params = rescue_params or RescueParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
-    if n % 2:
-        raise ValueError("seed_extend_pairs_rescue_arrays: an odd number of reads")
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n, 1), dtype=np.uint8)
-    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
-    rescued = np.zeros(max(n // 2, 1), dtype=np.uint8)
-    # a reported hit has at most read + window operations; a rescue window is up to max_span bytes
-    cap = int(off[-1] + (max(int(np.diff(off).max(initial=0)) + 2 * params.pad, pair_params.max_span) + 4) * n) + 8 if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc, pp, rp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c()
-    rc = _lib.lib().bg_seed_extend_pairs_rescue_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), n // 2, rd.ctypes.data,
-                                                      off.ctypes.data, hits.ctypes.data, strand.ctypes.data, pairs.ctypes.data,
-                                                      rescued.ctypes.data, ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_pairs_rescue_batch")
-    return hits, strand[:n], pairs[:n // 2], rescued[:n // 2], (ops[:used.value] if want_ops else None)
+    return _host_call("seed_extend_pairs_rescue", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet,
+                      modes=[pair_params, rescue_params or RescueParams()], outs=["strand", "pairs", "rescued"],
+                      max_span=pair_params.max_span)
 
 
 def seed_extend_pairs_rescue_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_rescued, d_strand=0, d_ops=0,
@@ -263,47 +214,21 @@ def seed_extend_pairs_rescue_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_
     """bg_seed_extend_pairs_rescue_batch_dev (pointers are ints; as seed_extend_pairs_dev, plus d_rescued: n_pairs bytes;
     ops_stride >= max_read_len + max(max_read_len + 2 pad, max_span) + 4); `totals`, if given, is a uint64[4] numpy array that
     receives (suffix-array rows resolved, seeded candidates aligned, rescue alignments run, pairs rescued)."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    rescue_params = rescue_params or RescueParams()
-    sc, pc, pp, rp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_pairs_rescue_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), n_pairs, d_reads,
-                                                                d_read_off, max_read_len, d_hits, d_strand or None, d_pairs or None,
-                                                                d_rescued or None, d_ops or None, ops_stride,
-                                                                totals.ctypes.data if totals is not None else None, stream),
-               "bg_seed_extend_pairs_rescue_batch_dev")
+    _dev_call("seed_extend_pairs_rescue", fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits=d_hits,
+              d_outs=[d_strand, d_pairs, d_rescued], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals,
+              modes=[pair_params or PairParams(), rescue_params or RescueParams()])
 
 
 def seed_extend_pairs_rescue_mapq_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, rescue_params=None,
                                          quality_params=None, want_ops=True, allow_out_of_alphabet=False):
     """bg_seed_extend_pairs_rescue_mapq_batch, host buffers: seed_extend_pairs_rescue_arrays plus a mapping quality per mate, the
     mates of rescued pairs included.  Returns (hits, strand, pairs, rescued, multi: MULTI_HIT_DTYPE[2n], ops)."""
-    params = params or SeedParams()
     pair_params = pair_params or PairParams()
-    rescue_params = rescue_params or RescueParams()
-    quality_params = quality_params or PairQualityParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
-    if n % 2:
-        raise ValueError("seed_extend_pairs_rescue_mapq_arrays: an odd number of reads")
-    hits = np.zeros(n, dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n, 1), dtype=np.uint8)
-    pairs = np.zeros(max(n // 2, 1), dtype=_lib.PAIR_HIT_DTYPE)
-    rescued = np.zeros(max(n // 2, 1), dtype=np.uint8)
-    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
-    # a reported hit has at most read + window operations; a rescue window is up to max_span bytes
-    cap = int(off[-1] + (max(int(np.diff(off).max(initial=0)) + 2 * params.pad, pair_params.max_span) + 4) * n) + 8 if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc, pp, rp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c(), quality_params.to_c()
-    rc = _lib.lib().bg_seed_extend_pairs_rescue_mapq_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), C.byref(qp), n // 2,
-                                                           rd.ctypes.data, off.ctypes.data, hits.ctypes.data, strand.ctypes.data,
-                                                           pairs.ctypes.data, rescued.ctypes.data, multi.ctypes.data,
-                                                           ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_pairs_rescue_mapq_batch")
-    return hits, strand[:n], pairs[:n // 2], rescued[:n // 2], multi[:n], (ops[:used.value] if want_ops else None)
+    return _host_call("seed_extend_pairs_rescue_mapq", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet,
+                      modes=[pair_params, rescue_params or RescueParams(), quality_params or PairQualityParams()],
+                      outs=["strand", "pairs", "rescued", "multi"], max_span=pair_params.max_span)
 
 
 def seed_extend_pairs_rescue_mapq_dev(fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_pairs, d_rescued, d_multi,
@@ -312,17 +237,10 @@ def seed_extend_pairs_rescue_mapq_dev(fm, scoring, n_pairs, d_reads, d_read_off,
     """bg_seed_extend_pairs_rescue_mapq_batch_dev (pointers are ints; as seed_extend_pairs_rescue_dev, plus d_multi: 2 n_pairs
     bg_multi_hit_t, which bg_sam_emit_batch_dev takes as its d_multi together with SAM_PAIRED); `totals` as
     seed_extend_pairs_rescue_dev."""
-    params = params or SeedParams()
-    pair_params = pair_params or PairParams()
-    rescue_params = rescue_params or RescueParams()
-    quality_params = quality_params or PairQualityParams()
-    sc, pc, pp, rp, qp = scoring.to_c(), params.to_c(), pair_params.to_c(), rescue_params.to_c(), quality_params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_pairs_rescue_mapq_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(pp), C.byref(rp), C.byref(qp),
-                                                                     n_pairs, d_reads, d_read_off, max_read_len, d_hits, d_strand or None,
-                                                                     d_pairs or None, d_rescued or None, d_multi or None, d_ops or None,
-                                                                     ops_stride, totals.ctypes.data if totals is not None else None,
-                                                                     stream),
-               "bg_seed_extend_pairs_rescue_mapq_batch_dev")
+    _dev_call("seed_extend_pairs_rescue_mapq", fm, scoring, n_pairs, d_reads, d_read_off, max_read_len, d_hits=d_hits,
+              d_outs=[d_strand, d_pairs, d_rescued, d_multi], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals,
+              modes=[pair_params or PairParams(), rescue_params or RescueParams(), quality_params or PairQualityParams()])
 
 
 def seed_extend_multi_arrays(fm, scoring, reads, read_off, params=None, multi_params=None, strands=_lib.STRAND_BOTH, want_ops=True,
@@ -330,39 +248,19 @@ def seed_extend_multi_arrays(fm, scoring, reads, read_off, params=None, multi_pa
     """bg_seed_extend_multi_batch, host buffers.  With K = multi_params.max_hits, returns (hits: SEED_HIT_DTYPE[n, K], strand:
     uint8[n, K], multi: MULTI_HIT_DTYPE[n], ops: the reported hits' operations back to back in slot order): read r's loci are
     hits[r, :multi["n_reported"][r]], the best first; the other slots read like an unmapped read.  Errors as seed_extend_arrays."""
-    params = params or SeedParams()
     multi_params = multi_params or MultiParams()
-    rd = _lib.as_u8(reads)
-    off = np.ascontiguousarray(read_off, dtype=np.uint64)
-    n = len(off) - 1
     K = max(int(multi_params.max_hits), 1) if 0 < multi_params.max_hits <= _lib.SEED_MAX_HITS else 1  # (the call rejects the rest)
-    hits = np.zeros((n, K), dtype=_lib.SEED_HIT_DTYPE)
-    strand = np.zeros(max(n * K, 1), dtype=np.uint8)
-    multi = np.zeros(max(n, 1), dtype=_lib.MULTI_HIT_DTYPE)
-    cap = K * (int(2 * off[-1] + (2 * params.pad + 4) * n) + 8) if want_ops else 0
-    ops = np.zeros(max(cap, 1), dtype=np.uint8) if want_ops else None
-    used = C.c_uint64(0)
-    sc, pc, mp = scoring.to_c(), params.to_c(), multi_params.to_c()
-    rc = _lib.lib().bg_seed_extend_multi_batch(fm.h, C.byref(sc), C.byref(pc), C.byref(mp), strands, n, rd.ctypes.data, off.ctypes.data,
-                                               hits.ctypes.data, strand.ctypes.data, multi.ctypes.data,
-                                               ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
-        _lib.check(rc, "bg_seed_extend_multi_batch")
-    return hits, strand[:n * K].reshape(n, K), multi[:n], (ops[:used.value] if want_ops else None)
+    hits, strand, multi, ops = _host_call("seed_extend_multi", fm, scoring, reads, read_off, params=params, want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet, modes=[multi_params], outs=["strand", "multi"], strands=strands, K=K)
+    return hits, strand.reshape(len(hits), K), multi, ops
 
 
 def seed_extend_multi_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_multi, d_strand=0, d_ops=0, ops_stride=0,
                           params=None, multi_params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
     """bg_seed_extend_multi_batch_dev (pointers are ints; d_hits / d_strand / d_ops hold max_hits slots per read, slot K r + k,
     d_multi n_reads bg_multi_hit_t; d_strand / d_ops may be 0); `totals` as seed_extend_strands_dev."""
-    params = params or SeedParams()
-    multi_params = multi_params or MultiParams()
-    sc, pc, mp = scoring.to_c(), params.to_c(), multi_params.to_c()
-    _lib.check(_lib.lib().bg_seed_extend_multi_batch_dev(fm.h, C.byref(sc), C.byref(pc), C.byref(mp), strands, n_reads, d_reads,
-                                                         d_read_off, max_read_len, d_hits, d_strand or None, d_multi or None,
-                                                         d_ops or None, ops_stride, totals.ctypes.data if totals is not None else None,
-                                                         stream),
-               "bg_seed_extend_multi_batch_dev")
+    _dev_call("seed_extend_multi", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand, d_multi], d_ops=d_ops,
+              ops_stride=ops_stride, params=params, stream=stream, totals=totals, modes=[multi_params or MultiParams()], strands=strands)
 
 
 def revcomp_dev(n, d_in, d_off, d_out, ctx=None, stream=0):
