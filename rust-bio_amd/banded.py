@@ -63,9 +63,11 @@ class Aligner:
                                                    cells.ctypes.data), "bg_band_create_batch")
         return boff, start, end, cells
 
-    def align_arrays(self, mode, x, x_off, y, y_off, want_ops=True, out=None, ops=None):
+    def align_arrays(self, mode, x, x_off, y, y_off, want_ops=True, out=None, ops=None, ops_cap=None):
         """Host-buffer batch through bg_align_banded_batch.  Returns (records, ops_buf); `out` / `ops` may be the arrays of an
-        earlier call of the same shape (reused, like a caller's own Vecs — fresh ones cost a page fault per 4 KB written)."""
+        earlier call of the same shape (reused, like a caller's own Vecs — fresh ones cost a page fault per 4 KB written).
+        `ops_cap`: the capacity the engine is told instead of the full need, with `ops` the caller's own buffer of at least
+        that size.  `last_ops_used` holds the bytes the operations need, also when the call raises."""
         xb, yb = _lib.as_u8(x), _lib.as_u8(y)
         xo = np.ascontiguousarray(x_off, dtype=np.uint64)
         yo = np.ascontiguousarray(y_off, dtype=np.uint64)
@@ -73,7 +75,10 @@ class Aligner:
         if out is None or len(out) != n:
             out = np.zeros(n, dtype=_lib.ALN_DTYPE)
         cap = int(xo[-1] + yo[-1]) + 4 * n + 8 if want_ops else 0
-        if want_ops and (ops is None or len(ops) != max(cap, 1)):
+        if want_ops and ops_cap is not None:
+            cap = int(ops_cap)
+            assert ops is not None and ops.dtype == np.uint8 and len(ops) >= cap
+        elif want_ops and (ops is None or len(ops) != max(cap, 1)):
             ops = np.zeros(max(cap, 1), dtype=np.uint8)
         if not want_ops:
             ops = None
@@ -86,7 +91,7 @@ class Aligner:
                                               ops.ctypes.data if want_ops else None, cap, C.byref(used),
                                               cells.ctypes.data)
         self.last_cells = cells
-        self.last_out, self.last_ops = out, ops
+        self.last_out, self.last_ops, self.last_ops_used = out, ops, int(used.value)
         _lib.check(rc, "bg_align_banded_batch")
         return out, ops
 

@@ -526,3 +526,109 @@ def test_many_small_sub_batches_equal_one_sub_batch():
     for p in range(0, P, 250):
         want = orc.banded_align(osc, "semiglobal", 10, 12, bytes(x[int(off[p]):int(off[p + 1])]), bytes(y[int(off[p]):int(off[p + 1])]))
         assert int(ref_rec["score"][p]) == want["score"]
+
+
+_RAGGED70 = {}
+
+
+def _ragged70():
+    """The 70 ragged pairs of the sub-batch tests above and their full host-entry run (chunk_pairs = 16, operations wanted:
+    the run test_several_sub_batches_and_the_remainder_first holds against the oracle), computed once and left unchanged."""
+    if not _RAGGED70:
+        xs, ys = synth.ragged_pairs(70, 700, seed=4711, min_len=150)
+        al = Aligner.with_scoring(engine_scoring(dict(BASE, yclip_prefix=0, yclip_suffix=0), True), 9, 11)
+        x, xo = _lib.concat(xs)
+        y, yo = _lib.concat(ys)
+        al.ctx.set_option("chunk_pairs", 16)
+        try:
+            out, ops = al.align_arrays(MODES["custom"], x, xo, y, yo)
+        finally:
+            al.ctx.set_option("chunk_pairs", 0)
+        assert (out["status"] == 0).all()
+        for a in (x, xo, y, yo, out, ops):
+            a.flags.writeable = False
+        _RAGGED70.update(al=al, x=x, xo=xo, y=y, yo=yo, out=out, ops=ops, used=al.last_ops_used,
+                         stride=max(len(a) for a in xs) + max(len(b) for b in ys) + 8)
+    return _RAGGED70
+
+
+RECORD_FIELDS = ("score", "xstart", "xend", "ystart", "yend", "n_ops", "status")
+
+
+def test_no_operations_wanted_over_several_sub_batches():
+    """want_ops = False over five sub-batches (nothing is compacted or downloaded, the host numbers an empty compact
+    buffer): the records of the full run, ops_off the running sum of n_ops, ops_used their total."""
+    r = _ragged70()
+    al = r["al"]
+    al.ctx.set_option("chunk_pairs", 16)
+    try:
+        out, ops = al.align_arrays(MODES["custom"], r["x"], r["xo"], r["y"], r["yo"], want_ops=False)
+    finally:
+        al.ctx.set_option("chunk_pairs", 0)
+    assert ops is None
+    for f in RECORD_FIELDS:
+        assert (out[f] == r["out"][f]).all(), f
+    n_ops = r["out"]["n_ops"].astype(np.uint64)
+    assert (out["ops_off"] == np.concatenate([[0], np.cumsum(n_ops)[:-1]])).all()
+    assert al.last_ops_used == int(n_ops.sum()) == r["used"]
+
+
+def test_ops_cap_too_small():
+    """A buffer that ends one byte into the 41st pair's operations (compact order): BG_ERR_OPS_CAP, ops_used the full need,
+    the whole pairs in front as in the full run, nothing at or beyond the cap (guard bytes behind it)."""
+    r = _ragged70()
+    al = r["al"]
+    off, n_ops = r["out"]["ops_off"].astype(np.int64), r["out"]["n_ops"].astype(np.int64)
+    cap = int(off[np.argsort(off, kind="stable")[40]]) + 1
+    bad = np.nonzero(off + n_ops > cap)[0]
+    fit = int(off[bad[0]])  # the first pair (in pair order) that does not fit: the caller gets what lies below it
+    assert 0 < fit < cap < r["used"]
+    GUARD = 0xA5
+    buf = np.full(cap + 4096, GUARD, dtype=np.uint8)
+    al.ctx.set_option("chunk_pairs", 16)
+    try:
+        with pytest.raises(_lib.BiogpuError) as e:
+            al.align_arrays(MODES["custom"], r["x"], r["xo"], r["y"], r["yo"], ops=buf, ops_cap=cap)
+    finally:
+        al.ctx.set_option("chunk_pairs", 0)
+    assert _lib.ERRORS[e.value.status] == "OPS_CAP"
+    assert al.last_ops_used == r["used"] == int(n_ops.sum())
+    assert (buf[:fit] == r["ops"][:fit]).all()
+    assert (buf[cap:] == GUARD).all()
+    for f in RECORD_FIELDS + ("ops_off",):
+        assert (al.last_out[f] == r["out"][f]).all(), f
+
+
+def test_event_timing_over_several_sub_batches():
+    """Event timing (every kernel on one stream, no preparation stream) through the device-resident entry over five
+    sub-batches: records and operations of the full run, one timed fill and one timed traceback per sub-batch."""
+    import torch
+    r = _ragged70()
+    al, P, stride = r["al"], len(r["out"]), r["stride"]
+    dev = torch.device("cuda:0")
+    dx, dy = torch.from_numpy(r["x"].copy()).to(dev), torch.from_numpy(r["y"].copy()).to(dev)
+    dxo, dyo = torch.from_numpy(r["xo"].astype(np.int64)).to(dev), torch.from_numpy(r["yo"].astype(np.int64)).to(dev)
+    runs = []
+    al.ctx.set_option("chunk_pairs", 16)
+    try:
+        for timing in (False, True):
+            d_out = torch.zeros(P * 64, dtype=torch.uint8, device=dev)
+            d_ops = torch.zeros(P * stride, dtype=torch.uint8, device=dev)
+            al.ctx.enable_timing(timing)
+            al.align_dev(MODES["custom"], P, dx.data_ptr(), dxo.data_ptr(), dy.data_ptr(), dyo.data_ptr(), d_out.data_ptr(),
+                         d_ops.data_ptr(), stride)
+            t = al.ctx.timing()
+            runs.append((d_out.cpu().numpy().view(_lib.ALN_DTYPE).copy(), d_ops.cpu().numpy().reshape(P, stride).copy(), t))
+    finally:
+        al.ctx.enable_timing(False)  # (the default ctx is shared between Aligners)
+        al.ctx.set_option("chunk_pairs", 0)
+    (rec0, ops0, t0), (rec1, ops1, t1) = runs
+    assert t0["fill_launches"] == t0["traceback_launches"] == 0
+    assert t1["fill_launches"] == t1["traceback_launches"] == 5
+    assert rec1.tobytes() == rec0.tobytes() and (ops1 == ops0).all()
+    for f in RECORD_FIELDS:
+        assert (rec1[f] == r["out"][f]).all(), f
+    for p in range(P):
+        k_, o_ = int(rec1["n_ops"][p]), int(r["out"]["ops_off"][p])
+        assert int(rec1["ops_off"][p]) == (p + 1) * stride - k_
+        assert (ops1[p, stride - k_:] == r["ops"][o_:o_ + k_]).all(), p
