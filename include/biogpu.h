@@ -534,6 +534,49 @@ int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg
                                      uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
                                      uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
                                      uint64_t ops_stride, uint64_t* totals, void* stream);
+/* Seeds from the SMEMs of an FMD index, both strands in one seeding pass.  The handle is an FMD index over T$R$ (T: the
+ * forward text of n_t = (n - 2) / 2 symbols, which may itself hold '$' between sequences; R = revcomp(T); the check K7 makes,
+ * else BG_ERR_UNSUPPORTED) with its text attached, all n bytes of T$R$ (n odd or n < 2: BG_ERR_INVALID_ARG), and a raw or
+ * sampled suffix array.  Fixed seed windows miss a read that has an error in every window; its exact stretches between the
+ * errors are SMEMs, and over T$R$ the rows of an SMEM's interval in the T half place the read, those in the R half its
+ * revcomp.  The definition (stated on the CPU by tests/smem_seed_oracle.py):
+ *   seeds        the records of FMDIndex::all_smems(read, min_seed_len) (fmindex.rs:479-501) on the caller's read, once per
+ *                read (not again on its revcomp), in the reference's push order: a BiInterval {lower, lower_rev, size,
+ *                match_size}, a position a on the read and a length len.  Only the first max_smems records are used; if a read
+ *                has more, the call still answers every read from those and returns BG_ERR_OPS_CAP (bg_fmd_smems_batch's
+ *                convention for its cap).  A read on which the reference would panic (K7's count 0xFFFFFFFF) does not vote:
+ *                the call returns BG_ERR_OUT_OF_ALPHABET with every read answered; this error takes precedence over
+ *                BG_ERR_OPS_CAP;
+ *   votes        a record votes when 1 <= size <= max_occ;
+ *   locate       Interval::occ of [lower, lower + size) (BiInterval::forward()), through K6 unchanged;
+ *   proposals    text position p of a voting record, L the read's length:
+ *                  forward half   p + len <= n_t: the read starts at s = p - a (dropped if p < a);
+ *                  reverse half   p >= n_t + 1 and p + len <= 2 n_t + 1, q = p - n_t - 1: revcomp(read) starts on the forward
+ *                                 text at s = n_t + a - q - L (dropped if q + L > n_t + a);
+ *                anything else is dropped (a hit across a sentinel, which only a read that holds '$' can have, BG_SA_NONE,
+ *                BG_SA_PANIC), and so are s >= n_t and a proposal of a strand that `strands` excludes;
+ *   after that   the strands call word for word with n_text = n_t: per (read, strand) the starts are sorted, equal ones and
+ *                those within pad / 2 of the last start kept are merged; windows [max(0, s - pad), min(n_t, s + L + pad));
+ *                Aligner::semiglobal; best hit (highest score, forward on a tie between strands, smallest s within one).
+ * n_seed_hits: the suffix-array rows of the read's voting records that fall in the half (as the two conditions above define
+ * it) of a strand that ran; totals[0]: every row K6 resolved; totals[1]: candidates aligned.  Limits: max_smems * max_occ <=
+ * 1024 (else BG_ERR_UNSUPPORTED), a zero min_seed_len / max_smems / max_occ is BG_ERR_INVALID_ARG, pad <= 65535, reads of up to
+ * 65534 bases (K7's limit; longer: BG_ERR_TOO_LARGE); indexes with 32-bit and with 64-bit positions.  Arguments, slots, the
+ * ops_stride rule, passes (seed_chunk_reads) and the two totals are those of bg_seed_extend_strands_batch[_dev]; the device
+ * flavour waits once more per pass, for the check of the reads' lengths against max_read_len that K7's scratch depends on. */
+typedef struct {
+    uint32_t min_seed_len;  /* l of FMDIndex::all_smems(read, l), fmindex.rs:479-501; >= 1 */
+    uint32_t max_smems;     /* records used per read, in the reference's push order; >= 1 */
+    uint32_t max_occ;       /* an SMEM whose BiInterval.size exceeds this does not vote; >= 1 */
+    uint32_t pad;           /* as bg_seed_params_t.pad */
+} bg_smem_seed_params_t;
+int bg_seed_extend_smem_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_smem_seed_params_t* prm, uint32_t strands,
+                              uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                              uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+int bg_seed_extend_smem_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_smem_seed_params_t* prm, uint32_t strands,
+                                  uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                  bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops, uint64_t ops_stride,
+                                  uint64_t* totals, void* stream);
 /* Read pairs.  Paired-end reads come as two mates per DNA fragment, read towards each other from opposite strands.  The
  * reads are interleaved mates: read 2p is mate 1 of pair p, read 2p + 1 its mate 2 (2 n_pairs + 1 offsets; an interleaved
  * FASTQ parsed by bg_fastq_parse[_dev] gives this layout).

@@ -685,6 +685,40 @@ public:
         }
         return res;
     }
+    // Seeds from SMEMs (bg_seed_extend_smem_batch): this index is an FMD index over T$R$ with all of T$R$ attached as its text; the
+    // records of FMDIndex::all_smems(read, min_seed_len) seed both strands in one pass.  Hits as seed_extend_batch_strands, in
+    // coordinates of the forward text T.  allow_truncated: a read with more than max_smems records is answered from the first
+    // max_smems instead of raising.
+    std::vector<StrandedSeedHit> seed_extend_batch_smem(const alignment::pairwise::Scoring& scoring, const std::vector<Text>& reads,
+                                                        uint32_t strands = BG_STRAND_BOTH, uint32_t min_seed_len = 19, uint32_t max_smems = 16,
+                                                        uint32_t max_occ = 16, uint32_t pad = 25, bool allow_truncated = false) const {
+        std::vector<int32_t> table;
+        const bg_scoring_t sc = scoring.to_c(table);
+        const bg_smem_seed_params_t prm = {min_seed_len, max_smems, max_occ, pad};
+        Text buf;
+        std::vector<uint64_t> off{0};
+        for (auto& r : reads) {
+            buf.insert(buf.end(), r.begin(), r.end());
+            off.push_back(buf.size());
+        }
+        std::vector<bg_seed_hit_t> hits(reads.size());
+        std::vector<uint8_t> strand(reads.size());
+        std::vector<uint8_t> ops(2 * buf.size() + (2 * (size_t)pad + 4) * reads.size() + 8);
+        uint64_t used = 0;
+        const int rc = bg_seed_extend_smem_batch(h_, &sc, &prm, strands, reads.size(), buf.data(), off.data(), hits.data(), strand.data(),
+                                                 ops.data(), ops.size(), &used);
+        if (rc == BG_ERR_OUT_OF_ALPHABET) throw Panic("index out of bounds: a read holds a byte all_smems panics on");
+        if (!(rc == BG_ERR_OPS_CAP && allow_truncated)) check(rc, "bg_seed_extend_smem_batch");
+        std::vector<StrandedSeedHit> res(reads.size());
+        for (size_t r = 0; r < reads.size(); r++) {
+            if (hits[r].aln.score != BG_MIN_SCORE) res[r].alignment = alignment::pairwise::detail::to_alignment(hits[r].aln, ops.data());
+            res[r].ref_start = (size_t)hits[r].ref_start;
+            res[r].ref_end = (size_t)hits[r].ref_end;
+            res[r].n_candidates = hits[r].n_candidates;
+            res[r].reverse = strand[r] == BG_HIT_REVERSE;
+        }
+        return res;
+    }
     // Read pairs (bg_seed_extend_pairs_batch): reads[2p], reads[2p + 1] are the two mates of pair p.  Each mate is mapped on both
     // strands; where the best proper FR combination (span in min_span ..= max_span) gives up at most pen_unpaired of score
     // against the mates' own bests, both mates report it and `proper` is set; otherwise each mate reports its strands-call hit.

@@ -82,6 +82,14 @@ class SeedParamsC(C.Structure):
     _fields_ = [("seed_len", C.c_uint32), ("stride", C.c_uint32), ("max_occ", C.c_uint32), ("pad", C.c_uint32)]
 
 
+# bg_smem_seed_params_t (bg_seed_extend_smem_batch[_dev])
+class SMEM_SEED_PARAMS(C.Structure):
+    _fields_ = [("min_seed_len", C.c_uint32), ("max_smems", C.c_uint32), ("max_occ", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(SMEM_SEED_PARAMS) == 16, C.sizeof(SMEM_SEED_PARAMS)
+
+
 # bg_pair_params_t (bg_seed_extend_pairs_batch[_dev])
 class PAIR_PARAMS(C.Structure):
     _fields_ = [("min_span", C.c_uint32), ("max_span", C.c_uint32), ("pen_unpaired", C.c_int32)]
@@ -153,6 +161,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_last_fill_framed", "bg_pack2_host",
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
+           "bg_seed_extend_smem_batch", "bg_seed_extend_smem_batch_dev",
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
            "bg_seed_extend_pairs_rescue_batch", "bg_seed_extend_pairs_rescue_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
@@ -273,6 +282,10 @@ def lib():
                                                    C.POINTER(u64)]
         L.bg_seed_extend_strands_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), u32, u64, vp, vp, u32, vp, vp,
                                                        vp, u64, vp, vp]
+        L.bg_seed_extend_smem_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SMEM_SEED_PARAMS), u32, u64, vp, vp, vp, vp, vp, u64,
+                                                C.POINTER(u64)]
+        L.bg_seed_extend_smem_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SMEM_SEED_PARAMS), u32, u64, vp, vp, u32, vp, vp,
+                                                    vp, u64, vp, vp]
         L.bg_seed_extend_pairs_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp, vp,
                                                  vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_pairs_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp,

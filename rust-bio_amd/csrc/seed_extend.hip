@@ -22,6 +22,8 @@
 //   S3 K6               Interval::occ of every voting interval                          -> text positions
 //   S4 propose          one wavefront per read: s = pos - seed offset, sort, dedup      -> per-read candidate lists
 //      (scan of the per-read candidate / x-byte / y-byte counts; the three totals are the SECOND host round trip)
+//      SMEM mode (SeedCall::smem, seed_smem.hip) instead of S1, S2, S4: a length check with a host round trip of its own, S1' K7
+//      over the caller's reads, S2' votes of the record slots, S4' one wavefront per caller read proposes for both strands
 //   se_align
 //   S5 gather           (read, text window) pairs, offsets                              -> x, x_off, y, y_off
 //   S6 align            Aligner::semiglobal on every candidate (bg_align_batch_dev)      -> records + operations
@@ -46,7 +48,8 @@ enum SeedBuf {
     kVotes,                // S1 writes the seeds' matched lengths here (not read), S2 the votes over them
     kHitOff,               // S2: scan of the votes
     kScanPartials,         // bg_scan_u32's own scratch, every scan of a pass
-    kFlags,                // 64 bytes: bit 0 a seed out of the alphabet, bit 1 a read longer than max_read_len
+    kFlags,                // 64 bytes: bit 0 a seed out of the alphabet, bit 1 a read longer than max_read_len, bit 2 (SMEM mode) a
+                           // read with more than max_smems records
     kPos,                  // S3: text positions; S4 leaves each read's candidate starts at the front of its slice
     kPerReadCounts,        // S4: n_cand | n_hits | x_bytes | y_bytes per virtual read
     kPerReadOffsets,       // their scans: coff | xoff | yoff
@@ -59,6 +62,8 @@ enum SeedBuf {
     kPerPairOffsets,       // their scans: roff | xoff | yoff
     kRescueX, kRescueY, kRescueOff, kRescueAln, kRescueOps,  // R2, R3: as kX .. kCandOps, for the rescue alignments
     kRescuedCount,         // 64 bytes: the call's rescued pairs (totals[3])
+    kSmemCount, kSmemRec,  // S1': K7's count per caller read and its max_smems records of six uint64
+    kStartOff,             // S4': where each virtual read's kept starts begin in kPos
     kSeedBufs
 };
 struct bg_seed_scratch {
@@ -221,12 +226,14 @@ __global__ __launch_bounds__(64) void se_propose_kernel(SeedPrm prm, uint64_t n_
     }
 }
 
-// S5: one wavefront per read: the (read, window) pairs of its candidates + their offsets
+// S5: one wavefront per read: the (read, window) pairs of its candidates + their offsets.  The read's starts are pos[soff[r *
+// soff_stride] + c]: its hits' first slot where S4 left them (soff = hoff, soff_stride = S), or the array S4' wrote.
 __global__ __launch_bounds__(64) void se_gather_kernel(SeedPrm prm, uint64_t n_reads, const uint8_t* __restrict__ reads,
                                                        const uint64_t* __restrict__ read_off, const uint8_t* __restrict__ text,
-                                                       const uint64_t* __restrict__ hoff, const uint64_t* __restrict__ pos,
-                                                       const uint64_t* __restrict__ coff, const uint64_t* __restrict__ xoff,
-                                                       const uint64_t* __restrict__ yoff, uint8_t* __restrict__ x,
+                                                       const uint64_t* __restrict__ soff, uint32_t soff_stride,
+                                                       const uint64_t* __restrict__ pos, const uint64_t* __restrict__ coff,
+                                                       const uint64_t* __restrict__ xoff, const uint64_t* __restrict__ yoff,
+                                                       uint8_t* __restrict__ x,
                                                        uint64_t* __restrict__ x_off, uint8_t* __restrict__ y, uint64_t* __restrict__ y_off,
                                                        uint64_t* __restrict__ w_lo) {
     const uint64_t r = blockIdx.x;
@@ -241,7 +248,7 @@ __global__ __launch_bounds__(64) void se_gather_kernel(SeedPrm prm, uint64_t n_r
     if (!nc) return;
     const uint64_t ro = read_off[r];
     const uint32_t L = (uint32_t)(read_off[r + 1] - ro);
-    const uint64_t h0 = hoff[r * prm.S];
+    const uint64_t h0 = soff[r * soff_stride];
     uint64_t yo = yoff[r];
     for (uint32_t c = 0; c < nc; c++) {
         const uint64_t v = pos[h0 + c];
@@ -381,6 +388,7 @@ namespace {
 //   pairq        with pair: one `multi` record per mate
 //   rescue       with pair: `rescued` one byte per pair, `totals` 4 entries (otherwise 2)
 //   multi_prm    multi mode: hits / strand / ops hold max_hits slots per read, `multi` one record per read
+//   smem         SMEM mode: seeds are the SMEMs of the caller's reads on an FMD index, `prm` is null
 struct SeedCall {
     bg_fm* fm = nullptr;
     const bg_scoring_t* sc = nullptr;
@@ -402,7 +410,9 @@ struct SeedCall {
     const bg_multi_params_t* multi_prm = nullptr;
     const bg_rescue_params_t* rescue = nullptr;
     const bg_pairq_params_t* pairq = nullptr;
+    const bg_smem_seed_params_t* smem = nullptr;
     void* stream = nullptr;
+    uint32_t pad() const { return smem ? smem->pad : prm->pad; }
 };
 
 // consecutive arrays out of one scratch buffer
@@ -423,6 +433,7 @@ struct SeedRun {
     bg_ctx* ctx = nullptr;
     hipStream_t st = nullptr;
     SeedPrm prm = {};
+    SeedSmemPrm smem = {};  // SMEM mode
     uint32_t G = 1;         // virtual reads per read
     bool virt = false;      // the virtual reads are materialised (S0)
     uint32_t win_max = 0;   // the longest candidate window
@@ -443,6 +454,8 @@ struct SeedPassRun {
     const uint8_t* vreads;    // the virtual reads and their nv + 1 offsets
     const uint64_t* roff;
     uint64_t* hoff;           // S2
+    const uint64_t* soff;     // S4: virtual read v's kept starts begin at pos[soff[v * soff_stride]]
+    uint32_t soff_stride;
     uint64_t* pos;            // S3, S4
     uint32_t* n_hits;         // S4: per virtual read, and the scans of its other counts
     SeedXYOff off;
@@ -453,7 +466,7 @@ struct SeedPassRun {
 
 // S0-S4: seeds -> votes -> text positions -> per-read candidate lists.  Two host round trips: the hit total with the flag word
 // (sizes the position array), then the candidate / x-byte / y-byte totals (size the aligner's input).
-int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
+int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic, bool* any_truncated) {
     int rc;
     const SeedCall& c = R.call;
     const uint64_t nv = p.nv, nq = p.nq;
@@ -471,6 +484,13 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
     uint32_t* d_flags = R.buf<uint32_t>(kFlags);
     p.hoff = R.buf<uint64_t>(kHitOff);
     BG_HIP(hipMemsetAsync(d_flags, 0, 8, R.st));
+    if (c.smem) {
+        // K7 sizes its interval lists by max_read_len: a longer read (the caller's error) ends the call before it runs
+        if ((rc = bg_seed_smem_lengths_launch(p.nr, c.read_off + p.r0, c.max_read_len, d_flags, R.st))) return rc;
+        BG_HIP(hipMemcpyAsync(&R.W.h_tot[4], d_flags, 8, hipMemcpyDeviceToHost, R.st));
+        BG_HIP(hipStreamSynchronize(R.st));
+        if (R.W.h_tot[4] & kFlagLongRead) return BG_ERR_INVALID_ARG;
+    }
     // ---- S0: the virtual reads and their offsets, relative to the pass's first read
     p.vreads = c.reads;
     p.roff = c.read_off + p.r0;
@@ -490,7 +510,16 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
         p.roff = d_voff;
     }
     // ---- S1/S2: seeds -> votes -> hit offsets
-    if (R.prm.S) {
+    const uint64_t* d_rec = nullptr;
+    if (c.smem) {
+        // S1', S2': the SMEMs of the pass's caller reads (not of their revcomps: the index holds both strands)
+        if ((rc = R.need(kSmemCount, p.nr * 4))) return rc;
+        if ((rc = R.need(kSmemRec, nq * 6 * 8))) return rc;
+        d_rec = R.buf<uint64_t>(kSmemRec);
+        if ((rc = bg_seed_smem_seeds_launch(c.fm, R.smem, c.smem->min_seed_len, p.nr, c.reads, c.read_off + p.r0, c.max_read_len,
+                                            R.buf<uint32_t>(kSmemCount), R.buf<uint64_t>(kSmemRec), d_votes, d_lo, d_flags, R.st)))
+            return rc;
+    } else if (R.prm.S) {
         if ((rc = bg_fm_search_seeds_dev(c.fm, nv, p.vreads, p.roff, R.prm.S, R.prm.stride, R.prm.seed_len, d_tag, d_lo, d_hi, d_matched_len,
                                          R.st)))
             return rc;
@@ -503,8 +532,9 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
     BG_HIP(hipMemcpyAsync(&R.W.h_tot[4], d_flags, 8, hipMemcpyDeviceToHost, R.st));
     BG_HIP(hipStreamSynchronize(R.st));  // sizes the position array
     p.n_sa_rows = R.W.h_tot[0];
-    if (R.W.h_tot[4] & 1) *any_panic = true;
-    if (R.W.h_tot[4] & 2) return BG_ERR_INVALID_ARG;  // a read longer than max_read_len (S0 kept within its scratch)
+    if (R.W.h_tot[4] & kFlagPanic) *any_panic = true;
+    if (R.W.h_tot[4] & kFlagTruncated) *any_truncated = true;
+    if (R.W.h_tot[4] & kFlagLongRead) return BG_ERR_INVALID_ARG;  // a read longer than max_read_len (S0 kept within its scratch)
     // ---- S3: Interval::occ of the voting intervals
     if ((rc = R.need(kPos, p.n_sa_rows * 8))) return rc;
     p.pos = R.buf<uint64_t>(kPos);
@@ -518,7 +548,15 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic) {
     uint32_t *d_xb = counts.take<uint32_t>(nv), *d_yb = counts.take<uint32_t>(nv);
     uint64_t *d_coff = offsets.take<uint64_t>(nv + 1), *d_xoff = offsets.take<uint64_t>(nv + 1), *d_yoff = offsets.take<uint64_t>(nv + 1);
     p.off = SeedXYOff{d_coff, d_xoff, d_yoff};
-    if (c.fm->wide)
+    p.soff = p.hoff, p.soff_stride = R.prm.S;
+    if (c.smem) {
+        if ((rc = R.need(kStartOff, nv * 8))) return rc;
+        uint64_t* d_soff = R.buf<uint64_t>(kStartOff);
+        p.soff = d_soff, p.soff_stride = 1;
+        if ((rc = bg_seed_smem_propose_launch(c.fm->wide, R.smem, p.nr, c.read_off + p.r0, p.hoff, d_rec, p.pos, d_soff, d_nc, p.n_hits, d_xb,
+                                              d_yb, R.st)))
+            return rc;
+    } else if (c.fm->wide)
         se_propose_kernel<uint64_t><<<dim3((unsigned)nv), dim3(64), 0, R.st>>>(R.prm, nv, p.roff, p.hoff, p.pos, d_nc, p.n_hits, d_xb, d_yb);
     else
         se_propose_kernel<uint32_t><<<dim3((unsigned)nv), dim3(64), 0, R.st>>>(R.prm, nv, p.roff, p.hoff, p.pos, d_nc, p.n_hits, d_xb, d_yb);
@@ -550,8 +588,8 @@ int se_align(SeedRun& R, SeedPassRun& p) {
     uint64_t* d_wlo = R.buf<uint64_t>(kWLo);
     bg_alignment_t* d_aln = R.buf<bg_alignment_t>(kAln);
     uint8_t* d_cops = c.ops ? R.buf<uint8_t>(kCandOps) : nullptr;
-    se_gather_kernel<<<dim3((unsigned)p.nv), dim3(64), 0, R.st>>>(R.prm, p.nv, p.vreads, p.roff, (const uint8_t*)c.fm->d_text, p.hoff, p.pos,
-                                                                  p.off.roff, p.off.xoff, p.off.yoff, xy.x, xy.x_off, xy.y, xy.y_off, d_wlo);
+    se_gather_kernel<<<dim3((unsigned)p.nv), dim3(64), 0, R.st>>>(R.prm, p.nv, p.vreads, p.roff, (const uint8_t*)c.fm->d_text, p.soff, p.soff_stride,
+                                                                  p.pos, p.off.roff, p.off.xoff, p.off.yoff, xy.x, xy.x_off, xy.y, xy.y_off, d_wlo);
     BG_HIP(hipGetLastError());
     if (p.C && (rc = bg_align_batch_dev_hint(R.ctx, c.sc, BG_MODE_SEMIGLOBAL, p.C, xy.x, xy.x_off, xy.y, xy.y_off, c.max_read_len, R.win_max,
                                              d_aln, d_cops, cstride, R.st, -1)))
@@ -633,12 +671,23 @@ int se_rescue(SeedRun& R, SeedPassRun& p) {
 
 // The call's checks, its passes, its totals.
 int se_run(const SeedCall& c) {
-    if (!c.fm || !c.sc || !c.prm || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
+    if (!c.fm || !c.sc || (!c.prm && !c.smem) || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
+    const uint64_t n_index = c.fm->wide ? c.fm->wdev.n : (uint64_t)c.fm->dev.n;
+    if (c.smem) {  // an FMD index over T$R$ (FMDIndex::from's assert, as K7 checks it)
+        if (!c.fm->fmd_ok) return BG_ERR_UNSUPPORTED;
+        if (n_index < 2 || n_index % 2) return BG_ERR_INVALID_ARG;
+    }
     if (!c.fm->d_text || c.fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
-    if (c.prm->seed_len == 0 || c.prm->stride == 0 || c.prm->max_occ == 0) return BG_ERR_INVALID_ARG;
-    if (c.max_read_len > 65535 || c.prm->pad > 65535) return BG_ERR_TOO_LARGE;
+    if (c.smem) {
+        if (c.smem->min_seed_len == 0 || c.smem->max_smems == 0 || c.smem->max_occ == 0) return BG_ERR_INVALID_ARG;
+        if ((uint64_t)c.smem->max_smems * c.smem->max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
+    } else if (c.prm->seed_len == 0 || c.prm->stride == 0 || c.prm->max_occ == 0) {
+        return BG_ERR_INVALID_ARG;
+    }
+    if (c.max_read_len > 65535 || c.pad() > 65535) return BG_ERR_TOO_LARGE;
+    if (c.smem && c.max_read_len > 65534) return BG_ERR_TOO_LARGE;  // K7's own limit
     if (c.rescue && c.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
-    const uint32_t win_max = c.max_read_len + 2 * c.prm->pad;
+    const uint32_t win_max = c.max_read_len + 2 * c.pad();
     const uint32_t rwin_max = c.rescue ? c.pair->max_span : 0;
     if (c.ops && c.ops_stride < (uint64_t)c.max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
     if (c.totals) c.totals[0] = c.totals[1] = 0;
@@ -648,26 +697,32 @@ int se_run(const SeedCall& c) {
     hipStream_t st = (hipStream_t)c.stream;
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);  // ctx->seed is one scratch set: calls on other streams wait for this one's last kernel
-    SeedPrm prm;
-    prm.S = c.max_read_len >= c.prm->seed_len ? (c.max_read_len - c.prm->seed_len) / c.prm->stride + 1 : 0;
-    prm.stride = c.prm->stride;
-    prm.seed_len = c.prm->seed_len;
-    prm.max_occ = c.prm->max_occ;
-    prm.pad = c.prm->pad;
-    prm.n_text = c.fm->n_text;
-    if (prm.S > 64 || (uint64_t)prm.S * prm.max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
+    SeedPrm prm = {};
+    SeedSmemPrm smem = {};
+    if (c.smem) {  // the slots of a read are its max_smems records; the text the windows are cut from is T, the first half
+        smem = SeedSmemPrm{c.smem->max_smems, c.smem->max_occ, c.smem->pad, c.strands, (n_index - 2) / 2};
+        prm.S = smem.M, prm.max_occ = smem.max_occ, prm.pad = smem.pad, prm.n_text = smem.n_t;
+    } else {
+        prm.S = c.max_read_len >= c.prm->seed_len ? (c.max_read_len - c.prm->seed_len) / c.prm->stride + 1 : 0;
+        prm.stride = c.prm->stride;
+        prm.seed_len = c.prm->seed_len;
+        prm.max_occ = c.prm->max_occ;
+        prm.pad = c.prm->pad;
+        prm.n_text = c.fm->n_text;
+        if (prm.S > 64 || (uint64_t)prm.S * prm.max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
+    }
     if (!ctx->seed) ctx->seed = new bg_seed_scratch();
     bg_seed_scratch& W = *ctx->seed;
     if (!W.h_tot) BG_HIP(hipHostMalloc((void**)&W.h_tot, 64, hipHostMallocDefault));
     const uint32_t G = c.strands == BG_STRAND_BOTH ? 2 : 1;
     SeedRun R{c, W};
-    R.ctx = ctx, R.st = st, R.prm = prm, R.G = G, R.win_max = win_max, R.rwin_max = rwin_max;
+    R.ctx = ctx, R.st = st, R.prm = prm, R.smem = smem, R.G = G, R.win_max = win_max, R.rwin_max = rwin_max;
     R.virt = c.strands == BG_STRAND_REVERSE || c.strands == BG_STRAND_BOTH;
     R.out.hits = c.hits, R.out.ops = c.ops, R.out.ops_stride = c.ops_stride, R.out.strand = c.strand;
     R.out.pairs = c.pairs, R.out.multi = c.multi, R.out.rescued = c.rescued;
     int rc;
     uint64_t done_hits = 0, done_cand = 0, done_rescue = 0;
-    bool any_panic = false;
+    bool any_panic = false, any_truncated = false;
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
     // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size).  The option counts the caller's reads;
     // in pair mode it is rounded down to whole pairs (at least one), and so are the equal passes.
@@ -680,8 +735,8 @@ int se_run(const SeedCall& c) {
         p.r0 = r0;
         p.nr = std::min(chunk, c.n_reads - r0);
         p.nv = G * p.nr;
-        p.nq = p.nv * std::max<uint32_t>(prm.S, 1);
-        if ((rc = se_candidates(R, p, &any_panic))) return rc;
+        p.nq = (c.smem ? p.nr : p.nv) * std::max<uint32_t>(prm.S, 1);
+        if ((rc = se_candidates(R, p, &any_panic, &any_truncated))) return rc;
         if ((rc = se_align(R, p))) return rc;
         if ((rc = c.rescue ? se_rescue(R, p) : se_reduce(R, p))) return rc;
         done_hits += p.n_sa_rows;
@@ -705,7 +760,9 @@ int se_run(const SeedCall& c) {
     }
     // a seed that reaches a byte outside the alphabet makes the reference's backward_search panic; here it does not
     // vote, every read is still answered, and the call says so
-    return any_panic ? BG_ERR_OUT_OF_ALPHABET : BG_OK;
+    // (SMEM mode: a read the reference's all_smems panics on does not vote either; a read with more than max_smems records was
+    // answered from the first max_smems, K7's convention for its cap)
+    return any_panic ? BG_ERR_OUT_OF_ALPHABET : any_truncated ? BG_ERR_OPS_CAP : BG_OK;
 }
 
 // the mode calls' own argument checks; every other one is se_run's
@@ -748,6 +805,18 @@ extern "C" int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* s
     if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
     SeedCall c;
     c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand;
+    return se_run(c);
+}
+
+extern "C" int bg_seed_extend_smem_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_smem_seed_params_t* prm, uint32_t strands,
+                                             uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                             bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops, uint64_t ops_stride,
+                                             uint64_t* totals, void* stream) {
+    if (!prm || strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.smem = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
     c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
     c.strand = d_strand;
     return se_run(c);
@@ -836,7 +905,7 @@ namespace {
 // stream are not set).  The same call runs on device copies; then the reported hits' operations are compacted into ops_buf in
 // slot order (multi mode: max_hits slots per read).
 int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
-    if (!h.fm || !h.sc || !h.prm || (h.n_reads && (!h.read_off || !h.hits))) return BG_ERR_INVALID_ARG;
+    if (!h.fm || !h.sc || (!h.prm && !h.smem) || (h.n_reads && (!h.read_off || !h.hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (h.n_reads == 0) return BG_OK;
     bg_ctx* ctx = h.fm->ctx;
@@ -847,7 +916,7 @@ int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t*
     if (max_len > 65535) return BG_ERR_TOO_LARGE;
     if (h.rescue && h.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
     // (rescue call: a slot also holds the operations of a read against a rescue window of max_span bytes)
-    const uint64_t stride = ops_buf ? max_len + std::max<uint64_t>(max_len + 2 * (uint64_t)h.prm->pad, h.rescue ? h.pair->max_span : 0) + 4 : 0;
+    const uint64_t stride = ops_buf ? max_len + std::max<uint64_t>(max_len + 2 * (uint64_t)h.pad(), h.rescue ? h.pair->max_span : 0) + 4 : 0;
     const uint64_t n_slots = n_reads * (h.multi_prm ? h.multi_prm->max_hits : 1);
     const uint64_t bytes = h.read_off[n_reads], n_pairs = n_reads / 2;
     std::vector<uint8_t> h_ops;
@@ -871,7 +940,8 @@ int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t*
         BG_HIP(hipMemcpyAsync(d_off, h.read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         d.reads = d_reads, d.read_off = d_off;
         int rc = se_run(d);
-        if (rc && rc != BG_ERR_OUT_OF_ALPHABET) return rc;
+        // (every read is answered under these two; the stride above is the call's own, so BG_ERR_OPS_CAP is the SMEM cap's)
+        if (rc && rc != BG_ERR_OUT_OF_ALPHABET && !(rc == BG_ERR_OPS_CAP && h.smem)) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(h.hits, d.hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
         if (h.strand) BG_HIP(hipMemcpyAsync(h.strand, d.strand, n_slots, hipMemcpyDeviceToHost, st));
@@ -926,6 +996,16 @@ extern "C" int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, c
     if (strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
     SeedCall c;
     c.fm = fm, c.sc = sc, c.prm = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
+}
+
+extern "C" int bg_seed_extend_smem_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_smem_seed_params_t* prm, uint32_t strands,
+                                         uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                         uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (!prm || strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.smem = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
     c.hits = hits, c.strand = strand;
     return se_run_host(c, ops_buf, ops_cap, ops_used);
 }

@@ -1,6 +1,7 @@
 // One pass of seed-and-extend as its reduction stages see it (seed_pairs.hip, seed_pairq.hip, seed_multi.hip, seed_rescue.hip,
 // seed_rescueq.hip, and se_best_kernel of seed_extend.hip): what stages S0-S6 of seed_extend.hip left in the pass scratch
 // (SeedPass), where the answers go (SeedOut), and the launchers of the stages, which take these two plus what is their own.
+// The SMEM-seeded call's candidate stages (seed_smem.hip) are declared here as well.
 #ifndef BG_SEED_PASS_H
 #define BG_SEED_PASS_H
 #include "fm_kernels.h"
@@ -67,6 +68,28 @@ struct SeedRescueAln {
 
 }  // namespace bgseed
 
+// seed_smem.hip: the SMEM-seeded call's own stages (bg_seed_extend_smem_batch).  The pass has nr caller reads with M = max_smems
+// record slots each; read r's records are rec[(r * M + t) * 6 ..], six uint64 as bg_fmd_smems_batch64_dev writes them.
+namespace bgseed {
+struct SeedSmemPrm {
+    uint32_t M, max_occ, pad, strands;  // max_smems; BG_STRAND_*
+    uint64_t n_t;                       // length of the forward text: the index is over T$R$, 2 n_t + 2 symbols
+};
+// bits of the pass's flag word
+constexpr uint32_t kFlagPanic = 1, kFlagLongRead = 2, kFlagTruncated = 4;
+}  // namespace bgseed
+// a read longer than max_read_len sets kFlagLongRead (K7 sizes its interval lists by max_read_len: checked before it runs)
+int bg_seed_smem_lengths_launch(uint64_t nr, const uint64_t* d_read_off, uint32_t max_read_len, uint32_t* d_flags, hipStream_t st);
+// S1', S2': K7 (all_smems, uint64 records) over the reads, then per slot its votes and its interval's first row; a read K7
+// marks as a panic sets kFlagPanic, one with more than M records kFlagTruncated
+int bg_seed_smem_seeds_launch(bg_fm* fm, const bgseed::SeedSmemPrm& prm, uint32_t min_seed_len, uint64_t nr, const uint8_t* d_reads,
+                              const uint64_t* d_read_off, uint32_t max_read_len, uint32_t* d_count, uint64_t* d_rec, uint32_t* d_votes,
+                              uint64_t* d_lower, uint32_t* d_flags, hipStream_t st);
+// S4': hits -> (strand, start) proposals, sorted and merged per strand; read r's kept starts go back over pos from hoff[r * M]
+// on, the forward strand's first; per virtual read (G r + g): where its starts begin (soff), candidates, hits, x and y bytes
+int bg_seed_smem_propose_launch(bool wide, const bgseed::SeedSmemPrm& prm, uint64_t nr, const uint64_t* d_read_off, const uint64_t* d_hoff,
+                                const uint64_t* d_rec, uint64_t* d_pos, uint64_t* d_soff, uint32_t* d_n_cand, uint32_t* d_n_hits,
+                                uint32_t* d_x_bytes, uint32_t* d_y_bytes, hipStream_t st);
 // seed_pairs.hip: S7 of the paired call: hits, strand and operations of reads r0 + 2p, r0 + 2p + 1 and pairs[r0 / 2 + p].
 int bg_seed_pairs_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, hipStream_t st);
 // seed_pairq.hip: S7 of the pairs-mapq call: what bg_seed_pairs_launch writes, plus multi[r0 + 2p], multi[r0 + 2p + 1].

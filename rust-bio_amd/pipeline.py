@@ -9,7 +9,8 @@ the reverse strand (its `dna::revcomp`), or on both, and say which strand won.  
 paired-end reads and report the best proper FR pair where there is one; the `_pairs_rescue` calls also look for a mate without a
 seeded candidate inside its partner's insert window; the `_pairs_mapq` calls add a MAPQ per mate, judged against the pair.  The
 `_multi` calls report up to K loci per read that
-do not touch, the runner-up's score and a MAPQ.  This module only marshals arguments."""
+do not touch, the runner-up's score and a MAPQ.  The `_smem` calls take an FMD index over T$R$ and seed both strands with the
+SMEMs of each read (`FMDIndex::all_smems`) instead of fixed windows.  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -24,6 +25,17 @@ class SeedParams:
 
     def to_c(self):
         return _lib.SeedParamsC(self.seed_len, self.stride, self.max_occ, self.pad)
+
+
+class SmemSeedParams:
+    """bg_smem_seed_params_t: the records of FMDIndex::all_smems(read, min_seed_len) seed the read; the first max_smems of a read
+    are used, one whose interval holds more than max_occ rows does not vote; pad as SeedParams."""
+
+    def __init__(self, min_seed_len=19, max_smems=16, max_occ=16, pad=25):
+        self.min_seed_len, self.max_smems, self.max_occ, self.pad = min_seed_len, max_smems, max_occ, pad
+
+    def to_c(self):
+        return _lib.SMEM_SEED_PARAMS(self.min_seed_len, self.max_smems, self.max_occ, self.pad)
 
 
 class PairParams:
@@ -85,10 +97,11 @@ _OUT_DTYPE = {"strand": np.uint8, "pairs": _lib.PAIR_HIT_DTYPE, "rescued": np.ui
 
 
 def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_out_of_alphabet, modes=(), outs=(), strands=None, K=None,
-               max_span=None):
+               max_span=None, allow_truncated=False):
     """The host-buffer call bg_<stem>_batch, behind the public function <stem>_arrays.  modes: the mode's parameter objects in the call's order; outs: the
     names of its output arrays after `hits`, in the call's order (keys of _OUT_DTYPE); strands: None for a call without that
-    argument; K: slots per read of the multi call; max_span: of a rescue call, whose operation slots also hold a rescue window.
+    argument; K: slots per read of the multi call; max_span: of a rescue call, whose operation slots also hold a rescue window;
+    allow_truncated: of the SMEM call, whose status BG_ERR_OPS_CAP (-9) says that a read had more records than max_smems.
     Returns (hits, *outs, ops)."""
     name = f"bg_{stem}_batch"
     params = params or SeedParams()
@@ -114,7 +127,7 @@ def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_ou
     rc = getattr(_lib.lib(), name)(fm.h, *map(C.byref, structs), *([] if strands is None else [strands]), n // 2 if "pairs" in outs else n,
                                    rd.ctypes.data, off.ctypes.data, hits.ctypes.data, *[a.ctypes.data for a in arrays],
                                    ops.ctypes.data if want_ops else None, cap, C.byref(used))
-    if not (rc == -7 and allow_out_of_alphabet):
+    if not (rc == -7 and allow_out_of_alphabet) and not (rc == -9 and allow_truncated):
         _lib.check(rc, name)
     return (hits, *[a[:size[o]] for a, o in zip(arrays, outs)], ops[:used.value] if want_ops else None)
 
@@ -161,6 +174,26 @@ def seed_extend_strands_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_
     over the strands that ran."""
     _dev_call("seed_extend_strands", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand], d_ops=d_ops,
               ops_stride=ops_stride, params=params, stream=stream, totals=totals, strands=strands)
+
+
+def seed_extend_smem_arrays(fm, scoring, reads, read_off, params=None, strands=_lib.STRAND_BOTH, want_ops=True,
+                            allow_out_of_alphabet=False, allow_truncated=False):
+    """bg_seed_extend_smem_batch, host buffers: `fm` is an FMD index over T$R$ with all of T$R$ attached and a suffix array.
+    Returns (hits, strand, ops) as seed_extend_strands_arrays, in coordinates of the forward text T.  A read on which the
+    reference's all_smems panics raises AlphabetError unless allow_out_of_alphabet (it does not vote); a read with more than
+    params.max_smems records raises BiogpuError (OPS_CAP) unless allow_truncated (its first max_smems records vote).  Every read
+    is answered either way."""
+    return _host_call("seed_extend_smem", fm, scoring, reads, read_off, params=params or SmemSeedParams(), want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet, outs=["strand"], strands=strands, allow_truncated=allow_truncated)
+
+
+def seed_extend_smem_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand=0, d_ops=0, ops_stride=0,
+                         params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
+    """bg_seed_extend_smem_batch_dev (pointers are ints; d_strand / d_ops may be 0); `totals`, if given, is a uint64[2] numpy
+    array that receives (suffix-array rows resolved, candidates aligned).  Raises as seed_extend_smem_arrays without its switches;
+    the slots are written before it does."""
+    _dev_call("seed_extend_smem", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand], d_ops=d_ops,
+              ops_stride=ops_stride, params=params or SmemSeedParams(), stream=stream, totals=totals, strands=strands)
 
 
 def seed_extend_pairs_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, want_ops=True, allow_out_of_alphabet=False):
