@@ -160,7 +160,10 @@ int bg_sa_sample_dev64(bg_ctx* ctx, const uint64_t* d_sa, const uint8_t* d_bwt, 
  * Occ::get's result does not depend on k.  The reference's third argument, the host-built `Occ` table itself,
  * is deliberately NOT part of this signature: the engine ranks on its own packed blocks built from `bwt`, so a
  * Rust shim drops its `Occ` (or never builds it) and passes (bwt, less, k, alphabet) — INTEGRATION.md.  BG_ERR_OUT_OF_ALPHABET when a BWT byte exceeds
- * the alphabet's max symbol (Occ::new would panic, bwt.rs:114). */
+ * the alphabet's max symbol (Occ::new would panic, bwt.rs:114).  The BWT is uploaded and the index laid out on the device
+ * (the builder of bg_fm_build_dev, with the caller's `less` kept): while the call runs it needs n bytes of device memory
+ * for the uploaded BWT plus the builder's count and scan temporaries (about n / 6 bytes), on top of the index; both are
+ * freed before it returns.  Synchronous. */
 int bg_fm_build(bg_ctx* ctx, const uint8_t* bwt, uint64_t n, const uint64_t* less,
                 uint32_t less_len, uint32_t occ_k, const uint8_t* alphabet, uint32_t n_sym,
                 bg_fm** out);

@@ -315,9 +315,6 @@ struct bg_fm {
 int fm_decode_bwt_dev(const bg_fm* fm, uint8_t* d_out, hipStream_t st);  // fm_persist.hip: the handle's BWT bytes
 void fm_remember_inputs(bg_fm* fm, const uint8_t* alphabet, uint32_t n_sym, uint32_t occ_k, const uint64_t* less, uint32_t less_len);
 
-// fm_wide.hip: the index with 64-bit positions (built from a BWT in HBM; `less` null: the BWT's own cumulative counts)
-int fm_wide_build_dev(bg_ctx* ctx, const uint8_t* d_bwt, uint64_t n, const uint8_t* alphabet, uint32_t n_sym, const uint64_t* less,
-                      uint32_t less_len, uint64_t* less_out, bg_fm** out, hipStream_t st);
 // fm_wide.hip: fmw_search2x_kernel, the generic search on 64-bit positions, for one flavour (SeedSrc; DEFER: only the
 // queries tagged kTagDeferred).  fm_index.hip's fm_search decides when it runs.
 template <bool SEEDS, bool PACKED, bool DEFER>

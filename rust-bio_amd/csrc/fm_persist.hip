@@ -3,7 +3,7 @@
 // The reference derives Serialize / Deserialize for what an index is made of — Occ (/root/reference/src/data_structures/
 // bwt.rs:76), FMIndex (fmindex.rs:214), SampledSuffixArray (suffix_array.rs:124) — so that the suffix array, by far the
 // expensive part of construction, is computed once per genome.  Here the device layout is the engine's own and cheap to
-// lay out again (0.06 s per Gbp from a BWT in HBM, fm_index.hip), so what goes to disk is what the reference's FMIndex
+// lay out again (0.06 s per Gbp from a BWT in HBM, fm_build.hip), so what goes to disk is what the reference's FMIndex
 // holds, not the rank blocks: the BWT, less, the alphabet and k, and the suffix array attached to the handle (raw or
 // sampled + the rows kept for the sentinel) — and the text, if the handle owns a copy (seed-and-extend).  bg_fm_load
 // reads the file, rebuilds the index with the builder the sizes call for (the 64-bit layout from 2^32 - 1 symbols on) and
@@ -151,7 +151,7 @@ int fm_decode_bwt_dev(const bg_fm* fm, uint8_t* d_out, hipStream_t st) {
     return BG_OK;
 }
 
-// what a handle has to remember for bg_fm_save (set by bg_fm_build / bg_fm_build_dev, fm_index.hip)
+// what a handle has to remember for bg_fm_save (set by bg_fm_build / bg_fm_build_dev, fm_build.hip)
 void fm_remember_inputs(bg_fm* fm, const uint8_t* alphabet, uint32_t n_sym, uint32_t occ_k, const uint64_t* less, uint32_t less_len) {
     fm->alphabet.assign(alphabet, alphabet + n_sym);
     fm->occ_k = occ_k;

@@ -1,6 +1,6 @@
 // 2-step rank blocks of the FM index (fm_kernels.h: Fm2Dev, block2_part; consumer: fm_search_fast_kernel<STEP2> in
-// fm_index.hip), built on the device from the finished 1-step index — both builders (bg_fm_build: host BWT;
-// bg_fm_build_dev: BWT in HBM) end here.  Reference semantics served: FMIndexable::backward_search
+// fm_index.hip), built on the device from the finished 1-step index — the builder of fm_build.hip (bg_fm_build: host BWT,
+// uploaded; bg_fm_build_dev: BWT in HBM) ends here when less[] is the BWT's own.  Reference semantics served: FMIndexable::backward_search
 // (/root/reference/src/data_structures/fmindex.rs:144-208), two iterations of its loop per block access.
 //
 //   pass 1 (one thread per BWT position i): c = code of L[i]; j = LF(i) = less[c] + Occ(c, i) - 1 — a thread-serial rank

@@ -6,9 +6,8 @@
 // uint32 in five kernels and two builders (rounds 1-4: BG_ERR_TOO_LARGE).  This file is the same search on the layout
 // fm_kernels.h describes under "64-bit positions": the 64-byte blocks of K5 with counters relative to a superblock, one
 // absolute 64-bit base per code and superblock, everything a position can reach in 64 bits.
-//   fm_wide_build_dev   the index from a BWT in HBM (bg_fm_build_dev, and bg_fm_build after an upload): the block kernels
-//                       of fm_index.hip's device builder, a 64-bit scan of the per-block counts, heads relative to the
-//                       superblock's first block
+//   (the index itself is laid out by fm_build.hip, the one builder of both layouts: the block kernel of the narrow index, a
+//    64-bit scan of the per-block counts, heads relative to the superblock's first block)
 //   fmw_search2x_kernel FMIndexable::backward_search (fmindex.rs:144-208), the generic search: two queries per quad, l and r
 //                       64-bit, Occ::get = base[superblock][code] + cnt[code] + popcount; byte, packed and seed-window
 //                       patterns.  fm_index.hip's fm_search decides when it runs: alone, or behind the 2x fast kernel
@@ -21,12 +20,8 @@
 // rank bit vectors, the FMD entry points with 32-bit records, and the counted search (bg_fm_backward_search_count_lines_dev).
 #include <algorithm>
 #include <cstring>
-#include <numeric>
 #include <string.h>
 #include <vector>
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "fm_kernels.h"
 
@@ -37,69 +32,6 @@ uint64_t fm_wide_threshold(const bg_ctx* ctx) { return ctx ? ctx->fm_wide_from :
 namespace {
 
 constexpr uint32_t kWideMaxExc = kMaxExcLds;
-
-__global__ __launch_bounds__(256) void fmw_hist_kernel(const uint8_t* __restrict__ b, uint64_t n, unsigned long long* __restrict__ hist) {
-    __shared__ uint32_t s[256];
-    s[threadIdx.x] = 0;
-    __syncthreads();
-    // (a block's share of a 2^40-symbol text stays below 2^32: at most 2^40 / 8192 blocks' worth per block)
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) atomicAdd(&s[b[i]], 1u);
-    __syncthreads();
-    if (s[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)s[threadIdx.x]);
-}
-
-// one thread per block: 192 symbols -> 12 words of 2-bit codes + how many of each code the block holds
-__global__ __launch_bounds__(256) void fmw_blocks_kernel(const uint8_t* __restrict__ b, uint64_t n, uint64_t nblk, const uint8_t* __restrict__ code_of,
-                                                         uint32_t* __restrict__ blocks, uint32_t* __restrict__ cnt /* [4][nblk] */) {
-    __shared__ uint8_t s_code[256];
-    s_code[threadIdx.x] = code_of[threadIdx.x];
-    __syncthreads();
-    const uint64_t blk = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk >= nblk) return;
-    const uint64_t lo = blk * kSymPerBlock;
-    uint32_t c[4] = {0, 0, 0, 0};
-    for (uint32_t w = 0; w < 12; w++) {
-        uint32_t word = 0;
-        for (uint32_t t = 0; t < 16; t++) {
-            const uint64_t i = lo + 16 * w + t;
-            if (i < n) {
-                const uint32_t code = s_code[b[i]];
-                word |= code << (2 * t);
-                c[code]++;
-            }
-        }
-        blocks[blk * 16 + 4 + w] = word;
-    }
-    for (int k = 0; k < 4; k++) cnt[(uint64_t)k * nblk + blk] = c[k];
-}
-// absolute counts (64-bit exclusive scan of cnt) -> the superblock's base and the block's counter relative to it
-__global__ __launch_bounds__(256) void fmw_heads_kernel(uint64_t nblk, uint32_t sb_shift, const uint64_t* __restrict__ scanned /* [4][nblk] */,
-                                                        uint32_t* __restrict__ blocks, uint64_t* __restrict__ sb) {
-    const uint64_t blk = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk >= nblk) return;
-    const uint64_t first = (blk >> sb_shift) << sb_shift;
-    for (int k = 0; k < 4; k++) {
-        const uint64_t base = scanned[(uint64_t)k * nblk + first];
-        blocks[blk * 16 + k] = (uint32_t)(scanned[(uint64_t)k * nblk + blk] - base);
-        if (blk == first) sb[(blk >> sb_shift) * 4 + k] = base;
-    }
-}
-// sparse exceptions: (position, byte) appended in any order; the host sorts the few of them
-__global__ __launch_bounds__(256) void fmw_sparse_kernel(const uint8_t* __restrict__ b, uint64_t n, const uint8_t* __restrict__ is_sparse,
-                                                         uint32_t cap, uint32_t* __restrict__ n_out, ulonglong2* __restrict__ out) {
-    // (grid-stride: a launch may not exceed 2^32 threads)
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint8_t ch = b[i];
-        if (is_sparse[ch]) {
-            const uint32_t k = atomicAdd(n_out, 1u);
-            if (k < cap) out[k] = make_ulonglong2(i, ch);
-        }
-    }
-}
-
-struct U32ToU64 {
-    __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
-};
 
 // Occ::get(r, code) for the quad: the block's line is in `v` (lane t holds bytes [16t, 16t + 16)), `base` the superblock's
 // absolute count of the code
@@ -382,193 +314,6 @@ __global__ __launch_bounds__(256) void fmw_sampled_get_kernel(FmWideDev fm, SaWi
 }
 
 }  // namespace
-
-int fm_wide_build_dev(bg_ctx* ctx, const uint8_t* d_bwt, uint64_t n, const uint8_t* alphabet, uint32_t n_sym, const uint64_t* less_in,
-                      uint32_t less_len_in, uint64_t* less_out, bg_fm** out, hipStream_t st) {
-    if (n > (1ull << 40)) return BG_ERR_TOO_LARGE;
-    BG_HIP(hipSetDevice(ctx->device));
-    bool in_alpha[256] = {};
-    uint32_t max_symbol = 0;
-    for (uint32_t i = 0; i < n_sym; i++) {
-        in_alpha[alphabet[i]] = true;
-        max_symbol = std::max<uint32_t>(max_symbol, alphabet[i]);
-    }
-    const uint32_t m = max_symbol + 1;
-    if ((uint32_t)'$' < m) in_alpha['$'] = true;  // bwt.rs:101-104: '$' is always tabulated
-    const uint32_t less_len = max_symbol + 2;
-    if (less_in && less_len_in != less_len) return BG_ERR_INVALID_ARG;
-
-    std::vector<void*> tmp;  // device temporaries, freed on every exit
-    auto dalloc = [&](void** p, size_t bytes) -> int {
-        BG_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-        tmp.push_back(*p);
-        return BG_OK;
-    };
-    bg_fm* fm = nullptr;
-    auto body = [&]() -> int {
-        int rc;
-        unsigned long long* d_hist = nullptr;
-        if ((rc = dalloc((void**)&d_hist, 256 * 8))) return rc;
-        BG_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, st));
-        fmw_hist_kernel<<<dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, st>>>(d_bwt, n, d_hist);
-        uint64_t hist[256];
-        BG_HIP(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        for (uint32_t c = m; c < 256; c++)
-            if (hist[c]) return BG_ERR_OUT_OF_ALPHABET;  // Occ::new: curr_occ[c] out of bounds
-        // less(bwt, alphabet) (bwt.rs:186-199) falls out of the histogram; a caller's own is taken as it is
-        uint64_t less[256] = {};
-        {
-            uint64_t acc = 0;
-            for (uint32_t c = 0; c < less_len && c < 256; c++) {
-                less[c] = less_in ? less_in[c] : acc;
-                acc += hist[c];
-            }
-            if (less_out)
-                for (uint32_t c = 0; c < less_len; c++) less_out[c] = c < 256 ? less[c] : acc;
-        }
-        // classes: the four most frequent bytes get the codes (ties: smaller byte first), every other byte that occurs is a
-        // sparse exception — at most kWideMaxExc positions in all, or the text is not DNA-like
-        int order[256];
-        std::iota(order, order + 256, 0);
-        std::stable_sort(order, order + 256, [&](int a, int b) { return hist[a] > hist[b]; });
-        uint64_t beyond4 = 0;
-        for (int i = 4; i < 256; i++) beyond4 += hist[order[i]];
-        if (beyond4 > kWideMaxExc) return BG_ERR_UNSUPPORTED;  // would need rank bit vectors: not on 64-bit positions
-        int code_of[256], sparse_of[256];
-        std::fill(code_of, code_of + 256, -1);
-        std::fill(sparse_of, sparse_of + 256, -1);
-        int n_codes = 0;
-        std::vector<int> sparse_syms;
-        for (int i = 0; i < 4 && hist[order[i]] > 0; i++) code_of[order[i]] = n_codes++;
-        for (int c = 0; c < 256; c++)
-            if (hist[c] && code_of[c] < 0) {
-                sparse_of[c] = (int)sparse_syms.size();
-                sparse_syms.push_back(c);
-            }
-        uint16_t cls[256];
-        uint8_t code_tab[256], sparse_tab[256];
-        for (int c = 0; c < 256; c++) {
-            cls[c] = !in_alpha[c] ? kClsPanic : code_of[c] >= 0 ? (uint16_t)code_of[c] : hist[c] == 0 ? kClsZero : (uint16_t)(kClsSparse + sparse_of[c]);
-            code_tab[c] = code_of[c] >= 0 ? (uint8_t)code_of[c] : 0;
-            sparse_tab[c] = sparse_of[c] >= 0 ? 1 : 0;
-        }
-        fm = new bg_fm;
-        fm->ctx = ctx;
-        fm->wide = true;
-        fm->less_len = less_len;
-        fm->fmd_ok = true;  // the BWT is a word over dna::n_alphabet() + '$' (FMDIndex::from, fmindex.rs:323-327)
-        for (int c = 0; c < 256; c++)
-            if (hist[c] && (c == 0 || !strchr("ACGTNacgtn$", c))) fm->fmd_ok = false;
-        for (int c = 0; c < 256; c++)
-            if (code_of[c] >= 0) fm->code_byte[code_of[c]] = (uint8_t)c;
-        fm->n_codes = n_codes;
-        auto keep = [&](void** p, size_t bytes) -> int {  // device memory the handle owns
-            const size_t alloc = std::max<size_t>(bytes, 16);
-            BG_HIP(hipMalloc(p, alloc));
-            fm->bytes += alloc;
-            return BG_OK;
-        };
-        const uint64_t nblk = (n + kSymPerBlock - 1) / kSymPerBlock;
-        const uint32_t sb_shift = ctx->fm_wide_sb_shift;
-        const uint64_t n_sb = ((nblk - 1) >> sb_shift) + 1;
-        uint8_t *d_code = nullptr, *d_sparse = nullptr;
-        uint32_t* d_cnt = nullptr;
-        uint64_t* d_scan = nullptr;
-        void* d_cub = nullptr;
-        if ((rc = dalloc((void**)&d_code, 256)) || (rc = dalloc((void**)&d_sparse, 256))) return rc;
-        BG_HIP(hipMemcpyAsync(d_code, code_tab, 256, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_sparse, sparse_tab, 256, hipMemcpyHostToDevice, st));
-        if ((rc = keep(&fm->d_blocks, nblk * 64))) return rc;
-        if ((rc = keep(&fm->d_sb, n_sb * 32))) return rc;
-        if ((rc = dalloc((void**)&d_cnt, 4 * nblk * 4))) return rc;
-        if ((rc = dalloc((void**)&d_scan, 4 * nblk * 8))) return rc;
-        auto in64 = rocprim::make_transform_iterator(d_cnt, U32ToU64());
-        size_t cub_bytes = 0;
-        BG_HIP(rocprim::exclusive_scan(nullptr, cub_bytes, in64, d_scan, (uint64_t)0, nblk, rocprim::plus<uint64_t>(), st));
-        if ((rc = dalloc(&d_cub, cub_bytes))) return rc;
-        fmw_blocks_kernel<<<dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st>>>(d_bwt, n, nblk, d_code, (uint32_t*)fm->d_blocks, d_cnt);
-        BG_HIP(hipGetLastError());
-        for (int k = 0; k < 4; k++) {
-            auto ink = rocprim::make_transform_iterator(d_cnt + (uint64_t)k * nblk, U32ToU64());
-            BG_HIP(rocprim::exclusive_scan(d_cub, cub_bytes, ink, d_scan + (uint64_t)k * nblk, (uint64_t)0, nblk, rocprim::plus<uint64_t>(), st));
-        }
-        fmw_heads_kernel<<<dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st>>>(nblk, sb_shift, d_scan, (uint32_t*)fm->d_blocks, (uint64_t*)fm->d_sb);
-        BG_HIP(hipGetLastError());
-        // ---- sparse exceptions
-        uint32_t* d_ns = nullptr;
-        ulonglong2* d_sp = nullptr;
-        if ((rc = dalloc((void**)&d_ns, 4))) return rc;
-        if ((rc = dalloc((void**)&d_sp, (size_t)(kWideMaxExc + 8) * 16))) return rc;
-        BG_HIP(hipMemsetAsync(d_ns, 0, 4, st));
-        fmw_sparse_kernel<<<dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 22)), dim3(256), 0, st>>>(d_bwt, n, d_sparse, kWideMaxExc + 8, d_ns, d_sp);
-        BG_HIP(hipGetLastError());
-        uint32_t ns = 0;
-        BG_HIP(hipMemcpyAsync(&ns, d_ns, 4, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        if (ns > kWideMaxExc) return BG_ERR_HIP;  // cannot happen: counted above
-        std::vector<ulonglong2> sp(ns);
-        if (ns) BG_HIP(hipMemcpy(sp.data(), d_sp, (size_t)ns * 16, hipMemcpyDeviceToHost));
-        std::sort(sp.begin(), sp.end(), [](const ulonglong2& a, const ulonglong2& b) { return a.x < b.x; });
-        std::vector<uint64_t> exc_pos(ns), exc_sym_pos;
-        std::vector<uint32_t> sparse_off(sparse_syms.size() + 1, 0);
-        std::vector<uint8_t> exc_byte(ns);
-        for (uint32_t e = 0; e < ns; e++) {
-            exc_pos[e] = sp[e].x;
-            exc_byte[e] = (uint8_t)sp[e].y;
-        }
-        for (size_t e = 0; e < sparse_syms.size(); e++) {
-            for (uint32_t k = 0; k < ns; k++)
-                if ((int)sp[k].y == sparse_syms[e]) exc_sym_pos.push_back(sp[k].x);
-            sparse_off[e + 1] = (uint32_t)exc_sym_pos.size();
-        }
-        auto upload = [&](void** dptr, const void* src, size_t bytes) -> int {
-            int r2 = keep(dptr, bytes);
-            if (r2) return r2;
-            if (bytes) BG_HIP(hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
-            return BG_OK;
-        };
-        if ((rc = upload(&fm->d_exc_pos, exc_pos.data(), exc_pos.size() * 8))) return rc;
-        if ((rc = upload(&fm->d_exc_sym_pos, exc_sym_pos.data(), exc_sym_pos.size() * 8))) return rc;
-        if ((rc = upload(&fm->d_sparse_off, sparse_off.data(), sparse_off.size() * 4))) return rc;
-        if ((rc = upload(&fm->d_exc_byte, exc_byte.data(), exc_byte.size()))) return rc;
-        if ((rc = upload(&fm->d_class, cls, 256 * sizeof(uint16_t)))) return rc;
-        memcpy(fm->h_class, cls, sizeof(fm->h_class));
-        if ((rc = upload(&fm->d_less, less, sizeof(less)))) return rc;
-        BG_HIP(hipStreamSynchronize(st));
-        fm->wdev.blocks = (const uint4*)fm->d_blocks;
-        fm->wdev.sb = (const uint64_t*)fm->d_sb;
-        fm->wdev.exc_pos = (const uint64_t*)fm->d_exc_pos;
-        fm->wdev.exc_sym_pos = (const uint64_t*)fm->d_exc_sym_pos;
-        fm->wdev.sparse_off = (const uint32_t*)fm->d_sparse_off;
-        fm->wdev.sym_class = (const uint16_t*)fm->d_class;
-        fm->wdev.less = (const uint64_t*)fm->d_less;
-        fm->wdev.n = n;
-        fm->wdev.n_exc = ns;
-        fm->wdev.sb_shift = sb_shift;
-        fm->n_text = 0;
-        {
-            // 2-step rank blocks (fm_step2.hip) lean on less[] being the BWT's own cumulative counts; a caller's less that
-            // says otherwise keeps single steps (as on the 32-bit layout, fm_index.hip)
-            bool consistent = true;
-            uint64_t run = 0;
-            for (uint32_t c = 0; c < m && c < 256 && consistent; c++) {
-                if (hist[c] && less[c] != run) consistent = false;
-                run += hist[c];
-            }
-            if (consistent) fm_build_step2_wide(fm, st);
-        }
-        return BG_OK;
-    };
-    const int rc = body();
-    for (void* p : tmp) hipFree(p);
-    if (rc) {
-        bg_fm_free(fm);
-        return rc;
-    }
-    *out = fm;
-    return BG_OK;
-}
 
 template <bool SEEDS, bool PACKED, bool DEFER>
 int fm_wide_search_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const uint64_t* d_pat_off, uint8_t* d_tag, uint64_t* d_lower,

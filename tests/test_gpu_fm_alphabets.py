@@ -129,8 +129,9 @@ def test_fmd_smems_on_a_genome_with_many_n():
 
 @pytest.mark.parametrize("kind", ["dna", "dna_n", "protein", "tiny"])
 def test_index_built_on_the_device_equals_the_host_built_one(kind):
-    """bg_fm_build_dev (blocks, bit vectors, exception lists and `less` from a BWT in HBM) against bg_fm_build: same
-    searches, same located positions, same `less`."""
+    """bg_fm_build_dev (`less` derived from a BWT in HBM) against bg_fm_build (host BWT, caller's `less`).  Both run one
+    builder (csrc/fm_build.hip), so each handle is held against the oracle's searches and the suffix array, not only
+    against the other: same searches, same located positions, same `less`, same sizes."""
     import torch
     from rust_bio_amd.suffix_array import bwt_dev, suffix_array_dev
     rng = np.random.default_rng(17)
@@ -152,13 +153,20 @@ def test_index_built_on_the_device_equals_the_host_built_one(kind):
     d_b = bwt_dev(d_text, d_sa)
     dev = FMIndex.from_device(d_b, 64, alpha)
     assert (dev._less == ls).all() and (dev.bwt() == b).all()
+    assert host.device_bytes() == dev.device_bytes() and host.step2_bytes() == dev.step2_bytes()
     plen = 8 if kind != "tiny" else 3
     pat, off = patterns_from(t, 20_000 if kind != "tiny" else 50, plen, 3, pal)
-    for a_, b_ in zip(host.backward_search_arrays(pat, off), dev.backward_search_arrays(pat, off)):
+    otag, olo, ohi, oml = orc.backward_search_batch(b, ls, orc.Occ(b, 64, alpha), pat, off, threads=8)
+    assert not (otag == 3).any()
+    got = [fm.backward_search_arrays(pat, off) for fm in (host, dev)]
+    for tag, lo, hi, ml in got:
+        assert (tag == otag).all() and (lo == olo).all() and (hi == ohi).all() and (ml.astype(np.uint64) == oml).all()
+    for a_, b_ in zip(*got):
         assert (a_ == b_).all()
     for fm in (host, dev):
         SampledSuffixArray(sa, t, b, 4, fmindex=fm)
     rows = rng.integers(0, len(sa), size=min(5000, len(sa))).astype(np.uint64)
     lo, hi = rows, rows + np.uint64(1)
     assert (host.interval_occ_arrays(lo, hi)[1] == dev.interval_occ_arrays(lo, hi)[1]).all()
-    assert (dev.interval_occ_arrays(lo, hi)[1] == sa[rows.astype(np.intp)]).all()
+    for fm in (host, dev):
+        assert (fm.interval_occ_arrays(lo, hi)[1] == sa[rows.astype(np.intp)]).all()
