@@ -867,6 +867,48 @@ int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const ui
                     const uint8_t* x, const uint64_t* x_off, const uint8_t* y, const uint64_t* y_off, uint32_t ncol,
                     char* out, uint64_t out_cap, uint64_t* out_off);
 
+/* ---- FASTA ingest and the reference text (fasta_ingest.hip) ----------------------------------------------
+ * bio::io::fasta::Reader::read / Records on a text that is in memory (io/fasta.rs:334-359, 1090-1111) and Record::check
+ * (fasta.rs:982-1009); conventions as for bg_fastq_parse[_dev] above.
+ * Lines.  A line is the bytes up to and including '\n', or to the end of the text.  A line that is not valid UTF-8 makes
+ * read_line fail (the validity rule of the FASTQ reader).  str::trim_end strips trailing Unicode White_Space: the line's
+ * own '\n', '\r', and the multi-byte members U+0085, U+00A0, U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F, U+3000.
+ * First line and headers.  The first line must start with '>': otherwise *status = BG_FASTA_MISSING_GT with no records and
+ * *err_pos = 0 (a leading blank line is that error).  An empty text is BG_FASTA_OK with 0 records.  After the first header
+ * every line whose first byte is '>' is a header; every other line is a sequence line, whose trimmed bytes are appended to
+ * the record's sequence (interior white space stays; check rejects it).
+ * Header fields.  line[1..].trim_end() is split once at its first char::is_whitespace: the id is the part in front of that
+ * character (it may be empty), the description everything behind that one character (it may begin with more white space);
+ * without white space has_desc = 0.
+ * Errors.  A read_line failure anywhere inside `read` of record k loses record k — also a failure on the header line of
+ * record k + 1, which record k's loop reads: *status = BG_FASTA_IO, *err_pos = that line's offset, *n_records = k.
+ * Early end.  Records ends at the first record that is_empty() (empty id, no description, empty sequence):
+ * ">\n\n>x\nAC\n" yields 0 records with BG_FASTA_OK.
+ * check: first failing rule of BG_FACHECK_EMPTY_ID, _NONASCII_SEQ, _INVALID_SEQ (a byte is valid if it is an ASCII letter
+ * or one of - . *).
+ * seq holds `len` bytes, seq_off rec_cap + 1 entries; BG_ERR_TOO_LARGE if there are more than rec_cap records (*n_records
+ * says how many).  The device kernels work on tiles of BG_FASTA_TILE bytes of the text; a text at a 16-byte aligned address
+ * is loaded with vector loads, any other address byte by byte (coalesced, but slower).  bg_fasta_parse, like bg_fastq_parse,
+ * copies the text to the device and runs the same kernels: it needs a ctx and a GPU (bg_fasta_reference below does not).
+ * recs, seq and seq_off must not be NULL for a text that is not empty, also with rec_cap == 0 (a call that only counts). */
+#define BG_FASTA_TILE 8192
+enum { BG_FASTA_OK = 0, BG_FASTA_MISSING_GT = 1, BG_FASTA_IO = 2 };
+enum { BG_FACHECK_OK = 0, BG_FACHECK_EMPTY_ID = 1, BG_FACHECK_NONASCII_SEQ = 2, BG_FACHECK_INVALID_SEQ = 3 };  /* CheckError */
+typedef struct {
+    uint64_t id_off, desc_off;   /* into the text */
+    uint64_t seq_off, seq_len;   /* into seq; 64-bit: a chromosome may exceed 2^32 */
+    uint32_t id_len, desc_len;
+    int32_t has_desc;            /* 0: Record::desc() is None */
+    int32_t check;               /* Record::check(): BG_FACHECK_* (first failing rule) */
+} bg_fasta_record_t;             /* 48 bytes */
+int bg_fasta_parse(bg_ctx* ctx, const uint8_t* text, uint64_t len, bg_fasta_record_t* recs, uint64_t rec_cap,
+                   uint8_t* seq, uint64_t* seq_off, uint64_t* n_records, int32_t* status, uint64_t* err_pos);
+/* the same with text, records, sequences and offsets in device memory (n_records/status/err_pos are host pointers; the
+ * call synchronises `stream`) */
+int bg_fasta_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t len, bg_fasta_record_t* d_recs, uint64_t rec_cap,
+                       uint8_t* d_seq, uint64_t* d_seq_off, uint64_t* n_records, int32_t* status, uint64_t* err_pos,
+                       void* stream);
+
 /* ---- SAM records from seed-and-extend hits (sam_emit.hip) -----------------------------------------------
  * The output half of "wire format in, format out": one SAM line (SAM v1.6, section 1.4) per hit slot, formatted in HBM
  * from exactly what bg_fastq_parse_dev and bg_seed_extend_strands / _pairs / _pairs_mapq / _multi_batch_dev leave there; nothing is
@@ -949,6 +991,28 @@ int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, co
                       const uint8_t* seq, const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand,
                       const uint8_t* ops, const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap,
                       uint64_t* out_off, uint64_t* out_bytes);
+
+/* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
+ * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header
+ * take as they are.  Without BG_FASTA_REF_FMD the text is S0 $ S1 $ ... S(k-1) $ and *n_text = sum(len_i + 1).  With it,
+ * T = S0 $ S1 ... $ S(k-1) (n_t = sum(len_i) + k - 1 bytes) and the text is T $ R $ with R = dna::revcomp(T), the byte map
+ * of bg_revcomp_batch_dev ('$' maps to itself): *n_text = 2 n_t + 2, the text bg_seed_extend_smem_batch requires.
+ * BG_FASTA_REF_UPPER folds a-z to A-Z first (soft-masked genomes); every other byte is copied as it is (whether it is in
+ * the index's alphabet remains the FM builder's check).  contigs[i] = {start of S_i in the text, len_i, name_off, id_len},
+ * the ids back to back in names; a zero-length sequence gives a zero-length contig.
+ * text_out == NULL with text_cap == 0 is a sizing call (fills *n_text and *names_bytes).  BG_ERR_OPS_CAP if text_cap or
+ * names_cap is too small, BG_ERR_INVALID_ARG for n_records == 0, unknown flag bits, or a record with check != OK (*first_bad
+ * = its index, otherwise UINT64_MAX): nothing is written in any of these cases.  The device flavour reads the sizes back
+ * with one synchronisation of `stream`; its write pass is asynchronous on `stream`.  The host flavour uses no GPU (ctx may
+ * be NULL). */
+enum { BG_FASTA_REF_FMD = 1, BG_FASTA_REF_UPPER = 2 };
+int bg_fasta_reference_dev(bg_ctx* ctx, uint64_t n_records, const bg_fasta_record_t* d_recs, const uint8_t* d_fasta_text,
+                           const uint8_t* d_seq, uint32_t flags, uint8_t* d_text_out, uint64_t text_cap,
+                           bg_sam_contig_t* d_contigs, char* d_names, uint64_t names_cap, uint64_t* n_text,
+                           uint64_t* names_bytes, uint64_t* first_bad, void* stream);
+int bg_fasta_reference(bg_ctx* ctx, uint64_t n_records, const bg_fasta_record_t* recs, const uint8_t* fasta_text,
+                       const uint8_t* seq, uint32_t flags, uint8_t* text_out, uint64_t text_cap, bg_sam_contig_t* contigs,
+                       char* names, uint64_t names_cap, uint64_t* n_text, uint64_t* names_bytes, uint64_t* first_bad);
 
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI

@@ -1102,6 +1102,80 @@ private:
     bool raised_ = false;
 };
 }  // namespace fastq
+
+// bio::io::fasta, reading side (io/fasta.rs:334-359, 982-1009, 1090-1111), over a text held in memory; parsed on the device
+namespace fasta {
+struct ReadError : Panic {  // the io::Error of Reader::read
+    enum Kind { MissingGt = BG_FASTA_MISSING_GT, Io = BG_FASTA_IO } kind;
+    uint64_t pos;
+    ReadError(Kind k, uint64_t p) : Panic(k == MissingGt ? "MissingGt" : "Io"), kind(k), pos(p) {}
+};
+enum class CheckError { Ok = 0, EmptyId, NonAsciiSequence, InvalidSequence };  // fasta.rs:993-1009
+
+class Record {  // fasta.rs:940-1040
+public:
+    Record() = default;
+    Record(std::string id, std::optional<std::string> desc, Text seq, CheckError chk = CheckError::Ok)
+        : id_(std::move(id)), desc_(std::move(desc)), seq_(std::move(seq)), check_(chk) {}
+    bool is_empty() const { return id_.empty() && !desc_ && seq_.empty(); }
+    CheckError check() const { return check_; }  // Ok(()) == CheckError::Ok; evaluated on the device with the parse
+    const std::string& id() const { return id_; }
+    const std::optional<std::string>& desc() const { return desc_; }
+    const Text& seq() const { return seq_; }
+    bool operator==(const Record& o) const { return id_ == o.id_ && desc_ == o.desc_ && seq_ == o.seq_; }
+
+private:
+    std::string id_;
+    std::optional<std::string> desc_;
+    Text seq_;
+    CheckError check_ = CheckError::Ok;
+};
+
+// `Reader::new(&[u8])` + `read()` / `records()`: all records are parsed by one device call; read() hands them out one by
+// one, an empty Record at the end (fasta.rs:338-340), ReadError where the reference returns Err
+class Reader {
+public:
+    explicit Reader(const Text& t, std::shared_ptr<Context> ctx = nullptr) {
+        if (!ctx) ctx = Context::shared_default();
+        const uint64_t cap = t.size() / 3 + 2;  // a record that is not empty takes three bytes, the last one two
+        std::vector<bg_fasta_record_t> recs(cap);
+        std::vector<uint8_t> seq(t.size() + 1);
+        std::vector<uint64_t> so(cap + 1);
+        uint64_t n = 0, err = 0;
+        int32_t st = 0;
+        check(bg_fasta_parse(ctx->raw(), t.data(), t.size(), recs.data(), cap, seq.data(), so.data(), &n, &st, &err), "bg_fasta_parse");
+        for (uint64_t k = 0; k < n; k++) {
+            const bg_fasta_record_t& r = recs[k];
+            std::optional<std::string> d;
+            if (r.has_desc) d = std::string(t.begin() + r.desc_off, t.begin() + r.desc_off + r.desc_len);
+            records_.emplace_back(std::string(t.begin() + r.id_off, t.begin() + r.id_off + r.id_len), std::move(d),
+                                  Text(seq.begin() + so[k], seq.begin() + so[k + 1]), (CheckError)r.check);
+        }
+        status_ = st;
+        err_pos_ = err;
+    }
+    void read(Record& record) {
+        if (next_ < records_.size()) {
+            record = records_[next_++];
+        } else if (status_ != BG_FASTA_OK && !raised_) {
+            raised_ = true;
+            throw ReadError((ReadError::Kind)status_, err_pos_);
+        } else {
+            record = Record();
+        }
+    }
+    // the records read before the first error or the first empty record; `status()` tells whether the iterator would end with Err
+    const std::vector<Record>& records() const { return records_; }
+    int status() const { return status_; }
+
+private:
+    std::vector<Record> records_;
+    size_t next_ = 0;
+    int status_ = 0;
+    uint64_t err_pos_ = 0;
+    bool raised_ = false;
+};
+}  // namespace fasta
 }  // namespace io
 }  // namespace bio
 #endif

@@ -138,6 +138,13 @@ FQREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8
                         ("has_desc", "<i4"), ("check", "<i4")])
 assert FQREC_DTYPE.itemsize == 56, FQREC_DTYPE.itemsize
 
+# bg_fasta_record_t, BG_FASTA_TILE (the bytes of the text one block of the FASTA kernels works on) and BG_FASTA_REF_*
+FAREC_DTYPE = np.dtype([("id_off", "<u8"), ("desc_off", "<u8"), ("seq_off", "<u8"), ("seq_len", "<u8"),
+                        ("id_len", "<u4"), ("desc_len", "<u4"), ("has_desc", "<i4"), ("check", "<i4")])
+assert FAREC_DTYPE.itemsize == 48, FAREC_DTYPE.itemsize
+FASTA_TILE = 8192
+FASTA_REF_FMD, FASTA_REF_UPPER = 1, 2
+
 # bg_sam_contig_t, BG_SAM_* and bg_sam_params_t (bg_sam_header, bg_sam_emit_batch[_dev])
 SAM_CONTIG_DTYPE = np.dtype([("start", "<u8"), ("len", "<u8"), ("name_off", "<u8"), ("name_len", "<u4"), ("reserved", "<u4")])
 assert SAM_CONTIG_DTYPE.itemsize == 32, SAM_CONTIG_DTYPE.itemsize
@@ -168,6 +175,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_seed_extend_pairs_mapq_batch", "bg_seed_extend_pairs_mapq_batch_dev",
            "bg_seed_extend_pairs_rescue_mapq_batch", "bg_seed_extend_pairs_rescue_mapq_batch_dev",
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
+           "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
@@ -243,6 +251,10 @@ def lib():
         L.bg_sa_get_batch.argtypes = [vp, u64, vp, vp]
         L.bg_fastq_parse.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
         L.bg_fastq_parse_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64), vp]
+        L.bg_fasta_parse.argtypes = [vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
+        L.bg_fasta_parse_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64), vp]
+        L.bg_fasta_reference.argtypes = [vp, u64, vp, vp, vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.bg_fasta_reference_dev.argtypes = [vp, u64, vp, vp, vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_cigar_batch.argtypes = [vp, u64, vp, vp, u64, i32, vp, u64, vp]
         L.bg_cigar_batch_dev.argtypes = [vp, u64, vp, vp, i32, vp, u64, vp, vp]
         L.bg_sa_get_batch_dev.argtypes = [vp, u64, vp, vp, vp]

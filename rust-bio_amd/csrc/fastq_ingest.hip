@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "bg_common.h"
+#include "white_space.h"
 
 namespace {
 
@@ -149,10 +150,6 @@ __global__ __launch_bounds__(256) void fq_line_starts_kernel(const uint8_t* __re
 }
 
 // ---- F2 ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool is_ws(uint32_t cp) {  // char::is_whitespace
-    return (cp >= 9 && cp <= 13) || cp == 0x20 || cp == 0x85 || cp == 0xA0 || cp == 0x1680 || (cp >= 0x2000 && cp <= 0x200A) ||
-           cp == 0x2028 || cp == 0x2029 || cp == 0x202F || cp == 0x205F || cp == 0x3000;
-}
 __device__ bool valid_utf8(const uint8_t* s, uint64_t n) {
     uint64_t i = 0;
     while (i < n) {

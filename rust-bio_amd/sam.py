@@ -23,6 +23,14 @@ class Contigs:
             names += name
         self.names = np.frombuffer(names + b"\0", dtype=np.uint8).copy()  # (never empty: a buffer to point at)
 
+    @classmethod
+    def from_arrays(cls, table, names):
+        """a table and names buffer that already have the layout (what `fasta.reference_arrays` returns)"""
+        self = cls([])
+        self.table = np.ascontiguousarray(table, dtype=_lib.SAM_CONTIG_DTYPE)
+        self.names = np.concatenate([np.ascontiguousarray(names, dtype=np.uint8), np.zeros(1, np.uint8)])
+        return self
+
     def __len__(self):
         return len(self.table)
 
