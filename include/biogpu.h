@@ -580,6 +580,55 @@ int bg_seed_extend_smem_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_sm
                                   uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                   bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops, uint64_t ops_stride,
                                   uint64_t* totals, void* stream);
+/* Tiered seeds: one call on one FMD index, fixed windows for every read and SMEMs only for the reads the windows leave weak.
+ * The handle is what bg_seed_extend_smem_batch takes: an FMD index over T$R$ (else BG_ERR_UNSUPPORTED; n odd or n < 2:
+ * BG_ERR_INVALID_ARG) with all of T$R$ attached and a raw or sampled suffix array, on 32- or 64-bit positions.  The definition
+ * (stated on the CPU by tests/tiered_seed_oracle.py):
+ *   tier 1       the SMEM call above word for word, with its `seeds` line replaced:
+ *     seeds        the records of a read of length L are its windows read[o .. o + seed_len) for o = 0, stride, 2 stride, ...
+ *                  while the window fits in the read, each searched once with FMIndex::backward_search (fmindex.rs:144-208) on
+ *                  the FMD index — on the caller's read only, never on its revcomp.  A Complete search gives the record {lower,
+ *                  size = upper - lower, a = o, len = seed_len}; a Partial or Absent one a record of size 0.  A window that
+ *                  reaches a byte outside the alphabet does not vote (the read's other windows do), and the call returns
+ *                  BG_ERR_OUT_OF_ALPHABET with every read answered.  There is no truncation: a read's records are all its
+ *                  windows;
+ *     votes        a record votes when 1 <= size <= window.max_occ, size being the whole interval over T$R$, both halves together;
+ *     after that   locate, the two half formulas and their dropped cases, `strands`, the merge within a strand with window.pad,
+ *                  windows, Aligner::semiglobal, best hit, n_seed_hits and n_candidates are the SMEM call's, with n_text = n_t.
+ *                This is NOT bg_seed_extend_strands_batch on a forward index of T$: a window whose rows lie in the R half proposes
+ *                revcomp(read) from a window that is not on revcomp(read)'s own stride grid (its offset on revcomp(read) is L - o -
+ *                seed_len), and max_occ counts the occurrences on both strands together.
+ *   selection    read r is re-seeded when its tier-1 winner's score is below reseed_below.  A read without candidates has
+ *                BG_MIN_SCORE, so reseed_below = BG_MIN_SCORE re-seeds no read and INT32_MAX every read.
+ *   tier 2       bg_seed_extend_smem_batch with `smem` and the same `strands` on exactly the re-seeded reads.
+ *   answer       a read that is not re-seeded reports tier 1 alone.  A re-seeded read reports the better of its two tier winners
+ *                (a tier without a hit loses to one with a hit): the higher score, then the forward strand, then the smaller
+ *                window_start, then tier 1.  Strand and operations are the winner's; n_candidates and n_seed_hits are the sums
+ *                of both tiers.
+ * tier[r] (optional): BG_TIER_NONE — not re-seeded; BG_TIER_FIRST — re-seeded, tier 1's hit (or no hit) kept; BG_TIER_SECOND —
+ * tier 2's hit.  totals (optional, host, 3 entries): suffix-array rows resolved and candidates aligned, each over both tiers,
+ * then reads re-seeded.  Status: BG_ERR_OUT_OF_ALPHABET from either tier comes before BG_ERR_OPS_CAP, which says that a
+ * re-seeded read has more than smem.max_smems SMEMs (answered from the first max_smems, as in the SMEM call); every read is
+ * answered under both.  Refused before any work, outputs untouched: window.pad != smem.pad (one ops_stride and one merge distance
+ * serve both tiers), a zero seed_len / stride / window.max_occ / min_seed_len / max_smems / smem.max_occ (BG_ERR_INVALID_ARG);
+ * more than 64 window slots at max_read_len ((max_read_len - seed_len) / stride + 1), slots * window.max_occ > 1024, max_smems *
+ * smem.max_occ > 1024 (BG_ERR_UNSUPPORTED); max_read_len > 65534 (BG_ERR_TOO_LARGE).  Arguments, slots, the ops_stride rule and
+ * passes (seed_chunk_reads) are those of bg_seed_extend_strands_batch[_dev]; the hits are ordinary bg_seed_hit_t slots
+ * (bg_sam_emit_batch[_dev] takes them as they are).  The device flavour waits once more per pass for the number of re-seeded
+ * reads and their bytes; a pass that re-seeds no read launches nothing of tier 2. */
+typedef struct {
+    bg_seed_params_t window;      /* tier 1: seed_len, stride, max_occ, pad */
+    bg_smem_seed_params_t smem;   /* tier 2: min_seed_len, max_smems, max_occ, pad (== window.pad) */
+    int32_t reseed_below;         /* a read whose tier-1 winner scores less is re-seeded */
+} bg_tiered_seed_params_t;
+enum { BG_TIER_NONE = 0, BG_TIER_FIRST = 1, BG_TIER_SECOND = 2 };   /* tier[r] */
+int bg_seed_extend_tiered_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
+                                uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                uint8_t* strand, uint8_t* tier, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+int bg_seed_extend_tiered_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
+                                    uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                    bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_tier, uint8_t* d_ops, uint64_t ops_stride,
+                                    uint64_t* totals, void* stream);
 /* Read pairs.  Paired-end reads come as two mates per DNA fragment, read towards each other from opposite strands.  The
  * reads are interleaved mates: read 2p is mate 1 of pair p, read 2p + 1 its mate 2 (2 n_pairs + 1 offsets; an interleaved
  * FASTQ parsed by bg_fastq_parse[_dev] gives this layout).

@@ -90,6 +90,15 @@ class SMEM_SEED_PARAMS(C.Structure):
 assert C.sizeof(SMEM_SEED_PARAMS) == 16, C.sizeof(SMEM_SEED_PARAMS)
 
 
+# bg_tiered_seed_params_t (bg_seed_extend_tiered_batch[_dev]) and BG_TIER_* (tier[r] of a read)
+class TIERED_SEED_PARAMS(C.Structure):
+    _fields_ = [("window", SeedParamsC), ("smem", SMEM_SEED_PARAMS), ("reseed_below", C.c_int32)]
+
+
+assert C.sizeof(TIERED_SEED_PARAMS) == 36, C.sizeof(TIERED_SEED_PARAMS)
+TIER_NONE, TIER_FIRST, TIER_SECOND = 0, 1, 2
+
+
 # bg_pair_params_t (bg_seed_extend_pairs_batch[_dev])
 class PAIR_PARAMS(C.Structure):
     _fields_ = [("min_span", C.c_uint32), ("max_span", C.c_uint32), ("pen_unpaired", C.c_int32)]
@@ -169,6 +178,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_seed_extend_smem_batch", "bg_seed_extend_smem_batch_dev",
+           "bg_seed_extend_tiered_batch", "bg_seed_extend_tiered_batch_dev",
            "bg_seed_extend_pairs_batch", "bg_seed_extend_pairs_batch_dev",
            "bg_seed_extend_pairs_rescue_batch", "bg_seed_extend_pairs_rescue_batch_dev",
            "bg_seed_extend_multi_batch", "bg_seed_extend_multi_batch_dev",
@@ -298,6 +308,10 @@ def lib():
                                                 C.POINTER(u64)]
         L.bg_seed_extend_smem_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SMEM_SEED_PARAMS), u32, u64, vp, vp, u32, vp, vp,
                                                     vp, u64, vp, vp]
+        L.bg_seed_extend_tiered_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(TIERED_SEED_PARAMS), u32, u64, vp, vp, vp, vp, vp, vp,
+                                                  u64, C.POINTER(u64)]
+        L.bg_seed_extend_tiered_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(TIERED_SEED_PARAMS), u32, u64, vp, vp, u32, vp,
+                                                      vp, vp, vp, u64, vp, vp]
         L.bg_seed_extend_pairs_batch.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp, vp,
                                                  vp, vp, vp, u64, C.POINTER(u64)]
         L.bg_seed_extend_pairs_batch_dev.argtypes = [vp, C.POINTER(ScoringC), C.POINTER(SeedParamsC), C.POINTER(PAIR_PARAMS), u64, vp, vp,

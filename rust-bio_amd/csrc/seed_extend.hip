@@ -24,6 +24,7 @@
 //      (scan of the per-read candidate / x-byte / y-byte counts; the three totals are the SECOND host round trip)
 //      SMEM mode (SeedCall::smem, seed_smem.hip) instead of S1, S2, S4: a length check with a host round trip of its own, S1' K7
 //      over the caller's reads, S2' votes of the record slots, S4' one wavefront per caller read proposes for both strands
+//      tiered mode (SeedCall::tiered, seed_tiered.hip), tier 1: S1 on the caller's reads, S1" the windows as records, then S2', S4'
 //   se_align
 //   S5 gather           (read, text window) pairs, offsets                              -> x, x_off, y, y_off
 //   S6 align            Aligner::semiglobal on every candidate (bg_align_batch_dev)      -> records + operations
@@ -37,6 +38,8 @@
 //   se_rescue           rescue modes, instead of se_reduce: (pairs-mapq records of every pair,) R1 plan, one more host
 //                       round trip, R2 gather, R3 align, R4 pick (seed_rescue.hip), (records of the rescued pairs,
 //                       seed_rescueq.hip)
+//   se_reseed           tiered mode, after se_reduce: T1 select, one more host round trip, T2 gather, the SMEM mode's pass on the
+//                       re-seeded reads into scratch slots (tier 2), T3 merge (seed_tiered.hip)
 // The rules the reduction kernels share are device functions in seed_rule.h, seed_pair_rule.h and seed_rescue_rule.h.
 #include <algorithm>
 
@@ -62,8 +65,13 @@ enum SeedBuf {
     kPerPairOffsets,       // their scans: roff | xoff | yoff
     kRescueX, kRescueY, kRescueOff, kRescueAln, kRescueOps,  // R2, R3: as kX .. kCandOps, for the rescue alignments
     kRescuedCount,         // 64 bytes: the call's rescued pairs (totals[3])
-    kSmemCount, kSmemRec,  // S1': K7's count per caller read and its max_smems records of six uint64
+    kSmemCount, kSmemRec,  // S1': K7's count per caller read and its max_smems records of six uint64 (S1": the window records)
     kStartOff,             // S4': where each virtual read's kept starts begin in kPos
+    kReseedCounts,         // T1: flag | bytes per read of the pass
+    kReseedOffsets,        // their scans: compact index | byte offset
+    kReseedReads, kReseedReadOff, kReseedMap,  // T2: the re-seeded reads back to back, their offsets, compact index -> read of the pass
+    kTier1Strand,          // tier 1's strand per read of the call, where the caller has no strand array
+    kTier2Hits, kTier2Strand, kTier2Ops,  // tier 2's answers: one slot per re-seeded read of the pass
     kSeedBufs
 };
 struct bg_seed_scratch {
@@ -389,6 +397,8 @@ namespace {
 //   rescue       with pair: `rescued` one byte per pair, `totals` 4 entries (otherwise 2)
 //   multi_prm    multi mode: hits / strand / ops hold max_hits slots per read, `multi` one record per read
 //   smem         SMEM mode: seeds are the SMEMs of the caller's reads on an FMD index, `prm` is null
+//   tiered       tiered mode: `prm` and `smem` are null; tier 1 seeds with tiered->window on the FMD index, tier 2 is an SMEM-mode
+//                call of its own on the re-seeded reads (se_reseed); `tier` one byte per read, `totals` 3 entries
 struct SeedCall {
     bg_fm* fm = nullptr;
     const bg_scoring_t* sc = nullptr;
@@ -411,8 +421,10 @@ struct SeedCall {
     const bg_rescue_params_t* rescue = nullptr;
     const bg_pairq_params_t* pairq = nullptr;
     const bg_smem_seed_params_t* smem = nullptr;
+    const bg_tiered_seed_params_t* tiered = nullptr;
+    uint8_t* tier = nullptr;
     void* stream = nullptr;
-    uint32_t pad() const { return smem ? smem->pad : prm->pad; }
+    uint32_t pad() const { return tiered ? tiered->window.pad : smem ? smem->pad : prm->pad; }
 };
 
 // consecutive arrays out of one scratch buffer
@@ -433,7 +445,7 @@ struct SeedRun {
     bg_ctx* ctx = nullptr;
     hipStream_t st = nullptr;
     SeedPrm prm = {};
-    SeedSmemPrm smem = {};  // SMEM mode
+    SeedSmemPrm smem = {};  // SMEM and tiered modes: the record slots of a read
     uint32_t G = 1;         // virtual reads per read
     bool virt = false;      // the virtual reads are materialised (S0)
     uint32_t win_max = 0;   // the longest candidate window
@@ -511,7 +523,23 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic, bool* any_truncat
     }
     // ---- S1/S2: seeds -> votes -> hit offsets
     const uint64_t* d_rec = nullptr;
-    if (c.smem) {
+    if (c.tiered) {
+        // S1, S1", S2': the windows of the pass's caller reads, searched once on the FMD index, as records
+        if (!R.prm.S) {  // no window fits in max_read_len: one empty slot per read
+            BG_HIP(hipMemsetAsync(d_votes, 0, nq * 4, R.st));
+        } else {
+            if ((rc = R.need(kSmemCount, p.nr * 4))) return rc;
+            if ((rc = R.need(kSmemRec, nq * 6 * 8))) return rc;
+            d_rec = R.buf<uint64_t>(kSmemRec);
+            if ((rc = bg_fm_search_seeds_dev(c.fm, p.nr, c.reads, c.read_off + p.r0, R.prm.S, R.prm.stride, R.prm.seed_len, d_tag, d_lo, d_hi,
+                                             d_matched_len, R.st)))
+                return rc;
+            if ((rc = bg_seed_tiered_records_launch(p.nr, R.prm.S, R.prm.stride, R.prm.seed_len, c.read_off + p.r0, d_tag, d_lo, d_hi,
+                                                    R.buf<uint32_t>(kSmemCount), R.buf<uint64_t>(kSmemRec), d_flags, R.st)))
+                return rc;
+            if ((rc = bg_seed_smem_votes_launch(nq, R.smem, R.buf<uint32_t>(kSmemCount), d_rec, d_votes, d_lo, d_flags, R.st))) return rc;
+        }
+    } else if (c.smem) {
         // S1', S2': the SMEMs of the pass's caller reads (not of their revcomps: the index holds both strands)
         if ((rc = R.need(kSmemCount, p.nr * 4))) return rc;
         if ((rc = R.need(kSmemRec, nq * 6 * 8))) return rc;
@@ -549,7 +577,7 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic, bool* any_truncat
     uint64_t *d_coff = offsets.take<uint64_t>(nv + 1), *d_xoff = offsets.take<uint64_t>(nv + 1), *d_yoff = offsets.take<uint64_t>(nv + 1);
     p.off = SeedXYOff{d_coff, d_xoff, d_yoff};
     p.soff = p.hoff, p.soff_stride = R.prm.S;
-    if (c.smem) {
+    if (c.smem || c.tiered) {
         if ((rc = R.need(kStartOff, nv * 8))) return rc;
         uint64_t* d_soff = R.buf<uint64_t>(kStartOff);
         p.soff = d_soff, p.soff_stride = 1;
@@ -669,48 +697,129 @@ int se_rescue(SeedRun& R, SeedPassRun& p) {
     return BG_OK;
 }
 
-// The call's checks, its passes, its totals.
-int se_run(const SeedCall& c) {
-    if (!c.fm || !c.sc || (!c.prm && !c.smem) || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
-    const uint64_t n_index = c.fm->wide ? c.fm->wdev.n : (uint64_t)c.fm->dev.n;
-    if (c.smem) {  // an FMD index over T$R$ (FMDIndex::from's assert, as K7 checks it)
-        if (!c.fm->fmd_ok) return BG_ERR_UNSUPPORTED;
-        if (n_index < 2 || n_index % 2) return BG_ERR_INVALID_ARG;
-    }
-    if (!c.fm->d_text || c.fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
-    if (c.smem) {
-        if (c.smem->min_seed_len == 0 || c.smem->max_smems == 0 || c.smem->max_occ == 0) return BG_ERR_INVALID_ARG;
-        if ((uint64_t)c.smem->max_smems * c.smem->max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
-    } else if (c.prm->seed_len == 0 || c.prm->stride == 0 || c.prm->max_occ == 0) {
-        return BG_ERR_INVALID_ARG;
-    }
-    if (c.max_read_len > 65535 || c.pad() > 65535) return BG_ERR_TOO_LARGE;
-    if (c.smem && c.max_read_len > 65534) return BG_ERR_TOO_LARGE;  // K7's own limit
-    if (c.rescue && c.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
-    const uint32_t win_max = c.max_read_len + 2 * c.pad();
-    const uint32_t rwin_max = c.rescue ? c.pair->max_span : 0;
-    if (c.ops && c.ops_stride < (uint64_t)c.max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
-    if (c.totals) c.totals[0] = c.totals[1] = 0;
-    if (c.totals && c.rescue) c.totals[2] = c.totals[3] = 0;
-    if (c.n_reads == 0) return BG_OK;
-    bg_ctx* ctx = c.fm->ctx;
-    hipStream_t st = (hipStream_t)c.stream;
-    BG_HIP(hipSetDevice(ctx->device));
-    bg_scratch_guard guard(ctx, st);  // ctx->seed is one scratch set: calls on other streams wait for this one's last kernel
+// The seeds of a call in its mode: the slots of a read (prm.S) and what the candidate stages need to know about them.
+int se_seed_params(const SeedCall& c, uint64_t n_index, SeedPrm* prm_out, SeedSmemPrm* smem_out) {
     SeedPrm prm = {};
     SeedSmemPrm smem = {};
     if (c.smem) {  // the slots of a read are its max_smems records; the text the windows are cut from is T, the first half
         smem = SeedSmemPrm{c.smem->max_smems, c.smem->max_occ, c.smem->pad, c.strands, (n_index - 2) / 2};
         prm.S = smem.M, prm.max_occ = smem.max_occ, prm.pad = smem.pad, prm.n_text = smem.n_t;
     } else {
-        prm.S = c.max_read_len >= c.prm->seed_len ? (c.max_read_len - c.prm->seed_len) / c.prm->stride + 1 : 0;
-        prm.stride = c.prm->stride;
-        prm.seed_len = c.prm->seed_len;
-        prm.max_occ = c.prm->max_occ;
-        prm.pad = c.prm->pad;
+        const bg_seed_params_t& w = c.tiered ? c.tiered->window : *c.prm;
+        prm.S = c.max_read_len >= w.seed_len ? (c.max_read_len - w.seed_len) / w.stride + 1 : 0;
+        prm.stride = w.stride;
+        prm.seed_len = w.seed_len;
+        prm.max_occ = w.max_occ;
+        prm.pad = w.pad;
         prm.n_text = c.fm->n_text;
         if (prm.S > 64 || (uint64_t)prm.S * prm.max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
+        if (c.tiered) {  // tier 1: the slots of a read are its windows as records, on T$R$ as in SMEM mode
+            smem = SeedSmemPrm{prm.S, w.max_occ, w.pad, c.strands, (n_index - 2) / 2};
+            prm.n_text = smem.n_t;
+        }
     }
+    *prm_out = prm, *smem_out = smem;
+    return BG_OK;
+}
+
+// one pass of a call: its candidates, their alignments, the answers
+int se_pass(SeedRun& R, SeedPassRun& p, bool* any_panic, bool* any_truncated) {
+    int rc;
+    if ((rc = se_candidates(R, p, any_panic, any_truncated))) return rc;
+    if ((rc = se_align(R, p))) return rc;
+    return R.call.rescue ? se_rescue(R, p) : se_reduce(R, p);
+}
+
+// Tiered mode, after tier 1's pass has answered reads r0 .. r0 + nr: T1 select, the re-seeded count and bytes (one host round
+// trip; count 0 ends here), T2 gather, tier 2 — an SMEM-mode pass of its own over the compact reads, into scratch slots —, T3 merge.
+// strand1: tier 1's strand per read of the call.  Adds tier 2's rows, candidates and reads to the three counters.
+int se_reseed(SeedRun& R, const SeedPassRun& p, uint8_t* strand1, uint64_t n_index, uint64_t* rows, uint64_t* cand, uint64_t* reseeded,
+              bool* any_panic, bool* any_truncated) {
+    int rc;
+    const SeedCall& c = R.call;
+    const uint64_t nr = p.nr;
+    if ((rc = R.need(kReseedCounts, 2 * nr * 4))) return rc;
+    if ((rc = R.need(kReseedOffsets, 2 * (nr + 1) * 8))) return rc;
+    if ((rc = R.need(kScanPartials, 2 * (nr / 2048 + 2) * 8))) return rc;
+    Carve counts{R.buf<uint8_t>(kReseedCounts)}, offsets{R.buf<uint8_t>(kReseedOffsets)};
+    uint32_t *d_flag = counts.take<uint32_t>(nr), *d_bytes = counts.take<uint32_t>(nr);
+    uint64_t *d_idx = offsets.take<uint64_t>(nr + 1), *d_boff = offsets.take<uint64_t>(nr + 1);
+    uint64_t* d_sums = R.buf<uint64_t>(kScanPartials);
+    if ((rc = bg_seed_tiered_select_launch(nr, p.r0, c.hits, c.read_off, c.tiered->reseed_below, d_flag, d_bytes, c.tier, R.st))) return rc;
+    if ((rc = bg_scan_u32(d_flag, nr, d_idx, d_sums, R.st))) return rc;
+    if ((rc = bg_scan_u32(d_bytes, nr, d_boff, d_sums, R.st))) return rc;
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[5], d_idx + nr, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipMemcpyAsync(&R.W.h_tot[6], d_boff + nr, 8, hipMemcpyDeviceToHost, R.st));
+    BG_HIP(hipStreamSynchronize(R.st));  // sizes tier 2
+    const uint64_t n2 = R.W.h_tot[5], n_bytes = R.W.h_tot[6];
+    if (!n2) return BG_OK;
+    // ---- T2: the re-seeded reads, back to back
+    if ((rc = R.need(kReseedReads, n_bytes))) return rc;
+    if ((rc = R.need(kReseedReadOff, (n2 + 1) * 8))) return rc;
+    if ((rc = R.need(kReseedMap, n2 * 4))) return rc;
+    if ((rc = R.need(kTier2Hits, n2 * sizeof(bg_seed_hit_t)))) return rc;
+    if ((rc = R.need(kTier2Strand, n2))) return rc;
+    if ((rc = R.need(kTier2Ops, c.ops ? n2 * c.ops_stride : 0))) return rc;
+    uint32_t* d_map = R.buf<uint32_t>(kReseedMap);
+    if ((rc = bg_seed_tiered_gather_launch(nr, p.r0, c.reads, c.read_off, d_flag, d_idx, d_boff, R.buf<uint8_t>(kReseedReads),
+                                           R.buf<uint64_t>(kReseedReadOff), d_map, R.st)))
+        return rc;
+    // ---- tier 2: the SMEM call's pass on them
+    SeedCall c2 = c;
+    c2.tiered = nullptr, c2.smem = &c.tiered->smem, c2.tier = nullptr, c2.totals = nullptr;
+    c2.n_reads = n2, c2.reads = R.buf<uint8_t>(kReseedReads), c2.read_off = R.buf<uint64_t>(kReseedReadOff);
+    c2.hits = R.buf<bg_seed_hit_t>(kTier2Hits), c2.strand = R.buf<uint8_t>(kTier2Strand), c2.ops = c.ops ? R.buf<uint8_t>(kTier2Ops) : nullptr;
+    SeedRun R2{c2, R.W};
+    R2.ctx = R.ctx, R2.st = R.st, R2.G = R.G, R2.virt = R.virt, R2.win_max = R.win_max;
+    if ((rc = se_seed_params(c2, n_index, &R2.prm, &R2.smem))) return rc;
+    R2.out.hits = c2.hits, R2.out.ops = c2.ops, R2.out.ops_stride = c2.ops_stride, R2.out.strand = c2.strand;
+    SeedPassRun p2{};
+    p2.nr = n2;
+    p2.nv = R.G * n2;
+    p2.nq = n2 * R2.prm.S;
+    if ((rc = se_pass(R2, p2, any_panic, any_truncated))) return rc;
+    // ---- T3: the better of the two tier winners into the caller's slots
+    if ((rc = bg_seed_tiered_merge_launch(n2, p.r0, d_map, R.out, strand1, c2.hits, c2.strand, c2.ops, c.tier, R.st))) return rc;
+    *rows += p2.n_sa_rows;
+    *cand += p2.C;
+    *reseeded += n2;
+    return BG_OK;
+}
+
+// The call's checks, its passes, its totals.
+int se_run(const SeedCall& c) {
+    if (!c.fm || !c.sc || (!c.prm && !c.smem && !c.tiered) || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
+    const uint64_t n_index = c.fm->wide ? c.fm->wdev.n : (uint64_t)c.fm->dev.n;
+    const bg_smem_seed_params_t* sp = c.tiered ? &c.tiered->smem : c.smem;  // the SMEM seeds of the call, if it has any
+    const bg_seed_params_t* wp = c.tiered ? &c.tiered->window : c.prm;      // its window seeds, if it has any
+    if (sp) {  // an FMD index over T$R$ (FMDIndex::from's assert, as K7 checks it)
+        if (!c.fm->fmd_ok) return BG_ERR_UNSUPPORTED;
+        if (n_index < 2 || n_index % 2) return BG_ERR_INVALID_ARG;
+    }
+    if (!c.fm->d_text || c.fm->sa_kind == 0) return BG_ERR_INVALID_ARG;  // needs bg_fm_set_text + a suffix array
+    if (sp && (sp->min_seed_len == 0 || sp->max_smems == 0 || sp->max_occ == 0)) return BG_ERR_INVALID_ARG;
+    if (wp && (wp->seed_len == 0 || wp->stride == 0 || wp->max_occ == 0)) return BG_ERR_INVALID_ARG;
+    if (c.tiered && c.tiered->window.pad != c.tiered->smem.pad) return BG_ERR_INVALID_ARG;  // one ops_stride, one merge distance
+    if (sp && (uint64_t)sp->max_smems * sp->max_occ > kMaxProposals) return BG_ERR_UNSUPPORTED;
+    if (c.max_read_len > 65535 || c.pad() > 65535) return BG_ERR_TOO_LARGE;
+    if (sp && c.max_read_len > 65534) return BG_ERR_TOO_LARGE;  // K7's own limit
+    if (c.rescue && c.pair->max_span > 65535) return BG_ERR_TOO_LARGE;
+    const uint32_t win_max = c.max_read_len + 2 * c.pad();
+    const uint32_t rwin_max = c.rescue ? c.pair->max_span : 0;
+    if (c.ops && c.ops_stride < (uint64_t)c.max_read_len + std::max(win_max, rwin_max) + 4) return BG_ERR_OPS_CAP;
+    int rc;
+    SeedPrm prm = {};
+    SeedSmemPrm smem = {};
+    if (c.tiered && (rc = se_seed_params(c, n_index, &prm, &smem))) return rc;  // (its limits refuse before any output is touched)
+    if (c.totals) c.totals[0] = c.totals[1] = 0;
+    if (c.totals && c.rescue) c.totals[2] = c.totals[3] = 0;
+    if (c.totals && c.tiered) c.totals[2] = 0;
+    if (c.n_reads == 0) return BG_OK;
+    bg_ctx* ctx = c.fm->ctx;
+    hipStream_t st = (hipStream_t)c.stream;
+    BG_HIP(hipSetDevice(ctx->device));
+    bg_scratch_guard guard(ctx, st);  // ctx->seed is one scratch set: calls on other streams wait for this one's last kernel
+    if ((rc = se_seed_params(c, n_index, &prm, &smem))) return rc;
     if (!ctx->seed) ctx->seed = new bg_seed_scratch();
     bg_seed_scratch& W = *ctx->seed;
     if (!W.h_tot) BG_HIP(hipHostMalloc((void**)&W.h_tot, 64, hipHostMallocDefault));
@@ -720,8 +829,11 @@ int se_run(const SeedCall& c) {
     R.virt = c.strands == BG_STRAND_REVERSE || c.strands == BG_STRAND_BOTH;
     R.out.hits = c.hits, R.out.ops = c.ops, R.out.ops_stride = c.ops_stride, R.out.strand = c.strand;
     R.out.pairs = c.pairs, R.out.multi = c.multi, R.out.rescued = c.rescued;
-    int rc;
-    uint64_t done_hits = 0, done_cand = 0, done_rescue = 0;
+    if (c.tiered && !c.strand) {  // T3 chooses by the tier winners' strands: tier 1's go to scratch where the caller keeps none
+        if ((rc = R.need(kTier1Strand, c.n_reads))) return rc;
+        R.out.strand = R.buf<uint8_t>(kTier1Strand);
+    }
+    uint64_t done_hits = 0, done_cand = 0, done_rescue = 0, done_reseed = 0;
     bool any_panic = false, any_truncated = false;
     // reads per pass: bounds the scratch (seed slots, proposals, candidate pairs); bg_set_option("seed_chunk_reads") for tests
     // (default: up to 2^21 virtual reads per pass, the passes of a call of equal size).  The option counts the caller's reads;
@@ -735,10 +847,10 @@ int se_run(const SeedCall& c) {
         p.r0 = r0;
         p.nr = std::min(chunk, c.n_reads - r0);
         p.nv = G * p.nr;
-        p.nq = (c.smem ? p.nr : p.nv) * std::max<uint32_t>(prm.S, 1);
-        if ((rc = se_candidates(R, p, &any_panic, &any_truncated))) return rc;
-        if ((rc = se_align(R, p))) return rc;
-        if ((rc = c.rescue ? se_rescue(R, p) : se_reduce(R, p))) return rc;
+        p.nq = (c.smem || c.tiered ? p.nr : p.nv) * std::max<uint32_t>(prm.S, 1);
+        if ((rc = se_pass(R, p, &any_panic, &any_truncated))) return rc;
+        if (c.tiered && (rc = se_reseed(R, p, R.out.strand, n_index, &done_hits, &done_cand, &done_reseed, &any_panic, &any_truncated)))
+            return rc;
         done_hits += p.n_sa_rows;
         done_cand += p.C;
         done_rescue += p.n_rescue;
@@ -747,6 +859,7 @@ int se_run(const SeedCall& c) {
         c.totals[0] = done_hits;
         c.totals[1] = done_cand;
     }
+    if (c.totals && c.tiered) c.totals[2] = done_reseed;
     if (c.totals && c.rescue) {
         // pairs rescued: counted on the device from the bytes R1 / R4 wrote (the call's last wait, outside the passes)
         c.totals[2] = done_rescue;
@@ -819,6 +932,18 @@ extern "C" int bg_seed_extend_smem_batch_dev(bg_fm* fm, const bg_scoring_t* sc, 
     c.fm = fm, c.sc = sc, c.smem = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
     c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
     c.strand = d_strand;
+    return se_run(c);
+}
+
+extern "C" int bg_seed_extend_tiered_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
+                                               uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
+                                               bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_tier, uint8_t* d_ops,
+                                               uint64_t ops_stride, uint64_t* totals, void* stream) {
+    if (!prm || strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.tiered = prm, c.strands = strands, c.n_reads = n_reads, c.reads = d_reads, c.read_off = d_read_off;
+    c.max_read_len = max_read_len, c.hits = d_hits, c.ops = d_ops, c.ops_stride = ops_stride, c.totals = totals, c.stream = stream;
+    c.strand = d_strand, c.tier = d_tier;
     return se_run(c);
 }
 
@@ -905,7 +1030,7 @@ namespace {
 // stream are not set).  The same call runs on device copies; then the reported hits' operations are compacted into ops_buf in
 // slot order (multi mode: max_hits slots per read).
 int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
-    if (!h.fm || !h.sc || (!h.prm && !h.smem) || (h.n_reads && (!h.read_off || !h.hits))) return BG_ERR_INVALID_ARG;
+    if (!h.fm || !h.sc || (!h.prm && !h.smem && !h.tiered) || (h.n_reads && (!h.read_off || !h.hits))) return BG_ERR_INVALID_ARG;
     if (ops_used) *ops_used = 0;
     if (h.n_reads == 0) return BG_OK;
     bg_ctx* ctx = h.fm->ctx;
@@ -923,7 +1048,7 @@ int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t*
     SeedCall d = h;  // the same call on device copies; an output the call does not have stays null
     uint8_t* d_reads = nullptr;
     uint64_t* d_off = nullptr;
-    d.hits = nullptr, d.strand = nullptr, d.pairs = nullptr, d.rescued = nullptr, d.multi = nullptr;
+    d.hits = nullptr, d.strand = nullptr, d.pairs = nullptr, d.rescued = nullptr, d.multi = nullptr, d.tier = nullptr;
     d.max_read_len = (uint32_t)max_len, d.ops_stride = stride, d.stream = ctx->stream;
     int panic_rc = BG_OK;
     auto run = [&]() -> int {
@@ -936,18 +1061,20 @@ int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t*
         if (h.pairs) BG_HIP(hipMalloc((void**)&d.pairs, n_pairs * sizeof(bg_pair_hit_t)));
         if (h.rescued) BG_HIP(hipMalloc((void**)&d.rescued, std::max<uint64_t>(n_pairs, 16)));
         if (h.multi) BG_HIP(hipMalloc((void**)&d.multi, n_reads * sizeof(bg_multi_hit_t)));
+        if (h.tier) BG_HIP(hipMalloc((void**)&d.tier, std::max<uint64_t>(n_reads, 16)));
         if (bytes) BG_HIP(hipMemcpyAsync(d_reads, h.reads, bytes, hipMemcpyHostToDevice, st));
         BG_HIP(hipMemcpyAsync(d_off, h.read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         d.reads = d_reads, d.read_off = d_off;
         int rc = se_run(d);
         // (every read is answered under these two; the stride above is the call's own, so BG_ERR_OPS_CAP is the SMEM cap's)
-        if (rc && rc != BG_ERR_OUT_OF_ALPHABET && !(rc == BG_ERR_OPS_CAP && h.smem)) return rc;
+        if (rc && rc != BG_ERR_OUT_OF_ALPHABET && !(rc == BG_ERR_OPS_CAP && (h.smem || h.tiered))) return rc;
         panic_rc = rc;
         BG_HIP(hipMemcpyAsync(h.hits, d.hits, n_slots * sizeof(bg_seed_hit_t), hipMemcpyDeviceToHost, st));
         if (h.strand) BG_HIP(hipMemcpyAsync(h.strand, d.strand, n_slots, hipMemcpyDeviceToHost, st));
         if (h.pairs) BG_HIP(hipMemcpyAsync(h.pairs, d.pairs, n_pairs * sizeof(bg_pair_hit_t), hipMemcpyDeviceToHost, st));
         if (h.rescued) BG_HIP(hipMemcpyAsync(h.rescued, d.rescued, n_pairs, hipMemcpyDeviceToHost, st));
         if (h.multi) BG_HIP(hipMemcpyAsync(h.multi, d.multi, n_reads * sizeof(bg_multi_hit_t), hipMemcpyDeviceToHost, st));
+        if (h.tier) BG_HIP(hipMemcpyAsync(h.tier, d.tier, n_reads, hipMemcpyDeviceToHost, st));
         if (stride) {
             h_ops.resize(n_slots * stride);
             BG_HIP(hipMemcpyAsync(h_ops.data(), d.ops, n_slots * stride, hipMemcpyDeviceToHost, st));
@@ -956,7 +1083,7 @@ int se_run_host(const SeedCall& h, uint8_t* ops_buf, uint64_t ops_cap, uint64_t*
         return BG_OK;
     };
     int rc = run();
-    for (void* q : {(void*)d_reads, (void*)d_off, (void*)d.hits, (void*)d.ops, (void*)d.strand, (void*)d.pairs, (void*)d.rescued, (void*)d.multi})
+    for (void* q : {(void*)d_reads, (void*)d_off, (void*)d.hits, (void*)d.ops, (void*)d.strand, (void*)d.pairs, (void*)d.rescued, (void*)d.multi, (void*)d.tier})
         hipFree(q);
     if (rc) return rc;
     // compact the winners' operations into the caller's buffer, in read order
@@ -1007,6 +1134,16 @@ extern "C" int bg_seed_extend_smem_batch(bg_fm* fm, const bg_scoring_t* sc, cons
     SeedCall c;
     c.fm = fm, c.sc = sc, c.smem = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
     c.hits = hits, c.strand = strand;
+    return se_run_host(c, ops_buf, ops_cap, ops_used);
+}
+
+extern "C" int bg_seed_extend_tiered_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
+                                           uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
+                                           uint8_t* strand, uint8_t* tier, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used) {
+    if (!prm || strands < BG_STRAND_FORWARD || strands > BG_STRAND_BOTH) return BG_ERR_INVALID_ARG;
+    SeedCall c;
+    c.fm = fm, c.sc = sc, c.tiered = prm, c.strands = strands, c.n_reads = n_reads, c.reads = reads, c.read_off = read_off;
+    c.hits = hits, c.strand = strand, c.tier = tier;
     return se_run_host(c, ops_buf, ops_cap, ops_used);
 }
 

@@ -1,7 +1,8 @@
 // One pass of seed-and-extend as its reduction stages see it (seed_pairs.hip, seed_pairq.hip, seed_multi.hip, seed_rescue.hip,
 // seed_rescueq.hip, and se_best_kernel of seed_extend.hip): what stages S0-S6 of seed_extend.hip left in the pass scratch
 // (SeedPass), where the answers go (SeedOut), and the launchers of the stages, which take these two plus what is their own.
-// The SMEM-seeded call's candidate stages (seed_smem.hip) are declared here as well.
+// The SMEM-seeded call's candidate stages (seed_smem.hip) and the tiered call's own stages (seed_tiered.hip) are declared here as
+// well.
 #ifndef BG_SEED_PASS_H
 #define BG_SEED_PASS_H
 #include "fm_kernels.h"
@@ -85,11 +86,36 @@ int bg_seed_smem_lengths_launch(uint64_t nr, const uint64_t* d_read_off, uint32_
 int bg_seed_smem_seeds_launch(bg_fm* fm, const bgseed::SeedSmemPrm& prm, uint32_t min_seed_len, uint64_t nr, const uint8_t* d_reads,
                               const uint64_t* d_read_off, uint32_t max_read_len, uint32_t* d_count, uint64_t* d_rec, uint32_t* d_votes,
                               uint64_t* d_lower, uint32_t* d_flags, hipStream_t st);
+// S2' alone, over n_q = nr * M record slots that are already written (the tiered call's window records)
+int bg_seed_smem_votes_launch(uint64_t n_q, const bgseed::SeedSmemPrm& prm, const uint32_t* d_count, const uint64_t* d_rec, uint32_t* d_votes,
+                              uint64_t* d_lower, uint32_t* d_flags, hipStream_t st);
 // S4': hits -> (strand, start) proposals, sorted and merged per strand; read r's kept starts go back over pos from hoff[r * M]
 // on, the forward strand's first; per virtual read (G r + g): where its starts begin (soff), candidates, hits, x and y bytes
 int bg_seed_smem_propose_launch(bool wide, const bgseed::SeedSmemPrm& prm, uint64_t nr, const uint64_t* d_read_off, const uint64_t* d_hoff,
                                 const uint64_t* d_rec, uint64_t* d_pos, uint64_t* d_soff, uint32_t* d_n_cand, uint32_t* d_n_hits,
                                 uint32_t* d_x_bytes, uint32_t* d_y_bytes, hipStream_t st);
+// seed_tiered.hip: the tiered call's own stages (bg_seed_extend_tiered_batch).
+// S1": K5's (tag, lower, upper) of the nr * S window slots of the caller's reads -> their records in K7's layout (six uint64 per
+// slot: lower, lower_rev = 0, size, match_size, position, length; size 0 unless the search is Complete) and the reads' own window
+// counts (<= S); a window that reached a byte outside the alphabet sets kFlagPanic
+int bg_seed_tiered_records_launch(uint64_t nr, uint32_t S, uint32_t stride, uint32_t seed_len, const uint64_t* d_read_off,
+                                  const uint8_t* d_tag, const uint64_t* d_lower, const uint64_t* d_upper, uint32_t* d_count,
+                                  uint64_t* d_rec, uint32_t* d_flags, hipStream_t st);
+// T1: per read r of the pass (caller read r0 + r; d_read_off: the caller's offsets): flag = its hit scores below reseed_below,
+// bytes = its length if flagged; tier[r0 + r] = BG_TIER_NONE where the caller has a tier array
+int bg_seed_tiered_select_launch(uint64_t nr, uint64_t r0, const bg_seed_hit_t* d_hits, const uint64_t* d_read_off, int32_t reseed_below,
+                                 uint32_t* d_flag, uint32_t* d_bytes, uint8_t* d_tier, hipStream_t st);
+// T2: the flagged reads back to back (d_idx, d_boff: the scans of T1's two arrays, nr + 1 entries): bytes, idx[nr] + 1 offsets,
+// and map[j] = the read of the pass that compact read j is
+int bg_seed_tiered_gather_launch(uint64_t nr, uint64_t r0, const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_flag,
+                                 const uint64_t* d_idx, const uint64_t* d_boff, uint8_t* d_out, uint64_t* d_out_off, uint32_t* d_map,
+                                 hipStream_t st);
+// T3: the answer of every re-seeded read (seed_tier_rule.h) into the caller's slot r0 + map[j]; d_strand1: tier 1's strand per
+// caller read (O.strand or scratch), rewritten with the winner's; slot j of d_hits2 / d_strand2 / d_ops2 (stride O.ops_stride)
+// is tier 2's answer
+int bg_seed_tiered_merge_launch(uint64_t n2, uint64_t r0, const uint32_t* d_map, const bgseed::SeedOut& O, uint8_t* d_strand1,
+                                const bg_seed_hit_t* d_hits2, const uint8_t* d_strand2, const uint8_t* d_ops2, uint8_t* d_tier,
+                                hipStream_t st);
 // seed_pairs.hip: S7 of the paired call: hits, strand and operations of reads r0 + 2p, r0 + 2p + 1 and pairs[r0 / 2 + p].
 int bg_seed_pairs_launch(const bgseed::SeedPass& P, const bgseed::SeedOut& O, const bg_pair_params_t* pp, hipStream_t st);
 // seed_pairq.hip: S7 of the pairs-mapq call: what bg_seed_pairs_launch writes, plus multi[r0 + 2p], multi[r0 + 2p + 1].

@@ -235,7 +235,12 @@ int bg_seed_smem_seeds_launch(bg_fm* fm, const SeedSmemPrm& prm, uint32_t min_se
     // K7's device entry point reports neither a truncated read nor a panic in its status: both stay in the counts, and S2' turns
     // them into flag bits, so every read of the pass is answered
     if (int rc = bg_fmd_smems_batch64_dev(fm, 1, nr, d_reads, d_read_off, nullptr, min_seed_len, max_read_len, prm.M, d_count, d_rec, st)) return rc;
-    const uint64_t n_q = nr * prm.M;
+    return bg_seed_smem_votes_launch(nr * prm.M, prm, d_count, d_rec, d_votes, d_lower, d_flags, st);
+}
+
+int bg_seed_smem_votes_launch(uint64_t n_q, const SeedSmemPrm& prm, const uint32_t* d_count, const uint64_t* d_rec, uint32_t* d_votes,
+                              uint64_t* d_lower, uint32_t* d_flags, hipStream_t st) {
+    if (!n_q) return BG_OK;
     se_smem_votes_kernel<<<dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, st>>>(n_q, prm, d_count, d_rec, d_votes, d_lower, d_flags);
     BG_HIP(hipGetLastError());
     return BG_OK;

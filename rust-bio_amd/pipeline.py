@@ -10,7 +10,9 @@ paired-end reads and report the best proper FR pair where there is one; the `_pa
 seeded candidate inside its partner's insert window; the `_pairs_mapq` calls add a MAPQ per mate, judged against the pair.  The
 `_multi` calls report up to K loci per read that
 do not touch, the runner-up's score and a MAPQ.  The `_smem` calls take an FMD index over T$R$ and seed both strands with the
-SMEMs of each read (`FMDIndex::all_smems`) instead of fixed windows.  This module only marshals arguments."""
+SMEMs of each read (`FMDIndex::all_smems`) instead of fixed windows.  The `_tiered` calls take the same index, seed every read with
+fixed windows searched once for both strands, and re-seed with SMEMs only the reads whose winner scores below a threshold.  This
+module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -36,6 +38,21 @@ class SmemSeedParams:
 
     def to_c(self):
         return _lib.SMEM_SEED_PARAMS(self.min_seed_len, self.max_smems, self.max_occ, self.pad)
+
+
+class TieredSeedParams:
+    """bg_tiered_seed_params_t: `window` (a SeedParams) seeds every read on the FMD index, `smem` (a SmemSeedParams, the same pad)
+    the reads whose tier-1 winner scores below reseed_below (MIN_SCORE: none, 2**31 - 1: all)."""
+
+    def __init__(self, window=None, smem=None, reseed_below=MIN_SCORE):
+        self.window, self.smem, self.reseed_below = window or SeedParams(), smem or SmemSeedParams(), reseed_below
+
+    @property
+    def pad(self):
+        return max(self.window.pad, self.smem.pad)
+
+    def to_c(self):
+        return _lib.TIERED_SEED_PARAMS(self.window.to_c(), self.smem.to_c(), self.reseed_below)
 
 
 class PairParams:
@@ -93,7 +110,7 @@ def attach_text(fm, text=None, d_text=None):
         _lib.check(_lib.lib().bg_fm_set_text(fm.h, t.ctypes.data, len(t)), "bg_fm_set_text")
 
 
-_OUT_DTYPE = {"strand": np.uint8, "pairs": _lib.PAIR_HIT_DTYPE, "rescued": np.uint8, "multi": _lib.MULTI_HIT_DTYPE}
+_OUT_DTYPE = {"strand": np.uint8, "tier": np.uint8, "pairs": _lib.PAIR_HIT_DTYPE, "rescued": np.uint8, "multi": _lib.MULTI_HIT_DTYPE}
 
 
 def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_out_of_alphabet, modes=(), outs=(), strands=None, K=None,
@@ -101,7 +118,7 @@ def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_ou
     """The host-buffer call bg_<stem>_batch, behind the public function <stem>_arrays.  modes: the mode's parameter objects in the call's order; outs: the
     names of its output arrays after `hits`, in the call's order (keys of _OUT_DTYPE); strands: None for a call without that
     argument; K: slots per read of the multi call; max_span: of a rescue call, whose operation slots also hold a rescue window;
-    allow_truncated: of the SMEM call, whose status BG_ERR_OPS_CAP (-9) says that a read had more records than max_smems.
+    allow_truncated: of the SMEM and tiered calls, whose status BG_ERR_OPS_CAP (-9) says that a read had more records than max_smems.
     Returns (hits, *outs, ops)."""
     name = f"bg_{stem}_batch"
     params = params or SeedParams()
@@ -112,7 +129,7 @@ def _host_call(stem, fm, scoring, reads, read_off, *, params, want_ops, allow_ou
         raise ValueError(f"{stem}_arrays: an odd number of reads")
     hits = np.zeros(n if K is None else (n, K), dtype=_lib.SEED_HIT_DTYPE)
     K = K or 1
-    size = {"strand": n * K, "pairs": n // 2, "rescued": n // 2, "multi": n}
+    size = {"strand": n * K, "tier": n, "pairs": n // 2, "rescued": n // 2, "multi": n}
     arrays = [np.zeros(max(size[o], 1), dtype=_OUT_DTYPE[o]) for o in outs]
     if not want_ops:
         cap = 0
@@ -194,6 +211,27 @@ def seed_extend_smem_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len
     the slots are written before it does."""
     _dev_call("seed_extend_smem", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand], d_ops=d_ops,
               ops_stride=ops_stride, params=params or SmemSeedParams(), stream=stream, totals=totals, strands=strands)
+
+
+def seed_extend_tiered_arrays(fm, scoring, reads, read_off, params=None, strands=_lib.STRAND_BOTH, want_ops=True,
+                              allow_out_of_alphabet=False, allow_truncated=False):
+    """bg_seed_extend_tiered_batch, host buffers: `fm` as seed_extend_smem_arrays takes it.  Returns (hits, strand, tier: uint8[n]
+    of TIER_NONE / TIER_FIRST / TIER_SECOND, ops), hits and ops as seed_extend_smem_arrays.  A window that reaches a byte outside
+    the alphabet, or a re-seeded read on which all_smems panics, raises AlphabetError unless allow_out_of_alphabet; a re-seeded
+    read with more than params.smem.max_smems records raises BiogpuError (OPS_CAP) unless allow_truncated.  Every read is answered
+    either way."""
+    return _host_call("seed_extend_tiered", fm, scoring, reads, read_off, params=params or TieredSeedParams(), want_ops=want_ops,
+                      allow_out_of_alphabet=allow_out_of_alphabet, outs=["strand", "tier"], strands=strands,
+                      allow_truncated=allow_truncated)
+
+
+def seed_extend_tiered_dev(fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits, d_strand=0, d_tier=0, d_ops=0, ops_stride=0,
+                           params=None, strands=_lib.STRAND_BOTH, stream=0, totals=None):
+    """bg_seed_extend_tiered_batch_dev (pointers are ints; d_strand / d_tier / d_ops may be 0); `totals`, if given, is a uint64[3]
+    numpy array that receives (suffix-array rows resolved, candidates aligned, reads re-seeded), the first two over both tiers.
+    Raises as seed_extend_tiered_arrays without its switches; the slots are written before it does."""
+    _dev_call("seed_extend_tiered", fm, scoring, n_reads, d_reads, d_read_off, max_read_len, d_hits=d_hits, d_outs=[d_strand, d_tier],
+              d_ops=d_ops, ops_stride=ops_stride, params=params or TieredSeedParams(), stream=stream, totals=totals, strands=strands)
 
 
 def seed_extend_pairs_arrays(fm, scoring, reads, read_off, params=None, pair_params=None, want_ops=True, allow_out_of_alphabet=False):
