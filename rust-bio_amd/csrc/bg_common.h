@@ -100,7 +100,9 @@ struct bg_ctx {
 
 // grow-only device scratch
 int bg_reserve(void** p, size_t* cur, size_t need);
-// exclusive scan of n uint32 counts into n + 1 uint64 offsets (fastq_ingest.hip); d_sums: 2 * (n / 2048 + 1) uint64 of scratch
+// exclusive scan of n uint32 counts into n + 1 uint64 offsets, d_off[n] the total (scan.hip).  d_sums: scratch of
+// 2 * (n / 2048 + 1) uint64 — a sum and a base for each of the n / 2048 + 1 blocks; that is all it touches.  Callers that
+// reserve 2 * (n / 2048 + 2) words carry two words of slack.
 int bg_scan_u32(const uint32_t* d_len, uint64_t n, uint64_t* d_off, uint64_t* d_sums, hipStream_t st);
 // bg_align_batch_dev with what the caller knows about the lengths: 1 all pairs share (m, n), 0 they differ, -1 unknown
 int bg_align_batch_dev_hint(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint64_t n_pairs, const uint8_t* d_x,

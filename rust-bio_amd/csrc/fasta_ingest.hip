@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "bg_common.h"
+#include "dna_complement.h"
 #include "white_space.h"
 
 namespace {
@@ -533,25 +534,6 @@ __global__ __launch_bounds__(256) void fa_error_kernel(const uint8_t* __restrict
 }
 
 // ---- the reference builder ----------------------------------------------------------------------------------------------
-// dna::complement (alphabets/dna.rs), the byte map of bg_revcomp_batch_dev: AGCTYRWSKMDVHBN -> TCGARYWSMKHBDVN, the same in
-// lower case, every other byte ('$' too) itself
-struct alignas(16) FaComplement {
-    uint8_t v[256];
-};
-constexpr FaComplement fa_make_complement() {
-    FaComplement t{};
-    for (int i = 0; i < 256; i++) t.v[i] = (uint8_t)i;
-    const char* a = "AGCTYRWSKMDVHBN";
-    const char* b = "TCGARYWSMKHBDVN";
-    for (int i = 0; a[i]; i++) {
-        t.v[(uint8_t)a[i]] = (uint8_t)b[i];
-        t.v[(uint8_t)a[i] + 32] = (uint8_t)(b[i] + 32);
-    }
-    return t;
-}
-constexpr FaComplement kFaComplementHost = fa_make_complement();
-__constant__ FaComplement kFaComplement = fa_make_complement();
-
 // R1: starts[i] = sum over j < i of (seq_len_j + 1), name_off[i] = sum of id_len_j (n + 1 entries each); the first record whose
 // check is not OK.  One block; contigs are few next to the bases they hold.
 __global__ __launch_bounds__(1024) void fa_ref_layout_kernel(const bg_fasta_record_t* __restrict__ recs, uint64_t n, uint64_t* __restrict__ starts,
@@ -610,9 +592,8 @@ __global__ __launch_bounds__(256) void fa_ref_contigs_kernel(const bg_fasta_reco
 __global__ __launch_bounds__(256) void fa_ref_text_kernel(const bg_fasta_record_t* __restrict__ recs, uint64_t n, const uint8_t* __restrict__ seq,
                                                           const uint64_t* __restrict__ starts, uint64_t n_t, uint64_t n_text, int upper,
                                                           uint8_t* __restrict__ out) {
-    __shared__ FaComplement s_comp;
-    if (threadIdx.x < 64) ((uint32_t*)s_comp.v)[threadIdx.x] = ((const uint32_t*)kFaComplement.v)[threadIdx.x];
-    __syncthreads();
+    __shared__ __attribute__((aligned(4))) uint8_t s_comp[256];
+    load_complement(s_comp);
     const uint64_t q0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
     if (q0 >= n_text) return;
     uint64_t ci = kFaNone;
@@ -639,7 +620,7 @@ __global__ __launch_bounds__(256) void fa_ref_text_kernel(const bg_fasta_record_
             if (r < recs[ci].seq_len) {
                 c = seq[recs[ci].seq_off + r];
                 if (upper && c >= 'a' && c <= 'z') c -= 32;
-                if (rev) c = s_comp.v[c];
+                if (rev) c = s_comp[c];
             }
         }
         w[j >> 2] |= c << (8 * (j & 3));
@@ -861,8 +842,9 @@ extern "C" int bg_fasta_reference(bg_ctx* ctx, uint64_t n_records, const bg_fast
         if (o < n_t || !fmd) text_out[o++] = '$';
     }
     if (fmd) {  // T $ R $ with R = dna::revcomp(T)
+        constexpr ComplementTable comp = make_complement();
         text_out[n_t] = '$';
-        for (uint64_t j = 0; j < n_t; j++) text_out[2 * n_t - j] = kFaComplementHost.v[text_out[j]];
+        for (uint64_t j = 0; j < n_t; j++) text_out[2 * n_t - j] = comp.v[text_out[j]];
         text_out[2 * n_t + 1] = '$';
     }
     return BG_OK;

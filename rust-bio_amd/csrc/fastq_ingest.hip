@@ -1,6 +1,5 @@
 // FASTQ ingest on the device: bio::io::fastq::Reader::read / Records and Record::check
-// (/root/reference/src/io/fastq.rs:266-303, 388-410, 508-527) over a text that is already in HBM, and CIGAR
-// emission (bio-types 1.0 Alignment::cigar) for a batch of alignment records.
+// (/root/reference/src/io/fastq.rs:266-303, 388-410, 508-527) over a text that is already in HBM.
 //
 // The reader is a sequential state machine over LINES (a record is a header line, sequence lines up to a line
 // that starts with '+', then as many quality lines as there were sequence lines), but nearly every FASTQ is four
@@ -17,7 +16,6 @@
 // Everything is byte/integer work bound by HBM reads of the text (about three passes).
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 #include "bg_common.h"
 #include "white_space.h"
@@ -72,58 +70,6 @@ __global__ __launch_bounds__(256) void fq_count_newlines_kernel(const uint8_t* _
         cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
         hi[blockIdx.x] = (uint8_t)(sh[0] | sh[1] | sh[2] | sh[3]);
     }
-}
-// exclusive scan of up to 2^32 items by one block (items are per-chunk / per-block partial sums: few).  4096 items per trip:
-// four per thread, wavefront scans by shuffles, the sixteen wavefront totals scanned by the first wavefront — three barriers a
-// trip.  (Until round 6 a Hillis-Steele scan in LDS, twenty barriers per 1024 items: 320 us for the 14 000 partial sums of a
-// seed-and-extend pass, four times per pass.)
-template <typename T>
-__global__ __launch_bounds__(1024) void fq_scan_small_kernel(const T* __restrict__ in, uint64_t* __restrict__ out, uint64_t n, uint64_t* total) {
-    __shared__ uint64_t s_w[16], s_wb[17];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto shfl_up64 = [](uint64_t v, int o) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), o);
-        return (uint64_t)hi << 32 | lo;
-    };
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < n; b += 4096) {
-        const uint64_t i0 = b + (uint64_t)tid * 4;
-        uint64_t v[4], tsum = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            v[k] = i0 + k < n ? (uint64_t)in[i0 + k] : 0;
-            tsum += v[k];
-        }
-        uint64_t incl = tsum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t u = shfl_up64(incl, o);
-            if ((int)lane >= o) incl += u;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        if (wave == 0) {
-            const uint64_t w = lane < 16 ? s_w[lane] : 0;
-            uint64_t wi = w;
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const uint64_t u = shfl_up64(wi, o);
-                if ((int)lane >= o) wi += u;
-            }
-            if (lane < 16) s_wb[lane] = wi - w;
-            if (lane == 15) s_wb[16] = wi;
-        }
-        __syncthreads();
-        uint64_t run = carry + s_wb[wave] + incl - tsum;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (i0 + k < n) out[i0 + k] = run;
-            run += v[k];
-        }
-        carry += s_wb[16];
-        __syncthreads();
-    }
-    if (tid == 0 && total) *total = carry;
 }
 __global__ __launch_bounds__(256) void fq_line_starts_kernel(const uint8_t* __restrict__ t, uint64_t len, const uint64_t* __restrict__ base,
                                                              uint64_t* __restrict__ ls) {
@@ -376,46 +322,6 @@ __global__ __launch_bounds__(256) void fq_measure_kernel(const uint8_t* __restri
     recs[k] = o;
     seq_len[k] = (uint32_t)sl;
     qual_len[k] = (uint32_t)ql;
-}
-// exclusive scan of uint32 lengths into uint64 offsets, three kernels
-__global__ __launch_bounds__(256) void fq_block_sums_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ sums) {
-    const uint64_t b0 = (uint64_t)blockIdx.x * 2048;
-    uint64_t v = 0;
-    for (int i = 0; i < 8; i++) {
-        const uint64_t j = b0 + (uint64_t)i * 256 + threadIdx.x;
-        if (j < n) v += in[j];
-    }
-    __shared__ uint64_t s[4];
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-__global__ __launch_bounds__(256) void fq_scan_apply_kernel(const uint32_t* __restrict__ in, uint64_t n, const uint64_t* __restrict__ base,
-                                                            uint64_t* __restrict__ out) {
-    __shared__ uint64_t s[256];
-    const uint64_t b0 = (uint64_t)blockIdx.x * 2048 + (uint64_t)threadIdx.x * 8;
-    uint64_t loc[8], v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        loc[i] = b0 + i < n ? in[b0 + i] : 0;
-        v += loc[i];
-    }
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint64_t u = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0;
-        __syncthreads();
-        s[threadIdx.x] += u;
-        __syncthreads();
-    }
-    uint64_t run = base[blockIdx.x] + s[threadIdx.x] - v;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        if (b0 + i <= n) out[b0 + i] = run;  // index n: the closing offset
-        run += loc[i];
-    }
 }
 
 // ---- F6: gather + Record::check (fastq.rs:388-410) ----------------------------------------------------
@@ -1236,170 +1142,7 @@ __global__ __launch_bounds__(256) void fq_fused_kernel(const FusedArgs a) {
     }
 }
 
-int scan_lengths(const uint32_t* d_len, uint64_t n, uint64_t* d_off, uint64_t* d_sums, hipStream_t st) {
-    const uint32_t nb = (uint32_t)(n / 2048 + 1);  // one more block than items need: it writes the closing offset
-    fq_block_sums_kernel<<<dim3(nb), dim3(256), 0, st>>>(d_len, n, d_sums);
-    fq_scan_small_kernel<uint64_t><<<dim3(1), dim3(1024), 0, st>>>(d_sums, d_sums + nb, nb, nullptr);
-    fq_scan_apply_kernel<<<dim3(nb), dim3(256), 0, st>>>(d_len, n, d_sums + nb, d_off);
-    BG_HIP(hipGetLastError());
-    return BG_OK;
-}
-
-// ---- CIGAR ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t put_num(char* o, uint32_t v) {
-    char tmp[10];
-    uint32_t n = 0;
-    do {
-        tmp[n++] = (char)('0' + v % 10);
-        v /= 10;
-    } while (v);
-    for (uint32_t i = 0; i < n; i++) o[i] = tmp[n - 1 - i];
-    return n;
-}
-// one thread per alignment; out slot of `stride` chars per alignment, len[p] = chars written or a negative status
-__global__ __launch_bounds__(256) void cigar_kernel(const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ ops, uint64_t n, int hard_clip,
-                                                    char* __restrict__ out, uint64_t stride, int32_t* __restrict__ len) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const bg_alignment_t a = aln[p];
-    if (a.mode == BG_MODE_CUSTOM) {  // bio-types: "Cigar fn not supported for custom alignment mode" (panic)
-        len[p] = BG_ERR_UNSUPPORTED;
-        return;
-    }
-    char* o = out + p * stride;
-    uint64_t w = 0;
-    const char clip = hard_clip ? 'H' : 'S';
-    bool overflow = false;
-    auto emit = [&](uint32_t k, char c) {
-        if (w + 11 > stride) {
-            overflow = true;
-            return;
-        }
-        w += put_num(o + w, k);
-        o[w++] = c;
-    };
-    auto add = [&](uint32_t kind, uint32_t k) {
-        if (kind == BG_OP_MATCH) emit(k, '=');
-        else if (kind == BG_OP_SUBST) emit(k, 'X');
-        else if (kind == BG_OP_DEL) emit(k, 'D');
-        else if (kind == BG_OP_INS) emit(k, 'I');
-    };
-    if (a.n_ops) {
-        const uint8_t* q = ops + a.ops_off;
-        uint32_t last = q[0], k = 1;
-        if (a.xstart > 0) emit(a.xstart, clip);
-        for (uint32_t i = 1; i < a.n_ops; i++) {
-            const uint32_t op = q[i];
-            if (op == last) {
-                k++;
-            } else {
-                add(last, k);
-                k = 1;
-            }
-            last = op;
-        }
-        add(last, k);
-        if (a.xlen > a.xend) emit(a.xlen - a.xend, clip);
-    }
-    len[p] = overflow ? BG_ERR_OPS_CAP : (int32_t)w;
-}
-
-// Alignment::pretty(x, y, ncol) (bio-types): three rows — x, the operation marks ('|' match, '\\' mismatch, '+' insertion,
-// 'x' deletion, ' ' clipped), y — cut into blocks of ncol columns, every block "x row\n marks\n y row\n\n\n".  The standard
-// modes print the clipped prefixes / suffixes of x and y around the operations, AlignmentMode::Custom walks its
-// Xclip / Yclip operations instead (the crate prints the FIRST len symbols of the sequence for a clip operation,
-// wherever the clip sits: reproduced).  One thread per alignment; two passes over the operations (length, then text).
-__global__ __launch_bounds__(256) void pretty_kernel(const bg_alignment_t* __restrict__ aln, const uint8_t* __restrict__ ops, uint64_t n,
-                                                     const uint8_t* __restrict__ xs, const uint64_t* __restrict__ x_off,
-                                                     const uint8_t* __restrict__ ys, const uint64_t* __restrict__ y_off, uint32_t ncol,
-                                                     char* __restrict__ out, uint64_t stride, int64_t* __restrict__ len) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const bg_alignment_t a = aln[p];
-    const uint8_t* x = xs + x_off[p];
-    const uint8_t* y = ys + y_off[p];
-    const uint64_t xl = x_off[p + 1] - x_off[p], yl = y_off[p + 1] - y_off[p];
-    char* o = out + p * stride;
-    bool bad = xl != a.xlen || yl != a.ylen;  // not the sequences this alignment was computed from
-    uint64_t ml = 0;
-    for (int pass = 0; pass < 2 && !bad; pass++) {
-        uint64_t col = 0;
-        auto put = [&](uint8_t cx, char ci, uint8_t cy) {
-            if (pass == 1) {
-                const uint64_t blk = col / ncol, w = col - blk * ncol;
-                const uint64_t bl = min((uint64_t)ncol, ml - blk * ncol);
-                char* b = o + blk * (3ull * ncol + 5);
-                b[w] = (char)cx;
-                b[bl + 1 + w] = ci;
-                b[2 * (bl + 1) + w] = (char)cy;
-            }
-            bad = bad || cx >= 0x80 || cy >= 0x80;  // from_utf8_lossy widens such a byte: the crate's length assert fires
-            col++;
-        };
-        if (a.n_ops) {
-            uint64_t xi = 0, yi = 0;
-            const uint8_t* q = ops + a.ops_off;
-            uint32_t clip = 0;
-            if (a.mode != BG_MODE_CUSTOM) {
-                xi = a.xstart;
-                yi = a.ystart;
-                for (uint64_t k = 0; k < a.xstart && k < xl; k++) put(x[k], ' ', ' ');
-                for (uint64_t k = 0; k < a.ystart && k < yl; k++) put(' ', ' ', y[k]);
-            }
-            for (uint32_t i = 0; i < a.n_ops && !bad; i++) {
-                const uint32_t op = q[i];
-                if (op == BG_OP_MATCH || op == BG_OP_SUBST) {
-                    if (xi >= xl || yi >= yl) { bad = true; break; }
-                    put(x[xi++], op == BG_OP_MATCH ? '|' : '\\', y[yi++]);
-                } else if (op == BG_OP_DEL) {
-                    if (yi >= yl) { bad = true; break; }
-                    put('-', 'x', y[yi++]);
-                } else if (op == BG_OP_INS) {
-                    if (xi >= xl) { bad = true; break; }
-                    put(x[xi++], '+', '-');
-                } else {
-                    const uint32_t cl = clip < 4 ? a.clip_len[clip] : 0;
-                    clip++;
-                    if (op == BG_OP_XCLIP) {
-                        for (uint64_t k = 0; k < cl && k < xl; k++, xi++) put(x[k], ' ', ' ');
-                    } else {
-                        for (uint64_t k = 0; k < cl && k < yl; k++, yi++) put(' ', ' ', y[k]);
-                    }
-                }
-            }
-            if (a.mode != BG_MODE_CUSTOM) {
-                for (uint64_t k = xi; k < xl; k++) put(x[k], ' ', ' ');
-                for (uint64_t k = yi; k < yl; k++) put(' ', ' ', y[k]);
-            }
-        }
-        if (pass == 0) {
-            ml = col;
-            const uint64_t nb = (ml + ncol - 1) / ncol;
-            if (3 * ml + 5 * nb > stride) {
-                len[p] = BG_ERR_OPS_CAP;
-                return;
-            }
-        }
-    }
-    if (bad) {
-        len[p] = BG_ERR_UNSUPPORTED;
-        return;
-    }
-    const uint64_t nb = (ml + ncol - 1) / ncol;
-    for (uint64_t blk = 0; blk < nb; blk++) {
-        const uint64_t bl = min((uint64_t)ncol, ml - blk * ncol);
-        char* b = o + blk * (3ull * ncol + 5);
-        b[bl] = b[2 * bl + 1] = b[3 * bl + 2] = b[3 * bl + 3] = b[3 * bl + 4] = '\n';
-    }
-    len[p] = (int64_t)(3 * ml + 5 * nb);
-}
-
 }  // namespace
-
-// shared with seed_extend.hip: exclusive scan of n uint32 counts into n + 1 uint64 offsets; d_sums holds 2 * (n / 2048 + 1) words
-int bg_scan_u32(const uint32_t* d_len, uint64_t n, uint64_t* d_off, uint64_t* d_sums, hipStream_t st) {
-    return scan_lengths(d_len, n, d_off, d_sums, st);
-}
 
 extern "C" int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t len, bg_fastq_record_t* d_recs, uint64_t rec_cap, uint8_t* d_seq,
                                   uint64_t* d_seq_off, uint8_t* d_qual, uint64_t* d_qual_off, uint64_t* n_records, int32_t* status,
@@ -1411,13 +1154,14 @@ extern "C" int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
     hipStream_t st = (hipStream_t)stream;
     bg_scratch_guard guard(ctx, st);
     BG_HIP(hipSetDevice(ctx->device));
-    if (len == 0) {
+    auto no_records = [&]() -> int {  // the offsets of an empty result
         const uint64_t z = 0;
         if (d_seq_off) BG_HIP(hipMemcpyAsync(d_seq_off, &z, 8, hipMemcpyHostToDevice, st));
         if (d_qual_off) BG_HIP(hipMemcpyAsync(d_qual_off, &z, 8, hipMemcpyHostToDevice, st));
         BG_HIP(hipStreamSynchronize(st));
         return BG_OK;
-    }
+    };
+    if (len == 0) return no_records();
     if (!d_text || !d_recs || !d_seq || !d_seq_off || !d_qual || !d_qual_off) return BG_ERR_INVALID_ARG;
     int rc;
     // FF: the one-pass reader (four-line ASCII records: nearly every FASTQ); anything else raises its flag and takes F1 .. F6
@@ -1427,18 +1171,8 @@ extern "C" int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
             const size_t words = 6 * n_tiles + 8;
             if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, words * 8))) return rc;
             BG_HIP(hipMemsetAsync(ctx->aux, 0, words * 8, st));
-            FusedArgs fa = {};
-            fa.t = d_text;
-            fa.len = len;
-            fa.tiles = (uint64_t*)ctx->aux;
-            fa.out = fa.tiles + 6 * n_tiles;
-            fa.recs = d_recs;
-            fa.rec_cap = rec_cap;
-            fa.seq = d_seq;
-            fa.qual = d_qual;
-            fa.seq_off = d_seq_off;
-            fa.qual_off = d_qual_off;
-            fa.n_tiles = (uint32_t)n_tiles;
+            uint64_t* const tiles = (uint64_t*)ctx->aux;
+            const FusedArgs fa = {d_text, len, tiles, tiles + 6 * n_tiles, d_recs, rec_cap, d_seq, d_qual, d_seq_off, d_qual_off, (uint32_t)n_tiles};
             fq_fused_kernel<<<dim3((uint32_t)n_tiles), dim3(256), 0, st>>>(fa);
             BG_HIP(hipGetLastError());
             uint64_t res[4] = {0, 1, 0, 0};
@@ -1461,8 +1195,7 @@ extern "C" int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
     uint64_t* d_part = d_total + 2;
     uint8_t* d_hi = (uint8_t*)(d_part + n_part);
     fq_count_newlines_kernel<<<dim3((uint32_t)nchunks), dim3(256), 0, st>>>(d_text, len, d_cnt, d_hi);
-    // (a single block scanning the ~79 000 chunk counts of a 323 MB text took 148 us; block sums + their scan + apply: 20)
-    if ((rc = scan_lengths(d_cnt, nchunks, d_base, d_part, st))) return rc;
+    if ((rc = bg_scan_u32(d_cnt, nchunks, d_base, d_part, st))) return rc;
     BG_HIP(hipGetLastError());
     uint64_t n_nl = 0;
     uint8_t last_byte = 0;
@@ -1517,17 +1250,11 @@ extern "C" int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
     }
     *n_records = n_rec;
     if (n_rec > rec_cap) return BG_ERR_TOO_LARGE;
-    if (n_rec == 0) {
-        const uint64_t z = 0;
-        BG_HIP(hipMemcpyAsync(d_seq_off, &z, 8, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_qual_off, &z, 8, hipMemcpyHostToDevice, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return BG_OK;
-    }
+    if (n_rec == 0) return no_records();
     // F5, F6
     fq_measure_kernel<<<dim3((uint32_t)((n_rec + 255) / 256)), dim3(256), 0, st>>>(d_text, d_ls, d_info, n_lines, d_rl, n_rec, d_recs, d_sl, d_ql);
-    if ((rc = scan_lengths(d_sl, n_rec, d_seq_off, d_sum, st))) return rc;
-    if ((rc = scan_lengths(d_ql, n_rec, d_qual_off, d_sum, st))) return rc;
+    if ((rc = bg_scan_u32(d_sl, n_rec, d_seq_off, d_sum, st))) return rc;
+    if ((rc = bg_scan_u32(d_ql, n_rec, d_qual_off, d_sum, st))) return rc;
     if (len / n_lines <= 256)
         fq_gather_kernel<16><<<dim3((uint32_t)((n_rec + 15) / 16)), dim3(256), 0, st>>>(d_text, len, d_ls, d_info, n_lines, d_rl, n_rec, d_recs, d_seq_off,
                                                                                           d_qual_off, d_seq, d_qual);
@@ -1567,115 +1294,4 @@ extern "C" int bg_fastq_parse(bg_ctx* ctx, const uint8_t* text, uint64_t len, bg
         BG_HIP(hipStreamSynchronize(st));
     }
     return BG_OK;
-}
-
-extern "C" int bg_cigar_batch_dev(bg_ctx* ctx, uint64_t n, const bg_alignment_t* d_aln, const uint8_t* d_ops, int hard_clip, char* d_out,
-                                  uint64_t stride, int32_t* d_len, void* stream) {
-    if (!ctx) return BG_ERR_INVALID_ARG;
-    if (n == 0) return BG_OK;
-    if (!d_aln || !d_out || !d_len || stride < 24) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    cigar_kernel<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(d_aln, d_ops, n, hard_clip, d_out, stride, d_len);
-    BG_HIP(hipGetLastError());
-    return BG_OK;
-}
-
-extern "C" int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const uint8_t* ops, uint64_t ops_bytes, const uint8_t* x,
-                               const uint64_t* x_off, const uint8_t* y, const uint64_t* y_off, uint32_t ncol, char* out, uint64_t out_cap,
-                               uint64_t* out_off) {
-    if (!ctx || !out_off || ncol == 0) return BG_ERR_INVALID_ARG;
-    out_off[0] = 0;
-    if (n == 0) return BG_OK;
-    if (!aln || (!ops && ops_bytes) || !x_off || !y_off || !out) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    uint64_t max_ml = 0;
-    for (uint64_t p = 0; p < n; p++) {
-        if (aln[p].n_ops && aln[p].ops_off + aln[p].n_ops > ops_bytes) return BG_ERR_INVALID_ARG;
-        max_ml = std::max<uint64_t>(max_ml, (x_off[p + 1] - x_off[p]) + (y_off[p + 1] - y_off[p]));
-    }
-    const uint64_t stride = (3 * max_ml + 5 * ((max_ml + ncol - 1) / ncol) + 15) & ~15ull;
-    const uint64_t xb = x_off[n], yb = y_off[n];
-    void* d[8] = {};
-    const size_t need[8] = {n * sizeof(bg_alignment_t), std::max<uint64_t>(ops_bytes, 16), std::max<uint64_t>(xb, 16), (n + 1) * 8,
-                            std::max<uint64_t>(yb, 16), (n + 1) * 8, std::max<uint64_t>(n * stride, 16), n * 8};
-    const void* src[6] = {aln, ops, x, x_off, y, y_off};
-    const size_t src_bytes[6] = {need[0], (size_t)ops_bytes, (size_t)xb, need[3], (size_t)yb, need[5]};
-    std::vector<char> h;
-    std::vector<int64_t> hl(n);
-    auto run = [&]() -> int {
-        hipStream_t st = ctx->stream;
-        for (int i = 0; i < 8; i++) BG_HIP(hipMalloc(&d[i], need[i]));
-        for (int i = 0; i < 6; i++)
-            if (src_bytes[i]) BG_HIP(hipMemcpyAsync(d[i], src[i], src_bytes[i], hipMemcpyHostToDevice, st));
-        pretty_kernel<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st>>>((const bg_alignment_t*)d[0], (const uint8_t*)d[1], n,
-                                                                              (const uint8_t*)d[2], (const uint64_t*)d[3], (const uint8_t*)d[4],
-                                                                              (const uint64_t*)d[5], ncol, (char*)d[6], stride, (int64_t*)d[7]);
-        BG_HIP(hipGetLastError());
-        h.resize((size_t)(n * stride));
-        BG_HIP(hipMemcpyAsync(h.data(), d[6], n * stride, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(hl.data(), d[7], n * 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return BG_OK;
-    };
-    int rc = run();
-    for (void* q : d) hipFree(q);
-    if (rc) return rc;
-    uint64_t used = 0;
-    int status = BG_OK;
-    for (uint64_t p = 0; p < n; p++) {
-        if (hl[p] < 0) {
-            status = (int)hl[p];
-            out_off[p + 1] = used;
-            continue;
-        }
-        if (used + (uint64_t)hl[p] > out_cap) return BG_ERR_OPS_CAP;
-        memcpy(out + used, h.data() + p * stride, (size_t)hl[p]);
-        used += (uint64_t)hl[p];
-        out_off[p + 1] = used;
-    }
-    return status;
-}
-
-extern "C" int bg_cigar_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const uint8_t* ops, uint64_t ops_bytes, int hard_clip, char* out,
-                              uint64_t out_cap, uint64_t* out_off) {
-    if (!ctx || !out_off) return BG_ERR_INVALID_ARG;
-    out_off[0] = 0;
-    if (n == 0) return BG_OK;
-    if (!aln || (!ops && ops_bytes) || !out) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    uint32_t max_ops = 0;
-    for (uint64_t p = 0; p < n; p++) {
-        if (aln[p].n_ops && aln[p].ops_off + aln[p].n_ops > ops_bytes) return BG_ERR_INVALID_ARG;
-        max_ops = std::max(max_ops, aln[p].n_ops);
-    }
-    const uint64_t stride = ((uint64_t)max_ops * 2 + 24 + 11 + 15) & ~15ull;  // every run is at least "1=": two chars per op, + two clips
-    int rc;
-    const size_t need[4] = {n * sizeof(bg_alignment_t), std::max<uint64_t>(ops_bytes, 16), n * stride, n * 4};
-    for (int i = 0; i < 4; i++)
-        if ((rc = bg_reserve(&ctx->io[i], &ctx->io_cap[i], need[i]))) return rc;
-    hipStream_t st = ctx->stream;
-    BG_HIP(hipMemcpyAsync(ctx->io[0], aln, need[0], hipMemcpyHostToDevice, st));
-    if (ops_bytes) BG_HIP(hipMemcpyAsync(ctx->io[1], ops, ops_bytes, hipMemcpyHostToDevice, st));
-    rc = bg_cigar_batch_dev(ctx, n, (const bg_alignment_t*)ctx->io[0], (const uint8_t*)ctx->io[1], hard_clip, (char*)ctx->io[2], stride,
-                            (int32_t*)ctx->io[3], st);
-    if (rc) return rc;
-    std::vector<char> h((size_t)(n * stride));
-    std::vector<int32_t> hl(n);
-    BG_HIP(hipMemcpyAsync(h.data(), ctx->io[2], n * stride, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(hl.data(), ctx->io[3], n * 4, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    uint64_t used = 0;
-    int status = BG_OK;
-    for (uint64_t p = 0; p < n; p++) {
-        if (hl[p] < 0) {
-            status = hl[p];  // BG_ERR_UNSUPPORTED: AlignmentMode::Custom (the reference panics)
-            out_off[p + 1] = used;
-            continue;
-        }
-        if (used + (uint64_t)hl[p] > out_cap) return BG_ERR_OPS_CAP;
-        memcpy(out + used, h.data() + p * stride, (size_t)hl[p]);
-        used += (uint64_t)hl[p];
-        out_off[p + 1] = used;
-    }
-    return status;
 }

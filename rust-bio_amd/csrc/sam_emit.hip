@@ -11,6 +11,7 @@
 // (sam_line), so they cannot disagree about a length.
 #include <algorithm>
 
+#include "dna_complement.h"
 #include "fm_kernels.h"
 
 namespace {
@@ -42,23 +43,6 @@ struct SamDesc {  // what the length pass learned from a slot's operations, and 
     uint32_t cigar_at, md_at;  // 0: no such string (a line never starts with either)
     uint32_t reserved;
 };
-
-// dna::complement, as seed_extend.hip tabulates it for bg_revcomp_batch_dev
-struct alignas(16) ComplementTable {
-    uint8_t v[256];
-};
-constexpr ComplementTable make_complement() {
-    ComplementTable t{};
-    for (int i = 0; i < 256; i++) t.v[i] = (uint8_t)i;
-    const char* a = "AGCTYRWSKMDVHBN";
-    const char* b = "TCGARYWSMKHBDVN";
-    for (int i = 0; a[i]; i++) {
-        t.v[(uint8_t)a[i]] = (uint8_t)b[i];
-        t.v[(uint8_t)a[i] + 32] = (uint8_t)(b[i] + 32);
-    }
-    return t;
-}
-__constant__ ComplementTable kSamComplement = make_complement();
 
 __device__ __forceinline__ uint32_t ndig(uint64_t v) {
     uint32_t n = 1;
@@ -165,7 +149,7 @@ __device__ SamLine sam_line(const SamArgs& a, uint64_t slot) {
     return L;
 }
 
-// The CIGAR of cigar_kernel (fastq_ingest.hip) with soft clips; o == nullptr: only its length.
+// The CIGAR of cigar_kernel (align_text.hip) with soft clips; o == nullptr: only its length.
 __device__ uint32_t sam_cigar(const bg_alignment_t& al, const uint8_t* __restrict__ q, char* o) {
     if (!al.n_ops) return 0;
     uint32_t w = 0;
@@ -393,8 +377,7 @@ __global__ __launch_bounds__(256) void sam_write_kernel(const SamArgs a, const S
                                                         char* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) char s_stage[(256 / G) * kStageBuf];
     __shared__ __attribute__((aligned(4))) uint8_t s_comp[256];
-    if (threadIdx.x < 64) ((uint32_t*)s_comp)[threadIdx.x] = ((const uint32_t*)kSamComplement.v)[threadIdx.x];
-    __syncthreads();
+    load_complement(s_comp);
     const uint32_t g = threadIdx.x / G, lane = threadIdx.x % G;
     const uint64_t slot = (uint64_t)blockIdx.x * (256 / G) + g;
     uint64_t o0 = 0;

@@ -43,6 +43,7 @@
 // The rules the reduction kernels share are device functions in seed_rule.h, seed_pair_rule.h and seed_rescue_rule.h.
 #include <algorithm>
 
+#include "dna_complement.h"
 #include "seed_rule.h"
 
 // The pass scratch: one growing device buffer per name (bg_reserve), kept by the context between calls.
@@ -272,36 +273,6 @@ __global__ __launch_bounds__(64) void se_gather_kernel(SeedPrm prm, uint64_t n_r
         for (uint32_t i = lane; i < (uint32_t)(hi - lo); i += 64) y[yo + i] = text[lo + i];
         yo += hi - lo;
     }
-}
-
-// dna::complement (rust-bio alphabets/dna.rs): AGCTYRWSKMDVHBN -> TCGARYWSMKHBDVN, the same in lower case, every other
-// byte (N, $, ...) itself
-struct alignas(16) ComplementTable {
-    uint8_t v[256];
-};
-constexpr ComplementTable make_complement() {
-    ComplementTable t{};
-    for (int i = 0; i < 256; i++) t.v[i] = (uint8_t)i;
-    const char* a = "AGCTYRWSKMDVHBN";
-    const char* b = "TCGARYWSMKHBDVN";
-    for (int i = 0; a[i]; i++) {
-        t.v[(uint8_t)a[i]] = (uint8_t)b[i];
-        t.v[(uint8_t)a[i] + 32] = (uint8_t)(b[i] + 32);
-    }
-    return t;
-}
-__constant__ ComplementTable kComplement = make_complement();
-
-// the block's copy of the table: 64 dwords, one per lane of the first wavefront
-__device__ __forceinline__ void load_complement(uint8_t* s_comp) {
-    if (threadIdx.x < 64) ((uint32_t*)s_comp)[threadIdx.x] = ((const uint32_t*)kComplement.v)[threadIdx.x];
-    __syncthreads();
-}
-
-// dst[0 .. L) = revcomp(src[0 .. L)) by the 64 lanes of one wavefront
-__device__ __forceinline__ void revcomp_wave(const uint8_t* s_comp, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                             uint64_t L, uint32_t lane) {
-    for (uint64_t i = lane; i < L; i += 64) dst[i] = s_comp[src[L - 1 - i]];
 }
 
 // bg_revcomp_batch_dev: one wavefront per sequence, four per block

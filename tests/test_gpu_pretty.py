@@ -1,4 +1,4 @@
-"""`bg_pretty_batch` (bio-types `Alignment::pretty`, parity unpinned) against the oracle's restatement, on the
+"""`bg_pretty_batch` (csrc/align_text.hip: bio-types `Alignment::pretty`, parity unpinned) against the oracle's restatement, on the
 alignments of the reference's own known-answer tests and on random pairs in every mode."""
 import numpy as np
 import pytest

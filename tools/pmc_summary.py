@@ -22,7 +22,7 @@ from csrc_hash import csrc_sha  # noqa: E402
 
 out, tag = sys.argv[1], sys.argv[2]
 SHA = csrc_sha()  # the kernel sources these counters were collected with: bench.py reports them only while they match
-OURS = ("bgsw", "bgband", "bgfm", "fm_backward", "fm_search_fast", "fq_", "se_", "sa_", "fmd_", "cigar_kernel", "pretty_kernel", "interval_rows", "pack2_", "ops_compact")
+OURS = ("bgsw", "bgband", "bgfm", "fm_backward", "fm_search_fast", "fq_", "scan_block_sums_kernel", "scan_small_kernel", "scan_apply_kernel", "se_", "sa_", "fmd_", "cigar_kernel", "pretty_kernel", "interval_rows", "pack2_", "ops_compact")
 
 
 def short(k):
