@@ -115,6 +115,10 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *                      tests use small values so that short texts take several passes)
  *   band_budget_gb     traceback + aux bytes per scratch set of the banded pipeline, in GB (0 = default: 40, and never more
  *                      than a third of the device's free memory); a sub-batch that does not fit is cut
+ *   myers_chunk_jobs   jobs per launch of bg_myers_*_batch[_dev] (0 = by a 256 MB budget for the traceback columns; tests use
+ *                      small values so that small batches take several launches)
+ *   myers_lds_bytes    LDS bytes the pattern tables of one group of bg_myers_*_batch[_dev] may take (0 = 48 KB; 4096 .. 65536;
+ *                      tests lower it so that a few patterns need two groups)
  * Unknown keys return BG_ERR_INVALID_ARG. */
 int bg_set_option(bg_ctx* ctx, const char* key, int64_t value);
 
@@ -1062,6 +1066,79 @@ int bg_fasta_reference_dev(bg_ctx* ctx, uint64_t n_records, const bg_fasta_recor
 int bg_fasta_reference(bg_ctx* ctx, uint64_t n_records, const bg_fasta_record_t* recs, const uint8_t* fasta_text,
                        const uint8_t* seq, uint32_t flags, uint8_t* text_out, uint64_t text_cap, bg_sam_contig_t* contigs,
                        char* names, uint64_t names_cap, uint64_t* n_text, uint64_t* names_bytes, uint64_t* first_bad);
+
+/* ---- approximate pattern matching in batches of texts (myers.hip) and trimming (fastq_trim.hip) ----------------------
+ * bio::pattern_matching::myers::Myers<u64> (src/pattern_matching/myers/): Myers' bit-parallel algorithm for patterns of
+ * 1 to 64 symbols with DistType = u8.  Out of scope: `myers::long` (block-based, unlimited patterns), Myers<u128> and
+ * find_all_lazy's incremental interface (LazyMatches: hit_at / path_at on a search in progress).
+ *
+ * The pattern crosses the boundary as its tabulated `peq` (simple.rs:55-74; closures and hash maps do not cross it):
+ * peq[c] has bit i set where pattern symbol i accepts text byte c, ambiguities (builder.rs:84-92) and text wildcards
+ * (builder.rs:115-118, all ones) included; bits at or above m are ignored (the reference's wildcard sets them too).
+ * m == 0 is BG_ERR_INVALID_ARG ("Pattern is empty", simple.rs:53), m > 64 BG_ERR_TOO_LARGE ("Pattern too long",
+ * simple.rs:52).  These and the other argument checks come before the ctx is looked at.
+ *
+ * Jobs: n_texts texts (text + off[n_texts + 1], the seq / seq_off bg_fastq_parse_dev leaves; every text shorter than 2^32)
+ * against 1 <= n_pat <= 1024 patterns (0: BG_ERR_INVALID_ARG, more: BG_ERR_TOO_LARGE); job t * n_pat + p is text t
+ * against pattern p.  max_dist is clamped to 255 (myers_impl.rs:194, 224).
+ *
+ * A hit is a bg_alignment_t filled as update_aln (helpers.rs:83-99) fills an Alignment: score = dist, xstart = 0,
+ * xend = xlen = m, ylen = the text's length, yend = end + 1, ystart = yend - aligned columns, mode = BG_MODE_SEMIGLOBAL,
+ * n_clips = 0; operations in pattern order as BG_OP_* bytes (x = pattern, y = text: Ins consumes a pattern symbol, Del a
+ * text byte), chosen as _traceback_at does (traceback.rs:235-318 with simple.rs:202-297: Subst, then Ins, then Del, then
+ * Match) on the two extra columns left of the text (traceback.rs:153-186).  bg_cigar_batch[_dev] and bg_pretty_batch take
+ * the records as they are.  No hit: score = BG_MIN_SCORE, xlen = m, ylen, mode, every other byte 0.
+ *
+ * bg_myers_best_batch[_dev]: per job the hit find_all(text, max_dist).min_by_key(dist) returns — the smallest distance,
+ *   the first end among equals (myers_impl.rs:197-207, 214-225) — with the start and path next_alignment gives there
+ *   (myers_impl.rs:400-406, 456-479).  max_dist >= 255 makes it find_best_end plus its alignment; an empty text has no hit
+ *   (find_best_end panics).  Job j's operations end at ops + (j + 1) * ops_stride and ops_off points at the first;
+ *   ops_stride >= 2 * max m always suffices (m vertical or diagonal moves, at most dist <= m horizontal ones).  With a
+ *   smaller stride a job whose path does not fit gets status = BG_ERR_OPS_CAP in its record, its exact n_ops, ops_off =
+ *   j * ops_stride and no operations, and the call returns BG_ERR_OPS_CAP (the device flavour then reads a flag back: one
+ *   synchronisation of `stream`; with ops_stride >= 2 * max m or ops == NULL it is asynchronous, and uploads nothing when
+ *   the patterns are those of the ctx's previous Myers call).  ops == NULL skips the operations, not ystart / n_ops.
+ * bg_myers_find_all_batch[_dev]: the iteration of find_all (myers_impl.rs:482-494): every end column whose distance is at
+ *   most max_dist, in text order.  The first max_hits (1 .. 64, else BG_ERR_INVALID_ARG) of job j fill
+ *   aln[j * max_hits ..], unused slots are no-hit records, count[j] is the job's total.  Coordinates and distance only
+ *   (n_ops = 0).  flags & BG_MYERS_ENDS_ONLY is find_all_end (myers_impl.rs:185-195, 284-294): no traceback, ystart = yend.
+ * Options (bg_set_option): myers_chunk_jobs — jobs per launch (0: by a 256 MB budget for the traceback columns; rounded
+ *   up to a multiple of 256); myers_lds_bytes — LDS bytes the peq tables of one pattern group may take (0: 48 KB; at
+ *   least 4096).  Tests use both to reach the sub-batch and group loops with small inputs. */
+typedef struct { uint64_t peq[256]; uint32_t m; uint32_t _reserved; } bg_myers_pattern_t;
+enum { BG_MYERS_ENDS_ONLY = 1 };
+enum { BG_MYERS_MAX_PATTERNS = 1024, BG_MYERS_MAX_HITS = 64 };
+int bg_myers_best_batch(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t max_dist, uint64_t n_texts,
+                        const uint8_t* text, const uint64_t* off, bg_alignment_t* aln, uint8_t* ops, uint64_t ops_stride);
+int bg_myers_best_batch_dev(bg_ctx* ctx, const bg_myers_pattern_t* pats /* host */, uint32_t n_pat, uint32_t max_dist,
+                            uint64_t n_texts, const uint8_t* d_text, const uint64_t* d_off, bg_alignment_t* d_aln,
+                            uint8_t* d_ops, uint64_t ops_stride, void* stream);
+int bg_myers_find_all_batch(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t max_dist, uint32_t max_hits,
+                            uint32_t flags, uint64_t n_texts, const uint8_t* text, const uint64_t* off, bg_alignment_t* aln,
+                            uint32_t* count);
+int bg_myers_find_all_batch_dev(bg_ctx* ctx, const bg_myers_pattern_t* pats /* host */, uint32_t n_pat, uint32_t max_dist,
+                                uint32_t max_hits, uint32_t flags, uint64_t n_texts, const uint8_t* d_text,
+                                const uint64_t* d_off, bg_alignment_t* d_aln, uint32_t* d_count, void* stream);
+
+/* Trimming parsed FASTQ records by the hits of bg_myers_best_batch[_dev] (rust-bio has no trimmer: the rule is defined
+ * here).  hits holds n * n_pat records, read r's at r * n_pat; a pattern has a hit where score != BG_MIN_SCORE.
+ *   BG_TRIM_3P keeps [0, e) of the sequence, e the smallest ystart over the read's patterns with a hit, seq_len if none;
+ *   BG_TRIM_5P keeps [b, seq_len), b the largest yend over the patterns with a hit, 0 if none
+ * (both clamped to seq_len); the same byte range clamped to qual_len is kept of the qualities.  Output records are copies
+ * with seq_off, qual_off, seq_len, qual_len rewritten (ids, descriptions and `check` unchanged); sequences, qualities and
+ * their n + 1 offsets are compacted (seq_off_out[0] = 0), i.e. what the seed-and-extend *_dev calls and
+ * bg_sam_emit_batch_dev take.  A read trimmed to nothing stays as an empty record.  seq_out / qual_out need the capacity
+ * of the inputs and no output may alias an input (lanes read the source while others write: the call does not work in place).  Lengths, the exclusive scan of scan.hip, the copy; totals (optional, host, 2 entries: sequence and
+ * quality bytes kept) costs the device flavour its only synchronisation of `stream`.  Unknown mode: BG_ERR_INVALID_ARG. */
+enum { BG_TRIM_3P = 0, BG_TRIM_5P = 1 };
+int bg_fastq_trim_dev(bg_ctx* ctx, uint64_t n, int mode, const bg_alignment_t* d_hits, uint32_t n_pat,
+                      const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
+                      const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
+                      uint8_t* d_qual_out, uint64_t* d_qual_off_out, uint64_t* totals, void* stream);
+int bg_fastq_trim(bg_ctx* ctx, uint64_t n, int mode, const bg_alignment_t* hits, uint32_t n_pat, const bg_fastq_record_t* recs,
+                  const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual, const uint64_t* qual_off,
+                  bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out, uint8_t* qual_out,
+                  uint64_t* qual_off_out, uint64_t* totals);
 
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI

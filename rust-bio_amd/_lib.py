@@ -166,6 +166,12 @@ class SAM_PARAMS(C.Structure):
 
 assert C.sizeof(SAM_PARAMS) == 8, C.sizeof(SAM_PARAMS)
 
+# bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
+MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
+assert MYERS_PATTERN_DTYPE.itemsize == 2056, MYERS_PATTERN_DTYPE.itemsize
+MYERS_ENDS_ONLY, MYERS_MAX_PATTERNS, MYERS_MAX_HITS = 1, 1024, 64
+TRIM_3P, TRIM_5P = 0, 1
+
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
            "bg_set_option", "bg_suffix_array", "bg_bwt", "bg_less", "bg_fm_build", "bg_fm_free",
            "bg_fm_device_bytes", "bg_fm_set_option", "bg_fm_backward_search_batch", "bg_fm_backward_search_batch_dev",
@@ -191,7 +197,9 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_shard_range", "bg_shard_balanced", "bg_comm_unique_id", "bg_comm_init", "bg_comm_init_host",
            "bg_gather_records", "bg_gather_records_cap", "bg_gather_records_host", "bg_comm_free", "bg_fm_save", "bg_fm_load",
            "bg_fm_len", "bg_fm_less", "bg_fm_bwt", "bg_fm_bwt_dev", "bg_comm_world",
-           "bg_fmd_smems_batch64", "bg_fmd_smems_batch64_dev", "bg_fmd_interval_batch64"]
+           "bg_fmd_smems_batch64", "bg_fmd_smems_batch64_dev", "bg_fmd_interval_batch64",
+           "bg_myers_best_batch", "bg_myers_best_batch_dev", "bg_myers_find_all_batch", "bg_myers_find_all_batch_dev",
+           "bg_fastq_trim", "bg_fastq_trim_dev"]
 
 
 def build(force=False):
@@ -352,6 +360,12 @@ def lib():
         L.bg_last_fill_kernels.argtypes = [vp, C.POINTER(u32)]
         L.bg_last_fill_framed.argtypes = [vp, C.POINTER(i32)]
         L.bg_pack2_host.argtypes = [vp, u64, vp, vp]
+        L.bg_myers_best_batch.argtypes = [vp, vp, u32, u32, u64, vp, vp, vp, vp, u64]
+        L.bg_myers_best_batch_dev.argtypes = [vp, vp, u32, u32, u64, vp, vp, vp, vp, u64, vp]
+        L.bg_myers_find_all_batch.argtypes = [vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp]
+        L.bg_myers_find_all_batch_dev.argtypes = [vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp]
+        L.bg_fastq_trim.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_trim_dev.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for s in SYMBOLS:
             if getattr(L, s).restype is C.c_int or s.startswith("bg_") and getattr(L, s).restype is None:
                 pass

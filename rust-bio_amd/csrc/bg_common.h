@@ -32,6 +32,8 @@ struct bg_host_pipe;  // sw_api.hip: staging sets of the pipelined host-buffer p
 void bg_host_pipe_free(bg_host_pipe*);
 struct bg_fm_pipe;  // fm_index.hip: staging sets of bg_fm_backward_search_batch
 void bg_fm_pipe_free(bg_fm_pipe*);
+struct bg_myers_scratch;  // myers.hip: the class-compacted peq tables of the last call, pinned and on the device
+void bg_myers_scratch_free(bg_myers_scratch*);
 
 struct bg_ctx {
     int device = 0;
@@ -62,6 +64,9 @@ struct bg_ctx {
     bg_host_pipe* pipe = nullptr;     // persistent staging of bg_align_batch's pipelined path
     bg_seed_scratch* seed = nullptr;  // persistent scratch of the seed-and-extend pipeline
     bg_fm_pipe* fm_pipe = nullptr;    // persistent pinned / device staging of bg_fm_backward_search_batch
+    bg_myers_scratch* myers = nullptr;  // persistent pattern tables of bg_myers_*_batch[_dev]
+    int64_t myers_chunk_jobs = 0;     // jobs per launch of the Myers kernels (0: by a 256 MB budget for the traceback columns)
+    int64_t myers_lds_bytes = 0;      // LDS bytes for the peq tables of one pattern group (0: 48 KB; tests lower it)
     uint64_t fm_wide_from = 0xFFFFFFFFull;  // texts of this many symbols or more get the 64-bit FM layout (tests: lower it)
     uint32_t fm_wide_sb_shift = 17;         // ... with superblocks of 2^this blocks (tests: a few blocks, so that bases matter)
     bool fm_host_bytes = false;       // tests, A/B: bg_fm_backward_search_batch stages the pattern bytes (no 2-bit packing on the host)

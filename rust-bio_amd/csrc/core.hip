@@ -156,6 +156,7 @@ extern "C" int bg_free(bg_ctx* ctx) {
     bg_host_pipe_free(ctx->pipe);
     bg_seed_scratch_free(ctx->seed);
     bg_fm_pipe_free(ctx->fm_pipe);
+    bg_myers_scratch_free(ctx->myers);
     if (ctx->ev[0]) hipEventDestroy(ctx->ev[0]);
     if (ctx->ev[1]) hipEventDestroy(ctx->ev[1]);
     if (ctx->scratch_done) hipEventDestroy(ctx->scratch_done);
@@ -216,6 +217,16 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "sam_lanes")) {
         if (value != 0 && value != 16 && value != 32) return BG_ERR_INVALID_ARG;
         ctx->sam_lanes = (int)value;
+        return BG_OK;
+    }
+    if (!strcmp(key, "myers_chunk_jobs")) {
+        if (value < 0) return BG_ERR_INVALID_ARG;
+        ctx->myers_chunk_jobs = value;
+        return BG_OK;
+    }
+    if (!strcmp(key, "myers_lds_bytes")) {
+        if (value != 0 && (value < 4096 || value > 65536)) return BG_ERR_INVALID_ARG;
+        ctx->myers_lds_bytes = value;
         return BG_OK;
     }
     if (!strcmp(key, "sa_chunk_symbols")) {
