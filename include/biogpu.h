@@ -1069,7 +1069,7 @@ int bg_fasta_reference(bg_ctx* ctx, uint64_t n_records, const bg_fasta_record_t*
 
 /* ---- approximate pattern matching in batches of texts (myers.hip) and trimming (fastq_trim.hip) ----------------------
  * bio::pattern_matching::myers::Myers<u64> (src/pattern_matching/myers/): Myers' bit-parallel algorithm for patterns of
- * 1 to 64 symbols with DistType = u8.  Out of scope: `myers::long` (block-based, unlimited patterns), Myers<u128> and
+ * 1 to 64 symbols with DistType = u8; `myers::long` (block-based) follows below.  Out of scope: Myers<u128> and
  * find_all_lazy's incremental interface (LazyMatches: hit_at / path_at on a search in progress).
  *
  * The pattern crosses the boundary as its tabulated `peq` (simple.rs:55-74; closures and hash maps do not cross it):
@@ -1120,7 +1120,47 @@ int bg_myers_find_all_batch_dev(bg_ctx* ctx, const bg_myers_pattern_t* pats /* h
                                 uint32_t max_hits, uint32_t flags, uint64_t n_texts, const uint8_t* d_text,
                                 const uint64_t* d_off, bg_alignment_t* d_aln, uint32_t* d_count, void* stream);
 
-/* Trimming parsed FASTQ records by the hits of bg_myers_best_batch[_dev] (rust-bio has no trimmer: the rule is defined
+/* ---- patterns of more than 64 symbols: the block-based variant (myers_long.hip) ---------------------------------------
+ * bio::pattern_matching::myers::long::Myers<u64> (src/pattern_matching/myers/long.rs): the pattern cut into blocks of 64
+ * symbols, a carry of -1, 0 or +1 handed from block to block in every text column (advance_block, long.rs:136-179), with
+ * DistType = usize.  The same calls as above with these differences, and nothing else:
+ *   Patterns.  Pattern p has m[p] symbols in ceil(m[p] / 64) blocks; block b's table is
+ *     peq[(blk_off[p] + b) * 256 + byte], bit i set where pattern symbol 64 * b + i accepts the byte (long.rs:86-115).
+ *     blk_off has n_pat + 1 entries, blk_off[0] = 0 and blk_off[p + 1] - blk_off[p] == ceil(m[p] / 64), else
+ *     BG_ERR_INVALID_ARG.  Bits at or above a block's chunk length are ignored (the reference's wildcards set them,
+ *     long.rs:105-109); Peq::high_mask (long.rs:113) is derived from m.  m == 0 is BG_ERR_INVALID_ARG ("Pattern is empty",
+ *     long.rs:83); m > BG_MYERS_LONG_MAX_M is BG_ERR_TOO_LARGE (the reference has no limit).  peq, blk_off and m are host
+ *     arrays in both flavours.  Patterns of several block counts may share a call, and m <= 64 is legal: for
+ *     max_dist <= 255 such a pattern gives the records and operations of the calls above byte for byte.
+ *   Distances are 32-bit and max_dist is clamped to the pattern's m instead of 255 ("distances cannot exceed m",
+ *     States::new, long.rs:205-206): a job's ring is m + min(max_dist, m) + 2 columns (myers_impl.rs:327).
+ *   Paths are those of _traceback_at with LongTracebackHandler (long.rs:402-563), block boundaries and the one-symbol last
+ *     block (long.rs:430-434) included.  The reference computes, per column, only the blocks of its Ukkonen band
+ *     (long.rs:239-268) and reports a column when all were computed (known_dist, long.rs:272-274); the kernels compute every
+ *     block, which gives the same ends, distances and paths (myers_long.hip says why; the tests compare).
+ *   Traceback scratch per job: (16 * NB + 4) * (m + min(max_dist, m) + 2) bytes, NB the block count of the kernel
+ *     instantiation (1, 2, 3, 4, 8, 16) that holds the pattern — 533 000 bytes at m = 1024, about 500 jobs per launch under
+ *     the 256 MB budget of myers_chunk_jobs = 0.
+ * Job numbering, records, the no-hit record, the operation slots with BG_ERR_OPS_CAP (2 * max m always suffices), max_hits,
+ * BG_MYERS_ENDS_ONLY, 1 .. 1024 patterns, the empty text, the order of the argument checks, both options and the _dev
+ * flavour's asynchrony are those of bg_myers_*_batch[_dev].  bg_fastq_trim[_dev] takes the best records as they are. */
+enum { BG_MYERS_LONG_MAX_M = 1024 };
+int bg_myers_long_best_batch(bg_ctx* ctx, const uint64_t* peq, const uint64_t* blk_off, const uint32_t* m, uint32_t n_pat,
+                             uint32_t max_dist, uint64_t n_texts, const uint8_t* text, const uint64_t* off, bg_alignment_t* aln,
+                             uint8_t* ops, uint64_t ops_stride);
+int bg_myers_long_best_batch_dev(bg_ctx* ctx, const uint64_t* peq /* host */, const uint64_t* blk_off /* host */,
+                                 const uint32_t* m /* host */, uint32_t n_pat, uint32_t max_dist, uint64_t n_texts,
+                                 const uint8_t* d_text, const uint64_t* d_off, bg_alignment_t* d_aln, uint8_t* d_ops,
+                                 uint64_t ops_stride, void* stream);
+int bg_myers_long_find_all_batch(bg_ctx* ctx, const uint64_t* peq, const uint64_t* blk_off, const uint32_t* m, uint32_t n_pat,
+                                 uint32_t max_dist, uint32_t max_hits, uint32_t flags, uint64_t n_texts, const uint8_t* text,
+                                 const uint64_t* off, bg_alignment_t* aln, uint32_t* count);
+int bg_myers_long_find_all_batch_dev(bg_ctx* ctx, const uint64_t* peq /* host */, const uint64_t* blk_off /* host */,
+                                     const uint32_t* m /* host */, uint32_t n_pat, uint32_t max_dist, uint32_t max_hits,
+                                     uint32_t flags, uint64_t n_texts, const uint8_t* d_text, const uint64_t* d_off,
+                                     bg_alignment_t* d_aln, uint32_t* d_count, void* stream);
+
+/* Trimming parsed FASTQ records by the hits of bg_myers_best_batch[_dev] or bg_myers_long_best_batch[_dev] (rust-bio has no trimmer: the rule is defined
  * here).  hits holds n * n_pat records, read r's at r * n_pat; a pattern has a hit where score != BG_MIN_SCORE.
  *   BG_TRIM_3P keeps [0, e) of the sequence, e the smallest ystart over the read's patterns with a hit, seq_len if none;
  *   BG_TRIM_5P keeps [b, seq_len), b the largest yend over the patterns with a hit, 0 if none

@@ -170,6 +170,7 @@ assert C.sizeof(SAM_PARAMS) == 8, C.sizeof(SAM_PARAMS)
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
 assert MYERS_PATTERN_DTYPE.itemsize == 2056, MYERS_PATTERN_DTYPE.itemsize
 MYERS_ENDS_ONLY, MYERS_MAX_PATTERNS, MYERS_MAX_HITS = 1, 1024, 64
+MYERS_LONG_MAX_M = 1024
 TRIM_3P, TRIM_5P = 0, 1
 
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
@@ -199,6 +200,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_fm_len", "bg_fm_less", "bg_fm_bwt", "bg_fm_bwt_dev", "bg_comm_world",
            "bg_fmd_smems_batch64", "bg_fmd_smems_batch64_dev", "bg_fmd_interval_batch64",
            "bg_myers_best_batch", "bg_myers_best_batch_dev", "bg_myers_find_all_batch", "bg_myers_find_all_batch_dev",
+           "bg_myers_long_best_batch", "bg_myers_long_best_batch_dev", "bg_myers_long_find_all_batch", "bg_myers_long_find_all_batch_dev",
            "bg_fastq_trim", "bg_fastq_trim_dev"]
 
 
@@ -364,6 +366,10 @@ def lib():
         L.bg_myers_best_batch_dev.argtypes = [vp, vp, u32, u32, u64, vp, vp, vp, vp, u64, vp]
         L.bg_myers_find_all_batch.argtypes = [vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp]
         L.bg_myers_find_all_batch_dev.argtypes = [vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp]
+        L.bg_myers_long_best_batch.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, u64]
+        L.bg_myers_long_best_batch_dev.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, u64, vp]
+        L.bg_myers_long_find_all_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp]
+        L.bg_myers_long_find_all_batch_dev.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp]
         L.bg_fastq_trim.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bg_fastq_trim_dev.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for s in SYMBOLS:

@@ -32,7 +32,7 @@ struct bg_host_pipe;  // sw_api.hip: staging sets of the pipelined host-buffer p
 void bg_host_pipe_free(bg_host_pipe*);
 struct bg_fm_pipe;  // fm_index.hip: staging sets of bg_fm_backward_search_batch
 void bg_fm_pipe_free(bg_fm_pipe*);
-struct bg_myers_scratch;  // myers.hip: the class-compacted peq tables of the last call, pinned and on the device
+struct bg_myers_scratch;  // myers_common.h: the class-compacted peq tables of the last call, pinned and on the device
 void bg_myers_scratch_free(bg_myers_scratch*);
 
 struct bg_ctx {
@@ -64,7 +64,7 @@ struct bg_ctx {
     bg_host_pipe* pipe = nullptr;     // persistent staging of bg_align_batch's pipelined path
     bg_seed_scratch* seed = nullptr;  // persistent scratch of the seed-and-extend pipeline
     bg_fm_pipe* fm_pipe = nullptr;    // persistent pinned / device staging of bg_fm_backward_search_batch
-    bg_myers_scratch* myers = nullptr;  // persistent pattern tables of bg_myers_*_batch[_dev]
+    bg_myers_scratch* myers = nullptr;  // persistent pattern tables of bg_myers_*_batch[_dev] and bg_myers_long_*_batch[_dev]
     int64_t myers_chunk_jobs = 0;     // jobs per launch of the Myers kernels (0: by a 256 MB budget for the traceback columns)
     int64_t myers_lds_bytes = 0;      // LDS bytes for the peq tables of one pattern group (0: 48 KB; tests lower it)
     uint64_t fm_wide_from = 0xFFFFFFFFull;  // texts of this many symbols or more get the 64-bit FM layout (tests: lower it)

@@ -1,5 +1,7 @@
 // bg_myers_best_batch[_dev], bg_myers_find_all_batch[_dev]: bio::pattern_matching::myers::Myers<u64> for batches of texts
 // against a handful of patterns (include/biogpu.h has the contract; the tests hold the reference restated line by line).
+// myers_common.h holds what this file shares with myers_long.hip (patterns of more than 64 symbols): the text walk, the
+// records, the byte classes, the tables' upload and the host flavour.
 //
 // One lane per job (text t, pattern p): pv, mv and dist live in registers and one step is the reference's _step
 // (simple.rs:95-117) in 64-bit integer operations — the add in xh is a real 64-bit add, its carry out of bit 31 is the
@@ -21,13 +23,9 @@
 // stores coalesce: 17 * (m + min(k, m) + 2) <= 2210 bytes per job, independent of the text's length.  The find-all call
 // keeps the reference's ring in the same layout and traces back (coordinates only) at each hit column; ENDS_ONLY stores
 // nothing.  Launches are cut so that the scratch of one stays within a budget (option myers_chunk_jobs).
-#include <map>
-
-#include "bg_common.h"
+#include "myers_common.h"
 
 namespace {
-
-constexpr uint32_t MY_BLOCK = 256;
 
 struct MyArgs {
     const uint8_t* text;
@@ -77,32 +75,6 @@ __host__ __device__ __forceinline__ void my_one_up(MyState& s, uint64_t pos_mask
 __host__ __device__ __forceinline__ void my_up_by(MyState& s, uint64_t range_mask) {
     s.dist = (s.dist + __builtin_popcountll(s.mv & range_mask) - __builtin_popcountll(s.pv & range_mask)) & 0xFFu;
 }
-
-// a lane's walk over its own text [p, end): bytes to the first 8-byte boundary, aligned words, bytes to the end
-struct MyText {
-    const uint8_t* p;
-    const uint8_t* end;
-    uint64_t w;
-    uint32_t have;
-    __host__ __device__ __forceinline__ MyText(const uint8_t* b, const uint8_t* e) : p(b), end(e), w(0), have(0) {}
-    __host__ __device__ __forceinline__ uint32_t next() {  // the caller takes exactly end - p bytes
-        if (have == 0) {
-            if (((uintptr_t)p & 7) == 0 && end - p >= 8) {
-                w = *(const uint64_t*)p;
-                have = 8;
-                p += 8;
-            } else {
-                w = *p;
-                have = 1;
-                p += 1;
-            }
-        }
-        const uint32_t c = (uint32_t)w & 0xFFu;
-        w >>= 8;
-        have--;
-        return c;
-    }
-};
 
 struct MyScratch {
     uint64_t* pv;
@@ -182,26 +154,6 @@ __host__ __device__ inline uint32_t my_traceback(const MyScratch& S, uint32_t po
     return h;
 }
 
-__host__ __device__ __forceinline__ bg_alignment_t my_no_hit(uint32_t m, uint32_t ylen) {
-    bg_alignment_t r = {};
-    r.score = BG_MIN_SCORE;
-    r.xlen = m;
-    r.ylen = ylen;
-    r.mode = BG_MODE_SEMIGLOBAL;
-    return r;
-}
-__host__ __device__ __forceinline__ bg_alignment_t my_hit(uint32_t m, uint32_t ylen, uint32_t start, uint32_t end1, uint32_t dist) {
-    bg_alignment_t r = {};  // update_aln, helpers.rs:83-99
-    r.score = (int32_t)dist;
-    r.xend = m;
-    r.xlen = m;
-    r.ylen = ylen;
-    r.yend = end1;
-    r.ystart = start;
-    r.mode = BG_MODE_SEMIGLOBAL;
-    return r;
-}
-
 // cls[256] and the group's peq[pl][class] into LDS; returns false for the lanes past the launch's range
 struct MyJob {
     uint64_t job, lane;
@@ -271,17 +223,7 @@ __host__ __device__ inline void my_best_job(const MyArgs& a, const MyJob& j, con
     uint8_t* slot_end = a.ops ? a.ops + (j.job + 1) * a.ops_stride : nullptr;
     const uint32_t h = my_traceback(S, (uint32_t)(v_e - v_lo), 0, m, slot_end, a.ops_stride, n_ops, broken);
     bg_alignment_t r = my_hit(m, n, best_end + 1 - h, best_end + 1, best);
-    r.n_ops = n_ops;
-    if (broken) r.status = (int8_t)BG_ERR_TRACEBACK;
-    if (a.ops) {
-        if (n_ops > a.ops_stride) {
-            r.status = (int8_t)BG_ERR_OPS_CAP;
-            r.ops_off = j.job * a.ops_stride;
-            *a.flag = 1;
-        } else {
-            r.ops_off = (j.job + 1) * a.ops_stride - n_ops;
-        }
-    }
+    my_set_ops(r, n_ops, broken, a.ops, a.ops_stride, j.job, a.flag);
     a.aln[j.job] = r;
 }
 
@@ -349,14 +291,6 @@ __global__ __launch_bounds__(MY_BLOCK) void myers_find_all_kernel(MyArgs a) {
 
 }  // namespace
 
-// the last call's tables: pinned on the host (what the device copy was made from) and on the device
-struct bg_myers_scratch {
-    uint8_t* h = nullptr;  // pinned
-    uint8_t* d = nullptr;
-    size_t cap = 0, used = 0;
-    bool valid = false;
-    int* d_flag = nullptr;
-};
 void bg_myers_scratch_free(bg_myers_scratch* s) {
     if (!s) return;
     if (s->h) hipHostFree(s->h);
@@ -383,24 +317,13 @@ int my_check(const bg_myers_pattern_t* pats, uint32_t n_pat) {
     return BG_OK;
 }
 
-// bytes into classes: two bytes share one when their peq words (below bit m) agree in every pattern
+// the patterns' peq words by class of text byte (bits at or above m do not count)
 void my_tables(const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t k, MyTables& T) {
-    std::map<std::vector<uint64_t>, uint32_t> seen;
     uint8_t cls[256];
+    std::vector<MyRow> rows(n_pat);
+    for (uint32_t p = 0; p < n_pat; p++) rows[p] = MyRow{pats[p].peq, pats[p].m == 64 ? ~0ull : (1ull << pats[p].m) - 1};
     std::vector<std::vector<uint64_t>> cols;
-    std::vector<uint64_t> col(n_pat);
-    for (int c = 0; c < 256; c++) {
-        for (uint32_t p = 0; p < n_pat; p++) {
-            const uint32_t m = pats[p].m;
-            col[p] = pats[p].peq[c] & (m == 64 ? ~0ull : (1ull << m) - 1);
-        }
-        auto it = seen.find(col);
-        if (it == seen.end()) {
-            it = seen.emplace(col, (uint32_t)cols.size()).first;
-            cols.push_back(col);
-        }
-        cls[c] = (uint8_t)it->second;
-    }
+    my_classes(rows, cls, cols);
     T.n_cls = (uint32_t)cols.size();
     T.off_pm = (size_t)n_pat * T.n_cls * 8;
     T.off_cls = T.off_pm + (size_t)n_pat * 4;
@@ -417,52 +340,12 @@ void my_tables(const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t k, MyTab
     memcpy(T.blob.data() + T.off_cls, cls, 256);
 }
 
-// the tables on the device; nothing moves when they are those of the previous call
-int my_upload(bg_ctx* ctx, const MyTables& T, hipStream_t st) {
-    if (!ctx->myers) ctx->myers = new bg_myers_scratch;
-    bg_myers_scratch* M = ctx->myers;
-    if (!M->d_flag) BG_HIP(hipMalloc(&M->d_flag, sizeof(int)));
-    const size_t need = T.blob.size();
-    if (M->valid && M->used == need && !memcmp(M->h, T.blob.data(), need)) return BG_OK;
-    // the pinned copy may still be the source of an earlier call's transfer
-    BG_HIP(hipStreamSynchronize(st));
-    if (ctx->scratch_used && ctx->scratch_stream != st) BG_HIP(hipStreamSynchronize(ctx->scratch_stream));
-    M->valid = false;
-    if (M->cap < need) {
-        if (M->h) hipHostFree(M->h);
-        hipFree(M->d);
-        M->h = M->d = nullptr;
-        M->cap = 0;
-        const size_t cap = need + need / 2 + 4096;
-        BG_HIP(hipHostMalloc(&M->h, cap));
-        BG_HIP(hipMalloc(&M->d, cap));
-        M->cap = cap;
-    }
-    memcpy(M->h, T.blob.data(), need);
-    M->used = need;
-    BG_HIP(hipMemcpyAsync(M->d, M->h, need, hipMemcpyHostToDevice, st));
-    M->valid = true;
-    return BG_OK;
-}
-
-struct MyCall {
-    bool find_all = false, ends_only = false;
-    uint32_t k = 0, max_hits = 0;
-    uint64_t n_texts = 0;
-    const uint8_t* d_text = nullptr;
-    const uint64_t* d_off = nullptr;
-    bg_alignment_t* d_aln = nullptr;
-    uint32_t* d_count = nullptr;
-    uint8_t* d_ops = nullptr;
-    uint64_t ops_stride = 0;
-};
-
 int my_run(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, const MyCall& c, hipStream_t st) {
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);
     MyTables T;
     my_tables(pats, n_pat, c.k, T);
-    if (int rc = my_upload(ctx, T, st)) return rc;
+    if (int rc = my_upload(ctx, T.blob, 0, st)) return rc;
     bg_myers_scratch* M = ctx->myers;
     const bool need_scratch = !(c.find_all && c.ends_only);
     const bool may_overflow = !c.find_all && c.d_ops && c.ops_stride < 2ull * T.max_m;
@@ -525,51 +408,6 @@ int my_run(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, const My
     return BG_OK;
 }
 
-// host flavours: device copies of the inputs, the device call on the ctx's stream, the results back
-struct MyDev {
-    void* p = nullptr;
-    ~MyDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-};
-
-int my_host(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, MyCall c, const uint8_t* text, const uint64_t* off,
-            bg_alignment_t* aln, uint32_t* count, uint8_t* ops) {
-    if (c.n_texts == 0) return BG_OK;
-    if (!text || !off || !aln) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    const uint64_t t0 = off[0], bytes = off[c.n_texts] - t0;
-    const uint64_t n_rec = c.n_texts * n_pat * (c.find_all ? c.max_hits : 1), n_jobs = c.n_texts * n_pat;
-    MyDev d_text, d_off, d_aln, d_count, d_ops;
-    std::vector<uint64_t> rel(c.n_texts + 1);
-    for (uint64_t i = 0; i <= c.n_texts; i++) rel[i] = off[i] - t0;
-    if (int rc = d_text.alloc(bytes)) return rc;
-    if (int rc = d_off.alloc(rel.size() * 8)) return rc;
-    if (int rc = d_aln.alloc(n_rec * sizeof(bg_alignment_t))) return rc;
-    if (c.find_all)
-        if (int rc = d_count.alloc(n_jobs * 4)) return rc;
-    if (ops)
-        if (int rc = d_ops.alloc(n_jobs * c.ops_stride)) return rc;
-    hipStream_t st = ctx->stream;
-    BG_HIP(hipMemcpyAsync(d_text.p, text + t0, bytes, hipMemcpyHostToDevice, st));
-    BG_HIP(hipMemcpyAsync(d_off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-    BG_HIP(hipStreamSynchronize(st));
-    c.d_text = (const uint8_t*)d_text.p;
-    c.d_off = (const uint64_t*)d_off.p;
-    c.d_aln = (bg_alignment_t*)d_aln.p;
-    c.d_count = (uint32_t*)d_count.p;
-    c.d_ops = ops ? (uint8_t*)d_ops.p : nullptr;
-    const int rc = my_run(ctx, pats, n_pat, c, st);
-    if (rc != BG_OK && rc != BG_ERR_OPS_CAP) return rc;
-    BG_HIP(hipMemcpyAsync(aln, d_aln.p, n_rec * sizeof(bg_alignment_t), hipMemcpyDeviceToHost, st));
-    if (c.find_all) BG_HIP(hipMemcpyAsync(count, d_count.p, n_jobs * 4, hipMemcpyDeviceToHost, st));
-    if (ops) BG_HIP(hipMemcpyAsync(ops, d_ops.p, n_jobs * c.ops_stride, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return rc;
-}
-
 }  // namespace
 
 extern "C" int bg_myers_best_batch_dev(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t max_dist,
@@ -599,7 +437,8 @@ extern "C" int bg_myers_best_batch(bg_ctx* ctx, const bg_myers_pattern_t* pats, 
     c.k = std::min(max_dist, 255u);
     c.n_texts = n_texts;
     c.ops_stride = ops_stride;
-    return my_host(ctx, pats, n_pat, c, text, off, aln, nullptr, ops);
+    return my_host(ctx, n_pat, c, text, off, aln, nullptr, ops,
+                   [&](const MyCall& cc, hipStream_t st) { return my_run(ctx, pats, n_pat, cc, st); });
 }
 
 extern "C" int bg_myers_find_all_batch_dev(bg_ctx* ctx, const bg_myers_pattern_t* pats, uint32_t n_pat, uint32_t max_dist,
@@ -636,5 +475,6 @@ extern "C" int bg_myers_find_all_batch(bg_ctx* ctx, const bg_myers_pattern_t* pa
     c.k = std::min(max_dist, 255u);
     c.max_hits = max_hits;
     c.n_texts = n_texts;
-    return my_host(ctx, pats, n_pat, c, text, off, aln, count, nullptr);
+    return my_host(ctx, n_pat, c, text, off, aln, count, nullptr,
+                   [&](const MyCall& cc, hipStream_t st) { return my_run(ctx, pats, n_pat, cc, st); });
 }

@@ -2,15 +2,17 @@
 (csrc/myers.hip), plus trimming of parsed FASTQ records by the hits (csrc/fastq_trim.hip; the rule is defined in
 include/biogpu.h, rust-bio has no trimmer).
 
-In scope: patterns of 1 to 64 symbols (DistType u8), `distance`, `find_all_end`, `find_best_end`, `find_all`, the best
-hit's alignment with its path.  Out of scope: `myers::long`, `Myers<u128>`, `find_all_lazy`.  The pattern's `peq` table
+In scope: patterns of 1 to 64 symbols (`Myers`, DistType u8) and, block-based, of up to 1024 (`MyersLong`, the reference's
+`myers::long::Myers<u64>`, DistType usize; csrc/myers_long.hip): `distance`, `find_all_end`, `find_best_end`, `find_all`, the
+best hit's alignment with its path.  Out of scope: `Myers<u128>`, `find_all_lazy`.  The pattern's `peq` table
 (simple.rs:55-74) is built here on the host; everything that walks a text runs on the GPU, one text or a batch."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DTYPE, MIN_SCORE, MYERS_ENDS_ONLY, MYERS_MAX_HITS, MYERS_PATTERN_DTYPE, TRIM_3P, TRIM_5P  # noqa: F401
+from ._lib import (ALN_DTYPE, MIN_SCORE, MYERS_ENDS_ONLY, MYERS_LONG_MAX_M, MYERS_MAX_HITS, MYERS_PATTERN_DTYPE, TRIM_3P,  # noqa: F401
+                   TRIM_5P)
 
 OPS = ["Match", "Subst", "Del", "Ins"]
 
@@ -86,6 +88,63 @@ class Myers:
         return _aln_dict(aln[0], [OPS[int(b)] for b in o])
 
 
+class MyersLong(Myers):
+    """myers::long::Myers::<u64>::new_ambig(pattern, ambigs, wildcards) (long.rs:57-122): `peq` is [blocks][256]"""
+
+    def __init__(self, pattern, ambigs=None, wildcards=None, ctx=None):
+        pattern = bytes(pattern)
+        if len(pattern) == 0:
+            raise ValueError("Pattern is empty")  # long.rs:83
+        if len(pattern) > MYERS_LONG_MAX_M:
+            raise ValueError(f"Pattern too long: more than the {MYERS_LONG_MAX_M} symbols the device variant takes")
+        n_blocks = (len(pattern) + 63) // 64
+        peq = [[0] * 256 for _ in range(n_blocks)]
+        for i, symbol in enumerate(pattern):  # long.rs:88-103
+            block, mask = peq[i // 64], 1 << (i % 64)
+            block[symbol] |= mask
+            for eq in (ambigs or {}).get(symbol, ()):
+                block[eq] |= mask
+        for block in peq:  # long.rs:105-109
+            for w in wildcards or ():
+                block[w] = (1 << 64) - 1
+        self.peq = np.array(peq, dtype=np.uint64)
+        self.m = len(pattern)
+        self._ctx = ctx
+
+    NO_DISTANCE = (1 << 64) - 1 - 64  # impl_myers!'s max_dist, usize::MAX - 64 (long.rs:586): distance() of an empty text
+
+    def _max(self):
+        return 0xFFFFFFFF
+
+    def distance(self, text):
+        """myers_impl.rs:163-181; usize::MAX - 64 for an empty text"""
+        t, off = self._one(text)
+        aln, _ = long_best_batch([self], t, off, self._max(), ctx=self._ctx)
+        return self.NO_DISTANCE if aln["score"][0] == MIN_SCORE else int(aln["score"][0])
+
+    def find_best_end(self, text):
+        t, off = self._one(text)
+        aln, _ = long_best_batch([self], t, off, self._max(), ctx=self._ctx)
+        if aln["score"][0] == MIN_SCORE:
+            raise ValueError("find_best_end: no end column (empty text)")
+        return int(aln["yend"][0]) - 1, int(aln["score"][0])
+
+    def _all(self, text, max_dist, ends_only):
+        t, off = self._one(text)
+        aln, count = long_find_all_batch([self], t, off, max_dist, MYERS_MAX_HITS, ends_only, ctx=self._ctx)
+        if count[0] > MYERS_MAX_HITS:
+            raise _lib.BiogpuError(-8, f"{int(count[0])} hits in one text: more than the {MYERS_MAX_HITS} a job reports")
+        return aln[:int(count[0])]
+
+    def best_alignment(self, text, max_dist=0xFFFFFFFF):
+        t, off = self._one(text)
+        aln, ops = long_best_batch([self], t, off, max_dist, ops_stride=2 * self.m, ctx=self._ctx)
+        if aln["score"][0] == MIN_SCORE:
+            return None
+        o = ops[int(aln["ops_off"][0]):int(aln["ops_off"][0]) + int(aln["n_ops"][0])]
+        return _aln_dict(aln[0], [OPS[int(b)] for b in o])
+
+
 def _aln_dict(a, operations):
     return {"score": int(a["score"]), "xstart": int(a["xstart"]), "xend": int(a["xend"]), "xlen": int(a["xlen"]),
             "ystart": int(a["ystart"]), "yend": int(a["yend"]), "ylen": int(a["ylen"]), "mode": "Semiglobal", "operations": operations}
@@ -107,6 +166,9 @@ class MyersBuilder:
 
     def build_64(self, pattern, ctx=None):  # builder.rs:122-129
         return Myers(pattern, self._ambigs, self._wildcards, ctx)
+
+    def build_long_64(self, pattern, ctx=None):  # builder.rs:169-176
+        return MyersLong(pattern, self._ambigs, self._wildcards, ctx)
 
 
 def _byte(b):
@@ -199,6 +261,91 @@ def find_all_batch_dev(patterns, d_text, d_off, max_dist, max_hits, ends_only=Fa
     _lib.check(_lib.lib().bg_myers_find_all_batch_dev(ctx.h, pats.ctypes.data, len(pats), int(max_dist), int(max_hits),
                                                       MYERS_ENDS_ONLY if ends_only else 0, n, d_text.data_ptr(), d_off.data_ptr(),
                                                       d_aln.data_ptr(), d_count.data_ptr(), stream), "bg_myers_find_all_batch_dev")
+    return d_aln, d_count
+
+
+# ---- batches of the block-based variant ------------------------------------------------------------------------------
+def long_patterns_array(patterns):
+    """(peq uint64[blocks * 256], blk_off uint64[n_pat + 1], m uint32[n_pat]) of MyersLong objects — or of Myers objects, whose
+    one table is one block — or such a triple already"""
+    if isinstance(patterns, tuple):
+        peq, blk_off, m = patterns
+        return (np.ascontiguousarray(peq, dtype=np.uint64).reshape(-1), np.ascontiguousarray(blk_off, dtype=np.uint64),
+                np.ascontiguousarray(m, dtype=np.uint32))
+    blocks = [np.asarray(p.peq, dtype=np.uint64).reshape(-1, 256) for p in patterns]
+    blk_off = np.zeros(len(blocks) + 1, dtype=np.uint64)
+    blk_off[1:] = np.cumsum([len(b) for b in blocks])
+    peq = np.concatenate(blocks).reshape(-1) if blocks else np.zeros(0, dtype=np.uint64)
+    return np.ascontiguousarray(peq), blk_off, np.array([p.m for p in patterns], dtype=np.uint32)
+
+
+def _max_dist(max_dist):
+    return max(0, min(int(max_dist), 0xFFFFFFFF))  # the call clamps to each pattern's m anyway
+
+
+def long_best_batch(patterns, text, off, max_dist, ops_stride=None, ctx=None, allow_ops_cap=False):
+    """bg_myers_long_best_batch over host arrays; arguments and results as best_batch"""
+    ctx = ctx or _lib.default_context()
+    peq, blk_off, m = long_patterns_array(patterns)
+    text, off = _lib.as_u8(text), np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    aln = np.zeros(n * len(m), dtype=ALN_DTYPE)
+    ops = np.zeros(max(1, len(aln) * ops_stride), dtype=np.uint8) if ops_stride is not None else None
+    rc = _lib.lib().bg_myers_long_best_batch(ctx.h, peq.ctypes.data, blk_off.ctypes.data, m.ctypes.data, len(m), _max_dist(max_dist), n,
+                                             text.ctypes.data, off.ctypes.data, aln.ctypes.data,
+                                             ops.ctypes.data if ops is not None else None, ops_stride or 0)
+    _raise_unless(rc, "bg_myers_long_best_batch", (-9,) if allow_ops_cap else ())
+    return aln, ops
+
+
+def long_find_all_batch(patterns, text, off, max_dist, max_hits, ends_only=False, ctx=None):
+    """bg_myers_long_find_all_batch over host arrays; arguments and results as find_all_batch"""
+    ctx = ctx or _lib.default_context()
+    peq, blk_off, m = long_patterns_array(patterns)
+    text, off = _lib.as_u8(text), np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    aln = np.zeros(n * len(m) * max(0, min(int(max_hits), MYERS_MAX_HITS)), dtype=ALN_DTYPE)
+    count = np.zeros(n * len(m), dtype=np.uint32)
+    _lib.check(_lib.lib().bg_myers_long_find_all_batch(ctx.h, peq.ctypes.data, blk_off.ctypes.data, m.ctypes.data, len(m),
+                                                       _max_dist(max_dist), int(max_hits), MYERS_ENDS_ONLY if ends_only else 0, n,
+                                                       text.ctypes.data, off.ctypes.data, aln.ctypes.data, count.ctypes.data),
+               "bg_myers_long_find_all_batch")
+    return aln, count
+
+
+def long_best_batch_dev(patterns, d_text, d_off, max_dist, ops_stride=None, ctx=None, stream=0, allow_ops_cap=False, out=None):
+    """bg_myers_long_best_batch_dev; arguments and results as best_batch_dev"""
+    import torch
+    ctx = ctx or _lib.default_context()
+    peq, blk_off, m = long_patterns_array(patterns)
+    n = int(d_off.numel()) - 1
+    if out is not None:
+        d_aln, d_ops = out
+    else:
+        d_aln = torch.empty(n * len(m) * 64, dtype=torch.uint8, device=d_text.device)
+        d_ops = torch.empty(max(1, n * len(m) * ops_stride), dtype=torch.uint8, device=d_text.device) if ops_stride is not None else None
+    rc = _lib.lib().bg_myers_long_best_batch_dev(ctx.h, peq.ctypes.data, blk_off.ctypes.data, m.ctypes.data, len(m), _max_dist(max_dist), n,
+                                                 d_text.data_ptr(), d_off.data_ptr(), d_aln.data_ptr(),
+                                                 d_ops.data_ptr() if d_ops is not None else None, ops_stride or 0, stream)
+    _raise_unless(rc, "bg_myers_long_best_batch_dev", (-9,) if allow_ops_cap else ())
+    return d_aln, d_ops
+
+
+def long_find_all_batch_dev(patterns, d_text, d_off, max_dist, max_hits, ends_only=False, ctx=None, stream=0, out=None):
+    """bg_myers_long_find_all_batch_dev; arguments and results as find_all_batch_dev"""
+    import torch
+    ctx = ctx or _lib.default_context()
+    peq, blk_off, m = long_patterns_array(patterns)
+    n = int(d_off.numel()) - 1
+    if out is not None:
+        d_aln, d_count = out
+    else:
+        d_aln = torch.empty(n * len(m) * max(0, min(int(max_hits), MYERS_MAX_HITS)) * 64, dtype=torch.uint8, device=d_text.device)
+        d_count = torch.empty(n * len(m), dtype=torch.int32, device=d_text.device)
+    _lib.check(_lib.lib().bg_myers_long_find_all_batch_dev(ctx.h, peq.ctypes.data, blk_off.ctypes.data, m.ctypes.data, len(m),
+                                                           _max_dist(max_dist), int(max_hits), MYERS_ENDS_ONLY if ends_only else 0, n,
+                                                           d_text.data_ptr(), d_off.data_ptr(), d_aln.data_ptr(), d_count.data_ptr(),
+                                                           stream), "bg_myers_long_find_all_batch_dev")
     return d_aln, d_count
 
 
