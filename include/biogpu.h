@@ -111,6 +111,8 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *                      four-line ASCII records in front (tests, A/B)
  *   sam_lanes          lanes that format one line in bg_sam_emit_batch_dev's write pass: 16 or 32 (0 = default; tests, A/B: the
  *                      text does not depend on it)
+ *   fq_emit_mode       bg_fastq_emit_dev's text pass: 1 byte stores straight to the output, 2 lines staged in LDS and stored 16
+ *                      bytes wide (0 = default, which is 1; tests, A/B: the text does not depend on it)
  *   sa_chunk_symbols   suffixes sorted per pass of round 0 of bg_suffix_array_dev[64] (0 = derived from free device memory;
  *                      tests use small values so that short texts take several passes)
  *   band_budget_gb     traceback + aux bytes per scratch set of the banded pipeline, in GB (0 = default: 40, and never more
@@ -1179,6 +1181,63 @@ int bg_fastq_trim(bg_ctx* ctx, uint64_t n, int mode, const bg_alignment_t* hits,
                   const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual, const uint64_t* qual_off,
                   bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out, uint8_t* qual_out,
                   uint64_t* qual_off_out, uint64_t* totals);
+
+/* ---- FASTQ out (fastq_emit.hip): select parsed or trimmed records, write FASTQ text -----------------------------------
+ * bg_fastq_filter[_dev] drops records and compacts what stays (rust-bio has no filter: the rule is defined here).  The inputs
+ * are the columns bg_fastq_parse[_dev] or bg_fastq_trim[_dev] leave: n records, their sequences and qualities with n + 1
+ * offsets each; a record's sequence length is seq_off[r + 1] - seq_off[r], as the trim takes it.
+ *   A record PASSES if every criterion that is switched on holds:
+ *     min_len <= sequence length <= max_len (0 and 0xFFFFFFFF: no bound);
+ *     at most max_n bytes 'N' or 'n' in the sequence (0xFFFFFFFF: not counted, the sequence is not read);
+ *     BG_FQF_CHECK_OK: recs[r].check == BG_FQCHECK_OK;
+ *     BG_FQF_DISCARD_UNTRIMMED: the record is trimmed; BG_FQF_DISCARD_TRIMMED: it is not.  A record is "trimmed" if some
+ *       pattern of it has a hit, hits[r * n_pat + p].score != BG_MIN_SCORE: the records of the best call the trim was given
+ *       (hits and n_pat are not looked at without one of the two flags; hits may then be null and n_pat 0).
+ *   A record is KEPT if it passes; with BG_FQF_PAIRED records 2p and 2p + 1 are mates and are kept or dropped together:
+ *     the pair is kept if both pass, with BG_FQF_PAIR_BOTH unless both fail.
+ * The kept records come out in input order, compacted: copies with seq_off and qual_off rewritten (ids, descriptions,
+ * lengths and `check` unchanged; id_off and desc_off keep pointing into the FASTQ text), sequences and qualities with
+ * n_kept + 1 offsets each (the first 0; capacity n + 1).  keep (optional) receives n bytes 0 or 1.  totals (optional, host, 3
+ * entries: records kept, sequence bytes, quality bytes) costs the device flavour its only synchronisation of `stream`.
+ * Capacities are those of the inputs; no output may alias an input.  A filter with nothing switched on copies its input.
+ * BG_ERR_INVALID_ARG: unknown flag bits, both DISCARD flags, a DISCARD flag with null hits or n_pat == 0, BG_FQF_PAIR_BOTH
+ * without BG_FQF_PAIRED, BG_FQF_PAIRED with odd n, min_len > max_len, null pointers as bg_fastq_trim refuses them;
+ * BG_ERR_TOO_LARGE: n_pat > BG_MYERS_MAX_PATTERNS.  All of them before any device call. */
+enum { BG_FQF_PAIRED = 1, BG_FQF_PAIR_BOTH = 2, BG_FQF_DISCARD_UNTRIMMED = 4, BG_FQF_DISCARD_TRIMMED = 8, BG_FQF_CHECK_OK = 16 };
+typedef struct {
+    uint32_t flags;     /* BG_FQF_* */
+    uint32_t min_len;   /* pass: sequence length >= min_len (0: every length) */
+    uint32_t max_len;   /* pass: sequence length <= max_len (0xFFFFFFFF: no bound) */
+    uint32_t max_n;     /* pass: at most max_n bytes 'N' or 'n' in the sequence; 0xFFFFFFFF: not counted, the sequence is not read */
+} bg_fastq_filter_t;
+int bg_fastq_filter_dev(bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t* flt, const bg_alignment_t* d_hits, uint32_t n_pat,
+                        const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
+                        const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
+                        uint8_t* d_qual_out, uint64_t* d_qual_off_out, uint8_t* d_keep, uint64_t* totals, void* stream);
+int bg_fastq_filter(bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t* flt, const bg_alignment_t* hits, uint32_t n_pat,
+                    const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
+                    const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out,
+                    uint8_t* qual_out, uint64_t* qual_off_out, uint8_t* keep, uint64_t* totals);
+/* bio::io::fastq::Writer::write(id, desc, seq, qual) (io/fastq.rs:573-593; also Display for Record, 473-485) for records
+ * first, first + step, ... below n: m lines and m + 1 offsets.  step 1 writes every record; (0, 2) and (1, 2) split
+ * interleaved mates into an R1 and an R2 text.  A line is
+ *     '@' id [' ' desc] '\n' seq '\n' '+' '\n' qual '\n'
+ * with the space and the description where has_desc != 0 (has_desc with desc_len == 0 gives "@id \n"); id and description are
+ * id_len / desc_len bytes of the FASTQ text at id_off / desc_off, sequence and qualities seq_len / qual_len bytes at
+ * seq + seq_off / qual + qual_off: the record's own fields, as bg_sam_emit_batch_dev takes them (a line is shorter than 2^32
+ * bytes).  Like the reference's writer the call checks nothing: a record with unequal lengths or an empty sequence is written
+ * as it is.  The reference's READER rejects the latter — the empty quality line of "@id\n\n+\n\n" raises IncompleteRecord
+ * (fastq.rs:298-300) — so records that bg_fastq_trim left empty go through bg_fastq_filter with min_len >= 1 first.
+ * Output conventions of bg_sam_emit_batch_dev: one contiguous buffer, lines in order; all lengths and offsets are computed
+ * first and the total is read back with one synchronisation of `stream` into *out_bytes; out == NULL with out_cap == 0 is a
+ * sizing call that fills out_off; a total above out_cap returns BG_ERR_OPS_CAP before one byte is written.
+ * BG_ERR_INVALID_ARG: step == 0, a null out_off or out_bytes, a null out with out_cap != 0, or (m > 0) a null text, recs,
+ * seq or qual.  The host flavour takes the extents of the text, seq and qual from the records it writes. */
+int bg_fastq_emit_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, const uint8_t* d_fastq_text,
+                      const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint8_t* d_qual, char* d_out, uint64_t out_cap,
+                      uint64_t* d_out_off, uint64_t* out_bytes, void* stream);
+int bg_fastq_emit(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, const uint8_t* fastq_text, const bg_fastq_record_t* recs,
+                  const uint8_t* seq, const uint8_t* qual, char* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_bytes);
 
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI

@@ -1025,7 +1025,7 @@ inline SampledSuffixArray sample(const RawSuffixArray& sa, const Text& t, const 
 }  // namespace suffix_array
 }  // namespace data_structures
 
-// bio::io::fastq, reading side (io/fastq.rs:153-527), over a text held in memory; parsed on the device
+// bio::io::fastq (io/fastq.rs:153-599) over texts held in memory: parsed, filtered and written on the device
 namespace io {
 namespace fastq {
 struct ReadError : Panic {  // fastq.rs:113-126
@@ -1101,6 +1101,87 @@ private:
     uint64_t err_pos_ = 0;
     bool raised_ = false;
 };
+
+// fastq::Writer (fastq.rs:528-599) into memory: records are collected, flush() writes their text with one device call
+// (bg_fastq_emit) and get_ref() is what the reference's writer holds after flush().  Like the reference it checks nothing.
+class Writer {
+public:
+    explicit Writer(std::shared_ptr<Context> ctx = nullptr) : ctx_(ctx ? std::move(ctx) : Context::shared_default()) {}
+    void write(const std::string& id, const std::optional<std::string>& desc, const Text& seq, const Text& qual) {  // fastq.rs:573-593
+        bg_fastq_record_t r = {};
+        r.id_off = names_.size();
+        r.id_len = (uint32_t)id.size();
+        names_.insert(names_.end(), id.begin(), id.end());
+        if (desc) {
+            r.has_desc = 1;
+            r.desc_off = names_.size();
+            r.desc_len = (uint32_t)desc->size();
+            names_.insert(names_.end(), desc->begin(), desc->end());
+        }
+        r.seq_off = seq_.size();
+        r.seq_len = (uint32_t)seq.size();
+        seq_.insert(seq_.end(), seq.begin(), seq.end());
+        r.qual_off = qual_.size();
+        r.qual_len = (uint32_t)qual.size();
+        qual_.insert(qual_.end(), qual.begin(), qual.end());
+        recs_.push_back(r);
+    }
+    void write_record(const Record& record) { write(record.id(), record.desc(), record.seq(), record.qual()); }  // fastq.rs:568-570
+    void flush() {  // fastq.rs:596-598
+        if (recs_.empty()) return;
+        Text names = names_, seq = seq_, qual = qual_;
+        names.push_back(0), seq.push_back(0), qual.push_back(0);  // no empty buffers: the call refuses null pointers
+        std::vector<uint64_t> off(recs_.size() + 1);
+        uint64_t total = 0;
+        check(bg_fastq_emit(ctx_->raw(), recs_.size(), 0, 1, names.data(), recs_.data(), seq.data(), qual.data(), nullptr, 0, off.data(), &total),
+              "bg_fastq_emit");
+        const size_t at = out_.size();
+        out_.resize(at + total + 1);
+        check(bg_fastq_emit(ctx_->raw(), recs_.size(), 0, 1, names.data(), recs_.data(), seq.data(), qual.data(), (char*)out_.data() + at, total,
+                            off.data(), &total),
+              "bg_fastq_emit");
+        out_.resize(at + total);
+        recs_.clear(), names_.clear(), seq_.clear(), qual_.clear();
+    }
+    const Text& get_ref() const { return out_; }
+
+private:
+    std::shared_ptr<Context> ctx_;
+    std::vector<bg_fastq_record_t> recs_;
+    Text names_, seq_, qual_, out_;
+};
+
+// bg_fastq_filter over the columns of a parse or a trim (the rule is defined in include/biogpu.h; rust-bio has no filter)
+struct Columns {
+    std::vector<bg_fastq_record_t> recs;
+    Text seq, qual;
+    std::vector<uint64_t> seq_off, qual_off;  // recs.size() + 1 entries each
+};
+inline Columns filter(const Columns& in, const bg_fastq_filter_t& flt, const std::vector<bg_alignment_t>& hits = {}, uint32_t n_pat = 0,
+                      std::vector<uint8_t>* keep = nullptr, std::shared_ptr<Context> ctx = nullptr) {
+    if (!ctx) ctx = Context::shared_default();
+    const uint64_t n = in.recs.size();
+    Columns out;
+    out.recs.resize(n);
+    out.seq.resize(in.seq.size() + 1);
+    out.qual.resize(in.qual.size() + 1);
+    out.seq_off.resize(n + 1);
+    out.qual_off.resize(n + 1);
+    if (keep) keep->resize(n);
+    Text seq = in.seq, qual = in.qual;
+    seq.push_back(0), qual.push_back(0);
+    uint64_t totals[3] = {0, 0, 0};
+    check(bg_fastq_filter(ctx->raw(), n, &flt, hits.empty() ? nullptr : hits.data(), n_pat, in.recs.data(), seq.data(), in.seq_off.data(),
+                          qual.data(), in.qual_off.data(), out.recs.data(), out.seq.data(), out.seq_off.data(), out.qual.data(),
+                          out.qual_off.data(), keep ? keep->data() : nullptr, totals),
+          "bg_fastq_filter");
+    out.recs.resize(totals[0]);
+    out.seq.resize(totals[1]);
+    out.qual.resize(totals[2]);
+    out.seq_off.resize(totals[0] + 1);
+    out.qual_off.resize(totals[0] + 1);
+    return out;
+}
 }  // namespace fastq
 
 // bio::io::fasta, reading side (io/fasta.rs:334-359, 982-1009, 1090-1111), over a text held in memory; parsed on the device

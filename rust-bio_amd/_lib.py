@@ -172,6 +172,10 @@ assert MYERS_PATTERN_DTYPE.itemsize == 2056, MYERS_PATTERN_DTYPE.itemsize
 MYERS_ENDS_ONLY, MYERS_MAX_PATTERNS, MYERS_MAX_HITS = 1, 1024, 64
 MYERS_LONG_MAX_M = 1024
 TRIM_3P, TRIM_5P = 0, 1
+# bg_fastq_filter_t and BG_FQF_* (bg_fastq_filter[_dev])
+FQ_FILTER_DTYPE = np.dtype([("flags", "<u4"), ("min_len", "<u4"), ("max_len", "<u4"), ("max_n", "<u4")])
+assert FQ_FILTER_DTYPE.itemsize == 16, FQ_FILTER_DTYPE.itemsize
+FQF_PAIRED, FQF_PAIR_BOTH, FQF_DISCARD_UNTRIMMED, FQF_DISCARD_TRIMMED, FQF_CHECK_OK = 1, 2, 4, 8, 16
 
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
            "bg_set_option", "bg_suffix_array", "bg_bwt", "bg_less", "bg_fm_build", "bg_fm_free",
@@ -201,7 +205,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_fmd_smems_batch64", "bg_fmd_smems_batch64_dev", "bg_fmd_interval_batch64",
            "bg_myers_best_batch", "bg_myers_best_batch_dev", "bg_myers_find_all_batch", "bg_myers_find_all_batch_dev",
            "bg_myers_long_best_batch", "bg_myers_long_best_batch_dev", "bg_myers_long_find_all_batch", "bg_myers_long_find_all_batch_dev",
-           "bg_fastq_trim", "bg_fastq_trim_dev"]
+           "bg_fastq_trim", "bg_fastq_trim_dev", "bg_fastq_filter", "bg_fastq_filter_dev", "bg_fastq_emit", "bg_fastq_emit_dev"]
 
 
 def build(force=False):
@@ -372,6 +376,10 @@ def lib():
         L.bg_myers_long_find_all_batch_dev.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp]
         L.bg_fastq_trim.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bg_fastq_trim_dev.argtypes = [vp, u64, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_filter.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_filter_dev.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_emit.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+        L.bg_fastq_emit_dev.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64), vp]
         for s in SYMBOLS:
             if getattr(L, s).restype is C.c_int or s.startswith("bg_") and getattr(L, s).restype is None:
                 pass

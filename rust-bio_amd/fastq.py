@@ -1,11 +1,15 @@
-"""`bio::io::fastq` reading side (io/fastq.rs:153-527) on a FASTQ text held in memory: the records are parsed
-on the device (csrc/fastq_ingest.hip) — line index, four-line hypothesis, sequential walk only where it fails —
-and the sequences land concatenated with offsets, i.e. in the layout the aligner's batch calls take."""
+"""`bio::io::fastq` (io/fastq.rs:153-599) on FASTQ text held in memory.  Reading: the records are parsed on the device
+(csrc/fastq_ingest.hip) — line index, four-line hypothesis, sequential walk only where it fails — and the sequences land
+concatenated with offsets, i.e. in the layout the aligner's batch calls take.  Writing (csrc/fastq_emit.hip): `Writer`,
+`emit_arrays` / `emit_dev` write the text of parsed, trimmed or filtered records on the device, `filter_arrays` /
+`filter_dev` select records by length, 'N' count, `check`, trim state and pair (the rule is defined in include/biogpu.h)."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
+
+from ._lib import FQF_CHECK_OK, FQF_DISCARD_TRIMMED, FQF_DISCARD_UNTRIMMED, FQF_PAIR_BOTH, FQF_PAIRED  # noqa: F401
 
 STATUS = ["ok", "MissingAt", "IncompleteRecord", "Io"]
 CHECK = ["ok", "EmptyId", "NonAsciiSequence", "InvalidSequence", "NonAsciiQualities", "UnequalLength"]
@@ -133,3 +137,163 @@ class Reader:
             yield p.record(k)
         if p.status != "ok":
             raise ReadError(p.status, p.err_pos)
+
+
+# ---- filtering -------------------------------------------------------------------------------------------------------
+NO_BOUND = 0xFFFFFFFF
+
+
+def filter_params(flags=0, min_len=0, max_len=NO_BOUND, max_n=NO_BOUND):
+    """bg_fastq_filter_t as a one-element array"""
+    f = np.zeros(1, dtype=_lib.FQ_FILTER_DTYPE)
+    f["flags"], f["min_len"], f["max_len"], f["max_n"] = flags, min_len, max_len, max_n
+    return f
+
+
+def filter_arrays(recs, seq, seq_off, qual, qual_off, flags=0, min_len=0, max_len=NO_BOUND, max_n=NO_BOUND, hits=None, n_pat=0, ctx=None):
+    """bg_fastq_filter over host arrays (the columns of parse_arrays or myers.trim; hits: the records of best_batch the trim
+    was given, needed by the two DISCARD flags only).  Returns (recs, seq, seq_off, qual, qual_off, keep): the kept records
+    compacted, and keep[n] = 0 / 1."""
+    ctx = ctx or _lib.default_context()
+    n = len(recs)
+    f = filter_params(flags, min_len, max_len, max_n)
+    hits = np.ascontiguousarray(hits, dtype=_lib.ALN_DTYPE) if hits is not None else None
+    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
+    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
+    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    o_recs = np.zeros(n, dtype=_lib.FQREC_DTYPE)
+    o_seq, o_qual = np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(max(1, len(qual)), dtype=np.uint8)
+    o_so, o_qo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    keep = np.zeros(max(1, n), dtype=np.uint8)
+    tot = (C.c_uint64 * 3)()
+    _lib.check(_lib.lib().bg_fastq_filter(ctx.h, n, f.ctypes.data, hits.ctypes.data if hits is not None else None, int(n_pat),
+                                          recs.ctypes.data, seq.ctypes.data, seq_off.ctypes.data, qual.ctypes.data, qual_off.ctypes.data,
+                                          o_recs.ctypes.data, o_seq.ctypes.data, o_so.ctypes.data, o_qual.ctypes.data, o_qo.ctypes.data,
+                                          keep.ctypes.data, tot), "bg_fastq_filter")
+    k = int(tot[0])
+    return o_recs[:k], o_seq[:int(tot[1])], o_so[:k + 1], o_qual[:int(tot[2])], o_qo[:k + 1], keep[:n]
+
+
+def filter_dev(n, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, flags=0, min_len=0, max_len=NO_BOUND, max_n=NO_BOUND, d_hits=None, n_pat=0,
+               ctx=None, stream=0, want_totals=True, want_keep=False, out=None):
+    """bg_fastq_filter_dev on torch device tensors (the outputs of parse_dev or myers.trim_dev).  Returns (d_recs, d_seq,
+    d_seq_off, d_qual, d_qual_off, d_keep, totals) — new tensors in HBM, never the inputs; totals = (records kept, sequence
+    bytes, quality bytes), and the record and offset tensors cut to the kept records — or None (then the call does not
+    synchronise and the tensors keep the capacity of the inputs).  d_keep: n bytes 0 / 1, or None without want_keep.  `out`:
+    the first six results of an earlier call of the same shape made without totals, to write into instead of allocating."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    dev = d_seq.device
+    f = filter_params(flags, min_len, max_len, max_n)
+    if out is not None:
+        o_recs, o_seq, o_so, o_qual, o_qo, d_keep = out[:6]
+    else:
+        o_recs = torch.empty(n * 56, dtype=torch.uint8, device=dev)
+        o_seq = torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev)
+        o_qual = torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev)
+        o_so = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        o_qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_keep = torch.empty(max(1, n), dtype=torch.uint8, device=dev) if want_keep else None
+    tot = (C.c_uint64 * 3)()
+    _lib.check(_lib.lib().bg_fastq_filter_dev(ctx.h, n, f.ctypes.data, d_hits.data_ptr() if d_hits is not None else None, int(n_pat),
+                                              d_recs.data_ptr(), d_seq.data_ptr(), d_seq_off.data_ptr(), d_qual.data_ptr(),
+                                              d_qual_off.data_ptr(), o_recs.data_ptr(), o_seq.data_ptr(), o_so.data_ptr(),
+                                              o_qual.data_ptr(), o_qo.data_ptr(), d_keep.data_ptr() if d_keep is not None else None,
+                                              tot if want_totals else None, stream), "bg_fastq_filter_dev")
+    if not want_totals:
+        return o_recs, o_seq, o_so, o_qual, o_qo, d_keep, None
+    k = int(tot[0])
+    return o_recs[:k * 56], o_seq, o_so[:k + 1], o_qual, o_qo[:k + 1], d_keep, (k, int(tot[1]), int(tot[2]))
+
+
+# ---- writing ---------------------------------------------------------------------------------------------------------
+def n_lines(n, first=0, step=1):
+    """how many of n records `first, first + step, ...` are"""
+    return (n - first - 1) // step + 1 if first < n else 0
+
+
+def emit_arrays(parsed, first=0, step=1, ctx=None):
+    """bg_fastq_emit over host arrays: `parsed` is a Parsed, or (text, recs, seq, qual) — the FASTQ text the ids point into
+    and the columns of parse_arrays, myers.trim or filter_arrays.  Returns (text bytes, offsets uint64[m + 1]) of the records
+    first, first + step, ..."""
+    ctx = ctx or _lib.default_context()
+    text, recs, seq, qual = (parsed.text, parsed.recs, parsed.seq, parsed.qual) if isinstance(parsed, Parsed) else parsed
+    text, seq, qual = _lib.as_u8(text), _lib.as_u8(seq), _lib.as_u8(qual)
+    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
+    n = len(recs)
+    off = np.zeros(n_lines(n, first, step) + 1, dtype=np.uint64)
+    total = C.c_uint64(0)
+    args = (ctx.h, n, int(first), int(step), text.ctypes.data, recs.ctypes.data, seq.ctypes.data, qual.ctypes.data)
+    _lib.check(_lib.lib().bg_fastq_emit(*args, None, 0, off.ctypes.data, C.byref(total)), "bg_fastq_emit")
+    out = np.zeros(max(1, int(total.value)), dtype=np.uint8)
+    _lib.check(_lib.lib().bg_fastq_emit(*args, out.ctypes.data, int(total.value), off.ctypes.data, C.byref(total)), "bg_fastq_emit")
+    return out[:int(total.value)].tobytes(), off
+
+
+def emit_dev(n, d_text, d_recs, d_seq, d_qual, first=0, step=1, ctx=None, stream=0, out=None):
+    """bg_fastq_emit_dev on torch device tensors (d_text: the FASTQ text that was parsed; the other three as parse_dev,
+    myers.trim_dev or filter_dev return them).  Returns (d_out uint8[total], d_off int64[m + 1], total) in HBM: a sizing call,
+    then the writing one.  `out`: (d_out, d_off) to write into — one call; BiogpuError OPS_CAP if d_out is too small."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    total = C.c_uint64(0)
+    args = (ctx.h, n, int(first), int(step), d_text.data_ptr(), d_recs.data_ptr(), d_seq.data_ptr(), d_qual.data_ptr())
+    if out is not None:
+        d_out, d_off = out
+    else:
+        d_off = torch.empty(n_lines(n, first, step) + 1, dtype=torch.int64, device=d_seq.device)
+        _lib.check(_lib.lib().bg_fastq_emit_dev(*args, None, 0, d_off.data_ptr(), C.byref(total), stream), "bg_fastq_emit_dev")
+        d_out = torch.empty(max(1, int(total.value)), dtype=torch.uint8, device=d_seq.device)
+    _lib.check(_lib.lib().bg_fastq_emit_dev(*args, d_out.data_ptr(), int(d_out.numel()), d_off.data_ptr(), C.byref(total), stream),
+               "bg_fastq_emit_dev")
+    return d_out[:int(total.value)], d_off, int(total.value)
+
+
+class Writer:
+    """fastq::Writer (fastq.rs:528-599) into memory: records are collected and their text is written on the device, a batch
+    at a time (bg_fastq_emit); getvalue() is what the reference's writer has written after flush()."""
+
+    def __init__(self, ctx=None, batch=1 << 16):
+        self._ctx, self._batch = ctx, batch
+        self._pending, self._done = [], []
+
+    def write(self, id, desc, seq, qual):  # fastq.rs:573-593
+        self._pending.append((_bytes(id), None if desc is None else _bytes(desc), bytes(seq), bytes(qual)))
+        if len(self._pending) >= self._batch:
+            self.flush()
+
+    def write_record(self, record):  # fastq.rs:568-570
+        self.write(record._id, record._desc, record._seq, record._qual)
+
+    def flush(self):  # fastq.rs:596-598
+        if not self._pending:
+            return
+        recs = np.zeros(len(self._pending), dtype=_lib.FQREC_DTYPE)
+        names, seqs, quals = [], [], []
+        t = s = q = 0
+        for k, (id_, desc, seq, qual) in enumerate(self._pending):
+            r = recs[k]
+            r["id_off"], r["id_len"] = t, len(id_)
+            names.append(id_)
+            t += len(id_)
+            if desc is not None:
+                r["has_desc"], r["desc_off"], r["desc_len"] = 1, t, len(desc)
+                names.append(desc)
+                t += len(desc)
+            r["seq_off"], r["seq_len"], r["qual_off"], r["qual_len"] = s, len(seq), q, len(qual)
+            seqs.append(seq)
+            quals.append(qual)
+            s += len(seq)
+            q += len(qual)
+        pad = b"\0"  # no empty buffers: the call refuses null pointers
+        text, _ = emit_arrays((b"".join(names) + pad, recs, b"".join(seqs) + pad, b"".join(quals) + pad), ctx=self._ctx)
+        self._done.append(text)
+        self._pending = []
+
+    def getvalue(self):
+        self.flush()
+        return b"".join(self._done)
+
+
+def _bytes(s):
+    return s.encode() if isinstance(s, str) else bytes(s)
