@@ -1,8 +1,10 @@
-"""`bg_pretty_batch` (csrc/align_text.hip: bio-types `Alignment::pretty`, parity unpinned) against the oracle's restatement, on the
-alignments of the reference's own known-answer tests and on random pairs in every mode."""
+"""`bg_pretty_batch` (csrc/align_text.hip: bio-types `Alignment::pretty`, parity unpinned) against the oracle's restatement and
+the plain one of tests/align_text_oracle.py, on the alignments of the reference's own known-answer tests and on random pairs in
+every mode."""
 import numpy as np
 import pytest
 
+import align_text_oracle as ato
 import oracle_py as orc
 from kat_util import load, scoring_kwargs
 from rust_bio_amd import _lib, synth
@@ -31,6 +33,8 @@ def test_reference_kat_alignments_pretty():
             a = al.align_batch(MODES[mode], [x], [y])[0]
             want = orc.pretty({"xstart": a.xstart, "ystart": a.ystart, "mode": mode}, ops_u64(a.operations), x, y, 60)
             assert a.pretty(x, y, 60) == want, (case.get("name"), mode)
+            kinds, clips = [KIND[t[0]] for t in a.operations], [int(t[1:]) for t in a.operations if t[0] in "XY"]
+            assert want == ato.pretty({"xstart": a.xstart, "ystart": a.ystart, "xlen": a.xlen, "ylen": a.ylen, "mode": mode}, kinds, clips, x, y, 60)
 
 
 @pytest.mark.parametrize("mode", ["custom", "global", "semiglobal", "local"])
@@ -50,6 +54,8 @@ def test_random_pairs_batch(mode):
         toks = [int(v) | ((next(clip) if v >= 4 else 0) << 8) for v in ops[o:o + k]]
         want = orc.pretty({"xstart": int(out["xstart"][p]), "ystart": int(out["ystart"][p]), "mode": mode}, toks, xs[p], ys[p], 50)
         assert got[p] == want, p
+        rec = {f: int(out[f][p]) for f in ("xstart", "ystart", "xlen", "ylen")}
+        assert got[p] == ato.pretty(dict(rec, mode=mode), ops[o:o + k], out["clip_len"][p], xs[p], ys[p], 50), p
 
 
 def test_non_ascii_byte_is_the_crates_panic():
@@ -60,3 +66,5 @@ def test_non_ascii_byte_is_the_crates_panic():
         a.pretty(x, y, 80)
     with pytest.raises(AssertionError):
         orc.pretty({"xstart": a.xstart, "ystart": a.ystart, "mode": "local"}, ops_u64(a.operations), x, y, 80)
+    with pytest.raises(AssertionError):
+        ato.pretty({"xstart": a.xstart, "ystart": a.ystart, "mode": "local"}, [KIND[t[0]] for t in a.operations], [], x, y, 80)
