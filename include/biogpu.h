@@ -1239,6 +1239,79 @@ int bg_fastq_emit_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, co
 int bg_fastq_emit(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, const uint8_t* fastq_text, const bg_fastq_record_t* recs,
                   const uint8_t* seq, const uint8_t* qual, char* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_bytes);
 
+/* ---- demultiplexing by barcode (fastq_demux.hip): a sample per read, the records grouped by sample -------------------
+ * rust-bio has no demultiplexer, as it has no trimmer and no filter: both rules are defined here.
+ *
+ * bg_fastq_demux_assign[_dev] turns the n * n_pat records of bg_myers_best_batch[_dev] or bg_myers_long_best_batch[_dev]
+ * (read r's at r * n_pat) into one sample per read.  pat_bin (host, n_pat entries) names the sample of every pattern:
+ * pat_bin[p] < n_bins, several patterns may share one; BG_DMX_IGNORE skips a pattern, so that adapters and barcodes can go
+ * through one Myers call.
+ *   1. A hit COUNTS if score != BG_MIN_SCORE, its pattern is not ignored, with BG_DMX_ANCHOR_5P ystart <= max_offset, with
+ *      BG_DMX_ANCHOR_3P ylen - yend <= max_offset.  With neither anchor flag a hit anywhere counts and max_offset is not
+ *      looked at.
+ *   2. The WINNER is the counting hit with the smallest (score, p); `best` is its score, b the bin of its pattern.
+ *   3. `second` is the smallest score among the counting hits whose bin is not b, infinite if there is none.
+ *   4. bin[r] = n_bins (UNASSIGNED) if no hit counts; n_bins + 1 (AMBIGUOUS) if second - best < min_margin; b otherwise.
+ *      With min_margin = 0 nothing is ambiguous and a tie between bins goes to the lower pattern index.
+ *   5. hit_out[r] is the winning record, copied verbatim, where the read is assigned (bin[r] < n_bins); otherwise a no-hit
+ *      record: score = BG_MIN_SCORE, ylen and mode of hits[r * n_pat], every other byte 0.  bg_fastq_trim[_dev] with
+ *      n_pat = 1 on hit_out cuts exactly the read's own barcode, and nothing off a read that has none.
+ *   6. pat_out[r] (optional) is the p of the record in hit_out[r], BG_DMX_IGNORE where that is a no-hit record.
+ *   7. With BG_DMX_PAIRED (n even) records 2q and 2q + 1 are mates.  BG_DMX_MATE1 and / or BG_DMX_MATE2 say whose hits count
+ *      (neither flag: both).  The pair's candidates are the counting hits of those mates, mate 1 before mate 2 among equal
+ *      (score, p); rules 2 to 4 over them give ONE bin, which both mates get.  hit_out and pat_out carry the winner on the
+ *      mate that holds it and a no-hit record on the other.
+ * Refused before any device call — BG_ERR_INVALID_ARG: null params, unknown flag bits, both anchor flags, a MATE flag
+ * without BG_DMX_PAIRED, BG_DMX_PAIRED with odd n, n_bins == 0, n_pat == 0, a null pat_bin, a pat_bin entry that is neither
+ * below n_bins nor BG_DMX_IGNORE, (n > 0) a null hits, bin or hit_out; BG_ERR_TOO_LARGE: n_bins > BG_DMX_MAX_BINS,
+ * n_pat > BG_MYERS_MAX_PATTERNS.  hit_out must not alias hits.  The device flavour is asynchronous on `stream` (pat_bin is
+ * consumed before it returns); the call is deterministic.
+ *
+ * bg_fastq_demux_split[_dev] is a stable partition of the columns of a parse, a trim or a filter by bin.  There are
+ * n_bins + 2 groups: the samples, then unassigned, then ambiguous; a bin value above n_bins + 1 counts as unassigned.
+ * The output columns are the input columns reordered so that group 0's records come first, each group in input order:
+ * records are copies with seq_off / qual_off rewritten, sequences and qualities are compacted with n + 1 offsets each
+ * (capacities of the inputs).  bin_off (n_bins + 3 entries): group g's records are bin_off[g] .. bin_off[g + 1], and
+ * bin_off[n_bins + 2] = n.  perm (optional, n entries): perm[k] is the input index of output record k.  With hit (n
+ * records, e.g. assign's hit_out) hit_out[k] = hit[perm[k]], so trimming works before or after the split.  bin_off_host
+ * (optional, host, n_bins + 3 entries) costs the device flavour its only synchronisation of `stream`.  n == 0 writes zero
+ * offsets and returns.  No output may alias an input.
+ *   Pairs: mates that share a bin, as assign leaves them, stay adjacent because the partition is stable, so there is no
+ *   pair flag, and every bin_off of interleaved mates is even.
+ *   Per-sample texts: ONE bg_fastq_emit_dev over the split columns writes every sample's FASTQ into one buffer; sample g's
+ *   text is out[out_off[bin_off[g]] .. out_off[bin_off[g + 1]]).  With (first, step) = (0, 2) and (1, 2) that gives the R1
+ *   and the R2 texts, out_off indexed by bin_off[g] / 2.  Records trimmed to nothing are written as they are (see
+ *   bg_fastq_emit above).
+ * Refused before any device call — BG_ERR_INVALID_ARG: n_bins == 0, a null bin_off or output offsets, hit_out without hit,
+ * (n > 0) a null bin or column; BG_ERR_TOO_LARGE: n_bins > BG_DMX_MAX_BINS.
+ * Out of scope: combinatorial dual-index tables (an i7 x i5 pair of pattern sets mapped to a sample), correcting barcodes
+ * against a whitelist beyond what the Myers call's max_dist gives, and writing files. */
+enum { BG_DMX_ANCHOR_5P = 1, BG_DMX_ANCHOR_3P = 2, BG_DMX_PAIRED = 4, BG_DMX_MATE1 = 8, BG_DMX_MATE2 = 16 };
+enum { BG_DMX_MAX_BINS = 1024 };
+#define BG_DMX_IGNORE 0xFFFFFFFFu /* a pat_bin entry: the pattern names no sample; a pat_out entry: no winner */
+typedef struct {
+    uint32_t flags;       /* BG_DMX_* */
+    uint32_t n_bins;      /* samples: 1 .. BG_DMX_MAX_BINS */
+    uint32_t min_margin;  /* ambiguous: second - best < min_margin */
+    uint32_t max_offset;  /* with an anchor flag: how far from its end of the read a counting hit may lie */
+} bg_demux_params_t;
+int bg_fastq_demux_assign_dev(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* params, const bg_alignment_t* d_hits, uint32_t n_pat,
+                              const uint32_t* pat_bin /* host, n_pat */, uint32_t* d_bin, bg_alignment_t* d_hit_out,
+                              uint32_t* d_pat_out /* optional */, void* stream);
+int bg_fastq_demux_assign(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* params, const bg_alignment_t* hits, uint32_t n_pat,
+                          const uint32_t* pat_bin, uint32_t* bin, bg_alignment_t* hit_out, uint32_t* pat_out /* optional */);
+int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* d_bin, const bg_alignment_t* d_hit /* optional, n */,
+                             const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
+                             const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
+                             uint8_t* d_qual_out, uint64_t* d_qual_off_out, bg_alignment_t* d_hit_out /* optional */,
+                             uint64_t* d_perm /* optional, n */, uint64_t* d_bin_off /* n_bins + 3 */, uint64_t* bin_off_host /* optional */,
+                             void* stream);
+int bg_fastq_demux_split(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* bin, const bg_alignment_t* hit /* optional, n */,
+                         const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
+                         const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out, uint8_t* qual_out,
+                         uint64_t* qual_off_out, bg_alignment_t* hit_out /* optional */, uint64_t* perm /* optional, n */,
+                         uint64_t* bin_off /* n_bins + 3 */);
+
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI
  * only to collect per-query scores/intervals".  One process and one bg_ctx per GPU.  rust-bio has no counterpart (a

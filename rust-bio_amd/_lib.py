@@ -176,6 +176,11 @@ TRIM_3P, TRIM_5P = 0, 1
 FQ_FILTER_DTYPE = np.dtype([("flags", "<u4"), ("min_len", "<u4"), ("max_len", "<u4"), ("max_n", "<u4")])
 assert FQ_FILTER_DTYPE.itemsize == 16, FQ_FILTER_DTYPE.itemsize
 FQF_PAIRED, FQF_PAIR_BOTH, FQF_DISCARD_UNTRIMMED, FQF_DISCARD_TRIMMED, FQF_CHECK_OK = 1, 2, 4, 8, 16
+# bg_demux_params_t and BG_DMX_* (bg_fastq_demux_assign[_dev], bg_fastq_demux_split[_dev])
+DEMUX_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("n_bins", "<u4"), ("min_margin", "<u4"), ("max_offset", "<u4")])
+assert DEMUX_PARAMS_DTYPE.itemsize == 16, DEMUX_PARAMS_DTYPE.itemsize
+DMX_ANCHOR_5P, DMX_ANCHOR_3P, DMX_PAIRED, DMX_MATE1, DMX_MATE2 = 1, 2, 4, 8, 16
+DMX_IGNORE, DMX_MAX_BINS = 0xFFFFFFFF, 1024
 
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
            "bg_set_option", "bg_suffix_array", "bg_bwt", "bg_less", "bg_fm_build", "bg_fm_free",
@@ -205,7 +210,8 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_fmd_smems_batch64", "bg_fmd_smems_batch64_dev", "bg_fmd_interval_batch64",
            "bg_myers_best_batch", "bg_myers_best_batch_dev", "bg_myers_find_all_batch", "bg_myers_find_all_batch_dev",
            "bg_myers_long_best_batch", "bg_myers_long_best_batch_dev", "bg_myers_long_find_all_batch", "bg_myers_long_find_all_batch_dev",
-           "bg_fastq_trim", "bg_fastq_trim_dev", "bg_fastq_filter", "bg_fastq_filter_dev", "bg_fastq_emit", "bg_fastq_emit_dev"]
+           "bg_fastq_trim", "bg_fastq_trim_dev", "bg_fastq_filter", "bg_fastq_filter_dev", "bg_fastq_emit", "bg_fastq_emit_dev",
+           "bg_fastq_demux_assign", "bg_fastq_demux_assign_dev", "bg_fastq_demux_split", "bg_fastq_demux_split_dev"]
 
 
 def build(force=False):
@@ -380,6 +386,10 @@ def lib():
         L.bg_fastq_filter_dev.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bg_fastq_emit.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
         L.bg_fastq_emit_dev.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64), vp]
+        L.bg_fastq_demux_assign.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp]
+        L.bg_fastq_demux_assign_dev.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.bg_fastq_demux_split.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_demux_split_dev.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for s in SYMBOLS:
             if getattr(L, s).restype is C.c_int or s.startswith("bg_") and getattr(L, s).restype is None:
                 pass

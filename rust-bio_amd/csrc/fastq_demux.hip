@@ -1,0 +1,338 @@
+// bg_fastq_demux_assign[_dev] and bg_fastq_demux_split[_dev]: which sample a read belongs to, by the records of a Myers best
+// call, and the stable grouping of parsed, trimmed or filtered records by sample (include/biogpu.h has both rules; rust-bio
+// has no demultiplexer).  The per-record bodies are in fastq_demux_rule.h.
+//
+// Assign, 1 launch: a read's records are 64 bytes apart, so a group of lanes takes a read (1 lane below 16 patterns, 16
+// otherwise) and strides over its patterns; the group reduces (winner's score, pattern, bin; best score of any other bin) by
+// shuffles, the pair rule is one more shuffle with the neighbouring group, and the group's lanes write the 16 words of
+// hit_out.  No lane leaves before the shuffles.  pat_bin travels by value, 16 bits an entry: nothing is staged, nothing of
+// the caller's is read after the call returns.
+//
+// Split, 13 launches — one wide radix pass over up to 1026 groups: a histogram per tile of 2048 records and per group in LDS
+// (atomics only count), written group-major; the shared scan (scan.hip) over that table gives every (group, tile) its base
+// rank; the rank kernel gives every record its stable rank inside its tile's group — per-wavefront counts in LDS turned
+// into bases in wavefront order, then, step by step in input order, the earlier lanes of the same group by ballots over the
+// bits of the group number — and writes perm[k] and the two lengths at k; two more scans give the byte offsets; the copy
+// kernel (16 lanes per output record, the filter's fq_copy_record) moves the bytes.  No atomic decides an order.
+#include <algorithm>
+
+#include "bg_common.h"
+#include "fastq_demux_rule.h"
+
+namespace {
+
+int refuse(const char* why, int rc = BG_ERR_INVALID_ARG) {
+    bg_tls_error = why;
+    return rc;
+}
+
+// ---- assign -------------------------------------------------------------------------------------------------------------
+// G lanes per read.  With BG_DMX_PAIRED n is even and 256 / G is, so a read's mate is in the same wavefront and in range
+// exactly when the read is.
+template <int G>
+__global__ __launch_bounds__(256) void dmx_assign_kernel(uint64_t n, const bg_demux_params_t prm, const bg_alignment_t* __restrict__ hits,
+                                                         uint32_t n_pat, const dmx_bins bins, uint32_t* __restrict__ bin_out,
+                                                         bg_alignment_t* __restrict__ hit_out, uint32_t* __restrict__ pat_out) {
+    const uint64_t r = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / G;
+    const uint32_t lane = threadIdx.x % G, mate = (uint32_t)(r & 1);
+    const bool live = r < n;
+    const bg_alignment_t* mine = hits + r * n_pat;
+    dmx_state s = dmx_empty();
+    if (live && dmx_mate_counts(prm.flags, mate)) s = dmx_lane_share(mine, n_pat, bins.b, prm.flags, prm.max_offset, lane, G);
+    auto from = [&](const dmx_state& v, int o) {
+        return dmx_state{__shfl_xor(v.s1, o), (uint32_t)__shfl_xor((int)v.p1, o), (uint32_t)__shfl_xor((int)v.bin1, o), __shfl_xor(v.s2, o),
+                         (uint32_t)__shfl_xor((int)v.has2, o)};
+    };
+#pragma unroll
+    for (int o = G / 2; o; o >>= 1) s = dmx_merge(s, from(s, o));
+    bool holds = !dmx_is_empty(s);
+    const dmx_state other = from(s, G);
+    if (prm.flags & BG_DMX_PAIRED) s = dmx_pair(s, other, mate, &holds);
+    if (!live) return;
+    const uint32_t bin = dmx_verdict(s, prm.n_bins, prm.min_margin);
+    const bool carries = bin < prm.n_bins && holds;
+    dmx_write_hit(hit_out + r, mine, carries ? mine + s.p1 : nullptr, lane, G);
+    if (lane == 0) {
+        bin_out[r] = bin;
+        if (pat_out) pat_out[r] = carries ? s.p1 : BG_DMX_IGNORE;
+    }
+}
+
+int assign_check(const bg_ctx* ctx, uint64_t n, const bg_demux_params_t* p, const void* hits, uint32_t n_pat, const uint32_t* pat_bin,
+                 const void* bin, const void* hit_out) {
+    if (!p) return refuse("bg_fastq_demux_assign: null params");
+    const uint32_t known = BG_DMX_ANCHOR_5P | BG_DMX_ANCHOR_3P | BG_DMX_PAIRED | BG_DMX_MATE1 | BG_DMX_MATE2;
+    if (p->flags & ~known) return refuse("bg_fastq_demux_assign: unknown flag bits");
+    if ((p->flags & BG_DMX_ANCHOR_5P) && (p->flags & BG_DMX_ANCHOR_3P)) return refuse("bg_fastq_demux_assign: both ANCHOR flags");
+    if ((p->flags & (BG_DMX_MATE1 | BG_DMX_MATE2)) && !(p->flags & BG_DMX_PAIRED)) return refuse("bg_fastq_demux_assign: a MATE flag without PAIRED");
+    if ((p->flags & BG_DMX_PAIRED) && (n & 1)) return refuse("bg_fastq_demux_assign: PAIRED with an odd record count");
+    if (p->n_bins == 0) return refuse("bg_fastq_demux_assign: n_bins 0");
+    if (p->n_bins > BG_DMX_MAX_BINS) return refuse("bg_fastq_demux_assign: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
+    if (n_pat == 0) return refuse("bg_fastq_demux_assign: n_pat 0");
+    if (n_pat > BG_MYERS_MAX_PATTERNS) return refuse("bg_fastq_demux_assign: n_pat above BG_MYERS_MAX_PATTERNS", BG_ERR_TOO_LARGE);
+    if (!pat_bin) return refuse("bg_fastq_demux_assign: null pat_bin");
+    for (uint32_t q = 0; q < n_pat; q++)
+        if (pat_bin[q] >= p->n_bins && pat_bin[q] != BG_DMX_IGNORE) return refuse("bg_fastq_demux_assign: a pat_bin entry names no bin");
+    if (n && (!hits || !bin || !hit_out)) return refuse("bg_fastq_demux_assign: null hits, bin or hit_out");
+    if (!ctx) return refuse("bg_fastq_demux_assign: null ctx");
+    return BG_OK;
+}
+
+// ---- split --------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kGroups = BG_DMX_MAX_BINS + 2;
+
+// count[g * n_tiles + t]: records of tile t in group g
+__global__ __launch_bounds__(256) void dmx_hist_kernel(uint64_t n, uint32_t n_bins, uint32_t n_tiles, const uint32_t* __restrict__ bin,
+                                                       uint32_t* __restrict__ count) {
+    __shared__ uint32_t s_cnt[kGroups];
+    const uint32_t ng = n_bins + 2;
+    for (uint32_t g = threadIdx.x; g < ng; g += 256) s_cnt[g] = 0;
+    __syncthreads();
+    for (uint32_t i = 0; i < DMX_TILE / 256; i++) {
+        const uint64_t r = (uint64_t)blockIdx.x * DMX_TILE + i * 256 + threadIdx.x;
+        if (r < n) atomicAdd(&s_cnt[dmx_group(bin[r], n_bins)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < ng; g += 256) count[(uint64_t)g * n_tiles + blockIdx.x] = s_cnt[g];
+}
+
+// base[g * n_tiles + t]: the scanned table.  A record's place is its (group, tile) base, plus the records of its group in the
+// wavefronts before its own, plus those in the earlier steps of its own wavefront, plus the earlier lanes of its step.
+__global__ __launch_bounds__(256) void dmx_rank_kernel(uint64_t n, uint32_t n_bins, uint32_t n_bits, uint32_t n_tiles,
+                                                       const uint32_t* __restrict__ bin, const uint64_t* __restrict__ base,
+                                                       const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ qual_off,
+                                                       uint64_t* __restrict__ perm, uint32_t* __restrict__ sl_out, uint32_t* __restrict__ ql_out) {
+    __shared__ uint32_t s_w[DMX_WAVES][kGroups];
+    const uint32_t ng = n_bins + 2, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (uint32_t g = threadIdx.x; g < ng; g += 256)
+        for (uint32_t w = 0; w < DMX_WAVES; w++) s_w[w][g] = 0;
+    __syncthreads();
+    uint32_t grp[DMX_STEPS];
+#pragma unroll
+    for (uint32_t i = 0; i < DMX_STEPS; i++) {
+        const uint64_t r = dmx_item(blockIdx.x, wave, i, lane);
+        grp[i] = r < n ? dmx_group(bin[r], n_bins) : 0;
+        if (r < n) atomicAdd(&s_w[wave][grp[i]], 1u);
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < ng; g += 256) {
+        uint32_t run = 0;
+        for (uint32_t w = 0; w < DMX_WAVES; w++) {
+            const uint32_t c = s_w[w][g];
+            s_w[w][g] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    volatile uint32_t* mine = s_w[wave];
+#pragma unroll
+    for (uint32_t i = 0; i < DMX_STEPS; i++) {
+        const uint64_t r = dmx_item(blockIdx.x, wave, i, lane);
+        const bool live = r < n;
+        const uint32_t g = grp[i];
+        uint64_t peers = __ballot(live);
+        for (uint32_t b = 0; b < n_bits; b++) {
+            const uint32_t bit = live ? (g >> b) & 1u : 0u;
+            peers = dmx_narrow(peers, __ballot(bit), bit);
+        }
+        const uint32_t below = dmx_rank_below(peers, lane);
+        const uint32_t before = live ? mine[g] : 0;
+        __builtin_amdgcn_wave_barrier();
+        if (live && below == 0) mine[g] = before + dmx_peer_count(peers);
+        __builtin_amdgcn_wave_barrier();
+        if (live) {
+            const uint64_t k = base[(uint64_t)g * n_tiles + blockIdx.x] + before + below;
+            perm[k] = r;
+            sl_out[k] = (uint32_t)(seq_off[r + 1] - seq_off[r]);
+            ql_out[k] = (uint32_t)(qual_off[r + 1] - qual_off[r]);
+        }
+    }
+}
+
+// bin_off[g] = base[g * n_tiles] for the n_bins + 2 groups, and the closing n (the scan's total)
+__global__ __launch_bounds__(256) void dmx_bin_off_kernel(uint32_t ng, uint32_t n_tiles, const uint64_t* __restrict__ base,
+                                                          uint64_t* __restrict__ bin_off) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g <= ng) bin_off[g] = base[(uint64_t)g * n_tiles];
+}
+
+// 16 lanes per output record k = perm's index.  seq_off_out / qual_off_out hold the scans' n + 1 offsets; fq_copy_record
+// writes entry k again, with the value it was given from there.
+__global__ __launch_bounds__(256) void dmx_copy_kernel(uint64_t n, const uint64_t* __restrict__ perm, const bg_fastq_record_t* __restrict__ recs,
+                                                       const uint8_t* __restrict__ seq, const uint64_t* __restrict__ seq_off,
+                                                       const uint8_t* __restrict__ qual, const uint64_t* __restrict__ qual_off,
+                                                       const bg_alignment_t* __restrict__ hit, bg_fastq_record_t* __restrict__ recs_out,
+                                                       uint8_t* __restrict__ seq_out, uint64_t* seq_off_out, uint8_t* __restrict__ qual_out,
+                                                       uint64_t* qual_off_out, bg_alignment_t* __restrict__ hit_out) {
+    const uint64_t k = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const uint32_t lane = threadIdx.x & 15;
+    if (k >= n) return;
+    const uint64_t r = perm[k];
+    const uint64_t s0 = seq_off[r], q0 = qual_off[r];
+    fq_copy_record(recs[r], seq + s0, (uint32_t)(seq_off[r + 1] - s0), qual + q0, (uint32_t)(qual_off[r + 1] - q0), k, seq_off_out[k],
+                   qual_off_out[k], recs_out, seq_out, seq_off_out, qual_out, qual_off_out, lane, 16);
+    if (hit_out) ((uint32_t*)(hit_out + k))[lane] = ((const uint32_t*)(hit + r))[lane];
+}
+
+int split_check(const bg_ctx* ctx, uint64_t n, uint32_t n_bins, const void* bin, const void* hit, const void* recs, const void* seq,
+                const void* seq_off, const void* qual, const void* qual_off, const void* recs_out, const void* seq_out, const void* seq_off_out,
+                const void* qual_out, const void* qual_off_out, const void* hit_out, const void* bin_off) {
+    if (n_bins == 0) return refuse("bg_fastq_demux_split: n_bins 0");
+    if (n_bins > BG_DMX_MAX_BINS) return refuse("bg_fastq_demux_split: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
+    if (!bin_off) return refuse("bg_fastq_demux_split: null bin_off");
+    if (!seq_off_out || !qual_off_out) return refuse("bg_fastq_demux_split: null output offsets");
+    if (hit_out && !hit) return refuse("bg_fastq_demux_split: hit_out without hit");
+    if (n && (!bin || !recs || !seq || !seq_off || !qual || !qual_off || !recs_out || !seq_out || !qual_out))
+        return refuse("bg_fastq_demux_split: null bin or column");
+    if (!ctx) return refuse("bg_fastq_demux_split: null ctx");
+    return BG_OK;
+}
+
+struct DmxDev {
+    void* p = nullptr;
+    ~DmxDev() { hipFree(p); }
+    int alloc(size_t bytes) {
+        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
+        return BG_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int bg_fastq_demux_assign_dev(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* params, const bg_alignment_t* d_hits, uint32_t n_pat,
+                                         const uint32_t* pat_bin, uint32_t* d_bin, bg_alignment_t* d_hit_out, uint32_t* d_pat_out,
+                                         void* stream) {
+    if (int rc = assign_check(ctx, n, params, d_hits, n_pat, pat_bin, d_bin, d_hit_out)) return rc;
+    if (n == 0) return BG_OK;
+    hipStream_t st = (hipStream_t)stream;
+    BG_HIP(hipSetDevice(ctx->device));
+    dmx_bins bins;
+    for (uint32_t p = 0; p < n_pat; p++) bins.b[p] = pat_bin[p] == BG_DMX_IGNORE ? (uint16_t)DMX_BIN_IGNORE : (uint16_t)pat_bin[p];
+    std::fill(bins.b + n_pat, bins.b + BG_MYERS_MAX_PATTERNS, (uint16_t)DMX_BIN_IGNORE);
+    if (n_pat >= 16)
+        dmx_assign_kernel<16><<<dim3((uint32_t)((n * 16 + 255) / 256)), dim3(256), 0, st>>>(n, *params, d_hits, n_pat, bins, d_bin, d_hit_out,
+                                                                                            d_pat_out);
+    else
+        dmx_assign_kernel<1><<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st>>>(n, *params, d_hits, n_pat, bins, d_bin, d_hit_out, d_pat_out);
+    BG_HIP(hipGetLastError());
+    return BG_OK;
+}
+
+extern "C" int bg_fastq_demux_assign(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* params, const bg_alignment_t* hits, uint32_t n_pat,
+                                     const uint32_t* pat_bin, uint32_t* bin, bg_alignment_t* hit_out, uint32_t* pat_out) {
+    if (int rc = assign_check(ctx, n, params, hits, n_pat, pat_bin, bin, hit_out)) return rc;
+    if (n == 0) return BG_OK;
+    BG_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DmxDev d_hits, d_bin, d_hit_out, d_pat;
+    const size_t hb = (size_t)n * n_pat * sizeof(bg_alignment_t), ob = (size_t)n * sizeof(bg_alignment_t);
+    for (auto pr : {std::pair<DmxDev*, size_t>{&d_hits, hb}, {&d_bin, (size_t)n * 4}, {&d_hit_out, ob}, {&d_pat, (size_t)n * 4}})
+        if (int rc = pr.first->alloc(pr.second)) return rc;
+    BG_HIP(hipMemcpyAsync(d_hits.p, hits, hb, hipMemcpyHostToDevice, st));
+    BG_HIP(hipStreamSynchronize(st));
+    if (int rc = bg_fastq_demux_assign_dev(ctx, n, params, (const bg_alignment_t*)d_hits.p, n_pat, pat_bin, (uint32_t*)d_bin.p,
+                                           (bg_alignment_t*)d_hit_out.p, pat_out ? (uint32_t*)d_pat.p : nullptr, st))
+        return rc;
+    BG_HIP(hipMemcpyAsync(bin, d_bin.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    BG_HIP(hipMemcpyAsync(hit_out, d_hit_out.p, ob, hipMemcpyDeviceToHost, st));
+    if (pat_out) BG_HIP(hipMemcpyAsync(pat_out, d_pat.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    BG_HIP(hipStreamSynchronize(st));
+    return BG_OK;
+}
+
+extern "C" int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* d_bin, const bg_alignment_t* d_hit,
+                                        const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
+                                        const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
+                                        uint8_t* d_qual_out, uint64_t* d_qual_off_out, bg_alignment_t* d_hit_out, uint64_t* d_perm,
+                                        uint64_t* d_bin_off, uint64_t* bin_off_host, void* stream) {
+    if (int rc = split_check(ctx, n, n_bins, d_bin, d_hit, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_recs_out, d_seq_out, d_seq_off_out,
+                             d_qual_out, d_qual_off_out, d_hit_out, d_bin_off))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    BG_HIP(hipSetDevice(ctx->device));
+    const uint32_t ng = n_bins + 2;
+    if (n == 0) {
+        BG_HIP(hipMemsetAsync(d_bin_off, 0, (size_t)(ng + 1) * 8, st));
+        BG_HIP(hipMemsetAsync(d_seq_off_out, 0, 8, st));
+        BG_HIP(hipMemsetAsync(d_qual_off_out, 0, 8, st));
+        if (bin_off_host) std::fill(bin_off_host, bin_off_host + ng + 1, (uint64_t)0);
+        return BG_OK;
+    }
+    bg_scratch_guard guard(ctx, st);
+    // aux: the scanned (group, tile) table (uint64[cells + 1]) and perm (uint64[n], unless the caller takes it), the block sums
+    // of the three scans, then the table's counts and the two length columns at their places (uint32)
+    const uint32_t n_tiles = (uint32_t)((n + DMX_TILE - 1) / DMX_TILE);
+    const size_t cells = (size_t)ng * n_tiles, t_sums = 2 * (cells / 2048 + 2), r_sums = 2 * (size_t)(n / 2048 + 2);
+    const size_t words64 = cells + 1 + (d_perm ? 0 : (size_t)n) + t_sums + 2 * r_sums;
+    if (int rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, words64 * 8 + (cells + 2 * (size_t)n) * 4)) return rc;
+    uint64_t* d_base = (uint64_t*)ctx->aux;
+    uint64_t* perm = d_perm ? d_perm : d_base + cells + 1;
+    uint64_t* d_sums = d_base + cells + 1 + (d_perm ? 0 : (size_t)n);
+    uint32_t* d_count = (uint32_t*)(d_sums + t_sums + 2 * r_sums);
+    uint32_t* d_sl = d_count + cells;
+    uint32_t* d_ql = d_sl + n;
+    dmx_hist_kernel<<<dim3(n_tiles), dim3(256), 0, st>>>(n, n_bins, n_tiles, d_bin, d_count);
+    BG_HIP(hipGetLastError());
+    if (int rc = bg_scan_u32(d_count, cells, d_base, d_sums, st)) return rc;
+    dmx_rank_kernel<<<dim3(n_tiles), dim3(256), 0, st>>>(n, n_bins, dmx_group_bits(n_bins), n_tiles, d_bin, d_base, d_seq_off, d_qual_off, perm,
+                                                         d_sl, d_ql);
+    dmx_bin_off_kernel<<<dim3((ng + 256) / 256), dim3(256), 0, st>>>(ng, n_tiles, d_base, d_bin_off);
+    BG_HIP(hipGetLastError());
+    if (int rc = bg_scan_u32(d_sl, n, d_seq_off_out, d_sums + t_sums, st)) return rc;
+    if (int rc = bg_scan_u32(d_ql, n, d_qual_off_out, d_sums + t_sums + r_sums, st)) return rc;
+    dmx_copy_kernel<<<dim3((uint32_t)((n * 16 + 255) / 256)), dim3(256), 0, st>>>(n, perm, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_hit,
+                                                                                  d_recs_out, d_seq_out, d_seq_off_out, d_qual_out,
+                                                                                  d_qual_off_out, d_hit_out);
+    BG_HIP(hipGetLastError());
+    if (bin_off_host) {
+        BG_HIP(hipMemcpyAsync(bin_off_host, d_bin_off, (size_t)(ng + 1) * 8, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipStreamSynchronize(st));
+    }
+    return BG_OK;
+}
+
+extern "C" int bg_fastq_demux_split(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* bin, const bg_alignment_t* hit,
+                                    const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
+                                    const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out,
+                                    uint8_t* qual_out, uint64_t* qual_off_out, bg_alignment_t* hit_out, uint64_t* perm, uint64_t* bin_off) {
+    if (int rc = split_check(ctx, n, n_bins, bin, hit, recs, seq, seq_off, qual, qual_off, recs_out, seq_out, seq_off_out, qual_out,
+                             qual_off_out, hit_out, bin_off))
+        return rc;
+    BG_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t sb = n ? seq_off[n] : 0, qb = n ? qual_off[n] : 0;
+    DmxDev d_bin, d_hit, d_recs, d_seq, d_so, d_qual, d_qo, o_recs, o_seq, o_so, o_qual, o_qo, o_hit, o_perm, o_boff;
+    const size_t hb = hit ? (size_t)n * sizeof(bg_alignment_t) : 0, rb = (size_t)n * sizeof(bg_fastq_record_t), ob = (size_t)(n + 1) * 8,
+                 gb = (size_t)(n_bins + 3) * 8;
+    for (auto pr : {std::pair<DmxDev*, size_t>{&d_bin, (size_t)n * 4}, {&d_hit, hb}, {&d_recs, rb}, {&d_seq, sb}, {&d_so, ob}, {&d_qual, qb},
+                    {&d_qo, ob}, {&o_recs, rb}, {&o_seq, sb}, {&o_so, ob}, {&o_qual, qb}, {&o_qo, ob}, {&o_hit, hit_out ? hb : 0},
+                    {&o_perm, (size_t)n * 8}, {&o_boff, gb}})
+        if (int rc = pr.first->alloc(pr.second)) return rc;
+    if (n) {
+        BG_HIP(hipMemcpyAsync(d_bin.p, bin, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        if (hb) BG_HIP(hipMemcpyAsync(d_hit.p, hit, hb, hipMemcpyHostToDevice, st));
+        BG_HIP(hipMemcpyAsync(d_recs.p, recs, rb, hipMemcpyHostToDevice, st));
+        if (sb) BG_HIP(hipMemcpyAsync(d_seq.p, seq, sb, hipMemcpyHostToDevice, st));
+        if (qb) BG_HIP(hipMemcpyAsync(d_qual.p, qual, qb, hipMemcpyHostToDevice, st));
+        BG_HIP(hipMemcpyAsync(d_so.p, seq_off, ob, hipMemcpyHostToDevice, st));
+        BG_HIP(hipMemcpyAsync(d_qo.p, qual_off, ob, hipMemcpyHostToDevice, st));
+        BG_HIP(hipStreamSynchronize(st));
+    }
+    if (int rc = bg_fastq_demux_split_dev(ctx, n, n_bins, (const uint32_t*)d_bin.p, hit ? (const bg_alignment_t*)d_hit.p : nullptr,
+                                          (const bg_fastq_record_t*)d_recs.p, (const uint8_t*)d_seq.p, (const uint64_t*)d_so.p,
+                                          (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p, (bg_fastq_record_t*)o_recs.p, (uint8_t*)o_seq.p,
+                                          (uint64_t*)o_so.p, (uint8_t*)o_qual.p, (uint64_t*)o_qo.p, hit_out ? (bg_alignment_t*)o_hit.p : nullptr,
+                                          (uint64_t*)o_perm.p, (uint64_t*)o_boff.p, bin_off, st))
+        return rc;
+    if (n) {
+        BG_HIP(hipMemcpyAsync(recs_out, o_recs.p, rb, hipMemcpyDeviceToHost, st));
+        if (sb) BG_HIP(hipMemcpyAsync(seq_out, o_seq.p, sb, hipMemcpyDeviceToHost, st));
+        if (qb) BG_HIP(hipMemcpyAsync(qual_out, o_qual.p, qb, hipMemcpyDeviceToHost, st));
+        if (hit_out) BG_HIP(hipMemcpyAsync(hit_out, o_hit.p, hb, hipMemcpyDeviceToHost, st));
+        if (perm) BG_HIP(hipMemcpyAsync(perm, o_perm.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    }
+    BG_HIP(hipMemcpyAsync(seq_off_out, o_so.p, ob, hipMemcpyDeviceToHost, st));
+    BG_HIP(hipMemcpyAsync(qual_off_out, o_qo.p, ob, hipMemcpyDeviceToHost, st));
+    BG_HIP(hipStreamSynchronize(st));
+    return BG_OK;
+}

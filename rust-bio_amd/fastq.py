@@ -2,7 +2,9 @@
 (csrc/fastq_ingest.hip) — line index, four-line hypothesis, sequential walk only where it fails — and the sequences land
 concatenated with offsets, i.e. in the layout the aligner's batch calls take.  Writing (csrc/fastq_emit.hip): `Writer`,
 `emit_arrays` / `emit_dev` write the text of parsed, trimmed or filtered records on the device, `filter_arrays` /
-`filter_dev` select records by length, 'N' count, `check`, trim state and pair (the rule is defined in include/biogpu.h)."""
+`filter_dev` select records by length, 'N' count, `check`, trim state and pair (the rule is defined in include/biogpu.h).
+Demultiplexing (csrc/fastq_demux.hip): `demux_assign_*` turn the records of a Myers best call into a sample per read,
+`demux_split_*` group the records by sample, `demux_texts` slices one emitted buffer into per-sample texts."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +12,7 @@ import numpy as np
 from . import _lib
 
 from ._lib import FQF_CHECK_OK, FQF_DISCARD_TRIMMED, FQF_DISCARD_UNTRIMMED, FQF_PAIR_BOTH, FQF_PAIRED  # noqa: F401
+from ._lib import DMX_ANCHOR_3P, DMX_ANCHOR_5P, DMX_IGNORE, DMX_MATE1, DMX_MATE2, DMX_MAX_BINS, DMX_PAIRED  # noqa: F401
 
 STATUS = ["ok", "MissingAt", "IncompleteRecord", "Io"]
 CHECK = ["ok", "EmptyId", "NonAsciiSequence", "InvalidSequence", "NonAsciiQualities", "UnequalLength"]
@@ -204,6 +207,125 @@ def filter_dev(n, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, flags=0, min_len
         return o_recs, o_seq, o_so, o_qual, o_qo, d_keep, None
     k = int(tot[0])
     return o_recs[:k * 56], o_seq, o_so[:k + 1], o_qual, o_qo[:k + 1], d_keep, (k, int(tot[1]), int(tot[2]))
+
+
+# ---- demultiplexing --------------------------------------------------------------------------------------------------
+def demux_params(n_bins, flags=0, min_margin=0, max_offset=0):
+    """bg_demux_params_t as a one-element array"""
+    p = np.zeros(1, dtype=_lib.DEMUX_PARAMS_DTYPE)
+    p["flags"], p["n_bins"], p["min_margin"], p["max_offset"] = flags, n_bins, min_margin, max_offset
+    return p
+
+
+def demux_assign_arrays(hits, n_pat, pat_bin, n_bins, flags=0, min_margin=0, max_offset=0, want_pat=True, ctx=None):
+    """bg_fastq_demux_assign over host arrays: hits are the n * n_pat records of myers.best_batch / long_best_batch, pat_bin
+    the sample of every pattern (DMX_IGNORE: none).  Returns (bin uint32[n], hit_out records[n], pat_out uint32[n] or None):
+    bin n_bins is unassigned, n_bins + 1 ambiguous; hit_out is what myers.trim takes with n_pat = 1."""
+    ctx = ctx or _lib.default_context()
+    hits = np.ascontiguousarray(hits, dtype=_lib.ALN_DTYPE)
+    pat_bin = np.ascontiguousarray(pat_bin, dtype=np.uint32)
+    n = len(hits) // max(1, int(n_pat))
+    prm = demux_params(n_bins, flags, min_margin, max_offset)
+    o_bin, o_hit = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=_lib.ALN_DTYPE)
+    o_pat = np.zeros(max(1, n), dtype=np.uint32) if want_pat else None
+    _lib.check(_lib.lib().bg_fastq_demux_assign(ctx.h, n, prm.ctypes.data, hits.ctypes.data, int(n_pat), pat_bin.ctypes.data,
+                                                o_bin.ctypes.data, o_hit.ctypes.data, o_pat.ctypes.data if want_pat else None),
+               "bg_fastq_demux_assign")
+    return o_bin[:n], o_hit[:n], o_pat[:n] if want_pat else None
+
+
+def demux_assign_dev(n, d_hits, n_pat, pat_bin, n_bins, flags=0, min_margin=0, max_offset=0, ctx=None, stream=0, want_pat=False, out=None):
+    """bg_fastq_demux_assign_dev on the device records of myers.best_batch_dev (pat_bin is a host array).  Returns (d_bin
+    int32[n], d_hit_out uint8[n * 64], d_pat int32[n] or None) in HBM without synchronising; the 32-bit columns hold
+    unsigned values.  `out`: the results of an earlier call of the same shape, to write into instead of allocating."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    pat_bin = np.ascontiguousarray(pat_bin, dtype=np.uint32)
+    prm = demux_params(n_bins, flags, min_margin, max_offset)
+    if out is not None:
+        d_bin, d_hit, d_pat = out[:3]
+    else:
+        dev = d_hits.device
+        d_bin = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+        d_hit = torch.empty(max(1, n) * 64, dtype=torch.uint8, device=dev)
+        d_pat = torch.empty(max(1, n), dtype=torch.int32, device=dev) if want_pat else None
+    _lib.check(_lib.lib().bg_fastq_demux_assign_dev(ctx.h, n, prm.ctypes.data, d_hits.data_ptr(), int(n_pat), pat_bin.ctypes.data,
+                                                    d_bin.data_ptr(), d_hit.data_ptr(), d_pat.data_ptr() if d_pat is not None else None,
+                                                    stream), "bg_fastq_demux_assign_dev")
+    return d_bin[:n], d_hit[:n * 64], d_pat[:n] if d_pat is not None else None
+
+
+def demux_split_arrays(bins, n_bins, recs, seq, seq_off, qual, qual_off, hit=None, ctx=None):
+    """bg_fastq_demux_split over host arrays: the columns of parse_arrays, myers.trim or filter_arrays grouped by `bins` (the
+    first result of demux_assign_arrays), stably.  Returns (recs, seq, seq_off, qual, qual_off, hit_out or None, perm
+    uint64[n], bin_off uint64[n_bins + 3]): group g's records are bin_off[g] .. bin_off[g + 1]."""
+    ctx = ctx or _lib.default_context()
+    n = len(recs)
+    bins = np.ascontiguousarray(bins, dtype=np.uint32)
+    hit = np.ascontiguousarray(hit, dtype=_lib.ALN_DTYPE) if hit is not None else None
+    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
+    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
+    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    o_recs = np.zeros(max(1, n), dtype=_lib.FQREC_DTYPE)
+    o_seq, o_qual = np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(max(1, len(qual)), dtype=np.uint8)
+    o_so, o_qo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    o_hit = np.zeros(max(1, n), dtype=_lib.ALN_DTYPE) if hit is not None else None
+    perm, bin_off = np.zeros(max(1, n), dtype=np.uint64), np.zeros(int(n_bins) + 3, dtype=np.uint64)
+    pad = np.zeros(1, dtype=np.uint8)  # no empty buffers: the call refuses null pointers
+    _lib.check(_lib.lib().bg_fastq_demux_split(ctx.h, n, int(n_bins), bins.ctypes.data if n else pad.ctypes.data,
+                                               hit.ctypes.data if hit is not None else None, recs.ctypes.data, seq.ctypes.data,
+                                               seq_off.ctypes.data, qual.ctypes.data, qual_off.ctypes.data, o_recs.ctypes.data,
+                                               o_seq.ctypes.data, o_so.ctypes.data, o_qual.ctypes.data, o_qo.ctypes.data,
+                                               o_hit.ctypes.data if o_hit is not None else None, perm.ctypes.data, bin_off.ctypes.data),
+               "bg_fastq_demux_split")
+    return (o_recs[:n], o_seq[:int(o_so[n])], o_so, o_qual[:int(o_qo[n])], o_qo, o_hit[:n] if o_hit is not None else None, perm[:n],
+            bin_off)
+
+
+def demux_split_dev(n, d_bin, n_bins, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_hit=None, ctx=None, stream=0, want_bin_off=True,
+                    want_perm=False, out=None):
+    """bg_fastq_demux_split_dev on torch device tensors (d_bin: demux_assign_dev's; the columns of parse_dev, myers.trim_dev or
+    filter_dev; d_hit: n records, e.g. demux_assign_dev's second result).  Returns (d_recs, d_seq, d_seq_off, d_qual,
+    d_qual_off, d_hit_out or None, d_perm or None, d_bin_off int64[n_bins + 3], bin_off) — new tensors in HBM, never the
+    inputs; bin_off is the host copy of d_bin_off (a uint64 array), or None without want_bin_off, and then the call does not
+    synchronise.  `out`: the first eight results of an earlier call of the same shape, to write into instead of allocating."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    dev = d_seq.device
+    if out is not None:
+        o_recs, o_seq, o_so, o_qual, o_qo, o_hit, d_perm, d_boff = out[:8]
+    else:
+        o_recs = torch.empty(max(1, n) * 56, dtype=torch.uint8, device=dev)
+        o_seq = torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev)
+        o_qual = torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev)
+        o_so = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        o_qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        o_hit = torch.empty(max(1, n) * 64, dtype=torch.uint8, device=dev) if d_hit is not None else None
+        d_perm = torch.empty(max(1, n), dtype=torch.int64, device=dev) if want_perm else None
+        d_boff = torch.empty(int(n_bins) + 3, dtype=torch.int64, device=dev)
+    bin_off = np.zeros(int(n_bins) + 3, dtype=np.uint64) if want_bin_off else None
+    _lib.check(_lib.lib().bg_fastq_demux_split_dev(ctx.h, n, int(n_bins), d_bin.data_ptr(), d_hit.data_ptr() if d_hit is not None else None,
+                                                   d_recs.data_ptr(), d_seq.data_ptr(), d_seq_off.data_ptr(), d_qual.data_ptr(),
+                                                   d_qual_off.data_ptr(), o_recs.data_ptr(), o_seq.data_ptr(), o_so.data_ptr(),
+                                                   o_qual.data_ptr(), o_qo.data_ptr(), o_hit.data_ptr() if o_hit is not None else None,
+                                                   d_perm.data_ptr() if d_perm is not None else None, d_boff.data_ptr(),
+                                                   bin_off.ctypes.data if want_bin_off else None, stream), "bg_fastq_demux_split_dev")
+    return (o_recs[:n * 56], o_seq, o_so, o_qual, o_qo, o_hit[:n * 64] if o_hit is not None else None,
+            d_perm[:n] if d_perm is not None else None, d_boff, bin_off)
+
+
+def demux_texts(out, out_off, bin_off, n_bins, first=0, step=1):
+    """The per-sample texts inside ONE emit over split columns: `out`, `out_off` as emit_dev / emit_arrays return them for
+    (first, step), bin_off the host offsets of the split.  Returns n_bins + 2 slices of `out` (views, nothing is copied):
+    the samples, then unassigned, then ambiguous.  With (0, 2) and (1, 2) on interleaved mates: the R1 and the R2 texts."""
+    lines = [n_lines(int(b), first, step) for b in bin_off[:int(n_bins) + 3]]
+    idx = np.asarray(lines, dtype=np.int64)
+    if isinstance(out_off, np.ndarray):
+        cuts = out_off[idx]
+    else:  # a device tensor: n_bins + 3 offsets cross, not the column
+        import torch
+        cuts = out_off[torch.from_numpy(idx).to(out_off.device)].cpu().numpy()
+    return [out[int(cuts[g]):int(cuts[g + 1])] for g in range(int(n_bins) + 2)]
 
 
 # ---- writing ---------------------------------------------------------------------------------------------------------
