@@ -1312,6 +1312,116 @@ int bg_fastq_demux_split(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_
                          uint64_t* qual_off_out, bg_alignment_t* hit_out /* optional */, uint64_t* perm /* optional, n */,
                          uint64_t* bin_off /* n_bins + 3 */);
 
+/* ---- qualities (fastq_qual.hip): cut points, a pass / fail bin and per-cycle tables from the quality column ----------
+ * rust-bio has none of this, as it has no trimmer, filter or demultiplexer: the three rules are defined here.  All
+ * arithmetic is integer, so every result is bit-exact and the same on every run.
+ *
+ * Common.  The quality of byte c is q = max(0, c - phred_offset), phred_offset 0 .. 255.  Read r's qualities are
+ * qual[qual_off[r] .. qual_off[r + 1]), L of them.  The calls take the columns a parse, a trim, a filter or a split leaves
+ * and change none of them; each has a device flavour (device pointers, asynchronous on `stream` unless a host total is
+ * asked for) and a host-buffer flavour that stages through it.  Every refusal comes before any device call and says why
+ * (bg_last_error).
+ *
+ * bg_fastq_qual_cut[_dev]: where to cut each read.  Both ends are computed on the whole read, independently.
+ *   BG_QCUT_RUNSUM at the 3' end (the BWA / cutadapt rule): s = 0, best = 0, e = L; for i = L - 1 down to 0:
+ *     s += cutoff_3p - q[i]; stop if s < 0; if s > best: best = s, e = i.
+ *   BG_QCUT_RUNSUM at the 5' end: s = 0, best = 0, b = 0; for i = 0 to L - 1:
+ *     s += cutoff_5p - q[i]; stop if s < 0; if s > best: best = s, b = i + 1.
+ *     (s is a signed 64-bit number.)
+ *   BG_QCUT_WINDOW at the 3' end (Trimmomatic's SLIDINGWINDOW): W = min(window, L); the smallest i in 0 .. L - W with
+ *     q[i] + ... + q[i + W - 1] < cutoff_3p * W; if there is none e = L; otherwise e = i, then while e > 0 and
+ *     q[e - 1] < cutoff_3p: e -= 1.  (A low last symbol inside a passing window stays.)
+ *   BG_QCUT_NONE: b = 0, e = L.
+ *   If e < b then e = b.
+ *   cut_out[r], one bg_alignment_t per read: where L == 0 or nothing is cut (b == 0 and e == L) a no-hit record —
+ *     score = BG_MIN_SCORE, ylen = L, every other byte 0; otherwise score = L - (e - b), the symbols removed, ystart = e,
+ *     yend = b, ylen = L, every other byte 0.  NOTE ystart >= yend here, unlike a Myers hit: the record is made for the trim.
+ *   Composition: bg_fastq_trim[_dev](BG_TRIM_3P, cut_out, n_pat = 1) keeps [0, e); bg_fastq_trim[_dev](BG_TRIM_5P, ...) of its
+ *     output with the same records (gathered again if a filter or a split came in between) then keeps [b, e).  The trim's
+ *     own clamping handles records whose sequence and quality lengths differ.  BG_FQF_DISCARD_TRIMMED / _UNTRIMMED of the
+ *     filter read the same records.
+ *   totals (optional, host, 2 entries: reads cut, quality symbols removed) costs the device flavour its only
+ *     synchronisation of `stream`.
+ *   BG_ERR_INVALID_ARG: null params, an unknown method, BG_QCUT_WINDOW as method_5p, window == 0 with BG_QCUT_WINDOW,
+ *     phred_offset > 255, a null qual_off, (n > 0) a null qual or cut_out.  Both methods BG_QCUT_NONE is legal and writes
+ *     no-hit records.
+ *
+ * bg_fastq_qual_select[_dev]: statistics of each read and a pass / fail bin.
+ *   stats_out[r] (optional): sum_q = the sum of q; len = L; n_low = symbols with q < low_q; min_q = the smallest q, 0 for
+ *     L == 0; weight_sum = the sum of weight[c] over the read's RAW bytes c, 0 without a table.  weight (optional, host,
+ *     256 entries) is consumed before the call returns.
+ *   A read PASSES if every criterion holds:
+ *     sum_q >= (uint64) min_mean_q * L;
+ *     (uint64) n_low * 100 <= (uint64) max_low_pct * L — a max_low_pct of 100 or more always holds;
+ *     with a table, weight_sum <= max_weight.
+ *     An empty read passes all three: length is the filter's business.
+ *   bin_out[r] (optional) is 0 for pass and 1 for fail: bg_fastq_demux_split[_dev] with n_bins = 1 puts the passed records
+ *     in group 0 and the failed ones in the "unassigned" group, and one bg_fastq_emit_dev writes both texts.
+ *   BG_QSEL_PAIRED / BG_QSEL_PAIR_BOTH have the filter's meaning: records 2p and 2p + 1 are mates and get one verdict — pass
+ *     if both pass, with BG_QSEL_PAIR_BOTH unless both fail — so mates stay adjacent through the split.  stats_out is each
+ *     mate's own.
+ *   Expected errors: a table weight[c] = round(10^(-q(c) / 10) * 2^20) and max_weight = max_ee * 2^20 make the third
+ *     criterion "at most max_ee expected errors"; floating point stays outside this interface.
+ *   totals (optional, host, 1 entry: records whose bin is 0) costs the device flavour its only synchronisation.
+ *   BG_ERR_INVALID_ARG: null params, unknown flag bits, BG_QSEL_PAIR_BOTH without BG_QSEL_PAIRED, BG_QSEL_PAIRED with odd
+ *     n, phred_offset > 255, a non-zero _reserved, a null qual_off, (n > 0) a null qual or both outputs null.
+ *
+ * bg_fastq_qc_tables[_dev]: per-cycle tables of records first, first + step, ... below n (as bg_fastq_emit selects them:
+ *   (0, 2) and (1, 2) give the R1 and the R2 tables of interleaved mates).  max_cycles is 1 .. BG_QC_MAX_CYCLES;
+ *   R = max_cycles + 1 rows, row max_cycles collects every position at or beyond max_cycles.  `tables` is ONE buffer of
+ *   bg_qc_tables_words(max_cycles) 64-bit words, zeroed by the call, holding in this order
+ *     base[R][5]        counts of A/a, C/c, G/g, T/t and anything else, by position in the SEQUENCE;
+ *     qhist[R][64]      counts of min(q, 63), by position in the QUALITY string;
+ *     len_hist[R + 1]   sequence lengths 0 .. max_cycles, longer ones in the last entry;
+ *     meanq_hist[64]    min(63, sum_q / L) (integer division) of the reads with L > 0;
+ *     n_reads[1].
+ *   so bg_qc_tables_words = 5 R + 64 R + (R + 1) + 64 + 1.  Sums of integers commute: the tables are the same on every run.
+ *   BG_ERR_INVALID_ARG: step == 0, max_cycles outside its range, phred_offset > 255, a null tables or offsets, with
+ *     records selected a null seq or qual.
+ *
+ * Out of scope: poly-G / poly-X tail trimming, trimming ends by 'N', window cutting from the 5' end, per-tile or
+ * per-sample tables in one call (call it once per group of a split), floating-point error probabilities in this interface. */
+enum { BG_QCUT_NONE = 0, BG_QCUT_RUNSUM = 1, BG_QCUT_WINDOW = 2 };
+enum { BG_QSEL_PAIRED = 1, BG_QSEL_PAIR_BOTH = 2 };
+enum { BG_QC_MAX_CYCLES = 1024 };
+typedef struct {
+    uint32_t phred_offset;  /* 0 .. 255 */
+    uint32_t method_5p;     /* BG_QCUT_NONE or BG_QCUT_RUNSUM */
+    uint32_t method_3p;     /* BG_QCUT_NONE, BG_QCUT_RUNSUM or BG_QCUT_WINDOW */
+    uint32_t cutoff_5p;
+    uint32_t cutoff_3p;
+    uint32_t window;        /* BG_QCUT_WINDOW: symbols per window, at least 1 */
+} bg_qual_cut_t;
+typedef struct {
+    uint64_t sum_q, weight_sum;
+    uint32_t len, n_low, min_q, _reserved;
+} bg_qual_stats_t;
+typedef struct {
+    uint32_t flags;         /* BG_QSEL_* */
+    uint32_t phred_offset;  /* 0 .. 255 */
+    uint32_t min_mean_q;    /* pass: sum_q >= min_mean_q * L */
+    uint32_t low_q;         /* a symbol is low if q < low_q */
+    uint32_t max_low_pct;   /* pass: n_low * 100 <= max_low_pct * L; 100 or more: always */
+    uint32_t _reserved;     /* 0 */
+    uint64_t max_weight;    /* with a table: pass: weight_sum <= max_weight */
+} bg_qual_select_t;
+uint64_t bg_qc_tables_words(uint32_t max_cycles);
+int bg_fastq_qual_cut_dev(bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* params, const uint8_t* d_qual, const uint64_t* d_qual_off,
+                          bg_alignment_t* d_cut_out, uint64_t* totals /* optional, host, 2 */, void* stream);
+int bg_fastq_qual_cut(bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* params, const uint8_t* qual, const uint64_t* qual_off,
+                      bg_alignment_t* cut_out, uint64_t* totals /* optional, 2 */);
+int bg_fastq_qual_select_dev(bg_ctx* ctx, uint64_t n, const bg_qual_select_t* params, const uint32_t* weight /* optional, host, 256 */,
+                             const uint8_t* d_qual, const uint64_t* d_qual_off, bg_qual_stats_t* d_stats_out /* optional */,
+                             uint32_t* d_bin_out /* optional */, uint64_t* totals /* optional, host, 1 */, void* stream);
+int bg_fastq_qual_select(bg_ctx* ctx, uint64_t n, const bg_qual_select_t* params, const uint32_t* weight /* optional, 256 */,
+                         const uint8_t* qual, const uint64_t* qual_off, bg_qual_stats_t* stats_out /* optional */,
+                         uint32_t* bin_out /* optional */, uint64_t* totals /* optional, 1 */);
+int bg_fastq_qc_tables_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, uint32_t phred_offset, uint32_t max_cycles,
+                           const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual, const uint64_t* d_qual_off,
+                           uint64_t* d_tables, void* stream);
+int bg_fastq_qc_tables(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, uint32_t phred_offset, uint32_t max_cycles,
+                       const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual, const uint64_t* qual_off, uint64_t* tables);
+
 /* ------------------------------------------------------------------ several GPUs (comm.hip)
  * north_star: "query batches shard embarrassingly across the 8 GPUs of one node with a single RCCL all-gather over xGMI
  * only to collect per-query scores/intervals".  One process and one bg_ctx per GPU.  rust-bio has no counterpart (a

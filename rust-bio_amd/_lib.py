@@ -181,6 +181,19 @@ DEMUX_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("n_bins", "<u4"), ("min_margin
 assert DEMUX_PARAMS_DTYPE.itemsize == 16, DEMUX_PARAMS_DTYPE.itemsize
 DMX_ANCHOR_5P, DMX_ANCHOR_3P, DMX_PAIRED, DMX_MATE1, DMX_MATE2 = 1, 2, 4, 8, 16
 DMX_IGNORE, DMX_MAX_BINS = 0xFFFFFFFF, 1024
+# bg_qual_cut_t, bg_qual_select_t, bg_qual_stats_t, BG_QCUT_*, BG_QSEL_* and BG_QC_MAX_CYCLES (bg_fastq_qual_cut[_dev],
+# bg_fastq_qual_select[_dev], bg_fastq_qc_tables[_dev])
+QUAL_CUT_DTYPE = np.dtype([("phred_offset", "<u4"), ("method_5p", "<u4"), ("method_3p", "<u4"), ("cutoff_5p", "<u4"), ("cutoff_3p", "<u4"),
+                           ("window", "<u4")])
+assert QUAL_CUT_DTYPE.itemsize == 24, QUAL_CUT_DTYPE.itemsize
+QUAL_SELECT_DTYPE = np.dtype([("flags", "<u4"), ("phred_offset", "<u4"), ("min_mean_q", "<u4"), ("low_q", "<u4"), ("max_low_pct", "<u4"),
+                              ("_reserved", "<u4"), ("max_weight", "<u8")])
+assert QUAL_SELECT_DTYPE.itemsize == 32, QUAL_SELECT_DTYPE.itemsize
+QUAL_STATS_DTYPE = np.dtype([("sum_q", "<u8"), ("weight_sum", "<u8"), ("len", "<u4"), ("n_low", "<u4"), ("min_q", "<u4"), ("_reserved", "<u4")])
+assert QUAL_STATS_DTYPE.itemsize == 32, QUAL_STATS_DTYPE.itemsize
+QCUT_NONE, QCUT_RUNSUM, QCUT_WINDOW = 0, 1, 2
+QSEL_PAIRED, QSEL_PAIR_BOTH = 1, 2
+QC_MAX_CYCLES = 1024
 
 SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_error",
            "bg_set_option", "bg_suffix_array", "bg_bwt", "bg_less", "bg_fm_build", "bg_fm_free",
@@ -211,7 +224,9 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_myers_best_batch", "bg_myers_best_batch_dev", "bg_myers_find_all_batch", "bg_myers_find_all_batch_dev",
            "bg_myers_long_best_batch", "bg_myers_long_best_batch_dev", "bg_myers_long_find_all_batch", "bg_myers_long_find_all_batch_dev",
            "bg_fastq_trim", "bg_fastq_trim_dev", "bg_fastq_filter", "bg_fastq_filter_dev", "bg_fastq_emit", "bg_fastq_emit_dev",
-           "bg_fastq_demux_assign", "bg_fastq_demux_assign_dev", "bg_fastq_demux_split", "bg_fastq_demux_split_dev"]
+           "bg_fastq_demux_assign", "bg_fastq_demux_assign_dev", "bg_fastq_demux_split", "bg_fastq_demux_split_dev",
+           "bg_qc_tables_words", "bg_fastq_qual_cut", "bg_fastq_qual_cut_dev", "bg_fastq_qual_select", "bg_fastq_qual_select_dev",
+           "bg_fastq_qc_tables", "bg_fastq_qc_tables_dev"]
 
 
 def build(force=False):
@@ -390,6 +405,14 @@ def lib():
         L.bg_fastq_demux_assign_dev.argtypes = [vp, u64, vp, vp, u32, vp, vp, vp, vp, vp]
         L.bg_fastq_demux_split.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bg_fastq_demux_split_dev.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_qc_tables_words.restype = u64
+        L.bg_qc_tables_words.argtypes = [u32]
+        L.bg_fastq_qual_cut.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        L.bg_fastq_qual_cut_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_qual_select.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_qual_select_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_fastq_qc_tables.argtypes = [vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, vp]
+        L.bg_fastq_qc_tables_dev.argtypes = [vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, vp, vp]
         for s in SYMBOLS:
             if getattr(L, s).restype is C.c_int or s.startswith("bg_") and getattr(L, s).restype is None:
                 pass

@@ -4,7 +4,10 @@ concatenated with offsets, i.e. in the layout the aligner's batch calls take.  W
 `emit_arrays` / `emit_dev` write the text of parsed, trimmed or filtered records on the device, `filter_arrays` /
 `filter_dev` select records by length, 'N' count, `check`, trim state and pair (the rule is defined in include/biogpu.h).
 Demultiplexing (csrc/fastq_demux.hip): `demux_assign_*` turn the records of a Myers best call into a sample per read,
-`demux_split_*` group the records by sample, `demux_texts` slices one emitted buffer into per-sample texts."""
+`demux_split_*` group the records by sample, `demux_texts` slices one emitted buffer into per-sample texts.
+Qualities (csrc/fastq_qual.hip): `qual_cut_*` give a cut point per read by the running-sum or the sliding-window rule,
+`qual_select_*` per-read statistics and a pass / fail bin, `qc_tables_*` the per-cycle tables of a batch; `qual_trim_arrays`
+is cut, trim 3', trim 5' in one call and `ee_weights` the table that makes the selection an expected-error filter."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +16,7 @@ from . import _lib
 
 from ._lib import FQF_CHECK_OK, FQF_DISCARD_TRIMMED, FQF_DISCARD_UNTRIMMED, FQF_PAIR_BOTH, FQF_PAIRED  # noqa: F401
 from ._lib import DMX_ANCHOR_3P, DMX_ANCHOR_5P, DMX_IGNORE, DMX_MATE1, DMX_MATE2, DMX_MAX_BINS, DMX_PAIRED  # noqa: F401
+from ._lib import QC_MAX_CYCLES, QCUT_NONE, QCUT_RUNSUM, QCUT_WINDOW, QSEL_PAIR_BOTH, QSEL_PAIRED  # noqa: F401
 
 STATUS = ["ok", "MissingAt", "IncompleteRecord", "Io"]
 CHECK = ["ok", "EmptyId", "NonAsciiSequence", "InvalidSequence", "NonAsciiQualities", "UnequalLength"]
@@ -326,6 +330,160 @@ def demux_texts(out, out_off, bin_off, n_bins, first=0, step=1):
         import torch
         cuts = out_off[torch.from_numpy(idx).to(out_off.device)].cpu().numpy()
     return [out[int(cuts[g]):int(cuts[g + 1])] for g in range(int(n_bins) + 2)]
+
+
+# ---- qualities -------------------------------------------------------------------------------------------------------
+def qual_cut_params(method_5p=QCUT_NONE, method_3p=QCUT_RUNSUM, cutoff_5p=0, cutoff_3p=0, window=0, phred_offset=33):
+    """bg_qual_cut_t as a one-element array"""
+    p = np.zeros(1, dtype=_lib.QUAL_CUT_DTYPE)
+    p["phred_offset"], p["method_5p"], p["method_3p"] = phred_offset, method_5p, method_3p
+    p["cutoff_5p"], p["cutoff_3p"], p["window"] = cutoff_5p, cutoff_3p, window
+    return p
+
+
+def qual_cut_arrays(qual, qual_off, want_totals=False, ctx=None, **params):
+    """bg_fastq_qual_cut over host arrays (the quality column of parse_arrays, myers.trim, filter_arrays or a split; params:
+    those of qual_cut_params).  Returns the cut records[n] — what myers.trim takes with n_pat = 1: TRIM_3P keeps [0, e),
+    TRIM_5P of its output then [b, e) — or (records, (reads cut, symbols removed)) with want_totals."""
+    ctx = ctx or _lib.default_context()
+    qual, qual_off = _lib.as_u8(qual), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    n = len(qual_off) - 1
+    prm = qual_cut_params(**params)
+    pad = np.zeros(1, dtype=np.uint8)  # no empty buffers: the call refuses null pointers
+    cut = np.zeros(max(1, n), dtype=_lib.ALN_DTYPE)
+    tot = (C.c_uint64 * 2)()
+    _lib.check(_lib.lib().bg_fastq_qual_cut(ctx.h, n, prm.ctypes.data, qual.ctypes.data if len(qual) else pad.ctypes.data, qual_off.ctypes.data,
+                                            cut.ctypes.data, tot if want_totals else None), "bg_fastq_qual_cut")
+    return (cut[:n], (int(tot[0]), int(tot[1]))) if want_totals else cut[:n]
+
+
+def qual_cut_dev(n, d_qual, d_qual_off, ctx=None, stream=0, want_totals=False, out=None, **params):
+    """bg_fastq_qual_cut_dev on torch device tensors.  Returns (d_cut uint8[n * 64], totals): the records in HBM — what
+    myers.trim_dev takes as d_hits with n_pat = 1 — and (reads cut, symbols removed), or None without want_totals, and then
+    the call does not synchronise.  `out`: d_cut of an earlier call of the same shape, to write into instead of allocating."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    prm = qual_cut_params(**params)
+    d_cut = out if out is not None else torch.empty(max(1, n) * 64, dtype=torch.uint8, device=d_qual.device)
+    tot = (C.c_uint64 * 2)()
+    _lib.check(_lib.lib().bg_fastq_qual_cut_dev(ctx.h, n, prm.ctypes.data, d_qual.data_ptr(), d_qual_off.data_ptr(), d_cut.data_ptr(),
+                                                tot if want_totals else None, stream), "bg_fastq_qual_cut_dev")
+    return d_cut[:n * 64], ((int(tot[0]), int(tot[1])) if want_totals else None)
+
+
+def ee_weights(phred_offset=33, scale_bits=20):
+    """The weight table of an expected-error filter: round(10^(-q / 10) * 2^scale_bits) per raw byte, q = max(0, c - phred_offset)"""
+    q = np.maximum(np.arange(256, dtype=np.int64) - int(phred_offset), 0)
+    return np.round(10.0 ** (-q / 10.0) * float(1 << scale_bits)).astype(np.uint32)
+
+
+def qual_select_params(flags=0, min_mean_q=0, low_q=0, max_low_pct=100, max_weight=0, phred_offset=33):
+    """bg_qual_select_t as a one-element array"""
+    p = np.zeros(1, dtype=_lib.QUAL_SELECT_DTYPE)
+    p["flags"], p["phred_offset"], p["min_mean_q"], p["low_q"] = flags, phred_offset, min_mean_q, low_q
+    p["max_low_pct"], p["max_weight"] = max_low_pct, max_weight
+    return p
+
+
+def _select_table(params, weight, max_ee, scale_bits):
+    """max_ee (a float) is ee_weights with max_weight scaled the same way"""
+    if max_ee is not None:
+        weight = ee_weights(params.get("phred_offset", 33), scale_bits)
+        params["max_weight"] = int(round(float(max_ee) * float(1 << scale_bits)))
+    return qual_select_params(**params), (np.ascontiguousarray(weight, dtype=np.uint32) if weight is not None else None)
+
+
+def qual_select_arrays(qual, qual_off, weight=None, max_ee=None, scale_bits=20, want_totals=False, ctx=None, **params):
+    """bg_fastq_qual_select over host arrays (params: those of qual_select_params; weight: uint32[256] by raw byte, or max_ee:
+    the largest expected number of errors).  Returns (stats QUAL_STATS_DTYPE[n], bin uint32[n]) — bin 0 passed, 1 failed: what
+    demux_split_arrays takes with n_bins = 1 — and the number of records passed as a third with want_totals."""
+    ctx = ctx or _lib.default_context()
+    qual, qual_off = _lib.as_u8(qual), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    n = len(qual_off) - 1
+    prm, weight = _select_table(dict(params), weight, max_ee, scale_bits)
+    pad = np.zeros(1, dtype=np.uint8)
+    stats, bins = np.zeros(max(1, n), dtype=_lib.QUAL_STATS_DTYPE), np.zeros(max(1, n), dtype=np.uint32)
+    tot = (C.c_uint64 * 1)()
+    _lib.check(_lib.lib().bg_fastq_qual_select(ctx.h, n, prm.ctypes.data, weight.ctypes.data if weight is not None else None,
+                                               qual.ctypes.data if len(qual) else pad.ctypes.data, qual_off.ctypes.data, stats.ctypes.data,
+                                               bins.ctypes.data, tot if want_totals else None), "bg_fastq_qual_select")
+    return (stats[:n], bins[:n], int(tot[0])) if want_totals else (stats[:n], bins[:n])
+
+
+def qual_select_dev(n, d_qual, d_qual_off, weight=None, max_ee=None, scale_bits=20, ctx=None, stream=0, want_stats=True, want_bin=True,
+                    want_totals=False, out=None, **params):
+    """bg_fastq_qual_select_dev on torch device tensors (weight is a host array).  Returns (d_stats uint8[n * 32] or None, d_bin
+    int32[n] or None, passed): in HBM; `passed` is the number of records passed, or None without want_totals, and then the call
+    does not synchronise.  `out`: the first two results of an earlier call of the same shape, to write into."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    prm, weight = _select_table(dict(params), weight, max_ee, scale_bits)
+    if out is not None:
+        d_stats, d_bin = out[:2]
+    else:
+        d_stats = torch.empty(max(1, n) * 32, dtype=torch.uint8, device=d_qual.device) if want_stats else None
+        d_bin = torch.empty(max(1, n), dtype=torch.int32, device=d_qual.device) if want_bin else None
+    tot = (C.c_uint64 * 1)()
+    _lib.check(_lib.lib().bg_fastq_qual_select_dev(ctx.h, n, prm.ctypes.data, weight.ctypes.data if weight is not None else None,
+                                                   d_qual.data_ptr(), d_qual_off.data_ptr(), d_stats.data_ptr() if d_stats is not None else None,
+                                                   d_bin.data_ptr() if d_bin is not None else None, tot if want_totals else None, stream),
+               "bg_fastq_qual_select_dev")
+    return (d_stats[:n * 32] if d_stats is not None else None, d_bin[:n] if d_bin is not None else None,
+            int(tot[0]) if want_totals else None)
+
+
+def qc_tables_words(max_cycles):
+    """bg_qc_tables_words: 64-bit words of the tables' buffer"""
+    return int(_lib.lib().bg_qc_tables_words(int(max_cycles)))
+
+
+class QcTables:
+    """views into the one buffer of bg_fastq_qc_tables (a uint64 array, or an int64 device tensor): base[R, 5], qhist[R, 64],
+    len_hist[R + 1], meanq_hist[64], n_reads[1], R = max_cycles + 1"""
+
+    def __init__(self, buf, max_cycles):
+        R = int(max_cycles) + 1
+        self.buf, self.max_cycles = buf, int(max_cycles)
+        self.base = buf[:R * 5].reshape(R, 5)
+        self.qhist = buf[R * 5:R * 69].reshape(R, 64)
+        self.len_hist = buf[R * 69:R * 70 + 1]
+        self.meanq_hist = buf[R * 70 + 1:R * 70 + 65]
+        self.n_reads = buf[R * 70 + 65:R * 70 + 66]
+
+
+def qc_tables_arrays(seq, seq_off, qual, qual_off, max_cycles, first=0, step=1, phred_offset=33, ctx=None):
+    """bg_fastq_qc_tables over host arrays: the tables of records first, first + step, ... as a QcTables of uint64 arrays"""
+    ctx = ctx or _lib.default_context()
+    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
+    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    pad = np.zeros(1, dtype=np.uint8)
+    buf = np.zeros(qc_tables_words(max_cycles), dtype=np.uint64)
+    _lib.check(_lib.lib().bg_fastq_qc_tables(ctx.h, len(seq_off) - 1, int(first), int(step), int(phred_offset), int(max_cycles),
+                                             seq.ctypes.data if len(seq) else pad.ctypes.data, seq_off.ctypes.data,
+                                             qual.ctypes.data if len(qual) else pad.ctypes.data, qual_off.ctypes.data, buf.ctypes.data),
+               "bg_fastq_qc_tables")
+    return QcTables(buf, max_cycles)
+
+
+def qc_tables_dev(n, d_seq, d_seq_off, d_qual, d_qual_off, max_cycles, first=0, step=1, phred_offset=33, ctx=None, stream=0, out=None):
+    """bg_fastq_qc_tables_dev on torch device tensors: a QcTables of views into one int64 tensor in HBM (the counts are
+    unsigned), without synchronising.  `out`: the `buf` of an earlier result for the same max_cycles, to write into."""
+    import torch
+    ctx = ctx or _lib.default_context()
+    buf = out if out is not None else torch.empty(qc_tables_words(max_cycles), dtype=torch.int64, device=d_seq.device)
+    _lib.check(_lib.lib().bg_fastq_qc_tables_dev(ctx.h, n, int(first), int(step), int(phred_offset), int(max_cycles), d_seq.data_ptr(),
+                                                 d_seq_off.data_ptr(), d_qual.data_ptr(), d_qual_off.data_ptr(), buf.data_ptr(), stream),
+               "bg_fastq_qc_tables_dev")
+    return QcTables(buf, max_cycles)
+
+
+def qual_trim_arrays(recs, seq, seq_off, qual, qual_off, ctx=None, **params):
+    """Quality trimming of host columns in one call: qual_cut_arrays, then myers.trim at the 3' end, then at the 5' end with
+    the same records.  Returns (recs, seq, seq_off, qual, qual_off, cut records)."""
+    from . import myers
+    cut = qual_cut_arrays(qual, qual_off, ctx=ctx, **params)
+    cols = myers.trim(_lib.TRIM_3P, cut, 1, recs, seq, seq_off, qual, qual_off, ctx=ctx)
+    return (*myers.trim(_lib.TRIM_5P, cut, 1, *cols, ctx=ctx), cut)
 
 
 # ---- writing ---------------------------------------------------------------------------------------------------------
