@@ -1016,7 +1016,8 @@ int bg_fasta_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t len, bg_fast
  * bg_sam_header (host only, no GPU) writes "@HD\tVN:1.6\tSO:unsorted\n", one "@SQ\tSN:<name>\tLN:<len>\n" per contig and
  * "@PG\tID:biogpu\tPN:biogpu\n"; *out_bytes receives the length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if
  * out_cap is too small (nothing written).
- * Not covered: BAM / BGZF, sorting, supplementary (chimeric) records, read groups.  (Mate rescue happens before this call:
+ * Not covered: BAM / BGZF, supplementary (chimeric) records, read groups.  (Coordinate order and duplicate flags: the section
+ * below.)  (Mate rescue happens before this call:
  * bg_seed_extend_pairs_rescue_batch[_dev]; a rescued hit is written like any other.)  Known limit: the
  * seed-and-extend windows know nothing of contig boundaries, so a read whose best alignment crosses one is reported
  * unmapped here (not clipped to the contig) even where a slightly worse alignment inside one contig exists. */
@@ -1046,6 +1047,99 @@ int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, co
                       const uint8_t* seq, const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand,
                       const uint8_t* ops, const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap,
                       uint64_t* out_off, uint64_t* out_bytes);
+
+/* ---- coordinate-sorted SAM and duplicate marking (sam_sort.hip; the bodies in csrc/sam_rule.h) ------------------------
+ * What the next tool takes: records in coordinate order, PCR duplicates flagged 0x400.  The order of use is
+ *   bg_sam_markdup[_dev]         one duplicate byte per read, from the hits and the qualities
+ *   bg_sam_emit_dup_batch[_dev]  the writer above with `dup`: SAM text that carries the flags
+ *   bg_sam_sort_keys[_dev]       a 64-bit key per slot
+ *   bg_sam_sort[_dev]            the lines permuted into key order
+ *   bg_sam_header_so             a header that says SO:coordinate
+ * rust-bio has none of this; as with the pair and multi rules the definitions are this header's.  PLACED and "writes a line"
+ * are the writer's (one definition: csrc/sam_rule.h).
+ *
+ * bg_sam_markdup.  Only slot K r of read r takes part (K = max_hits); secondary slots never do.
+ *   score(r)   the sum of q - phred_offset over the quality bytes q of read r (qual[recs[r].qual_off .. + qual_len)) with
+ *              q >= phred_offset + min_qual; a 32-bit integer.
+ *   end(r)     exists only if slot K r is placed: the triple (contig, u5, rev) with rev = (strand == BG_HIT_REVERSE) and u5
+ *              the unclipped 5' coordinate in the index text: forward u5 = ref_start - aln.xstart, saturating at 0; reverse
+ *              u5 = ref_end - 1 + (aln.xlen - aln.xend).  (After the semiglobal extension the clip terms are 0; the rule
+ *              holds for any hit record.)  Coordinates are 64-bit throughout.
+ *   Without BG_SAM_PAIRED: reads with an end are grouped by end.  In each group the read with the highest score stays, on a
+ *              tie the smallest r; every other read of the group gets dup[r] = 1.
+ *   With BG_SAM_PAIRED (n_reads even, K = 1, reads 2p and 2p + 1 the mates of pair p):
+ *     both mates have an end: order the two ends by (contig, u5, rev, mate number) into lo and hi.  The pair's key is
+ *              (lo, hi, whether lo is mate 2), its score the sum of the mates' scores.  Pairs are grouped by key; the
+ *              highest score stays, then the smallest p; both mates of every other pair of the group get 1.
+ *     exactly one mate has an end (a fragment): if any both-ended pair, kept or not, has lo or hi equal to the fragment's
+ *              end, the placed mate gets 1.  Otherwise the fragments are grouped by end among themselves; the highest score
+ *              of the placed mate stays, then the smallest r; the placed mates of the rest get 1.  The mate without an end
+ *              gets 0.
+ *     neither mate has an end: both get 0.
+ *   counts (host, 4 entries, read back with one stream synchronisation like the other calls' totals): [0] reads with an
+ *              end, [1] reads flagged, [2] pairs flagged, [3] fragments flagged because of a pair's end.
+ *   The result does not depend on how a sort breaks ties: every tie of the rule is stated by index and is part of the order
+ *   that is sorted by.  BG_ERR_INVALID_ARG: unknown flag bits (anything but BG_SAM_PAIRED); max_hits 0 or above
+ *   BG_SEED_MAX_HITS; n_contigs 0; paired with an odd n_reads or max_hits != 1; a null ctx, mp or counts, or (n_reads > 0) a
+ *   null contigs, hits, strand, recs, qual or dup.  n_reads == 0 is BG_OK with the counts zero.
+ *
+ * bg_sam_emit_dup_batch[_dev]: bg_sam_emit_batch[_dev] with `dup` (n_reads entries, optional) behind `pairs`.  Every placed
+ *   line of read r (slot 0 and secondary slots) carries 0x400 in FLAG when dup[r] != 0; nothing else in the line changes
+ *   (the length of FLAG's decimal text may).  With dup == NULL the output is byte for byte bg_sam_emit_batch[_dev]'s, which
+ *   pass a null dup through.
+ *
+ * bg_sam_sort_keys[_dev]: key[K r + k], n_reads * K entries.  A slot that writes a line and is placed gets ref_start
+ *   (contigs ascend in `start`, so this orders by (RNAME's index, POS)); a paired, unplaced slot whose mate is placed gets
+ *   the mate's ref_start (its line carries the mate's RNAME and POS); every other slot — unmapped lines with "*", slots that
+ *   write no line — gets UINT64_MAX.  BG_ERR_INVALID_ARG as for the writer where it applies: unknown flag bits, max_hits 0
+ *   or above BG_SEED_MAX_HITS, n_contigs 0, paired with an odd n_reads or max_hits != 1, a null ctx or sp, or (n_reads > 0)
+ *   a null contigs, hits, strand or key.  The device flavour is asynchronous on `stream`.
+ *
+ * bg_sam_sort[_dev] knows nothing of SAM: it sorts ANY buffer of variable-length records by a 64-bit key.  Record i is
+ *   in[in_off[i] .. in_off[i + 1]), in_off ascending with in_off[n_slots] <= in_bytes.  perm is the stable ascending sort of
+ *   0 .. n_slots - 1 by key; output record j is input record perm[j]; out_off is the running sum of the permuted lengths
+ *   (n_slots + 1 entries).  Records of length 0 stay in the permutation and add no bytes.  out_cap < in_bytes returns
+ *   BG_ERR_OPS_CAP with nothing written.  d_out must not overlap d_in.  BG_ERR_INVALID_ARG: a null ctx, out_off or perm, or
+ *   (n_slots > 0) a null key, in_off, or (in_bytes > 0) in or out.  The device flavour is asynchronous on `stream`, with no
+ *   read-back; with bg_enable_timing on it waits and reports its stable radix sort (rocPRIM) in bg_timing_t.fm_ms and its
+ *   permuted copy in bg_timing_t.fill_ms.
+ *
+ * bg_sam_header_so: bg_sam_header with the sort order named: BG_SAM_SO_UNSORTED gives exactly bg_sam_header's bytes,
+ *   BG_SAM_SO_COORDINATE the same with SO:coordinate; anything else is BG_ERR_INVALID_ARG.
+ * Not covered: BAM / BGZF, queryname order, optical duplicates, duplicate sets across calls, UMIs. */
+enum { BG_SAM_SO_UNSORTED = 0, BG_SAM_SO_COORDINATE = 1 };
+typedef struct {
+    uint32_t flags;         /* BG_SAM_PAIRED or 0; anything else BG_ERR_INVALID_ARG */
+    uint32_t max_hits;      /* K, as in bg_sam_params_t; only slot K r of read r takes part */
+    uint32_t phred_offset;  /* 33 for Sanger qualities */
+    uint32_t min_qual;      /* quality symbols below it do not count towards a read's score (Picard: 15) */
+} bg_markdup_params_t;
+int bg_sam_markdup_dev(bg_ctx* ctx, const bg_markdup_params_t* mp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                       uint64_t n_contigs, const bg_seed_hit_t* d_hits, const uint8_t* d_strand, const bg_fastq_record_t* d_recs,
+                       const uint8_t* d_qual, uint8_t* d_dup, uint64_t* counts, void* stream);
+int bg_sam_markdup(bg_ctx* ctx, const bg_markdup_params_t* mp, uint64_t n_reads, const bg_sam_contig_t* contigs,
+                   uint64_t n_contigs, const bg_seed_hit_t* hits, const uint8_t* strand, const bg_fastq_record_t* recs,
+                   const uint8_t* qual, uint8_t* dup, uint64_t* counts);
+int bg_sam_emit_dup_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                              uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                              const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                              const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, const uint8_t* d_dup,
+                              char* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream);
+int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs,
+                          uint64_t n_contigs, const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs,
+                          const uint8_t* seq, const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand,
+                          const uint8_t* ops, const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, const uint8_t* dup, char* out,
+                          uint64_t out_cap, uint64_t* out_off, uint64_t* out_bytes);
+int bg_sam_sort_keys_dev(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                         uint64_t n_contigs, const bg_seed_hit_t* d_hits, const uint8_t* d_strand, uint64_t* d_key, void* stream);
+int bg_sam_sort_keys(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
+                     const bg_seed_hit_t* hits, const uint8_t* strand, uint64_t* key);
+int bg_sam_sort_dev(bg_ctx* ctx, uint64_t n_slots, const uint64_t* d_key, const char* d_in, const uint64_t* d_in_off,
+                    uint64_t in_bytes, char* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_perm, void* stream);
+int bg_sam_sort(bg_ctx* ctx, uint64_t n_slots, const uint64_t* key, const char* in, const uint64_t* in_off, uint64_t in_bytes,
+                char* out, uint64_t out_cap, uint64_t* out_off, uint64_t* perm);
+int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, char* out,
+                     uint64_t out_cap, uint64_t* out_bytes);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

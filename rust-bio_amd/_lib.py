@@ -166,6 +166,11 @@ class SAM_PARAMS(C.Structure):
 
 assert C.sizeof(SAM_PARAMS) == 8, C.sizeof(SAM_PARAMS)
 
+# bg_markdup_params_t and BG_SAM_SO_* (bg_sam_markdup[_dev], bg_sam_header_so)
+MARKDUP_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("max_hits", "<u4"), ("phred_offset", "<u4"), ("min_qual", "<u4")])
+assert MARKDUP_PARAMS_DTYPE.itemsize == 16, MARKDUP_PARAMS_DTYPE.itemsize
+SAM_SO_UNSORTED, SAM_SO_COORDINATE = 0, 1
+
 # bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
 assert MYERS_PATTERN_DTYPE.itemsize == 2056, MYERS_PATTERN_DTYPE.itemsize
@@ -214,6 +219,8 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_seed_extend_pairs_mapq_batch", "bg_seed_extend_pairs_mapq_batch_dev",
            "bg_seed_extend_pairs_rescue_mapq_batch", "bg_seed_extend_pairs_rescue_mapq_batch_dev",
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
+           "bg_sam_markdup", "bg_sam_markdup_dev", "bg_sam_emit_dup_batch", "bg_sam_emit_dup_batch_dev", "bg_sam_sort_keys",
+           "bg_sam_sort_keys_dev", "bg_sam_sort", "bg_sam_sort_dev", "bg_sam_header_so",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -375,6 +382,17 @@ def lib():
                                             C.POINTER(u64), vp]
         L.bg_sam_emit_batch.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
                                         C.POINTER(u64)]
+        L.bg_sam_markdup_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.bg_sam_markdup.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+        L.bg_sam_emit_dup_batch_dev.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64,
+                                                vp, C.POINTER(u64), vp]
+        L.bg_sam_emit_dup_batch.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                            C.POINTER(u64)]
+        L.bg_sam_sort_keys_dev.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp, vp]
+        L.bg_sam_sort_keys.argtypes = [vp, C.POINTER(SAM_PARAMS), u64, vp, u64, vp, vp, vp]
+        L.bg_sam_sort_dev.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, vp, vp]
+        L.bg_sam_sort.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, vp]
+        L.bg_sam_header_so.argtypes = [vp, u64, vp, i32, vp, u64, C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

@@ -1,4 +1,6 @@
-// SAM records from seed-and-extend hits (bg_sam_emit_batch[_dev], bg_sam_header): the record is defined in include/biogpu.h.
+// SAM records from seed-and-extend hits (bg_sam_emit[_dup]_batch[_dev], bg_sam_header[_so]): the record is defined in include/biogpu.h;
+// whether a slot is placed and whether it writes a line are decided in sam_rule.h, which the duplicate marker and the sort keys
+// (sam_sort.hip) share.
 // Two passes over the hit slots.  The length pass (one lane per slot) decides what each line holds, walks the slot's
 // operations for the CIGAR, NM and MD lengths and writes the line length; a scan turns the lengths into offsets.  The write
 // pass gives every line a fixed group of 16 or 32 lanes: the group stages the line in LDS at the same offset inside a 16-byte
@@ -13,6 +15,7 @@
 
 #include "dna_complement.h"
 #include "fm_kernels.h"
+#include "sam_rule.h"
 
 namespace {
 
@@ -36,6 +39,7 @@ struct SamArgs {
     const bg_pair_hit_t* pairs;
     const uint8_t* text;
     uint64_t n_text;
+    const uint8_t* dup;  // optional: read r's placed lines carry 0x400 where dup[r] != 0
 };
 
 struct SamDesc {  // what the length pass learned from a slot's operations, and where the two strings go in the line
@@ -69,20 +73,9 @@ __device__ __forceinline__ uint32_t put_signed(char* d, int64_t v) {
     return w + n;
 }
 
-// the contig a slot is placed on, -1 if it is not placed
-__device__ int64_t sam_place(const SamArgs& a, uint64_t slot) {
-    const bg_seed_hit_t& h = a.hits[slot];
-    if (h.aln.score == BG_MIN_SCORE || a.strand[slot] == BG_HIT_NONE) return -1;
-    const uint64_t s = h.ref_start, e = h.ref_end;
-    uint64_t lo = 0, hi = a.n_contigs;  // the first contig that starts behind s
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a.contigs[mid].start <= s) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo == 0) return -1;
-    const uint64_t end = a.contigs[lo - 1].start + a.contigs[lo - 1].len;
-    return s < end && s <= e && e <= end ? (int64_t)(lo - 1) : -1;
+// the contig a slot is placed on, -1 if it is not placed (the rule: sam_rule.h)
+__device__ __forceinline__ int64_t sam_place(const SamArgs& a, uint64_t slot) {
+    return sam_rule_place(a.contigs, a.n_contigs, a.hits[slot], a.strand[slot]);
 }
 
 struct SamLine {
@@ -102,12 +95,12 @@ __device__ SamLine sam_line(const SamArgs& a, uint64_t slot) {
     const uint32_t k = (uint32_t)(slot - r * a.K);
     const int64_t own = sam_place(a, slot);
     L.placed = own >= 0;
-    L.writes = k == 0 || ((a.flags & BG_SAM_SECONDARY) && L.placed && sam_place(a, r * a.K) >= 0);
+    L.writes = sam_rule_writes(a.flags, k, L.placed, k == 0 ? L.placed : sam_place(a, r * a.K) >= 0);
     if (!L.writes) return L;
     const bg_seed_hit_t& h = a.hits[slot];
     const bg_fastq_record_t& rec = a.recs[r];
     L.rev = L.placed && a.strand[slot] == BG_HIT_REVERSE;
-    L.flag = (L.placed ? 0u : 0x4u) | (L.rev ? 0x10u : 0u) | (k ? 0x100u : 0u);
+    L.flag = (L.placed ? 0u : 0x4u) | (L.rev ? 0x10u : 0u) | (k ? 0x100u : 0u) | (a.dup && L.placed && a.dup[r] ? 0x400u : 0u);
     L.contig = own;
     L.pos = L.placed ? h.ref_start - a.contigs[own].start + 1 : 0;
     L.next = -1;
@@ -412,10 +405,11 @@ int sam_check(const bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, uint
 
 }  // namespace
 
-extern "C" int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, char* out, uint64_t out_cap,
-                             uint64_t* out_bytes) {
+extern "C" int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, char* out,
+                                uint64_t out_cap, uint64_t* out_bytes) {
     if (!out_bytes || (n_contigs && (!contigs || !names)) || (!out && out_cap)) return BG_ERR_INVALID_ARG;
-    std::string s = "@HD\tVN:1.6\tSO:unsorted\n";
+    if (sort_order != BG_SAM_SO_UNSORTED && sort_order != BG_SAM_SO_COORDINATE) return BG_ERR_INVALID_ARG;
+    std::string s = sort_order == BG_SAM_SO_COORDINATE ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\n";
     for (uint64_t c = 0; c < n_contigs; c++) {
         s += "@SQ\tSN:";
         s.append(names + contigs[c].name_off, contigs[c].name_len);
@@ -429,11 +423,16 @@ extern "C" int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs,
     return BG_OK;
 }
 
-extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
-                                     uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
-                                     const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
-                                     const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, char* d_out,
-                                     uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream) {
+extern "C" int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, char* out, uint64_t out_cap,
+                             uint64_t* out_bytes) {
+    return bg_sam_header_so(contigs, n_contigs, names, BG_SAM_SO_UNSORTED, out, out_cap, out_bytes);
+}
+
+extern "C" int bg_sam_emit_dup_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                                         uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                                         const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                                         const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, const uint8_t* d_dup,
+                                         char* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream) {
     if (!d_out_off || !out_bytes) return BG_ERR_INVALID_ARG;
     *out_bytes = 0;
     int rc = sam_check(fm, sp, n_reads, n_contigs, d_pairs);
@@ -458,7 +457,7 @@ extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint6
     SamDesc* d_desc = (SamDesc*)((uint8_t*)ctx->aux + len_bytes);
     uint64_t* d_sums = (uint64_t*)((uint8_t*)ctx->aux + len_bytes + desc_bytes);
     const SamArgs a = {n_slots, sp->max_hits, sp->flags, d_contigs, n_contigs, d_names, d_fastq_text, d_recs, d_seq, d_qual, d_hits,
-                       d_strand, d_ops, d_multi, (sp->flags & BG_SAM_PAIRED) ? d_pairs : nullptr, (const uint8_t*)fm->d_text, fm->n_text};
+                       d_strand, d_ops, d_multi, (sp->flags & BG_SAM_PAIRED) ? d_pairs : nullptr, (const uint8_t*)fm->d_text, fm->n_text, d_dup};
     sam_length_kernel<<<dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, st>>>(a, d_len, d_desc);
     BG_HIP(hipGetLastError());
     if ((rc = bg_scan_u32(d_len, n_slots, d_out_off, d_sums, st))) return rc;
@@ -477,11 +476,20 @@ extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint6
     return BG_OK;
 }
 
-extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
-                                 const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
-                                 const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
-                                 const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap, uint64_t* out_off,
-                                 uint64_t* out_bytes) {
+extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                                     uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                                     const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                                     const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, char* d_out,
+                                     uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream) {
+    return bg_sam_emit_dup_batch_dev(fm, sp, n_reads, d_contigs, n_contigs, d_names, d_fastq_text, d_recs, d_seq, d_qual, d_hits, d_strand, d_ops,
+                                     d_multi, d_pairs, nullptr, d_out, out_cap, d_out_off, out_bytes, stream);
+}
+
+extern "C" int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
+                                     const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
+                                     const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
+                                     const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, const uint8_t* dup, char* out, uint64_t out_cap,
+                                     uint64_t* out_off, uint64_t* out_bytes) {
     if (!out_off || !out_bytes) return BG_ERR_INVALID_ARG;
     *out_bytes = 0;
     int rc = sam_check(fm, sp, n_reads, n_contigs, pairs);
@@ -503,27 +511,27 @@ extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t 
     for (uint64_t s = 0; s < n_slots; s++)
         if (hits[s].aln.score != BG_MIN_SCORE) ops_bytes = std::max<uint64_t>(ops_bytes, hits[s].aln.ops_off + hits[s].aln.n_ops);
     for (uint64_t c = 0; c < n_contigs; c++) name_bytes = std::max<uint64_t>(name_bytes, contigs[c].name_off + contigs[c].name_len);
-    enum { CONTIGS, NAMES, FQ, RECS, SEQ, QUAL, HITS, STRAND, OPS, MULTI, PAIRS, OFF, OUT, N };
-    const void* src[N] = {contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi, pairs, nullptr, nullptr};
+    enum { CONTIGS, NAMES, FQ, RECS, SEQ, QUAL, HITS, STRAND, OPS, MULTI, PAIRS, DUP, OFF, OUT, N };
+    const void* src[N] = {contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi, pairs, dup, nullptr, nullptr};
     const size_t bytes[N] = {(size_t)(n_contigs * sizeof(bg_sam_contig_t)), (size_t)name_bytes, (size_t)fq_bytes,
                              (size_t)(n_reads * sizeof(bg_fastq_record_t)), (size_t)seq_bytes, (size_t)qual_bytes,
                              (size_t)(n_slots * sizeof(bg_seed_hit_t)), (size_t)n_slots, (size_t)ops_bytes,
                              multi ? (size_t)(n_reads * sizeof(bg_multi_hit_t)) : 0, pairs ? (size_t)(n_reads / 2 * sizeof(bg_pair_hit_t)) : 0,
-                             (size_t)((n_slots + 1) * 8), (size_t)out_cap};
+                             dup ? (size_t)n_reads : 0, (size_t)((n_slots + 1) * 8), (size_t)out_cap};
     void* d[N] = {};
     auto run = [&]() -> int {
         hipStream_t st = ctx->stream;
         for (int i = 0; i < N; i++) {
-            if (!src[i] && i < OFF) continue;  // multi / pairs not given
+            if (!src[i] && i < OFF) continue;  // multi / pairs / dup not given
             if (i == OUT && !out) continue;    // a sizing call
             BG_HIP(hipMalloc(&d[i], std::max<size_t>(bytes[i], 16)));
             if (src[i] && bytes[i]) BG_HIP(hipMemcpyAsync(d[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
         }
-        const int rc2 = bg_sam_emit_batch_dev(fm, sp, n_reads, (const bg_sam_contig_t*)d[CONTIGS], n_contigs, (const char*)d[NAMES],
-                                              (const uint8_t*)d[FQ], (const bg_fastq_record_t*)d[RECS], (const uint8_t*)d[SEQ],
-                                              (const uint8_t*)d[QUAL], (const bg_seed_hit_t*)d[HITS], (const uint8_t*)d[STRAND],
-                                              (const uint8_t*)d[OPS], (const bg_multi_hit_t*)d[MULTI], (const bg_pair_hit_t*)d[PAIRS],
-                                              (char*)d[OUT], out_cap, (uint64_t*)d[OFF], out_bytes, st);
+        const int rc2 = bg_sam_emit_dup_batch_dev(fm, sp, n_reads, (const bg_sam_contig_t*)d[CONTIGS], n_contigs, (const char*)d[NAMES],
+                                                  (const uint8_t*)d[FQ], (const bg_fastq_record_t*)d[RECS], (const uint8_t*)d[SEQ],
+                                                  (const uint8_t*)d[QUAL], (const bg_seed_hit_t*)d[HITS], (const uint8_t*)d[STRAND],
+                                                  (const uint8_t*)d[OPS], (const bg_multi_hit_t*)d[MULTI], (const bg_pair_hit_t*)d[PAIRS],
+                                                  (const uint8_t*)d[DUP], (char*)d[OUT], out_cap, (uint64_t*)d[OFF], out_bytes, st);
         if (rc2 && rc2 != BG_ERR_OPS_CAP) return rc2;
         BG_HIP(hipMemcpyAsync(out_off, d[OFF], bytes[OFF], hipMemcpyDeviceToHost, st));
         if (!rc2 && out && *out_bytes) BG_HIP(hipMemcpyAsync(out, d[OUT], *out_bytes, hipMemcpyDeviceToHost, st));
@@ -533,4 +541,13 @@ extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t 
     rc = run();
     for (void* p : d) hipFree(p);
     return rc;
+}
+
+extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
+                                 const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
+                                 const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
+                                 const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, char* out, uint64_t out_cap, uint64_t* out_off,
+                                 uint64_t* out_bytes) {
+    return bg_sam_emit_dup_batch(fm, sp, n_reads, contigs, n_contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi, pairs, nullptr,
+                                 out, out_cap, out_off, out_bytes);
 }
