@@ -103,10 +103,12 @@ LINE_LENGTHS = (0, 1, 15, 16, 17, 31, 32, 33, 255, 256, 257)
 
 def synthetic_lines(rng, n, lengths=LINE_LENGTHS, long_at=None, long_len=140_000):
     """n records of the given lengths in random order (every byte value but chosen so that a misplaced byte shows), one of
-    long_len bytes at index long_at; returns (records: list of bytes, text: bytes, off: uint64[n + 1])"""
+    long_len bytes at index long_at, or several: long_at = {index: length}; returns (records: list of bytes, text: bytes,
+    off: uint64[n + 1])"""
     recs = []
+    longs = long_at if isinstance(long_at, dict) else {long_at: long_len}
     for i in range(n):
-        ln = long_len if i == long_at else rng.choice(lengths)
+        ln = longs[i] if i in longs else rng.choice(lengths)
         j = np.arange(ln, dtype=np.uint64)
         recs.append(((i * 7 + j * 13 + (j >> 8) * 5 + (j >> 12)) & 0xFF).astype(np.uint8).tobytes())
     return recs, b"".join(recs), so.offsets(recs)

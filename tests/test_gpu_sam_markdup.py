@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import sam_edge_cases as ec
 import sam_oracle as so
 import sam_sort_oracle as sso
 from rust_bio_amd import _lib, sam
@@ -120,3 +121,87 @@ def test_random_batches(paired, K):
     assert seen["group won on index"] >= 10 and seen["group won on score"] >= 20 and seen["unplaced"] >= 50, seen
     if paired:
         assert seen["pair group"] >= 20 and seen["fragment flagged by a pair"] >= 10 and seen["fragment group"] >= 5, seen
+
+
+# ---- the lanes of the score kernel, batch shapes, and the chain without pairs (tests/sam_edge_cases.py) ---------------------
+@pytest.mark.parametrize("min_qual", ec.MIN_QUALS)
+def test_quality_lengths_around_the_lanes_of_a_read(min_qual):
+    fq, hits, strand = ec.qual_lengths()
+    assert tuple(int(r["qual_len"]) for r in fq.recs[::3]) == ec.QUAL_LENGTHS
+    dup, counts = check(fq, hits, strand, min_qual=min_qual)
+    assert dup.tolist() == [0, 1, 1] + [1, 1, 0] * (len(ec.QUAL_LENGTHS) - 1)  # the last quality byte decides every group
+
+
+@pytest.mark.parametrize("n", [15, 16, 17, 255, 256, 257])
+def test_batch_sizes_around_a_block(n):
+    fq, hits, strand = random_batch(random.Random(50 + n), n, n_coords=4)
+    dup, counts = check(fq, hits, strand)
+    assert n < 255 or counts[1] >= 50
+    if n % 2 == 0:
+        fq, hits, strand = random_batch(random.Random(60 + n), n, paired=True, n_coords=4)
+        check(fq, hits, strand, so.PAIRED)
+
+
+def test_nothing_is_placed():
+    for paired in (False, True):
+        fq, hits, strand = random_batch(random.Random(71), 300, paired=paired, p_unmapped=1.0)
+        dup, counts = check(fq, hits, strand, so.PAIRED if paired else 0)
+        assert counts == [0, 0, 0, 0] and not dup.any()
+
+
+def test_fragments_only():
+    fq, hits, strand = ec.fragments_only()
+    dup, counts = check(fq, hits, strand, so.PAIRED)
+    assert counts[0] == len(fq.recs) // 2 and counts[1] >= 20 and counts[2:] == [0, 0]
+
+
+@pytest.mark.parametrize("K,flags", [(1, 0), (4, so.SECONDARY)])
+def test_the_chain_without_pairs(K, flags):
+    """markdup -> emit with dup -> keys -> sort on a synthetic unpaired batch: `sam.sorted_sam`, and the four device calls chained
+    in HBM, against the composition of the four oracles under an SO:coordinate header"""
+    from test_gpu_sam_emit_edges import index
+    fm = index()
+    n = 600
+    fq, hits, strand = random_batch(random.Random(80 + K), n, K=K, p_unmapped=0.3)
+    flags |= so.TAG_NM
+    ops = np.zeros(0, dtype=np.uint8)
+    dup, counts = sso.markdup(CONTIGS, fq, hits, strand, 0, K, PHRED, MIN_QUAL)
+    plain = so.lines(CONTIGS, fq, hits, strand, ops, flags, K)
+    flagged = sso.add_dup_flag(plain, dup, K)
+    key = sso.sort_keys(CONTIGS, hits, strand, flags, K)
+    perm, out_off, want = sso.sort(key, flagged)
+    assert counts[1] >= 50 and sum(a != b for a, b in zip(plain, flagged)) >= counts[1] and (key == 2**64 - 1).sum() >= 100
+    assert K == 1 or sum(not x for x in plain) >= 100 <= sum(bool(x) for s, x in enumerate(plain) if s % K)
+    table = sam.Contigs(CONTIGS)
+    header = so.header(CONTIGS).replace(b"SO:unsorted", b"SO:coordinate")
+    mp = sam.MarkdupParams(0, K, PHRED, MIN_QUAL)
+    assert sam.sorted_sam(fm, sam.SamParams(flags, K), table, fq, hits, strand, ops, markdup=mp, ctx=fm.ctx) == header + want
+    # the device calls, chained in HBM
+    stream = torch.cuda.current_stream().cuda_stream
+    d_table, d_names, d_text, d_recs, d_seq, d_qual, d_hits, d_strand, d_ops = (dev(x) for x in (
+        table.table, table.names, fq.text, fq.recs, fq.seq, fq.qual, hits, strand, np.zeros(16, np.uint8)))
+    d_dup = torch.full((n,), 0x7e, dtype=torch.uint8, device=DEV)
+    assert sam.markdup_dev(mp, n, d_table.data_ptr(), len(table), d_hits.data_ptr(), d_strand.data_ptr(), d_recs.data_ptr(), d_qual.data_ptr(),
+                           d_dup.data_ptr(), stream=stream, ctx=fm.ctx) == counts
+    d_off = torch.zeros(n * K + 1, dtype=torch.int64, device=DEV)
+    emit = (fm, sam.SamParams(flags, K), n, d_table.data_ptr(), len(table), d_names.data_ptr(), d_text.data_ptr(), d_recs.data_ptr(),
+            d_seq.data_ptr(), d_qual.data_ptr(), d_hits.data_ptr(), d_strand.data_ptr(), d_ops.data_ptr())
+    total = sam.emit_dev(*emit, 0, 0, d_off.data_ptr(), d_dup=d_dup.data_ptr(), stream=stream)
+    assert total == len(want)
+    d_lines = torch.full((total,), 0x7e, dtype=torch.uint8, device=DEV)
+    assert sam.emit_dev(*emit, d_lines.data_ptr(), total, d_off.data_ptr(), d_dup=d_dup.data_ptr(), stream=stream) == total
+    d_key = torch.zeros(n * K, dtype=torch.int64, device=DEV)
+    sam.sort_keys_dev(sam.SamParams(flags, K), n, d_table.data_ptr(), len(table), d_hits.data_ptr(), d_strand.data_ptr(), d_key.data_ptr(),
+                      stream=stream, ctx=fm.ctx)
+    d_sorted = torch.full((total + 64,), 0x7e, dtype=torch.uint8, device=DEV)
+    d_sorted_off = torch.zeros(n * K + 1, dtype=torch.int64, device=DEV)
+    d_perm = torch.zeros(n * K, dtype=torch.int64, device=DEV)
+    sam.sort_dev(n * K, d_key.data_ptr(), d_lines.data_ptr(), d_off.data_ptr(), total, d_sorted.data_ptr(), total, d_sorted_off.data_ptr(),
+                 d_perm.data_ptr(), stream=stream, ctx=fm.ctx)
+    torch.cuda.synchronize()
+    assert d_dup.cpu().numpy().tobytes() == dup.tobytes() and d_lines.cpu().numpy().tobytes() == b"".join(flagged)
+    assert (d_key.cpu().numpy().astype(np.uint64) == key).all() and (d_perm.cpu().numpy().astype(np.uint64) == perm).all()
+    assert (d_sorted_off.cpu().numpy().astype(np.uint64) == out_off).all()
+    body = d_sorted.cpu().numpy()
+    assert (body[total:] == 0x7e).all() and body[:total].tobytes() == want
+    sso.check_sorted_text([c[0] for c in CONTIGS], b"".join(flagged), want)

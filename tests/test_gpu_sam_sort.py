@@ -12,6 +12,7 @@ import torch
 import sam_oracle as so
 import sam_sort_oracle as sso
 from rust_bio_amd import _lib, sam
+import sam_edge_cases as ec
 from sam_sort_cases import LINE_LENGTHS, synthetic_lines
 
 pytestmark = pytest.mark.gpu
@@ -106,3 +107,38 @@ def test_tiny(n):
     check([9] * n, [b"only line\n"] * n)
     if n:
         check([9], [b""])
+
+
+# ---- the edges of the two copy kernels (the batches of tests/sam_edge_cases.py; tests/test_sam_edge_cases.py shows what they hold)
+def test_lengths_around_the_switch_between_the_copy_kernels():
+    b = ec.sort_switch()
+    assert {(ln, res) for ln, res, _ in b.placed() if ln >= 16383} == {(ln, res) for ln in ec.SWITCH_LENGTHS for res in ec.RESIDUES}
+    check(b.key, b.recs)
+
+
+def test_lengths_around_a_chunk_and_the_column_wrap():
+    b = ec.sort_chunk()
+    assert {(ln >> 4) // 256 + 1 for ln, _, _ in b.placed()} == {5, 6, 32, 33, 34}  # chunks as the long-line kernel counts them
+    check(b.key, b.recs)
+
+
+@pytest.mark.parametrize("n_long", [255, 256, 257])
+def test_row_wrap_of_the_long_line_kernel(n_long):
+    b = ec.sort_rows(n_long)
+    assert sum(len(r) > ec.LONG_LINE for r in b.recs) == n_long
+    check(b.key, b.recs, host=n_long == 257)
+
+
+@pytest.mark.parametrize("which", ["first", "last"])
+def test_a_long_line_at_either_end_of_the_buffer(which):
+    b = ec.sort_ends(which)
+    perm, _ = check(b.key, b.recs, host=which == "last")  # (check() requires the 64 poisoned bytes behind the text intact)
+    assert len(b.recs[int(perm[0 if which == "first" else -1])]) == 20_000
+
+
+def test_several_long_lines_from_the_generator():
+    rng = random.Random(13)
+    longs = {3: 16_385, 40: 20_480, 41: 16_384, 99: 70_001}
+    recs, _, _ = synthetic_lines(rng, 100, long_at=longs)
+    assert all(len(recs[i]) == ln for i, ln in longs.items())
+    check([rng.randrange(8) for _ in recs], recs, host=False)

@@ -4,14 +4,15 @@ that picks a group's winner, and the per-line copy plan — head, destination-al
 source, tail) run on the CPU by a stand-alone program (tests/sam_sort_host_bodies.cpp) built with AddressSanitizer and UBSan, on
 seeded random batches against the restatement (tests/sam_sort_oracle.py), byte for byte.  Every buffer has exactly its size and
 the lines follow a poisoned prefix of 0 .. 15 bytes: a byte loaded or stored outside one stops the program.  Single-end with K = 1
-and K = 3, paired with a quarter to two thirds of the reads unmapped (many pairs, many fragments); lines of every length around the 16-byte granule, and one beyond the long-line threshold per round.  Nothing is
-loaded into Python."""
+and K = 3, paired with a quarter to two thirds of the reads unmapped (many pairs, many fragments); lines of every length around the 16-byte granule, and one beyond the long-line threshold per round; then the
+batches of tests/sam_edge_cases.py at the edges of the copy's two paths and of the score's lane loop.  Nothing is loaded into Python."""
 import os
 import random
 import subprocess
 
 import numpy as np
 
+import sam_edge_cases as ec
 import sam_oracle as so
 import sam_sort_oracle as sso
 from rust_bio_amd import _lib
@@ -33,20 +34,16 @@ def test_sam_sort_bodies_on_the_host_under_sanitizers(tmp_path):
         table[c] = (start, ln, 0, len(name), 0)
     seen = {}
     rounds = [(True, 1, so.PAIRED), (False, 1, 0), (False, 3, so.SECONDARY), (True, 1, so.PAIRED), (False, 3, 0), (True, 1, so.PAIRED)] * 3
-    for rnd, (paired, K, key_flags) in enumerate(rounds):
-        n = 2 * rng.randint(150, 220)
-        fq, hits, strand = random_batch(rng, n, K=K, paired=paired, p_unmapped=(0.3, 0.55, 0.7)[rnd // 3 % 3] if paired else 0.12)
-        prefix = (rnd * 7 + 3) % 16
-        recs, text, off = synthetic_lines(rng, n * K, lengths=LINE_LENGTHS + (40, 77, 100), long_at=rng.randrange(n * K),
-                                          long_len=sso_long_len(rnd))
-        md_flags = so.PAIRED if paired else 0
+
+    def run(rnd, fq, hits, strand, K, key_flags, md_flags, recs, prefix, min_qual=MIN_QUAL):
+        n, text, off = len(fq.recs), b"".join(recs), so.offsets(recs)
         with open(inp, "wb") as f:
-            f.write(np.array([n, K, key_flags, md_flags, PHRED, MIN_QUAL, len(CONTIGS), len(fq.qual), prefix, len(text)], dtype=np.uint64).tobytes())
+            f.write(np.array([n, K, key_flags, md_flags, PHRED, min_qual, len(CONTIGS), len(fq.qual), prefix, len(text)], dtype=np.uint64).tobytes())
             f.write(table.tobytes() + hits.tobytes() + strand.tobytes() + fq.recs.tobytes() + bytes(fq.qual))
             f.write(bytes(prefix) + text + off.tobytes())
         subprocess.check_call([exe, inp, outp])
         raw = open(outp, "rb").read()
-        w_dup, w_counts = sso.markdup(CONTIGS, fq, hits, strand, md_flags, K, PHRED, MIN_QUAL, events=seen)
+        w_dup, w_counts = sso.markdup(CONTIGS, fq, hits, strand, md_flags, K, PHRED, min_qual, events=seen)
         w_key = sso.sort_keys(CONTIGS, hits, strand, key_flags, K, events=seen)
         w_perm, w_off, w_text = sso.sort(w_key, recs)
         want = [w_dup.tobytes(), np.array(w_counts, dtype=np.uint64).tobytes(), w_key.tobytes(), w_perm.tobytes(), w_off.tobytes(), w_text]
@@ -55,6 +52,25 @@ def test_sam_sort_bodies_on_the_host_under_sanitizers(tmp_path):
         for what, w in zip(("dup", "counts", "key", "perm", "out_off", "text"), want):
             assert raw[at:at + len(w)] == w, (rnd, what)
             at += len(w)
+        return w_key
+
+    for rnd, (paired, K, key_flags) in enumerate(rounds):
+        n = 2 * rng.randint(150, 220)
+        fq, hits, strand = random_batch(rng, n, K=K, paired=paired, p_unmapped=(0.3, 0.55, 0.7)[rnd // 3 % 3] if paired else 0.12)
+        prefix = (rnd * 7 + 3) % 16
+        recs, text, off = synthetic_lines(rng, n * K, lengths=LINE_LENGTHS + (40, 77, 100), long_at=rng.randrange(n * K),
+                                          long_len=sso_long_len(rnd))
+        run(rnd, fq, hits, strand, K, key_flags, so.PAIRED if paired else 0, recs, prefix)
+    # the copy at the edges of its two paths (tests/sam_edge_cases.py): lengths around the switch to chunks, around a chunk and
+    # the 32-column wrap, 256 long lines; the keys go in as hit records
+    for i, b in enumerate((ec.sort_switch(), ec.sort_chunk(), ec.sort_rows(256))):
+        fq, hits, strand = b.hits()
+        assert (run(b.name, fq, hits, strand, 1, 0, 0, b.recs, (5 * i + 9) % 16) == b.key).all()
+    # the score at the edges of the lane loop: quality strings of 0 ... 65 535 bytes whose last byte decides
+    fq, hits, strand = ec.qual_lengths()
+    for min_qual in ec.MIN_QUALS:
+        recs, _, _ = synthetic_lines(rng, len(fq.recs))
+        run("qualities %d" % min_qual, fq, hits, strand, 1, 0, 0, recs, 1, min_qual)
     assert not {k: seen.get(k, 0) for k in EVENTS if seen.get(k, 0) < 50}, seen
 
 
