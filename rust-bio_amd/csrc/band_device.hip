@@ -18,7 +18,8 @@
 //
 // Pairs the device path does not cover (more matches than the LDS tree holds, overlong hash chains)
 // are flagged and rebuilt by the host builder (band_host.cpp); results are identical either way —
-// tests/test_gpu_banded.py compares the two builders band by band.
+// tests/test_gpu_banded.py compares the two builders band by band, tests/test_gpu_band_builder_edges.py on pairs that
+// sit on every limit below, counting the pairs that were handed back.
 #include "banded_kernels.h"
 #include "band_device.h"
 
@@ -1094,12 +1095,18 @@ __global__ __launch_bounds__(256) void band_rows_kernel(const BandDevArgs a) {
     else if (n == 0 || j_first == 0xFFFFFFFFu)
         flags = BP_UNSUPPORTED;
     if (flags == BP_OK) {
+        // A guard, not a path: band_kernel leaves no hole between the first and the last column.  Every add_kmer writes
+        // the whole interval [c - w, c + k + w), a continuation's box starts at c + k - w, a gap's boxes step by at most
+        // one column from the k-mer behind it to the one in front, and set_boundaries extends the first / last k-mer
+        // outwards the same way.  An untouched column holds (m + 1, 0), so the thread that meets the first column of a
+        // hole also sees end[j] < end[j - 1], and the one behind the hole start[j] < start[j - 1]: which of the two values
+        // s_bad keeps is then a race between them, not a hand-over to the host sweep one could rely on.
         for (uint32_t j = j_first + threadIdx.x; j <= j_last; j += blockDim.x) {
             if (end[j] <= start[j]) s_bad = 1;  // a hole
             if (j > j_first && (start[j] < start[j - 1] || end[j] < end[j - 1])) s_bad = 2;  // not monotone
         }
         __syncthreads();
-        if (s_bad == 1) flags = BP_HOST_FALLBACK;  // the host sweep copes with holes
+        if (s_bad == 1) flags = BP_HOST_FALLBACK;
         if (s_bad == 2) flags = BP_UNSUPPORTED;
     }
     uint64_t tb_bytes = 0;
