@@ -504,6 +504,30 @@ def as_u8(b):
     return np.frombuffer(bytes(b), dtype=np.uint8)
 
 
+# The five FASTQ columns (recs, seq, seq_off, qual, qual_off) of myers.trim, fastq.filter_arrays and fastq.demux_split_arrays
+# and of their *_dev twins.  `rec_slots`: the records the output record column is allocated for; the callers differ in it
+# (n, or max(1, n) where the call refuses a null record column).
+def fq_columns(recs, seq, seq_off, qual, qual_off):
+    """the five host columns, contiguous and of the dtypes the C ABI reads"""
+    return (np.ascontiguousarray(recs, dtype=FQREC_DTYPE), as_u8(seq), np.ascontiguousarray(seq_off, dtype=np.uint64), as_u8(qual),
+            np.ascontiguousarray(qual_off, dtype=np.uint64))
+
+
+def fq_host_outputs(n, rec_slots, seq, qual):
+    """host output columns for n records of at most the bytes of `seq` and `qual`"""
+    return (np.zeros(rec_slots, dtype=FQREC_DTYPE), np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64),
+            np.zeros(max(1, len(qual)), dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64))
+
+
+def fq_dev_outputs(n, rec_slots, d_seq, d_qual):
+    """device output columns (torch) for n records of at most the bytes of d_seq and d_qual, on their device"""
+    import torch
+    dev = d_seq.device
+    return (torch.empty(rec_slots * 56, dtype=torch.uint8, device=dev), torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev),
+            torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev),
+            torch.empty(n + 1, dtype=torch.int64, device=dev))
+
+
 def concat(seqs):
     """list of bytes -> (uint8 buffer, uint64 offsets[n+1])"""
     off = np.zeros(len(seqs) + 1, dtype=np.uint64)

@@ -175,39 +175,32 @@ extern "C" int bg_pretty_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* al
     out_off[0] = 0;
     if (n == 0) return BG_OK;
     if (!aln || (!ops && ops_bytes) || !x_off || !y_off || !out) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
     uint64_t max_ml = 0;
     for (uint64_t p = 0; p < n; p++) {
         if (aln[p].n_ops && aln[p].ops_off + aln[p].n_ops > ops_bytes) return BG_ERR_INVALID_ARG;
         max_ml = std::max<uint64_t>(max_ml, (x_off[p + 1] - x_off[p]) + (y_off[p + 1] - y_off[p]));
     }
     const uint64_t stride = (3 * max_ml + 5 * ((max_ml + ncol - 1) / ncol) + 15) & ~15ull;
-    const uint64_t xb = x_off[n], yb = y_off[n];
-    void* d[8] = {};
-    const size_t need[8] = {n * sizeof(bg_alignment_t), std::max<uint64_t>(ops_bytes, 16), std::max<uint64_t>(xb, 16), (n + 1) * 8,
-                            std::max<uint64_t>(yb, 16), (n + 1) * 8, std::max<uint64_t>(n * stride, 16), n * 8};
-    const void* src[6] = {aln, ops, x, x_off, y, y_off};
-    const size_t src_bytes[6] = {need[0], (size_t)ops_bytes, (size_t)xb, need[3], (size_t)yb, need[5]};
-    std::vector<char> h;
+    std::vector<char> h((size_t)(n * stride));
     std::vector<int64_t> hl(n);
-    auto run = [&]() -> int {
-        hipStream_t st = ctx->stream;
-        for (int i = 0; i < 8; i++) BG_HIP(hipMalloc(&d[i], need[i]));
-        for (int i = 0; i < 6; i++)
-            if (src_bytes[i]) BG_HIP(hipMemcpyAsync(d[i], src[i], src_bytes[i], hipMemcpyHostToDevice, st));
-        pretty_kernel<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st>>>((const bg_alignment_t*)d[0], (const uint8_t*)d[1], n,
-                                                                              (const uint8_t*)d[2], (const uint64_t*)d[3], (const uint8_t*)d[4],
-                                                                              (const uint64_t*)d[5], ncol, (char*)d[6], stride, (int64_t*)d[7]);
+    {
+        bg_stage s(ctx, ctx->stream);
+        const bg_alignment_t* d_aln = s.up(aln, n);
+        const uint8_t* d_ops = s.up(ops, ops_bytes);
+        const uint8_t* d_x = s.up(x, x_off[n]);
+        const uint64_t* d_x_off = s.up(x_off, n + 1);
+        const uint8_t* d_y = s.up(y, y_off[n]);
+        const uint64_t* d_y_off = s.up(y_off, n + 1);
+        char* d_text = s.out<char>(n * stride);
+        int64_t* d_len = s.out<int64_t>(n);
+        if (s.rc) return s.rc;
+        pretty_kernel<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s.st>>>(d_aln, d_ops, n, d_x, d_x_off, d_y, d_y_off, ncol, d_text, stride,
+                                                                                d_len);
         BG_HIP(hipGetLastError());
-        h.resize((size_t)(n * stride));
-        BG_HIP(hipMemcpyAsync(h.data(), d[6], n * stride, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(hl.data(), d[7], n * 8, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return BG_OK;
-    };
-    int rc = run();
-    for (void* q : d) hipFree(q);
-    if (rc) return rc;
+        s.down(h.data(), d_text, n * stride);
+        s.down(hl.data(), d_len, n);
+        if (s.sync()) return s.rc;
+    }
     uint64_t used = 0;
     int status = BG_OK;
     for (uint64_t p = 0; p < n; p++) {

@@ -24,6 +24,12 @@ extern thread_local std::string bg_tls_error;
         }                                                                                \
     } while (0)
 
+// a refusal that says why (bg_last_error), so that each can be told from the others where no device is present
+inline int bg_refuse(const char* why, int rc = BG_ERR_INVALID_ARG) {
+    bg_tls_error = why;
+    return rc;
+}
+
 struct bg_band_scratch;  // banded_api.hip
 void bg_band_scratch_free(bg_band_scratch*);
 struct bg_seed_scratch;  // seed_extend.hip
@@ -160,6 +166,7 @@ inline hipError_t bg_copy_pieces(void* dst, const void* src, size_t bytes, hipMe
     }
     return hipSuccess;
 }
+#include "bg_stage.h"  // the device copies of the host-buffer entry points
 // host threads this process may really use (affinity mask and cgroup CPU quota)
 unsigned bg_host_threads();
 namespace bgpack {

@@ -14,17 +14,12 @@
 // into bases in wavefront order, then, step by step in input order, the earlier lanes of the same group by ballots over the
 // bits of the group number — and writes perm[k] and the two lengths at k; two more scans give the byte offsets; the copy
 // kernel (16 lanes per output record, the filter's fq_copy_record) moves the bytes.  No atomic decides an order.
-#include <algorithm>
-
-#include "bg_common.h"
+//
+// The host flavours stage their arrays through a bg_stage, the split its columns by fastq_cols.h.
+#include "fastq_cols.h"
 #include "fastq_demux_rule.h"
 
 namespace {
-
-int refuse(const char* why, int rc = BG_ERR_INVALID_ARG) {
-    bg_tls_error = why;
-    return rc;
-}
 
 // ---- assign -------------------------------------------------------------------------------------------------------------
 // G lanes per read.  With BG_DMX_PAIRED n is even and 256 / G is, so a read's mate is in the same wavefront and in range
@@ -60,21 +55,21 @@ __global__ __launch_bounds__(256) void dmx_assign_kernel(uint64_t n, const bg_de
 
 int assign_check(const bg_ctx* ctx, uint64_t n, const bg_demux_params_t* p, const void* hits, uint32_t n_pat, const uint32_t* pat_bin,
                  const void* bin, const void* hit_out) {
-    if (!p) return refuse("bg_fastq_demux_assign: null params");
+    if (!p) return bg_refuse("bg_fastq_demux_assign: null params");
     const uint32_t known = BG_DMX_ANCHOR_5P | BG_DMX_ANCHOR_3P | BG_DMX_PAIRED | BG_DMX_MATE1 | BG_DMX_MATE2;
-    if (p->flags & ~known) return refuse("bg_fastq_demux_assign: unknown flag bits");
-    if ((p->flags & BG_DMX_ANCHOR_5P) && (p->flags & BG_DMX_ANCHOR_3P)) return refuse("bg_fastq_demux_assign: both ANCHOR flags");
-    if ((p->flags & (BG_DMX_MATE1 | BG_DMX_MATE2)) && !(p->flags & BG_DMX_PAIRED)) return refuse("bg_fastq_demux_assign: a MATE flag without PAIRED");
-    if ((p->flags & BG_DMX_PAIRED) && (n & 1)) return refuse("bg_fastq_demux_assign: PAIRED with an odd record count");
-    if (p->n_bins == 0) return refuse("bg_fastq_demux_assign: n_bins 0");
-    if (p->n_bins > BG_DMX_MAX_BINS) return refuse("bg_fastq_demux_assign: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
-    if (n_pat == 0) return refuse("bg_fastq_demux_assign: n_pat 0");
-    if (n_pat > BG_MYERS_MAX_PATTERNS) return refuse("bg_fastq_demux_assign: n_pat above BG_MYERS_MAX_PATTERNS", BG_ERR_TOO_LARGE);
-    if (!pat_bin) return refuse("bg_fastq_demux_assign: null pat_bin");
+    if (p->flags & ~known) return bg_refuse("bg_fastq_demux_assign: unknown flag bits");
+    if ((p->flags & BG_DMX_ANCHOR_5P) && (p->flags & BG_DMX_ANCHOR_3P)) return bg_refuse("bg_fastq_demux_assign: both ANCHOR flags");
+    if ((p->flags & (BG_DMX_MATE1 | BG_DMX_MATE2)) && !(p->flags & BG_DMX_PAIRED)) return bg_refuse("bg_fastq_demux_assign: a MATE flag without PAIRED");
+    if ((p->flags & BG_DMX_PAIRED) && (n & 1)) return bg_refuse("bg_fastq_demux_assign: PAIRED with an odd record count");
+    if (p->n_bins == 0) return bg_refuse("bg_fastq_demux_assign: n_bins 0");
+    if (p->n_bins > BG_DMX_MAX_BINS) return bg_refuse("bg_fastq_demux_assign: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
+    if (n_pat == 0) return bg_refuse("bg_fastq_demux_assign: n_pat 0");
+    if (n_pat > BG_MYERS_MAX_PATTERNS) return bg_refuse("bg_fastq_demux_assign: n_pat above BG_MYERS_MAX_PATTERNS", BG_ERR_TOO_LARGE);
+    if (!pat_bin) return bg_refuse("bg_fastq_demux_assign: null pat_bin");
     for (uint32_t q = 0; q < n_pat; q++)
-        if (pat_bin[q] >= p->n_bins && pat_bin[q] != BG_DMX_IGNORE) return refuse("bg_fastq_demux_assign: a pat_bin entry names no bin");
-    if (n && (!hits || !bin || !hit_out)) return refuse("bg_fastq_demux_assign: null hits, bin or hit_out");
-    if (!ctx) return refuse("bg_fastq_demux_assign: null ctx");
+        if (pat_bin[q] >= p->n_bins && pat_bin[q] != BG_DMX_IGNORE) return bg_refuse("bg_fastq_demux_assign: a pat_bin entry names no bin");
+    if (n && (!hits || !bin || !hit_out)) return bg_refuse("bg_fastq_demux_assign: null hits, bin or hit_out");
+    if (!ctx) return bg_refuse("bg_fastq_demux_assign: null ctx");
     return BG_OK;
 }
 
@@ -174,28 +169,17 @@ __global__ __launch_bounds__(256) void dmx_copy_kernel(uint64_t n, const uint64_
     if (hit_out) ((uint32_t*)(hit_out + k))[lane] = ((const uint32_t*)(hit + r))[lane];
 }
 
-int split_check(const bg_ctx* ctx, uint64_t n, uint32_t n_bins, const void* bin, const void* hit, const void* recs, const void* seq,
-                const void* seq_off, const void* qual, const void* qual_off, const void* recs_out, const void* seq_out, const void* seq_off_out,
-                const void* qual_out, const void* qual_off_out, const void* hit_out, const void* bin_off) {
-    if (n_bins == 0) return refuse("bg_fastq_demux_split: n_bins 0");
-    if (n_bins > BG_DMX_MAX_BINS) return refuse("bg_fastq_demux_split: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
-    if (!bin_off) return refuse("bg_fastq_demux_split: null bin_off");
-    if (!seq_off_out || !qual_off_out) return refuse("bg_fastq_demux_split: null output offsets");
-    if (hit_out && !hit) return refuse("bg_fastq_demux_split: hit_out without hit");
-    if (n && (!bin || !recs || !seq || !seq_off || !qual || !qual_off || !recs_out || !seq_out || !qual_out))
-        return refuse("bg_fastq_demux_split: null bin or column");
-    if (!ctx) return refuse("bg_fastq_demux_split: null ctx");
+int split_check(const bg_ctx* ctx, uint64_t n, uint32_t n_bins, const void* bin, const void* hit, const fq_cols_in& in, const fq_cols_out& out,
+                const void* hit_out, const void* bin_off) {
+    if (n_bins == 0) return bg_refuse("bg_fastq_demux_split: n_bins 0");
+    if (n_bins > BG_DMX_MAX_BINS) return bg_refuse("bg_fastq_demux_split: n_bins above BG_DMX_MAX_BINS", BG_ERR_TOO_LARGE);
+    if (!bin_off) return bg_refuse("bg_fastq_demux_split: null bin_off");
+    if (!out.offsets()) return bg_refuse("bg_fastq_demux_split: null output offsets");
+    if (hit_out && !hit) return bg_refuse("bg_fastq_demux_split: hit_out without hit");
+    if (n && (!bin || !in.complete() || !out.data())) return bg_refuse("bg_fastq_demux_split: null bin or column");
+    if (!ctx) return bg_refuse("bg_fastq_demux_split: null ctx");
     return BG_OK;
 }
-
-struct DmxDev {
-    void* p = nullptr;
-    ~DmxDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-};
 
 }  // namespace
 
@@ -222,22 +206,17 @@ extern "C" int bg_fastq_demux_assign(bg_ctx* ctx, uint64_t n, const bg_demux_par
                                      const uint32_t* pat_bin, uint32_t* bin, bg_alignment_t* hit_out, uint32_t* pat_out) {
     if (int rc = assign_check(ctx, n, params, hits, n_pat, pat_bin, bin, hit_out)) return rc;
     if (n == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DmxDev d_hits, d_bin, d_hit_out, d_pat;
-    const size_t hb = (size_t)n * n_pat * sizeof(bg_alignment_t), ob = (size_t)n * sizeof(bg_alignment_t);
-    for (auto pr : {std::pair<DmxDev*, size_t>{&d_hits, hb}, {&d_bin, (size_t)n * 4}, {&d_hit_out, ob}, {&d_pat, (size_t)n * 4}})
-        if (int rc = pr.first->alloc(pr.second)) return rc;
-    BG_HIP(hipMemcpyAsync(d_hits.p, hits, hb, hipMemcpyHostToDevice, st));
-    BG_HIP(hipStreamSynchronize(st));
-    if (int rc = bg_fastq_demux_assign_dev(ctx, n, params, (const bg_alignment_t*)d_hits.p, n_pat, pat_bin, (uint32_t*)d_bin.p,
-                                           (bg_alignment_t*)d_hit_out.p, pat_out ? (uint32_t*)d_pat.p : nullptr, st))
-        return rc;
-    BG_HIP(hipMemcpyAsync(bin, d_bin.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(hit_out, d_hit_out.p, ob, hipMemcpyDeviceToHost, st));
-    if (pat_out) BG_HIP(hipMemcpyAsync(pat_out, d_pat.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const bg_alignment_t* d_hits = s.up(hits, (size_t)n * n_pat);
+    uint32_t* d_bin = s.out<uint32_t>(n);
+    bg_alignment_t* d_hit_out = s.out<bg_alignment_t>(n);
+    uint32_t* d_pat = pat_out ? s.out<uint32_t>(n) : nullptr;
+    if (s.sync()) return s.rc;
+    if (int rc = bg_fastq_demux_assign_dev(ctx, n, params, d_hits, n_pat, pat_bin, d_bin, d_hit_out, d_pat, s.st)) return rc;
+    s.down(bin, d_bin, n);
+    s.down(hit_out, d_hit_out, n);
+    if (pat_out) s.down(pat_out, d_pat, n);
+    return s.sync();
 }
 
 extern "C" int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* d_bin, const bg_alignment_t* d_hit,
@@ -245,8 +224,8 @@ extern "C" int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins
                                         const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
                                         uint8_t* d_qual_out, uint64_t* d_qual_off_out, bg_alignment_t* d_hit_out, uint64_t* d_perm,
                                         uint64_t* d_bin_off, uint64_t* bin_off_host, void* stream) {
-    if (int rc = split_check(ctx, n, n_bins, d_bin, d_hit, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_recs_out, d_seq_out, d_seq_off_out,
-                             d_qual_out, d_qual_off_out, d_hit_out, d_bin_off))
+    if (int rc = split_check(ctx, n, n_bins, d_bin, d_hit, {d_recs, d_seq, d_seq_off, d_qual, d_qual_off},
+                             {d_recs_out, d_seq_out, d_seq_off_out, d_qual_out, d_qual_off_out}, d_hit_out, d_bin_off))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
@@ -295,44 +274,24 @@ extern "C" int bg_fastq_demux_split(bg_ctx* ctx, uint64_t n, uint32_t n_bins, co
                                     const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
                                     const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out,
                                     uint8_t* qual_out, uint64_t* qual_off_out, bg_alignment_t* hit_out, uint64_t* perm, uint64_t* bin_off) {
-    if (int rc = split_check(ctx, n, n_bins, bin, hit, recs, seq, seq_off, qual, qual_off, recs_out, seq_out, seq_off_out, qual_out,
-                             qual_off_out, hit_out, bin_off))
-        return rc;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    const fq_cols_in in = {recs, seq, seq_off, qual, qual_off};
+    const fq_cols_out out = {recs_out, seq_out, seq_off_out, qual_out, qual_off_out};
+    if (int rc = split_check(ctx, n, n_bins, bin, hit, in, out, hit_out, bin_off)) return rc;
     const uint64_t sb = n ? seq_off[n] : 0, qb = n ? qual_off[n] : 0;
-    DmxDev d_bin, d_hit, d_recs, d_seq, d_so, d_qual, d_qo, o_recs, o_seq, o_so, o_qual, o_qo, o_hit, o_perm, o_boff;
-    const size_t hb = hit ? (size_t)n * sizeof(bg_alignment_t) : 0, rb = (size_t)n * sizeof(bg_fastq_record_t), ob = (size_t)(n + 1) * 8,
-                 gb = (size_t)(n_bins + 3) * 8;
-    for (auto pr : {std::pair<DmxDev*, size_t>{&d_bin, (size_t)n * 4}, {&d_hit, hb}, {&d_recs, rb}, {&d_seq, sb}, {&d_so, ob}, {&d_qual, qb},
-                    {&d_qo, ob}, {&o_recs, rb}, {&o_seq, sb}, {&o_so, ob}, {&o_qual, qb}, {&o_qo, ob}, {&o_hit, hit_out ? hb : 0},
-                    {&o_perm, (size_t)n * 8}, {&o_boff, gb}})
-        if (int rc = pr.first->alloc(pr.second)) return rc;
-    if (n) {
-        BG_HIP(hipMemcpyAsync(d_bin.p, bin, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        if (hb) BG_HIP(hipMemcpyAsync(d_hit.p, hit, hb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_recs.p, recs, rb, hipMemcpyHostToDevice, st));
-        if (sb) BG_HIP(hipMemcpyAsync(d_seq.p, seq, sb, hipMemcpyHostToDevice, st));
-        if (qb) BG_HIP(hipMemcpyAsync(d_qual.p, qual, qb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_so.p, seq_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_qo.p, qual_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipStreamSynchronize(st));
-    }
-    if (int rc = bg_fastq_demux_split_dev(ctx, n, n_bins, (const uint32_t*)d_bin.p, hit ? (const bg_alignment_t*)d_hit.p : nullptr,
-                                          (const bg_fastq_record_t*)d_recs.p, (const uint8_t*)d_seq.p, (const uint64_t*)d_so.p,
-                                          (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p, (bg_fastq_record_t*)o_recs.p, (uint8_t*)o_seq.p,
-                                          (uint64_t*)o_so.p, (uint8_t*)o_qual.p, (uint64_t*)o_qo.p, hit_out ? (bg_alignment_t*)o_hit.p : nullptr,
-                                          (uint64_t*)o_perm.p, (uint64_t*)o_boff.p, bin_off, st))
+    bg_stage s(ctx, ctx->stream);
+    const uint32_t* d_bin = s.up(bin, n);
+    const bg_alignment_t* d_hit = hit ? s.up(hit, n) : nullptr;
+    const fq_cols_in d = fq_cols_upload(s, n, in);
+    const fq_cols_out o = fq_cols_alloc(s, n, sb, qb);
+    bg_alignment_t* d_hit_out = hit_out ? s.out<bg_alignment_t>(n) : nullptr;
+    uint64_t* d_perm = s.out<uint64_t>(n);
+    uint64_t* d_bin_off = s.out<uint64_t>((size_t)n_bins + 3);
+    if (s.sync()) return s.rc;
+    if (int rc = bg_fastq_demux_split_dev(ctx, n, n_bins, d_bin, d_hit, d.recs, d.seq, d.seq_off, d.qual, d.qual_off, o.recs, o.seq, o.seq_off,
+                                          o.qual, o.qual_off, d_hit_out, d_perm, d_bin_off, bin_off, s.st))
         return rc;
-    if (n) {
-        BG_HIP(hipMemcpyAsync(recs_out, o_recs.p, rb, hipMemcpyDeviceToHost, st));
-        if (sb) BG_HIP(hipMemcpyAsync(seq_out, o_seq.p, sb, hipMemcpyDeviceToHost, st));
-        if (qb) BG_HIP(hipMemcpyAsync(qual_out, o_qual.p, qb, hipMemcpyDeviceToHost, st));
-        if (hit_out) BG_HIP(hipMemcpyAsync(hit_out, o_hit.p, hb, hipMemcpyDeviceToHost, st));
-        if (perm) BG_HIP(hipMemcpyAsync(perm, o_perm.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    }
-    BG_HIP(hipMemcpyAsync(seq_off_out, o_so.p, ob, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(qual_off_out, o_qo.p, ob, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    fq_cols_download(s, out, o, n, sb, qb);
+    if (hit_out) s.down(hit_out, d_hit_out, n);
+    if (perm) s.down(perm, d_perm, n);
+    return s.sync();
 }

@@ -11,9 +11,10 @@
 // selects the other flavour that was measured, sam_emit.hip's write pass: the group gathers the line into LDS at the offset
 // inside a 16-byte granule that it has in the output and stores it with 16-byte stores between a byte head and a byte tail
 // (a line longer than the staging area goes straight to global memory).  DESIGN.md 4.8 has the measurements.
-#include <algorithm>
-
-#include "bg_common.h"
+//
+// The host flavours stage their arrays through a bg_stage: the filter its columns by fastq_cols.h, the writer as much of the
+// text and of the two byte columns as the written records reach into (fq_record_extents).
+#include "fastq_cols.h"
 #include "fastq_emit_rule.h"
 
 namespace {
@@ -83,40 +84,24 @@ __global__ __launch_bounds__(256) void fq_copy_kernel(uint64_t n, const uint8_t*
                    recs_out, seq_out, seq_off_out, qual_out, qual_off_out, lane, 16);
 }
 
-// every refusal says why (bg_last_error), so that each can be told from the others where no device is present
-int refuse(const char* why, int rc = BG_ERR_INVALID_ARG) {
-    bg_tls_error = why;
-    return rc;
-}
-
-int filter_check(const bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t* f, const void* hits, uint32_t n_pat, const void* recs, const void* seq,
-                 const void* seq_off, const void* qual, const void* qual_off, const void* recs_out, const void* seq_out,
-                 const void* seq_off_out, const void* qual_out, const void* qual_off_out) {
-    if (!f) return refuse("bg_fastq_filter: null filter");
+// every refusal says why (bg_refuse); device or host pointers alike
+int filter_check(const bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t* f, const void* hits, uint32_t n_pat, const fq_cols_in& in,
+                 const fq_cols_out& out) {
+    if (!f) return bg_refuse("bg_fastq_filter: null filter");
     const uint32_t known = BG_FQF_PAIRED | BG_FQF_PAIR_BOTH | BG_FQF_DISCARD_UNTRIMMED | BG_FQF_DISCARD_TRIMMED | BG_FQF_CHECK_OK;
     const uint32_t discard = f->flags & (BG_FQF_DISCARD_UNTRIMMED | BG_FQF_DISCARD_TRIMMED);
-    if (f->flags & ~known) return refuse("bg_fastq_filter: unknown flag bits");
-    if (discard == (BG_FQF_DISCARD_UNTRIMMED | BG_FQF_DISCARD_TRIMMED)) return refuse("bg_fastq_filter: both DISCARD flags");
-    if (n_pat > BG_MYERS_MAX_PATTERNS) return refuse("bg_fastq_filter: n_pat above BG_MYERS_MAX_PATTERNS", BG_ERR_TOO_LARGE);
-    if (discard && (!hits || n_pat == 0)) return refuse("bg_fastq_filter: a DISCARD flag without hits");
-    if ((f->flags & BG_FQF_PAIR_BOTH) && !(f->flags & BG_FQF_PAIRED)) return refuse("bg_fastq_filter: PAIR_BOTH without PAIRED");
-    if ((f->flags & BG_FQF_PAIRED) && (n & 1)) return refuse("bg_fastq_filter: PAIRED with an odd record count");
-    if (f->min_len > f->max_len) return refuse("bg_fastq_filter: min_len above max_len");
-    if (!seq_off_out || !qual_off_out) return refuse("bg_fastq_filter: null output offsets");
-    if (n && (!recs || !seq || !seq_off || !qual || !qual_off || !recs_out || !seq_out || !qual_out))
-        return refuse("bg_fastq_filter: null column");
-    if (!ctx) return refuse("bg_fastq_filter: null ctx");
+    if (f->flags & ~known) return bg_refuse("bg_fastq_filter: unknown flag bits");
+    if (discard == (BG_FQF_DISCARD_UNTRIMMED | BG_FQF_DISCARD_TRIMMED)) return bg_refuse("bg_fastq_filter: both DISCARD flags");
+    if (n_pat > BG_MYERS_MAX_PATTERNS) return bg_refuse("bg_fastq_filter: n_pat above BG_MYERS_MAX_PATTERNS", BG_ERR_TOO_LARGE);
+    if (discard && (!hits || n_pat == 0)) return bg_refuse("bg_fastq_filter: a DISCARD flag without hits");
+    if ((f->flags & BG_FQF_PAIR_BOTH) && !(f->flags & BG_FQF_PAIRED)) return bg_refuse("bg_fastq_filter: PAIR_BOTH without PAIRED");
+    if ((f->flags & BG_FQF_PAIRED) && (n & 1)) return bg_refuse("bg_fastq_filter: PAIRED with an odd record count");
+    if (f->min_len > f->max_len) return bg_refuse("bg_fastq_filter: min_len above max_len");
+    if (!out.offsets()) return bg_refuse("bg_fastq_filter: null output offsets");
+    if (n && (!in.complete() || !out.data())) return bg_refuse("bg_fastq_filter: null column");
+    if (!ctx) return bg_refuse("bg_fastq_filter: null ctx");
     return BG_OK;
 }
-
-struct FqDev {
-    void* p = nullptr;
-    ~FqDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-};
 
 // ---- emit ---------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kStage = 1024;            // bytes of a staged line
@@ -161,16 +146,14 @@ __global__ __launch_bounds__(256) void fq_emit_kernel(uint64_t m, uint64_t first
     if (staged) fq_line_flush(stage, line, len, lane, kLanes);
 }
 
-uint64_t emit_lines(uint64_t n, uint64_t first, uint64_t step) { return first < n ? (n - first - 1) / step + 1 : 0; }
-
 int emit_check(const bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, const void* text, const void* recs, const void* seq,
                const void* qual, const void* out, uint64_t out_cap, const void* out_off, uint64_t* out_bytes) {
-    if (!out_off || !out_bytes) return refuse("bg_fastq_emit: null out_off or out_bytes");
+    if (!out_off || !out_bytes) return bg_refuse("bg_fastq_emit: null out_off or out_bytes");
     *out_bytes = 0;
-    if (step == 0) return refuse("bg_fastq_emit: step 0");
-    if (!out && out_cap) return refuse("bg_fastq_emit: null out with a capacity");
-    if (emit_lines(n, first, step) && (!text || !recs || !seq || !qual)) return refuse("bg_fastq_emit: null text, recs, seq or qual");
-    if (!ctx) return refuse("bg_fastq_emit: null ctx");
+    if (step == 0) return bg_refuse("bg_fastq_emit: step 0");
+    if (!out && out_cap) return bg_refuse("bg_fastq_emit: null out with a capacity");
+    if (fq_strided_count(n, first, step) && (!text || !recs || !seq || !qual)) return bg_refuse("bg_fastq_emit: null text, recs, seq or qual");
+    if (!ctx) return bg_refuse("bg_fastq_emit: null ctx");
     return BG_OK;
 }
 
@@ -180,8 +163,8 @@ extern "C" int bg_fastq_filter_dev(bg_ctx* ctx, uint64_t n, const bg_fastq_filte
                                    const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
                                    const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
                                    uint8_t* d_qual_out, uint64_t* d_qual_off_out, uint8_t* d_keep, uint64_t* totals, void* stream) {
-    if (int rc = filter_check(ctx, n, flt, d_hits, n_pat, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_recs_out, d_seq_out, d_seq_off_out,
-                              d_qual_out, d_qual_off_out))
+    if (int rc = filter_check(ctx, n, flt, d_hits, n_pat, {d_recs, d_seq, d_seq_off, d_qual, d_qual_off},
+                              {d_recs_out, d_seq_out, d_seq_off_out, d_qual_out, d_qual_off_out}))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
@@ -231,40 +214,22 @@ extern "C" int bg_fastq_filter(bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t*
                                const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
                                const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out,
                                uint8_t* qual_out, uint64_t* qual_off_out, uint8_t* keep, uint64_t* totals) {
-    if (int rc = filter_check(ctx, n, flt, hits, n_pat, recs, seq, seq_off, qual, qual_off, recs_out, seq_out, seq_off_out, qual_out,
-                              qual_off_out))
-        return rc;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const uint64_t sb = n ? seq_off[n] : 0, qb = n ? qual_off[n] : 0;
-    FqDev d_hits, d_recs, d_seq, d_so, d_qual, d_qo, o_recs, o_seq, o_so, o_qual, o_qo, o_keep;
-    const size_t hb = hits ? (size_t)n * n_pat * sizeof(bg_alignment_t) : 0, rb = (size_t)n * sizeof(bg_fastq_record_t),
-                 ob = (size_t)(n + 1) * 8;
-    for (auto pr : {std::pair<FqDev*, size_t>{&d_hits, hb}, {&d_recs, rb}, {&d_seq, sb}, {&d_so, ob}, {&d_qual, qb}, {&d_qo, ob},
-                    {&o_recs, rb}, {&o_seq, sb}, {&o_so, ob}, {&o_qual, qb}, {&o_qo, ob}, {&o_keep, (size_t)n}})
-        if (int rc = pr.first->alloc(pr.second)) return rc;
-    if (n) {
-        if (hb) BG_HIP(hipMemcpyAsync(d_hits.p, hits, hb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_recs.p, recs, rb, hipMemcpyHostToDevice, st));
-        if (sb) BG_HIP(hipMemcpyAsync(d_seq.p, seq, sb, hipMemcpyHostToDevice, st));
-        if (qb) BG_HIP(hipMemcpyAsync(d_qual.p, qual, qb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_so.p, seq_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_qo.p, qual_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipStreamSynchronize(st));
-    }
+    const fq_cols_in in = {recs, seq, seq_off, qual, qual_off};
+    const fq_cols_out out = {recs_out, seq_out, seq_off_out, qual_out, qual_off_out};
+    if (int rc = filter_check(ctx, n, flt, hits, n_pat, in, out)) return rc;
+    bg_stage s(ctx, ctx->stream);
+    const bg_alignment_t* d_hits = hits ? s.up(hits, (size_t)n * n_pat) : nullptr;
+    const fq_cols_in d = fq_cols_upload(s, n, in);
+    const fq_cols_out o = fq_cols_alloc(s, n, n ? seq_off[n] : 0, n ? qual_off[n] : 0);
+    uint8_t* d_keep = s.out<uint8_t>(n);
+    if (s.sync()) return s.rc;
     uint64_t tot[3] = {0, 0, 0};
-    if (int rc = bg_fastq_filter_dev(ctx, n, flt, hits ? (const bg_alignment_t*)d_hits.p : nullptr, n_pat, (const bg_fastq_record_t*)d_recs.p,
-                                     (const uint8_t*)d_seq.p, (const uint64_t*)d_so.p, (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p,
-                                     (bg_fastq_record_t*)o_recs.p, (uint8_t*)o_seq.p, (uint64_t*)o_so.p, (uint8_t*)o_qual.p,
-                                     (uint64_t*)o_qo.p, (uint8_t*)o_keep.p, tot, st))
+    if (int rc = bg_fastq_filter_dev(ctx, n, flt, d_hits, n_pat, d.recs, d.seq, d.seq_off, d.qual, d.qual_off, o.recs, o.seq, o.seq_off, o.qual,
+                                     o.qual_off, d_keep, tot, s.st))
         return rc;
-    if (tot[0]) BG_HIP(hipMemcpyAsync(recs_out, o_recs.p, (size_t)tot[0] * sizeof(bg_fastq_record_t), hipMemcpyDeviceToHost, st));
-    if (tot[1]) BG_HIP(hipMemcpyAsync(seq_out, o_seq.p, tot[1], hipMemcpyDeviceToHost, st));
-    if (tot[2]) BG_HIP(hipMemcpyAsync(qual_out, o_qual.p, tot[2], hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(seq_off_out, o_so.p, (size_t)(tot[0] + 1) * 8, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(qual_off_out, o_qo.p, (size_t)(tot[0] + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (keep && n) BG_HIP(hipMemcpyAsync(keep, o_keep.p, n, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
+    fq_cols_download(s, out, o, tot[0], tot[1], tot[2]);
+    if (keep) s.down(keep, d_keep, n);
+    if (s.sync()) return s.rc;
     if (totals) std::copy(tot, tot + 3, totals);
     return BG_OK;
 }
@@ -275,7 +240,7 @@ extern "C" int bg_fastq_emit_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64
     if (int rc = emit_check(ctx, n, first, step, d_fastq_text, d_recs, d_seq, d_qual, d_out, out_cap, d_out_off, out_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
-    const uint64_t m = emit_lines(n, first, step);
+    const uint64_t m = fq_strided_count(n, first, step);
     if (m == 0) {
         BG_HIP(hipMemsetAsync(d_out_off, 0, 8, st));
         BG_HIP(hipStreamSynchronize(st));
@@ -309,33 +274,20 @@ extern "C" int bg_fastq_emit(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t s
                              uint64_t* out_off, uint64_t* out_bytes) {
     if (int rc = emit_check(ctx, n, first, step, fastq_text, recs, seq, qual, out, out_cap, out_off, out_bytes)) return rc;
     out_off[0] = 0;
-    const uint64_t m = emit_lines(n, first, step);
+    const uint64_t m = fq_strided_count(n, first, step);
     if (m == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // the buffers the written records point into end where the last of them ends
-    uint64_t fq_bytes = 0, seq_bytes = 0, qual_bytes = 0;
-    for (uint64_t r = first; r < n; r += step) {
-        fq_bytes = std::max<uint64_t>(fq_bytes, recs[r].id_off + recs[r].id_len);
-        if (recs[r].has_desc) fq_bytes = std::max<uint64_t>(fq_bytes, recs[r].desc_off + recs[r].desc_len);
-        seq_bytes = std::max<uint64_t>(seq_bytes, recs[r].seq_off + recs[r].seq_len);
-        qual_bytes = std::max<uint64_t>(qual_bytes, recs[r].qual_off + recs[r].qual_len);
-        if (n - r <= step) break;  // r + step would pass n (or wrap)
-    }
-    FqDev d_fq, d_recs, d_seq, d_qual, d_off, d_out;
-    const size_t rb = (size_t)n * sizeof(bg_fastq_record_t), ob = (size_t)(m + 1) * 8;
-    for (auto pr : {std::pair<FqDev*, size_t>{&d_fq, fq_bytes}, {&d_recs, rb}, {&d_seq, seq_bytes}, {&d_qual, qual_bytes}, {&d_off, ob},
-                    {&d_out, out ? (size_t)out_cap : 0}})
-        if (int rc = pr.first->alloc(pr.second)) return rc;
-    if (fq_bytes) BG_HIP(hipMemcpyAsync(d_fq.p, fastq_text, fq_bytes, hipMemcpyHostToDevice, st));
-    BG_HIP(hipMemcpyAsync(d_recs.p, recs, rb, hipMemcpyHostToDevice, st));
-    if (seq_bytes) BG_HIP(hipMemcpyAsync(d_seq.p, seq, seq_bytes, hipMemcpyHostToDevice, st));
-    if (qual_bytes) BG_HIP(hipMemcpyAsync(d_qual.p, qual, qual_bytes, hipMemcpyHostToDevice, st));
-    const int rc = bg_fastq_emit_dev(ctx, n, first, step, (const uint8_t*)d_fq.p, (const bg_fastq_record_t*)d_recs.p, (const uint8_t*)d_seq.p,
-                                     (const uint8_t*)d_qual.p, out ? (char*)d_out.p : nullptr, out_cap, (uint64_t*)d_off.p, out_bytes, st);
+    const fq_extents e = fq_record_extents(recs, n, first, step);  // as much of the three buffers as the written records reach into
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_fq = s.up(fastq_text, std::max(e.id, e.desc));
+    const bg_fastq_record_t* d_recs = s.up(recs, n);
+    const uint8_t* d_seq = s.up(seq, e.seq);
+    const uint8_t* d_qual = s.up(qual, e.qual);
+    uint64_t* d_off = s.out<uint64_t>(m + 1);
+    char* d_out = out ? s.out<char>(out_cap) : nullptr;
+    if (s.rc) return s.rc;
+    const int rc = bg_fastq_emit_dev(ctx, n, first, step, d_fq, d_recs, d_seq, d_qual, d_out, out_cap, d_off, out_bytes, s.st);
     if (rc && rc != BG_ERR_OPS_CAP) return rc;
-    BG_HIP(hipMemcpyAsync(out_off, d_off.p, ob, hipMemcpyDeviceToHost, st));
-    if (!rc && out && *out_bytes) BG_HIP(hipMemcpyAsync(out, d_out.p, *out_bytes, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return rc;
+    s.down(out_off, d_off, m + 1);
+    if (!rc && out) s.down(out, d_out, *out_bytes);
+    return s.sync() ? s.rc : rc;
 }

@@ -21,17 +21,12 @@
 // Overflow: every counter kept in LDS grows by at most 1 per read (a read has one symbol per position below max_cycles,
 // one length and one mean), and the grid is chosen so that a block takes fewer than 2^32 reads; the collecting row, which
 // a long read hits many times, is never kept in LDS.  Ordinary vector atomics only.
-#include <algorithm>
-
-#include "bg_common.h"
+//
+// The host flavours make their device copies through a bg_stage.
+#include "fastq_cols.h"
 #include "fastq_qual_rule.h"
 
 namespace {
-
-int refuse(const char* why, int rc = BG_ERR_INVALID_ARG) {
-    bg_tls_error = why;
-    return rc;
-}
 
 constexpr uint32_t kGroupsPerBlock = 256 / QL_G;
 constexpr uint32_t kMaxBlocks = 8192;
@@ -143,16 +138,16 @@ __global__ __launch_bounds__(256) void ql_cut_kernel(uint64_t n, uint64_t iters,
 }
 
 int cut_check(const bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* p, const void* qual, const void* qual_off, const void* cut_out) {
-    if (!p) return refuse("bg_fastq_qual_cut: null params");
-    if (p->method_5p == BG_QCUT_WINDOW) return refuse("bg_fastq_qual_cut: WINDOW as method_5p");
-    if (p->method_5p != BG_QCUT_NONE && p->method_5p != BG_QCUT_RUNSUM) return refuse("bg_fastq_qual_cut: unknown method");
+    if (!p) return bg_refuse("bg_fastq_qual_cut: null params");
+    if (p->method_5p == BG_QCUT_WINDOW) return bg_refuse("bg_fastq_qual_cut: WINDOW as method_5p");
+    if (p->method_5p != BG_QCUT_NONE && p->method_5p != BG_QCUT_RUNSUM) return bg_refuse("bg_fastq_qual_cut: unknown method");
     if (p->method_3p != BG_QCUT_NONE && p->method_3p != BG_QCUT_RUNSUM && p->method_3p != BG_QCUT_WINDOW)
-        return refuse("bg_fastq_qual_cut: unknown method");
-    if (p->method_3p == BG_QCUT_WINDOW && p->window == 0) return refuse("bg_fastq_qual_cut: window 0 with WINDOW");
-    if (p->phred_offset > 255) return refuse("bg_fastq_qual_cut: phred_offset above 255");
-    if (!qual_off) return refuse("bg_fastq_qual_cut: null qual_off");
-    if (n && (!qual || !cut_out)) return refuse("bg_fastq_qual_cut: null qual or cut_out");
-    if (!ctx) return refuse("bg_fastq_qual_cut: null ctx");
+        return bg_refuse("bg_fastq_qual_cut: unknown method");
+    if (p->method_3p == BG_QCUT_WINDOW && p->window == 0) return bg_refuse("bg_fastq_qual_cut: window 0 with WINDOW");
+    if (p->phred_offset > 255) return bg_refuse("bg_fastq_qual_cut: phred_offset above 255");
+    if (!qual_off) return bg_refuse("bg_fastq_qual_cut: null qual_off");
+    if (n && (!qual || !cut_out)) return bg_refuse("bg_fastq_qual_cut: null qual or cut_out");
+    if (!ctx) return bg_refuse("bg_fastq_qual_cut: null ctx");
     return BG_OK;
 }
 
@@ -203,16 +198,16 @@ __global__ __launch_bounds__(256) void ql_select_kernel(uint64_t n, uint64_t ite
 
 int select_check(const bg_ctx* ctx, uint64_t n, const bg_qual_select_t* p, const void* qual, const void* qual_off, const void* stats_out,
                  const void* bin_out) {
-    if (!p) return refuse("bg_fastq_qual_select: null params");
-    if (p->flags & ~(uint32_t)(BG_QSEL_PAIRED | BG_QSEL_PAIR_BOTH)) return refuse("bg_fastq_qual_select: unknown flag bits");
-    if ((p->flags & BG_QSEL_PAIR_BOTH) && !(p->flags & BG_QSEL_PAIRED)) return refuse("bg_fastq_qual_select: PAIR_BOTH without PAIRED");
-    if ((p->flags & BG_QSEL_PAIRED) && (n & 1)) return refuse("bg_fastq_qual_select: PAIRED with an odd record count");
-    if (p->phred_offset > 255) return refuse("bg_fastq_qual_select: phred_offset above 255");
-    if (p->_reserved != 0) return refuse("bg_fastq_qual_select: non-zero _reserved");
-    if (!qual_off) return refuse("bg_fastq_qual_select: null qual_off");
-    if (n && !qual) return refuse("bg_fastq_qual_select: null qual");
-    if (n && !stats_out && !bin_out) return refuse("bg_fastq_qual_select: both outputs null");
-    if (!ctx) return refuse("bg_fastq_qual_select: null ctx");
+    if (!p) return bg_refuse("bg_fastq_qual_select: null params");
+    if (p->flags & ~(uint32_t)(BG_QSEL_PAIRED | BG_QSEL_PAIR_BOTH)) return bg_refuse("bg_fastq_qual_select: unknown flag bits");
+    if ((p->flags & BG_QSEL_PAIR_BOTH) && !(p->flags & BG_QSEL_PAIRED)) return bg_refuse("bg_fastq_qual_select: PAIR_BOTH without PAIRED");
+    if ((p->flags & BG_QSEL_PAIRED) && (n & 1)) return bg_refuse("bg_fastq_qual_select: PAIRED with an odd record count");
+    if (p->phred_offset > 255) return bg_refuse("bg_fastq_qual_select: phred_offset above 255");
+    if (p->_reserved != 0) return bg_refuse("bg_fastq_qual_select: non-zero _reserved");
+    if (!qual_off) return bg_refuse("bg_fastq_qual_select: null qual_off");
+    if (n && !qual) return bg_refuse("bg_fastq_qual_select: null qual");
+    if (n && !stats_out && !bin_out) return bg_refuse("bg_fastq_qual_select: both outputs null");
+    if (!ctx) return bg_refuse("bg_fastq_qual_select: null ctx");
     return BG_OK;
 }
 
@@ -299,33 +294,17 @@ __global__ __launch_bounds__(kTabThreads) void ql_tables_kernel(uint64_t m, uint
     if (threadIdx.x == 0 && s_reads) add64(tables + ql_tab_reads(max_cycles), s_reads);
 }
 
-uint64_t selected(uint64_t n, uint64_t first, uint64_t step) { return first < n ? (n - first - 1) / step + 1 : 0; }
-
 int tables_check(const bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, uint32_t phred_offset, uint32_t max_cycles, const void* seq,
                  const void* seq_off, const void* qual, const void* qual_off, const void* tables) {
-    if (step == 0) return refuse("bg_fastq_qc_tables: step 0");
-    if (max_cycles == 0 || max_cycles > BG_QC_MAX_CYCLES) return refuse("bg_fastq_qc_tables: max_cycles outside 1 .. BG_QC_MAX_CYCLES");
-    if (phred_offset > 255) return refuse("bg_fastq_qc_tables: phred_offset above 255");
-    if (!tables) return refuse("bg_fastq_qc_tables: null tables");
-    if (!seq_off || !qual_off) return refuse("bg_fastq_qc_tables: null offsets");
-    if (selected(n, first, step) && (!seq || !qual)) return refuse("bg_fastq_qc_tables: null seq or qual");
-    if (!ctx) return refuse("bg_fastq_qc_tables: null ctx");
+    if (step == 0) return bg_refuse("bg_fastq_qc_tables: step 0");
+    if (max_cycles == 0 || max_cycles > BG_QC_MAX_CYCLES) return bg_refuse("bg_fastq_qc_tables: max_cycles outside 1 .. BG_QC_MAX_CYCLES");
+    if (phred_offset > 255) return bg_refuse("bg_fastq_qc_tables: phred_offset above 255");
+    if (!tables) return bg_refuse("bg_fastq_qc_tables: null tables");
+    if (!seq_off || !qual_off) return bg_refuse("bg_fastq_qc_tables: null offsets");
+    if (fq_strided_count(n, first, step) && (!seq || !qual)) return bg_refuse("bg_fastq_qc_tables: null seq or qual");
+    if (!ctx) return bg_refuse("bg_fastq_qc_tables: null ctx");
     return BG_OK;
 }
-
-struct QualDev {
-    void* p = nullptr;
-    ~QualDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-    int upload(const void* src, size_t bytes, hipStream_t st) {
-        if (int rc = alloc(bytes)) return rc;
-        if (bytes) BG_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st));
-        return BG_OK;
-    }
-};
 
 // blocks and rounds of a kernel that gives 16 lanes to each of `items` reads
 void shape(uint64_t items, uint32_t max_blocks, uint32_t* blocks, uint64_t* iters, uint32_t per_block = kGroupsPerBlock) {
@@ -369,18 +348,14 @@ extern "C" int bg_fastq_qual_cut(bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* p
     if (int rc = cut_check(ctx, n, params, qual, qual_off, cut_out)) return rc;
     if (totals) totals[0] = totals[1] = 0;
     if (n == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QualDev d_qual, d_qo, d_cut;
-    if (int rc = d_qual.upload(qual, qual_off[n], st)) return rc;
-    if (int rc = d_qo.upload(qual_off, (size_t)(n + 1) * 8, st)) return rc;
-    if (int rc = d_cut.alloc((size_t)n * sizeof(bg_alignment_t))) return rc;
-    BG_HIP(hipStreamSynchronize(st));
-    if (int rc = bg_fastq_qual_cut_dev(ctx, n, params, (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p, (bg_alignment_t*)d_cut.p, totals, st))
-        return rc;
-    BG_HIP(hipMemcpyAsync(cut_out, d_cut.p, (size_t)n * sizeof(bg_alignment_t), hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_qual = s.up(qual, qual_off[n]);
+    const uint64_t* d_qo = s.up(qual_off, (size_t)n + 1);
+    bg_alignment_t* d_cut = s.out<bg_alignment_t>(n);
+    if (s.sync()) return s.rc;
+    if (int rc = bg_fastq_qual_cut_dev(ctx, n, params, d_qual, d_qo, d_cut, totals, s.st)) return rc;
+    s.down(cut_out, d_cut, n);
+    return s.sync();
 }
 
 extern "C" int bg_fastq_qual_select_dev(bg_ctx* ctx, uint64_t n, const bg_qual_select_t* params, const uint32_t* weight, const uint8_t* d_qual,
@@ -421,21 +396,16 @@ extern "C" int bg_fastq_qual_select(bg_ctx* ctx, uint64_t n, const bg_qual_selec
     if (int rc = select_check(ctx, n, params, qual, qual_off, stats_out, bin_out)) return rc;
     if (totals) totals[0] = 0;
     if (n == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QualDev d_qual, d_qo, d_stats, d_bin;
-    if (int rc = d_qual.upload(qual, qual_off[n], st)) return rc;
-    if (int rc = d_qo.upload(qual_off, (size_t)(n + 1) * 8, st)) return rc;
-    if (int rc = d_stats.alloc((size_t)n * sizeof(bg_qual_stats_t))) return rc;
-    if (int rc = d_bin.alloc((size_t)n * 4)) return rc;
-    BG_HIP(hipStreamSynchronize(st));
-    if (int rc = bg_fastq_qual_select_dev(ctx, n, params, weight, (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p,
-                                          stats_out ? (bg_qual_stats_t*)d_stats.p : nullptr, bin_out ? (uint32_t*)d_bin.p : nullptr, totals, st))
-        return rc;
-    if (stats_out) BG_HIP(hipMemcpyAsync(stats_out, d_stats.p, (size_t)n * sizeof(bg_qual_stats_t), hipMemcpyDeviceToHost, st));
-    if (bin_out) BG_HIP(hipMemcpyAsync(bin_out, d_bin.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_qual = s.up(qual, qual_off[n]);
+    const uint64_t* d_qo = s.up(qual_off, (size_t)n + 1);
+    bg_qual_stats_t* d_stats = stats_out ? s.out<bg_qual_stats_t>(n) : nullptr;
+    uint32_t* d_bin = bin_out ? s.out<uint32_t>(n) : nullptr;
+    if (s.sync()) return s.rc;
+    if (int rc = bg_fastq_qual_select_dev(ctx, n, params, weight, d_qual, d_qo, d_stats, d_bin, totals, s.st)) return rc;
+    if (stats_out) s.down(stats_out, d_stats, n);
+    if (bin_out) s.down(bin_out, d_bin, n);
+    return s.sync();
 }
 
 extern "C" int bg_fastq_qc_tables_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, uint32_t phred_offset, uint32_t max_cycles,
@@ -445,7 +415,7 @@ extern "C" int bg_fastq_qc_tables_dev(bg_ctx* ctx, uint64_t n, uint64_t first, u
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
     BG_HIP(hipMemsetAsync(d_tables, 0, ql_tab_words(max_cycles) * 8, st));
-    const uint64_t m = selected(n, first, step);
+    const uint64_t m = fq_strided_count(n, first, step);
     if (m == 0) return BG_OK;
     uint32_t blocks;
     uint64_t iters;
@@ -463,19 +433,14 @@ extern "C" int bg_fastq_qc_tables_dev(bg_ctx* ctx, uint64_t n, uint64_t first, u
 extern "C" int bg_fastq_qc_tables(bg_ctx* ctx, uint64_t n, uint64_t first, uint64_t step, uint32_t phred_offset, uint32_t max_cycles,
                                   const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual, const uint64_t* qual_off, uint64_t* tables) {
     if (int rc = tables_check(ctx, n, first, step, phred_offset, max_cycles, seq, seq_off, qual, qual_off, tables)) return rc;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QualDev d_seq, d_so, d_qual, d_qo, d_tab;
-    if (int rc = d_seq.upload(seq, n ? seq_off[n] : 0, st)) return rc;
-    if (int rc = d_so.upload(seq_off, (size_t)(n + 1) * 8, st)) return rc;
-    if (int rc = d_qual.upload(qual, n ? qual_off[n] : 0, st)) return rc;
-    if (int rc = d_qo.upload(qual_off, (size_t)(n + 1) * 8, st)) return rc;
-    if (int rc = d_tab.alloc(ql_tab_words(max_cycles) * 8)) return rc;
-    BG_HIP(hipStreamSynchronize(st));
-    if (int rc = bg_fastq_qc_tables_dev(ctx, n, first, step, phred_offset, max_cycles, (const uint8_t*)d_seq.p, (const uint64_t*)d_so.p,
-                                        (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p, (uint64_t*)d_tab.p, st))
-        return rc;
-    BG_HIP(hipMemcpyAsync(tables, d_tab.p, ql_tab_words(max_cycles) * 8, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_seq = s.up(seq, n ? seq_off[n] : 0);
+    const uint64_t* d_so = s.up(seq_off, (size_t)n + 1);
+    const uint8_t* d_qual = s.up(qual, n ? qual_off[n] : 0);
+    const uint64_t* d_qo = s.up(qual_off, (size_t)n + 1);
+    uint64_t* d_tab = s.out<uint64_t>(ql_tab_words(max_cycles));
+    if (s.sync()) return s.rc;
+    if (int rc = bg_fastq_qc_tables_dev(ctx, n, first, step, phred_offset, max_cycles, d_seq, d_so, d_qual, d_qo, d_tab, s.st)) return rc;
+    s.down(tables, d_tab, ql_tab_words(max_cycles));
+    return s.sync();
 }

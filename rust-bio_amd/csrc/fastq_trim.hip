@@ -1,8 +1,9 @@
 // bg_fastq_trim[_dev]: cut adapters off parsed FASTQ records by the hits of bg_myers_best_batch[_dev] without a host
 // round trip (include/biogpu.h has the rule; rust-bio has no trimmer).  Three steps on the stream: the kept range and
 // the two lengths of every read (one lane per read), the shared exclusive scan (scan.hip) of the sequence and of the
-// quality lengths into the output offsets, and the copy (16 lanes per read; lane 0 writes the record).
-#include "bg_common.h"
+// quality lengths into the output offsets, and the copy (16 lanes per read; lane 0 writes the record).  The host flavour
+// stages its columns through fastq_cols.h.
+#include "fastq_cols.h"
 
 namespace {
 
@@ -61,14 +62,14 @@ __global__ __launch_bounds__(256) void trim_copy_kernel(uint64_t n, const bg_fas
     }
 }
 
-struct TrimDev {
-    void* p = nullptr;
-    ~TrimDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-};
+// what both entry points refuse, device or host pointers alike; the codes carry no message
+int trim_check(const bg_ctx* ctx, uint64_t n, int mode, const void* hits, uint32_t n_pat, const fq_cols_in& in, const fq_cols_out& out) {
+    if (mode != BG_TRIM_3P && mode != BG_TRIM_5P) return BG_ERR_INVALID_ARG;
+    if (n_pat == 0 || n_pat > BG_MYERS_MAX_PATTERNS) return n_pat ? BG_ERR_TOO_LARGE : BG_ERR_INVALID_ARG;
+    if (!ctx || !out.offsets()) return BG_ERR_INVALID_ARG;
+    if (n && (!hits || !in.complete() || !out.data())) return BG_ERR_INVALID_ARG;
+    return BG_OK;
+}
 
 }  // namespace
 
@@ -77,11 +78,9 @@ extern "C" int bg_fastq_trim_dev(bg_ctx* ctx, uint64_t n, int mode, const bg_ali
                                  const uint8_t* d_qual, const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out,
                                  uint8_t* d_seq_out, uint64_t* d_seq_off_out, uint8_t* d_qual_out, uint64_t* d_qual_off_out,
                                  uint64_t* totals, void* stream) {
-    if (mode != BG_TRIM_3P && mode != BG_TRIM_5P) return BG_ERR_INVALID_ARG;
-    if (n_pat == 0 || n_pat > BG_MYERS_MAX_PATTERNS) return n_pat ? BG_ERR_TOO_LARGE : BG_ERR_INVALID_ARG;
-    if (!ctx || !d_seq_off_out || !d_qual_off_out) return BG_ERR_INVALID_ARG;
-    if (n && (!d_hits || !d_recs || !d_seq || !d_seq_off || !d_qual || !d_qual_off || !d_recs_out || !d_seq_out || !d_qual_out))
-        return BG_ERR_INVALID_ARG;
+    if (int rc = trim_check(ctx, n, mode, d_hits, n_pat, {d_recs, d_seq, d_seq_off, d_qual, d_qual_off},
+                            {d_recs_out, d_seq_out, d_seq_off_out, d_qual_out, d_qual_off_out}))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);
@@ -117,39 +116,20 @@ extern "C" int bg_fastq_trim(bg_ctx* ctx, uint64_t n, int mode, const bg_alignme
                              const bg_fastq_record_t* recs, const uint8_t* seq, const uint64_t* seq_off, const uint8_t* qual,
                              const uint64_t* qual_off, bg_fastq_record_t* recs_out, uint8_t* seq_out, uint64_t* seq_off_out,
                              uint8_t* qual_out, uint64_t* qual_off_out, uint64_t* totals) {
-    if (mode != BG_TRIM_3P && mode != BG_TRIM_5P) return BG_ERR_INVALID_ARG;
-    if (n_pat == 0 || n_pat > BG_MYERS_MAX_PATTERNS) return n_pat ? BG_ERR_TOO_LARGE : BG_ERR_INVALID_ARG;
-    if (!ctx || !seq_off_out || !qual_off_out) return BG_ERR_INVALID_ARG;
-    if (n && (!hits || !recs || !seq || !seq_off || !qual || !qual_off || !recs_out || !seq_out || !qual_out)) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const uint64_t sb = n ? seq_off[n] : 0, qb = n ? qual_off[n] : 0;
-    TrimDev d_hits, d_recs, d_seq, d_so, d_qual, d_qo, o_recs, o_seq, o_so, o_qual, o_qo;
-    const size_t hb = (size_t)n * n_pat * sizeof(bg_alignment_t), rb = (size_t)n * sizeof(bg_fastq_record_t), ob = (size_t)(n + 1) * 8;
-    for (auto pr : {std::pair<TrimDev*, size_t>{&d_hits, hb}, {&d_recs, rb}, {&d_seq, sb}, {&d_so, ob}, {&d_qual, qb}, {&d_qo, ob},
-                    {&o_recs, rb}, {&o_seq, sb}, {&o_so, ob}, {&o_qual, qb}, {&o_qo, ob}})
-        if (int rc = pr.first->alloc(pr.second)) return rc;
-    if (n) {
-        BG_HIP(hipMemcpyAsync(d_hits.p, hits, hb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_recs.p, recs, rb, hipMemcpyHostToDevice, st));
-        if (sb) BG_HIP(hipMemcpyAsync(d_seq.p, seq, sb, hipMemcpyHostToDevice, st));
-        if (qb) BG_HIP(hipMemcpyAsync(d_qual.p, qual, qb, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_so.p, seq_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_qo.p, qual_off, ob, hipMemcpyHostToDevice, st));
-        BG_HIP(hipStreamSynchronize(st));
-    }
+    const fq_cols_in in = {recs, seq, seq_off, qual, qual_off};
+    const fq_cols_out out = {recs_out, seq_out, seq_off_out, qual_out, qual_off_out};
+    if (int rc = trim_check(ctx, n, mode, hits, n_pat, in, out)) return rc;
+    bg_stage s(ctx, ctx->stream);
+    const bg_alignment_t* d_hits = s.up(hits, (size_t)n * n_pat);
+    const fq_cols_in d = fq_cols_upload(s, n, in);
+    const fq_cols_out o = fq_cols_alloc(s, n, n ? seq_off[n] : 0, n ? qual_off[n] : 0);
+    if (s.sync()) return s.rc;
     uint64_t tot[2] = {0, 0};
-    if (int rc = bg_fastq_trim_dev(ctx, n, mode, (const bg_alignment_t*)d_hits.p, n_pat, (const bg_fastq_record_t*)d_recs.p,
-                                   (const uint8_t*)d_seq.p, (const uint64_t*)d_so.p, (const uint8_t*)d_qual.p, (const uint64_t*)d_qo.p,
-                                   (bg_fastq_record_t*)o_recs.p, (uint8_t*)o_seq.p, (uint64_t*)o_so.p, (uint8_t*)o_qual.p,
-                                   (uint64_t*)o_qo.p, tot, st))
+    if (int rc = bg_fastq_trim_dev(ctx, n, mode, d_hits, n_pat, d.recs, d.seq, d.seq_off, d.qual, d.qual_off, o.recs, o.seq, o.seq_off, o.qual,
+                                   o.qual_off, tot, s.st))
         return rc;
-    if (n) BG_HIP(hipMemcpyAsync(recs_out, o_recs.p, rb, hipMemcpyDeviceToHost, st));
-    if (tot[0]) BG_HIP(hipMemcpyAsync(seq_out, o_seq.p, tot[0], hipMemcpyDeviceToHost, st));
-    if (tot[1]) BG_HIP(hipMemcpyAsync(qual_out, o_qual.p, tot[1], hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(seq_off_out, o_so.p, ob, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(qual_off_out, o_qo.p, ob, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
+    fq_cols_download(s, out, o, n, tot[0], tot[1]);
+    if (s.sync()) return s.rc;
     if (totals) {
         totals[0] = tot[0];
         totals[1] = tot[1];

@@ -688,39 +688,21 @@ int smems_host(bg_fm* fm, bool out64, int all, uint64_t n_p, const uint8_t* pat,
     if (!fm || (n_p && (!pat_off || !count || (cap && !out))) || (!all && n_p && !i_pos)) return BG_ERR_INVALID_ARG;
     if (n_p == 0) return BG_OK;
     const size_t rec = out64 ? 48 : 24;
-    bg_ctx* ctx = fm->ctx;
-    BG_HIP(hipSetDevice(ctx->device));
     uint64_t max_len = 0;
     for (uint64_t q = 0; q < n_p; q++) max_len = std::max(max_len, pat_off[q + 1] - pat_off[q]);
-    const uint64_t pat_bytes = pat_off[n_p];
-    uint8_t* d_pat = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t *d_i = nullptr, *d_cnt = nullptr;
-    void* d_out = nullptr;
-    auto run = [&]() -> int {
-        BG_HIP(hipMalloc((void**)&d_pat, std::max<uint64_t>(pat_bytes, 16)));
-        BG_HIP(hipMalloc((void**)&d_off, (n_p + 1) * 8));
-        BG_HIP(hipMalloc((void**)&d_i, n_p * 4));
-        BG_HIP(hipMalloc((void**)&d_cnt, n_p * 4));
-        BG_HIP(hipMalloc(&d_out, std::max<uint64_t>(n_p * (uint64_t)cap * rec, 16)));
-        hipStream_t st = ctx->stream;
-        if (pat_bytes) BG_HIP(hipMemcpyAsync(d_pat, pat, pat_bytes, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_off, pat_off, (n_p + 1) * 8, hipMemcpyHostToDevice, st));
-        if (i_pos) BG_HIP(hipMemcpyAsync(d_i, i_pos, n_p * 4, hipMemcpyHostToDevice, st));
-        int rc = smems_dev(fm, out64, all, n_p, d_pat, d_off, i_pos ? d_i : nullptr, min_len, (uint32_t)max_len, cap, d_cnt, d_out, st);
-        if (rc) return rc;
-        BG_HIP(hipMemcpyAsync(count, d_cnt, n_p * 4, hipMemcpyDeviceToHost, st));
-        if (cap) BG_HIP(hipMemcpyAsync(out, d_out, n_p * (uint64_t)cap * rec, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return BG_OK;
-    };
-    int rc = run();
-    hipFree(d_pat);
-    hipFree(d_off);
-    hipFree(d_i);
-    hipFree(d_cnt);
-    hipFree(d_out);
-    if (rc) return rc;
+    {
+        bg_stage s(fm->ctx, fm->ctx->stream);
+        const uint8_t* d_pat = s.up(pat, pat_off[n_p]);
+        const uint64_t* d_off = s.up(pat_off, n_p + 1);
+        const uint32_t* d_i = i_pos ? s.up(i_pos, n_p) : nullptr;
+        uint32_t* d_cnt = s.out<uint32_t>(n_p);
+        uint8_t* d_out = s.out<uint8_t>(n_p * (uint64_t)cap * rec);
+        if (s.rc) return s.rc;
+        if (int rc = smems_dev(fm, out64, all, n_p, d_pat, d_off, d_i, min_len, (uint32_t)max_len, cap, d_cnt, d_out, s.st)) return rc;
+        s.down(count, d_cnt, n_p);
+        s.down((uint8_t*)out, d_out, n_p * (uint64_t)cap * rec);
+        if (s.sync()) return s.rc;
+    }
     int status = BG_OK;
     for (uint64_t q = 0; q < n_p; q++) {
         if (count[q] == 0xFFFFFFFFu)
@@ -737,41 +719,27 @@ int interval_host(bg_fm* fm, bool out64, uint64_t n_req, const uint8_t* op, cons
     if (fm->wide && !out64) return BG_ERR_UNSUPPORTED;
     if (n_req == 0) return BG_OK;
     const size_t rec = out64 ? 32 : 16;
-    bg_ctx* ctx = fm->ctx;
-    BG_HIP(hipSetDevice(ctx->device));
-    uint8_t *d_op = nullptr, *d_sym = nullptr, *d_ok = nullptr;
-    void *d_in = nullptr, *d_out = nullptr;
     std::vector<uint8_t> okv(n_req);
-    auto run = [&]() -> int {
-        BG_HIP(hipMalloc((void**)&d_op, n_req));
-        BG_HIP(hipMalloc((void**)&d_sym, n_req));
-        BG_HIP(hipMalloc((void**)&d_ok, n_req));
-        BG_HIP(hipMalloc(&d_in, n_req * rec));
-        BG_HIP(hipMalloc(&d_out, n_req * rec));
-        hipStream_t st = ctx->stream;
-        BG_HIP(hipMemcpyAsync(d_op, op, n_req, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_sym, sym, n_req, hipMemcpyHostToDevice, st));
-        BG_HIP(hipMemcpyAsync(d_in, iv_in, n_req * rec, hipMemcpyHostToDevice, st));
+    {
+        bg_stage s(fm->ctx, fm->ctx->stream);
+        const uint8_t* d_op = s.up(op, n_req);
+        const uint8_t* d_sym = s.up(sym, n_req);
+        uint8_t* d_ok = s.out<uint8_t>(n_req);
+        const void* d_in = s.up((const uint8_t*)iv_in, n_req * rec);
+        void* d_out = s.out<uint8_t>(n_req * rec);
+        if (s.rc) return s.rc;
         const dim3 grid((unsigned)((n_req + 63) / 64));
         if (fm->wide)
-            fmd_interval_kernel<true, true><<<grid, dim3(256), 0, st>>>(k7_args<true>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
+            fmd_interval_kernel<true, true><<<grid, dim3(256), 0, s.st>>>(k7_args<true>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
         else if (out64)
-            fmd_interval_kernel<false, true><<<grid, dim3(256), 0, st>>>(k7_args<false>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
+            fmd_interval_kernel<false, true><<<grid, dim3(256), 0, s.st>>>(k7_args<false>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
         else
-            fmd_interval_kernel<false, false><<<grid, dim3(256), 0, st>>>(k7_args<false>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
+            fmd_interval_kernel<false, false><<<grid, dim3(256), 0, s.st>>>(k7_args<false>(fm), n_req, d_op, d_in, d_sym, d_out, d_ok);
         BG_HIP(hipGetLastError());
-        BG_HIP(hipMemcpyAsync(iv_out, d_out, n_req * rec, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipMemcpyAsync(okv.data(), d_ok, n_req, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return BG_OK;
-    };
-    int rc = run();
-    hipFree(d_op);
-    hipFree(d_sym);
-    hipFree(d_ok);
-    hipFree(d_in);
-    hipFree(d_out);
-    if (rc) return rc;
+        s.down((uint8_t*)iv_out, (const uint8_t*)d_out, n_req * rec);
+        s.down(okv.data(), d_ok, n_req);
+        if (s.sync()) return s.rc;
+    }
     for (uint64_t q = 0; q < n_req; q++)
         if (!okv[q]) return BG_ERR_OUT_OF_ALPHABET;
     return BG_OK;

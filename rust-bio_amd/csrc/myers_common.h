@@ -1,6 +1,6 @@
 // What the two Myers variants share (myers.hip: Myers<u64>; myers_long.hip: myers::long, blocks of 64 bits): the walk of a
 // lane over its own text, the hit / no-hit records, the compaction of the 256 text bytes into classes, the pinned upload
-// of a call's tables, and the host flavour (device copies in, the device call, results back).
+// of a call's tables, and the host flavour (device copies in through a bg_stage, the device call, results back).
 #ifndef BG_MYERS_COMMON_H
 #define BG_MYERS_COMMON_H
 #include <map>
@@ -144,50 +144,30 @@ struct MyCall {
     uint64_t ops_stride = 0;
 };
 
-// host flavours: device copies of the inputs, the device call `run(call, stream)` on the ctx's stream, the results back
-struct MyDev {
-    void* p = nullptr;
-    ~MyDev() { hipFree(p); }
-    int alloc(size_t bytes) {
-        BG_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        return BG_OK;
-    }
-};
-
+// host flavours: device copies of the texts the offsets span (text + off[0] on, with the offsets rebased to it), the device
+// call `run(call, stream)` on the ctx's stream, the results back
 template <class Run>
 int my_host(bg_ctx* ctx, uint32_t n_pat, MyCall c, const uint8_t* text, const uint64_t* off, bg_alignment_t* aln, uint32_t* count,
             uint8_t* ops, Run run) {
     if (c.n_texts == 0) return BG_OK;
     if (!text || !off || !aln) return BG_ERR_INVALID_ARG;
-    BG_HIP(hipSetDevice(ctx->device));
-    const uint64_t t0 = off[0], bytes = off[c.n_texts] - t0;
+    const uint64_t t0 = off[0];
     const uint64_t n_rec = c.n_texts * n_pat * (c.find_all ? c.max_hits : 1), n_jobs = c.n_texts * n_pat;
-    MyDev d_text, d_off, d_aln, d_count, d_ops;
     std::vector<uint64_t> rel(c.n_texts + 1);
     for (uint64_t i = 0; i <= c.n_texts; i++) rel[i] = off[i] - t0;
-    if (int rc = d_text.alloc(bytes)) return rc;
-    if (int rc = d_off.alloc(rel.size() * 8)) return rc;
-    if (int rc = d_aln.alloc(n_rec * sizeof(bg_alignment_t))) return rc;
-    if (c.find_all)
-        if (int rc = d_count.alloc(n_jobs * 4)) return rc;
-    if (ops)
-        if (int rc = d_ops.alloc(n_jobs * c.ops_stride)) return rc;
-    hipStream_t st = ctx->stream;
-    BG_HIP(hipMemcpyAsync(d_text.p, text + t0, bytes, hipMemcpyHostToDevice, st));
-    BG_HIP(hipMemcpyAsync(d_off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-    BG_HIP(hipStreamSynchronize(st));
-    c.d_text = (const uint8_t*)d_text.p;
-    c.d_off = (const uint64_t*)d_off.p;
-    c.d_aln = (bg_alignment_t*)d_aln.p;
-    c.d_count = (uint32_t*)d_count.p;
-    c.d_ops = ops ? (uint8_t*)d_ops.p : nullptr;
-    const int rc = run(c, st);
+    bg_stage s(ctx, ctx->stream);
+    c.d_text = s.up(text + t0, rel.back());
+    c.d_off = s.up(rel.data(), rel.size());
+    c.d_aln = s.out<bg_alignment_t>(n_rec);
+    c.d_count = c.find_all ? s.out<uint32_t>(n_jobs) : nullptr;
+    c.d_ops = ops ? s.out<uint8_t>(n_jobs * c.ops_stride) : nullptr;
+    if (s.sync()) return s.rc;
+    const int rc = run(c, s.st);
     if (rc != BG_OK && rc != BG_ERR_OPS_CAP) return rc;
-    BG_HIP(hipMemcpyAsync(aln, d_aln.p, n_rec * sizeof(bg_alignment_t), hipMemcpyDeviceToHost, st));
-    if (c.find_all) BG_HIP(hipMemcpyAsync(count, d_count.p, n_jobs * 4, hipMemcpyDeviceToHost, st));
-    if (ops) BG_HIP(hipMemcpyAsync(ops, d_ops.p, n_jobs * c.ops_stride, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return rc;
+    s.down(aln, c.d_aln, n_rec);
+    if (c.find_all) s.down(count, c.d_count, n_jobs);
+    if (ops) s.down(ops, c.d_ops, n_jobs * c.ops_stride);
+    return s.sync() ? s.rc : rc;
 }
 
 }  // namespace

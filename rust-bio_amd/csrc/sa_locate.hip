@@ -256,21 +256,14 @@ extern "C" int bg_sa_get_batch(bg_fm* fm, uint64_t n_idx, const uint64_t* index,
     if (!fm || (n_idx && (!index || !pos))) return BG_ERR_INVALID_ARG;
     if (fm->sa_kind == 0) return BG_ERR_INVALID_ARG;
     if (n_idx == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
-    BG_HIP(hipSetDevice(ctx->device));
-    uint64_t* d = nullptr;
-    auto run = [&]() -> int {
-        BG_HIP(hipMalloc((void**)&d, n_idx * 8));
-        BG_HIP(hipMemcpyAsync(d, index, n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
-        int rc = launch_get(fm, n_idx, d, d, ctx->stream);
-        if (rc) return rc;
-        BG_HIP(hipMemcpyAsync(pos, d, n_idx * 8, hipMemcpyDeviceToHost, ctx->stream));
-        BG_HIP(hipStreamSynchronize(ctx->stream));
-        return BG_OK;
-    };
-    int rc = run();
-    hipFree(d);
-    if (rc) return rc;
+    {
+        bg_stage s(fm->ctx, fm->ctx->stream);
+        uint64_t* d = s.up(index, n_idx);  // rows -> positions in place
+        if (s.rc) return s.rc;
+        if (int rc = launch_get(fm, n_idx, d, d, s.st)) return rc;
+        s.down(pos, d, n_idx);
+        if (s.sync()) return s.rc;
+    }
     for (uint64_t i = 0; i < n_idx; i++)
         if (pos[i] == BG_SA_PANIC) return BG_ERR_OUT_OF_ALPHABET;
     return BG_OK;
@@ -291,26 +284,16 @@ extern "C" int bg_interval_occ_batch(bg_fm* fm, uint64_t n_iv, const uint64_t* l
     if (total > pos_cap) return BG_ERR_OPS_CAP;
     if (total == 0) return BG_OK;
     if (!pos) return BG_ERR_INVALID_ARG;
-    bg_ctx* ctx = fm->ctx;
-    BG_HIP(hipSetDevice(ctx->device));
-    uint64_t *d_lo = nullptr, *d_off = nullptr, *d_pos = nullptr;
-    auto run = [&]() -> int {
-        BG_HIP(hipMalloc((void**)&d_lo, n_iv * 8));
-        BG_HIP(hipMalloc((void**)&d_off, (n_iv + 1) * 8));
-        BG_HIP(hipMalloc((void**)&d_pos, total * 8));
-        BG_HIP(hipMemcpyAsync(d_lo, lower, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-        BG_HIP(hipMemcpyAsync(d_off, out_off, (n_iv + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        int rc = bg_interval_occ_batch_dev(fm, n_iv, d_lo, d_off, total, d_pos, ctx->stream);
-        if (rc) return rc;
-        BG_HIP(hipMemcpyAsync(pos, d_pos, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        BG_HIP(hipStreamSynchronize(ctx->stream));
-        return BG_OK;
-    };
-    int rc = run();
-    hipFree(d_lo);
-    hipFree(d_off);
-    hipFree(d_pos);
-    if (rc) return rc;
+    {
+        bg_stage s(fm->ctx, fm->ctx->stream);
+        const uint64_t* d_lo = s.up(lower, n_iv);
+        const uint64_t* d_off = s.up(out_off, n_iv + 1);
+        uint64_t* d_pos = s.out<uint64_t>(total);
+        if (s.rc) return s.rc;
+        if (int rc = bg_interval_occ_batch_dev(fm, n_iv, d_lo, d_off, total, d_pos, s.st)) return rc;
+        s.down(pos, d_pos, total);
+        if (s.sync()) return s.rc;
+    }
     for (uint64_t i = 0; i < total; i++)
         if (pos[i] == BG_SA_PANIC) return BG_ERR_OUT_OF_ALPHABET;
     return BG_OK;

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "dna_complement.h"
+#include "fastq_cols.h"
 #include "fm_kernels.h"
 #include "sam_rule.h"
 
@@ -498,49 +499,35 @@ extern "C" int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint6
     if (n_reads && (!contigs || !names || !fastq_text || !recs || !seq || !qual || !hits || !strand || !ops)) return BG_ERR_INVALID_ARG;
     out_off[0] = 0;
     if (n_reads == 0) return BG_OK;
-    bg_ctx* ctx = fm->ctx;
-    BG_HIP(hipSetDevice(ctx->device));
     const uint64_t n_slots = n_reads * sp->max_hits;
-    // the buffers the records point into end where their last record ends
-    uint64_t fq_bytes = 0, seq_bytes = 0, qual_bytes = 0, ops_bytes = 0, name_bytes = 0;
-    for (uint64_t r = 0; r < n_reads; r++) {
-        fq_bytes = std::max<uint64_t>(fq_bytes, recs[r].id_off + recs[r].id_len);
-        seq_bytes = std::max<uint64_t>(seq_bytes, recs[r].seq_off + recs[r].seq_len);
-        qual_bytes = std::max<uint64_t>(qual_bytes, recs[r].qual_off + recs[r].qual_len);
-    }
+    // the buffers the records, the hits and the contigs point into end where the last of them ends (no description is written)
+    const fq_extents e = fq_record_extents(recs, n_reads);
+    uint64_t ops_bytes = 0, name_bytes = 0;
     for (uint64_t s = 0; s < n_slots; s++)
         if (hits[s].aln.score != BG_MIN_SCORE) ops_bytes = std::max<uint64_t>(ops_bytes, hits[s].aln.ops_off + hits[s].aln.n_ops);
     for (uint64_t c = 0; c < n_contigs; c++) name_bytes = std::max<uint64_t>(name_bytes, contigs[c].name_off + contigs[c].name_len);
-    enum { CONTIGS, NAMES, FQ, RECS, SEQ, QUAL, HITS, STRAND, OPS, MULTI, PAIRS, DUP, OFF, OUT, N };
-    const void* src[N] = {contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi, pairs, dup, nullptr, nullptr};
-    const size_t bytes[N] = {(size_t)(n_contigs * sizeof(bg_sam_contig_t)), (size_t)name_bytes, (size_t)fq_bytes,
-                             (size_t)(n_reads * sizeof(bg_fastq_record_t)), (size_t)seq_bytes, (size_t)qual_bytes,
-                             (size_t)(n_slots * sizeof(bg_seed_hit_t)), (size_t)n_slots, (size_t)ops_bytes,
-                             multi ? (size_t)(n_reads * sizeof(bg_multi_hit_t)) : 0, pairs ? (size_t)(n_reads / 2 * sizeof(bg_pair_hit_t)) : 0,
-                             dup ? (size_t)n_reads : 0, (size_t)((n_slots + 1) * 8), (size_t)out_cap};
-    void* d[N] = {};
-    auto run = [&]() -> int {
-        hipStream_t st = ctx->stream;
-        for (int i = 0; i < N; i++) {
-            if (!src[i] && i < OFF) continue;  // multi / pairs / dup not given
-            if (i == OUT && !out) continue;    // a sizing call
-            BG_HIP(hipMalloc(&d[i], std::max<size_t>(bytes[i], 16)));
-            if (src[i] && bytes[i]) BG_HIP(hipMemcpyAsync(d[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
-        }
-        const int rc2 = bg_sam_emit_dup_batch_dev(fm, sp, n_reads, (const bg_sam_contig_t*)d[CONTIGS], n_contigs, (const char*)d[NAMES],
-                                                  (const uint8_t*)d[FQ], (const bg_fastq_record_t*)d[RECS], (const uint8_t*)d[SEQ],
-                                                  (const uint8_t*)d[QUAL], (const bg_seed_hit_t*)d[HITS], (const uint8_t*)d[STRAND],
-                                                  (const uint8_t*)d[OPS], (const bg_multi_hit_t*)d[MULTI], (const bg_pair_hit_t*)d[PAIRS],
-                                                  (const uint8_t*)d[DUP], (char*)d[OUT], out_cap, (uint64_t*)d[OFF], out_bytes, st);
-        if (rc2 && rc2 != BG_ERR_OPS_CAP) return rc2;
-        BG_HIP(hipMemcpyAsync(out_off, d[OFF], bytes[OFF], hipMemcpyDeviceToHost, st));
-        if (!rc2 && out && *out_bytes) BG_HIP(hipMemcpyAsync(out, d[OUT], *out_bytes, hipMemcpyDeviceToHost, st));
-        BG_HIP(hipStreamSynchronize(st));
-        return rc2;
-    };
-    rc = run();
-    for (void* p : d) hipFree(p);
-    return rc;
+    bg_stage s(fm->ctx, fm->ctx->stream);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const char* d_names = s.up(names, name_bytes);
+    const uint8_t* d_fq = s.up(fastq_text, e.id);
+    const bg_fastq_record_t* d_recs = s.up(recs, n_reads);
+    const uint8_t* d_seq = s.up(seq, e.seq);
+    const uint8_t* d_qual = s.up(qual, e.qual);
+    const bg_seed_hit_t* d_hits = s.up(hits, n_slots);
+    const uint8_t* d_strand = s.up(strand, n_slots);
+    const uint8_t* d_ops = s.up(ops, ops_bytes);
+    const bg_multi_hit_t* d_multi = multi ? s.up(multi, n_reads) : nullptr;
+    const bg_pair_hit_t* d_pairs = pairs ? s.up(pairs, n_reads / 2) : nullptr;
+    const uint8_t* d_dup = dup ? s.up(dup, n_reads) : nullptr;
+    uint64_t* d_off = s.out<uint64_t>(n_slots + 1);
+    char* d_out = out ? s.out<char>(out_cap) : nullptr;  // null: a sizing call
+    if (s.rc) return s.rc;
+    rc = bg_sam_emit_dup_batch_dev(fm, sp, n_reads, d_contigs, n_contigs, d_names, d_fq, d_recs, d_seq, d_qual, d_hits, d_strand, d_ops, d_multi,
+                                   d_pairs, d_dup, d_out, out_cap, d_off, out_bytes, s.st);
+    if (rc && rc != BG_ERR_OPS_CAP) return rc;
+    s.down(out_off, d_off, n_slots + 1);
+    if (!rc && out) s.down(out, d_out, *out_bytes);
+    return s.sync() ? s.rc : rc;
 }
 
 extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,

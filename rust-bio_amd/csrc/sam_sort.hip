@@ -20,7 +20,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "bg_common.h"
+#include "fastq_cols.h"
 #include "sam_rule.h"
 
 namespace {
@@ -181,20 +181,6 @@ int sort_check(const bg_ctx* ctx, uint64_t n_slots, const void* key, const void*
 
 inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
-// device copies of host arrays for the host flavours
-struct DevCopies {
-    std::vector<void*> p;
-    ~DevCopies() {
-        for (void* q : p) hipFree(q);
-    }
-    int up(void** d, const void* src, size_t bytes, hipStream_t st) {
-        BG_HIP(hipMalloc(d, std::max<size_t>(bytes, 16)));
-        p.push_back(*d);
-        if (src && bytes) BG_HIP(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, st));
-        return BG_OK;
-    }
-};
-
 }  // namespace
 
 extern "C" int bg_sam_markdup_dev(bg_ctx* ctx, const bg_markdup_params_t* mp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
@@ -260,23 +246,18 @@ extern "C" int bg_sam_markdup(bg_ctx* ctx, const bg_markdup_params_t* mp, uint64
     if (n_reads && (!contigs || !hits || !strand || !recs || !qual || !dup)) return BG_ERR_INVALID_ARG;
     for (int i = 0; i < 4; i++) counts[i] = 0;
     if (n_reads == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const uint64_t n_slots = n_reads * mp->max_hits;
-    uint64_t qual_bytes = 0;  // the quality buffer ends where its last record ends
-    for (uint64_t r = 0; r < n_reads; r++) qual_bytes = std::max<uint64_t>(qual_bytes, recs[r].qual_off + recs[r].qual_len);
-    DevCopies dc;
-    void *d_contigs, *d_hits, *d_strand, *d_recs, *d_qual, *d_dup;
-    if ((rc = dc.up(&d_contigs, contigs, n_contigs * sizeof(bg_sam_contig_t), st)) || (rc = dc.up(&d_hits, hits, n_slots * sizeof(bg_seed_hit_t), st)) ||
-        (rc = dc.up(&d_strand, strand, n_slots, st)) || (rc = dc.up(&d_recs, recs, n_reads * sizeof(bg_fastq_record_t), st)) ||
-        (rc = dc.up(&d_qual, qual, qual_bytes, st)) || (rc = dc.up(&d_dup, nullptr, n_reads, st)))
-        return rc;
-    rc = bg_sam_markdup_dev(ctx, mp, n_reads, (const bg_sam_contig_t*)d_contigs, n_contigs, (const bg_seed_hit_t*)d_hits, (const uint8_t*)d_strand,
-                            (const bg_fastq_record_t*)d_recs, (const uint8_t*)d_qual, (uint8_t*)d_dup, counts, st);
-    if (rc) return rc;
-    BG_HIP(hipMemcpyAsync(dup, d_dup, n_reads, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const bg_seed_hit_t* d_hits = s.up(hits, n_slots);
+    const uint8_t* d_strand = s.up(strand, n_slots);
+    const bg_fastq_record_t* d_recs = s.up(recs, n_reads);
+    const uint8_t* d_qual = s.up(qual, fq_record_extents(recs, n_reads).qual);  // of the records' buffers only the qualities are read
+    uint8_t* d_dup = s.out<uint8_t>(n_reads);
+    if (s.rc) return s.rc;
+    if ((rc = bg_sam_markdup_dev(ctx, mp, n_reads, d_contigs, n_contigs, d_hits, d_strand, d_recs, d_qual, d_dup, counts, s.st))) return rc;
+    s.down(dup, d_dup, n_reads);
+    return s.sync();
 }
 
 extern "C" int bg_sam_sort_keys_dev(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs, uint64_t n_contigs,
@@ -299,20 +280,16 @@ extern "C" int bg_sam_sort_keys(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t
     if (rc) return rc;
     if (n_reads && (!contigs || !hits || !strand || !key)) return BG_ERR_INVALID_ARG;
     if (n_reads == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const uint64_t n_slots = n_reads * sp->max_hits;
-    DevCopies dc;
-    void *d_contigs, *d_hits, *d_strand, *d_key;
-    if ((rc = dc.up(&d_contigs, contigs, n_contigs * sizeof(bg_sam_contig_t), st)) || (rc = dc.up(&d_hits, hits, n_slots * sizeof(bg_seed_hit_t), st)) ||
-        (rc = dc.up(&d_strand, strand, n_slots, st)) || (rc = dc.up(&d_key, nullptr, n_slots * 8, st)))
-        return rc;
-    rc = bg_sam_sort_keys_dev(ctx, sp, n_reads, (const bg_sam_contig_t*)d_contigs, n_contigs, (const bg_seed_hit_t*)d_hits, (const uint8_t*)d_strand,
-                              (uint64_t*)d_key, st);
-    if (rc) return rc;
-    BG_HIP(hipMemcpyAsync(key, d_key, n_slots * 8, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const bg_seed_hit_t* d_hits = s.up(hits, n_slots);
+    const uint8_t* d_strand = s.up(strand, n_slots);
+    uint64_t* d_key = s.out<uint64_t>(n_slots);
+    if (s.rc) return s.rc;
+    if ((rc = bg_sam_sort_keys_dev(ctx, sp, n_reads, d_contigs, n_contigs, d_hits, d_strand, d_key, s.st))) return rc;
+    s.down(key, d_key, n_slots);
+    return s.sync();
 }
 
 extern "C" int bg_sam_sort_dev(bg_ctx* ctx, uint64_t n_slots, const uint64_t* d_key, const char* d_in, const uint64_t* d_in_off, uint64_t in_bytes,
@@ -379,20 +356,17 @@ extern "C" int bg_sam_sort(bg_ctx* ctx, uint64_t n_slots, const uint64_t* key, c
     if (rc) return rc;
     out_off[0] = 0;
     if (n_slots == 0) return BG_OK;
-    BG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DevCopies dc;
-    void *d_key, *d_in, *d_in_off, *d_out, *d_out_off, *d_perm;
-    if ((rc = dc.up(&d_key, key, n_slots * 8, st)) || (rc = dc.up(&d_in, in, in_bytes, st)) || (rc = dc.up(&d_in_off, in_off, (n_slots + 1) * 8, st)) ||
-        (rc = dc.up(&d_out, nullptr, in_bytes, st)) || (rc = dc.up(&d_out_off, nullptr, (n_slots + 1) * 8, st)) ||
-        (rc = dc.up(&d_perm, nullptr, n_slots * 8, st)))
-        return rc;
-    rc = bg_sam_sort_dev(ctx, n_slots, (const uint64_t*)d_key, (const char*)d_in, (const uint64_t*)d_in_off, in_bytes, (char*)d_out, in_bytes,
-                         (uint64_t*)d_out_off, (uint64_t*)d_perm, st);
-    if (rc) return rc;
-    BG_HIP(hipMemcpyAsync(out_off, d_out_off, (n_slots + 1) * 8, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipMemcpyAsync(perm, d_perm, n_slots * 8, hipMemcpyDeviceToHost, st));
-    if (in_bytes) BG_HIP(hipMemcpyAsync(out, d_out, in_bytes, hipMemcpyDeviceToHost, st));
-    BG_HIP(hipStreamSynchronize(st));
-    return BG_OK;
+    bg_stage s(ctx, ctx->stream);
+    const uint64_t* d_key = s.up(key, n_slots);
+    const char* d_in = s.up(in, in_bytes);
+    const uint64_t* d_in_off = s.up(in_off, n_slots + 1);
+    char* d_out = s.out<char>(in_bytes);
+    uint64_t* d_out_off = s.out<uint64_t>(n_slots + 1);
+    uint64_t* d_perm = s.out<uint64_t>(n_slots);
+    if (s.rc) return s.rc;
+    if ((rc = bg_sam_sort_dev(ctx, n_slots, d_key, d_in, d_in_off, in_bytes, d_out, in_bytes, d_out_off, d_perm, s.st))) return rc;
+    s.down(out_off, d_out_off, n_slots + 1);
+    s.down(perm, d_perm, n_slots);
+    s.down(out, d_out, in_bytes);
+    return s.sync();
 }

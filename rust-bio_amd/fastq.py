@@ -165,12 +165,8 @@ def filter_arrays(recs, seq, seq_off, qual, qual_off, flags=0, min_len=0, max_le
     n = len(recs)
     f = filter_params(flags, min_len, max_len, max_n)
     hits = np.ascontiguousarray(hits, dtype=_lib.ALN_DTYPE) if hits is not None else None
-    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
-    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
-    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
-    o_recs = np.zeros(n, dtype=_lib.FQREC_DTYPE)
-    o_seq, o_qual = np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(max(1, len(qual)), dtype=np.uint8)
-    o_so, o_qo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    recs, seq, seq_off, qual, qual_off = _lib.fq_columns(recs, seq, seq_off, qual, qual_off)
+    o_recs, o_seq, o_so, o_qual, o_qo = _lib.fq_host_outputs(n, n, seq, qual)
     keep = np.zeros(max(1, n), dtype=np.uint8)
     tot = (C.c_uint64 * 3)()
     _lib.check(_lib.lib().bg_fastq_filter(ctx.h, n, f.ctypes.data, hits.ctypes.data if hits is not None else None, int(n_pat),
@@ -190,17 +186,12 @@ def filter_dev(n, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, flags=0, min_len
     the first six results of an earlier call of the same shape made without totals, to write into instead of allocating."""
     import torch
     ctx = ctx or _lib.default_context()
-    dev = d_seq.device
     f = filter_params(flags, min_len, max_len, max_n)
     if out is not None:
         o_recs, o_seq, o_so, o_qual, o_qo, d_keep = out[:6]
     else:
-        o_recs = torch.empty(n * 56, dtype=torch.uint8, device=dev)
-        o_seq = torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev)
-        o_qual = torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev)
-        o_so = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        o_qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        d_keep = torch.empty(max(1, n), dtype=torch.uint8, device=dev) if want_keep else None
+        o_recs, o_seq, o_so, o_qual, o_qo = _lib.fq_dev_outputs(n, n, d_seq, d_qual)
+        d_keep = torch.empty(max(1, n), dtype=torch.uint8, device=d_seq.device) if want_keep else None
     tot = (C.c_uint64 * 3)()
     _lib.check(_lib.lib().bg_fastq_filter_dev(ctx.h, n, f.ctypes.data, d_hits.data_ptr() if d_hits is not None else None, int(n_pat),
                                               d_recs.data_ptr(), d_seq.data_ptr(), d_seq_off.data_ptr(), d_qual.data_ptr(),
@@ -267,12 +258,8 @@ def demux_split_arrays(bins, n_bins, recs, seq, seq_off, qual, qual_off, hit=Non
     n = len(recs)
     bins = np.ascontiguousarray(bins, dtype=np.uint32)
     hit = np.ascontiguousarray(hit, dtype=_lib.ALN_DTYPE) if hit is not None else None
-    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
-    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
-    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
-    o_recs = np.zeros(max(1, n), dtype=_lib.FQREC_DTYPE)
-    o_seq, o_qual = np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(max(1, len(qual)), dtype=np.uint8)
-    o_so, o_qo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    recs, seq, seq_off, qual, qual_off = _lib.fq_columns(recs, seq, seq_off, qual, qual_off)
+    o_recs, o_seq, o_so, o_qual, o_qo = _lib.fq_host_outputs(n, max(1, n), seq, qual)
     o_hit = np.zeros(max(1, n), dtype=_lib.ALN_DTYPE) if hit is not None else None
     perm, bin_off = np.zeros(max(1, n), dtype=np.uint64), np.zeros(int(n_bins) + 3, dtype=np.uint64)
     pad = np.zeros(1, dtype=np.uint8)  # no empty buffers: the call refuses null pointers
@@ -299,11 +286,7 @@ def demux_split_dev(n, d_bin, n_bins, d_recs, d_seq, d_seq_off, d_qual, d_qual_o
     if out is not None:
         o_recs, o_seq, o_so, o_qual, o_qo, o_hit, d_perm, d_boff = out[:8]
     else:
-        o_recs = torch.empty(max(1, n) * 56, dtype=torch.uint8, device=dev)
-        o_seq = torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev)
-        o_qual = torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev)
-        o_so = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        o_qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        o_recs, o_seq, o_so, o_qual, o_qo = _lib.fq_dev_outputs(n, max(1, n), d_seq, d_qual)
         o_hit = torch.empty(max(1, n) * 64, dtype=torch.uint8, device=dev) if d_hit is not None else None
         d_perm = torch.empty(max(1, n), dtype=torch.int64, device=dev) if want_perm else None
         d_boff = torch.empty(int(n_bins) + 3, dtype=torch.int64, device=dev)

@@ -361,12 +361,8 @@ def trim(mode, hits, n_pat, recs, seq, seq_off, qual, qual_off, ctx=None):
     ctx = ctx or _lib.default_context()
     n = len(recs)
     hits = np.ascontiguousarray(hits, dtype=ALN_DTYPE)
-    recs = np.ascontiguousarray(recs, dtype=_lib.FQREC_DTYPE)
-    seq, qual = _lib.as_u8(seq), _lib.as_u8(qual)
-    seq_off, qual_off = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(qual_off, dtype=np.uint64)
-    o_recs = np.zeros(n, dtype=_lib.FQREC_DTYPE)
-    o_seq, o_qual = np.zeros(max(1, len(seq)), dtype=np.uint8), np.zeros(max(1, len(qual)), dtype=np.uint8)
-    o_so, o_qo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    recs, seq, seq_off, qual, qual_off = _lib.fq_columns(recs, seq, seq_off, qual, qual_off)
+    o_recs, o_seq, o_so, o_qual, o_qo = _lib.fq_host_outputs(n, n, seq, qual)
     tot = (C.c_uint64 * 2)()
     _lib.check(_lib.lib().bg_fastq_trim(ctx.h, n, int(mode), hits.ctypes.data, int(n_pat), recs.ctypes.data, seq.ctypes.data,
                                         seq_off.ctypes.data, qual.ctypes.data, qual_off.ctypes.data, o_recs.ctypes.data,
@@ -379,17 +375,8 @@ def trim_dev(mode, d_hits, n_pat, n, d_recs, d_seq, d_seq_off, d_qual, d_qual_of
     (d_recs, d_seq, d_seq_off, d_qual, d_qual_off, totals) — new tensors in HBM (never the inputs: the call does not work in
     place); totals = (sequence bytes, quality bytes) or None (then the call does not synchronise).  `out`: the five tensors of
     an earlier call of the same shape, to write into instead of allocating."""
-    import torch
     ctx = ctx or _lib.default_context()
-    dev = d_seq.device
-    if out is not None:
-        o_recs, o_seq, o_so, o_qual, o_qo = out[:5]
-    else:
-        o_recs = torch.empty(n * 56, dtype=torch.uint8, device=dev)
-        o_seq = torch.empty(max(1, int(d_seq.numel())), dtype=torch.uint8, device=dev)
-        o_qual = torch.empty(max(1, int(d_qual.numel())), dtype=torch.uint8, device=dev)
-        o_so = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        o_qo = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    o_recs, o_seq, o_so, o_qual, o_qo = out[:5] if out is not None else _lib.fq_dev_outputs(n, n, d_seq, d_qual)
     tot = (C.c_uint64 * 2)()
     _lib.check(_lib.lib().bg_fastq_trim_dev(ctx.h, n, int(mode), d_hits.data_ptr(), int(n_pat), d_recs.data_ptr(), d_seq.data_ptr(),
                                             d_seq_off.data_ptr(), d_qual.data_ptr(), d_qual_off.data_ptr(), o_recs.data_ptr(),
