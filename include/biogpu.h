@@ -237,6 +237,8 @@ int bg_fm_backward_search_batch_dev(bg_fm* fm, uint64_t n_q, const uint8_t* d_pa
  * may read one dword past the last symbol; its content is never interpreted).  A byte that is none of the four
  * codes is stored as code 0 and counted in *d_n_invalid (a device counter the caller zeroes; may be NULL): a buffer
  * with a non-zero count must take the byte entry points.  Asynchronous on `stream`. */
+/* d_bytes (and bg_unpack2_dev's output) may be at any address: a whole word at a 16-byte aligned address is one vector load, any
+ * other address byte by byte. */
 int bg_pack2_dev(bg_ctx* ctx, const uint8_t* d_bytes, uint64_t n, const uint8_t* codes, uint32_t* d_packed,
                  uint64_t* d_n_invalid, void* stream);
 int bg_unpack2_dev(bg_ctx* ctx, const uint32_t* d_packed, uint64_t n, const uint8_t* codes, uint8_t* d_bytes,
@@ -382,6 +384,8 @@ int bg_align_batch(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint64_t n_pai
  * HOST pointer (it is compacted and uploaded by the call, which then synchronises `stream` once).
  * max_xlen/max_ylen are upper bounds on the sequence lengths in the batch: a pair that exceeds them is not
  * aligned and gets status BG_ERR_INVALID_ARG in its record (xlen/ylen filled in, no operations). */
+/* d_x, d_y and d_ops may be at any address (a pair whose slot ends 4-byte aligned stores four operations at a time, any other
+ * byte by byte). */
 int bg_align_batch_dev(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint64_t n_pairs,
                        const uint8_t* d_x, const uint64_t* d_x_off, const uint8_t* d_y,
                        const uint64_t* d_y_off, uint32_t max_xlen, uint32_t max_ylen,
@@ -415,6 +419,8 @@ int bg_align_banded_batch(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint32_
  * conventions: record p keeps ops_off = (p + 1) * ops_stride - n_ops, its operations right-aligned in
  * slot p; ops_stride >= longest x + longest y + 4).  The call is synchronous (it drives the engine's own
  * streams); work queued on `stream` before it is waited for.  band_cells is a host array (optional). */
+/* d_x, d_y and d_ops may be at any address (the band builder loads 16 bytes at a time from the first 16-byte boundary of a
+ * sequence on, the bytes around byte by byte). */
 int bg_align_banded_batch_dev(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint32_t k, uint32_t w,
                               uint64_t n_pairs, const uint8_t* d_x, const uint64_t* d_x_off,
                               const uint8_t* d_y, const uint64_t* d_y_off, bg_alignment_t* d_out,
@@ -491,6 +497,7 @@ uint64_t bg_sparse_expand_kmer_matches(const uint8_t* x, uint64_t m, const uint8
  * The index handle needs the text (bg_fm_set_text[_dev]: all n bytes the index was built from, final sentinel
  * included) and a suffix array (bg_fm_set_suffix_array / bg_fm_set_sampled_suffix_array). */
 int bg_fm_set_text(bg_fm* fm, const uint8_t* text, uint64_t n);         /* host text, copied to the device */
+/* (d_text of bg_fm_set_text_dev may be at any address) */
 int bg_fm_set_text_dev(bg_fm* fm, const uint8_t* d_text, uint64_t n);   /* device text, borrowed: must outlive the handle's use */
 typedef struct {
     uint32_t seed_len, stride; /* benches/fmindex.rs:21-25 searches 20-mers */
@@ -539,6 +546,7 @@ int bg_seed_extend_strands_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_see
                                  uint8_t* strand, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
 /* Device flavour (operation slots, totals and passes as bg_seed_extend_batch_dev; seed_chunk_reads counts the caller's
  * reads, and with both strands a pass takes at most 2^20 of them). */
+/* d_reads, d_strand and d_ops may be at any address. */
 int bg_seed_extend_strands_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_seed_params_t* prm, uint32_t strands,
                                      uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off,
                                      uint32_t max_read_len, bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_ops,
@@ -631,6 +639,8 @@ enum { BG_TIER_NONE = 0, BG_TIER_FIRST = 1, BG_TIER_SECOND = 2 };   /* tier[r] *
 int bg_seed_extend_tiered_batch(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
                                 uint64_t n_reads, const uint8_t* reads, const uint64_t* read_off, bg_seed_hit_t* hits,
                                 uint8_t* strand, uint8_t* tier, uint8_t* ops_buf, uint64_t ops_cap, uint64_t* ops_used);
+/* Device flavour: d_reads, d_strand, d_tier and d_ops may be at any address (a re-seeded read's operations move into the
+ * caller's slot 16 bytes at a time where the two addresses agree mod 16, else byte by byte). */
 int bg_seed_extend_tiered_batch_dev(bg_fm* fm, const bg_scoring_t* sc, const bg_tiered_seed_params_t* prm, uint32_t strands,
                                     uint64_t n_reads, const uint8_t* d_reads, const uint64_t* d_read_off, uint32_t max_read_len,
                                     bg_seed_hit_t* d_hits, uint8_t* d_strand, uint8_t* d_tier, uint8_t* d_ops, uint64_t ops_stride,
@@ -870,6 +880,7 @@ int bg_seed_extend_pairs_rescue_mapq_batch_dev(bg_fm* fm, const bg_scoring_t* sc
                                                void* stream);
 /* d_out[d_off[i] .. d_off[i + 1]) = revcomp(d_in[d_off[i] .. d_off[i + 1])) for i < n (the FMD / SMEM callers need the
  * same operation); asynchronous on `stream`.  d_in and d_out must not overlap. */
+/* (d_in and d_out may be at any address: read and written byte by byte) */
 int bg_revcomp_batch_dev(bg_ctx* ctx, uint64_t n, const uint8_t* d_in, const uint64_t* d_off, uint8_t* d_out, void* stream);
 
 /* ---- FASTQ ingest and CIGAR emission --------------------------------------
@@ -896,6 +907,8 @@ int bg_fastq_parse(bg_ctx* ctx, const uint8_t* text, uint64_t len, bg_fastq_reco
                    int32_t* status, uint64_t* err_pos);
 /* the same with text, records, sequences, qualities and offsets in device memory (n_records/status/err_pos are
  * host pointers; the call synchronises `stream`) */
+/* d_text, d_seq and d_qual may be at any address: a text at a 16-byte aligned address is loaded with vector loads, any other
+ * address byte by byte; the outputs are written 16 bytes at a time between their own 16-byte boundaries. */
 int bg_fastq_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t len, bg_fastq_record_t* d_recs,
                        uint64_t rec_cap, uint8_t* d_seq, uint64_t* d_seq_off, uint8_t* d_qual,
                        uint64_t* d_qual_off, uint64_t* n_records, int32_t* status, uint64_t* err_pos,
@@ -909,6 +922,7 @@ int bg_cigar_batch(bg_ctx* ctx, uint64_t n, const bg_alignment_t* aln, const uin
                    int hard_clip, char* out, uint64_t out_cap, uint64_t* out_off);
 /* device flavour: one slot of `stride` chars (>= 2 * max n_ops + 24) per alignment, d_len[p] = chars written
  * or a negative bg_status */
+/* (d_ops and d_out may be at any address: read and written byte by byte) */
 int bg_cigar_batch_dev(bg_ctx* ctx, uint64_t n, const bg_alignment_t* d_aln, const uint8_t* d_ops, int hard_clip,
                        char* d_out, uint64_t stride, int32_t* d_len, void* stream);
 
@@ -1035,6 +1049,8 @@ int bg_sam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char
                   uint64_t* out_bytes);
 /* Device flavour: every d_* pointer in HBM, d_out_off n_reads * K + 1 entries, out_bytes a host pointer; the text pass is
  * asynchronous on `stream`.  Goes through the handle's ctx (scratch): the ctx's single-thread rule applies. */
+/* The byte pointers (d_names, d_fastq_text, d_seq, d_qual, d_strand, d_ops, d_out) may be at any address: a line is written 16
+ * bytes at a time between its first and last 16-byte boundary in d_out, the columns are read byte by byte. */
 int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
                           uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
                           const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
@@ -1134,6 +1150,8 @@ int bg_sam_sort_keys_dev(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t n_read
                          uint64_t n_contigs, const bg_seed_hit_t* d_hits, const uint8_t* d_strand, uint64_t* d_key, void* stream);
 int bg_sam_sort_keys(bg_ctx* ctx, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
                      const bg_seed_hit_t* hits, const uint8_t* strand, uint64_t* key);
+/* d_in and d_out may be at any address: a record is copied 16 bytes at a time on the alignment of its place in d_out, from
+ * whole aligned loads where they lie inside the record and byte by byte at its ends. */
 int bg_sam_sort_dev(bg_ctx* ctx, uint64_t n_slots, const uint64_t* d_key, const char* d_in, const uint64_t* d_in_off,
                     uint64_t in_bytes, char* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_perm, void* stream);
 int bg_sam_sort(bg_ctx* ctx, uint64_t n_slots, const uint64_t* key, const char* in, const uint64_t* in_off, uint64_t in_bytes,
@@ -1155,6 +1173,8 @@ int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const c
  * with one synchronisation of `stream`; its write pass is asynchronous on `stream`.  The host flavour uses no GPU (ctx may
  * be NULL). */
 enum { BG_FASTA_REF_FMD = 1, BG_FASTA_REF_UPPER = 2 };
+/* d_fasta_text, d_seq, d_text_out and d_names may be at any address: the index text is stored 16 bytes at a time at a 16-byte
+ * aligned d_text_out, byte by byte at any other address. */
 int bg_fasta_reference_dev(bg_ctx* ctx, uint64_t n_records, const bg_fasta_record_t* d_recs, const uint8_t* d_fasta_text,
                            const uint8_t* d_seq, uint32_t flags, uint8_t* d_text_out, uint64_t text_cap,
                            bg_sam_contig_t* d_contigs, char* d_names, uint64_t names_cap, uint64_t* n_text,
@@ -1267,6 +1287,7 @@ int bg_myers_long_find_all_batch_dev(bg_ctx* ctx, const uint64_t* peq /* host */
  * of the inputs and no output may alias an input (lanes read the source while others write: the call does not work in place).  Lengths, the exclusive scan of scan.hip, the copy; totals (optional, host, 2 entries: sequence and
  * quality bytes kept) costs the device flavour its only synchronisation of `stream`.  Unknown mode: BG_ERR_INVALID_ARG. */
 enum { BG_TRIM_3P = 0, BG_TRIM_5P = 1 };
+/* (the byte columns d_seq, d_qual, d_seq_out, d_qual_out may be at any address: read and written byte by byte) */
 int bg_fastq_trim_dev(bg_ctx* ctx, uint64_t n, int mode, const bg_alignment_t* d_hits, uint32_t n_pat,
                       const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
                       const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
@@ -1304,6 +1325,7 @@ typedef struct {
     uint32_t max_len;   /* pass: sequence length <= max_len (0xFFFFFFFF: no bound) */
     uint32_t max_n;     /* pass: at most max_n bytes 'N' or 'n' in the sequence; 0xFFFFFFFF: not counted, the sequence is not read */
 } bg_fastq_filter_t;
+/* (the byte columns d_seq, d_qual, d_seq_out, d_qual_out, d_keep may be at any address: read and written byte by byte) */
 int bg_fastq_filter_dev(bg_ctx* ctx, uint64_t n, const bg_fastq_filter_t* flt, const bg_alignment_t* d_hits, uint32_t n_pat,
                         const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
                         const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
@@ -1394,6 +1416,7 @@ int bg_fastq_demux_assign_dev(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* 
                               uint32_t* d_pat_out /* optional */, void* stream);
 int bg_fastq_demux_assign(bg_ctx* ctx, uint64_t n, const bg_demux_params_t* params, const bg_alignment_t* hits, uint32_t n_pat,
                           const uint32_t* pat_bin, uint32_t* bin, bg_alignment_t* hit_out, uint32_t* pat_out /* optional */);
+/* (the byte columns d_seq, d_qual, d_seq_out, d_qual_out may be at any address: read and written byte by byte) */
 int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins, const uint32_t* d_bin, const bg_alignment_t* d_hit /* optional, n */,
                              const bg_fastq_record_t* d_recs, const uint8_t* d_seq, const uint64_t* d_seq_off, const uint8_t* d_qual,
                              const uint64_t* d_qual_off, bg_fastq_record_t* d_recs_out, uint8_t* d_seq_out, uint64_t* d_seq_off_out,
@@ -1500,6 +1523,7 @@ typedef struct {
     uint64_t max_weight;    /* with a table: pass: weight_sum <= max_weight */
 } bg_qual_select_t;
 uint64_t bg_qc_tables_words(uint32_t max_cycles);
+/* (d_qual may be at any address: read byte by byte) */
 int bg_fastq_qual_cut_dev(bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* params, const uint8_t* d_qual, const uint64_t* d_qual_off,
                           bg_alignment_t* d_cut_out, uint64_t* totals /* optional, host, 2 */, void* stream);
 int bg_fastq_qual_cut(bg_ctx* ctx, uint64_t n, const bg_qual_cut_t* params, const uint8_t* qual, const uint64_t* qual_off,
