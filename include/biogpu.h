@@ -37,7 +37,7 @@
  * Text positions are 64-bit at the boundary, like the reference's usize (fmindex.rs:70-71, bwt.rs:94, suffix_array.rs:
  * 264).  Inside, an index below 2^32 - 1 symbols keeps the uint32 layout of rounds 1-4 (and its speed); from 2^32 - 1
  * symbols on — T$R$ of a human genome for an FMD index is 6.2 G — bg_fm_build / bg_fm_build_dev lay the SAME rank blocks
- * out with superblock-relative counters and 64-bit bases (csrc/fm_wide.hip) and every entry point that takes a bg_fm works
+ * out with superblock-relative counters and 64-bit bases (csrc/fm_kernels.h) and every entry point that takes a bg_fm works
  * on them: backward search with byte or 2-bit packed patterns (2-step blocks included), bg_fm_set_[sampled_]suffix_array,
  * bg_sa_get_batch[_dev], bg_interval_occ_batch[_dev], bg_fm_set_text + bg_seed_extend_batch[_dev], bg_fm_save / bg_fm_load,
  * and the FMD kernels through their *64 entry points (bg_fmd_smems_batch64[_dev], bg_fmd_interval_batch64: uint64 records;
@@ -104,7 +104,7 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *   band_join_global = 1  k-mer join with its table in global memory even where the LDS flavour applies
  *   band_chain_rows    global-tree chaining with four pairs per wavefront (chain_rows_kernel; default 1) or one (0: A/B, tests)
  *   fm_wide_from       texts of this many symbols or more get the 64-bit index layout (default 2^32 - 1; tests lower it so
- *                      that small texts exercise csrc/fm_wide.hip); 0 restores the default
+ *                      that small texts exercise that layout); 0 restores the default
  *   fm_wide_sb_shift   log2 of the rank blocks per superblock of the 64-bit layout (default 17; 0 .. 24; tests use small
  *                      values so that short texts span many superblocks)
  *   fq_no_fused = 1    bg_fastq_parse[_dev] through its general multi-pass kernels only, without the one-pass kernel that serves

@@ -99,16 +99,7 @@ __global__ __launch_bounds__(256) void fm_backward_search_kernel(
                 q += n_quads;
                 continue;
             }
-            if (SEEDS) {
-                const uint64_t rd = q / seeds.S;
-                const uint32_t k = (uint32_t)(q - rd * seeds.S);
-                const uint64_t o = pat_off[rd];
-                off = o + (uint64_t)k * seeds.stride;
-                len = (uint64_t)k * seeds.stride + seeds.seed_len <= pat_off[rd + 1] - o ? seeds.seed_len : 0u;
-            } else {
-                off = pat_off[q];
-                len = (uint32_t)(pat_off[q + 1] - off);
-            }
+            len = query_span<SEEDS>(pat_off, seeds, q, off);
             if (len) {
                 pos = len;
                 l = 0;
@@ -717,8 +708,7 @@ extern "C" uint64_t bg_fm_step2_bytes(const bg_fm* fm) {
 
 static SeedSrc fm_codes(const bg_fm* fm) {
     SeedSrc ex{};
-    ex.code_bytes = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
-                    (uint32_t)fm->code_byte[3] << 24;
+    ex.code_bytes = fm_code_bytes(fm);
     return ex;
 }
 // grid of fm_search_fast2x_kernel: persistent blocks, as many as are resident (its registers decide), 128 queries each

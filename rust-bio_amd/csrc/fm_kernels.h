@@ -1,5 +1,6 @@
-// Shared device pieces of the FM-index kernels (K5 backward search, K6 suffix-array lookup):
-// the 2-bit block layout, the quad rank helper and the index handle.  Layout notes: fm_index.hip.
+// Shared device pieces of the FM-index kernels (K5 backward search, K6 suffix-array lookup, K7 bi-directional search):
+// the 2-bit block layout, the quad rank helpers, what differs between the two position widths, and the index handle.
+// Layout notes: fm_index.hip.
 #ifndef BG_FM_KERNELS_H
 #define BG_FM_KERNELS_H
 #include <vector>
@@ -34,11 +35,11 @@ struct FmDev {
     uint32_t n_dense;
 };
 
-// number of entries <= r in a sorted array
-template <typename P>
-__device__ __forceinline__ uint32_t count_le(P arr, uint32_t lo, uint32_t hi, uint32_t r) {
+// number of entries <= r in arr[lo, hi), sorted (uint32 or uint64 positions)
+template <typename A, typename K>
+__device__ __forceinline__ uint32_t count_le(const A* arr, uint32_t lo, uint32_t hi, K r) {
     while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
+        const uint32_t mid = (lo + hi) >> 1;
         if (arr[mid] <= r)
             lo = mid + 1;
         else
@@ -242,6 +243,17 @@ struct FmLayout<true> {
     using Dev = FmWideDev;
     using Dev2 = Fm2WideDev;
 };
+// What a kernel over FmLayout<WIDE> asks of its layout beyond the types (K6, K7, fm_step2.hip's builders):
+// the absolute count of code c in front of block blk's superblock — the narrow blocks' counters are absolute already
+__device__ __forceinline__ uint64_t sb_base(const FmDev&, uint64_t, uint32_t) { return 0; }
+__device__ __forceinline__ uint64_t sb_base(const FmWideDev& fm, uint64_t blk, uint32_t c) { return fm.sb[(blk >> fm.sb_shift) * 4 + c]; }
+// Occ::get(r, dense symbol d) for the quad; a wide index has no dense symbols (bg_fm_build refuses them): never reached
+__device__ __forceinline__ uint32_t dense_rank(const FmDev& fm, uint32_t d, uint32_t r, uint32_t t) {
+    uint32_t o;
+    const uint4 v = bv_load(fm, d, r, t, o);
+    return quad_sum(bv_part(v, t, o));
+}
+__device__ __forceinline__ uint32_t dense_rank(const FmWideDev&, uint32_t, uint64_t, uint32_t) { return 0; }
 
 // SEEDS: the patterns are the seed windows of a batch of reads (seed-and-extend, seed_extend.hip) — query q is
 // seed q % S of read q / S: pat[pat_off[r] + k * stride ..+ seed_len) while it fits in the read (else an empty
@@ -255,15 +267,21 @@ constexpr uint8_t kTagDeferred = 0xFF;  // the fast kernels leave such a query t
 static_assert(kTagDeferred > BG_FM_PANIC, "the deferral mark must not collide with a BG_FM_* tag");
 constexpr uint32_t kFastSyms = 256;     // symbols of a pattern slot of the fast kernels (LDS)
 
-__device__ __forceinline__ uint32_t count_le64(const uint64_t* arr, uint32_t lo, uint32_t hi, uint64_t r) {
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (arr[mid] <= r)
-            lo = mid + 1;
-        else
-            hi = mid;
+// Query q of a launch is pat[off .. off + len): with SEEDS window q % S of read q / S — empty where it does not fit in the
+// read — else what lies between two offsets.  Returns len.  (The generic kernels of both layouts; the fast kernels'
+// fetch_all keeps the same rule written out, with its clamp of a long pattern to kFastSyms + 1: through this function
+// their seed-window instantiations compile to a different instruction order, profiles/fm_layout_refactor_isa.txt.)
+template <bool SEEDS>
+__device__ __forceinline__ uint32_t query_span(const uint64_t* __restrict__ pat_off, const SeedSrc& seeds, uint64_t q, uint64_t& off) {
+    if (SEEDS) {
+        const uint64_t rd = q / seeds.S;
+        const uint32_t k = (uint32_t)(q - rd * seeds.S);
+        const uint64_t o = pat_off[rd];
+        off = o + (uint64_t)k * seeds.stride;
+        return (uint64_t)k * seeds.stride + seeds.seed_len <= pat_off[rd + 1] - o ? seeds.seed_len : 0u;
     }
-    return lo;
+    off = pat_off[q];
+    return (uint32_t)(pat_off[q + 1] - off);
 }
 
 }  // namespace bgfm
@@ -287,9 +305,10 @@ struct bg_fm {
     bool text_owned = false;
     uint64_t n_text = 0;
     uint64_t bytes = 0;
-    // suffix array attached for Interval::occ / SuffixArray::get (K6, sa_locate.hip)
+    // suffix array attached for Interval::occ / SuffixArray::get (K6, sa_locate.hip); its entries are the layout's Pos:
+    // uint32 on a narrow index, uint64 on a wide one
     int sa_kind = 0;               // 0 none, 1 raw, 2 sampled
-    void* d_sa = nullptr;          // raw: uint32 SA[n]; sampled: uint32 sample[]
+    void* d_sa = nullptr;          // raw: SA[n]; sampled: sample[]
     void* d_extra_row = nullptr;   // sampled: rows kept because their BWT byte is the sentinel (sorted)
     void* d_extra_pos = nullptr;
     uint64_t n_sample = 0, n_extra = 0;
@@ -301,7 +320,8 @@ struct bg_fm {
     uint32_t less_len = 0;
     bool fmd_ok = false;  // the BWT is a word over dna::n_alphabet() + '$' (FMDIndex::from, fmindex.rs:323-327)
     uint16_t h_class[256] = {};  // host copy of the symbol classes (K7 picks its plain-DNA instantiation from them)
-    // 64-bit positions (fm_wide.hip): `wdev` instead of `dev` / `dev2`; the suffix array attached to it is uint64
+    // 64-bit positions (FmLayout<true>): `wdev` / `wdev2` instead of `dev` / `dev2`; the kernels that exist for both layouts
+    // (K5x, K6, K7, the builders) pick their instantiation from `wide`, the generic search is fm_wide.hip's
     bool wide = false;
     bgfm::FmWideDev wdev = {};
     void* d_sb = nullptr;
@@ -312,6 +332,12 @@ struct bg_fm {
     std::vector<uint64_t> h_less;
     uint32_t occ_k = 0;
 };
+// symbols of the indexed text, whichever layout holds it
+inline uint64_t fm_len(const bg_fm* fm) { return fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n; }
+// the byte value of each 2-bit code, code c in bits [8c, 8c + 8) (SeedSrc::code_bytes, K6, the BWT decoder)
+inline uint32_t fm_code_bytes(const bg_fm* fm) {
+    return (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 | (uint32_t)fm->code_byte[3] << 24;
+}
 int fm_decode_bwt_dev(const bg_fm* fm, uint8_t* d_out, hipStream_t st);  // fm_persist.hip: the handle's BWT bytes
 void fm_remember_inputs(bg_fm* fm, const uint8_t* alphabet, uint32_t n_sym, uint32_t occ_k, const uint64_t* less, uint32_t less_len);
 
@@ -322,7 +348,6 @@ int fm_wide_search_launch(bg_fm* fm, uint64_t n_q, const uint8_t* d_pat, const u
                           uint64_t* d_upper, uint32_t* d_matched_len, const bgfm::SeedSrc& src, hipStream_t st);
 // fm_step2.hip: the 2-step blocks behind a finished 64-bit index (best effort; synchronises the stream)
 void fm_build_step2_wide(bg_fm* fm, hipStream_t st);
-int fm_wide_sa_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st);
 // texts from this many symbols on take the 64-bit layout (tests lower it through the ctx option "fm_wide_from")
 uint64_t fm_wide_threshold(const bg_ctx* ctx);
 

@@ -131,15 +131,13 @@ int put_positions(Writer& w, const void* d_arr, uint64_t n, bool is64, void* pin
 // The BWT of a handle, read back out of its rank blocks into n bytes of device memory: the 2-bit codes turned into their
 // bytes, the listed exceptions (sentinels, stray N) put back over them; an index with dense symbols keeps the raw bytes.
 int fm_decode_bwt_dev(const bg_fm* fm, uint8_t* d_out, hipStream_t st) {
-    const uint64_t n = fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n;
+    const uint64_t n = fm_len(fm);
     if (!fm->wide && fm->d_bwt_raw) {
         BG_HIP(hipMemcpyAsync(d_out, fm->d_bwt_raw, n, hipMemcpyDeviceToDevice, st));
         return BG_OK;
     }
-    const uint32_t code_bytes = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
-                                (uint32_t)fm->code_byte[3] << 24;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1u << 20);
-    fmp_codes_to_bytes_kernel<<<dim3(grid), dim3(256), 0, st>>>((const uint32_t*)fm->d_blocks, n, code_bytes, d_out);
+    fmp_codes_to_bytes_kernel<<<dim3(grid), dim3(256), 0, st>>>((const uint32_t*)fm->d_blocks, n, fm_code_bytes(fm), d_out);
     const uint32_t n_exc = fm->wide ? fm->wdev.n_exc : fm->dev.n_exc;
     if (n_exc) {
         if (fm->wide)
@@ -162,7 +160,7 @@ extern "C" int bg_fm_save(const bg_fm* fm, const char* path) {
     if (!fm || !path || fm->alphabet.empty() || fm->h_less.empty()) return BG_ERR_INVALID_ARG;
     BG_HIP(hipSetDevice(fm->ctx->device));
     BG_HIP(hipDeviceSynchronize());  // (the handle is immutable once built: this only waits for a builder's last copies)
-    const uint64_t n = fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n;
+    const uint64_t n = fm_len(fm);
     Header h = {};
     h.n = n;
     h.occ_k = fm->occ_k;
@@ -338,7 +336,7 @@ extern "C" int bg_fm_load(bg_ctx* ctx, const char* path, bg_fm** out) {
 // deserialized index, fmindex.rs:311-329, reads the BWT; the C++ mirror's len() the text length)
 extern "C" int bg_fm_len(const bg_fm* fm, uint64_t* n) {
     if (!fm || !n) return BG_ERR_INVALID_ARG;
-    *n = fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n;
+    *n = fm_len(fm);
     return BG_OK;
 }
 extern "C" int bg_fm_less(const bg_fm* fm, uint64_t* less_out, uint32_t* less_len) {
@@ -356,7 +354,7 @@ extern "C" int bg_fm_bwt_dev(const bg_fm* fm, uint8_t* d_bwt, void* stream) {
 extern "C" int bg_fm_bwt(const bg_fm* fm, uint8_t* bwt) {
     if (!fm || !bwt) return BG_ERR_INVALID_ARG;
     BG_HIP(hipSetDevice(fm->ctx->device));
-    const uint64_t n = fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n;
+    const uint64_t n = fm_len(fm);
     uint8_t* d = nullptr;
     BG_HIP(hipMalloc((void**)&d, std::max<uint64_t>(n, 16)));
     int rc = fm_decode_bwt_dev(fm, d, nullptr);

@@ -28,11 +28,7 @@ struct Less4T {
 using Less4 = Less4T<uint32_t>;
 
 // (the helpers below serve both layouts: FmDev with uint32 positions, FmWideDev with uint64 positions and counters relative
-//  to a superblock — wide_base() adds the superblock's absolute count)
-__device__ __forceinline__ uint64_t wide_base(const FmDev&, uint64_t, uint32_t) { return 0; }
-__device__ __forceinline__ uint64_t wide_base(const FmWideDev& fm, uint64_t blk, uint32_t c) { return fm.sb[(blk >> fm.sb_shift) * 4 + c]; }
-__device__ __forceinline__ uint32_t exc_count_le(const FmDev& fm, uint32_t p) { return count_le(fm.exc_pos, 0u, fm.n_exc, p); }
-__device__ __forceinline__ uint32_t exc_count_le(const FmWideDev& fm, uint64_t p) { return count_le64(fm.exc_pos, 0u, fm.n_exc, p); }
+//  to a superblock — sb_base(), fm_kernels.h, adds the superblock's absolute count)
 
 template <typename Dev, typename P>
 __device__ __forceinline__ uint32_t fm_code_at(const Dev& fm, P j) {
@@ -43,7 +39,7 @@ __device__ __forceinline__ uint32_t fm_code_at(const Dev& fm, P j) {
 template <typename Dev, typename P>
 __device__ __forceinline__ bool fm_is_exc(const Dev& fm, P p) {
     if (!fm.n_exc) return false;
-    const uint32_t k = exc_count_le(fm, p);
+    const uint32_t k = count_le(fm.exc_pos, 0u, fm.n_exc, p);
     return k > 0 && fm.exc_pos[k - 1] == p;
 }
 // Occ(code c, i) by ONE thread: counter + the matches among symbols 0 .. i % 192 of the block
@@ -63,8 +59,8 @@ __device__ P fm_rank_thread(const Dev& fm, uint32_t c, P i) {
         uint32_t e = ~(blk[4 + full] ^ pat);
         n += (uint32_t)__popc(e & (e >> 1) & 0x55555555u & ((1u << (2 * rem)) - 1u));
     }
-    P r = (P)wide_base(fm, b, c) + n;
-    if (c == 0 && fm.n_exc) r -= exc_count_le(fm, i);  // exceptions sit in the stream as code 0
+    P r = (P)sb_base(fm, b, c) + n;
+    if (c == 0 && fm.n_exc) r -= count_le(fm.exc_pos, 0u, fm.n_exc, i);  // exceptions sit in the stream as code 0
     return r;
 }
 

@@ -1,19 +1,19 @@
-// FM index with 64-bit text positions (round 5): what lifts the engine's 2^32 - 2 symbol limit.
+// FM index with 64-bit text positions (round 5, what lifts the engine's 2^32 - 2 symbol limit): the generic search.
 //
 // The reference indexes with usize throughout — Interval { lower, upper } (/root/reference/src/data_structures/fmindex.rs:
 // 70-71), Occ's counters (bwt.rs:94-125), less (bwt.rs:186-199), suffix-array entries (suffix_array.rs:264) — so a text of
 // 4.3 G symbols and more is nothing special there; here the rank blocks, less[], l / r and the suffix-array samples were
-// uint32 in five kernels and two builders (rounds 1-4: BG_ERR_TOO_LARGE).  This file is the same search on the layout
-// fm_kernels.h describes under "64-bit positions": the 64-byte blocks of K5 with counters relative to a superblock, one
-// absolute 64-bit base per code and superblock, everything a position can reach in 64 bits.
+// uint32 in five kernels and two builders (rounds 1-4: BG_ERR_TOO_LARGE).  The layout fm_kernels.h describes under "64-bit
+// positions" — the 64-byte blocks of K5 with counters relative to a superblock, one absolute 64-bit base per code and
+// superblock, everything a position can reach in 64 bits — is served by the kernels that are one body over FmLayout<WIDE>
+// (the 2x fast search in fm_index.hip, K6 in sa_locate.hip, K7 in fmd_smems.hip, the builders); this file keeps what has a
+// schedule of its own on that layout, the generic search, its launcher, and fm_wide_threshold.
 //   (the index itself is laid out by fm_build.hip, the one builder of both layouts: the block kernel of the narrow index, a
 //    64-bit scan of the per-block counts, heads relative to the superblock's first block)
 //   fmw_search2x_kernel FMIndexable::backward_search (fmindex.rs:144-208), the generic search: two queries per quad, l and r
 //                       64-bit, Occ::get = base[superblock][code] + cnt[code] + popcount; byte, packed and seed-window
 //                       patterns.  fm_index.hip's fm_search decides when it runs: alone, or behind the 2x fast kernel
 //                       (fm_search_fast2x_kernel<WIDE>, on the 2-step blocks fm_step2.hip builds) for what that defers
-//   fmw_sampled_get_kernel / fmw_raw_get_kernel   Interval::occ over a SampledSuffixArray / a raw one (suffix_array.rs:
-//                       134-184) with 64-bit samples
 // Narrow indexes (n < 2^32 - 1) never come here: their kernels, layouts and speed are those of rounds 1-4.  A wide
 // index takes packed patterns, 2-step rank blocks, seed-and-extend and the FMD-index kernels (fmd_smems.hip,
 // through the entry points with 64-bit records).  What is NOT offered on one (BG_ERR_UNSUPPORTED): alphabets that need
@@ -30,14 +30,6 @@ using namespace bgfm;
 uint64_t fm_wide_threshold(const bg_ctx* ctx) { return ctx ? ctx->fm_wide_from : 0xFFFFFFFFull; }
 
 namespace {
-
-constexpr uint32_t kWideMaxExc = kMaxExcLds;
-
-// Occ::get(r, code) for the quad: the block's line is in `v` (lane t holds bytes [16t, 16t + 16)), `base` the superblock's
-// absolute count of the code
-__device__ __forceinline__ uint64_t wide_rank(const FmWideDev& fm, const uint4 v, uint32_t t, uint64_t blk, uint32_t o, uint32_t code) {
-    return fm.sb[(blk >> fm.sb_shift) * 4 + code] + (uint64_t)quad_sum(block_part(v, t, o, code));
-}
 
 // K5 on 64-bit positions: FMIndexable::backward_search (fmindex.rs:144-208) with TWO queries per quad (round 5; what
 // fm_search_fast2x_kernel is to the narrow index, fm_index.hip): a step is one dependent block access, eight wavefronts per
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(256) void fmw_search2x_kernel(FmWideDev fm, uint64_
     constexpr int U = 2;
     __shared__ uint16_t s_class[256];
     __shared__ uint64_t s_less[256];
-    __shared__ uint64_t s_exc[kWideMaxExc];
+    __shared__ uint64_t s_exc[kMaxExcLds];
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
         s_class[i] = fm.sym_class[i];
         // PACKED: entry c (< 4) is less[] of the byte that code c stands for
@@ -93,17 +85,7 @@ __global__ __launch_bounds__(256) void fmw_search2x_kernel(FmWideDev fm, uint64_
                 s.q += n_streams;
                 continue;
             }
-            uint32_t len;
-            if (SEEDS) {
-                const uint64_t rd = s.q / seeds.S;
-                const uint32_t k = (uint32_t)(s.q - rd * seeds.S);
-                const uint64_t o = pat_off[rd];
-                s.off = o + (uint64_t)k * seeds.stride;
-                len = (uint64_t)k * seeds.stride + seeds.seed_len <= pat_off[rd + 1] - o ? seeds.seed_len : 0u;
-            } else {
-                s.off = pat_off[s.q];
-                len = (uint32_t)(pat_off[s.q + 1] - s.off);
-            }
+            const uint32_t len = query_span<SEEDS>(pat_off, seeds, s.q, s.off);
             if (len) {
                 s.pos = len;
                 s.l = 0;
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(256) void fmw_search2x_kernel(FmWideDev fm, uint64_
             const uint32_t code = coded ? cls[u] : 0u;
             vr[u] = fm.blocks[br[u] * 4 + t];
             vl[u] = fm.blocks[bl[u] * 4 + t];
-            base_r[u] = fm.sb[(br[u] >> fm.sb_shift) * 4 + code];
+            base_r[u] = fm.sb[(br[u] >> fm.sb_shift) * 4 + code];  // (sb_base() written out: through the helper the loads are scheduled differently)
             base_l[u] = fm.sb[(bl[u] >> fm.sb_shift) * 4 + code];
         }
         // ---- phase B: one iteration of the loop at fmindex.rs:160-182 per stream
@@ -169,14 +151,14 @@ __global__ __launch_bounds__(256) void fmw_search2x_kernel(FmWideDev fm, uint64_
                 occ_r = base_r[u] + (uint64_t)quad_sum(block_part(vr[u], t, orr[u], cls[u]));
                 if (s.l > 0) occ_l = base_l[u] + (uint64_t)quad_sum(block_part(vl[u], t, ol[u], cls[u]));
                 if (cls[u] == 0 && fm.n_exc) {  // sparse exceptions sit in the stream as code 0
-                    occ_r -= count_le64(s_exc, 0u, fm.n_exc, s.r);
-                    if (s.l > 0) occ_l -= count_le64(s_exc, 0u, fm.n_exc, s.l - 1);
+                    occ_r -= count_le(s_exc, 0u, fm.n_exc, s.r);
+                    if (s.l > 0) occ_l -= count_le(s_exc, 0u, fm.n_exc, s.l - 1);
                 }
             } else if (cls[u] >= kClsSparse) {  // (no dense symbols on a wide index)
                 const uint32_t e = cls[u] - kClsSparse;
                 const uint32_t lo = fm.sparse_off[e], hi = fm.sparse_off[e + 1];
-                occ_r = count_le64(fm.exc_sym_pos, lo, hi, s.r) - lo;
-                if (s.l > 0) occ_l = count_le64(fm.exc_sym_pos, lo, hi, s.l - 1) - lo;
+                occ_r = count_le(fm.exc_sym_pos, lo, hi, s.r) - lo;
+                if (s.l > 0) occ_l = count_le(fm.exc_sym_pos, lo, hi, s.l - 1) - lo;
             }  // kClsZero: both stay 0
             const uint64_t pl = s.l, pr = s.r;
             if (!stop) {
@@ -209,110 +191,6 @@ __global__ __launch_bounds__(256) void fmw_search2x_kernel(FmWideDev fm, uint64_
     }
 }
 
-struct SaWideDev {
-    const uint64_t* sa;         // raw SA or the samples
-    const uint64_t* extra_row;  // sorted
-    const uint64_t* extra_pos;
-    const uint8_t* exc_byte;    // byte of exception e (parallel to FmWideDev::exc_pos)
-    uint32_t n_extra;
-    uint32_t rate;
-    uint32_t sentinel;
-    uint32_t code_byte;         // byte of code c in bits [8c, 8c+8)
-};
-
-__global__ __launch_bounds__(256) void fmw_raw_get_kernel(const uint64_t* __restrict__ sa, uint64_t n_text, uint64_t n, const uint64_t* index,
-                                                          uint64_t* pos_out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t r = index[i];
-    pos_out[i] = r < n_text ? sa[r] : BG_SA_NONE;
-}
-
-// SampledSuffixArray::get (suffix_array.rs:157-184): every row LF-walks until it reaches a sampled row or a row whose BWT
-// byte is the sentinel; a quad per row, the rank block and the word that holds bwt[pos] loaded together
-__global__ __launch_bounds__(256) void fmw_sampled_get_kernel(FmWideDev fm, SaWideDev sa, uint64_t n, const uint64_t* index, uint64_t* pos_out) {
-    __shared__ uint16_t s_class[256];
-    __shared__ uint64_t s_less[256];
-    __shared__ uint64_t s_exc[kWideMaxExc];
-    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
-        s_class[i] = fm.sym_class[i];
-        s_less[i] = fm.less[i];
-    }
-    for (uint32_t i = threadIdx.x; i < fm.n_exc; i += blockDim.x) s_exc[i] = fm.exc_pos[i];
-    __syncthreads();
-    const uint32_t t = threadIdx.x & 3;
-    const uint64_t n_quads = (uint64_t)gridDim.x * (blockDim.x >> 2);
-    uint64_t q = (uint64_t)blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);
-    const uint32_t* blocks32 = (const uint32_t*)fm.blocks;
-    bool active = false;
-    uint64_t pos = 0, offset = 0;
-    auto emit = [&](uint64_t v) {
-        if (t == 0) pos_out[q] = v;
-    };
-    auto fetch = [&]() {
-        active = false;
-        while (q < n) {
-            const uint64_t r = index[q];
-            if (r < fm.n) {
-                pos = r;
-                offset = 0;
-                active = true;
-                return;
-            }
-            emit(BG_SA_NONE);  // SuffixArray::get -> None
-            q += n_quads;
-        }
-    };
-    fetch();
-    while (__any(active)) {
-        if (active) {
-            if (pos % sa.rate == 0) {  // suffix_array.rs:162-164
-                emit(sa.sa[pos / sa.rate] + offset);
-                q += n_quads;
-                fetch();
-                continue;
-            }
-            const uint64_t pb = pos / kSymPerBlock, rb = (pos - 1) / kSymPerBlock;
-            const uint32_t po = (uint32_t)(pos - pb * kSymPerBlock), ro = (uint32_t)((pos - 1) - rb * kSymPerBlock);
-            const uint4 vr = fm.blocks[rb * 4 + t];
-            const uint32_t word = blocks32[pb * 16 + 4 + (po >> 4)];
-            const uint32_t code = (word >> (2 * (po & 15))) & 3u;
-            uint32_t c = (sa.code_byte >> (8 * code)) & 255u;
-            if (code == 0 && fm.n_exc) {  // sparse exceptions sit in the stream as code 0
-                const uint32_t e = count_le64(s_exc, 0u, fm.n_exc, pos);
-                if (e > 0 && s_exc[e - 1] == pos) c = sa.exc_byte[e - 1];
-            }
-            if (c == sa.sentinel) {  // suffix_array.rs:168-175
-                uint32_t lo = 0, hi = sa.n_extra;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (sa.extra_row[mid] < pos)
-                        lo = mid + 1;
-                    else
-                        hi = mid;
-                }
-                emit(lo < sa.n_extra && sa.extra_row[lo] == pos ? sa.extra_pos[lo] + offset : BG_SA_PANIC);
-                q += n_quads;
-                fetch();
-                continue;
-            }
-            // pos = less[c] + occ.get(bwt, pos - 1, c)  (suffix_array.rs:177-178)
-            const uint32_t cls = s_class[c];
-            uint64_t occ = 0;
-            if (cls < 4) {
-                occ = wide_rank(fm, vr, t, rb, ro, cls);
-                if (cls == 0 && fm.n_exc) occ -= count_le64(s_exc, 0u, fm.n_exc, pos - 1);
-            } else if (cls != kClsPanic && cls >= kClsSparse) {
-                const uint32_t e = cls - kClsSparse;
-                const uint32_t lo = fm.sparse_off[e], hi = fm.sparse_off[e + 1];
-                occ = count_le64(fm.exc_sym_pos, lo, hi, pos - 1) - lo;
-            }
-            pos = s_less[c] + occ;
-            offset += 1;
-        }
-    }
-}
-
 }  // namespace
 
 template <bool SEEDS, bool PACKED, bool DEFER>
@@ -337,25 +215,3 @@ FMW_SEARCH_LAUNCH(true, false, true)
 FMW_SEARCH_LAUNCH(false, true, false)
 FMW_SEARCH_LAUNCH(false, true, true)
 #undef FMW_SEARCH_LAUNCH
-
-int fm_wide_sa_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st) {
-    if (n == 0) return BG_OK;
-    if (fm->sa_kind == 1) {
-        fmw_raw_get_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint64_t*)fm->d_sa, fm->wdev.n, n, d_index, d_pos);
-    } else {
-        SaWideDev sa = {};
-        sa.sa = (const uint64_t*)fm->d_sa;
-        sa.extra_row = (const uint64_t*)fm->d_extra_row;
-        sa.extra_pos = (const uint64_t*)fm->d_extra_pos;
-        sa.exc_byte = (const uint8_t*)fm->d_exc_byte;
-        sa.n_extra = (uint32_t)fm->n_extra;
-        sa.rate = fm->sa_rate;
-        sa.sentinel = fm->sa_sentinel;
-        sa.code_byte = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
-                       (uint32_t)fm->code_byte[3] << 24;
-        const uint64_t blocks = std::min<uint64_t>((n + 63) / 64, 256 * 8);
-        fmw_sampled_get_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->wdev, sa, n, d_index, d_pos);
-    }
-    BG_HIP(hipGetLastError());
-    return BG_OK;
-}

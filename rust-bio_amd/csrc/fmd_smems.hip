@@ -43,18 +43,6 @@ struct FmdArgsT {
     uint32_t list_cap;
 };
 
-
-__device__ __forceinline__ uint64_t k7_base(const FmDev&, uint64_t, uint32_t) { return 0; }
-__device__ __forceinline__ uint64_t k7_base(const FmWideDev& fm, uint64_t blk, uint32_t c) { return fm.sb[(blk >> fm.sb_shift) * 4 + c]; }
-__device__ __forceinline__ uint32_t k7_count_le(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t r) { return count_le(a, lo, hi, r); }
-__device__ __forceinline__ uint32_t k7_count_le(const uint64_t* a, uint32_t lo, uint32_t hi, uint64_t r) { return count_le64(a, lo, hi, r); }
-__device__ __forceinline__ uint32_t k7_dense(const FmDev& fm, uint32_t d, uint32_t r, uint32_t t) {
-    uint32_t o;
-    const uint4 v = bv_load(fm, d, r, t, o);
-    return quad_sum(bv_part(v, t, o));
-}
-__device__ __forceinline__ uint32_t k7_dense(const FmWideDev&, uint32_t, uint64_t, uint32_t) { return 0; }  // (no dense symbols there)
-
 // PLAIN: 0 the general extension, 1 plain DNA (straight line), 2 plain DNA whose '$' occurs at most twice and is the only listed
 // symbol (T$, T$R$: its rows in registers) — chosen by the host from the index's classes (smems_dev)
 template <bool WIDE, int PLAIN = 0>
@@ -80,7 +68,7 @@ struct Ctx {
     // LDS lists per extension.  small_dollar false: the searches.
     P dollar_row[2] = {~(P)0, ~(P)0};
 
-    __device__ uint32_t exc_le(P r) const { return k7_count_le(s_exc, 0u, a.fm.n_exc, r); }
+    __device__ uint32_t exc_le(P r) const { return count_le(s_exc, 0u, a.fm.n_exc, r); }
     __device__ P less_of(uint32_t s) {
         if (s >= a.less_len) {  // index out of bounds in the reference
             panic = true;
@@ -94,11 +82,11 @@ struct Ctx {
             panic = true;
             return 0;
         }
-        if (cls >= kClsDense) return k7_dense(a.fm, cls - kClsDense, r, t);  // a genome with many N: ranked in bit vectors
+        if (cls >= kClsDense) return dense_rank(a.fm, cls - kClsDense, r, t);  // a genome with many N: ranked in bit vectors
         if (cls >= kClsSparse) {
             const uint32_t e = cls - kClsSparse;
             const uint32_t lo = s_sparse_off[e], hi = s_sparse_off[e + 1];
-            return k7_count_le(s_exc_sym, lo, hi, r) - lo;
+            return count_le(s_exc_sym, lo, hi, r) - lo;
         }
         return 0;  // in the alphabet, never in the BWT
     }
@@ -157,8 +145,8 @@ struct Ctx {
             const uint32_t ctrL[4] = {quad_lane0(vL.x), quad_lane0(vL.y), quad_lane0(vL.z), quad_lane0(vL.w)};
 #pragma unroll
             for (uint32_t k = 0; k < 4; k++) {
-                cR[k] = (P)k7_base(a.fm, bR, k) + ctrR[k] + ((pkR >> (8 * k)) & 0xFFu);
-                cL[k] = (P)k7_base(a.fm, bL, k) + ctrL[k] + ((pkL >> (8 * k)) & 0xFFu);
+                cR[k] = (P)sb_base(a.fm, bR, k) + ctrR[k] + ((pkR >> (8 * k)) & 0xFFu);
+                cL[k] = (P)sb_base(a.fm, bL, k) + ctrL[k] + ((pkL >> (8 * k)) & 0xFFu);
             }
         }
         const bool has_l = iv.lower > 0;
@@ -184,8 +172,8 @@ struct Ctx {
             occR[0] = occL[0] = 0;
             if (plain_dollar != 0xFFFFu) {
                 const uint32_t lo = s_sparse_off[plain_dollar], hi = s_sparse_off[plain_dollar + 1];
-                occR[0] = k7_count_le(s_exc_sym, lo, hi, posR) - lo;
-                occL[0] = k7_count_le(s_exc_sym, lo, hi, posL) - lo;
+                occR[0] = count_le(s_exc_sym, lo, hi, posR) - lo;
+                occL[0] = count_le(s_exc_sym, lo, hi, posL) - lo;
             }
             plain_tail(cR, cL, occR, occL, has_l, iv, sym, r);
             return r;

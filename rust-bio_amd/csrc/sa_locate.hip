@@ -8,6 +8,8 @@
 // reference).  The walk reuses K5's machinery: a quad of 4 lanes per row, one 64-byte block per
 // rank; the BWT byte of the row is read from the same 2-bit stream (+ the exception list), both
 // loads of a step are issued together, and quads fetch the next row as soon as theirs resolves.
+// Both kernels are templates over the index layout (FmLayout<WIDE>, fm_kernels.h): uint32 positions and
+// entries on a narrow index, uint64 on a wide one; launch_get picks the instantiation.
 #include <algorithm>
 
 #include "fm_kernels.h"
@@ -16,19 +18,22 @@ using namespace bgfm;
 
 namespace {
 
-struct SaDev {
-    const uint32_t* sa;         // raw SA or the samples
-    const uint32_t* extra_row;  // sorted
-    const uint32_t* extra_pos;
-    const uint8_t* exc_byte;    // byte of exception e (parallel to FmDev::exc_pos)
+// the attached suffix array as K6 reads it; P is the layout's position type
+template <typename P>
+struct SaDevT {
+    const P* sa;                // raw SA or the samples
+    const P* extra_row;         // sorted
+    const P* extra_pos;
+    const uint8_t* exc_byte;    // byte of exception e (parallel to the index's exc_pos)
     uint32_t n_extra;
     uint32_t rate;
     uint32_t sentinel;
     uint32_t code_byte;         // byte of code c in bits [8c, 8c+8)
 };
 
-__global__ __launch_bounds__(256) void sa_raw_get_kernel(const uint32_t* __restrict__ sa, uint32_t n_text, uint64_t n,
-                                                         const uint64_t* index, uint64_t* pos_out) {
+template <typename P>
+__global__ __launch_bounds__(256) void sa_raw_get_kernel(const P* __restrict__ sa, P n_text, uint64_t n, const uint64_t* index,
+                                                         uint64_t* pos_out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t r = index[i];
@@ -52,18 +57,23 @@ __global__ __launch_bounds__(256) void interval_rows_kernel(uint64_t n_iv, const
     rows[k] = lower[lo] + (k - out_off[lo]);
 }
 
-__global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa, uint64_t n, const uint64_t* index,
-                                                             uint64_t* pos_out) {
+// One body for both layouts (FmLayout<WIDE>).  Only a narrow index can have dense symbols (bg_fm_build refuses them on
+// 64-bit positions): the read of bwt_raw and the bit-vector rank exist in the narrow instantiation alone.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void sa_sampled_get_kernel(typename FmLayout<WIDE>::Dev fm, SaDevT<typename FmLayout<WIDE>::Pos> sa,
+                                                             uint64_t n, const uint64_t* index, uint64_t* pos_out) {
+    using P = typename FmLayout<WIDE>::Pos;
     __shared__ uint16_t s_class[256];
-    __shared__ uint32_t s_less[256];
-    __shared__ uint32_t s_exc[kMaxExcLds];
+    __shared__ P s_less[256];
+    __shared__ P s_exc[kMaxExcLds];
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
         s_class[i] = fm.sym_class[i];
         s_less[i] = fm.less[i];
     }
     for (uint32_t i = threadIdx.x; i < fm.n_exc; i += blockDim.x) s_exc[i] = fm.exc_pos[i];  // n_exc <= kMaxExcLds
     __syncthreads();
-    const bool raw_bwt = fm.bwt_raw != nullptr;  // dense symbols exist: the stream's code 0 does not say which byte
+    const uint8_t* bwt_raw = nullptr;  // dense symbols exist: the stream's code 0 does not say which byte
+    if constexpr (!WIDE) bwt_raw = fm.bwt_raw;
 
     const uint32_t t = threadIdx.x & 3;
     const uint64_t n_quads = (uint64_t)gridDim.x * (blockDim.x >> 2);
@@ -71,7 +81,7 @@ __global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa,
     const uint32_t* blocks32 = (const uint32_t*)fm.blocks;
 
     bool active = false;
-    uint32_t pos = 0, offset = 0;
+    P pos = 0, offset = 0;
     auto emit = [&](uint64_t v) {
         if (t == 0) pos_out[q] = v;
     };
@@ -80,7 +90,7 @@ __global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa,
         while (q < n) {
             const uint64_t r = index[q];
             if (r < fm.n) {
-                pos = (uint32_t)r;
+                pos = (P)r;
                 offset = 0;
                 active = true;
                 return;
@@ -100,12 +110,12 @@ __global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa,
                 continue;
             }
             // both loads of the step: the block of rank(pos - 1, .) and the word holding bwt[pos]
-            const uint32_t pb = pos / kSymPerBlock, po = pos - pb * kSymPerBlock;
-            const uint32_t rb = (pos - 1) / kSymPerBlock, ro = (pos - 1) - rb * kSymPerBlock;
+            const P pb = pos / kSymPerBlock, rb = (pos - 1) / kSymPerBlock;
+            const uint32_t po = (uint32_t)(pos - pb * kSymPerBlock), ro = (uint32_t)((pos - 1) - rb * kSymPerBlock);
             const uint4 vr = fm.blocks[(uint64_t)rb * 4 + t];
             uint32_t c;
-            if (raw_bwt) {
-                c = fm.bwt_raw[pos];
+            if (bwt_raw) {
+                c = bwt_raw[pos];
             } else {
                 const uint32_t word = blocks32[(uint64_t)pb * 16 + 4 + (po >> 4)];
                 const uint32_t code = (word >> (2 * (po & 15))) & 3u;
@@ -131,15 +141,13 @@ __global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa,
             }
             // pos = less[c] + occ.get(bwt, pos - 1, c)  (suffix_array.rs:177-178)
             const uint32_t cls = s_class[c];
-            uint32_t occ = 0;
+            P occ = 0;
             if (cls < 4) {
-                occ = quad_sum(block_part(vr, t, ro, cls));
+                occ = (P)sb_base(fm, rb, cls) + quad_sum(block_part(vr, t, ro, cls));
                 if (cls == 0 && fm.n_exc) occ -= count_le(s_exc, 0u, fm.n_exc, pos - 1);
             } else if (cls == kClsPanic) {
-            } else if (cls >= kClsDense) {
-                uint32_t o;
-                const uint4 v = bv_load(fm, cls - kClsDense, pos - 1, t, o);
-                occ = quad_sum(bv_part(v, t, o));
+            } else if (!WIDE && cls >= kClsDense) {
+                occ = dense_rank(fm, cls - kClsDense, pos - 1, t);
             } else if (cls >= kClsSparse) {
                 const uint32_t e = cls - kClsSparse;
                 const uint32_t lo = fm.sparse_off[e], hi = fm.sparse_off[e + 1];
@@ -151,54 +159,48 @@ __global__ __launch_bounds__(256) void sa_sampled_get_kernel(FmDev fm, SaDev sa,
     }
 }
 
-int launch_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st) {
-    if (n == 0) return BG_OK;
-    if (fm->wide) return fm_wide_sa_get(fm, n, d_index, d_pos, st);  // 64-bit positions: fm_wide.hip
+template <bool WIDE>
+int launch_get(bg_fm* fm, const typename FmLayout<WIDE>::Dev& dev, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st) {
+    using P = typename FmLayout<WIDE>::Pos;
     if (fm->sa_kind == 1) {
-        sa_raw_get_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t*)fm->d_sa, fm->dev.n, n,
-                                                                                d_index, d_pos);
+        sa_raw_get_kernel<P><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const P*)fm->d_sa, dev.n, n, d_index, d_pos);
     } else {
-        SaDev sa = {};
-        sa.sa = (const uint32_t*)fm->d_sa;
-        sa.extra_row = (const uint32_t*)fm->d_extra_row;
-        sa.extra_pos = (const uint32_t*)fm->d_extra_pos;
+        SaDevT<P> sa = {};
+        sa.sa = (const P*)fm->d_sa;
+        sa.extra_row = (const P*)fm->d_extra_row;
+        sa.extra_pos = (const P*)fm->d_extra_pos;
         sa.exc_byte = (const uint8_t*)fm->d_exc_byte;
         sa.n_extra = (uint32_t)fm->n_extra;
         sa.rate = fm->sa_rate;
         sa.sentinel = fm->sa_sentinel;
-        sa.code_byte = (uint32_t)fm->code_byte[0] | (uint32_t)fm->code_byte[1] << 8 | (uint32_t)fm->code_byte[2] << 16 |
-                       (uint32_t)fm->code_byte[3] << 24;
-        uint64_t blocks = std::min<uint64_t>((n + 63) / 64, 256 * 8);
-        sa_sampled_get_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(fm->dev, sa, n, d_index, d_pos);
+        sa.code_byte = fm_code_bytes(fm);
+        const uint64_t blocks = std::min<uint64_t>((n + 63) / 64, 256 * 8);
+        sa_sampled_get_kernel<WIDE><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(dev, sa, n, d_index, d_pos);
     }
     BG_HIP(hipGetLastError());
     return BG_OK;
 }
+int launch_get(bg_fm* fm, uint64_t n, const uint64_t* d_index, uint64_t* d_pos, hipStream_t st) {
+    if (n == 0) return BG_OK;
+    return fm->wide ? launch_get<true>(fm, fm->wdev, n, d_index, d_pos, st) : launch_get<false>(fm, fm->dev, n, d_index, d_pos, st);
+}
 
-// 64-bit index: the entries stay uint64 (checked against the text's length like the narrow ones)
-int upload64(void** dptr, const uint64_t* src, uint64_t count, uint64_t limit, uint64_t* bytes) {
+// the caller's uint64 entries as the layout's position type T, each checked against `limit` (the text's length)
+template <typename T>
+int upload(void** dptr, const uint64_t* src, uint64_t count, uint64_t limit, uint64_t* bytes) {
     for (uint64_t i = 0; i < count; i++)
         if (src[i] >= limit) return BG_ERR_INVALID_ARG;
-    hipFree(*dptr);
-    *dptr = nullptr;
-    BG_HIP(hipMalloc(dptr, std::max<uint64_t>(count * 8, 16)));
-    if (count) BG_HIP(hipMemcpy(*dptr, src, count * 8, hipMemcpyHostToDevice));
-    *bytes += std::max<uint64_t>(count * 8, 16);
-    return BG_OK;
-}
-inline uint64_t fm_len(const bg_fm* fm) { return fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n; }
-
-int upload32(void** dptr, const uint64_t* src, uint64_t count, uint64_t limit, uint64_t* bytes) {
-    std::vector<uint32_t> tmp(count);
-    for (uint64_t i = 0; i < count; i++) {
-        if (src[i] >= limit) return BG_ERR_INVALID_ARG;
-        tmp[i] = (uint32_t)src[i];
+    std::vector<T> narrowed;
+    const void* h = src;
+    if (sizeof(T) != sizeof(uint64_t)) {
+        narrowed.assign(src, src + count);
+        h = narrowed.data();
     }
     hipFree(*dptr);
     *dptr = nullptr;
-    BG_HIP(hipMalloc(dptr, std::max<uint64_t>(count * 4, 16)));
-    if (count) BG_HIP(hipMemcpy(*dptr, tmp.data(), count * 4, hipMemcpyHostToDevice));
-    *bytes += std::max<uint64_t>(count * 4, 16);
+    BG_HIP(hipMalloc(dptr, std::max<uint64_t>(count * sizeof(T), 16)));
+    if (count) BG_HIP(hipMemcpy(*dptr, h, count * sizeof(T), hipMemcpyHostToDevice));
+    *bytes += std::max<uint64_t>(count * sizeof(T), 16);
     return BG_OK;
 }
 
@@ -207,7 +209,7 @@ int upload32(void** dptr, const uint64_t* src, uint64_t count, uint64_t limit, u
 extern "C" int bg_fm_set_suffix_array(bg_fm* fm, const uint64_t* sa, uint64_t n) {
     if (!fm || !sa || n != fm_len(fm)) return BG_ERR_INVALID_ARG;
     BG_HIP(hipSetDevice(fm->ctx->device));
-    int rc = (fm->wide ? upload64 : upload32)(&fm->d_sa, sa, n, n, &fm->bytes);
+    int rc = (fm->wide ? upload<uint64_t> : upload<uint32_t>)(&fm->d_sa, sa, n, n, &fm->bytes);
     if (rc) return rc;
     fm->sa_kind = 1;
     return BG_OK;
@@ -223,7 +225,7 @@ extern "C" int bg_fm_set_sampled_suffix_array(bg_fm* fm, const uint64_t* sample,
         if (extra_rows[i] <= extra_rows[i - 1]) return BG_ERR_INVALID_ARG;  // sorted, unique
     BG_HIP(hipSetDevice(fm->ctx->device));
     int rc;
-    auto up = fm->wide ? upload64 : upload32;
+    auto up = fm->wide ? upload<uint64_t> : upload<uint32_t>;
     if ((rc = up(&fm->d_sa, sample, n_sample, n, &fm->bytes))) return rc;
     if ((rc = up(&fm->d_extra_row, extra_rows, n_extra, n, &fm->bytes))) return rc;
     if ((rc = up(&fm->d_extra_pos, extra_pos, n_extra, n, &fm->bytes))) return rc;

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void se_best_kernel(SeedPass P, SeedOut O, uin
 }  // namespace
 
 extern "C" int bg_fm_set_text(bg_fm* fm, const uint8_t* text, uint64_t n) {
-    if (!fm || !text || n != (fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n)) return BG_ERR_INVALID_ARG;
+    if (!fm || !text || n != fm_len(fm)) return BG_ERR_INVALID_ARG;
     BG_HIP(hipSetDevice(fm->ctx->device));
     if (fm->text_owned) hipFree(fm->d_text);
     fm->d_text = nullptr;
@@ -350,7 +350,7 @@ extern "C" int bg_fm_set_text(bg_fm* fm, const uint8_t* text, uint64_t n) {
 }
 
 extern "C" int bg_fm_set_text_dev(bg_fm* fm, const uint8_t* d_text, uint64_t n) {
-    if (!fm || !d_text || n != (fm->wide ? fm->wdev.n : (uint64_t)fm->dev.n)) return BG_ERR_INVALID_ARG;
+    if (!fm || !d_text || n != fm_len(fm)) return BG_ERR_INVALID_ARG;
     if (fm->text_owned) hipFree(fm->d_text);
     fm->d_text = (void*)d_text;
     fm->text_owned = false;
@@ -760,7 +760,7 @@ int se_reseed(SeedRun& R, const SeedPassRun& p, uint8_t* strand1, uint64_t n_ind
 // The call's checks, its passes, its totals.
 int se_run(const SeedCall& c) {
     if (!c.fm || !c.sc || (!c.prm && !c.smem && !c.tiered) || (c.n_reads && (!c.read_off || !c.hits))) return BG_ERR_INVALID_ARG;
-    const uint64_t n_index = c.fm->wide ? c.fm->wdev.n : (uint64_t)c.fm->dev.n;
+    const uint64_t n_index = fm_len(c.fm);
     const bg_smem_seed_params_t* sp = c.tiered ? &c.tiered->smem : c.smem;  // the SMEM seeds of the call, if it has any
     const bg_seed_params_t* wp = c.tiered ? &c.tiered->window : c.prm;      // its window seeds, if it has any
     if (sp) {  // an FMD index over T$R$ (FMDIndex::from's assert, as K7 checks it)
