@@ -1030,8 +1030,8 @@ int bg_fasta_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t len, bg_fast
  * bg_sam_header (host only, no GPU) writes "@HD\tVN:1.6\tSO:unsorted\n", one "@SQ\tSN:<name>\tLN:<len>\n" per contig and
  * "@PG\tID:biogpu\tPN:biogpu\n"; *out_bytes receives the length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if
  * out_cap is too small (nothing written).
- * Not covered: BAM / BGZF, supplementary (chimeric) records, read groups.  (Coordinate order and duplicate flags: the section
- * below.)  (Mate rescue happens before this call:
+ * Not covered: supplementary (chimeric) records, read groups.  (Coordinate order and duplicate flags: the section below; BAM
+ * records and BGZF framing: the one after it.)  (Mate rescue happens before this call:
  * bg_seed_extend_pairs_rescue_batch[_dev]; a rescued hit is written like any other.)  Known limit: the
  * seed-and-extend windows know nothing of contig boundaries, so a read whose best alignment crosses one is reported
  * unmapped here (not clipped to the contig) even where a slightly worse alignment inside one contig exists. */
@@ -1122,7 +1122,7 @@ int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, co
  *
  * bg_sam_header_so: bg_sam_header with the sort order named: BG_SAM_SO_UNSORTED gives exactly bg_sam_header's bytes,
  *   BG_SAM_SO_COORDINATE the same with SO:coordinate; anything else is BG_ERR_INVALID_ARG.
- * Not covered: BAM / BGZF, queryname order, optical duplicates, duplicate sets across calls, UMIs. */
+ * Not covered: queryname order, optical duplicates, duplicate sets across calls, UMIs. */
 enum { BG_SAM_SO_UNSORTED = 0, BG_SAM_SO_COORDINATE = 1 };
 typedef struct {
     uint32_t flags;         /* BG_SAM_PAIRED or 0; anything else BG_ERR_INVALID_ARG */
@@ -1158,6 +1158,72 @@ int bg_sam_sort(bg_ctx* ctx, uint64_t n_slots, const uint64_t* key, const char* 
                 char* out, uint64_t out_cap, uint64_t* out_off, uint64_t* perm);
 int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, char* out,
                      uint64_t out_cap, uint64_t* out_bytes);
+
+/* ---- BAM records and BGZF framing (bam_emit.hip, bgzf.hip; the bodies in csrc/bam_rule.h) ------------------------------
+ * What every tool behind a mapper reads, from the same hits, without the text in between:
+ *   bg_bam_header            "BAM\1", the SAM header text, the reference table (host only, no GPU)
+ *   bg_bam_emit_batch[_dev]  one BAM record per hit slot
+ *   bg_bgzf_frame[_dev]      any byte stream cut into BGZF blocks
+ * BAM records are variable-length records like SAM lines: bg_sam_sort[_dev] sorts them with bg_sam_sort_keys[_dev]'s keys as
+ * they are.  A file is the framed header followed by the framed records with BG_BGZF_EOF (blocks are independent).
+ *
+ * bg_bam_header: arguments as bg_sam_header_so.  Writes "BAM\1", l_text, the bytes of bg_sam_header_so for the same
+ *   arguments (no NUL added), n_ref, and per contig l_name = name_len + 1, the name, a NUL and l_ref; every integer a
+ *   little-endian int32.  Sizing call and BG_ERR_OPS_CAP as bg_sam_header.  A contig with len > 2^31 - 1 is legal SAM but has
+ *   no l_ref: BG_ERR_UNSUPPORTED.
+ *
+ * bg_bam_emit_batch[_dev]: the arguments, the conventions and the BG_ERR_INVALID_ARG list of bg_sam_emit_dup_batch[_dev]
+ *   (dup optional); out is bytes: one contiguous buffer, out_off with n_reads * K + 1 entries, a slot that writes no line has
+ *   length 0; a length pass, a scan, one read-back of the total with one stream synchronisation; out == NULL with
+ *   out_cap == 0 sizes; BG_ERR_OPS_CAP before a byte is written; byte pointers at any address.
+ *   THE RULE: the record of a slot is the BAM encoding (SAM v1.6, section 4.2) of the SAM line bg_sam_emit_dup_batch writes
+ *   for that slot.
+ *     block_size           the record's length minus 4
+ *     refID / next_refID   the contig index of RNAME / RNEXT; "=" resolved to the index, "*" gives -1
+ *     pos / next_pos       POS - 1 / PNEXT - 1 (-1 for 0)
+ *     tlen, mapq, flag     the line's
+ *     bin                  the specification's reg2bin(pos, end), end = pos + the reference bases the CIGAR consumes, or
+ *                          pos + 1 where that is 0 or the line has no CIGAR; pos = -1 gives 4680
+ *     read_name            QNAME and a NUL; "*" stays "*"
+ *     cigar                len << 4 | op with MIDNSHP=X -> 0 .. 8, on the letters bg_cigar_batch_dev(hard_clip = 0) writes;
+ *                          "*" gives n_cigar_op = 0.  More than 65 535 operations: n_cigar_op = 2 holds <l_seq>S<reference
+ *                          length>N and the operations go into a CG:B:I tag behind the other tags (section 4.2.2)
+ *     seq                  4 bits a base, high nibble first, codes from "=ACMGRSVTWYHKDBN", lower case as upper case, every
+ *                          other byte 15, an odd length padded with 0; "*" gives l_seq = 0
+ *     qual                 q - 33 modulo 256 per byte; "*" with l_seq > 0 gives l_seq bytes 0xFF
+ *     tags                 in the line's order.  AS, XS, NM: the smallest integer type that holds the value (htslib's parse
+ *                          rule): c, s, i for a negative one, C, S, I otherwise.  MD: Z with a NUL.
+ *   Not representable: a slot whose QNAME exceeds 254 bytes; a slot that writes a line on, or borrows RNAME from, or names as
+ *   RNEXT a contig with len > 2^31 - 1.  The length pass counts such slots (they count 0 bytes) and the count comes back with
+ *   the total; the call then returns BG_ERR_UNSUPPORTED before a byte is written, with *out_bytes set.
+ *
+ * bg_bgzf_frame[_dev] knows nothing of BAM.  The input is cut into payloads of 65 280 bytes (0xff00, htslib's), the last one
+ *   shorter; each becomes one block: the 18-byte gzip header (MTIME 0, XFL 0, OS 255, the BC subfield with BSIZE - 1), a stored
+ *   deflate block (01, LEN, NLEN, the payload), CRC-32 and ISIZE — 31 bytes around the payload, 65 311 for a full block.  This
+ *   is htslib's level 0; every BGZF reader accepts it.  out_bytes = in_bytes + 31 * ceil(in_bytes / 65280), plus 28 for the
+ *   end-of-file block with BG_BGZF_EOF; in_bytes == 0 gives no block (and the end-of-file block if asked).  Every offset is
+ *   closed-form: byte i of the input is byte i + 31 * (i / 65280) + 23 of the output.  Nothing is read back; the device
+ *   flavour is asynchronous on `stream`.  out == NULL with out_cap == 0 sizes; BG_ERR_OPS_CAP if out_cap is too small (nothing
+ *   written); BG_ERR_INVALID_ARG: unknown flag bits, a null ctx or out_bytes, a null in with in_bytes > 0.  d_in and d_out may
+ *   be at any address and must not overlap.
+ * Not covered: deflate compression, BAI / CSI indexes, read groups, supplementary records. */
+enum { BG_BGZF_EOF = 1 };
+int bg_bam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, uint8_t* out,
+                  uint64_t out_cap, uint64_t* out_bytes);
+int bg_bam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* d_contigs,
+                          uint64_t n_contigs, const char* d_names, const uint8_t* d_fastq_text, const bg_fastq_record_t* d_recs,
+                          const uint8_t* d_seq, const uint8_t* d_qual, const bg_seed_hit_t* d_hits, const uint8_t* d_strand,
+                          const uint8_t* d_ops, const bg_multi_hit_t* d_multi, const bg_pair_hit_t* d_pairs, const uint8_t* d_dup,
+                          uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* out_bytes, void* stream);
+int bg_bam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs,
+                      uint64_t n_contigs, const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs,
+                      const uint8_t* seq, const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand,
+                      const uint8_t* ops, const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, const uint8_t* dup, uint8_t* out,
+                      uint64_t out_cap, uint64_t* out_off, uint64_t* out_bytes);
+int bg_bgzf_frame_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                      uint64_t* out_bytes, void* stream);
+int bg_bgzf_frame(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t flags, uint8_t* out, uint64_t out_cap,
+                  uint64_t* out_bytes);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

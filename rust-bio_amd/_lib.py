@@ -170,6 +170,7 @@ assert C.sizeof(SAM_PARAMS) == 8, C.sizeof(SAM_PARAMS)
 MARKDUP_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("max_hits", "<u4"), ("phred_offset", "<u4"), ("min_qual", "<u4")])
 assert MARKDUP_PARAMS_DTYPE.itemsize == 16, MARKDUP_PARAMS_DTYPE.itemsize
 SAM_SO_UNSORTED, SAM_SO_COORDINATE = 0, 1
+BGZF_EOF = 1  # BG_BGZF_EOF
 
 # bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
@@ -221,6 +222,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_sam_header", "bg_sam_emit_batch", "bg_sam_emit_batch_dev",
            "bg_sam_markdup", "bg_sam_markdup_dev", "bg_sam_emit_dup_batch", "bg_sam_emit_dup_batch_dev", "bg_sam_sort_keys",
            "bg_sam_sort_keys_dev", "bg_sam_sort", "bg_sam_sort_dev", "bg_sam_header_so",
+           "bg_bam_header", "bg_bam_emit_batch", "bg_bam_emit_batch_dev", "bg_bgzf_frame", "bg_bgzf_frame_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -393,6 +395,11 @@ def lib():
         L.bg_sam_sort_dev.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, vp, vp]
         L.bg_sam_sort.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, vp]
         L.bg_sam_header_so.argtypes = [vp, u64, vp, i32, vp, u64, C.POINTER(u64)]
+        L.bg_bam_header.argtypes = [vp, u64, vp, i32, vp, u64, C.POINTER(u64)]
+        L.bg_bam_emit_batch_dev.argtypes = L.bg_sam_emit_dup_batch_dev.argtypes
+        L.bg_bam_emit_batch.argtypes = L.bg_sam_emit_dup_batch.argtypes
+        L.bg_bgzf_frame_dev.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
+        L.bg_bgzf_frame.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

@@ -486,11 +486,14 @@ extern "C" int bg_sam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint6
                                      d_multi, d_pairs, nullptr, d_out, out_cap, d_out_off, out_bytes, stream);
 }
 
-extern "C" int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
-                                     const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
-                                     const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
-                                     const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, const uint8_t* dup, char* out, uint64_t out_cap,
-                                     uint64_t* out_off, uint64_t* out_bytes) {
+// the host flavour of a writer: `dev` (this file's, or bam_emit.hip's) between an upload and a download
+typedef int (*sam_emit_dev_fn)(bg_fm*, const bg_sam_params_t*, uint64_t, const bg_sam_contig_t*, uint64_t, const char*, const uint8_t*,
+                               const bg_fastq_record_t*, const uint8_t*, const uint8_t*, const bg_seed_hit_t*, const uint8_t*, const uint8_t*,
+                               const bg_multi_hit_t*, const bg_pair_hit_t*, const uint8_t*, char*, uint64_t, uint64_t*, uint64_t*, void*);
+static int sam_emit_host(sam_emit_dev_fn dev, bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs,
+                         uint64_t n_contigs, const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
+                         const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops, const bg_multi_hit_t* multi,
+                         const bg_pair_hit_t* pairs, const uint8_t* dup, char* out, uint64_t out_cap, uint64_t* out_off, uint64_t* out_bytes) {
     if (!out_off || !out_bytes) return BG_ERR_INVALID_ARG;
     *out_bytes = 0;
     int rc = sam_check(fm, sp, n_reads, n_contigs, pairs);
@@ -522,12 +525,21 @@ extern "C" int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint6
     uint64_t* d_off = s.out<uint64_t>(n_slots + 1);
     char* d_out = out ? s.out<char>(out_cap) : nullptr;  // null: a sizing call
     if (s.rc) return s.rc;
-    rc = bg_sam_emit_dup_batch_dev(fm, sp, n_reads, d_contigs, n_contigs, d_names, d_fq, d_recs, d_seq, d_qual, d_hits, d_strand, d_ops, d_multi,
-                                   d_pairs, d_dup, d_out, out_cap, d_off, out_bytes, s.st);
+    rc = dev(fm, sp, n_reads, d_contigs, n_contigs, d_names, d_fq, d_recs, d_seq, d_qual, d_hits, d_strand, d_ops, d_multi, d_pairs, d_dup, d_out,
+             out_cap, d_off, out_bytes, s.st);
     if (rc && rc != BG_ERR_OPS_CAP) return rc;
     s.down(out_off, d_off, n_slots + 1);
     if (!rc && out) s.down(out, d_out, *out_bytes);
     return s.sync() ? s.rc : rc;
+}
+
+extern "C" int bg_sam_emit_dup_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
+                                     const char* names, const uint8_t* fastq_text, const bg_fastq_record_t* recs, const uint8_t* seq,
+                                     const uint8_t* qual, const bg_seed_hit_t* hits, const uint8_t* strand, const uint8_t* ops,
+                                     const bg_multi_hit_t* multi, const bg_pair_hit_t* pairs, const uint8_t* dup, char* out, uint64_t out_cap,
+                                     uint64_t* out_off, uint64_t* out_bytes) {
+    return sam_emit_host(bg_sam_emit_dup_batch_dev, fm, sp, n_reads, contigs, n_contigs, names, fastq_text, recs, seq, qual, hits, strand, ops, multi,
+                         pairs, dup, out, out_cap, out_off, out_bytes);
 }
 
 extern "C" int bg_sam_emit_batch(bg_fm* fm, const bg_sam_params_t* sp, uint64_t n_reads, const bg_sam_contig_t* contigs, uint64_t n_contigs,
