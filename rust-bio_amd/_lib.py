@@ -209,7 +209,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_align_batch", "bg_align_batch_dev", "bg_align_banded_batch", "bg_align_banded_batch_dev", "bg_band_create_batch",
            "bg_align_banded_bands_batch", "bg_band_from_matches_batch", "bg_sparse_find_kmer_matches", "bg_sparse_sdpkpp",
            "bg_sparse_lcskpp", "bg_sparse_sdpkpp_union_lcskpp_path", "bg_sparse_expand_kmer_matches", "bg_fastq_parse",
-           "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_last_fill_framed", "bg_pack2_host",
+           "bg_fastq_parse_dev", "bg_cigar_batch", "bg_cigar_batch_dev", "bg_get_timing", "bg_enable_timing", "bg_band_redo_pairs", "bg_last_fill_kernels", "bg_last_fill_framed", "bg_last_fill_max3", "bg_pack2_host",
            "bg_pretty_batch", "bg_suffix_array_dev", "bg_bwt_dev", "bg_sa_sample_dev", "bg_suffix_array_dev64", "bg_bwt_dev64", "bg_sa_sample_dev64", "bg_fm_build_dev", "bg_fm_set_text", "bg_fm_set_text_dev", "bg_seed_extend_batch", "bg_seed_extend_batch_dev",
            "bg_seed_extend_strands_batch", "bg_seed_extend_strands_batch_dev", "bg_revcomp_batch_dev",
            "bg_seed_extend_smem_batch", "bg_seed_extend_smem_batch_dev",
@@ -411,6 +411,7 @@ def lib():
         L.bg_band_redo_pairs.argtypes = [vp, C.POINTER(u64)]
         L.bg_last_fill_kernels.argtypes = [vp, C.POINTER(u32)]
         L.bg_last_fill_framed.argtypes = [vp, C.POINTER(i32)]
+        L.bg_last_fill_max3.argtypes = [vp, C.POINTER(i32)]
         L.bg_pack2_host.argtypes = [vp, u64, vp, vp]
         L.bg_myers_best_batch.argtypes = [vp, vp, u32, u32, u64, vp, vp, vp, vp, u64]
         L.bg_myers_best_batch_dev.argtypes = [vp, vp, u32, u32, u64, vp, vp, vp, vp, u64, vp]
@@ -480,6 +481,12 @@ class Context:
         """True when the last align call ran K1p's LF flavour with its keys in the offset frame (FILL["K1P_LF"] either way)"""
         v = C.c_int(0)
         check(lib().bg_last_fill_framed(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def last_fill_max3(self):
+        """True when that framed cell took its best key with v_pk_maximum3_f16 (every key below 0x7c00; option no_pk16_max3)"""
+        v = C.c_int(0)
+        check(lib().bg_last_fill_max3(self.h, C.byref(v)))
         return bool(v.value)
 
     def close(self):

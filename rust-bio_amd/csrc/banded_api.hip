@@ -985,6 +985,7 @@ int band_run(const BandCall& c) {
     if (!ctx || !c.sc || c.mode < BG_MODE_CUSTOM || c.mode > BG_MODE_LOCAL) return BG_ERR_INVALID_ARG;
     ctx->fill_mask = 0;
     ctx->fill_framed = false;
+    ctx->fill_max3 = false;
     int rc = check_scoring(c.sc);
     if (rc) return rc;
     if (c.ops_used) *c.ops_used = 0;

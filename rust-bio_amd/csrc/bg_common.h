@@ -83,6 +83,7 @@ struct bg_ctx {
     bool no_pk16 = false;     // tests: disable K1p (two pairs per lane in packed int16 halves)
     bool no_local_fast = false;  // tests: Aligner::local on the general K1p (no LF flavour)
     bool no_pk16_frame = false;  // tests, A/B: K1p's LF flavour without the offset frame (sw_fill_pk16.inc, FR)
+    bool no_pk16_max3 = false;   // tests, A/B: the framed cell with v_pk_max_i16 only, no v_pk_maximum3_f16 (sw_fill_pk16.inc, FR == 2)
     bool no_couples = false;  // tests: K1p without the (m, n) slot order on ragged batches
     int band_chain_global = -1;  // chain_kernel tree placement: -1 by batch size, 0 LDS, 1 global scratch
     bool fq_no_fused = false;  // tests, A/B: bg_fastq_parse_dev through F1 .. F6 only (no one-pass kernel in front)
@@ -108,6 +109,7 @@ struct bg_ctx {
     bg_timing_t last = {};
     uint32_t fill_mask = 0;  // BG_FILL_* families the last align call launched (bg_last_fill_kernels)
     bool fill_framed = false;  // ... K1p's LF flavour among them with its framed cell (bg_last_fill_framed)
+    bool fill_max3 = false;    // ... and that cell's best key by v_pk_maximum3_f16 (bg_last_fill_max3)
 };
 
 // grow-only device scratch

@@ -293,6 +293,10 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
         ctx->no_pk16_frame = value != 0;
         return BG_OK;
     }
+    if (!strcmp(key, "no_pk16_max3")) {
+        ctx->no_pk16_max3 = value != 0;
+        return BG_OK;
+    }
     if (!strcmp(key, "no_pk16")) {
         ctx->no_pk16 = value != 0;
         return BG_OK;
@@ -320,6 +324,12 @@ extern "C" int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask) {
 extern "C" int bg_last_fill_framed(bg_ctx* ctx, int* framed) {
     if (!ctx || !framed) return BG_ERR_INVALID_ARG;
     *framed = ctx->fill_framed ? 1 : 0;
+    return BG_OK;
+}
+
+extern "C" int bg_last_fill_max3(bg_ctx* ctx, int* max3) {
+    if (!ctx || !max3) return BG_ERR_INVALID_ARG;
+    *max3 = ctx->fill_max3 ? 1 : 0;
     return BG_OK;
 }
 

@@ -65,7 +65,7 @@ struct FillPlan {
     sw_fill_fn fill = nullptr, fill_rest = nullptr, fill_second = nullptr;  // K1p: the fast launch, the rest, the second pairs
     uint32_t tb_fmt = TBF_K1;
     uint32_t fill_bit = 0;
-    bool k1p = false, framed = false;
+    bool k1p = false, framed = false, max3 = false;  // max3: the framed cell's v_pk_maximum3_f16 flavour (implies framed)
 };
 // the one place that chooses a fill: K1p where admitted and shaped, else K1's LF flavour where admitted, else K1 by score
 // source.  `c` carries the clip penalties of the mode.
@@ -95,7 +95,9 @@ static FillPlan plan_fill(const bg_ctx& ctx, const SwScoring& c, int sm, int64_t
         if (r) {  // (else no K1p instantiation for this shape: K1 runs)
             // LF keys in the offset frame (its cell does without the clamped gap adds) wherever they fit 15 bits there
             p.framed = lf && !ctx.no_pk16_frame && pk16_frame_fits(c, max_ylen, r, cfg.lp);
-            if (p.framed) f = FILL_K1P_LF_FRAMED;
+            // ... and its best key by v_pk_maximum3_f16 wherever they are finite halves as well (FR == 2)
+            p.max3 = p.framed && !ctx.no_pk16_max3 && pk16_max3_fits(c, max_ylen, r, cfg.lp);
+            if (p.framed) f = p.max3 ? FILL_K1P_LF_FRAMED_MAX3 : FILL_K1P_LF_FRAMED;
             p.r = r;
             p.fill = sw_fill_get(f, true, cfg.lp, r, 0);
             p.fill_rest = lf ? nullptr : sw_fill_get(f, true, cfg.lp, r, 1);  // LF: the first launch takes every wavefront
@@ -306,6 +308,7 @@ static void reset_fill_report(bg_ctx* ctx) {
     if (!ctx) return;
     ctx->fill_mask = 0;
     ctx->fill_framed = false;
+    ctx->fill_max3 = false;
 }
 
 // len_hint: what the caller knows about the lengths of the batch — 1 every pair has the same (m, n), 0 they differ,
@@ -392,6 +395,7 @@ static int align_batch_dev_impl(bg_ctx* ctx, const bg_scoring_t* sc, int mode, u
     if (!plan.fill) return BG_ERR_UNSUPPORTED;
     ctx->fill_mask |= plan.fill_bit;
     if (plan.framed) ctx->fill_framed = true;
+    if (plan.max3) ctx->fill_max3 = true;
     if (packed_codes) {
         if (plan.k1p) {
             a.packed = 1;  // K1p reads the 2-bit streams as they are

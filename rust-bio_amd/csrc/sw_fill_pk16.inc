@@ -25,6 +25,7 @@ typedef uint32_t pk;  // two int16: [15:0] = first pair of the couple, [31:16] =
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s16x2 as_s(pk v) { return __builtin_bit_cast(s16x2, v); }
 __device__ __forceinline__ u16x2 as_u(pk v) { return __builtin_bit_cast(u16x2, v); }
 __device__ __forceinline__ pk bits(s16x2 v) { return __builtin_bit_cast(pk, v); }
@@ -32,6 +33,12 @@ __device__ __forceinline__ pk bits(u16x2 v) { return __builtin_bit_cast(pk, v); 
 // v_pk_add_i16 clamp / v_pk_max_i16 / v_pk_add_u16 / v_pk_sub_u16 [clamp] / v_pk_mad_u16
 __device__ __forceinline__ pk pk_adds(pk a, pk b) { return bits(__builtin_elementwise_add_sat(as_s(a), as_s(b))); }
 __device__ __forceinline__ pk pk_max(pk a, pk b) { return bits(__builtin_elementwise_max(as_s(a), as_s(b))); }
+// v_pk_maximum3_f16: the integer maximum of three, bits untouched, while every half lies in [0, 0x7bff] — there the bit
+// patterns are the non-negative finite halves (denormals included), which IEEE maximum orders as the integers do
+__device__ __forceinline__ pk pk_max3h(pk a, pk b, pk c) {
+    const h16x2 x = __builtin_bit_cast(h16x2, a), y = __builtin_bit_cast(h16x2, b), z = __builtin_bit_cast(h16x2, c);
+    return __builtin_bit_cast(pk, __builtin_elementwise_maximum(__builtin_elementwise_maximum(x, y), z));
+}
 __device__ __forceinline__ pk pk_min(pk a, pk b) { return bits(__builtin_elementwise_min(as_s(a), as_s(b))); }
 __device__ __forceinline__ pk pk_add_u16(pk a, pk b) { return bits((u16x2)(as_u(a) + as_u(b))); }
 __device__ __forceinline__ pk pk_sub_u16(pk a, pk b) { return bits((u16x2)(as_u(a) - as_u(b))); }
@@ -88,7 +95,10 @@ enum { CZ = 0, CF = 1, CI = 2 };
 // the frame as they are taken (best^ - F + priority, one subtract instead of the or), and so do Sl / Il when they are
 // parked: the epilogue, the traceback cells and K2 see what the plain LF cell gives them.  The values crossing to the lane
 // below (row R - 1 there, row -1 here) are re-based by g (R - 1), and 0 is 'minus infinity' of I and D.
-template <int R, int LP, int MODE, int XP, int XS, int YP, int YS, bool LF = false, bool FR = false>
+// FR == 2 (where pk16_max3_fits: every key of the frame below 0x7c00, half precision's +inf): the same cell with the best
+// key max(m_key, F(r, s), D, I) taken by two v_pk_maximum3_f16 (pk_max3h) instead of three v_pk_max_i16 — one half-rate
+// instruction fewer per row; the keys, flags and traceback cells it forms are those of FR == 1 bit for bit.
+template <int R, int LP, int MODE, int XP, int XS, int YP, int YS, bool LF = false, int FR = 0>
 __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     constexpr bool FAST = MODE == 0;
     constexpr int PW = 64 / LP;
@@ -102,7 +112,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     static_assert(LP == 16 || LP == 32, "lanes per pair");
     static_assert(R >= 1 && R <= 12, "rows per lane");
     static_assert(!LF || LOCAL, "LF is a flavour of the local kernel");
-    static_assert(!FR || LF, "the frame is a cell of the LF flavour");
+    static_assert(FR >= 0 && FR <= 2 && (!FR || LF), "the frame is a cell of the LF flavour");
     (void)NARROW;
     (void)LOCAL;
     // LDS, two uses that never overlap in time: during the fill, the traceback words of the current tile (a
@@ -425,16 +435,18 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                         // the x-prefix clip; FR: the floor is that key in the frame, F(r, s)
                         const pk Fr = F0 + (uint32_t)r * GF;
                         (void)Fr;
-                        const pk m_key = FR   ? pk_max(pk_mad_u16(e, DELTA, diag) + KSUB, Fr)
-                                         : LF ? pk_subs_u16(pk_mad_u16(e, DELTA, diag), MISC)
-                                              : pk_adds(diag, pk_mad_u16(e, DELTA, MISK));
+                        // (FR == 2: the floor enters kb's first maximum of three instead)
+                        const pk m_key = FR == 2 ? pk_mad_u16(e, DELTA, diag) + KSUB
+                                         : FR    ? pk_max(pk_mad_u16(e, DELTA, diag) + KSUB, Fr)
+                                         : LF    ? pk_subs_u16(pk_mad_u16(e, DELTA, diag), MISC)
+                                                 : pk_adds(diag, pk_mad_u16(e, DELTA, MISK));
                         const pk Iv_t = FR ? pk_max(I_up, S_up + KGOI) : pk_max(pk_adds(I_up, GE), pk_adds(S_up, GOT_I));
                         const pk Dv_t = FR ? pk_max(Dl[r], Sl[r] + KGOD) : pk_max(pk_adds(Dl[r], GE), pk_adds(Sl[r], GOT_D));
                         const pk Iv = Iv_t & NOFLAG, Dv = Dv_t & NOFLAG;
                         // mod.rs:757-786: first maximum wins == max over (score | priority)
-                        pk kb = pk_max(m_key, Dv_t);
+                        pk kb = FR == 2 ? pk_max3h(m_key, Fr, Dv_t) : pk_max(m_key, Dv_t);
                         if (XP != CI && !LF) kb = pk_max(kb, XKEY);
-                        kb = pk_max(kb, Iv_t);  // the value that waits for the row above comes last
+                        kb = FR == 2 ? pk_max3h(kb, Iv_t, Iv_t) : pk_max(kb, Iv_t);  // the value that waits for the row above comes last
                         if (FOLD && maybe_m)
                             kb = pk_max(kb, is_m ? ((cmk & CLEAN) | (0x00010001u * K_XS)) : FLOORK);
                         const pk best = kb & CLEAN;
@@ -609,15 +621,15 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
 
 // the fast launch is tuned for three wavefronts per SIMD up to R = 10 (168 VGPRs, 46 KB of LDS per block); the two
 // others take what the generic row-m handling needs, two per SIMD at least
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, int FR = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_kernel(const SwArgs a) {
     sw_fill_pk16_body<R, LP, 0, XP, XS, YP, YS, LF, FR>(a);
 }
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, int FR = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_rest_kernel(const SwArgs a) {
     sw_fill_pk16_body<R, LP, 1, XP, XS, YP, YS, LF, FR>(a);
 }
-template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, bool FR = false>
+template <int R, int LP, int XP, int XS, int YP, int YS, bool LF, int FR = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R <= 10 ? 3 : 2, R <= 10 ? 3 : 2))) void sw_fill_pk16_second_kernel(const SwArgs a) {
     sw_fill_pk16_body<R, LP, 2, XP, XS, YP, YS, LF, FR>(a);
 }

@@ -75,6 +75,13 @@ inline bool pk16_frame_fits(const SwScoring& sc, uint32_t max_ylen, int r, int l
     const int64_t g = -16ll * sc.ge, nsteps = (int64_t)max_ylen + lp - 1;
     return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x8000;
 }
+// ... and whether they all stay below 0x7c00, +inf of half precision: then every key is the bit pattern of a non-negative
+// finite half and the cell may take its best key with v_pk_maximum3_f16 (FR == 2)
+inline bool pk16_max3_fits(const SwScoring& sc, uint32_t max_ylen, int r, int lp) {
+    if (sc.ge > 0 || sc.match < 0) return false;
+    const int64_t g = -16ll * sc.ge, nsteps = (int64_t)max_ylen + lp - 1;
+    return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x7c00;
+}
 
 // traceback cell formats (SwGeom::tb_fmt): what the fill writes and K2 decodes
 enum : uint32_t {
@@ -286,7 +293,7 @@ typedef void (*sw_fill_fn)(const SwArgs);
 // lp lanes per pair, r rows per lane and launch `which` (K1p: 0 the fast launch, 1 the rest, 2 the second pairs), or
 // nullptr where that is not instantiated.  plan_fill (sw_api.hip) is the one place that chooses among them.
 #define BG_SW_FILLS(X) \
-    X(K1) X(K1_LOCAL) X(K1_LF) X(K1_LDS) X(K1_LDS_LOCAL) X(K1_GLOBAL) X(K1P_CUSTOM) X(K1P_GLOBAL) X(K1P_SEMIGLOBAL) X(K1P_LOCAL) X(K1P_LF) X(K1P_LF_FRAMED)
+    X(K1) X(K1_LOCAL) X(K1_LF) X(K1_LDS) X(K1_LDS_LOCAL) X(K1_GLOBAL) X(K1P_CUSTOM) X(K1P_GLOBAL) X(K1P_SEMIGLOBAL) X(K1P_LOCAL) X(K1P_LF) X(K1P_LF_FRAMED) X(K1P_LF_FRAMED_MAX3)
 enum SwFill {
 #define BG_X(F) FILL_##F,
     BG_SW_FILLS(BG_X)

@@ -22,6 +22,18 @@ OPK(k_pklshl, "v_pk_lshlrev_b16")
 OPK(k_pkaddf16, "v_pk_add_f16")
 OPK(k_pkmaxf16, "v_pk_max_f16")
 OPK(k_pkminu, "v_pk_min_u16")
+// three-operand form (v_pk_maximum3_f16: gfx950 has no two-operand v_pk_maximum_f16); the start values are masked into
+// [0, 0x7bff] per half, the range the framed K1p cell feeds it (finite, non-negative, denormals included)
+#define OPK3(name, ins) \
+template <int DEP> __global__ __launch_bounds__(256) void name(uint32_t* o, uint32_t s, int iters) { \
+    uint32_t a[8]; for (int k = 0; k < 8; k++) a[k] = (threadIdx.x * 7 + k + s) & 0x3fff3fffu; uint32_t b = s | 0x10001, c = s | 0x20002; \
+    for (int it = 0; it < iters; it++) { \
+        _Pragma("unroll") for (int u = 0; u < 8; u++) { \
+            _Pragma("unroll") for (int k = 0; k < 8; k++) { \
+                if (DEP) asm volatile(ins " %0, %1, %2, %3" : "=v"(a[0]) : "v"(a[0]), "v"(b), "v"(c)); \
+                else asm volatile(ins " %0, %1, %2, %3" : "=v"(a[k]) : "v"(a[k]), "v"(b), "v"(c)); } } } \
+    uint32_t r = 0; for (int k = 0; k < 8; k++) r ^= a[k]; o[blockIdx.x * 256 + threadIdx.x] = r; }
+OPK3(k_pkmax3f16, "v_pk_maximum3_f16")
 template <typename F> void run(const char* nm, F f, uint32_t* d, int waves_per_simd) {
     const int iters = 2000; const int blocks = 256 * waves_per_simd;  // 4 waves per block = 1 per SIMD per CU
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
@@ -46,6 +58,7 @@ int main() {
         run("v_pk_lshlrev_b16 indep", k_pklshl<0>, d, w);
         run("v_pk_add_f16 indep", k_pkaddf16<0>, d, w);
         run("v_pk_max_f16 indep", k_pkmaxf16<0>, d, w); run("v_pk_max_f16 dep", k_pkmaxf16<1>, d, w);
+        run("v_pk_maximum3_f16 indep", k_pkmax3f16<0>, d, w); run("v_pk_maximum3_f16 dep", k_pkmax3f16<1>, d, w);
     }
     return 0;
 }
