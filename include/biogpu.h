@@ -1159,11 +1159,12 @@ int bg_sam_sort(bg_ctx* ctx, uint64_t n_slots, const uint64_t* key, const char* 
 int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, char* out,
                      uint64_t out_cap, uint64_t* out_bytes);
 
-/* ---- BAM records and BGZF framing (bam_emit.hip, bgzf.hip; the bodies in csrc/bam_rule.h) ------------------------------
+/* ---- BAM records and BGZF framing (bam_emit.hip, bgzf.hip, bgzf_deflate.hip; the bodies in csrc/bam_rule.h) ----------------
  * What every tool behind a mapper reads, from the same hits, without the text in between:
  *   bg_bam_header            "BAM\1", the SAM header text, the reference table (host only, no GPU)
  *   bg_bam_emit_batch[_dev]  one BAM record per hit slot
  *   bg_bgzf_frame[_dev]      any byte stream cut into BGZF blocks
+ *   bg_bgzf_deflate[_dev]    ... with deflate-compressed payloads
  * BAM records are variable-length records like SAM lines: bg_sam_sort[_dev] sorts them with bg_sam_sort_keys[_dev]'s keys as
  * they are.  A file is the framed header followed by the framed records with BG_BGZF_EOF (blocks are independent).
  *
@@ -1206,7 +1207,26 @@ int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const c
  *   flavour is asynchronous on `stream`.  out == NULL with out_cap == 0 sizes; BG_ERR_OPS_CAP if out_cap is too small (nothing
  *   written); BG_ERR_INVALID_ARG: unknown flag bits, a null ctx or out_bytes, a null in with in_bytes > 0.  d_in and d_out may
  *   be at any address and must not overlap.
- * Not covered: deflate compression, BAI / CSI indexes, read groups, supplementary records. */
+ *
+ * bg_bgzf_deflate[_dev] (bgzf_deflate.hip; the bodies in csrc/bgzf_deflate_rule.h): bg_bgzf_frame with the payloads
+ *   compressed.  THE RULE: the input is cut into payloads of 65 280 bytes exactly as bg_bgzf_frame cuts it; each becomes one
+ *   gzip member with the same 18-byte header, CRC-32 and ISIZE around ONE deflate block (BFINAL set) in one of three
+ *   encodings: stored, fixed Huffman codes, dynamic Huffman codes — the one with the fewest bits by exact count (stored:
+ *   8 * (len + 5)); stored wins a tie, then fixed.  A block therefore never exceeds len + 31 bytes and BSIZE always fits; a
+ *   block that comes out stored is bg_bgzf_frame's block byte for byte.  BG_BGZF_EOF appends the same 28 bytes.
+ *   The tokens: a greedy parse from byte 0 over matches of 3 .. 258 bytes at distances 1 .. 32 768 that never start in front
+ *   of the payload nor run behind it; blocks are independent.  Dynamic codes are length-limited Huffman codes (15 bits; 7 for
+ *   the code-length alphabet) with HLIT, HDIST and HCLEN trimmed and always at least one distance code.
+ *   The bytes are a function of the payload alone: the same on every run, at every alignment of source and destination, and
+ *   from the CPU run of the bodies (tests/bgzf_deflate_host_bodies.cpp); nothing that decides a byte depends on the order in
+ *   which lanes or wavefronts run.
+ *   out_cap must hold the stored bound, bg_bgzf_frame's out_bytes for the same arguments: BG_ERR_OPS_CAP otherwise (nothing
+ *   written); out == NULL with out_cap == 0 returns that bound in *out_bytes.  After a real call *out_bytes is the actual
+ *   size: the total is read back once, with one stream synchronisation (as bg_bam_emit_batch_dev).  block_off may be NULL;
+ *   otherwise it receives ceil(in_bytes / 65280) + 1 offsets into the output: the start of every block, then the end of the
+ *   last (the end-of-file block is not counted) — the table a virtual offset needs now that block sizes are not closed-form.
+ *   BG_ERR_INVALID_ARG as bg_bgzf_frame.  Scratch is the ctx's and does not grow with the input (sub-batches of 512 blocks).
+ * Not covered: BAI / CSI indexes, read groups, supplementary records; lazy matching, hash chains, compression levels. */
 enum { BG_BGZF_EOF = 1 };
 int bg_bam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, uint8_t* out,
                   uint64_t out_cap, uint64_t* out_bytes);
@@ -1224,6 +1244,10 @@ int bg_bgzf_frame_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uint3
                       uint64_t* out_bytes, void* stream);
 int bg_bgzf_frame(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t flags, uint8_t* out, uint64_t out_cap,
                   uint64_t* out_bytes);
+int bg_bgzf_deflate_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                        uint64_t* d_block_off, uint64_t* out_bytes, void* stream);
+int bg_bgzf_deflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t flags, uint8_t* out, uint64_t out_cap,
+                    uint64_t* block_off, uint64_t* out_bytes);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

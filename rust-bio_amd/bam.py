@@ -1,9 +1,10 @@
-"""BAM records and BGZF framing — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]` and `bg_bgzf_frame[_dev]`;
-`sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+"""BAM records and BGZF framing — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]` and
+`bg_bgzf_deflate[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
-container (rust-bio_amd/csrc/bgzf.hip) holds stored deflate blocks with a CRC-32 each.  This module only marshals arguments."""
+container holds stored deflate blocks with a CRC-32 each (rust-bio_amd/csrc/bgzf.hip) or blocks compressed on the device
+(rust-bio_amd/csrc/bgzf_deflate.hip).  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -94,6 +95,41 @@ def bgzf_frame_dev(d_in, in_bytes, d_out, out_cap, flags=0, stream=0, ctx=None):
     return int(n.value)
 
 
+def bgzf_deflate_arrays(data, flags=0, ctx=None):
+    """bg_bgzf_deflate, host buffers: `data` as BGZF blocks with deflate-compressed payloads.  Returns (bytes, block_off:
+    uint64[n_blocks + 1], the start of every block in the bytes and the end of the last; the end-of-file block is not counted)"""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(data)
+    nbytes = len(src)
+    src = src if nbytes else np.zeros(1, np.uint8)
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().bg_bgzf_deflate(ctx.h, src.ctypes.data, nbytes, flags, None, 0, None, C.byref(n)), "bg_bgzf_deflate")
+    out = np.zeros(max(n.value, 1), dtype=np.uint8)
+    block_off = np.zeros((nbytes + PAYLOAD - 1) // PAYLOAD + 1, dtype=np.uint64)
+    _lib.check(_lib.lib().bg_bgzf_deflate(ctx.h, src.ctypes.data, nbytes, flags, out.ctypes.data, n.value, block_off.ctypes.data, C.byref(n)),
+               "bg_bgzf_deflate")
+    return out[:n.value].tobytes(), block_off
+
+
+def bgzf_deflate_dev(d_in, in_bytes, d_out, out_cap, flags=0, stream=0, ctx=None, d_block_off=0):
+    """bg_bgzf_deflate_dev (pointers are ints; d_block_off may be 0; d_out = 0 with out_cap = 0 returns the stored bound,
+    `framed_bytes`, which out_cap must hold).  Returns the actual number of bytes, read back with one synchronisation of
+    `stream`; raises BiogpuError with status -9 (OPS_CAP) when out_cap is below the bound."""
+    ctx = ctx or _lib.default_context()
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().bg_bgzf_deflate_dev(ctx.h, d_in or None, in_bytes, flags, d_out or None, out_cap, d_block_off or None, C.byref(n), stream),
+               "bg_bgzf_deflate_dev")
+    return int(n.value)
+
+
+def virtual_offsets(stream_offsets, block_off, base=0):
+    """The BGZF virtual offsets of bytes `stream_offsets` of a stream framed by one bg_bgzf_deflate call whose output starts at
+    byte `base` of the file and whose block table is `block_off`: (base + block_off[o // 65280]) << 16 | o % 65280, as uint64."""
+    o = np.asarray(stream_offsets, dtype=np.uint64)
+    block_off = np.asarray(block_off, dtype=np.uint64)
+    return ((np.uint64(base) + block_off[(o // np.uint64(PAYLOAD)).astype(np.int64)]) << np.uint64(16)) | (o % np.uint64(PAYLOAD))
+
+
 def virtual_offset(stream_offset, base=0):
     """The BGZF virtual offset (block start << 16 | offset inside the block's payload) of byte `stream_offset` of a stream
     framed by one bg_bgzf_frame call whose output starts at byte `base` of the file."""
@@ -101,14 +137,17 @@ def virtual_offset(stream_offset, base=0):
     return ((base + block * (PAYLOAD + BLOCK_EXTRA)) << 16) | within
 
 
-def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None):
+def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False):
     """The chain on host buffers, as `sam.sorted_sam`: duplicate flags (markdup: a MarkdupParams, or None), BAM records that
     carry them, a key per record, the records in coordinate order.  Returns the complete file as bytes: the header
-    (SO:coordinate) framed, then the sorted records framed with the end-of-file block."""
+    (SO:coordinate) framed, then the sorted records framed with the end-of-file block.  compress: both framing calls are
+    bg_bgzf_deflate instead of bg_bgzf_frame (the same payloads, compressed)."""
     dup = None
     if markdup is not None:
         dup, _ = sam.markdup_arrays(markdup, contigs, parsed, hits, strand, ctx=ctx)
     recs, off = emit_arrays(fm, params, contigs, parsed, hits, strand, ops, multi=multi, pairs=pairs, dup=dup)
     key = sam.sort_keys_arrays(params, contigs, len(parsed.recs), hits, strand, ctx=ctx)
     body, _, _ = sam.sort_arrays(key, recs, off, ctx=ctx)
+    if compress:
+        return bgzf_deflate_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx)[0] + bgzf_deflate_arrays(body, BGZF_EOF, ctx=ctx)[0]
     return bgzf_frame_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx) + bgzf_frame_arrays(body, BGZF_EOF, ctx=ctx)

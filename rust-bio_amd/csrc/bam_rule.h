@@ -238,5 +238,32 @@ SAM_HD uint32_t bgzf_lane(const uint32_t* T, const uint32_t* K, const uint8_t* s
     }
     return c;
 }
+// bgzf_lane without the copy (a payload that leaves compressed still wants its CRC-32): the same shares, cut at the SOURCE's
+// 16-byte boundaries, so that every vector is one aligned load.  Every byte read lies in src[0 .. len).
+SAM_HD uint32_t bgzf_lane_crc(const uint32_t* T, const uint32_t* K, const uint8_t* src, uint32_t len, uint32_t lane) {
+    const sam_copy_plan_t p = sam_copy_plan((uint32_t)((uintptr_t)src & 15u), len);
+    const uint32_t body = (uint32_t)p.body;
+    uint32_t first = 0;
+    if (lane == 0)
+        for (uint32_t i = 0; i < p.head; i++) first = bam_crc_byte(T, first, src[i]);
+    uint32_t acc = first, behind = len - p.head;
+    for (uint32_t j = 0; j < BGZF_LANE_VECS; j++) {
+        const uint32_t v = lane + BGZF_LANES * j;
+        if (v >= body) break;
+        const sam_v16 x = *(const sam_v16*)(src + p.head + 16u * v);
+        uint32_t r = j ? 0u : first;
+        for (int i = 0; i < 4; i++) r = bam_crc_word(T, r, x.w[i]);
+        acc = j ? bam_crc_far(K, acc) ^ r : r;
+        behind = len - p.head - 16u * (v + 1);
+    }
+    uint32_t c = acc ? bam_crc_mul(acc, bam_crc_xpow8(behind)) : 0u;
+    if (lane == BGZF_LANES - 1) {
+        const uint32_t t = p.head + 16u * body;
+        uint32_t r = 0;
+        for (uint32_t i = 0; i < p.tail; i++) r = bam_crc_byte(T, r, src[t + i]);
+        c ^= r;
+    }
+    return c;
+}
 
 #endif
