@@ -1226,7 +1226,8 @@ int bg_sam_header_so(const bg_sam_contig_t* contigs, uint64_t n_contigs, const c
  *   otherwise it receives ceil(in_bytes / 65280) + 1 offsets into the output: the start of every block, then the end of the
  *   last (the end-of-file block is not counted) — the table a virtual offset needs now that block sizes are not closed-form.
  *   BG_ERR_INVALID_ARG as bg_bgzf_frame.  Scratch is the ctx's and does not grow with the input (sub-batches of 512 blocks).
- * Not covered: BAI / CSI indexes, read groups, supplementary records; lazy matching, hash chains, compression levels. */
+ * Not covered: CSI indexes (the BAI index: the section below), read groups, supplementary records; lazy matching, hash chains,
+ * compression levels. */
 enum { BG_BGZF_EOF = 1 };
 int bg_bam_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, int sort_order, uint8_t* out,
                   uint64_t out_cap, uint64_t* out_bytes);
@@ -1248,6 +1249,55 @@ int bg_bgzf_deflate_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uin
                         uint64_t* d_block_off, uint64_t* out_bytes, void* stream);
 int bg_bgzf_deflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t flags, uint8_t* out, uint64_t out_cap,
                     uint64_t* block_off, uint64_t* out_bytes);
+
+/* ---- the BAI index of a coordinate-sorted BAM stream (bam_index.hip; the bodies in csrc/bam_index_rule.h) ----------------
+ * What makes the file above usable by region: the bytes of the .bai file (SAM v1.6, section 5.2) beside it, from what is in
+ * HBM when the file is framed.  bg_bam_index[_dev] reads BAM RECORDS, not hits: slot i is recs[off[i] .. off[i + 1]) — the pair
+ * bg_bam_emit_batch_dev and bg_sam_sort_dev leave — and anything that is a coordinate-sorted run of BAM records will do.
+ * contigs gives n_ref = n_contigs and the contig lengths (start and the names are not read).  block_off and base say how the
+ * stream was framed: block_off is the table bg_bgzf_deflate[_dev] filled for these records (ceil(off[n_slots] / 65280) + 1
+ * entries), or NULL where bg_bgzf_frame[_dev] framed them (closed form); base is the file offset of the first block of that
+ * framing call: the length of the framed header.
+ * THE RULE.  The bytes are a function of the inputs alone.
+ *   slots      a slot of length 0 is ignored everywhere.  Of a record the call uses refID, pos, l_read_name, n_cigar_op, flag
+ *              and the CIGAR words.  end = pos + the reference bases the CIGAR consumes (M, D, N, =, X), pos + 1 where that
+ *              sum is 0 (the placeholder <l_seq>S<len>N of a record with a CG tag is no case of its own).  The bin is the
+ *              specification's reg2bin(pos, end), recomputed: the record's own bin field is not read.
+ *   voff(o)    of byte o of the stream: with a table (base + block_off[o / 65280]) << 16 | o % 65280; without one
+ *              (base + 65311 * (o / 65280)) << 16 | o % 65280.  o = off[n_slots] is legal even where it is a multiple of 65 280:
+ *              the table's last entry serves it.
+ *   indexed    are the records with refID >= 0, unmapped mates that borrow a position included (as in htslib); those with
+ *              refID < 0 only count into n_no_coor.
+ *   chunks     over the indexed records of one reference in file order, every maximal run of consecutive records with the
+ *              same bin is one chunk (voff(start of the first), voff(end of the last)); a bin's chunks are listed in file
+ *              order.  No further merging and no bin compression: readers need neither.
+ *   linear     a reference with records has n_intv = ((max end - 1) >> 14) + 1 (0 where max end is 0); ioffset[w] is
+ *              voff(start) of its first record in file order whose end > w << 14.  On sorted input that is the smallest start
+ *              offset among the records overlapping window w, an empty window taking the next non-empty window's value.
+ *   pseudo-bin 37450, for every reference with records: chunk 0 = (voff(start of its first record), voff(end of its last)),
+ *              chunk 1 = (its records with FLAG 0x4 clear, those with it set).
+ *   bytes      all integers little-endian: "BAI\1", n_ref; per reference n_bin, the bins with at least one chunk in ascending
+ *              bin number (bin, n_chunk, the chunks), the pseudo-bin last (n_bin counts it), n_intv, the offsets; a reference
+ *              without records is n_bin = 0, n_intv = 0; then n_no_coor (uint64), always.  (htslib lists bins in hash order:
+ *              byte identity with samtools index is no goal.)
+ * Checks.  Each leaves nothing written and sets *first_bad (optional; UINT64_MAX where no slot is to blame) to the first
+ *   offending slot, whose kind decides the status.  BG_ERR_INVALID_ARG: a non-empty slot shorter than 36 bytes, one whose
+ *   block_size + 4 is not its length, one whose name, CIGAR, bases and qualities run past its end, refID >= n_contigs,
+ *   pos < -1, end beyond the contig's length, off[i + 1] < off[i], or a record that sorts before the previous non-empty slot by
+ *   ((uint32) refID, pos): the input must be coordinate-sorted, unplaced records last.  BG_ERR_UNSUPPORTED: a record with
+ *   nothing else wrong whose end > 2^29, where BAI's bins stop.  BG_ERR_OPS_CAP if out_cap is too small (*out_bytes says what
+ *   is needed); out == NULL with out_cap == 0 sizes.  BG_ERR_TOO_LARGE: n_slots >= 2^32 - 1.  Also BG_ERR_INVALID_ARG: a null
+ *   ctx or out_bytes, (n_slots > 0) a null recs or off, (n_contigs > 0) a null contigs.
+ * The errors and the total are read back once, with one stream synchronisation (as bg_bam_emit_batch_dev); the bytes are then
+ * stored asynchronously on `stream`.  d_recs and d_out may be at any address: record fields are read byte by byte.  Scratch
+ * is the ctx's, 17 words a slot and 6 a contig; nothing grows with the windows or with n_contigs x bins.
+ * Not covered: CSI indexes (contigs beyond 2^29), htslib's bin compression and chunk merging, unsorted input, .gzi / tabix. */
+int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off, const bg_sam_contig_t* d_contigs,
+                     uint64_t n_contigs, const uint64_t* d_block_off, uint64_t base, uint8_t* d_out, uint64_t out_cap,
+                     uint64_t* out_bytes, uint64_t* first_bad, void* stream);
+int bg_bam_index(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
+                 uint64_t n_contigs, const uint64_t* block_off, uint64_t base, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes,
+                 uint64_t* first_bad);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

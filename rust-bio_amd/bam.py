@@ -1,10 +1,11 @@
-"""BAM records and BGZF framing — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]` and
-`bg_bgzf_deflate[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+"""BAM records, BGZF framing and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
+`bg_bgzf_deflate[_dev]` and `bg_bam_index[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
 container holds stored deflate blocks with a CRC-32 each (rust-bio_amd/csrc/bgzf.hip) or blocks compressed on the device
-(rust-bio_amd/csrc/bgzf_deflate.hip).  This module only marshals arguments."""
+(rust-bio_amd/csrc/bgzf_deflate.hip); the index is built from the sorted records and the framing's block table
+(rust-bio_amd/csrc/bam_index.hip).  This module only marshals arguments."""
 import ctypes as C
 
 import numpy as np
@@ -137,17 +138,77 @@ def virtual_offset(stream_offset, base=0):
     return ((base + block * (PAYLOAD + BLOCK_EXTRA)) << 16) | within
 
 
-def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False):
+class BamIndexError(_lib.BiogpuError):
+    """bg_bam_index[_dev] refused the records; `first_bad` is the offending slot (None: no slot is to blame)"""
+
+    def __init__(self, status, where, first_bad):
+        super().__init__(status, where)
+        self.first_bad = first_bad
+
+
+def _index_check(rc, where, first_bad):
+    if rc != _lib.BG_OK:
+        raise BamIndexError(rc, where, None if first_bad.value == 2**64 - 1 else int(first_bad.value))
+
+
+def index_arrays(records, out_off, contigs, block_off=None, base=0, ctx=None):
+    """bg_bam_index, host buffers: the bytes of the BAI index of the coordinate-sorted BAM records records[out_off[i] ..
+    out_off[i + 1]) (what `sam.sort_arrays` returns for `emit_arrays`' records).  block_off: the table `bgzf_deflate_arrays`
+    returned for these records, None where `bgzf_frame_arrays` framed them; base: the file offset of that framing call's first
+    block, the length of the framed header.  Raises BamIndexError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+    ctx = ctx or _lib.default_context()
+    off = np.ascontiguousarray(out_off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    src = _lib.as_u8(records)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    assert n == 0 or int(off[n]) <= len(src)
+    table = np.ascontiguousarray(contigs.table)
+    if block_off is not None:
+        block_off = np.ascontiguousarray(block_off, dtype=np.uint64)
+        assert len(block_off) == ((int(off[n]) if n else 0) + PAYLOAD - 1) // PAYLOAD + 1
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cap):
+        return _lib.lib().bg_bam_index(ctx.h, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                       len(table), block_off.ctypes.data if block_off is not None else None, base, out, cap, C.byref(total),
+                                       C.byref(bad))
+    _index_check(call(None, 0), "bg_bam_index", bad)
+    out = np.zeros(max(total.value, 1), dtype=np.uint8)
+    _index_check(call(out.ctypes.data, total.value), "bg_bam_index", bad)
+    return out[:total.value].tobytes()
+
+
+def index_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_out, out_cap, d_block_off=0, base=0, stream=0, ctx=None):
+    """bg_bam_index_dev (pointers are ints; d_block_off = 0: the stream was framed by bg_bgzf_frame; d_out = 0 with out_cap = 0
+    sizes).  Returns the number of bytes of the index, read back with one synchronisation of `stream`; raises BamIndexError with
+    the offending slot, BiogpuError with status -9 (OPS_CAP) when the index exceeds out_cap."""
+    ctx = ctx or _lib.default_context()
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_index_dev(ctx.h, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_block_off or None, base,
+                                     d_out or None, out_cap, C.byref(total), C.byref(bad), stream)
+    _index_check(rc, "bg_bam_index_dev", bad)
+    return int(total.value)
+
+
+def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False, index=False):
     """The chain on host buffers, as `sam.sorted_sam`: duplicate flags (markdup: a MarkdupParams, or None), BAM records that
     carry them, a key per record, the records in coordinate order.  Returns the complete file as bytes: the header
     (SO:coordinate) framed, then the sorted records framed with the end-of-file block.  compress: both framing calls are
-    bg_bgzf_deflate instead of bg_bgzf_frame (the same payloads, compressed)."""
+    bg_bgzf_deflate instead of bg_bgzf_frame (the same payloads, compressed).  index: returns (file, bai), bai the bytes of the
+    file's BAI index (`index_arrays` on the sorted records, the records' block table and the framed header's length)."""
     dup = None
     if markdup is not None:
         dup, _ = sam.markdup_arrays(markdup, contigs, parsed, hits, strand, ctx=ctx)
     recs, off = emit_arrays(fm, params, contigs, parsed, hits, strand, ops, multi=multi, pairs=pairs, dup=dup)
     key = sam.sort_keys_arrays(params, contigs, len(parsed.recs), hits, strand, ctx=ctx)
-    body, _, _ = sam.sort_arrays(key, recs, off, ctx=ctx)
+    body, body_off, _ = sam.sort_arrays(key, recs, off, ctx=ctx)
+    block_off = None
     if compress:
-        return bgzf_deflate_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx)[0] + bgzf_deflate_arrays(body, BGZF_EOF, ctx=ctx)[0]
-    return bgzf_frame_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx) + bgzf_frame_arrays(body, BGZF_EOF, ctx=ctx)
+        head = bgzf_deflate_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx)[0]
+        framed, block_off = bgzf_deflate_arrays(body, BGZF_EOF, ctx=ctx)
+    else:
+        head = bgzf_frame_arrays(header(contigs, SAM_SO_COORDINATE), 0, ctx=ctx)
+        framed = bgzf_frame_arrays(body, BGZF_EOF, ctx=ctx)
+    if not index:
+        return head + framed
+    return head + framed, index_arrays(body, body_off, contigs, block_off=block_off, base=len(head), ctx=ctx)
