@@ -1250,6 +1250,76 @@ int bg_bgzf_deflate_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uin
 int bg_bgzf_deflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t flags, uint8_t* out, uint64_t out_cap,
                     uint64_t* block_off, uint64_t* out_bytes);
 
+/* ---- reading BGZF: the block table and the payloads (bgzf_inflate.hip; the bodies in csrc/bgzf_inflate_rule.h) ------------
+ * The way back from a .bam or a bgzipped .fastq.gz that lies in HBM: bg_bgzf_blocks[_dev] finds the members, bg_bgzf_inflate
+ * [_dev] inflates every one to its final place and checks it; the text then goes to bg_fastq_parse_dev, BAM bodies to
+ * bg_bam_index_dev / bg_sam_sort_dev, without the bytes visiting the host.
+ *
+ * bg_bgzf_blocks[_dev].  THE RULE: the stream is a chain of gzip members from byte 0; member b starts at block_off[b] and is
+ *   BSIZE + 1 bytes long; the chain must end exactly at in_bytes.  block_off gets n_blocks + 1 entries, the last in_bytes (the
+ *   table bg_bgzf_deflate fills; bg_bam_index takes it as it is); out_off gets n_blocks + 1 entries, the exclusive prefix sum
+ *   of the members' ISIZE fields; *out_bytes = out_off[n_blocks].  Empty members (ISIZE 0, the 28-byte end-of-file block
+ *   among them) are blocks like any other.  The chain is the truth, not the signatures: payload bytes that look like a member
+ *   header are never reported.
+ *   Accepted header, exactly: 1f 8b 08 04, any MTIME / XFL / OS, XLEN = 6, the subfield 42 43 02 00 BSIZE.  What stands at
+ *   a chain position instead decides the error, in this order: no gzip magic (1f 8b) or fewer than 12 bytes left:
+ *   BG_ERR_INVALID_ARG; CM != 8, FLG != 4 or XLEN != 6: BG_ERR_UNSUPPORTED; fewer than 18 bytes left: BG_ERR_INVALID_ARG;
+ *   another subfield: BG_ERR_UNSUPPORTED; BSIZE + 1 < 28, a member running past in_bytes, ISIZE > 65 536:
+ *   BG_ERR_INVALID_ARG.  Both leave the tables unwritten, *first_bad = the index of the offending member (optional;
+ *   UINT64_MAX otherwise) and *n_blocks / *out_bytes = the members in front of it and their ISIZE sum.
+ *   in_bytes == 0 gives 0 blocks.  Null tables with cap_blocks == 0 size the call (*n_blocks, *out_bytes); cap_blocks <
+ *   n_blocks gives BG_ERR_OPS_CAP with both set and the tables unwritten (they hold cap_blocks + 1 entries).
+ *   BG_ERR_TOO_LARGE: in_bytes >= 2^35.  n_blocks, out_bytes and the error are read back once, with one stream
+ *   synchronisation (as bg_bam_emit_batch_dev).  Scratch is the ctx's: 18 bytes per 16 input bytes, the bound on how many
+ *   positions can carry an accepted member (two of them lie at least 16 bytes apart: the fixed header bytes forbid every closer
+ *   pair but the one 6 bytes apart, and that one needs BSIZE = 6, which 28 <= BSIZE + 1 refuses).
+ *
+ * bg_bgzf_inflate[_dev].  THE RULE: block b's deflate stream is in[block_off[b] + 18 .. block_off[b + 1] - 8), its payload
+ *   goes to out[out_off[b] .. out_off[b + 1]).  The bytes are RFC 1951's: any number of deflate blocks (stored, fixed,
+ *   dynamic, in any mix) up to the one with BFINAL.  A block is good if the stream decodes, ends inside its last byte (at
+ *   most 7 padding bits, no unused byte), produces exactly out_off[b + 1] - out_off[b] bytes, that is the trailer's ISIZE, and
+ *   the CRC-32 of those bytes is the trailer's.  Which code sets are legal is zlib's rule: an over-subscribed set is an error;
+ *   an incomplete one too, except a literal/length or distance set whose longest code is 1 bit; the code-length alphabet's set
+ *   must be complete; no distance code at all is legal (an error once a length symbol appears); symbol 256 must have a code;
+ *   HLIT > 286, HDIST > 30, a repeat with nothing before it or running past HLIT + HDIST are errors; the unassigned code of
+ *   an incomplete set, literal/length symbols 286 / 287 and distance codes 30 / 31 are errors where they are decoded; a
+ *   distance beyond the bytes this block has produced is an error (blocks share no window).
+ *   status (optional, one byte a block) gets BG_INFLATE_OK or the FIRST error in decode order; size and CRC are checked last,
+ *   in that order.  BAD_SYMBOL is every code that decodes to nothing usable, distance codes included; BAD_DISTANCE is the
+ *   distance that reaches too far.
+ *   Any bad block: BG_ERR_INVALID_ARG with *first_bad (optional) = the lowest bad block; good blocks' payloads are written
+ *   in full, a bad block's bytes inside its own range are unspecified.  Whatever the input, every read lies in the block's
+ *   own member and every write in its own output range.
+ *   BG_ERR_OPS_CAP if out_cap < out_off[n_blocks]; BG_ERR_INVALID_ARG with *first_bad = the first offending block if the
+ *   tables are not ascending, block_off[n_blocks] > in_bytes, an output range exceeds 65 536 bytes or a member is shorter
+ *   than 28 or longer than 65 536 bytes; a null ctx, or (n_blocks > 0) a null in or table, or a null out with out_cap > 0 (a null out with out_cap == 0 serves a
+ *   stream of empty members); BG_ERR_TOO_LARGE: n_blocks >= 2^31.  Nothing is
+ *   written in these cases.  One read-back (the error words) with one stream synchronisation.  d_in and d_out may be at any
+ *   address and must not overlap.
+ * Not covered: plain (non-BGZF) gzip, members with further extra subfields, walking BAM records out of the inflated stream,
+ * .gzi / tabix, speculative decoding inside a block. */
+enum {
+    BG_INFLATE_OK = 0,
+    BG_INFLATE_BAD_TYPE = 1,     /* deflate block type 3 */
+    BG_INFLATE_BAD_STORED = 2,   /* LEN is not ~NLEN */
+    BG_INFLATE_BAD_LENGTHS = 3,  /* the dynamic header: counts, repeats, an illegal code set, no code for 256 */
+    BG_INFLATE_BAD_SYMBOL = 4,   /* a code that is not assigned, literal/length 286 / 287, distance code 30 / 31 */
+    BG_INFLATE_BAD_DISTANCE = 5, /* a distance beyond the bytes produced so far */
+    BG_INFLATE_TRUNCATED = 6,    /* bits wanted beyond the stream */
+    BG_INFLATE_TRAILING = 7,     /* unused bytes behind the final deflate block */
+    BG_INFLATE_SIZE = 8,         /* not the output range's length, or not ISIZE */
+    BG_INFLATE_CRC = 9
+};
+int bg_bgzf_blocks_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uint64_t* d_block_off, uint64_t* d_out_off,
+                       uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* out_bytes, uint64_t* first_bad, void* stream);
+int bg_bgzf_blocks(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint64_t* block_off, uint64_t* out_off, uint64_t cap_blocks,
+                   uint64_t* n_blocks, uint64_t* out_bytes, uint64_t* first_bad);
+int bg_bgzf_inflate_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, uint64_t n_blocks, const uint64_t* d_block_off,
+                        const uint64_t* d_out_off, uint8_t* d_out, uint64_t out_cap, uint8_t* d_status, uint64_t* first_bad,
+                        void* stream);
+int bg_bgzf_inflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint64_t n_blocks, const uint64_t* block_off,
+                    const uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint8_t* status, uint64_t* first_bad);
+
 /* ---- the BAI index of a coordinate-sorted BAM stream (bam_index.hip; the bodies in csrc/bam_index_rule.h) ----------------
  * What makes the file above usable by region: the bytes of the .bai file (SAM v1.6, section 5.2) beside it, from what is in
  * HBM when the file is framed.  bg_bam_index[_dev] reads BAM RECORDS, not hits: slot i is recs[off[i] .. off[i + 1]) — the pair

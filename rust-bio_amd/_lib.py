@@ -224,6 +224,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_sam_sort_keys_dev", "bg_sam_sort", "bg_sam_sort_dev", "bg_sam_header_so",
            "bg_bam_header", "bg_bam_emit_batch", "bg_bam_emit_batch_dev", "bg_bgzf_frame", "bg_bgzf_frame_dev",
            "bg_bgzf_deflate", "bg_bgzf_deflate_dev", "bg_bam_index", "bg_bam_index_dev",
+           "bg_bgzf_blocks", "bg_bgzf_blocks_dev", "bg_bgzf_inflate", "bg_bgzf_inflate_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -403,6 +404,10 @@ def lib():
         L.bg_bgzf_frame.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
         L.bg_bgzf_deflate_dev.argtypes = [vp, vp, u64, u32, vp, u64, vp, C.POINTER(u64), vp]
         L.bg_bgzf_deflate.argtypes = [vp, vp, u64, u32, vp, u64, vp, C.POINTER(u64)]
+        L.bg_bgzf_blocks_dev.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bgzf_blocks.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bgzf_inflate_dev.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, vp, C.POINTER(u64), vp]
+        L.bg_bgzf_inflate.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, vp, C.POINTER(u64)]
         L.bg_bam_index_dev.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_bam_index.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]

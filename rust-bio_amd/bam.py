@@ -1,10 +1,11 @@
-"""BAM records, BGZF framing and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
-`bg_bgzf_deflate[_dev]` and `bg_bam_index[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+"""BAM records, BGZF framing and reading, and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
+`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]` and `bg_bam_index[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
 container holds stored deflate blocks with a CRC-32 each (rust-bio_amd/csrc/bgzf.hip) or blocks compressed on the device
-(rust-bio_amd/csrc/bgzf_deflate.hip); the index is built from the sorted records and the framing's block table
+(rust-bio_amd/csrc/bgzf_deflate.hip) and is read back by `read_bgzf` (rust-bio_amd/csrc/bgzf_inflate.hip: the block table
+of a stream, every block inflated and checked on the device); the index is built from the sorted records and the framing's block table
 (rust-bio_amd/csrc/bam_index.hip).  This module only marshals arguments."""
 import ctypes as C
 
@@ -121,6 +122,108 @@ def bgzf_deflate_dev(d_in, in_bytes, d_out, out_cap, flags=0, stream=0, ctx=None
     _lib.check(_lib.lib().bg_bgzf_deflate_dev(ctx.h, d_in or None, in_bytes, flags, d_out or None, out_cap, d_block_off or None, C.byref(n), stream),
                "bg_bgzf_deflate_dev")
     return int(n.value)
+
+
+INFLATE_STATUS = ["ok", "bad block type", "bad stored lengths", "bad code lengths", "bad symbol", "bad distance", "truncated",
+                  "trailing bytes", "size", "CRC"]  # BG_INFLATE_*
+
+
+class BgzfError(_lib.BiogpuError):
+    """bg_bgzf_blocks[_dev] or bg_bgzf_inflate[_dev] refused a stream: `block` is the index of the first offending member (None:
+    none is to blame), `offset` its file offset where known, `inflate_status` its BG_INFLATE_* status (None: it came from the
+    block table or from the call's arguments)"""
+
+    def __init__(self, status, where, block, offset=None, inflate_status=None):
+        super().__init__(status, where)
+        self.block, self.offset, self.inflate_status = block, offset, inflate_status
+
+
+def _bad(first_bad):
+    return None if first_bad.value == 2**64 - 1 else int(first_bad.value)
+
+
+def bgzf_blocks_arrays(data, ctx=None):
+    """bg_bgzf_blocks, host buffers: the block table of the BGZF stream `data`.  Returns (block_off, out_off), uint64[n_blocks + 1]
+    each: the members' starts and `len(data)`; the exclusive prefix sum of their ISIZE fields.  Raises BgzfError (status -1
+    INVALID_ARG, -11 UNSUPPORTED) with the index of the first member the chain cannot continue with and its file offset."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(data)
+    nbytes = len(src)
+    src = src if nbytes else np.zeros(1, np.uint8)
+    n, total, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(block_off, out_off, cap):
+        rc = _lib.lib().bg_bgzf_blocks(ctx.h, src.ctypes.data, nbytes, block_off, out_off, cap, C.byref(n), C.byref(total), C.byref(bad))
+        if rc != _lib.BG_OK:
+            at = 0
+            for _ in range(_bad(bad) or 0):  # the members in front of the offending one are good: their BSIZE leads to it
+                at += int(src[at + 16]) + (int(src[at + 17]) << 8) + 1
+            raise BgzfError(rc, "bg_bgzf_blocks", _bad(bad), None if _bad(bad) is None else at)
+    call(None, None, 0)
+    block_off, out_off = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+    call(block_off.ctypes.data, out_off.ctypes.data, n.value)
+    return block_off, out_off
+
+
+def bgzf_blocks_dev(d_in, in_bytes, d_block_off=0, d_out_off=0, cap_blocks=0, stream=0, ctx=None):
+    """bg_bgzf_blocks_dev (pointers are ints; both tables 0 with cap_blocks = 0 sizes).  Returns (n_blocks, out_bytes), read back
+    with one synchronisation of `stream`; the tables get n_blocks + 1 entries each.  Raises BgzfError as `bgzf_blocks_arrays`
+    (`block` only: the tables stay unwritten on an error and the file is in HBM, so `offset` is None),
+    BiogpuError with status -9 (OPS_CAP) when cap_blocks is too small."""
+    ctx = ctx or _lib.default_context()
+    n, total, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bgzf_blocks_dev(ctx.h, d_in or None, in_bytes, d_block_off or None, d_out_off or None, cap_blocks, C.byref(n), C.byref(total),
+                                       C.byref(bad), stream)
+    if rc in (-1, -11):
+        raise BgzfError(rc, "bg_bgzf_blocks_dev", _bad(bad))
+    _lib.check(rc, "bg_bgzf_blocks_dev")
+    return int(n.value), int(total.value)
+
+
+def bgzf_inflate_arrays(data, block_off, out_off, ctx=None):
+    """bg_bgzf_inflate, host buffers: the payloads of the members `block_off` names, each at its `out_off`.  Returns (bytes,
+    status: uint8[n_blocks]) when every block is good; raises BgzfError with the lowest bad block, its file offset and its
+    BG_INFLATE_* status otherwise."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(data)
+    nbytes = len(src)
+    src = src if nbytes else np.zeros(1, np.uint8)
+    block_off = np.ascontiguousarray(block_off, dtype=np.uint64)
+    out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+    n = len(block_off) - 1
+    assert n >= 0 and len(out_off) == n + 1
+    total = int(out_off[n])
+    out, status, bad = np.zeros(max(total, 1), np.uint8), np.zeros(max(n, 1), np.uint8), C.c_uint64(0)
+    rc = _lib.lib().bg_bgzf_inflate(ctx.h, src.ctypes.data, nbytes, n, block_off.ctypes.data, out_off.ctypes.data, out.ctypes.data, total,
+                                    status.ctypes.data, C.byref(bad))
+    if rc == -1:
+        b = _bad(bad)
+        raise BgzfError(rc, "bg_bgzf_inflate", b, None if b is None else int(block_off[b]), None if b is None or not status[b] else int(status[b]))
+    _lib.check(rc, "bg_bgzf_inflate")
+    return out[:total].tobytes(), status[:n]
+
+
+def bgzf_inflate_dev(d_in, in_bytes, n_blocks, d_block_off, d_out_off, d_out, out_cap, d_status=0, stream=0, ctx=None):
+    """bg_bgzf_inflate_dev (pointers are ints; d_status may be 0).  One read-back with one synchronisation of `stream`.  Raises
+    BgzfError (status -1) with the lowest bad block, or the first offending row of the tables; BiogpuError with status -9
+    (OPS_CAP) when out_cap is below out_off[n_blocks].  Good blocks' payloads are written in either case but the last.
+    The error carries `block` only: this module holds no device copy routine, so the caller reads d_status[block] (the
+    BG_INFLATE_* status; 0 there means the tables were refused) and d_block_off[block] (the file offset) from its own
+    buffers.  d_out may be 0 with out_cap = 0 for a stream of empty members."""
+    ctx = ctx or _lib.default_context()
+    bad = C.c_uint64(0)
+    rc = _lib.lib().bg_bgzf_inflate_dev(ctx.h, d_in or None, in_bytes, n_blocks, d_block_off or None, d_out_off or None, d_out or None, out_cap,
+                                        d_status or None, C.byref(bad), stream)
+    if rc == -1:
+        raise BgzfError(rc, "bg_bgzf_inflate_dev", _bad(bad))
+    _lib.check(rc, "bg_bgzf_inflate_dev")
+
+
+def read_bgzf(data, ctx=None):
+    """The payload of the BGZF stream `data` (a .bam, a bgzipped .fastq.gz) as bytes: `bgzf_blocks_arrays`, then
+    `bgzf_inflate_arrays`"""
+    block_off, out_off = bgzf_blocks_arrays(data, ctx=ctx)
+    return bgzf_inflate_arrays(data, block_off, out_off, ctx=ctx)[0]
 
 
 def virtual_offsets(stream_offsets, block_off, base=0):

@@ -122,6 +122,25 @@ def parse_dev(d_text, ctx=None, stream=0, bufs=None):
     return k, STATUS[st.value], int(ep.value), d_recs[:k * 56], d_seq, d_so[:k + 1], d_qual, d_qo[:k + 1]
 
 
+def parse_bgzf_dev(d_file, ctx=None, stream=0):
+    """d_file: uint8 torch tensor on the device holding a bgzipped FASTQ file (.fastq.gz written by bgzip, htslib or
+    `bam.bgzf_deflate_*`).  The block table (bg_bgzf_blocks_dev), the payloads (bg_bgzf_inflate_dev) and the parse
+    (`parse_dev`) run on the device; the text never visits the host.  Returns (d_text, the tuple of `parse_dev` on it); raises
+    `bam.BgzfError` where the file is not BGZF or a block does not inflate."""
+    import torch
+    from . import bam
+    ctx = ctx or _lib.default_context()
+    ln = int(d_file.numel())
+    cap = ln // 28 + 1  # a member has at least 28 bytes: the tables need no sizing call
+    d_block_off = torch.empty(cap + 1, dtype=torch.int64, device=d_file.device)
+    d_out_off = torch.empty(cap + 1, dtype=torch.int64, device=d_file.device)
+    n_blocks, out_bytes = bam.bgzf_blocks_dev(d_file.data_ptr(), ln, d_block_off.data_ptr(), d_out_off.data_ptr(), cap, stream=stream, ctx=ctx)
+    d_text = torch.empty(out_bytes, dtype=torch.uint8, device=d_file.device)  # (no bytes, no address: a file of empty members)
+    bam.bgzf_inflate_dev(d_file.data_ptr(), ln, n_blocks, d_block_off.data_ptr(), d_out_off.data_ptr(), d_text.data_ptr() if out_bytes else 0, out_bytes,
+                         stream=stream, ctx=ctx)
+    return d_text, parse_dev(d_text, ctx=ctx, stream=stream)
+
+
 def alloc_dev(ln, device):
     """output buffers of parse_dev for a text of `ln` bytes: records, sequences, qualities, their offsets"""
     import torch
