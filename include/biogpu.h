@@ -1252,8 +1252,9 @@ int bg_bgzf_deflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t 
 
 /* ---- reading BGZF: the block table and the payloads (bgzf_inflate.hip; the bodies in csrc/bgzf_inflate_rule.h) ------------
  * The way back from a .bam or a bgzipped .fastq.gz that lies in HBM: bg_bgzf_blocks[_dev] finds the members, bg_bgzf_inflate
- * [_dev] inflates every one to its final place and checks it; the text then goes to bg_fastq_parse_dev, BAM bodies to
- * bg_bam_index_dev / bg_sam_sort_dev, without the bytes visiting the host.
+ * [_dev] inflates every one to its final place and checks it; the text then goes to bg_fastq_parse_dev, a BAM stream through
+ * bg_bam_header_parse and bg_bam_records_dev (the section "reading BAM" below) to bg_bam_reads_dev, bg_bam_index_blocks_dev
+ * and bg_sam_sort_dev, without the bytes visiting the host.
  *
  * bg_bgzf_blocks[_dev].  THE RULE: the stream is a chain of gzip members from byte 0; member b starts at block_off[b] and is
  *   BSIZE + 1 bytes long; the chain must end exactly at in_bytes.  block_off gets n_blocks + 1 entries, the last in_bytes (the
@@ -1296,8 +1297,8 @@ int bg_bgzf_deflate(bg_ctx* ctx, const uint8_t* in, uint64_t in_bytes, uint32_t 
  *   stream of empty members); BG_ERR_TOO_LARGE: n_blocks >= 2^31.  Nothing is
  *   written in these cases.  One read-back (the error words) with one stream synchronisation.  d_in and d_out may be at any
  *   address and must not overlap.
- * Not covered: plain (non-BGZF) gzip, members with further extra subfields, walking BAM records out of the inflated stream,
- * .gzi / tabix, speculative decoding inside a block. */
+ * Not covered: plain (non-BGZF) gzip, members with further extra subfields, .gzi / tabix, speculative decoding inside a
+ * block. */
 enum {
     BG_INFLATE_OK = 0,
     BG_INFLATE_BAD_TYPE = 1,     /* deflate block type 3 */
@@ -1368,6 +1369,104 @@ int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const
 int bg_bam_index(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
                  uint64_t n_contigs, const uint64_t* block_off, uint64_t base, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes,
                  uint64_t* first_bad);
+
+/* ---- reading BAM: header, record table, reads, keys, index (bam_read.hip, bam_index.hip; the bodies in csrc/bam_read_rule.h) ----
+ * What turns the inflated stream of any .bam (bg_bgzf_blocks / bg_bgzf_inflate above) into what the rest of the library takes:
+ *   bg_bam_header_parse        the inverse of bg_bam_header: contigs, names, the SAM text, where the records start (host only)
+ *   bg_bam_records[_dev]       the record table `off`: with recs = the stream, the pair bg_bam_index and bg_sam_sort take
+ *   bg_bam_reads[_dev]         records -> the five FASTQ columns (uBAM in, a mapped BAM to be re-mapped)
+ *   bg_bam_sort_keys[_dev]     a coordinate key per record, for bg_sam_sort[_dev]
+ *   bg_bam_index_blocks[_dev]  bg_bam_index for a stream in any framing, from bg_bgzf_blocks' tables
+ * `off` holds ABSOLUTE offsets into the stream: off[0] = body_off, record i is bam[off[i] .. off[i + 1]).
+ *
+ * bg_bam_header_parse.  in[0 .. bytes) is a prefix of the stream.  Fills contigs[i] (len = l_ref, name_off / name_len into
+ *   `names`, the names back to back without their NULs, start = sum over j < i of (len_j + 1): the layout of
+ *   bg_fasta_reference without BG_FASTA_REF_FMD, so bg_bam_sort_keys gives the keys bg_sam_sort_keys gives the hits),
+ *   *text_off / *text_len (the SAM header text inside the prefix) and *body_off (the first record).  A prefix that ends inside
+ *   the header: BG_ERR_OPS_CAP with *need = the smallest length known to be required so far (> bytes, never beyond the
+ *   header's end: 9 bytes are counted for every reference not yet seen); a caller that fetches max(need, 2 * bytes) each time
+ *   copies a logarithmic number of prefixes.  BG_ERR_INVALID_ARG: a wrong magic, a negative l_text, n_ref or l_ref, an
+ *   l_name below 1, a name whose last byte is not NUL.  Null tables with zero caps size the call (*n_contigs,
+ *   *names_bytes); caps that are too small: BG_ERR_OPS_CAP with the counts set, *need = 0 and nothing written.
+ *
+ * bg_bam_records[_dev].  THE RULE: the records are the chain from body_off — a record at o is followed by one at
+ *   o + 4 + block_size — and the chain must end exactly at in_bytes.  A position o carries an accepted record when: at least
+ *   36 bytes are left; block_size >= 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq (in 64 bits; block_size is
+ *   unsigned); o + 4 + block_size <= in_bytes; l_read_name >= 1 and the name's last byte is NUL; l_seq >= 0; refID and
+ *   next_refID lie in [-1, n_ref); pos >= -1 and next_pos >= -1.  What stands at a chain position without being accepted is
+ *   the error: BG_ERR_INVALID_ARG, *first_bad (optional; UINT64_MAX otherwise) = *n_records = the records in front of it,
+ *   the table unwritten.  The chain is the truth: bytes inside a record that look like one (qualities, a B array, a Z tag)
+ *   are never reported.  body_off == in_bytes gives 0 records (off[0] = in_bytes).  A null off with cap_records == 0 sizes;
+ *   cap_records < n_records: BG_ERR_OPS_CAP with *n_records set and the table unwritten (it holds cap_records + 1
+ *   entries).  BG_ERR_TOO_LARGE: in_bytes >= 2^35, or 2^32 - 1 or more candidates (a 32-bit jump index).  BG_ERR_INVALID_ARG
+ *   also: a null ctx or n_records, a null stream with in_bytes > 0, body_off > in_bytes.  *n_candidates (optional): the
+ *   positions from body_off on that carry an accepted record, the chain's and the fakes.
+ *   Unlike BGZF members, accepted positions have no minimum distance (two may lie 4 bytes apart) and no bound short of one
+ *   a position: the candidates are counted first and that total is read back to size the scratch (the ctx's, 18 bytes a
+ *   candidate; BG_ERR_OOM with nothing written where it cannot be had), then n_records and the error: TWO stream
+ *   synchronisations, one more than bg_bgzf_blocks.
+ *
+ * bg_bam_reads[_dev].  prm: flags (BG_BAM_READS_ORIGINAL), require, exclude.  THE RULE: a record is kept when
+ *   (flag & require) == require && (flag & exclude) == 0; read j is the j-th kept record in file order (mates are adjacent
+ *   exactly where they are in the file).  A slot of length 0 is skipped.  recs[j]: id_off = off + 36 into the stream (the
+ *   stream stands where the other calls take d_fastq_text), id_len = l_read_name - 1, 0 for the name "*"; has_desc = 0,
+ *   desc_len = 0, desc_off = id_off + id_len; seq: one byte a base from "=ACMGRSVTWYHKDBN", high nibble first; qual: each
+ *   byte + 33 modulo 256, qual_len = 0 where l_seq > 0 and the first quality byte is 0xFF (the SAM writer then writes "*", as
+ *   before the record was encoded); seq_off / qual_off as bg_fastq_parse fills them (n_reads + 1 entries); check is
+ *   Record::check on these fields (a base "=" is BG_FQCHECK_INVALID_SEQ).  With BG_BAM_READS_ORIGINAL a record with FLAG 0x10
+ *   gives the bytes bg_revcomp_batch_dev gives for its bases ("=" stays) and its qualities reversed.  src (optional):
+ *   src[j] = the slot of read j.  A null recs (all caps 0, every output null) sizes: *n_reads, *seq_bytes, *qual_bytes;
+ *   cap_reads, seq_cap or qual_cap too small: BG_ERR_OPS_CAP with the three set and nothing written.
+ *   BG_ERR_INVALID_ARG with *first_bad = the first non-empty slot that is not exactly one accepted record by the verdict
+ *   above (the table may come from elsewhere; off must lie inside the stream); unknown flag bits; null pointers.
+ *   BG_ERR_TOO_LARGE: n_records >= 2^32 - 1.  One read-back with one stream synchronisation; the write pass is then
+ *   asynchronous on `stream`.  Byte pointers at any address: record bytes are read byte by byte, seq / qual are stored 16
+ *   bytes wide between their own 16-byte boundaries.
+ *
+ * bg_bam_sort_keys[_dev].  key[i] = contigs[refID].start + pos where refID >= 0 and pos >= 0, UINT64_MAX otherwise and for a
+ *   slot of length 0.  With bg_bam_header_parse's start this is bg_sam_sort_keys' key of the slot the record was written
+ *   from.  Checks as bg_bam_reads, with n_ref = n_contigs.
+ *
+ * bg_bam_index_blocks[_dev].  bg_bam_index[_dev] with recs = the stream, off absolute, and the framing given by n_blocks,
+ *   block_off and out_off as bg_bgzf_blocks fills them (n_blocks + 1 rows each; not checked), no base.  Everything in THE
+ *   RULE of bg_bam_index holds except voff(o): b is the first block with out_off[b + 1] > o; where there is none (o is the
+ *   stream's length) the first block with out_off[b] == o, the closing row where no block has; voff = block_off[b] << 16 |
+ *   (o - out_off[b]).  Empty members in front of a byte are skipped, the stream's end points at the end-of-file block where
+ *   there is one.
+ * Not covered: CSI / tabix / .gzi, collating mates by name, aux tags as columns, CRAM, SAM text in, header lines beyond
+ * what the text carries (the text is handed back, not interpreted). */
+enum { BG_BAM_READS_ORIGINAL = 1 };
+typedef struct {
+    uint32_t flags;     /* BG_BAM_READS_* */
+    uint16_t require;   /* FLAG bits a kept record has */
+    uint16_t exclude;   /* FLAG bits a kept record lacks */
+} bg_bam_reads_t;
+int bg_bam_header_parse(const uint8_t* in, uint64_t bytes, bg_sam_contig_t* contigs, uint64_t cap_contigs, char* names,
+                        uint64_t names_cap, uint64_t* n_contigs, uint64_t* names_bytes, uint64_t* text_off, uint64_t* text_len,
+                        uint64_t* body_off, uint64_t* need);
+int bg_bam_records_dev(bg_ctx* ctx, const uint8_t* d_bam, uint64_t in_bytes, uint64_t body_off, uint64_t n_ref, uint64_t* d_off,
+                       uint64_t cap_records, uint64_t* n_records, uint64_t* n_candidates, uint64_t* first_bad, void* stream);
+int bg_bam_records(bg_ctx* ctx, const uint8_t* bam, uint64_t in_bytes, uint64_t body_off, uint64_t n_ref, uint64_t* off,
+                   uint64_t cap_records, uint64_t* n_records, uint64_t* n_candidates, uint64_t* first_bad);
+int bg_bam_reads_dev(bg_ctx* ctx, const bg_bam_reads_t* prm, uint64_t n_records, const uint8_t* d_bam, const uint64_t* d_off,
+                     uint64_t n_ref, bg_fastq_record_t* d_recs, uint64_t cap_reads, uint8_t* d_seq, uint64_t seq_cap,
+                     uint64_t* d_seq_off, uint8_t* d_qual, uint64_t qual_cap, uint64_t* d_qual_off, uint64_t* d_src,
+                     uint64_t* n_reads, uint64_t* seq_bytes, uint64_t* qual_bytes, uint64_t* first_bad, void* stream);
+int bg_bam_reads(bg_ctx* ctx, const bg_bam_reads_t* prm, uint64_t n_records, const uint8_t* bam, const uint64_t* off,
+                 uint64_t n_ref, bg_fastq_record_t* recs, uint64_t cap_reads, uint8_t* seq, uint64_t seq_cap, uint64_t* seq_off,
+                 uint8_t* qual, uint64_t qual_cap, uint64_t* qual_off, uint64_t* src, uint64_t* n_reads, uint64_t* seq_bytes,
+                 uint64_t* qual_bytes, uint64_t* first_bad);
+int bg_bam_sort_keys_dev(bg_ctx* ctx, uint64_t n_records, const uint8_t* d_bam, const uint64_t* d_off,
+                         const bg_sam_contig_t* d_contigs, uint64_t n_contigs, uint64_t* d_key, uint64_t* first_bad, void* stream);
+int bg_bam_sort_keys(bg_ctx* ctx, uint64_t n_records, const uint8_t* bam, const uint64_t* off, const bg_sam_contig_t* contigs,
+                     uint64_t n_contigs, uint64_t* key, uint64_t* first_bad);
+int bg_bam_index_blocks_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                            const bg_sam_contig_t* d_contigs, uint64_t n_contigs, uint64_t n_blocks, const uint64_t* d_block_off,
+                            const uint64_t* d_out_off, uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad,
+                            void* stream);
+int bg_bam_index_blocks(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
+                        uint64_t n_contigs, uint64_t n_blocks, const uint64_t* block_off, const uint64_t* out_off, uint8_t* out,
+                        uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

@@ -171,6 +171,15 @@ MARKDUP_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("max_hits", "<u4"), ("phred_
 assert MARKDUP_PARAMS_DTYPE.itemsize == 16, MARKDUP_PARAMS_DTYPE.itemsize
 SAM_SO_UNSORTED, SAM_SO_COORDINATE = 0, 1
 BGZF_EOF = 1  # BG_BGZF_EOF
+BAM_READS_ORIGINAL = 1  # BG_BAM_READS_ORIGINAL
+
+
+# bg_bam_reads_t (bg_bam_reads[_dev])
+class BAM_READS(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("require", C.c_uint16), ("exclude", C.c_uint16)]
+
+
+assert C.sizeof(BAM_READS) == 8, C.sizeof(BAM_READS)
 
 # bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
@@ -225,6 +234,8 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_bam_header", "bg_bam_emit_batch", "bg_bam_emit_batch_dev", "bg_bgzf_frame", "bg_bgzf_frame_dev",
            "bg_bgzf_deflate", "bg_bgzf_deflate_dev", "bg_bam_index", "bg_bam_index_dev",
            "bg_bgzf_blocks", "bg_bgzf_blocks_dev", "bg_bgzf_inflate", "bg_bgzf_inflate_dev",
+           "bg_bam_header_parse", "bg_bam_records", "bg_bam_records_dev", "bg_bam_reads", "bg_bam_reads_dev",
+           "bg_bam_sort_keys", "bg_bam_sort_keys_dev", "bg_bam_index_blocks", "bg_bam_index_blocks_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -410,6 +421,15 @@ def lib():
         L.bg_bgzf_inflate.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, vp, C.POINTER(u64)]
         L.bg_bam_index_dev.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_bam_index.argtypes = [vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_header_parse.argtypes = [vp, u64, vp, u64, vp, u64] + [C.POINTER(u64)] * 6
+        L.bg_bam_records_dev.argtypes = [vp, vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_records.argtypes = [vp, vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_reads_dev.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_sort_keys_dev.argtypes = [vp, u64, vp, vp, vp, u64, vp, C.POINTER(u64), vp]
+        L.bg_bam_sort_keys.argtypes = [vp, u64, vp, vp, vp, u64, vp, C.POINTER(u64)]
+        L.bg_bam_index_blocks_dev.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_index_blocks.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

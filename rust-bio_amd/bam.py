@@ -1,5 +1,5 @@
 """BAM records, BGZF framing and reading, and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
-`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]` and `bg_bam_index[_dev]`; `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, sam
-from ._lib import BGZF_EOF, SAM_SO_COORDINATE, SAM_SO_UNSORTED  # noqa: F401
+from ._lib import BAM_READS_ORIGINAL, BGZF_EOF, SAM_SO_COORDINATE, SAM_SO_UNSORTED  # noqa: F401
 
 PAYLOAD = 65280      # bytes of a full block's payload
 BLOCK_HEAD = 23      # bytes of a block in front of its payload
@@ -291,6 +291,199 @@ def index_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_out, out_cap, d_bl
                                      d_out or None, out_cap, C.byref(total), C.byref(bad), stream)
     _index_check(rc, "bg_bam_index_dev", bad)
     return int(total.value)
+
+
+def index_blocks_arrays(stream, off, contigs, block_off, out_off, ctx=None):
+    """bg_bam_index_blocks, host buffers: `index_arrays` for a stream in any framing.  `stream` is the whole uncompressed stream,
+    `off` the absolute record table (`records_arrays`), block_off / out_off the tables `bgzf_blocks_arrays` gave for the file."""
+    ctx = ctx or _lib.default_context()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    table = np.ascontiguousarray(contigs.table)
+    block_off, out_off = np.ascontiguousarray(block_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+    assert len(block_off) == len(out_off) >= 1
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cap):
+        return _lib.lib().bg_bam_index_blocks(ctx.h, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                              len(table), len(block_off) - 1, block_off.ctypes.data, out_off.ctypes.data, out, cap, C.byref(total),
+                                              C.byref(bad))
+    _index_check(call(None, 0), "bg_bam_index_blocks", bad)
+    out = np.zeros(max(total.value, 1), dtype=np.uint8)
+    _index_check(call(out.ctypes.data, total.value), "bg_bam_index_blocks", bad)
+    return out[:total.value].tobytes()
+
+
+def index_blocks_dev(n_slots, d_stream, d_off, d_contigs, n_contigs, n_blocks, d_block_off, d_out_off, d_out, out_cap, stream=0, ctx=None):
+    """bg_bam_index_blocks_dev (pointers are ints; d_out = 0 with out_cap = 0 sizes).  Returns the number of bytes of the index;
+    raises BamIndexError with the offending slot, BiogpuError with status -9 (OPS_CAP) when the index exceeds out_cap."""
+    ctx = ctx or _lib.default_context()
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_index_blocks_dev(ctx.h, n_slots, d_stream or None, d_off or None, d_contigs or None, n_contigs, n_blocks, d_block_off or None,
+                                            d_out_off or None, d_out or None, out_cap, C.byref(total), C.byref(bad), stream)
+    _index_check(rc, "bg_bam_index_blocks_dev", bad)
+    return int(total.value)
+
+
+# ---- reading BAM ------------------------------------------------------------------------------------------------------------
+class BamReadError(_lib.BiogpuError):
+    """bg_bam_header_parse, bg_bam_records[_dev], bg_bam_reads[_dev] or bg_bam_sort_keys[_dev] refused a stream: `record` is the
+    index of the first offending record or slot (None: none is to blame), `offset` its offset in the stream where known"""
+
+    def __init__(self, status, where, record, offset=None):
+        super().__init__(status, where)
+        self.record, self.offset = record, offset
+
+
+def read_header(fetch, first=65536):
+    """bg_bam_header_parse on a growing prefix.  `fetch(n)` returns (at most) the first n bytes of the uncompressed stream —
+    bytes, or a function over a device buffer; each round asks for at least twice the previous prefix, so a long reference
+    list costs a logarithmic number of copies.  `fetch` may also be the bytes themselves.  Returns (text: bytes, contigs:
+    sam.Contigs with start = sum of (len + 1) over the contigs in front, body_off)."""
+    if not callable(fetch):
+        data = fetch
+        fetch = lambda n: data[:n]  # noqa: E731
+    want = first
+    out = [C.c_uint64(0) for _ in range(6)]  # n_contigs, names_bytes, text_off, text_len, body_off, need
+    refs = [C.byref(x) for x in out]
+    while True:
+        pre = _lib.as_u8(fetch(want))
+        buf = pre if len(pre) else np.zeros(1, np.uint8)
+        rc = _lib.lib().bg_bam_header_parse(buf.ctypes.data, len(pre), None, 0, None, 0, *refs)
+        if rc == -9 and out[5].value > len(pre) and len(pre) >= want:  # the prefix ends inside the header, and there may be more
+            want = max(int(out[5].value), 2 * want)
+            continue
+        if rc != _lib.BG_OK:
+            raise BamReadError(rc, "bg_bam_header_parse", None)
+        break
+    table = np.zeros(out[0].value, dtype=_lib.SAM_CONTIG_DTYPE)
+    names = np.zeros(out[1].value + 1, dtype=np.uint8)
+    rc = _lib.lib().bg_bam_header_parse(buf.ctypes.data, len(pre), table.ctypes.data if len(table) else None, len(table),
+                                        names.ctypes.data if len(table) else None, out[1].value if len(table) else 0, *refs)
+    if rc != _lib.BG_OK:
+        raise BamReadError(rc, "bg_bam_header_parse", None)
+    contigs = sam.Contigs.from_arrays(table, names[:out[1].value])
+    return buf[out[2].value:out[2].value + out[3].value].tobytes(), contigs, int(out[4].value)
+
+
+def _read_check(rc, where, bad, off=None):
+    if rc in (-1,):
+        b = _bad(bad)
+        raise BamReadError(rc, where, b, None if b is None or off is None else int(off[b]))
+    _lib.check(rc, where)
+
+
+def records_arrays(stream, body_off, n_ref, ctx=None, candidates=False):
+    """bg_bam_records, host buffers: the record table of the uncompressed BAM stream `stream`: uint64[n_records + 1], absolute
+    offsets, off[0] = body_off, off[-1] = len(stream).  Raises BamReadError with the number of records in front of what is no
+    record.  candidates: returns (off, n_candidates)."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    nbytes = len(src)
+    src = src if nbytes else np.zeros(1, np.uint8)
+    n, cand, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _read_check(_lib.lib().bg_bam_records(ctx.h, src.ctypes.data, nbytes, body_off, n_ref, None, 0, C.byref(n), C.byref(cand), C.byref(bad)),
+                "bg_bam_records", bad)
+    off = np.zeros(n.value + 1, np.uint64)
+    _read_check(_lib.lib().bg_bam_records(ctx.h, src.ctypes.data, nbytes, body_off, n_ref, off.ctypes.data, n.value, C.byref(n), C.byref(cand),
+                                          C.byref(bad)), "bg_bam_records", bad)
+    return (off, int(cand.value)) if candidates else off
+
+
+def records_dev(d_bam, in_bytes, body_off, n_ref, d_off=0, cap_records=0, stream=0, ctx=None):
+    """bg_bam_records_dev (pointers are ints; d_off = 0 with cap_records = 0 sizes).  Returns (n_records, n_candidates), read back
+    with two synchronisations of `stream`; d_off gets n_records + 1 entries.  Raises BamReadError (`record`: the records in
+    front of the offending position), BiogpuError with status -9 (OPS_CAP) when cap_records is too small."""
+    ctx = ctx or _lib.default_context()
+    n, cand, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_records_dev(ctx.h, d_bam or None, in_bytes, body_off, n_ref, d_off or None, cap_records, C.byref(n), C.byref(cand),
+                                       C.byref(bad), stream)
+    _read_check(rc, "bg_bam_records_dev", bad)
+    return int(n.value), int(cand.value)
+
+
+def reads_params(flags=0, require=0, exclude=0):
+    return _lib.BAM_READS(flags, require, exclude)
+
+
+def reads_arrays(stream, off, n_ref, flags=0, require=0, exclude=0, ctx=None):
+    """bg_bam_reads, host buffers: the kept records of the table `off` as the five FASTQ columns.  Returns (recs: FQREC_DTYPE[],
+    seq, seq_off, qual, qual_off, src: uint64[], the record of every read); id_off points into `stream`."""
+    ctx = ctx or _lib.default_context()
+    src_b = _lib.as_u8(stream)
+    src_b = src_b if len(src_b) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    prm = reads_params(flags, require, exclude)
+    k, sb, qb, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    tail = (C.byref(k), C.byref(sb), C.byref(qb), C.byref(bad))
+    head = (ctx.h, C.byref(prm), n, src_b.ctypes.data, off.ctypes.data if n else None, n_ref)
+    _read_check(_lib.lib().bg_bam_reads(*head, None, 0, None, 0, None, None, 0, None, None, *tail), "bg_bam_reads", bad, off)
+    recs = np.zeros(max(k.value, 1), dtype=_lib.FQREC_DTYPE)
+    seq, qual = np.zeros(max(sb.value, 1), np.uint8), np.zeros(max(qb.value, 1), np.uint8)
+    seq_off, qual_off, src = np.zeros(k.value + 1, np.uint64), np.zeros(k.value + 1, np.uint64), np.zeros(max(k.value, 1), np.uint64)
+    _read_check(_lib.lib().bg_bam_reads(*head, recs.ctypes.data, k.value, seq.ctypes.data, sb.value, seq_off.ctypes.data, qual.ctypes.data, qb.value,
+                                        qual_off.ctypes.data, src.ctypes.data, *tail), "bg_bam_reads", bad, off)
+    return recs[:k.value], seq[:sb.value], seq_off, qual[:qb.value], qual_off, src[:k.value]
+
+
+def reads_dev(n_records, d_bam, d_off, n_ref, d_recs=0, cap_reads=0, d_seq=0, seq_cap=0, d_seq_off=0, d_qual=0, qual_cap=0, d_qual_off=0, d_src=0,
+              flags=0, require=0, exclude=0, stream=0, ctx=None):
+    """bg_bam_reads_dev (pointers are ints; every output 0 with caps 0 sizes; d_src may be 0).  Returns (n_reads, seq_bytes,
+    qual_bytes), read back with one synchronisation of `stream`; the columns are then written asynchronously.  Raises
+    BamReadError with the first slot that is no record, BiogpuError with status -9 (OPS_CAP) when a cap is too small."""
+    ctx = ctx or _lib.default_context()
+    prm = reads_params(flags, require, exclude)
+    k, sb, qb, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_reads_dev(ctx.h, C.byref(prm), n_records, d_bam or None, d_off or None, n_ref, d_recs or None, cap_reads, d_seq or None, seq_cap,
+                                     d_seq_off or None, d_qual or None, qual_cap, d_qual_off or None, d_src or None, C.byref(k), C.byref(sb), C.byref(qb),
+                                     C.byref(bad), stream)
+    _read_check(rc, "bg_bam_reads_dev", bad)
+    return int(k.value), int(sb.value), int(qb.value)
+
+
+def sort_keys_records_arrays(stream, off, contigs, ctx=None):
+    """bg_bam_sort_keys, host buffers: uint64[n_records], contigs.start[refID] + pos, 2^64 - 1 for a record without a position
+    and for an empty slot: what `sam.sort_arrays` takes as `key` with (stream, off)"""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    table = np.ascontiguousarray(contigs.table)
+    key, bad = np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_sort_keys(ctx.h, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None, len(table),
+                                     key.ctypes.data, C.byref(bad))
+    _read_check(rc, "bg_bam_sort_keys", bad, off)
+    return key[:n]
+
+
+def sort_keys_records_dev(n_records, d_bam, d_off, d_contigs, n_contigs, d_key, stream=0, ctx=None):
+    """bg_bam_sort_keys_dev (pointers are ints); one synchronisation of `stream`.  Raises BamReadError with the first bad slot."""
+    ctx = ctx or _lib.default_context()
+    bad = C.c_uint64(0)
+    rc = _lib.lib().bg_bam_sort_keys_dev(ctx.h, n_records, d_bam or None, d_off or None, d_contigs or None, n_contigs, d_key or None, C.byref(bad), stream)
+    _read_check(rc, "bg_bam_sort_keys_dev", bad)
+
+
+def read_bam(data, ctx=None):
+    """A BAM file (bytes) in one call: block table, inflate, header, record table.  Returns (text: the SAM header text, contigs:
+    sam.Contigs, stream: the uncompressed bytes, off: uint64[n_records + 1], absolute offsets into `stream`)."""
+    stream = read_bgzf(data, ctx=ctx)
+    text, contigs, body_off = read_header(stream)
+    return text, contigs, stream, records_arrays(stream, body_off, len(contigs), ctx=ctx)
+
+
+def index_bam(data, ctx=None):
+    """The bytes of the .bai of the coordinate-sorted BAM file `data`, whatever wrote it: `bgzf_blocks_arrays`, `read_bgzf`'s
+    inflate, `read_header`, `records_arrays`, `index_blocks_arrays`."""
+    block_off, out_off = bgzf_blocks_arrays(data, ctx=ctx)
+    stream = bgzf_inflate_arrays(data, block_off, out_off, ctx=ctx)[0]
+    _, contigs, body_off = read_header(stream)
+    off = records_arrays(stream, body_off, len(contigs), ctx=ctx)
+    return index_blocks_arrays(stream, off, contigs, block_off, out_off, ctx=ctx)
 
 
 def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False, index=False):

@@ -34,6 +34,8 @@ struct BaiArgs {
     uint64_t n_contigs;
     const uint64_t* block_off;
     uint64_t base;
+    uint64_t n_blocks;        // bg_bam_index_blocks: the rows of block_off and out_off (bg_bgzf_blocks' tables) ...
+    const uint64_t* out_off;  // ... null for the two framings of our own
 };
 struct BaiWork {
     unsigned long long* bad;  // slot << 2 | kind of the first offending slot, BAI_NONE without one
@@ -196,8 +198,8 @@ __global__ __launch_bounds__(256) void bai_write_chunk_kernel(const BaiArgs a, c
     const uint64_t b = w.bins_before[k] + (head ? 1 : 0) - 1, at = w.bin_start[b], first = w.chunk_first[ref];
     uint8_t* bin = out + 8 + w.ref_base[ref] + bai_bin_at(b - w.bins_before[first], at - first);
     if (head) bai_put_bin(bin, (uint32_t)(key & 0xFFFFu), w.bin_start[b + 1] - at);
-    bai_put_chunk(bin + 8 + 16 * (k - at), bai_voff(a.off[w.rec[j0].slot], a.block_off, a.base),
-                  bai_voff(a.off[w.rec[j1 - 1].slot + 1], a.block_off, a.base));
+    bai_put_chunk(bin + 8 + 16 * (k - at), bai_voff_any(a.off[w.rec[j0].slot], a.block_off, a.base, a.n_blocks, a.out_off),
+                  bai_voff_any(a.off[w.rec[j1 - 1].slot + 1], a.block_off, a.base, a.n_blocks, a.out_off));
 }
 
 constexpr uint32_t kRefRows = 8;  // blocks that share a reference's windows
@@ -214,13 +216,13 @@ __global__ __launch_bounds__(256) void bai_write_ref_kernel(const BaiArgs a, con
     if (lead) {
         const uint64_t unmapped = (w.hu[f.end] >> 32) - (w.hu[f.first] >> 32);
         bai_put32(ref, (uint32_t)(f.n_bins + 1));
-        bai_put_pseudo(ref + bai_pseudo_at(f.n_bins, f.n_chunks), bai_voff(a.off[w.rec[f.first].slot], a.block_off, a.base),
-                       bai_voff(a.off[w.rec[f.end - 1].slot + 1], a.block_off, a.base), f.end - f.first - unmapped, unmapped, f.n_intv);
+        bai_put_pseudo(ref + bai_pseudo_at(f.n_bins, f.n_chunks), bai_voff_any(a.off[w.rec[f.first].slot], a.block_off, a.base, a.n_blocks, a.out_off),
+                       bai_voff_any(a.off[w.rec[f.end - 1].slot + 1], a.block_off, a.base, a.n_blocks, a.out_off), f.end - f.first - unmapped, unmapped, f.n_intv);
     }
     uint8_t* intv = ref + bai_intv_at(f.n_bins, f.n_chunks) + 4;
     for (uint64_t x = (uint64_t)blockIdx.y * 256 + threadIdx.x; x < f.n_intv; x += kRefRows * 256) {
         const uint64_t j = bai_window_first(w.end_max, f.first, f.end, (uint32_t)r, x);
-        bai_put64(intv + 8 * x, bai_voff(a.off[w.rec[j].slot], a.block_off, a.base));
+        bai_put64(intv + 8 * x, bai_voff_any(a.off[w.rec[j].slot], a.block_off, a.base, a.n_blocks, a.out_off));
     }
 }
 
@@ -243,11 +245,10 @@ int bai_check(const bg_ctx* ctx, uint64_t n_slots, const void* recs, const void*
     return BG_OK;
 }
 
-}  // namespace
-
-extern "C" int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off, const bg_sam_contig_t* d_contigs,
-                                uint64_t n_contigs, const uint64_t* d_block_off, uint64_t base, uint8_t* d_out, uint64_t out_cap,
-                                uint64_t* out_bytes, uint64_t* first_bad, void* stream) {
+// bg_bam_index_dev (d_out_off null) and bg_bam_index_blocks_dev
+int index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off, const bg_sam_contig_t* d_contigs, uint64_t n_contigs,
+              const uint64_t* d_block_off, uint64_t base, uint64_t n_blocks, const uint64_t* d_out_off, uint8_t* d_out, uint64_t out_cap,
+              uint64_t* out_bytes, uint64_t* first_bad, void* stream) {
     int rc = bai_check(ctx, n_slots, d_recs, d_off, d_contigs, n_contigs, d_out, out_cap, out_bytes, first_bad);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -293,7 +294,7 @@ extern "C" int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_
     w.ref_bytes = (uint64_t*)(s + o_rbytes);
     w.ref_base = (uint64_t*)(s + o_rbase);
     void* d_tmp = s + o_tmp;
-    const BaiArgs a = {n, d_recs, d_off, d_contigs, n_contigs, d_block_off, base};
+    const BaiArgs a = {n, d_recs, d_off, d_contigs, n_contigs, d_block_off, base, n_blocks, d_out_off};
     BG_HIP(hipMemsetAsync(d_cells, 0xFF, 8, st));
     BG_HIP(hipMemsetAsync(d_cells + 1, 0, 8, st));
     BG_HIP(hipMemsetAsync(w.ref_first, 0, 4 * c1 * 8, st));
@@ -339,16 +340,59 @@ extern "C" int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_
     return BG_OK;
 }
 
+// what no index of these inputs exceeds: at most a bin and a chunk a slot, and every window of every contig
+uint64_t bai_bound(uint64_t n_slots, const bg_sam_contig_t* contigs, uint64_t n_contigs) {
+    uint64_t bound = bai_total(0) + 24 * n_slots;
+    for (uint64_t c = 0; c < n_contigs; c++) bound += bai_ref_bytes(true, 0, 0, (contigs[c].len >> BAI_LINEAR_SHIFT) + 1);
+    return bound;
+}
+
+}  // namespace
+
+extern "C" int bg_bam_index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off, const bg_sam_contig_t* d_contigs,
+                                uint64_t n_contigs, const uint64_t* d_block_off, uint64_t base, uint8_t* d_out, uint64_t out_cap,
+                                uint64_t* out_bytes, uint64_t* first_bad, void* stream) {
+    return index_dev(ctx, n_slots, d_recs, d_off, d_contigs, n_contigs, d_block_off, base, 0, nullptr, d_out, out_cap, out_bytes, first_bad, stream);
+}
+
+extern "C" int bg_bam_index_blocks_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off, const bg_sam_contig_t* d_contigs,
+                                       uint64_t n_contigs, uint64_t n_blocks, const uint64_t* d_block_off, const uint64_t* d_out_off, uint8_t* d_out,
+                                       uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad, void* stream) {
+    if (!d_block_off || !d_out_off) {
+        if (first_bad) *first_bad = UINT64_MAX;
+        return BG_ERR_INVALID_ARG;
+    }
+    return index_dev(ctx, n_slots, d_recs, d_off, d_contigs, n_contigs, d_block_off, 0, n_blocks, d_out_off, d_out, out_cap, out_bytes, first_bad, stream);
+}
+
+extern "C" int bg_bam_index_blocks(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
+                                   uint64_t n_contigs, uint64_t n_blocks, const uint64_t* block_off, const uint64_t* out_off, uint8_t* out,
+                                   uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad) {
+    int rc = bai_check(ctx, n_slots, recs, off, contigs, n_contigs, out, out_cap, out_bytes, first_bad);
+    if (rc) return rc;
+    if (!block_off || !out_off) return BG_ERR_INVALID_ARG;
+    const uint64_t total = n_slots ? off[n_slots] : 0;
+    const uint64_t cap = out ? std::min(out_cap, bai_bound(n_slots, contigs, n_contigs)) : 0;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_recs = s.up(recs, total);
+    const uint64_t* d_off = s.up(off, n_slots ? n_slots + 1 : 0);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const uint64_t* d_block_off = s.up(block_off, n_blocks + 1);
+    const uint64_t* d_out_off = s.up(out_off, n_blocks + 1);
+    uint8_t* d_out = out ? s.out<uint8_t>(cap) : nullptr;
+    if (s.rc) return s.rc;
+    if ((rc = bg_bam_index_blocks_dev(ctx, n_slots, d_recs, d_off, d_contigs, n_contigs, n_blocks, d_block_off, d_out_off, d_out, cap, out_bytes, first_bad, s.st))) return rc;
+    if (out) s.down(out, d_out, *out_bytes);
+    return s.sync();
+}
+
 extern "C" int bg_bam_index(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
                             uint64_t n_contigs, const uint64_t* block_off, uint64_t base, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes,
                             uint64_t* first_bad) {
     int rc = bai_check(ctx, n_slots, recs, off, contigs, n_contigs, out, out_cap, out_bytes, first_bad);
     if (rc) return rc;
     const uint64_t total = n_slots ? off[n_slots] : 0, n_blocks = (total + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD;
-    // what no index of these inputs exceeds: at most a bin and a chunk a slot, and every window of every contig
-    uint64_t bound = bai_total(0) + 24 * n_slots;
-    for (uint64_t c = 0; c < n_contigs; c++) bound += bai_ref_bytes(true, 0, 0, (contigs[c].len >> BAI_LINEAR_SHIFT) + 1);
-    const uint64_t cap = out ? std::min(out_cap, bound) : 0;
+    const uint64_t cap = out ? std::min(out_cap, bai_bound(n_slots, contigs, n_contigs)) : 0;
     bg_stage s(ctx, ctx->stream);
     const uint8_t* d_recs = s.up(recs, total);
     const uint64_t* d_off = s.up(off, n_slots ? n_slots + 1 : 0);

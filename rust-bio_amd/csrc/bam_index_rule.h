@@ -77,6 +77,32 @@ SAM_HD uint64_t bai_voff(uint64_t o, const uint64_t* block_off, uint64_t base) {
     const uint64_t b = o / BGZF_PAYLOAD, within = o % BGZF_PAYLOAD;
     return ((base + (block_off ? block_off[b] : b * BAI_FRAME_BLOCK)) << 16) | within;
 }
+// ... of a stream in any framing (bg_bam_index_blocks), from the tables bg_bgzf_blocks fills (n_blocks + 1 rows each): the first
+// block whose payload ends behind o; where there is none (o is the stream's length) the first block whose payload starts at o,
+// the closing row if no block does.  Empty members in front of a byte are skipped, the stream's end points at the end-of-file
+// block where there is one.
+SAM_HD uint64_t bai_voff_blocks(uint64_t o, uint64_t n_blocks, const uint64_t* block_off, const uint64_t* out_off) {
+    uint64_t lo = 0, hi = n_blocks;  // the first b with out_off[b + 1] > o
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (out_off[mid + 1] > o) hi = mid;
+        else lo = mid + 1;
+    }
+    if (lo == n_blocks) {  // the first b with out_off[b] >= o (== o: o is the stream's length)
+        lo = 0;
+        hi = n_blocks;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (out_off[mid] >= o) hi = mid;
+            else lo = mid + 1;
+        }
+    }
+    return (block_off[lo] << 16) | (o - out_off[lo]);
+}
+// the three ways: a table of any framing (out_off given), bg_bgzf_deflate's table, bg_bgzf_frame's closed form
+SAM_HD uint64_t bai_voff_any(uint64_t o, const uint64_t* block_off, uint64_t base, uint64_t n_blocks, const uint64_t* out_off) {
+    return out_off ? bai_voff_blocks(o, n_blocks, block_off, out_off) : bai_voff(o, block_off, base);
+}
 
 SAM_HD uint64_t bai_chunk_key(int32_t ref, uint32_t binf) { return ((uint64_t)(uint32_t)ref << 16) | (binf & 0xFFFFu); }
 #define BAI_KEY_BITS 48u                 // a key of a chunk lies below 2^47

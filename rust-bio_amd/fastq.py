@@ -141,6 +141,39 @@ def parse_bgzf_dev(d_file, ctx=None, stream=0):
     return d_text, parse_dev(d_text, ctx=ctx, stream=stream)
 
 
+def parse_bam_dev(d_file, flags=0, require=0, exclude=0, ctx=None, stream=0):
+    """d_file: uint8 torch tensor on the device holding a BAM file (uBAM from an instrument, a mapped BAM to be re-mapped).  The
+    block table, the payloads, the record table (bg_bam_records_dev) and the reads (bg_bam_reads_dev) run on the device; only
+    the header's prefix visits the host.  Returns (d_stream, (n_reads, d_recs, d_seq, d_seq_off, d_qual, d_qual_off, d_src)):
+    the columns every call after `parse_dev` takes, with d_stream where those take the FASTQ text.  flags: bam.BAM_READS_ORIGINAL;
+    require / exclude: FLAG bits (exclude=0x900 drops secondary and supplementary records)."""
+    import torch
+    from . import bam
+    ctx = ctx or _lib.default_context()
+    ln = int(d_file.numel())
+    cap = ln // 28 + 1
+    dev = d_file.device
+    d_block_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    d_out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    n_blocks, out_bytes = bam.bgzf_blocks_dev(d_file.data_ptr(), ln, d_block_off.data_ptr(), d_out_off.data_ptr(), cap, stream=stream, ctx=ctx)
+    d_stream = torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=dev)[:out_bytes]
+    bam.bgzf_inflate_dev(d_file.data_ptr(), ln, n_blocks, d_block_off.data_ptr(), d_out_off.data_ptr(), d_stream.data_ptr() if out_bytes else 0, out_bytes,
+                         stream=stream, ctx=ctx)
+    _, contigs, body_off = bam.read_header(lambda n: d_stream[:n].cpu().numpy())
+    n_ref = len(contigs)
+    n_rec, _ = bam.records_dev(d_stream.data_ptr(), out_bytes, body_off, n_ref, stream=stream, ctx=ctx)
+    d_off = torch.empty(n_rec + 1, dtype=torch.int64, device=dev)
+    bam.records_dev(d_stream.data_ptr(), out_bytes, body_off, n_ref, d_off.data_ptr(), n_rec, stream=stream, ctx=ctx)
+    k, sb, qb = bam.reads_dev(n_rec, d_stream.data_ptr(), d_off.data_ptr(), n_ref, flags=flags, require=require, exclude=exclude, stream=stream, ctx=ctx)
+    d_recs = torch.empty(max(k, 1) * 56, dtype=torch.uint8, device=dev)
+    d_seq, d_qual = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev), torch.empty(max(qb, 1), dtype=torch.uint8, device=dev)
+    d_so, d_qo = torch.empty(k + 1, dtype=torch.int64, device=dev), torch.empty(k + 1, dtype=torch.int64, device=dev)
+    d_src = torch.empty(max(k, 1), dtype=torch.int64, device=dev)
+    bam.reads_dev(n_rec, d_stream.data_ptr(), d_off.data_ptr(), n_ref, d_recs.data_ptr(), k, d_seq.data_ptr(), sb, d_so.data_ptr(), d_qual.data_ptr(), qb,
+                  d_qo.data_ptr(), d_src.data_ptr(), flags=flags, require=require, exclude=exclude, stream=stream, ctx=ctx)
+    return d_stream, (k, d_recs[:k * 56], d_seq[:sb], d_so, d_qual[:qb], d_qo, d_src[:k])
+
+
 def alloc_dev(ln, device):
     """output buffers of parse_dev for a text of `ln` bytes: records, sequences, qualities, their offsets"""
     import torch
