@@ -1930,9 +1930,11 @@ int bg_last_fill_kernels(bg_ctx* ctx, uint32_t* mask);
 /* 1 when the last bg_align_batch* call ran K1p's local flavour (BG_FILL_K1P_LF) with its keys in the offset frame (the cell
  * taken where every key fits it; the option "no_pk16_frame" turns it off), else 0. */
 int bg_last_fill_framed(bg_ctx* ctx, int* framed);
-/* 1 when that framed cell took its best key with v_pk_maximum3_f16 (where every key of the frame is also a finite
- * half-precision bit pattern, below 0x7c00; the option "no_pk16_max3" turns it off: same results, the cell of
- * v_pk_max_i16), else 0.  Implies bg_last_fill_framed. */
+/* 1 when that framed cell was the one of v_pk_maximum3_f16: best key and row maxima by maxima of three, the local floor
+ * through D, the match term by one saturating subtract.  Taken where every key of the frame is also a finite
+ * half-precision bit pattern, below 0x7c00, and a match is worth at most 15 more than a mismatch (16 (match - mismatch)
+ * + 2 <= 256); the option "no_pk16_max3" turns it off: same results, the cell of v_pk_max_i16.  Else 0.  Implies
+ * bg_last_fill_framed. */
 int bg_last_fill_max3(bg_ctx* ctx, int* max3);
 int bg_enable_timing(bg_ctx* ctx, int on);
 

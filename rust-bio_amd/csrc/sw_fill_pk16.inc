@@ -18,6 +18,10 @@
 
 #include "sw_kernels.h"
 
+#ifndef PK16_CELL_KO
+#define PK16_CELL_KO 0
+#endif
+
 namespace bgsw {
 namespace pk16 {
 
@@ -95,9 +99,26 @@ enum { CZ = 0, CF = 1, CI = 2 };
 // the frame as they are taken (best^ - F + priority, one subtract instead of the or), and so do Sl / Il when they are
 // parked: the epilogue, the traceback cells and K2 see what the plain LF cell gives them.  The values crossing to the lane
 // below (row R - 1 there, row -1 here) are re-based by g (R - 1), and 0 is 'minus infinity' of I and D.
-// FR == 2 (where pk16_max3_fits: every key of the frame below 0x7c00, half precision's +inf): the same cell with the best
-// key max(m_key, F(r, s), D, I) taken by two v_pk_maximum3_f16 (pk_max3h) instead of three v_pk_max_i16 — one half-rate
-// instruction fewer per row; the keys, flags and traceback cells it forms are those of FR == 1 bit for bit.
+// FR == 2 (where pk16_max3_fits: every key of the frame below 0x7c00, half precision's +inf, and pk16_delta <= 256): the
+// same keys with maxima of three (v_pk_maximum3_f16, pk_max3h) and three things the result does not need left out.
+//  - The floor enters through D: D' = max3(D, S + open, F(r, s)) replaces D's v_pk_max_i16, and the best key is one
+//    max3(m_key, D', I).  A gap extension is free in the frame and F rises by g per step, so a floored D is F(r, s) <=
+//    F(r, s + 1) one step on and never passes the floor it meets there: by induction D'(r, s) = max(D(r, s), F(r, s)), the
+//    candidates of the best key are what they were, and since F's low nibble is 0 so is the key, move code included (on
+//    equal scores D's nibble wins, as before).  What differs from FR == 1 is Dl and the "D opens" bit of the traceback cell
+//    where D < F strictly.  K2 reads that bit only while it walks in state D (the epilogue never does); a path enters D in
+//    a cell where D won the best key, so D >= F there, and every cell further back along the gap holds the same D^
+//    against a smaller F: cells whose bit differs are cells no walk visits in state D.  Records and operations are
+//    those of FR == 1 bit for bit; the traceback words are not.
+//  - The symbols px[] / q sit in the high byte of their halves (shifted once at set-up and once per y_pair load), so
+//    px ^ q is 0 or >= 256 >= DELTA in each half and the match term is pk_subs_u16(DELTA, px ^ q): the v_pk_mad_u16 by
+//    DELTA becomes a full-rate add.
+//  - The row maxima SnB of the two steps of a trip of the unpredicated loop are taken in the second step by one
+//    max3(SnB, best(s - 1) - c(s - 1), best(s) - c(s)); best(s - 1) is still in Sl[r] there.  Trips start on even steps,
+//    so both steps share a 16-step priority block, merge_rows (s % 16 == 15) follows a second step, and the first step's
+//    key carries an odd priority: it is never 0, so the result does not depend on how maximum orders SnB's initial
+//    0x8000 (-0.0 as a half) against key 0 (+0.0).  In unpredicated steps every lane and row, those past m included, holds
+//    keys of the frame: no NaN pattern reaches a maximum.
 template <int R, int LP, int MODE, int XP, int XS, int YP, int YS, bool LF = false, int FR = 0>
 __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     constexpr bool FAST = MODE == 0;
@@ -164,6 +185,12 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     const pk KSUB = fr(((sc.mismatch * 16) | K_SUBST) + 2 * gF);                                // diagonal: both
     const pk KREB = fr(gF * (R - 1));  // row R - 1 of the lane above at step s -> row -1 here at step s + 1
     (void)GF; (void)KGOI; (void)KGOD; (void)KSUB; (void)KREB;
+    // the three savings of the FR == 2 cell (see above); PK16_CELL_KO knocks them out one by one for timing builds
+    // (tools/exp/ko_build.sh sw_fill_pk16_localfast.hip <name> -DPK16_CELL_KO=<bits>; results stay the same)
+    constexpr bool DFLOOR = FR == 2 && !(PK16_CELL_KO & 1);   // the floor enters through D
+    constexpr bool SYMHI = FR == 2 && !(PK16_CELL_KO & 2);    // symbols in the high byte, match term by one saturating subtract
+    constexpr bool ROWMAX2 = FR == 2 && !(PK16_CELL_KO & 4);  // row maxima of a two-step trip by one maximum of three
+    constexpr int SYM_SH = SYMHI ? 8 : 0;
     // the traceback cells are put together with v_pk_mad_u16; the factors are hidden from the compiler, which
     // otherwise rewrites every multiply-add by a power of two into a shift and an add (two instructions for one)
     pk C16 = dup16(16), C32 = dup16(32), C1024 = dup16(1024);
@@ -213,9 +240,10 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
         const bool packed = a.packed != 0;  // wave-uniform (kernel argument)
         // one y symbol of both pairs of the couple (only the two offsets stay live across the steps, as the two byte
         // pointers did)
+        // (SYMHI: in the high byte of each half, as px[])
         auto y_pair = [&](uint32_t col) -> pk {
-            if (packed) return sym2(a.y, ys0 + col) | (sym2(a.y, ys1 + col) << 16);
-            return (uint32_t)a.y[ys0 + col] | ((uint32_t)a.y[ys1 + col] << 16);
+            if (packed) return (sym2(a.y, ys0 + col) | (sym2(a.y, ys1 + col) << 16)) << SYM_SH;
+            return ((uint32_t)a.y[ys0 + col] | ((uint32_t)a.y[ys1 + col] << 16)) << SYM_SH;
         };
         const uint32_t Q0 = pair_ok ? P0 : 0, Q1 = pair_ok ? P1 : 0;
         uint32_t* tb0 = (uint32_t*)a.tb + (size_t)(Q0 / PW) * job_words + ((Q0 % PW) * LP + ll) * 16u;
@@ -281,6 +309,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
             if (pair_ok && i <= m) {
                 px[r] = packed ? (((uint32_t)(xw0 >> (2 * r)) & 3u) | (((uint32_t)(xw1 >> (2 * r)) & 3u) << 16))
                                : ((uint32_t)x0[i - 1] | ((uint32_t)x1[i - 1] << 16));
+                px[r] <<= SYM_SH;
                 const Col0 c = col0_cell(sc, i, m, fold0);
                 Sl[r] = dup16(scl(c.S));
                 Il[r] = dup16(scl(c.I) | K_INS);
@@ -362,8 +391,11 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
         s_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_all);
         auto run_steps = [&](auto mr_tag) {
         constexpr int MRk = decltype(mr_tag)::value;
-        auto step = [&](auto allon_tag, auto fast_tag, const uint32_t s) {
+        auto step = [&](auto allon_tag, auto fast_tag, auto trip_tag, const uint32_t s) {
             constexpr bool ALLON = decltype(allon_tag)::value;
+            // ROWMAX2: 1 / 2 = the first / second step of a two-step trip (s even / odd, both ALLON), 0 = a step on its own
+            constexpr int TRIP = decltype(trip_tag)::value;
+            static_assert(!TRIP || (ALLON && ROWMAX2), "trips are pairs of unpredicated steps of the FR == 2 cell");
             constexpr bool FB = decltype(fast_tag)::value;  // LF: no fold (see above)
             constexpr bool FOLD = XS != CI && !FB;
             if ((s & (LP - 1)) == 0) {  // wave-uniform: next LP columns of y
@@ -430,26 +462,37 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                         const bool maybe_m = MRk < 0 || r == MRk;
                         const bool is_m = MRk < 0 ? (r == mrow) : (r == MRk && mrow == MRk);
                         // mod.rs:733-755: substitution score with the MATCH/SUBST move code in its low bits
-                        const pk e = pk_subs_u16(ONE, px[r] ^ q);  // 1 where the characters agree
+                        // (SYMHI: DELTA where they agree — px[r] ^ q is 0 or >= 256 >= DELTA in each half)
+                        const pk e = pk_subs_u16(SYMHI ? DELTA : ONE, px[r] ^ q);  // 1 where the characters agree
                         // LF: diag >= 0, the sum saturates at key 0 = (score 0, code 0) where the reference's S falls back on
                         // the x-prefix clip; FR: the floor is that key in the frame, F(r, s)
                         const pk Fr = F0 + (uint32_t)r * GF;
                         (void)Fr;
-                        // (FR == 2: the floor enters kb's first maximum of three instead)
-                        const pk m_key = FR == 2 ? pk_mad_u16(e, DELTA, diag) + KSUB
+                        // (FR == 2: the floor enters D's maximum of three instead, or kb's first)
+                        // (SYMHI: two full-rate adds, kept apart: the compiler would make them one half-rate v_add3_u32)
+                        pk dk = diag + KSUB;
+                        if (SYMHI && !(PK16_CELL_KO & 8)) asm("" : "+v"(dk));
+                        const pk m_key = SYMHI   ? e + dk
+                                         : FR == 2 ? pk_mad_u16(e, DELTA, diag) + KSUB
                                          : FR    ? pk_max(pk_mad_u16(e, DELTA, diag) + KSUB, Fr)
                                          : LF    ? pk_subs_u16(pk_mad_u16(e, DELTA, diag), MISC)
                                                  : pk_adds(diag, pk_mad_u16(e, DELTA, MISK));
                         const pk Iv_t = FR ? pk_max(I_up, S_up + KGOI) : pk_max(pk_adds(I_up, GE), pk_adds(S_up, GOT_I));
-                        const pk Dv_t = FR ? pk_max(Dl[r], Sl[r] + KGOD) : pk_max(pk_adds(Dl[r], GE), pk_adds(Sl[r], GOT_D));
+                        // DFLOOR: D carries the floor, max(D, F(r, s)) — off the row-to-row chain — and kb takes one maximum of
+                        // three; why no record or operation changes: see FR == 2 above
+                        const pk Dv_t = DFLOOR ? pk_max3h(Dl[r], Sl[r] + KGOD, Fr)
+                                        : FR   ? pk_max(Dl[r], Sl[r] + KGOD)
+                                               : pk_max(pk_adds(Dl[r], GE), pk_adds(Sl[r], GOT_D));
                         const pk Iv = Iv_t & NOFLAG, Dv = Dv_t & NOFLAG;
                         // mod.rs:757-786: first maximum wins == max over (score | priority)
-                        pk kb = FR == 2 ? pk_max3h(m_key, Fr, Dv_t) : pk_max(m_key, Dv_t);
+                        pk kb = DFLOOR ? m_key : FR == 2 ? pk_max3h(m_key, Fr, Dv_t) : pk_max(m_key, Dv_t);
                         if (XP != CI && !LF) kb = pk_max(kb, XKEY);
-                        kb = FR == 2 ? pk_max3h(kb, Iv_t, Iv_t) : pk_max(kb, Iv_t);  // the value that waits for the row above comes last
+                        // the value that waits for the row above comes last
+                        kb = DFLOOR ? pk_max3h(kb, Dv_t, Iv_t) : FR == 2 ? pk_max3h(kb, Iv_t, Iv_t) : pk_max(kb, Iv_t);
                         if (FOLD && maybe_m)
                             kb = pk_max(kb, is_m ? ((cmk & CLEAN) | (0x00010001u * K_XS)) : FLOORK);
                         const pk best = kb & CLEAN;
+                        const pk best_prev = Sl[r];  // this row's best of the step before
                         diag = Sl[r];
                         Sl[r] = best;
                         Dl[r] = Dv;
@@ -463,7 +506,14 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                         }
                         if (YS != CI) {  // mod.rs:799-802
                             const pk t1 = YS == CZ ? best : pk_min(pk_adds(best, YS16), YSCAP);
-                            SnB[r] = pk_max(SnB[r], FR ? best - (Fr - sprio) : t1 | sprio);  // FR: out of the frame
+                            // ROWMAX2: nothing in the first step of a trip; the second takes both steps' keys with one maximum
+                            // of three (both lie in one 16-step priority block: s - 1 is even, its priority sprio + 1 >= 1, so
+                            // that key is never 0 and the result does not depend on how maximum orders SnB's initial 0x8000,
+                            // -0.0, against key 0, +0.0)
+                            if (TRIP == 2)
+                                SnB[r] = pk_max3h(SnB[r], best_prev - (Fr - GF - sprio - ONE), best - (Fr - sprio));
+                            else if (TRIP == 0)
+                                SnB[r] = pk_max(SnB[r], FR ? best - (Fr - sprio) : t1 | sprio);  // FR: out of the frame
                         }
                         // packed cell: I opens | 3-bit move << 1 | D opens << 4 (flipped to "extends" below)
                         const pk c5 = pk_mad_u16(Dv_t & ONE, C16, (kb & 0x000e000eu) | (Iv_t & ONE));
@@ -540,13 +590,19 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
         constexpr std::false_type no{};
         constexpr std::true_type yes{};
         constexpr std::bool_constant<LF> fast{};
-        for (; s < s_on; s++) step(no, fast, s);
+        constexpr std::integral_constant<int, 0> single{};
+        constexpr std::integral_constant<int, ROWMAX2 ? 1 : 0> first{};
+        constexpr std::integral_constant<int, ROWMAX2 ? 2 : 0> second{};
+        for (; s < s_on; s++) step(no, fast, single, s);
+        // ROWMAX2: trips start on an even step (s_on = LP - 1 is odd: one step on its own first), so that both steps of a
+        // trip share a priority block and merge_rows (s % 16 == 15) comes after a trip's second step
+        if (ROWMAX2 && (s & 1u) && s < s_off) step(yes, fast, single, s++);
         for (; s + 1 < s_off; s += 2) {  // two steps per trip: the row values alternate between two sets of registers
-            step(yes, fast, s);
-            step(yes, fast, s + 1);
+            step(yes, fast, first, s);
+            step(yes, fast, second, s + 1);
         }
-        for (; s < s_off; s++) step(yes, fast, s);
-        for (; s < nsteps_w; s++) step(no, fast, s);
+        for (; s < s_off; s++) step(yes, fast, single, s);
+        for (; s < nsteps_w; s++) step(no, fast, single, s);
         };
         run_steps(std::integral_constant<int, (FAST && !LF) ? R - 1 : -1>{});
         if (nsteps_w % tsteps) store_tile(nsteps_w - 1);  // the last, partial tile

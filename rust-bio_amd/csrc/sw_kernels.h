@@ -75,10 +75,17 @@ inline bool pk16_frame_fits(const SwScoring& sc, uint32_t max_ylen, int r, int l
     const int64_t g = -16ll * sc.ge, nsteps = (int64_t)max_ylen + lp - 1;
     return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x8000;
 }
+// match key - mismatch key of K1p's cells, what a matching symbol adds to the diagonal: 16 (match - mismatch) + 2
+__host__ __device__ inline int32_t pk16_delta(const SwScoring& sc) {
+    return ((sc.match * 16) | (int32_t)(C_MATCH << 1)) - ((sc.mismatch * 16) | (int32_t)(C_SUBST << 1));
+}
 // ... and whether they all stay below 0x7c00, +inf of half precision: then every key is the bit pattern of a non-negative
-// finite half and the cell may take its best key with v_pk_maximum3_f16 (FR == 2)
+// finite half and the cell may take its best key with v_pk_maximum3_f16 (FR == 2).  That cell also forms the match term
+// with one saturating subtract from symbols kept in the high byte of a half (x ^ y is 0 or >= 256), which needs
+// pk16_delta <= 256: match - mismatch <= 15.
 inline bool pk16_max3_fits(const SwScoring& sc, uint32_t max_ylen, int r, int lp) {
     if (sc.ge > 0 || sc.match < 0) return false;
+    if (pk16_delta(sc) < 0 || pk16_delta(sc) > 256) return false;
     const int64_t g = -16ll * sc.ge, nsteps = (int64_t)max_ylen + lp - 1;
     return 16ll * sc.match * max_ylen + pk16_frame_bias(sc) + g * (r + nsteps) + 15 < 0x7c00;
 }
