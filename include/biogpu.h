@@ -1468,6 +1468,70 @@ int bg_bam_index_blocks(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, cons
                         uint64_t n_contigs, uint64_t n_blocks, const uint64_t* block_off, const uint64_t* out_off, uint8_t* out,
                         uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad);
 
+/* ---- pileup: counters per reference position from sorted BAM records (bam_pileup.hip; the bodies in csrc/bam_pileup_rule.h) ----
+ * What lies over each reference position of a batch of regions: one row of counters a position, from a coordinate-sorted run
+ * of BAM records in HBM.  (d_recs, d_off) is the pair bg_bam_index[_dev] takes: bg_bam_emit_batch_dev + bg_sam_sort_dev leave
+ * it, and so does bg_bam_records_dev as (the stream, off).  contigs gives n_ref = n_contigs and the contig lengths.
+ * THE RULE.  The bytes are a function of the inputs alone (integer counts; no float, no order of arrival).
+ *   slots      a slot of length 0 is ignored everywhere.
+ *   checks     on every non-empty slot: those of bg_bam_index as they stand (length, block_size, fields inside the record,
+ *              refID < n_contigs, pos >= -1, end inside the contig, off[i + 1] >= off[i]; end > 2^29 is BG_ERR_UNSUPPORTED:
+ *              lifting that limit belongs with CSI); a slot must not sort before the previous non-empty one by ((uint32)
+ *              refID, pos); where n_cigar_op > 0 and l_seq > 0 the lengths of M, I, S, =, X must sum to l_seq; an operation
+ *              code above 9 is refused (9, htslib's B, is taken and consumes nothing).  All of these: BG_ERR_INVALID_ARG.
+ *              The placeholder of a CG tag — n_cigar_op == 2, the first op <l_seq>S, the second N, refID >= 0 — is
+ *              BG_ERR_UNSUPPORTED: the real CIGAR sits in a tag this call does not read, and counting the placeholder would
+ *              be silently wrong.  On any refusal *first_bad (optional) is the first offending slot, its kind decides the
+ *              status (INVALID before UNSUPPORTED), and nothing is written.
+ *   kept       a record is kept when refID >= 0, pos >= 0, FLAG 0x4 is clear (whatever `exclude` says),
+ *              (flag & require) == require, (flag & exclude) == 0 and mapq >= min_mapq.
+ *   the walk   of a kept record starts with r = pos, q = 0.  M, =, X of length n: position r + k (k < n) receives one count
+ *              — with l_seq == 0 in column OTHER, no quality test; otherwise none if qual[q + k] < min_baseq (unsigned, on
+ *              the raw byte: the absent quality 0xFF always passes), else in the column the 4-bit code of base q + k picks:
+ *              1 A, 2 C, 4 G, 8 T, everything else OTHER —; r += n, q += n.  I: one count in column INS at r - 1 when
+ *              r > pos (the anchor is the reference base in front; an insertion in front of the record's first reference
+ *              base is dropped; every I operation counts one); q += n.  D: DEL at r .. r + n - 1; r += n.  N: SKIP at
+ *              r .. r + n - 1; r += n.  S: q += n.  H, P: nothing.
+ *   columns    without BG_PILEUP_STRANDS a row is BG_PILEUP_COLS = 8 uint32.  With it a row is 16: columns 0 .. 7 hold the
+ *              records with FLAG 0x10 clear, 8 .. 15 those with it set.  Depth is the caller's sum of columns 0 .. 4, plus
+ *              DEL if wanted.
+ *   regions    0-based, half-open, in any order; they may overlap or repeat.  Each must satisfy 0 <= ref < n_contigs and
+ *              0 <= beg <= end <= contigs[ref].len, else BG_ERR_INVALID_ARG with *first_bad = UINT64_MAX (looked at before
+ *              the slots).  row_off[r] = the sum of the lengths of the regions in front of r; position p of region r is row
+ *              row_off[r] + p - beg, W = 8 or 16 adjacent uint32.  Every row of every region is written, zeros included, and
+ *              holds exactly what the region would get in a call of its own; nothing behind row n_rows is touched.
+ *              d_row_off (optional) receives the n_regions + 1 offsets.
+ *   sizing     a null d_rows with rows_cap == 0 sizes the call: *n_rows, every check still made, nothing written (d_row_off
+ *              included).  rows_cap < n_rows: BG_ERR_OPS_CAP with *n_rows set and nothing written.
+ *   limits     BG_ERR_TOO_LARGE: n_slots >= 2^32 - 1, n_regions >= 2^24, n_rows >= 2^32.  BG_ERR_INVALID_ARG also: unknown
+ *              flag bits, reserved != 0, a null ctx, prm or n_rows, a null d_rows with rows_cap > 0, (n_slots > 0) a null
+ *              recs or off, (n_contigs > 0) a null contigs, (n_regions > 0) a null regions.
+ * d_rows is 4-byte aligned (rows go out 16 bytes wide where it is 16-byte aligned, as dwords otherwise); d_recs may sit at any
+ * address.  The errors and the total are read back once, with one stream synchronisation; the rows are then written
+ * asynchronously on `stream`.  Scratch is the ctx's: 33 bytes a slot and 24 a region; nothing grows with contig lengths.
+ * Known costs: a tile (BG_PILEUP_TILE positions of one region) is one workgroup's work however deep the pile over it; a record
+ * of many operations is walked again by every tile it spans (an operation itself is clipped to the tile by arithmetic).
+ * Not covered: counting overlapping mates once, BAQ, reference bases (so no match / mismatch), the CG tag, unsorted input,
+ * per-read pileup iterators. */
+typedef struct { int32_t ref, beg, end; } bg_bam_region_t;           /* 0-based, half-open; 12 bytes */
+enum { BG_PILEUP_STRANDS = 1 };
+enum { BG_PILEUP_A, BG_PILEUP_C, BG_PILEUP_G, BG_PILEUP_T, BG_PILEUP_OTHER, BG_PILEUP_DEL, BG_PILEUP_SKIP, BG_PILEUP_INS,
+       BG_PILEUP_COLS /* 8 */ };
+typedef struct {
+    uint32_t flags;      /* BG_PILEUP_* */
+    uint16_t require;    /* FLAG bits a kept record has */
+    uint16_t exclude;    /* FLAG bits a kept record lacks */
+    uint8_t min_mapq;    /* a kept record has mapq >= this */
+    uint8_t min_baseq;   /* a counted base has a raw quality byte >= this */
+    uint16_t reserved;   /* 0 */
+} bg_bam_pileup_t;
+int bg_bam_pileup_dev(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                      const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions,
+                      uint32_t* d_rows, uint64_t rows_cap, uint64_t* d_row_off, uint64_t* n_rows, uint64_t* first_bad, void* stream);
+int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
+                  const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
+                  uint32_t* rows, uint64_t rows_cap, uint64_t* row_off, uint64_t* n_rows, uint64_t* first_bad);
+
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header
  * take as they are.  Without BG_FASTA_REF_FMD the text is S0 $ S1 $ ... S(k-1) $ and *n_text = sum(len_i + 1).  With it,

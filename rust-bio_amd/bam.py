@@ -1,5 +1,5 @@
 """BAM records, BGZF framing and reading, and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
-`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip) and of the pileup over sorted records (`bg_bam_pileup[_dev]`; rust-bio_amd/csrc/bam_pileup.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
@@ -8,6 +8,7 @@ container holds stored deflate blocks with a CRC-32 each (rust-bio_amd/csrc/bgzf
 of a stream, every block inflated and checked on the device); the index is built from the sorted records and the framing's block table
 (rust-bio_amd/csrc/bam_index.hip).  This module only marshals arguments."""
 import ctypes as C
+import zlib
 
 import numpy as np
 
@@ -484,6 +485,142 @@ def index_bam(data, ctx=None):
     _, contigs, body_off = read_header(stream)
     off = records_arrays(stream, body_off, len(contigs), ctx=ctx)
     return index_blocks_arrays(stream, off, contigs, block_off, out_off, ctx=ctx)
+
+
+# ---- pileup ------------------------------------------------------------------------------------------------------------------
+PILEUP_TILE = _lib.PILEUP_TILE  # BG_PILEUP_TILE: the positions one workgroup counts; results do not depend on it
+PILEUP_STRANDS = _lib.PILEUP_STRANDS
+PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER = _lib.PILEUP_A, _lib.PILEUP_C, _lib.PILEUP_G, _lib.PILEUP_T, _lib.PILEUP_OTHER
+PILEUP_DEL, PILEUP_SKIP, PILEUP_INS, PILEUP_COLS = _lib.PILEUP_DEL, _lib.PILEUP_SKIP, _lib.PILEUP_INS, _lib.PILEUP_COLS
+
+
+class BamPileupError(_lib.BiogpuError):
+    """bg_bam_pileup[_dev] refused the records or the regions: `slot` is the first offending slot (None: no slot is to blame)"""
+
+    def __init__(self, status, where, slot):
+        super().__init__(status, where)
+        self.slot = slot
+
+
+def _pileup_check(rc, where, bad):
+    if rc in (-1, -11):
+        raise BamPileupError(rc, where, _bad(bad))
+    _lib.check(rc, where)
+
+
+def pileup_params(flags=0, require=0, exclude=0x704, min_mapq=0, min_baseq=0):
+    """bg_bam_pileup_t.  The default `exclude` drops secondary alignments, QC failures and duplicates (and unmapped records,
+    which are never kept)."""
+    p = np.zeros(1, dtype=_lib.BAM_PILEUP_DTYPE)
+    p[0] = (flags, require, exclude, min_mapq, min_baseq, 0)
+    return p
+
+
+def pileup_regions(regions):
+    """(ref, beg, end) triples, 0-based and half-open, as bg_bam_region_t[]"""
+    if isinstance(regions, np.ndarray) and regions.dtype == _lib.BAM_REGION_DTYPE:
+        return np.ascontiguousarray(regions)
+    out = np.zeros(len(regions), dtype=_lib.BAM_REGION_DTYPE)
+    for k, (ref, beg, end) in enumerate(regions):
+        out[k] = (ref, beg, end)
+    return out
+
+
+def pileup_arrays(stream, off, contigs, regions, flags=0, require=0, exclude=0x704, min_mapq=0, min_baseq=0, ctx=None):
+    """bg_bam_pileup, host buffers: the counters of every position of `regions` ((ref, beg, end), 0-based, half-open) from the
+    coordinate-sorted records stream[off[i] .. off[i + 1]).  Returns (rows: uint32[n_rows, W], W = 16 under PILEUP_STRANDS and
+    8 otherwise, columns PILEUP_A .. PILEUP_INS; row_off: uint64[n_regions + 1]): position p of region r is
+    rows[row_off[r] + p - beg].  Raises BamPileupError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    table = np.ascontiguousarray(contigs.table)
+    reg = pileup_regions(regions)
+    prm = pileup_params(flags, require, exclude, min_mapq, min_baseq)
+    w = 2 * PILEUP_COLS if flags & PILEUP_STRANDS else PILEUP_COLS
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+
+    def call(rows, cap, row_off):
+        return _lib.lib().bg_bam_pileup(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                        len(table), reg.ctypes.data if len(reg) else None, len(reg), rows, cap, row_off, C.byref(total), C.byref(bad))
+    _pileup_check(call(None, 0, None), "bg_bam_pileup", bad)
+    rows = np.zeros((max(total.value, 1), w), dtype=np.uint32)
+    row_off = np.zeros(len(reg) + 1, dtype=np.uint64)
+    _pileup_check(call(rows.ctypes.data, total.value, row_off.ctypes.data), "bg_bam_pileup", bad)
+    return rows[:total.value], row_off
+
+
+def pileup_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_rows=0, rows_cap=0, d_row_off=0, flags=0, require=0, exclude=0x704,
+               min_mapq=0, min_baseq=0, stream=0, ctx=None):
+    """bg_bam_pileup_dev (pointers are ints; d_rows = 0 with rows_cap = 0 sizes; d_row_off may be 0; rows_cap counts rows).
+    Returns n_rows, read back with one synchronisation of `stream`; the rows are then written asynchronously.  Raises
+    BamPileupError with the offending slot, BiogpuError with status -9 (OPS_CAP) when rows_cap is too small."""
+    ctx = ctx or _lib.default_context()
+    prm = pileup_params(flags, require, exclude, min_mapq, min_baseq)
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_pileup_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_regions or None,
+                                      n_regions, d_rows or None, rows_cap, d_row_off or None, C.byref(total), C.byref(bad), stream)
+    _pileup_check(rc, "bg_bam_pileup_dev", bad)
+    return int(total.value)
+
+
+def resolve_regions(contigs, regions):
+    """regions given as (name or index, beg, end) against a contig table: bg_bam_region_t[].  Raises ValueError naming the
+    region for an unknown name, an index outside the table, or an interval that is not 0 <= beg <= end <= the contig's length."""
+    names = {contigs.name(c): c for c in reversed(range(len(contigs)))}
+    out = np.zeros(len(regions), dtype=_lib.BAM_REGION_DTYPE)
+    for k, region in enumerate(regions):
+        ref, beg, end = region
+        if isinstance(ref, (str, bytes)):
+            c = names.get(ref.encode() if isinstance(ref, str) else bytes(ref))
+            if c is None:
+                raise ValueError(f"region {region!r}: the header names no such reference")
+        else:
+            c = int(ref)
+            if not 0 <= c < len(contigs):
+                raise ValueError(f"region {region!r}: no reference of that index")
+        if not 0 <= beg <= end <= int(contigs.table["len"][c]):
+            raise ValueError(f"region {region!r}: not 0 <= beg <= end <= {int(contigs.table['len'][c])}")
+        out[k] = (c, beg, end)
+    return out
+
+
+def pileup_bam(data, regions, flags=0, require=0, exclude=0x704, min_mapq=0, min_baseq=0, ctx=None):
+    """The pileup of a coordinate-sorted BAM file (bytes): `read_bam`, then `pileup_arrays`, with `regions` given as (name or
+    index, beg, end) and resolved through the file's header (`resolve_regions`: a ValueError names a bad region before the
+    records are touched).  Returns (rows, row_off)."""
+    for region in regions:
+        if not 0 <= region[1] <= region[2]:
+            raise ValueError(f"region {region!r}: not 0 <= beg <= end")
+    src = _lib.as_u8(data)
+
+    def prefix(n):  # the header is a few members: inflated here, so that the regions are judged before any device work
+        out, at = b"", 0
+        while len(out) < n and at + 18 <= len(src):
+            size = int(src[at + 16]) + (int(src[at + 17]) << 8) + 1
+            try:
+                out += zlib.decompress(src[at + 18:at + size - 8].tobytes(), -15)
+            except zlib.error:  # no BGZF member: read_header says so of what there is
+                break
+            at += size
+        return out[:n]
+    _, contigs, _ = read_header(prefix)
+    reg = resolve_regions(contigs, regions)
+    _, contigs, stream, off = read_bam(data, ctx=ctx)
+    return pileup_arrays(stream, off, contigs, reg, flags, require, exclude, min_mapq, min_baseq, ctx=ctx)
+
+
+def depth(rows, deletions=False):
+    """The depth of every position: the sum of the base columns (A, C, G, T, OTHER; both strands where the rows carry them),
+    plus DEL where `deletions`"""
+    rows = np.asarray(rows)
+    cols = list(range(PILEUP_OTHER + 1)) + ([PILEUP_DEL] if deletions else [])
+    total = rows[:, cols].sum(axis=1, dtype=np.uint64)
+    if rows.shape[1] == 2 * PILEUP_COLS:
+        total += rows[:, [PILEUP_COLS + c for c in cols]].sum(axis=1, dtype=np.uint64)
+    return total
 
 
 def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False, index=False):
