@@ -1511,8 +1511,8 @@ int bg_bam_index_blocks(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, cons
  * asynchronously on `stream`.  Scratch is the ctx's: 33 bytes a slot and 24 a region; nothing grows with contig lengths.
  * Known costs: a tile (BG_PILEUP_TILE positions of one region) is one workgroup's work however deep the pile over it; a record
  * of many operations is walked again by every tile it spans (an operation itself is clipped to the tile by arithmetic).
- * Not covered: counting overlapping mates once, BAQ, reference bases (so no match / mismatch), the CG tag, unsorted input,
- * per-read pileup iterators. */
+ * Not covered: counting overlapping mates once, BAQ, reference bases in the rows (bg_bam_sites below holds the counters against
+ * the reference without storing rows), the CG tag, unsorted input, per-read pileup iterators. */
 typedef struct { int32_t ref, beg, end; } bg_bam_region_t;           /* 0-based, half-open; 12 bytes */
 enum { BG_PILEUP_STRANDS = 1 };
 enum { BG_PILEUP_A, BG_PILEUP_C, BG_PILEUP_G, BG_PILEUP_T, BG_PILEUP_OTHER, BG_PILEUP_DEL, BG_PILEUP_SKIP, BG_PILEUP_INS,
@@ -1531,6 +1531,84 @@ int bg_bam_pileup_dev(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots,
 int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
                   const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
                   uint32_t* rows, uint64_t rows_cap, uint64_t* row_off, uint64_t* n_rows, uint64_t* first_bad);
+
+/* ---- candidate variant sites and region summaries: the pileup held against the reference (bam_pileup.hip; the bodies in
+ * csrc/bam_sites_rule.h) ----
+ * The counters of bg_bam_pileup compared with the reference text where they are counted: one compact record for every
+ * candidate variant site and one summary for every region.  No row goes to HBM, so the regions may be whole genomes.
+ * (d_recs, d_off), contigs and regions are those of bg_bam_pileup; (d_text, n_text) is the index text contigs[i].start
+ * addresses: what bg_fasta_reference[_dev] leaves, in the layout bg_bam_header_parse gives the contig table.
+ * THE RULE.  The result is a function of the inputs alone (integer arithmetic; no float, no order of arrival).
+ *   counters   slots, checks, order, kept, the walk and the regions are those of bg_bam_pileup, word for word (the same
+ *              bodies).  The counters of a position are the 16 columns of the BG_PILEUP_STRANDS form, always.
+ *   reference  the reference byte of position p of contig ref is text[contigs[ref].start + p] with a-z folded to A-Z.  A, C,
+ *              G, T name the reference column.  Any other byte (N, IUPAC codes) makes the position unjudged: it yields no
+ *              site and counts into n_ref_other; its depth still counts.  A `$` is never read.  A region whose contig does not
+ *              lie inside [0, n_text) (start + len > n_text) is a region error: BG_ERR_INVALID_ARG with *first_bad =
+ *              UINT64_MAX, judged with the other region checks, before the slots.
+ *   depth      depth(p) = A + C + G + T + OTHER + DEL over both strands.
+ *   candidates of a judged position, in this order: the three non-reference columns among A, C, G, T, ascending
+ *              (BG_SITE_SNV, alt = the ASCII base); DEL (BG_SITE_DEL: one candidate a deleted position, not one a deletion
+ *              event); INS (BG_SITE_INS, anchored at p as the pileup anchors it).  alt_fwd / alt_rev are the candidate's
+ *              column in the two halves of the row, alt = alt_fwd + alt_rev.  A candidate is a site when depth >= min_depth,
+ *              alt >= max(min_alt, 1), (uint64) alt * 1000 >= (uint64) min_alt_permille * depth (equality passes),
+ *              alt_fwd >= min_alt_strand and alt_rev >= min_alt_strand.  A position gives 0 to 5 sites.
+ *   site       bg_bam_site_t, 32 bytes: ref_base is the folded byte, alt 0 for DEL and INS, ref_count the reference column over
+ *              both strands, region the index of the region the site belongs to.
+ *   order      sites come in region order, then by position, then in candidate order.  d_site_off[r] (optional, n_regions + 1
+ *              entries) is the index of region r's first site.  Regions may overlap, repeat and come in any order; a region's
+ *              sites are what it would get in a call of its own.
+ *   summary    bg_bam_region_summary_t, 48 bytes, one a region (d_summary is optional), zeros for an empty region: sum_depth;
+ *              match = the reference column summed over the judged positions, mismatch = the other three base columns over the
+ *              judged positions; covered[k] = the positions with depth >= cover[k] (0 counts every position); max_depth;
+ *              n_ref_other.
+ *   sizing     a null d_sites with sites_cap == 0 sizes the call: *n_sites, every check still made, nothing written (summaries
+ *              and d_site_off included).  sites_cap < n_sites: BG_ERR_OPS_CAP with *n_sites set and nothing written.
+ *   limits     BG_ERR_TOO_LARGE: those of bg_bam_pileup (n_rows counts the regions' positions) and n_sites >= 2^32.
+ *              BG_ERR_INVALID_ARG also: flags != 0, reserved != 0, min_alt_permille > 1000, a null d_text with n_text > 0, the
+ *              null pointers bg_bam_pileup refuses.  Every refusal of bg_bam_pileup is a refusal here, with the same status and
+ *              the same *first_bad, and nothing is written.
+ * d_sites and d_summary are 4-byte aligned (site records go out 16 bytes wide where d_sites is 16-byte aligned, as dwords
+ * otherwise); d_text and d_recs may sit at any address.  The counters are counted twice, once to count the sites of every tile
+ * and once to place them, instead of being parked in HBM.  TWO read-backs with one stream synchronisation each (the errors
+ * and the tiles; the number of sites); the records are then written asynchronously on `stream`.  A tile's share of its
+ * region's summary is parked in scratch and a pass of its own sums a region's tiles (integer sums and maxima: exact, whatever
+ * the order).  Scratch is the ctx's: the pileup's and 12 bytes a tile, 48 more a tile where d_summary is given.
+ * Not covered: genotype likelihoods, deletion events, inserted sequences, overlapping mates, BAQ, the CG tag, VCF text. */
+enum { BG_SITE_SNV = 0, BG_SITE_DEL = 1, BG_SITE_INS = 2 };
+typedef struct {
+    uint32_t flags;             /* 0 */
+    uint16_t require;           /* FLAG bits a kept record has */
+    uint16_t exclude;           /* FLAG bits a kept record lacks */
+    uint8_t min_mapq;           /* a kept record has mapq >= this */
+    uint8_t min_baseq;          /* a counted base has a raw quality byte >= this */
+    uint16_t reserved;          /* 0 */
+    uint32_t min_depth;         /* a site's position has depth >= this */
+    uint32_t min_alt;           /* a site has alt >= max(this, 1) */
+    uint32_t min_alt_permille;  /* ... and alt * 1000 >= this * depth; at most 1000 */
+    uint32_t min_alt_strand;    /* ... and alt_fwd, alt_rev >= this */
+    uint32_t cover[4];          /* covered[k] counts the positions with depth >= cover[k] */
+} bg_bam_sites_t;               /* 44 bytes */
+typedef struct {
+    int32_t ref, pos;           /* 0-based */
+    uint32_t region;
+    uint8_t kind, ref_base, alt, reserved;  /* BG_SITE_*; the folded reference byte; the ASCII base of an SNV, else 0; 0 */
+    uint32_t depth, ref_count, alt_fwd, alt_rev;
+} bg_bam_site_t;                /* 32 bytes */
+typedef struct {
+    uint64_t sum_depth, match, mismatch;
+    uint32_t covered[4];
+    uint32_t max_depth, n_ref_other;
+} bg_bam_region_summary_t;      /* 48 bytes */
+int bg_bam_sites_dev(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                     const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const uint8_t* d_text, uint64_t n_text,
+                     const bg_bam_region_t* d_regions, uint64_t n_regions, bg_bam_site_t* d_sites, uint64_t sites_cap,
+                     uint64_t* d_site_off, bg_bam_region_summary_t* d_summary, uint64_t* n_sites, uint64_t* first_bad,
+                     void* stream);
+int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
+                 const bg_sam_contig_t* contigs, uint64_t n_contigs, const uint8_t* text, uint64_t n_text,
+                 const bg_bam_region_t* regions, uint64_t n_regions, bg_bam_site_t* sites, uint64_t sites_cap,
+                 uint64_t* site_off, bg_bam_region_summary_t* summary, uint64_t* n_sites, uint64_t* first_bad);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

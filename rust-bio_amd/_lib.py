@@ -189,6 +189,17 @@ assert BAM_PILEUP_DTYPE.itemsize == 12, BAM_PILEUP_DTYPE.itemsize
 PILEUP_STRANDS = 1
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_SKIP, PILEUP_INS, PILEUP_COLS = range(9)
 PILEUP_TILE = 512
+# bg_bam_sites_t, bg_bam_site_t, bg_bam_region_summary_t and BG_SITE_* (bg_bam_sites[_dev])
+BAM_SITES_DTYPE = np.dtype([("flags", "<u4"), ("require", "<u2"), ("exclude", "<u2"), ("min_mapq", "u1"), ("min_baseq", "u1"), ("reserved", "<u2"),
+                            ("min_depth", "<u4"), ("min_alt", "<u4"), ("min_alt_permille", "<u4"), ("min_alt_strand", "<u4"), ("cover", "<u4", (4,))])
+assert BAM_SITES_DTYPE.itemsize == 44, BAM_SITES_DTYPE.itemsize
+BAM_SITE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<i4"), ("region", "<u4"), ("kind", "u1"), ("ref_base", "u1"), ("alt", "u1"), ("reserved", "u1"),
+                           ("depth", "<u4"), ("ref_count", "<u4"), ("alt_fwd", "<u4"), ("alt_rev", "<u4")])
+assert BAM_SITE_DTYPE.itemsize == 32, BAM_SITE_DTYPE.itemsize
+BAM_REGION_SUMMARY_DTYPE = np.dtype([("sum_depth", "<u8"), ("match", "<u8"), ("mismatch", "<u8"), ("covered", "<u4", (4,)), ("max_depth", "<u4"),
+                                     ("n_ref_other", "<u4")])
+assert BAM_REGION_SUMMARY_DTYPE.itemsize == 48, BAM_REGION_SUMMARY_DTYPE.itemsize
+SITE_SNV, SITE_DEL, SITE_INS = range(3)
 
 # bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
@@ -245,7 +256,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_bgzf_blocks", "bg_bgzf_blocks_dev", "bg_bgzf_inflate", "bg_bgzf_inflate_dev",
            "bg_bam_header_parse", "bg_bam_records", "bg_bam_records_dev", "bg_bam_reads", "bg_bam_reads_dev",
            "bg_bam_sort_keys", "bg_bam_sort_keys_dev", "bg_bam_index_blocks", "bg_bam_index_blocks_dev",
-           "bg_bam_pileup", "bg_bam_pileup_dev",
+           "bg_bam_pileup", "bg_bam_pileup_dev", "bg_bam_sites", "bg_bam_sites_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -442,6 +453,8 @@ def lib():
         L.bg_bam_index_blocks.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bg_bam_pileup_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_bam_pileup.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_sites_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_sites.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

@@ -1,5 +1,5 @@
 """BAM records, BGZF framing and reading, and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
-`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip) and of the pileup over sorted records (`bg_bam_pileup[_dev]`; rust-bio_amd/csrc/bam_pileup.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip) and of the pileup over sorted records and its candidate variant sites (`bg_bam_pileup[_dev]`, `bg_bam_sites[_dev]`; rust-bio_amd/csrc/bam_pileup.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
@@ -621,6 +621,97 @@ def depth(rows, deletions=False):
     if rows.shape[1] == 2 * PILEUP_COLS:
         total += rows[:, [PILEUP_COLS + c for c in cols]].sum(axis=1, dtype=np.uint64)
     return total
+
+
+# ---- candidate sites and region summaries ------------------------------------------------------------------------------------
+SITE_SNV, SITE_DEL, SITE_INS = _lib.SITE_SNV, _lib.SITE_DEL, _lib.SITE_INS
+
+
+def sites_params(require=0, exclude=0x704, min_mapq=0, min_baseq=0, min_depth=0, min_alt=1, min_alt_permille=0, min_alt_strand=0, cover=(1, 10, 20, 30)):
+    """bg_bam_sites_t: the pileup's filters, the four thresholds a candidate passes to be a site, and the four depths
+    `covered` counts positions at"""
+    p = np.zeros(1, dtype=_lib.BAM_SITES_DTYPE)
+    p[0] = (0, require, exclude, min_mapq, min_baseq, 0, min_depth, min_alt, min_alt_permille, min_alt_strand, tuple(cover))
+    return p
+
+
+def sites_arrays(stream, off, contigs, text, regions, ctx=None, **params):
+    """bg_bam_sites, host buffers: the candidate variant sites and the summaries of `regions` ((ref, beg, end), 0-based, half-open)
+    from the coordinate-sorted records stream[off[i] .. off[i + 1]) held against the index text `text` that contigs.table's
+    `start` addresses.  params: those of `sites_params`.  Returns (sites: BAM_SITE_DTYPE[], in region order, then by position,
+    then SNVs by base, DEL, INS; site_off: uint64[n_regions + 1]; summary: BAM_REGION_SUMMARY_DTYPE[n_regions]).  Raises
+    BamPileupError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    table = np.ascontiguousarray(contigs.table)
+    ref_text = _lib.as_u8(text)
+    reg = pileup_regions(regions)
+    prm = sites_params(**params)
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+
+    def call(sites, cap, site_off, summary):
+        return _lib.lib().bg_bam_sites(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                       len(table), ref_text.ctypes.data if len(ref_text) else None, len(ref_text), reg.ctypes.data if len(reg) else None,
+                                       len(reg), sites, cap, site_off, summary, C.byref(total), C.byref(bad))
+    _pileup_check(call(None, 0, None, None), "bg_bam_sites", bad)
+    sites = np.zeros(max(total.value, 1), dtype=_lib.BAM_SITE_DTYPE)
+    site_off = np.zeros(len(reg) + 1, dtype=np.uint64)
+    summary = np.zeros(max(len(reg), 1), dtype=_lib.BAM_REGION_SUMMARY_DTYPE)
+    _pileup_check(call(sites.ctypes.data, len(sites), site_off.ctypes.data, summary.ctypes.data), "bg_bam_sites", bad)
+    return sites[:total.value], site_off, summary[:len(reg)]
+
+
+def sites_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_text, n_text, d_regions, n_regions, d_sites=0, sites_cap=0, d_site_off=0, d_summary=0,
+              stream=0, ctx=None, **params):
+    """bg_bam_sites_dev (pointers are ints; d_sites = 0 with sites_cap = 0 sizes; d_site_off and d_summary may be 0).  Returns
+    n_sites, read back with the second synchronisation of `stream`; the records are then written asynchronously.  Raises
+    BamPileupError with the offending slot, BiogpuError with status -9 (OPS_CAP) when sites_cap is too small."""
+    ctx = ctx or _lib.default_context()
+    prm = sites_params(**params)
+    total, bad = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_sites_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_text or None, n_text,
+                                     d_regions or None, n_regions, d_sites or None, sites_cap, d_site_off or None, d_summary or None, C.byref(total),
+                                     C.byref(bad), stream)
+    _pileup_check(rc, "bg_bam_sites_dev", bad)
+    return int(total.value)
+
+
+def _reference_text(reference, contigs, ctx):
+    """the index text behind `contigs` (a BAM header's table) from FASTA text (it begins with '>') or from a ready index text
+    (sequences closed by '$' each); ValueError names the first contig whose length is not the header's"""
+    ref = _lib.as_u8(reference)
+    want = [int(v) for v in contigs.table["len"]]
+    if len(ref) and ref[0] == ord(">"):
+        from . import fasta
+        parsed = fasta.parse_arrays(ref, ctx=ctx)
+        if parsed.status != "ok":
+            raise ValueError("the reference is no FASTA text: %s at byte %d" % (parsed.status, parsed.err_pos))
+        text, got = fasta.reference_arrays(parsed)
+        have = [int(v) for v in got.table["len"]]
+    else:
+        text = ref
+        ends = np.nonzero(ref == ord("$"))[0].tolist()
+        have = [e - b for b, e in zip([0] + [e + 1 for e in ends], ends)]
+    for c in range(max(len(want), len(have))):
+        if c >= len(want) or c >= len(have) or want[c] != have[c]:
+            name = contigs.name(c).decode(errors="replace") if c < len(want) else "#%d" % c
+            raise ValueError("contig %r: the header says %s bases, the reference %s" % (name, want[c] if c < len(want) else "nothing of",
+                                                                                        have[c] if c < len(have) else "nothing of"))
+    return text
+
+
+def sites_bam(data, reference, regions, ctx=None, **params):
+    """The candidate sites of a coordinate-sorted BAM file (bytes) against `reference`, FASTA text or a ready index text:
+    `read_bam`, then `sites_arrays`, with `regions` given as (name or index, beg, end) and resolved through the file's header
+    (`resolve_regions`).  The reference's contig lengths must be the header's: a ValueError names the first contig that
+    differs.  Returns (sites, site_off, summary)."""
+    _, contigs, stream, off = read_bam(data, ctx=ctx)
+    reg = resolve_regions(contigs, regions)
+    text = _reference_text(reference, contigs, ctx)
+    return sites_arrays(stream, off, contigs, text, reg, ctx=ctx, **params)
 
 
 def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False, index=False):

@@ -64,6 +64,7 @@ struct plp_tile_t {
     uint32_t ref;
     int64_t t0, t1;  // the window: positions [t0, t1) of ref, at most BG_PILEUP_TILE
     uint64_t row;    // the row of position t0
+    uint32_t region;
 };
 // tile_off / row_off: the exclusive sums of the regions' tile counts and lengths (n_regions + 1 entries each); tile < tile_off[n_regions]
 SAM_HD plp_tile_t plp_tile(uint64_t tile, const bg_bam_region_t* regions, uint64_t n_regions, const uint64_t* tile_off, const uint64_t* row_off) {
@@ -80,6 +81,7 @@ SAM_HD plp_tile_t plp_tile(uint64_t tile, const bg_bam_region_t* regions, uint64
     t.t0 = (int64_t)g.beg + (int64_t)first;
     t.t1 = t.t0 + BG_PILEUP_TILE < g.end ? t.t0 + BG_PILEUP_TILE : g.end;
     t.row = row_off[lo] + first;
+    t.region = (uint32_t)lo;
     return t;
 }
 
