@@ -113,6 +113,8 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *                      text does not depend on it)
  *   fq_emit_mode       bg_fastq_emit_dev's text pass: 1 byte stores straight to the output, 2 lines staged in LDS and stored 16
  *                      bytes wide (0 = default, which is 1; tests, A/B: the text does not depend on it)
+ *   indels_stop_after  bg_bam_indels_dev returns BG_OK with no event after 1 its count pass, 2 its emit pass, 3 its sort (0 = default:
+ *                      it runs through; A/B only: timing tells the passes apart by differences of whole calls)
  *   sa_chunk_symbols   suffixes sorted per pass of round 0 of bg_suffix_array_dev[64] (0 = derived from free device memory;
  *                      tests use small values so that short texts take several passes)
  *   band_budget_gb     traceback + aux bytes per scratch set of the banded pipeline, in GB (0 = default: 40, and never more
@@ -1512,7 +1514,8 @@ int bg_bam_index_blocks(bg_ctx* ctx, uint64_t n_slots, const uint8_t* recs, cons
  * Known costs: a tile (BG_PILEUP_TILE positions of one region) is one workgroup's work however deep the pile over it; a record
  * of many operations is walked again by every tile it spans (an operation itself is clipped to the tile by arithmetic).
  * Not covered: counting overlapping mates once, BAQ, reference bases in the rows (bg_bam_sites below holds the counters against
- * the reference without storing rows), the CG tag, unsorted input, per-read pileup iterators. */
+ * the reference without storing rows; bg_bam_indels names deletions by length and insertions by sequence), the CG tag,
+ * unsorted input, per-read pileup iterators. */
 typedef struct { int32_t ref, beg, end; } bg_bam_region_t;           /* 0-based, half-open; 12 bytes */
 enum { BG_PILEUP_STRANDS = 1 };
 enum { BG_PILEUP_A, BG_PILEUP_C, BG_PILEUP_G, BG_PILEUP_T, BG_PILEUP_OTHER, BG_PILEUP_DEL, BG_PILEUP_SKIP, BG_PILEUP_INS,
@@ -1574,7 +1577,8 @@ int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, con
  * and the tiles; the number of sites); the records are then written asynchronously on `stream`.  A tile's share of its
  * region's summary is parked in scratch and a pass of its own sums a region's tiles (integer sums and maxima: exact, whatever
  * the order).  Scratch is the ctx's: the pileup's and 12 bytes a tile, 48 more a tile where d_summary is given.
- * Not covered: genotype likelihoods, deletion events, inserted sequences, overlapping mates, BAQ, the CG tag, VCF text. */
+ * Not covered: genotype likelihoods, overlapping mates, BAQ, the CG tag, VCF text (deletion events and inserted sequences:
+ * bg_bam_indels below). */
 enum { BG_SITE_SNV = 0, BG_SITE_DEL = 1, BG_SITE_INS = 2 };
 typedef struct {
     uint32_t flags;             /* 0 */
@@ -1609,6 +1613,79 @@ int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const
                  const bg_sam_contig_t* contigs, uint64_t n_contigs, const uint8_t* text, uint64_t n_text,
                  const bg_bam_region_t* regions, uint64_t n_regions, bg_bam_site_t* sites, uint64_t sites_cap,
                  uint64_t* site_off, bg_bam_region_summary_t* summary, uint64_t* n_sites, uint64_t* first_bad);
+
+/* ---- indel events: deletions by length and insertions by sequence, per anchor (bam_pileup.hip; the bodies in
+ * csrc/bam_indels_rule.h) ----
+ * What bg_bam_sites cannot name: one record for every distinct indel event of a batch of regions — a deletion of a given
+ * length, or an insertion of a given sequence, behind a given anchor — with counts per strand and the depth of the anchor,
+ * thresholded as sites are, and the inserted sequences beside the records.  (d_recs, d_off), contigs and regions are those of
+ * bg_bam_pileup; no reference text is needed.  A writer of VCF text is a formatting pass over bg_bam_site_t (SNVs) and these.
+ * THE RULE.  The result is a function of the inputs alone (integer arithmetic; no float, no order of arrival).
+ *   shared     slots, checks, order, kept, regions and every refusal are those of bg_bam_pileup, word for word (the same
+ *              bodies), with the same status and the same *first_bad; nothing is written on a refusal.
+ *   raw events the walk of a kept record is the pileup's: r = pos, q = 0.  An I of length n >= 1 with r > pos is a raw insertion:
+ *              anchor r - 1, length n, sequence the 4-bit codes of bases q .. q + n - 1.  A D of length n >= 1 with r > pos is a
+ *              raw deletion: anchor r - 1, length n.  An operation with r == pos has nothing of the record in front of it and is
+ *              dropped, as the pileup drops such an insertion.  An operation of length 0 gives no event; N, S, H, P and code 9
+ *              give none.  Adjacent operations are not merged (2D 3D is two events) and nothing is shifted (no
+ *              left-alignment).  A record with l_seq == 0 gives its deletions and drops its insertions.  min_baseq never
+ *              removes an event.  A raw event belongs to every region whose [beg, end) holds its anchor.
+ *   events     within a region, raw events with equal (anchor, kind, len and, for insertions, every 4-bit code) are ONE event.
+ *              alt_fwd counts its records with FLAG 0x10 clear, alt_rev those with it set, alt = alt_fwd + alt_rev.  depth is
+ *              bg_bam_sites' depth of the anchor: A + C + G + T + OTHER + DEL over both strands, under the same min_baseq.
+ *   kept       an event is kept under bg_bam_sites' four conditions: depth >= min_depth, alt >= max(min_alt, 1), (uint64) alt *
+ *              1000 >= (uint64) min_alt_permille * depth (equality passes), alt_fwd >= min_alt_strand and alt_rev >=
+ *              min_alt_strand.
+ *   order      events come by region, then anchor, then DEL before INS, then len ascending; insertions of one length then by
+ *              their 4-bit codes as unsigned numbers, left to right.  d_event_off[r] (optional, n_regions + 1 entries) is the
+ *              index of region r's first event.  Regions may overlap, repeat and come in any order; a region's events are what
+ *              it would get in a call of its own.
+ *   sequences  the bytes of d_seq are ASCII through "=ACMGRSVTWYHKDBN".  The sequences of the kept insertions lie in event order
+ *              without gaps: an insertion's len bytes start at d_seq[seq_off]; a deletion carries the running offset and has no
+ *              bytes.  *n_seq is their total.
+ *   sizing     a null d_events with events_cap == 0 sizes the call: *n_events and *n_seq, every check still made, nothing
+ *              written; d_seq must then be null with seq_cap == 0.  events_cap < n_events or seq_cap < n_seq: BG_ERR_OPS_CAP
+ *              with both totals set and nothing written.
+ *   limits     BG_ERR_TOO_LARGE: those of bg_bam_pileup, and raw events, events or sequence bytes >= 2^32.
+ *              BG_ERR_INVALID_ARG also: flags != 0, reserved != 0, min_alt_permille > 1000, a null n_events or n_seq, a null
+ *              d_seq with seq_cap > 0, a sizing call with a d_seq or a seq_cap, the null pointers bg_bam_pileup refuses.
+ * d_events and d_event_off are 8-byte aligned; d_seq and d_recs may sit at any address.  THREE read-backs with one stream
+ * synchronisation each (the errors and the tiles; the raw events; the events and sequence bytes); the records and sequences
+ * are then written asynchronously on `stream`.  A count pass walks the candidates of every tile, an emit pass counts the depth
+ * of the tiles that have raw events (8 columns, 16 KB of LDS) and writes them to scratch, a merge sort orders them by the full
+ * key (the comparator reads the inserted codes from the records: exact at any length, no hashing), heads of runs and prefix
+ * sums of the strand bits give every event's counts without an atomic.  Scratch is the ctx's: the pileup's, 12 bytes a tile and
+ * 88 a raw event plus the sort's own.
+ * Not covered: left-alignment or normalisation against the reference, merging adjacent operations, genotype likelihoods,
+ * overlapping mates, BAQ, the CG tag, VCF text. */
+typedef struct {
+    uint32_t flags;             /* 0 */
+    uint16_t require;           /* FLAG bits a kept record has */
+    uint16_t exclude;           /* FLAG bits a kept record lacks */
+    uint8_t min_mapq;           /* a kept record has mapq >= this */
+    uint8_t min_baseq;          /* enters the depth only, never an event */
+    uint16_t reserved;          /* 0 */
+    uint32_t min_depth;         /* a kept event's anchor has depth >= this */
+    uint32_t min_alt;           /* a kept event has alt >= max(this, 1) */
+    uint32_t min_alt_permille;  /* ... and alt * 1000 >= this * depth; at most 1000 */
+    uint32_t min_alt_strand;    /* ... and alt_fwd, alt_rev >= this */
+} bg_bam_indels_t;              /* 28 bytes */
+typedef struct {
+    int32_t ref, pos;           /* the anchor, 0-based: the reference base in front of the event */
+    uint32_t region;
+    uint8_t kind, reserved[3];  /* BG_SITE_DEL or BG_SITE_INS; 0 */
+    uint32_t len;               /* deleted reference bases / inserted bases, >= 1 */
+    uint32_t depth, alt_fwd, alt_rev;
+    uint64_t seq_off;           /* INS: its len bytes start at d_seq[seq_off]; DEL: the running offset, no bytes */
+} bg_bam_indel_t;               /* 40 bytes */
+int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                      const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions,
+                      bg_bam_indel_t* d_events, uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off,
+                      uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad, void* stream);
+int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
+                  const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
+                  bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq, uint64_t seq_cap, uint64_t* event_off,
+                  uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header

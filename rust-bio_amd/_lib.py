@@ -200,6 +200,13 @@ BAM_REGION_SUMMARY_DTYPE = np.dtype([("sum_depth", "<u8"), ("match", "<u8"), ("m
                                      ("n_ref_other", "<u4")])
 assert BAM_REGION_SUMMARY_DTYPE.itemsize == 48, BAM_REGION_SUMMARY_DTYPE.itemsize
 SITE_SNV, SITE_DEL, SITE_INS = range(3)
+# bg_bam_indels_t and bg_bam_indel_t (bg_bam_indels[_dev])
+BAM_INDELS_DTYPE = np.dtype([("flags", "<u4"), ("require", "<u2"), ("exclude", "<u2"), ("min_mapq", "u1"), ("min_baseq", "u1"), ("reserved", "<u2"),
+                             ("min_depth", "<u4"), ("min_alt", "<u4"), ("min_alt_permille", "<u4"), ("min_alt_strand", "<u4")])
+assert BAM_INDELS_DTYPE.itemsize == 28, BAM_INDELS_DTYPE.itemsize
+BAM_INDEL_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<i4"), ("region", "<u4"), ("kind", "u1"), ("reserved", "u1", (3,)), ("len", "<u4"), ("depth", "<u4"),
+                            ("alt_fwd", "<u4"), ("alt_rev", "<u4"), ("seq_off", "<u8")])
+assert BAM_INDEL_DTYPE.itemsize == 40, BAM_INDEL_DTYPE.itemsize
 
 # bg_myers_pattern_t, BG_MYERS_* and BG_TRIM_* (bg_myers_*_batch[_dev], bg_fastq_trim[_dev])
 MYERS_PATTERN_DTYPE = np.dtype([("peq", "<u8", (256,)), ("m", "<u4"), ("_reserved", "<u4")])
@@ -256,7 +263,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_bgzf_blocks", "bg_bgzf_blocks_dev", "bg_bgzf_inflate", "bg_bgzf_inflate_dev",
            "bg_bam_header_parse", "bg_bam_records", "bg_bam_records_dev", "bg_bam_reads", "bg_bam_reads_dev",
            "bg_bam_sort_keys", "bg_bam_sort_keys_dev", "bg_bam_index_blocks", "bg_bam_index_blocks_dev",
-           "bg_bam_pileup", "bg_bam_pileup_dev", "bg_bam_sites", "bg_bam_sites_dev",
+           "bg_bam_pileup", "bg_bam_pileup_dev", "bg_bam_sites", "bg_bam_sites_dev", "bg_bam_indels", "bg_bam_indels_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
            "bg_fm_backward_search_count_lines_dev", "bg_align_batch_packed_dev", "bg_fm_step2_bytes",
@@ -455,6 +462,8 @@ def lib():
         L.bg_bam_pileup.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
         L.bg_bam_sites_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_bam_sites.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_indels_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_indels.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.bg_pack2_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.bg_unpack2_dev.argtypes = [vp, vp, u64, vp, vp, vp]
         L.bg_fm_pattern_codes.argtypes = [vp, vp]

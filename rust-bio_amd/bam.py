@@ -714,6 +714,80 @@ def sites_bam(data, reference, regions, ctx=None, **params):
     return sites_arrays(stream, off, contigs, text, reg, ctx=ctx, **params)
 
 
+# ---- indel events ------------------------------------------------------------------------------------------------------------
+INDEL_DTYPE = _lib.BAM_INDEL_DTYPE
+SEQ_CODES = b"=ACMGRSVTWYHKDBN"  # the ASCII byte of a 4-bit base code
+
+
+def indels_params(require=0, exclude=0x704, min_mapq=0, min_baseq=0, min_depth=0, min_alt=1, min_alt_permille=0, min_alt_strand=0):
+    """bg_bam_indels_t: the pileup's filters (min_baseq enters the depth only) and the four thresholds a kept event passes"""
+    p = np.zeros(1, dtype=_lib.BAM_INDELS_DTYPE)
+    p[0] = (0, require, exclude, min_mapq, min_baseq, 0, min_depth, min_alt, min_alt_permille, min_alt_strand)
+    return p
+
+
+def indels_arrays(stream, off, contigs, regions, ctx=None, **params):
+    """bg_bam_indels, host buffers: the indel events of `regions` ((ref, beg, end), 0-based, half-open) from the coordinate-sorted
+    records stream[off[i] .. off[i + 1]).  params: those of `indels_params`.  Returns (events: INDEL_DTYPE[], in region order,
+    then by anchor, deletions before insertions, then by length, insertions of one length by their codes; seq: uint8[], the
+    inserted bases as ASCII, an insertion's at seq[seq_off : seq_off + len]; event_off: uint64[n_regions + 1]).  Raises
+    BamPileupError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    table = np.ascontiguousarray(contigs.table)
+    reg = pileup_regions(regions)
+    prm = indels_params(**params)
+    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(events, cap, seq, seq_cap, event_off):
+        return _lib.lib().bg_bam_indels(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                        len(table), reg.ctypes.data if len(reg) else None, len(reg), events, cap, seq, seq_cap, event_off, C.byref(total),
+                                        C.byref(n_seq), C.byref(bad))
+    _pileup_check(call(None, 0, None, 0, None), "bg_bam_indels", bad)
+    events = np.zeros(max(total.value, 1), dtype=INDEL_DTYPE)
+    seq = np.zeros(max(n_seq.value, 1), dtype=np.uint8)
+    event_off = np.zeros(len(reg) + 1, dtype=np.uint64)
+    _pileup_check(call(events.ctypes.data, len(events), seq.ctypes.data, len(seq), event_off.ctypes.data), "bg_bam_indels", bad)
+    return events[:total.value], seq[:n_seq.value], event_off
+
+
+def indels_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events=0, events_cap=0, d_seq=0, seq_cap=0, d_event_off=0, stream=0,
+               ctx=None, **params):
+    """bg_bam_indels_dev (pointers are ints; d_events = 0 with events_cap = 0 sizes, d_seq must then be 0 too; d_event_off may be
+    0).  Returns (n_events, n_seq), read back with the third synchronisation of `stream`; the records and sequences are then
+    written asynchronously.  Raises BamPileupError with the offending slot, BiogpuError with status -9 (OPS_CAP) when a
+    capacity is too small (`totals` then holds both totals)."""
+    ctx = ctx or _lib.default_context()
+    prm = indels_params(**params)
+    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_indels_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_regions or None,
+                                      n_regions, d_events or None, events_cap, d_seq or None, seq_cap, d_event_off or None, C.byref(total),
+                                      C.byref(n_seq), C.byref(bad), stream)
+    try:
+        _pileup_check(rc, "bg_bam_indels_dev", bad)
+    except _lib.BiogpuError as e:
+        e.totals = (int(total.value), int(n_seq.value))
+        raise
+    return int(total.value), int(n_seq.value)
+
+
+def indels_bam(data, regions, ctx=None, **params):
+    """The indel events of a coordinate-sorted BAM file (bytes): `read_bam`, then `indels_arrays`, with `regions` given as (name
+    or index, beg, end) and resolved through the file's header (`resolve_regions`).  Returns (events, seq, event_off)."""
+    _, contigs, stream, off = read_bam(data, ctx=ctx)
+    reg = resolve_regions(contigs, regions)
+    return indels_arrays(stream, off, contigs, reg, ctx=ctx, **params)
+
+
+def indel_sequences(events, seq):
+    """the inserted strings of `events` (bytes each; b"" for a deletion)"""
+    raw = _lib.as_u8(seq).tobytes()
+    return [raw[int(e["seq_off"]):int(e["seq_off"]) + int(e["len"])] if int(e["kind"]) == SITE_INS else b"" for e in events]
+
+
 def sorted_bam(fm, params, contigs, parsed, hits, strand, ops, multi=None, pairs=None, markdup=None, ctx=None, compress=False, index=False):
     """The chain on host buffers, as `sam.sorted_sam`: duplicate flags (markdup: a MarkdupParams, or None), BAM records that
     carry them, a key per record, the records in coordinate order.  Returns the complete file as bytes: the header

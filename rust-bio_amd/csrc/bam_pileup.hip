@@ -21,13 +21,20 @@
 // counts, an emit pass over the tiles that have sites.  A tile's share of its region's summary is parked in scratch, 48 bytes a
 // tile, and a pass of its own sums a region's tiles (global atomics into one summary were measured first: 58 594 tiles of one
 // region queue on one cache line for 1.7 ms).
+// bg_bam_indels[_dev] (the bodies in bam_indels_rule.h) shares steps 1 to 3 and plp_count_tile as well and keeps what the walk
+// reads and drops, an operation's length and the inserted bases: a count pass and an emit pass over the tiles leave the raw
+// events in scratch, a merge sort orders them by the full key, heads of runs and prefix sums of the strand bits make them events
+// (the steps are listed at the entry point).
 #include <algorithm>
 
+#include <rocprim/device/device_merge_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 #include "bg_common.h"
 #include "bam_pileup_rule.h"
 #include "bam_sites_rule.h"
+#include "bam_indels_rule.h"
 
 static_assert(sizeof(bg_bam_region_t) == 12 && sizeof(bg_bam_pileup_t) == 12, "the boundary's structs");
 static_assert(2 * BG_PILEUP_COLS * BG_PILEUP_TILE * 4 * 2 <= 160 * 1024, "two workgroups of the 16-column form must fit a CU's LDS");
@@ -257,6 +264,139 @@ __global__ __launch_bounds__(256) void sit_region_off_kernel(uint64_t n_regions,
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (r > n_regions) return;
     site_off[r] = tiles ? tile_site_off[tile_off[r]] : 0;
+}
+
+// ---- indel events -----------------------------------------------------------------------------------------------------------
+struct IndWork {
+    uint32_t* tile_raw;             // [tiles]: the count pass writes it
+    const uint64_t* tile_raw_off;   // [tiles + 1] scanned
+    ind_raw_t* raw;                 // [n_raw]: the emit pass fills a tile's range, in any order inside it
+    uint32_t* order;                // [n_raw]: the raw events by the full key
+    uint32_t* head;                 // [n_raw]: 1 where a run of equal raw events begins (sorted order)
+    uint32_t* rev;                  // [n_raw]: the strand bit (sorted order)
+    uint64_t* head_off;             // [n_raw + 1] scanned: head_off[i] of a head is its run's number; head_off[n_raw] the runs
+    uint64_t* rev_off;              // [n_raw + 1] scanned
+    uint32_t* run_start;            // [n_raw + 1]: the sorted index a run begins at; n_raw behind the last run
+    uint32_t* keep;                 // [n_raw]: by run, 1 for a kept event (0 behind the last run)
+    uint32_t* seq_len;              // [n_raw]: by run, the bytes of a kept insertion
+    uint64_t* keep_off;             // [n_raw + 1] scanned
+    uint64_t* seq_off;              // [n_raw + 1] scanned
+};
+struct IndOrder {  // the comparator of the merge sort: indices into raw
+    const ind_raw_t* raw;
+    const uint8_t* recs;
+    const uint64_t* off;
+    __device__ bool operator()(uint32_t a, uint32_t b) const { return ind_cmp(raw[a], raw[b], recs, off) < 0; }
+};
+
+// One workgroup per tile, one thread per candidate record.  The count pass (EMIT false) leaves the tile's number of raw events.
+// The emit pass runs in the tiles that have some: the 8-column counters of the tile for the depth of the anchors, then the same
+// walk again; a raw event takes the next place of the tile's range of scratch from a counter in LDS, so the order inside the
+// range is that of arrival and everything behind this pass is independent of it.
+template <bool EMIT>
+__global__ __launch_bounds__(kThreads) void ind_tile_kernel(const PlpArgs a, const PlpWork w, const IndWork x) {
+    __shared__ uint32_t cnt[EMIT ? BG_PILEUP_COLS * BG_PILEUP_TILE : 1];
+    __shared__ uint64_t range[2];
+    __shared__ uint32_t wave_sum[kWaves];
+    __shared__ uint32_t next;
+    uint64_t first = 0;
+    uint32_t room = 0;
+    if (EMIT) {
+        first = x.tile_raw_off[blockIdx.x];
+        room = (uint32_t)(x.tile_raw_off[blockIdx.x + 1] - first);
+        if (!room) return;  // (uniform)
+    }
+    const plp_tile_t t = plp_tile(blockIdx.x, a.regions, a.n_regions, w.tile_off, w.row_off);
+    if (EMIT) {
+        plp_count_tile<BG_PILEUP_COLS>(cnt, range, a, w, t);
+        if (threadIdx.x == 0) next = 0;
+    } else {
+        if (threadIdx.x == 0) range[0] = plp_lo(w.end_max, a.n, t);
+        if (threadIdx.x == 64) range[1] = plp_hi(w.pos_max, a.n, t);
+    }
+    __syncthreads();
+    const uint64_t lo = range[0], hi = range[1];
+    uint32_t mine = 0;
+    for (uint64_t s = lo + threadIdx.x; s < hi; s += kThreads) {
+        if (!w.kept[s]) continue;
+        const uint8_t* rec = a.recs + a.off[s];
+        const uint32_t flag = bai_get16(rec + 18);
+        ind_walk(rec, t.ref, t.t0, t.t1, [&](uint32_t kind, uint32_t anchor, uint32_t len, uint32_t q) {
+            if (EMIT) {
+                const uint32_t place = atomicAdd(&next, 1u);
+                if (place < room) x.raw[first + place] = ind_raw(blockIdx.x, kind, anchor, len, q, flag, ind_depth(cnt, anchor - (uint32_t)t.t0), s);
+            } else {
+                mine++;
+            }
+        });
+    }
+    if (EMIT) return;
+    for (int d = 32; d; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if (threadIdx.x % 64 == 0) wave_sum[threadIdx.x / 64] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t k = 0; k < kWaves; k++) all += wave_sum[k];
+        x.tile_raw[blockIdx.x] = all;
+    }
+}
+
+// sorted index i: does a run begin here, and the strand bit
+__global__ __launch_bounds__(256) void ind_head_kernel(uint64_t n_raw, const PlpArgs a, const IndWork x) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_raw) return;
+    const ind_raw_t e = x.raw[x.order[i]];
+    x.head[i] = i == 0 || ind_cmp(x.raw[x.order[i - 1]], e, a.recs, a.off) != 0;
+    x.rev[i] = ind_rev(e);
+}
+// a head's sorted index at its run's number; n_raw behind the last run
+__global__ __launch_bounds__(256) void ind_run_kernel(uint64_t n_raw, const IndWork x) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n_raw) return;
+    if (i == n_raw) x.run_start[x.head_off[n_raw]] = (uint32_t)n_raw;
+    else if (x.head[i]) x.run_start[x.head_off[i]] = (uint32_t)i;
+}
+// run k: its counts as differences, the verdict, the bytes it adds to the sequences
+__global__ __launch_bounds__(256) void ind_judge_kernel(uint64_t n_raw, const bg_bam_indels_t prm, const IndWork x) {
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_raw) return;
+    uint32_t keep = 0, bytes = 0;
+    if (k < x.head_off[n_raw]) {
+        const uint32_t s = x.run_start[k], e = x.run_start[k + 1];
+        const uint32_t rev = (uint32_t)(x.rev_off[e] - x.rev_off[s]);
+        const ind_raw_t v = x.raw[x.order[s]];
+        keep = ind_is_kept(e - s - rev, rev, v.depth, prm);
+        bytes = keep && ind_kind(v) == BG_SITE_INS ? v.len : 0;
+    }
+    x.keep[k] = keep;
+    x.seq_len[k] = bytes;
+}
+// PLP_G lanes a run: a kept event's record, and the bytes of a kept insertion
+__global__ __launch_bounds__(256) void ind_place_kernel(uint64_t n_raw, const PlpArgs a, const PlpWork w, const IndWork x, bg_bam_indel_t* __restrict__ events,
+                                                        uint8_t* __restrict__ seq) {
+    const uint64_t k = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / PLP_G;
+    const uint32_t lane = threadIdx.x % PLP_G;
+    if (k >= n_raw || !x.keep[k]) return;
+    const uint32_t s = x.run_start[k], e = x.run_start[k + 1];
+    const uint32_t rev = (uint32_t)(x.rev_off[e] - x.rev_off[s]);
+    const ind_raw_t v = x.raw[x.order[s]];
+    if (lane == 0) {
+        const plp_tile_t t = plp_tile(v.tile, a.regions, a.n_regions, w.tile_off, w.row_off);
+        ind_store(ind_event(v, t.ref, t.region, e - s - rev, rev, x.seq_off[k]), events + x.keep_off[k]);
+    }
+    if (ind_kind(v) == BG_SITE_INS) ind_seq_lane(v, a.recs, a.off, seq + x.seq_off[k], lane, PLP_G);
+}
+// event_off[r] = the events in front of region r's first tile: that tile's first raw event in sorted order is a head
+__global__ __launch_bounds__(256) void ind_region_off_kernel(uint64_t n_regions, const uint64_t* __restrict__ tile_off, uint64_t tiles, uint64_t n_raw,
+                                                             const IndWork x, uint64_t* __restrict__ event_off) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r > n_regions) return;
+    uint64_t v = 0;
+    if (tiles && n_raw) {
+        const uint64_t i = x.tile_raw_off[tile_off[r]];
+        v = x.keep_off[i < n_raw ? x.head_off[i] : x.head_off[n_raw]];
+    }
+    event_off[r] = v;
 }
 
 struct Carve {  // pieces of one scratch allocation, each 256-byte aligned
@@ -515,6 +655,165 @@ extern "C" int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_s
         s.down(sites, d_sites, *n_sites);
         if (site_off) s.down(site_off, d_site_off, n_regions + 1);
         if (summary) s.down(summary, d_summary, n_regions);
+    }
+    return s.sync();
+}
+
+namespace {
+
+int ind_check(const bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const void* recs, const void* off, const void* contigs, uint64_t n_contigs,
+              const void* regions, uint64_t n_regions, const void* events, uint64_t events_cap, const void* seq, uint64_t seq_cap, uint64_t* n_events,
+              uint64_t* n_seq, uint64_t* first_bad) {
+    if (first_bad) *first_bad = UINT64_MAX;
+    if (!ctx || !prm || !n_events || !n_seq || (!events && events_cap) || (!seq && seq_cap) || (!events && seq) || (n_slots && (!recs || !off)) ||
+        (n_contigs && !contigs) || (n_regions && !regions))
+        return BG_ERR_INVALID_ARG;
+    *n_events = 0;
+    *n_seq = 0;
+    if (prm->flags || prm->reserved) return bg_refuse("bg_bam_indels: flags or reserved is not 0");
+    if (prm->min_alt_permille > 1000) return bg_refuse("bg_bam_indels: min_alt_permille is above 1000");
+    if (n_slots >= 0xFFFFFFFFull || n_regions >= (1ull << 24) || n_contigs > BAM_MAX_REF) return BG_ERR_TOO_LARGE;
+    return BG_OK;
+}
+
+}  // namespace
+
+// bg_bam_indels_dev: the front (steps 1 to 3 of the pileup), then
+//   4. the count pass, one workgroup per tile: the raw events anchored in the tile; a scan places the tiles; the SECOND
+//      read-back gives the raw events;
+//   5. the emit pass over the tiles that have raw events: the depth counters, the raw events into the tile's range of scratch;
+//   6. a merge sort of their indices by the full key; heads of runs and strand bits, two scans; a run's start by its number;
+//   7. a run's counts as differences of the scans, the verdict, the bytes of a kept insertion; two scans; the THIRD read-back
+//      gives n_events and n_seq, and the sizing call ends here;
+//   8. the records, the sequences and the regions' offsets out.
+// Scratch: the front's lies in ctx->aux and must survive; 12 bytes a tile in ctx->tb; 88 bytes a raw event and the sort's own
+// in ctx->bnd.
+extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                                 const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions,
+                                 bg_bam_indel_t* d_events, uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events,
+                                 uint64_t* n_seq, uint64_t* first_bad, void* stream) {
+    int rc = ind_check(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, events_cap, d_seq, seq_cap, n_events, n_seq,
+                       first_bad);
+    if (rc) return rc;
+    if (((uintptr_t)d_events | (uintptr_t)d_event_off) & 7u) return bg_refuse("bg_bam_indels_dev: d_events or d_event_off is not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    BG_HIP(hipSetDevice(ctx->device));
+    bg_scratch_guard guard(ctx, st);
+    const uint64_t nr = n_regions;
+    const PlpArgs a = {n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, nr, ind_pileup_params(*prm), false, 0};
+    PlpFront f;
+    if ((rc = plp_front(ctx, st, a, &f, first_bad))) return rc;
+    const uint64_t tiles = f.tiles;
+    const bool sizing = !d_events;
+    IndWork x = {};
+    uint64_t n_raw = 0;
+    if (tiles && n_slots) {
+        Carve cv;
+        const size_t o_count = cv.take(tiles * 4), o_roff = cv.take((tiles + 1) * 8), o_sums = cv.take(2 * (tiles / 2048 + 2) * 8);
+        if ((rc = bg_reserve(&ctx->tb, &ctx->tb_bytes, cv.at))) return rc;
+        uint8_t* s = (uint8_t*)ctx->tb;
+        x.tile_raw = (uint32_t*)(s + o_count);
+        x.tile_raw_off = (uint64_t*)(s + o_roff);
+        // 4. the count pass
+        ind_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
+        BG_HIP(hipGetLastError());
+        if ((rc = bg_scan_u32(x.tile_raw, tiles, (uint64_t*)(s + o_roff), (uint64_t*)(s + o_sums), st))) return rc;
+        BG_HIP(hipMemcpyAsync(&n_raw, x.tile_raw_off + tiles, 8, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipStreamSynchronize(st));
+    }
+    if (n_raw >= (1ull << 32)) return BG_ERR_TOO_LARGE;
+    uint64_t totals[2] = {0, 0};
+    const int stop = ctx->indels_stop_after;  // (A/B: the passes told apart by whole calls)
+    if (stop == 1) return BG_OK;
+    if (n_raw) {
+        const uint64_t n = n_raw;
+        const rocprim::counting_iterator<uint32_t> iota(0);
+        size_t t_sort = 0;
+        BG_HIP(rocprim::merge_sort(nullptr, t_sort, iota, (uint32_t*)nullptr, n, IndOrder{nullptr, nullptr, nullptr}, st));
+        Carve cv;
+        const size_t o_raw = cv.take(n * sizeof(ind_raw_t)), o_order = cv.take(n * 4), o_head = cv.take(n * 4), o_rev = cv.take(n * 4),
+                     o_hoff = cv.take((n + 1) * 8), o_voff = cv.take((n + 1) * 8), o_run = cv.take((n + 1) * 4), o_keep = cv.take(n * 4), o_len = cv.take(n * 4),
+                     o_koff = cv.take((n + 1) * 8), o_soff = cv.take((n + 1) * 8), o_tot = cv.take(16), o_sums = cv.take(2 * (n / 2048 + 2) * 8),
+                     o_tmp = cv.take(t_sort);
+        if ((rc = bg_reserve(&ctx->bnd, &ctx->bnd_bytes, cv.at))) return rc;
+        uint8_t* s = (uint8_t*)ctx->bnd;
+        x.raw = (ind_raw_t*)(s + o_raw);
+        x.order = (uint32_t*)(s + o_order);
+        x.head = (uint32_t*)(s + o_head);
+        x.rev = (uint32_t*)(s + o_rev);
+        x.head_off = (uint64_t*)(s + o_hoff);
+        x.rev_off = (uint64_t*)(s + o_voff);
+        x.run_start = (uint32_t*)(s + o_run);
+        x.keep = (uint32_t*)(s + o_keep);
+        x.seq_len = (uint32_t*)(s + o_len);
+        x.keep_off = (uint64_t*)(s + o_koff);
+        x.seq_off = (uint64_t*)(s + o_soff);
+        uint64_t* d_tot = (uint64_t*)(s + o_tot);
+        uint64_t* d_sums = (uint64_t*)(s + o_sums);
+        // 5. the emit pass
+        ind_tile_kernel<true><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
+        BG_HIP(hipGetLastError());
+        if (stop == 2) return BG_OK;
+        // 6. the order, the runs
+        size_t t = t_sort;
+        BG_HIP(rocprim::merge_sort(s + o_tmp, t, iota, x.order, n, IndOrder{x.raw, d_recs, d_off}, st));
+        if (stop == 3) return BG_OK;
+        ind_head_kernel<<<lanes(n), dim3(256), 0, st>>>(n, a, x);
+        BG_HIP(hipGetLastError());
+        if ((rc = bg_scan_u32(x.head, n, x.head_off, d_sums, st))) return rc;
+        if ((rc = bg_scan_u32(x.rev, n, x.rev_off, d_sums, st))) return rc;
+        ind_run_kernel<<<lanes(n + 1), dim3(256), 0, st>>>(n, x);
+        // 7. the events
+        ind_judge_kernel<<<lanes(n), dim3(256), 0, st>>>(n, *prm, x);
+        BG_HIP(hipGetLastError());
+        if ((rc = bg_scan_u32(x.keep, n, x.keep_off, d_sums, st))) return rc;
+        if ((rc = bg_scan_u32(x.seq_len, n, x.seq_off, d_sums, st))) return rc;
+        BG_HIP(hipMemcpyAsync(d_tot, x.keep_off + n, 8, hipMemcpyDeviceToDevice, st));
+        BG_HIP(hipMemcpyAsync(d_tot + 1, x.seq_off + n, 8, hipMemcpyDeviceToDevice, st));
+        BG_HIP(hipMemcpyAsync(totals, d_tot, 16, hipMemcpyDeviceToHost, st));
+        BG_HIP(hipStreamSynchronize(st));
+    }
+    if (totals[0] >= (1ull << 32) || totals[1] >= (1ull << 32)) return BG_ERR_TOO_LARGE;
+    *n_events = totals[0];
+    *n_seq = totals[1];
+    if (sizing) return BG_OK;
+    if (totals[0] > events_cap || totals[1] > seq_cap) return BG_ERR_OPS_CAP;
+    // 8. out
+    if (d_event_off) {
+        ind_region_off_kernel<<<lanes(nr + 1), dim3(256), 0, st>>>(nr, f.w.tile_off, tiles, n_raw, x, d_event_off);
+        BG_HIP(hipGetLastError());
+    }
+    if (totals[0]) {
+        ind_place_kernel<<<lanes(n_raw * PLP_G), dim3(256), 0, st>>>(n_raw, a, f.w, x, d_events, d_seq);
+        BG_HIP(hipGetLastError());
+    }
+    return BG_OK;
+}
+
+extern "C" int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
+                             uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions, bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq,
+                             uint64_t seq_cap, uint64_t* event_off, uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad) {
+    int rc = ind_check(ctx, prm, n_slots, recs, off, contigs, n_contigs, regions, n_regions, events, events_cap, seq, seq_cap, n_events, n_seq, first_bad);
+    if (rc) return rc;
+    // what no call on these records exceeds: an event takes four bytes of a record in every region, a sequence byte half a byte
+    const uint64_t bytes = n_slots ? off[n_slots] : 0;
+    const uint64_t cap = events ? std::min(events_cap, n_regions * (bytes / 4)) : 0, cap_seq = seq ? std::min(seq_cap, n_regions * bytes * 2) : 0;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_recs = s.up(recs, bytes);
+    const uint64_t* d_off = s.up(off, n_slots ? n_slots + 1 : 0);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const bg_bam_region_t* d_regions = s.up(regions, n_regions);
+    bg_bam_indel_t* d_events = events ? s.out<bg_bam_indel_t>(cap) : nullptr;
+    uint8_t* d_seq = seq ? s.out<uint8_t>(cap_seq) : nullptr;
+    uint64_t* d_event_off = events && event_off ? s.out<uint64_t>(n_regions + 1) : nullptr;
+    if (s.rc) return s.rc;
+    if ((rc = bg_bam_indels_dev(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, cap, d_seq, cap_seq, d_event_off,
+                                n_events, n_seq, first_bad, s.st)))
+        return rc;
+    if (events) {
+        s.down(events, d_events, *n_events);
+        if (seq) s.down(seq, d_seq, *n_seq);
+        if (event_off) s.down(event_off, d_event_off, n_regions + 1);
     }
     return s.sync();
 }

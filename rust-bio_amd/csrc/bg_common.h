@@ -88,6 +88,7 @@ struct bg_ctx {
     int band_chain_global = -1;  // chain_kernel tree placement: -1 by batch size, 0 LDS, 1 global scratch
     bool fq_no_fused = false;  // tests, A/B: bg_fastq_parse_dev through F1 .. F6 only (no one-pass kernel in front)
     int sam_lanes = 0;  // lanes per line of bg_sam_emit_batch_dev's write pass: 16 or 32 (0: the default, 16; A/B, tests)
+    int indels_stop_after = 0;  // A/B: bg_bam_indels_dev returns with no event after 1 the count pass, 2 the emit pass, 3 the sort (0: runs through)
     int fq_emit_mode = 0;  // text pass of bg_fastq_emit_dev: 1 byte stores, 2 lines staged in LDS and stored 16 bytes wide (0: the default, 1; A/B, tests)
     int64_t sa_chunk_symbols = 0;  // tests: suffixes per pass of round 0 of the device suffix-array builder (0: by free memory)
     bool band_chain_rows = true;  // global-tree chaining: four pairs per wavefront (chain_rows_kernel); false: one (A/B, tests)

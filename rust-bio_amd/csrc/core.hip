@@ -214,6 +214,11 @@ extern "C" int bg_set_option(bg_ctx* ctx, const char* key, int64_t value) {
         ctx->fq_no_fused = value != 0;
         return BG_OK;
     }
+    if (!strcmp(key, "indels_stop_after")) {
+        if (value < 0 || value > 3) return BG_ERR_INVALID_ARG;
+        ctx->indels_stop_after = (int)value;
+        return BG_OK;
+    }
     if (!strcmp(key, "fq_emit_mode")) {
         if (value < 0 || value > 2) return BG_ERR_INVALID_ARG;
         ctx->fq_emit_mode = (int)value;
