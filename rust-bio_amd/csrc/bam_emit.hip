@@ -300,13 +300,16 @@ extern "C" int bg_bam_emit_batch_dev(bg_fm* fm, const bg_sam_params_t* sp, uint6
     }
     bg_scratch_guard guard(ctx, st);
     const uint64_t n_slots = n_reads * sp->max_hits;
-    const size_t len_bytes = (n_slots * 4 + 15) & ~(size_t)15, desc_bytes = n_slots * sizeof(BamDesc);
-    const size_t sums_bytes = 2 * (n_slots / 2048 + 1) * 8;
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, len_bytes + desc_bytes + sums_bytes + 16))) return rc;
-    uint32_t* d_len = (uint32_t*)ctx->aux;
-    BamDesc* d_desc = (BamDesc*)((uint8_t*)ctx->aux + len_bytes);
-    uint64_t* d_sums = (uint64_t*)((uint8_t*)ctx->aux + len_bytes + desc_bytes);
-    unsigned long long* d_tail = (unsigned long long*)((uint8_t*)ctx->aux + len_bytes + desc_bytes + sums_bytes);  // total, slots BAM cannot hold
+    uint32_t* d_len;
+    BamDesc* d_desc;
+    uint64_t* d_sums;
+    unsigned long long* d_tail;  // total, slots BAM cannot hold
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_len = cv.take<uint32_t>(n_slots);
+        d_desc = cv.take<BamDesc>(n_slots);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(n_slots));
+        d_tail = cv.take<unsigned long long>(2);
+    }))) return rc;
     const SamArgs a = {n_slots, sp->max_hits, sp->flags, d_contigs, n_contigs, d_names, d_fastq_text, d_recs, d_seq, d_qual, d_hits,
                        d_strand, d_ops, d_multi, (sp->flags & BG_SAM_PAIRED) ? d_pairs : nullptr, (const uint8_t*)fm->d_text, fm->n_text, d_dup};
     const dim3 per_slot((uint32_t)((n_slots + 255) / 256));

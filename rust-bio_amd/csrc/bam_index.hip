@@ -226,16 +226,6 @@ __global__ __launch_bounds__(256) void bai_write_ref_kernel(const BaiArgs a, con
     }
 }
 
-struct Carve {  // pieces of one scratch allocation, each 256-byte aligned
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 int bai_check(const bg_ctx* ctx, uint64_t n_slots, const void* recs, const void* off, const void* contigs, uint64_t n_contigs, const void* out,
               uint64_t out_cap, uint64_t* out_bytes, uint64_t* first_bad) {
     if (first_bad) *first_bad = UINT64_MAX;
@@ -263,37 +253,26 @@ int index_dev(bg_ctx* ctx, uint64_t n_slots, const uint8_t* d_recs, const uint64
     BG_HIP(rocprim::inclusive_scan(nullptr, t_max, (uint64_t*)nullptr, (uint64_t*)nullptr, n1, maxi, st));
     BG_HIP(rocprim::exclusive_scan(nullptr, t_ref, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, c1, plus, st));
     if (n) BG_HIP(rocprim::radix_sort_pairs(nullptr, t_sort, (uint64_t*)nullptr, (uint64_t*)nullptr, iota, (uint64_t*)nullptr, n, 0, BAI_KEY_BITS, st));
-    Carve cv;
-    const size_t o_cells = cv.take(4 * 8), o_flag = cv.take(n1 * 8), o_rank = cv.take(n1 * 8), o_rec = cv.take(n1 * sizeof(bai_rec_t)),
-                 o_hu = cv.take(n1 * 8), o_ekey = cv.take(n1 * 8), o_emax = cv.take(n1 * 8), o_key = cv.take(n1 * 8), o_hpos = cv.take(n1 * 8),
-                 o_skey = cv.take(n1 * 8), o_perm = cv.take(n1 * 8), o_bins = cv.take(n1 * 8), o_bstart = cv.take(n1 * 8),
-                 o_refs = cv.take(4 * c1 * 8), o_rbytes = cv.take(c1 * 8), o_rbase = cv.take(c1 * 8),
-                 o_tmp = cv.take(std::max(std::max(t_sum, t_max), std::max(t_ref, t_sort)));
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, cv.at))) return rc;
-    uint8_t* s = (uint8_t*)ctx->aux;
-    unsigned long long* d_cells = (unsigned long long*)(s + o_cells);  // the first error, n_indexed, then the two words read back
+    unsigned long long* d_cells;  // the first error, n_indexed, then the two words read back
+    uint8_t* d_tmp;
     BaiWork w;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_cells = cv.take<unsigned long long>(4);
+        w.flag = cv.take<uint64_t>(n1), w.rank = cv.take<uint64_t>(n1);
+        w.rec = cv.take<bai_rec_t>(n1);
+        w.hu = cv.take<uint64_t>(n1), w.end_key = cv.take<uint64_t>(n1), w.end_max = cv.take<uint64_t>(n1);
+        w.key = cv.take<uint64_t>(n1), w.head_pos = cv.take<uint64_t>(n1);
+        w.key_sorted = cv.take<uint64_t>(n1), w.perm = cv.take<uint64_t>(n1);
+        w.bins_before = cv.take<uint64_t>(n1), w.bin_start = cv.take<uint64_t>(n1);
+        w.ref_first = cv.take<uint64_t>(4 * c1);  // one piece: ref_end, chunk_first and chunk_end follow it
+        w.ref_bytes = cv.take<uint64_t>(c1), w.ref_base = cv.take<uint64_t>(c1);
+        d_tmp = cv.take<uint8_t>(std::max(std::max(t_sum, t_max), std::max(t_ref, t_sort)));
+    }))) return rc;
     w.bad = d_cells;
     w.n_indexed = (uint64_t*)(d_cells + 1);
-    w.flag = (uint64_t*)(s + o_flag);
-    w.rank = (uint64_t*)(s + o_rank);
-    w.rec = (bai_rec_t*)(s + o_rec);
-    w.hu = (uint64_t*)(s + o_hu);
-    w.end_key = (uint64_t*)(s + o_ekey);
-    w.end_max = (uint64_t*)(s + o_emax);
-    w.key = (uint64_t*)(s + o_key);
-    w.head_pos = (uint64_t*)(s + o_hpos);
-    w.key_sorted = (uint64_t*)(s + o_skey);
-    w.perm = (uint64_t*)(s + o_perm);
-    w.bins_before = (uint64_t*)(s + o_bins);
-    w.bin_start = (uint64_t*)(s + o_bstart);
-    w.ref_first = (uint64_t*)(s + o_refs);
     w.ref_end = w.ref_first + c1;
     w.chunk_first = w.ref_end + c1;
     w.chunk_end = w.chunk_first + c1;
-    w.ref_bytes = (uint64_t*)(s + o_rbytes);
-    w.ref_base = (uint64_t*)(s + o_rbase);
-    void* d_tmp = s + o_tmp;
     const BaiArgs a = {n, d_recs, d_off, d_contigs, n_contigs, d_block_off, base, n_blocks, d_out_off};
     BG_HIP(hipMemsetAsync(d_cells, 0xFF, 8, st));
     BG_HIP(hipMemsetAsync(d_cells + 1, 0, 8, st));

@@ -399,16 +399,6 @@ __global__ __launch_bounds__(256) void ind_region_off_kernel(uint64_t n_regions,
     event_off[r] = v;
 }
 
-struct Carve {  // pieces of one scratch allocation, each 256-byte aligned
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 int plp_check(const bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, const void* recs, const void* off, const void* contigs, uint64_t n_contigs,
               const void* regions, uint64_t n_regions, const void* rows, uint64_t rows_cap, uint64_t* n_rows, uint64_t* first_bad) {
     if (first_bad) *first_bad = UINT64_MAX;
@@ -432,27 +422,22 @@ int plp_front(bg_ctx* ctx, hipStream_t st, const PlpArgs& a, PlpFront* f, uint64
     const rocprim::maximum<uint64_t> maxi;
     size_t t_max = 0;
     if (n) BG_HIP(rocprim::inclusive_scan(nullptr, t_max, (uint64_t*)nullptr, (uint64_t*)nullptr, n, maxi, st));
-    Carve cv;
-    const size_t o_cells = cv.take(6 * 8), o_pkey = cv.take(n * 8), o_ekey = cv.take(n * 8), o_pmax = cv.take(n * 8), o_emax = cv.take(n * 8),
-                 o_kept = cv.take(n), o_rlen = cv.take(nr * 4), o_rtiles = cv.take(nr * 4), o_roff = cv.take((nr + 1) * 8), o_toff = cv.take((nr + 1) * 8),
-                 o_sums = cv.take(2 * (nr / 2048 + 2) * 8), o_tmp = cv.take(t_max);
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, cv.at))) return rc;
-    uint8_t* s = (uint8_t*)ctx->aux;
-    unsigned long long* d_cells = (unsigned long long*)(s + o_cells);  // the first error, the regions' verdict, then the four words read back
+    unsigned long long* d_cells;  // the first error, the regions' verdict, then the four words read back
+    uint64_t* d_sums;
+    uint8_t* d_tmp;
     PlpWork& w = f->w;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_cells = cv.take<unsigned long long>(6);
+        w.pos_key = cv.take<uint64_t>(n), w.end_key = cv.take<uint64_t>(n);
+        w.pos_max = cv.take<uint64_t>(n), w.end_max = cv.take<uint64_t>(n);
+        w.kept = cv.take<uint8_t>(n);
+        w.region_len = cv.take<uint32_t>(nr), w.region_tiles = cv.take<uint32_t>(nr);
+        w.row_off = cv.take<uint64_t>(nr + 1), w.tile_off = cv.take<uint64_t>(nr + 1);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(nr));
+        d_tmp = cv.take<uint8_t>(t_max);
+    }))) return rc;
     w.bad = d_cells;
     w.region_bad = (uint64_t*)(d_cells + 1);
-    w.pos_key = (uint64_t*)(s + o_pkey);
-    w.end_key = (uint64_t*)(s + o_ekey);
-    w.pos_max = (uint64_t*)(s + o_pmax);
-    w.end_max = (uint64_t*)(s + o_emax);
-    w.kept = s + o_kept;
-    w.region_len = (uint32_t*)(s + o_rlen);
-    w.region_tiles = (uint32_t*)(s + o_rtiles);
-    w.row_off = (uint64_t*)(s + o_roff);
-    w.tile_off = (uint64_t*)(s + o_toff);
-    uint64_t* d_sums = (uint64_t*)(s + o_sums);
-    void* d_tmp = s + o_tmp;
     BG_HIP(hipMemsetAsync(d_cells, 0xFF, 8, st));
     BG_HIP(hipMemsetAsync(d_cells + 1, 0, 8, st));
     // 1., 2. slots
@@ -585,18 +570,17 @@ extern "C" int bg_bam_sites_dev(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t
     PlpFront f;
     if ((rc = plp_front(ctx, st, a, &f, first_bad))) return rc;
     const uint64_t tiles = f.tiles;
-    Carve cv;
     const bool sizing = !d_sites;
-    const size_t o_count = cv.take(tiles * 4), o_soff = cv.take((tiles + 1) * 8), o_sums = cv.take(2 * (tiles / 2048 + 2) * 8),
-                 o_share = cv.take(sizing || !d_summary ? 0 : tiles * sizeof(bg_bam_region_summary_t));
-    if ((rc = bg_reserve(&ctx->tb, &ctx->tb_bytes, cv.at))) return rc;
-    uint8_t* s = (uint8_t*)ctx->tb;
     SitArgs sa;
+    uint64_t *d_soff, *d_sums;
+    if ((rc = bg_reserve_carved(&ctx->tb, &ctx->tb_bytes, [&](bg_carve& cv) {
+        sa.tile_sites = cv.take<uint32_t>(tiles);
+        sa.tile_site_off = d_soff = cv.take<uint64_t>(tiles + 1);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(tiles));
+        sa.tile_share = sizing || !d_summary ? nullptr : cv.take<bg_bam_region_summary_t>(tiles);
+    }))) return rc;
     sa.prm = *prm;
     sa.text = d_text;
-    sa.tile_sites = (uint32_t*)(s + o_count);
-    sa.tile_site_off = (uint64_t*)(s + o_soff);
-    sa.tile_share = sizing || !d_summary ? nullptr : (bg_bam_region_summary_t*)(s + o_share);
     sa.sites = d_sites;
     sa.wide = ((uintptr_t)d_sites & 15u) == 0;
     uint64_t total = 0;
@@ -605,7 +589,7 @@ extern "C" int bg_bam_sites_dev(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t
         sit_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, sa);
         BG_HIP(hipGetLastError());
         // 5. the tiles placed
-        if ((rc = bg_scan_u32(sa.tile_sites, tiles, (uint64_t*)(s + o_soff), (uint64_t*)(s + o_sums), st))) return rc;
+        if ((rc = bg_scan_u32(sa.tile_sites, tiles, d_soff, d_sums, st))) return rc;
         BG_HIP(hipMemcpyAsync(&total, sa.tile_site_off + tiles, 8, hipMemcpyDeviceToHost, st));
         BG_HIP(hipStreamSynchronize(st));
     }
@@ -708,16 +692,16 @@ extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64
     IndWork x = {};
     uint64_t n_raw = 0;
     if (tiles && n_slots) {
-        Carve cv;
-        const size_t o_count = cv.take(tiles * 4), o_roff = cv.take((tiles + 1) * 8), o_sums = cv.take(2 * (tiles / 2048 + 2) * 8);
-        if ((rc = bg_reserve(&ctx->tb, &ctx->tb_bytes, cv.at))) return rc;
-        uint8_t* s = (uint8_t*)ctx->tb;
-        x.tile_raw = (uint32_t*)(s + o_count);
-        x.tile_raw_off = (uint64_t*)(s + o_roff);
+        uint64_t *d_roff, *d_sums;
+        if ((rc = bg_reserve_carved(&ctx->tb, &ctx->tb_bytes, [&](bg_carve& cv) {
+            x.tile_raw = cv.take<uint32_t>(tiles);
+            x.tile_raw_off = d_roff = cv.take<uint64_t>(tiles + 1);
+            d_sums = cv.take<uint64_t>(bg_scan_sums_words(tiles));
+        }))) return rc;
         // 4. the count pass
         ind_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
         BG_HIP(hipGetLastError());
-        if ((rc = bg_scan_u32(x.tile_raw, tiles, (uint64_t*)(s + o_roff), (uint64_t*)(s + o_sums), st))) return rc;
+        if ((rc = bg_scan_u32(x.tile_raw, tiles, d_roff, d_sums, st))) return rc;
         BG_HIP(hipMemcpyAsync(&n_raw, x.tile_raw_off + tiles, 8, hipMemcpyDeviceToHost, st));
         BG_HIP(hipStreamSynchronize(st));
     }
@@ -730,33 +714,26 @@ extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64
         const rocprim::counting_iterator<uint32_t> iota(0);
         size_t t_sort = 0;
         BG_HIP(rocprim::merge_sort(nullptr, t_sort, iota, (uint32_t*)nullptr, n, IndOrder{nullptr, nullptr, nullptr}, st));
-        Carve cv;
-        const size_t o_raw = cv.take(n * sizeof(ind_raw_t)), o_order = cv.take(n * 4), o_head = cv.take(n * 4), o_rev = cv.take(n * 4),
-                     o_hoff = cv.take((n + 1) * 8), o_voff = cv.take((n + 1) * 8), o_run = cv.take((n + 1) * 4), o_keep = cv.take(n * 4), o_len = cv.take(n * 4),
-                     o_koff = cv.take((n + 1) * 8), o_soff = cv.take((n + 1) * 8), o_tot = cv.take(16), o_sums = cv.take(2 * (n / 2048 + 2) * 8),
-                     o_tmp = cv.take(t_sort);
-        if ((rc = bg_reserve(&ctx->bnd, &ctx->bnd_bytes, cv.at))) return rc;
-        uint8_t* s = (uint8_t*)ctx->bnd;
-        x.raw = (ind_raw_t*)(s + o_raw);
-        x.order = (uint32_t*)(s + o_order);
-        x.head = (uint32_t*)(s + o_head);
-        x.rev = (uint32_t*)(s + o_rev);
-        x.head_off = (uint64_t*)(s + o_hoff);
-        x.rev_off = (uint64_t*)(s + o_voff);
-        x.run_start = (uint32_t*)(s + o_run);
-        x.keep = (uint32_t*)(s + o_keep);
-        x.seq_len = (uint32_t*)(s + o_len);
-        x.keep_off = (uint64_t*)(s + o_koff);
-        x.seq_off = (uint64_t*)(s + o_soff);
-        uint64_t* d_tot = (uint64_t*)(s + o_tot);
-        uint64_t* d_sums = (uint64_t*)(s + o_sums);
+        uint64_t *d_tot, *d_sums;
+        uint8_t* d_tmp;
+        if ((rc = bg_reserve_carved(&ctx->bnd, &ctx->bnd_bytes, [&](bg_carve& cv) {
+            x.raw = cv.take<ind_raw_t>(n);
+            x.order = cv.take<uint32_t>(n), x.head = cv.take<uint32_t>(n), x.rev = cv.take<uint32_t>(n);
+            x.head_off = cv.take<uint64_t>(n + 1), x.rev_off = cv.take<uint64_t>(n + 1);
+            x.run_start = cv.take<uint32_t>(n + 1);
+            x.keep = cv.take<uint32_t>(n), x.seq_len = cv.take<uint32_t>(n);
+            x.keep_off = cv.take<uint64_t>(n + 1), x.seq_off = cv.take<uint64_t>(n + 1);
+            d_tot = cv.take<uint64_t>(2);
+            d_sums = cv.take<uint64_t>(bg_scan_sums_words(n));
+            d_tmp = cv.take<uint8_t>(t_sort);
+        }))) return rc;
         // 5. the emit pass
         ind_tile_kernel<true><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
         BG_HIP(hipGetLastError());
         if (stop == 2) return BG_OK;
         // 6. the order, the runs
         size_t t = t_sort;
-        BG_HIP(rocprim::merge_sort(s + o_tmp, t, iota, x.order, n, IndOrder{x.raw, d_recs, d_off}, st));
+        BG_HIP(rocprim::merge_sort(d_tmp, t, iota, x.order, n, IndOrder{x.raw, d_recs, d_off}, st));
         if (stop == 3) return BG_OK;
         ind_head_kernel<<<lanes(n), dim3(256), 0, st>>>(n, a, x);
         BG_HIP(hipGetLastError());

@@ -261,7 +261,6 @@ int reads_args(const bg_ctx* ctx, const bg_bam_reads_t* prm, uint64_t n, const v
     if (recs && (!seq_off || !qual_off || (!seq && seq_cap) || (!qual && qual_cap))) return BG_ERR_INVALID_ARG;
     return n >= 0xFFFFFFFFull ? BG_ERR_TOO_LARGE : BG_OK;
 }
-inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
 }  // namespace
 
@@ -302,15 +301,16 @@ extern "C" int bg_bam_records_dev(bg_ctx* ctx, const uint8_t* d_bam, uint64_t in
         return BG_OK;
     }
     bg_scratch_guard guard(ctx, st);
-    auto sums_words = [](uint64_t n) { return 2 * (n / 2048 + 2); };
-    // the count: 8-byte arrays first, then 4-byte
+    // the count
     const uint64_t n_pos = in_bytes - body_off, n_chunks = (n_pos + REC_CHUNK - 1) / REC_CHUNK;
-    const size_t w_off1 = n_chunks + 1, w_sums1 = sums_words(n_chunks);
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, 8 * (w_off1 + w_sums1) + sizeof(rec_result_t) + 4 * n_chunks + 16))) return rc;
-    uint64_t* d_off1 = (uint64_t*)ctx->aux;
-    uint64_t* d_sums1 = d_off1 + w_off1;
-    rec_result_t* d_res = (rec_result_t*)(d_sums1 + w_sums1);
-    uint32_t* d_cnt1 = (uint32_t*)(d_res + 1);
+    uint64_t *d_off1, *d_sums1;
+    rec_result_t* d_res;
+    uint32_t* d_cnt1;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_off1 = cv.take<uint64_t>(n_chunks + 1), d_sums1 = cv.take<uint64_t>(bg_scan_sums_words(n_chunks));
+        d_res = cv.take<rec_result_t>(1);
+        d_cnt1 = cv.take<uint32_t>(n_chunks);
+    }))) return rc;
     BG_HIP(hipMemsetAsync(d_res, 0xFF, sizeof(rec_result_t), st));
     rec_cand_kernel<false><<<dim3((uint32_t)n_chunks), dim3(256), 0, st>>>(d_bam, in_bytes, body_off, n_ref, d_cnt1, nullptr, nullptr, 0);
     BG_HIP(hipGetLastError());
@@ -322,15 +322,16 @@ extern "C" int bg_bam_records_dev(bg_ctx* ctx, const uint8_t* d_bam, uint64_t in
     if (n_cand >= BAMR_NONE) return BG_ERR_TOO_LARGE;
     // the candidates: 18 bytes each
     const uint64_t cap = n_cand ? n_cand : 1, c_chunks = (cap + REC_CHUNK - 1) / REC_CHUNK;
-    const size_t w_offm = c_chunks + 1, w_sums2 = sums_words(c_chunks);
-    if ((rc = bg_reserve(&ctx->tb, &ctx->tb_bytes, 8 * (cap + w_offm + w_sums2) + 4 * (2 * cap + c_chunks) + 2 * cap + 16))) return rc;
-    uint64_t* d_pos = (uint64_t*)ctx->tb;
-    uint64_t* d_offm = d_pos + cap;
-    uint64_t* d_sums2 = d_offm + w_offm;
-    uint32_t* d_jump[2] = {(uint32_t*)(d_sums2 + w_sums2), (uint32_t*)(d_sums2 + w_sums2) + cap};
-    uint32_t* d_cntm = d_jump[1] + cap;
-    uint8_t* d_chain = (uint8_t*)(d_cntm + c_chunks);
-    uint8_t* d_tail = d_chain + cap;
+    uint64_t *d_pos, *d_offm, *d_sums2;
+    uint32_t *d_jumps, *d_cntm;
+    uint8_t *d_chain, *d_tail;
+    if ((rc = bg_reserve_carved(&ctx->tb, &ctx->tb_bytes, [&](bg_carve& cv) {
+        d_pos = cv.take<uint64_t>(cap), d_offm = cv.take<uint64_t>(c_chunks + 1), d_sums2 = cv.take<uint64_t>(bg_scan_sums_words(c_chunks));
+        d_jumps = cv.take<uint32_t>(2 * cap);  // one piece: the two halves the doubling rounds swap
+        d_cntm = cv.take<uint32_t>(c_chunks);
+        d_chain = cv.take<uint8_t>(cap), d_tail = cv.take<uint8_t>(cap);
+    }))) return rc;
+    uint32_t* d_jump[2] = {d_jumps, d_jumps + cap};
     const uint32_t tables = d_off ? 1u : 0u;
     const uint32_t grid = (uint32_t)((cap + 255) / 256 < 2048 ? (cap + 255) / 256 : 2048);
     if (n_cand) {
@@ -390,17 +391,15 @@ extern "C" int bg_bam_reads_dev(bg_ctx* ctx, const bg_bam_reads_t* prm, uint64_t
         return BG_OK;
     }
     bg_scratch_guard guard(ctx, st);
-    // 8-byte arrays first (the three scans and their sums, the result), then the three 4-byte columns
-    const size_t w_scan = n + 1, w_sums = 2 * (n / 2048 + 2);
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, 8 * (3 * w_scan + w_sums) + sizeof(read_result_t) + 4 * 3 * n + 16))) return rc;
-    uint64_t* d_rank = (uint64_t*)ctx->aux;
-    uint64_t* d_soff = d_rank + w_scan;
-    uint64_t* d_qoff = d_soff + w_scan;
-    uint64_t* d_sums = d_qoff + w_scan;
-    read_result_t* d_res = (read_result_t*)(d_sums + w_sums);
-    uint32_t* d_keep = (uint32_t*)(d_res + 1);
-    uint32_t* d_slen = d_keep + n;
-    uint32_t* d_qlen = d_slen + n;
+    uint64_t *d_rank, *d_soff, *d_qoff, *d_sums;
+    read_result_t* d_res;
+    uint32_t *d_keep, *d_slen, *d_qlen;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_rank = cv.take<uint64_t>(n + 1), d_soff = cv.take<uint64_t>(n + 1), d_qoff = cv.take<uint64_t>(n + 1);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(n));
+        d_res = cv.take<read_result_t>(1);
+        d_keep = cv.take<uint32_t>(n), d_slen = cv.take<uint32_t>(n), d_qlen = cv.take<uint32_t>(n);
+    }))) return rc;
     const ReadArgs a = {n, d_bam, d_off, n_ref, *prm};
     BG_HIP(hipMemsetAsync(d_res, 0xFF, 8, st));
     read_length_kernel<<<lanes(n), dim3(256), 0, st>>>(a, d_keep, d_slen, d_qlen, d_res);

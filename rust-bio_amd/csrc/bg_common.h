@@ -115,10 +115,24 @@ struct bg_ctx {
 
 // grow-only device scratch
 int bg_reserve(void** p, size_t* cur, size_t need);
+#include "bg_carve.h"
+// ... laid out as the arrays that `list(bg_carve&)` takes: the list runs once to measure, the buffer is reserved, the list
+// runs again on the buffer.  Pointers are bound after the reserve and only here, so none survives a grow of its buffer.
+template <class List>
+int bg_reserve_carved(void** p, size_t* cur, List&& list) {
+    bg_carve measure;
+    list(measure);
+    if (int rc = bg_reserve(p, cur, measure.at)) return rc;
+    bg_carve bound{(uint8_t*)*p};
+    list(bound);
+    return BG_OK;
+}
 // exclusive scan of n uint32 counts into n + 1 uint64 offsets, d_off[n] the total (scan.hip).  d_sums: scratch of
-// 2 * (n / 2048 + 1) uint64 — a sum and a base for each of the n / 2048 + 1 blocks; that is all it touches.  Callers that
-// reserve 2 * (n / 2048 + 2) words carry two words of slack.
+// bg_scan_sums_words(n) uint64.  It touches a sum and a base for each of the n / 2048 + 1 blocks; two words are slack.
+inline size_t bg_scan_sums_words(uint64_t n) { return 2 * (size_t)(n / 2048 + 2); }
 int bg_scan_u32(const uint32_t* d_len, uint64_t n, uint64_t* d_off, uint64_t* d_sums, hipStream_t st);
+// a lane per item in workgroups of 256
+inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 // bg_align_batch_dev with what the caller knows about the lengths: 1 all pairs share (m, n), 0 they differ, -1 unknown
 int bg_align_batch_dev_hint(bg_ctx* ctx, const bg_scoring_t* sc, int mode, uint64_t n_pairs, const uint8_t* d_x,
                             const uint64_t* d_x_off, const uint8_t* d_y, const uint64_t* d_y_off, uint32_t max_xlen,

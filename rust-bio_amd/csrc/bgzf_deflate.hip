@@ -116,14 +116,16 @@ extern "C" int bg_bgzf_deflate_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);
     const uint64_t batch = n_blocks < BGZF_DFL_BATCH ? n_blocks : BGZF_DFL_BATCH;
-    const size_t slot_bytes = batch * DFL_SLOT_BYTES, len_bytes = (batch * 4 + 15) & ~(size_t)15, off_bytes = (batch + 2) * 8;
-    const size_t sums_bytes = 2 * (batch / 2048 + 2) * 8;
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, slot_bytes + len_bytes + off_bytes + sums_bytes + 16))) return rc;
-    uint8_t* d_slots = (uint8_t*)ctx->aux;
-    uint32_t* d_len = (uint32_t*)(d_slots + slot_bytes);
-    uint64_t* d_off = (uint64_t*)(d_slots + slot_bytes + len_bytes);
-    uint64_t* d_sums = (uint64_t*)(d_slots + slot_bytes + len_bytes + off_bytes);
-    uint64_t* d_base = (uint64_t*)(d_slots + slot_bytes + len_bytes + off_bytes + sums_bytes);  // where the next sub-batch starts
+    uint8_t* d_slots;
+    uint32_t* d_len;
+    uint64_t *d_off, *d_sums, *d_base;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_slots = cv.take<uint8_t>(batch * DFL_SLOT_BYTES);
+        d_len = cv.take<uint32_t>(batch);
+        d_off = cv.take<uint64_t>(batch + 2);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(batch));
+        d_base = cv.take<uint64_t>(1);  // where the next sub-batch starts
+    }))) return rc;
     BG_HIP(hipMemsetAsync(d_base, 0, 8, st));
     for (uint64_t b0 = 0; b0 < n_blocks; b0 += batch) {
         const uint32_t nb = (uint32_t)(n_blocks - b0 < batch ? n_blocks - b0 : batch);

@@ -261,24 +261,20 @@ extern "C" int bg_bgzf_blocks_dev(bg_ctx* ctx, const uint8_t* d_in, uint64_t in_
     }
     bg_scratch_guard guard(ctx, st);
     const uint64_t n_chunks = (in_bytes + BLK_CHUNK - 1) / BLK_CHUNK, cap = in_bytes / 16 + 1, c_chunks = (cap + BLK_CHUNK - 1) / BLK_CHUNK;
-    auto sums_words = [](uint64_t n) { return 2 * (n / 2048 + 2); };
-    // 8-byte arrays first, then 4-byte, then bytes
-    const size_t w_pos = cap, w_off1 = n_chunks + 1, w_offm = c_chunks + 1, w_offs = c_chunks + 1, w_sums = sums_words(n_chunks > c_chunks ? n_chunks : c_chunks);
-    const size_t words8 = w_pos + w_off1 + w_offm + w_offs + w_sums + sizeof(blk_result_t) / 8;
-    const size_t words4 = 2 * cap + n_chunks + 2 * c_chunks;
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, 8 * words8 + 4 * words4 + 2 * cap + 16))) return rc;
-    uint64_t* d_pos = (uint64_t*)ctx->aux;
-    uint64_t* d_off1 = d_pos + w_pos;
-    uint64_t* d_offm = d_off1 + w_off1;
-    uint64_t* d_offs = d_offm + w_offm;
-    uint64_t* d_sums = d_offs + w_offs;
-    blk_result_t* d_res = (blk_result_t*)(d_sums + w_sums);
-    uint32_t* d_jump[2] = {(uint32_t*)(d_res + 1), (uint32_t*)(d_res + 1) + cap};
-    uint32_t* d_cnt1 = d_jump[1] + cap;
-    uint32_t* d_cntm = d_cnt1 + n_chunks;
-    uint32_t* d_cnts = d_cntm + c_chunks;
-    uint8_t* d_chain = (uint8_t*)(d_cnts + c_chunks);
-    uint8_t* d_tail = d_chain + cap;
+    uint64_t *d_pos, *d_off1, *d_offm, *d_offs, *d_sums;
+    blk_result_t* d_res;
+    uint32_t *d_jumps, *d_cnt1, *d_cntm, *d_cnts;
+    uint8_t *d_chain, *d_tail;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_pos = cv.take<uint64_t>(cap), d_off1 = cv.take<uint64_t>(n_chunks + 1);
+        d_offm = cv.take<uint64_t>(c_chunks + 1), d_offs = cv.take<uint64_t>(c_chunks + 1);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(n_chunks > c_chunks ? n_chunks : c_chunks));
+        d_res = cv.take<blk_result_t>(1);
+        d_jumps = cv.take<uint32_t>(2 * cap);  // one piece: the two halves the doubling rounds swap
+        d_cnt1 = cv.take<uint32_t>(n_chunks), d_cntm = cv.take<uint32_t>(c_chunks), d_cnts = cv.take<uint32_t>(c_chunks);
+        d_chain = cv.take<uint8_t>(cap), d_tail = cv.take<uint8_t>(cap);
+    }))) return rc;
+    uint32_t* d_jump[2] = {d_jumps, d_jumps + cap};
     const uint64_t* d_ncand = d_off1 + n_chunks;
     const uint32_t tables = d_block_off ? 1u : 0u;
     const uint32_t grid = (uint32_t)((cap + 255) / 256 < 2048 ? (cap + 255) / 256 : 2048);

@@ -396,7 +396,7 @@ int bg_range_to_host(const uint8_t* d_src, uint8_t* h_dst, const uint64_t* d_slo
     return BG_OK;
 }
 
-size_t bg_compact_ops_scratch(uint64_t n) { return a256(n * 4) + a256((n + 1) * 8) + 2 * (n / 2048 + 2) * 8 + 256; }
+size_t bg_compact_ops_scratch(uint64_t n) { return a256(n * 4) + a256((n + 1) * 8) + bg_scan_sums_words(n) * 8 + 256; }
 
 int bg_compact_ops_dev(bg_alignment_t* d_rec, uint64_t n, const uint8_t* d_ops, uint8_t* d_compact, bool global_offsets, uint64_t* d_cell,
                        uint64_t* d_batch_total, void* d_scratch, bool long_ops, hipStream_t st) {

@@ -654,10 +654,13 @@ extern "C" int bg_fasta_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
     if (n_tiles >= (1ull << 31)) return BG_ERR_TOO_LARGE;
     int rc;
     // aux: tile summaries, tile carries, misc = {first bad byte, headers, sequence bytes, first empty record, error line, headers in front of it}
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, n_tiles * (sizeof(FaTileSum) + sizeof(FaTileIn)) + 64))) return rc;
-    FaTileSum* d_sum = (FaTileSum*)ctx->aux;
-    FaTileIn* d_tin = (FaTileIn*)(d_sum + n_tiles);
-    uint64_t* d_misc = (uint64_t*)(d_tin + n_tiles);
+    FaTileSum* d_sum;
+    FaTileIn* d_tin;
+    uint64_t* d_misc;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_sum = cv.take<FaTileSum>(n_tiles), d_tin = cv.take<FaTileIn>(n_tiles);
+        d_misc = cv.take<uint64_t>(8);
+    }))) return rc;
     uint64_t misc[6] = {kFaNone, 0, 0, kFaNone, 0, 0};
     BG_HIP(hipMemcpyAsync(d_misc, misc, sizeof(misc), hipMemcpyHostToDevice, st));
     fa_summary_kernel<<<dim3((uint32_t)n_tiles), dim3(kFaThreads), 0, st>>>(d_text, len, d_sum, (unsigned long long*)d_misc);
@@ -671,11 +674,14 @@ extern "C" int bg_fasta_parse_dev(bg_ctx* ctx, const uint8_t* d_text, uint64_t l
     // more header lines than rec_cap: the records go to scratch, so that the count (which an empty record or an error beyond
     // rec_cap may still clip) is exact; they are copied out if it fits after all
     const bool spill = n_raw > rec_cap;
-    const size_t chk_bytes = (n_raw * 4 + 255) & ~(size_t)255;
-    if ((rc = bg_reserve(&ctx->tb, &ctx->tb_bytes, chk_bytes + (spill ? n_raw * sizeof(bg_fasta_record_t) + (n_raw + 1) * 8 : 0) + 256))) return rc;
-    uint32_t* d_chk = (uint32_t*)ctx->tb;
-    bg_fasta_record_t* recs = spill ? (bg_fasta_record_t*)((uint8_t*)ctx->tb + chk_bytes) : d_recs;
-    uint64_t* seq_off = spill ? (uint64_t*)(recs + n_raw) : d_seq_off;
+    uint32_t* d_chk;
+    bg_fasta_record_t* recs;
+    uint64_t* seq_off;
+    if ((rc = bg_reserve_carved(&ctx->tb, &ctx->tb_bytes, [&](bg_carve& cv) {
+        d_chk = cv.take<uint32_t>(n_raw);
+        recs = spill ? cv.take<bg_fasta_record_t>(n_raw) : d_recs;
+        seq_off = spill ? cv.take<uint64_t>(n_raw + 1) : d_seq_off;
+    }))) return rc;
     if (first_bad != kFaNone) fa_error_kernel<<<dim3(1), dim3(256), 0, st>>>(d_text, d_sum, d_tin, (const unsigned long long*)d_misc, d_misc + 4);
     if (n_raw) {
         BG_HIP(hipMemsetAsync(d_chk, 0, n_raw * 4, st));
@@ -771,10 +777,11 @@ extern "C" int bg_fasta_reference_dev(bg_ctx* ctx, uint64_t n_records, const bg_
     bg_scratch_guard guard(ctx, st);
     BG_HIP(hipSetDevice(ctx->device));
     int rc;
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, (2 * (n_records + 1) + 1) * 8))) return rc;
-    uint64_t* d_starts = (uint64_t*)ctx->aux;
-    uint64_t* d_name_off = d_starts + n_records + 1;
-    uint64_t* d_bad = d_name_off + n_records + 1;
+    uint64_t *d_starts, *d_name_off, *d_bad;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_starts = cv.take<uint64_t>(n_records + 1), d_name_off = cv.take<uint64_t>(n_records + 1);
+        d_bad = cv.take<uint64_t>(1);
+    }))) return rc;
     BG_HIP(hipMemcpyAsync(d_bad, first_bad, 8, hipMemcpyHostToDevice, st));
     fa_ref_layout_kernel<<<dim3(1), dim3(1024), 0, st>>>(d_recs, n_records, d_starts, d_name_off, (unsigned long long*)d_bad);
     BG_HIP(hipGetLastError());

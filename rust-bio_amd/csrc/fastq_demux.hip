@@ -238,18 +238,18 @@ extern "C" int bg_fastq_demux_split_dev(bg_ctx* ctx, uint64_t n, uint32_t n_bins
         return BG_OK;
     }
     bg_scratch_guard guard(ctx, st);
-    // aux: the scanned (group, tile) table (uint64[cells + 1]) and perm (uint64[n], unless the caller takes it), the block sums
-    // of the three scans, then the table's counts and the two length columns at their places (uint32)
+    // aux: the scanned (group, tile) table and perm (unless the caller takes it), the block sums of the three scans, then the
+    // table's counts and the two length columns at their places
     const uint32_t n_tiles = (uint32_t)((n + DMX_TILE - 1) / DMX_TILE);
-    const size_t cells = (size_t)ng * n_tiles, t_sums = 2 * (cells / 2048 + 2), r_sums = 2 * (size_t)(n / 2048 + 2);
-    const size_t words64 = cells + 1 + (d_perm ? 0 : (size_t)n) + t_sums + 2 * r_sums;
-    if (int rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, words64 * 8 + (cells + 2 * (size_t)n) * 4)) return rc;
-    uint64_t* d_base = (uint64_t*)ctx->aux;
-    uint64_t* perm = d_perm ? d_perm : d_base + cells + 1;
-    uint64_t* d_sums = d_base + cells + 1 + (d_perm ? 0 : (size_t)n);
-    uint32_t* d_count = (uint32_t*)(d_sums + t_sums + 2 * r_sums);
-    uint32_t* d_sl = d_count + cells;
-    uint32_t* d_ql = d_sl + n;
+    const size_t cells = (size_t)ng * n_tiles, t_sums = bg_scan_sums_words(cells), r_sums = bg_scan_sums_words(n);
+    uint64_t *d_base, *perm, *d_sums;
+    uint32_t *d_count, *d_sl, *d_ql;
+    if (int rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_base = cv.take<uint64_t>(cells + 1);
+        perm = d_perm ? d_perm : cv.take<uint64_t>(n);
+        d_sums = cv.take<uint64_t>(t_sums + 2 * r_sums);
+        d_count = cv.take<uint32_t>(cells), d_sl = cv.take<uint32_t>(n), d_ql = cv.take<uint32_t>(n);
+    })) return rc;
     dmx_hist_kernel<<<dim3(n_tiles), dim3(256), 0, st>>>(n, n_bins, n_tiles, d_bin, d_count);
     BG_HIP(hipGetLastError());
     if (int rc = bg_scan_u32(d_count, cells, d_base, d_sums, st)) return rc;

@@ -176,18 +176,17 @@ extern "C" int bg_fastq_filter_dev(bg_ctx* ctx, uint64_t n, const bg_fastq_filte
         return BG_OK;
     }
     bg_scratch_guard guard(ctx, st);
-    // aux: three scanned columns rank / so / qo (uint64[n + 1]) and the block sums of their scans, the three uint32 columns they
-    // are scanned from, keep[n]
-    const size_t col = (size_t)n + 1, sums = 2 * (size_t)(n / 2048 + 2), words = ((size_t)n * 3 + 1) / 2 * 2;
-    if (int rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, (3 * col + 3 * sums) * 8 + words * 4 + n)) return rc;
-    uint64_t* d_rank = (uint64_t*)ctx->aux;
-    uint64_t* d_so = d_rank + col;
-    uint64_t* d_qo = d_so + col;
-    uint64_t* d_sums = d_qo + col;
-    uint32_t* d_k = (uint32_t*)(d_sums + 3 * sums);
-    uint32_t* d_sl = d_k + n;
-    uint32_t* d_ql = d_sl + n;
-    uint8_t* keep = d_keep ? d_keep : (uint8_t*)(d_k + words);
+    // aux: three scanned columns rank / so / qo and the block sums of their scans, the three columns they are scanned from, keep
+    const size_t sums = bg_scan_sums_words(n);
+    uint64_t *d_rank, *d_so, *d_qo, *d_sums;
+    uint32_t *d_k, *d_sl, *d_ql;
+    uint8_t* keep;
+    if (int rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_rank = cv.take<uint64_t>(n + 1), d_so = cv.take<uint64_t>(n + 1), d_qo = cv.take<uint64_t>(n + 1);
+        d_sums = cv.take<uint64_t>(3 * sums);  // one piece: scan k has d_sums + k * sums
+        d_k = cv.take<uint32_t>(n), d_sl = cv.take<uint32_t>(n), d_ql = cv.take<uint32_t>(n);
+        keep = d_keep ? d_keep : cv.take<uint8_t>(n);
+    })) return rc;
     const FqfArgs a = {n, *flt, d_hits, n_pat, d_recs, d_seq, d_seq_off, d_qual_off};
     if (flt->max_n != 0xFFFFFFFFu)
         fq_pass_kernel<16><<<dim3((uint32_t)((n * 16 + 255) / 256)), dim3(256), 0, st>>>(a, keep, d_k, d_sl, d_ql);
@@ -247,10 +246,12 @@ extern "C" int bg_fastq_emit_dev(bg_ctx* ctx, uint64_t n, uint64_t first, uint64
         return BG_OK;
     }
     bg_scratch_guard guard(ctx, st);
-    const size_t len_bytes = ((size_t)m * 4 + 15) & ~(size_t)15;
-    if (int rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, len_bytes + 2 * (size_t)(m / 2048 + 2) * 8)) return rc;
-    uint32_t* d_len = (uint32_t*)ctx->aux;
-    uint64_t* d_sums = (uint64_t*)((uint8_t*)ctx->aux + len_bytes);
+    uint32_t* d_len;
+    uint64_t* d_sums;
+    if (int rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_len = cv.take<uint32_t>(m);
+        d_sums = cv.take<uint64_t>(bg_scan_sums_words(m));
+    })) return rc;
     fq_length_kernel<<<dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st>>>(m, first, step, d_recs, d_len);
     BG_HIP(hipGetLastError());
     if (int rc = bg_scan_u32(d_len, m, d_out_off, d_sums, st)) return rc;

@@ -84,13 +84,13 @@ extern "C" int bg_fastq_trim_dev(bg_ctx* ctx, uint64_t n, int mode, const bg_ali
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);
-    // aux: lo[n], seq_len[n], qual_len[n] (uint32), then the block sums of the two scans
-    const size_t words = ((size_t)n * 3 + 1) / 2 * 2, sums = 2 * (size_t)(n / 2048 + 2);
-    if (int rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, words * 4 + 2 * sums * 8)) return rc;
-    uint32_t* d_lo = (uint32_t*)ctx->aux;
-    uint32_t* d_sl = d_lo + n;
-    uint32_t* d_ql = d_sl + n;
-    uint64_t* d_sums = (uint64_t*)(d_lo + words);
+    const size_t sums = bg_scan_sums_words(n);
+    uint32_t *d_lo, *d_sl, *d_ql;
+    uint64_t* d_sums;
+    if (int rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_lo = cv.take<uint32_t>(n), d_sl = cv.take<uint32_t>(n), d_ql = cv.take<uint32_t>(n);
+        d_sums = cv.take<uint64_t>(2 * sums);  // the block sums of the two scans
+    })) return rc;
     if (n) {
         trim_lengths_kernel<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st>>>(n, mode, d_hits, n_pat, d_seq_off, d_qual_off, d_lo,
                                                                                      d_sl, d_ql);

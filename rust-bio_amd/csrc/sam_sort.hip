@@ -145,15 +145,6 @@ __global__ __launch_bounds__(256) void sort_copy_long_kernel(const uint64_t* __r
     }
 }
 
-struct Carve {  // pieces of one scratch allocation, each 256-byte aligned
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 int md_check(const bg_ctx* ctx, const bg_markdup_params_t* mp, uint64_t n_reads, uint64_t n_contigs) {
     if (!ctx || !mp) return BG_ERR_INVALID_ARG;
     if (mp->flags & ~(uint32_t)BG_SAM_PAIRED) return BG_ERR_INVALID_ARG;
@@ -201,19 +192,17 @@ extern "C" int bg_sam_markdup_dev(bg_ctx* ctx, const bg_markdup_params_t* mp, ui
     const rocprim::counting_iterator<uint64_t> iota(0);
     BG_HIP(rocprim::merge_sort(nullptr, t_ends, iota, (uint64_t*)nullptr, n, MdOrder{nullptr}, st));
     if (np) BG_HIP(rocprim::merge_sort(nullptr, t_pairs, iota, (uint64_t*)nullptr, np, MdOrder{nullptr}, st));
-    Carve cv;
-    const size_t o_counts = cv.take(4 * 8), o_score = cv.take(n * 4), o_ends = cv.take(n * sizeof(md_entry_t)),
-                 o_pairs = cv.take(np * sizeof(md_entry_t)), o_order = cv.take(n * 8), o_sorted = cv.take(n * sizeof(md_entry_t)),
-                 o_tmp = cv.take(std::max(t_ends, t_pairs));
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, cv.at))) return rc;
-    uint8_t* base = (uint8_t*)ctx->aux;
-    uint64_t* d_counts = (uint64_t*)(base + o_counts);
-    uint32_t* d_score = (uint32_t*)(base + o_score);
-    md_entry_t* d_ends = (md_entry_t*)(base + o_ends);
-    md_entry_t* d_pairs = (md_entry_t*)(base + o_pairs);
-    uint64_t* d_order = (uint64_t*)(base + o_order);
-    md_entry_t* d_sorted = (md_entry_t*)(base + o_sorted);
-    void* d_tmp = base + o_tmp;
+    uint64_t *d_counts, *d_order;
+    uint32_t* d_score;
+    md_entry_t *d_ends, *d_pairs, *d_sorted;
+    uint8_t* d_tmp;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_counts = cv.take<uint64_t>(4);
+        d_score = cv.take<uint32_t>(n);
+        d_ends = cv.take<md_entry_t>(n), d_pairs = cv.take<md_entry_t>(np);
+        d_order = cv.take<uint64_t>(n), d_sorted = cv.take<md_entry_t>(n);
+        d_tmp = cv.take<uint8_t>(std::max(t_ends, t_pairs));
+    }))) return rc;
     BG_HIP(hipMemsetAsync(d_counts, 0, 4 * 8, st));
     BG_HIP(hipMemsetAsync(d_dup, 0, n, st));
     md_score_kernel<<<dim3(blocks_of(n, 256 / MD_G)), dim3(256), 0, st>>>(n, d_recs, d_qual, mp->phred_offset, mp->min_qual, d_score);
@@ -308,16 +297,12 @@ extern "C" int bg_sam_sort_dev(bg_ctx* ctx, uint64_t n_slots, const uint64_t* d_
     size_t t_sort = 0, t_scan = 0;
     BG_HIP(rocprim::radix_sort_pairs(nullptr, t_sort, d_key, (uint64_t*)nullptr, iota, d_perm, n, 0, 64, st));
     BG_HIP(rocprim::exclusive_scan(nullptr, t_scan, (uint64_t*)nullptr, d_out_off, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), st));
-    Carve cv;
-    const size_t o_keys = cv.take(n * 8), o_len = cv.take((n + 1) * 8), o_list = cv.take(n * 8), o_count = cv.take(8),
-                 o_tmp = cv.take(std::max(t_sort, t_scan));
-    if ((rc = bg_reserve(&ctx->aux, &ctx->aux_bytes, cv.at))) return rc;
-    uint8_t* base = (uint8_t*)ctx->aux;
-    uint64_t* d_keys_out = (uint64_t*)(base + o_keys);
-    uint64_t* d_len = (uint64_t*)(base + o_len);
-    uint64_t* d_list = (uint64_t*)(base + o_list);
-    uint64_t* d_count = (uint64_t*)(base + o_count);
-    void* d_tmp = base + o_tmp;
+    uint64_t *d_keys_out, *d_len, *d_list, *d_count;
+    uint8_t* d_tmp;
+    if ((rc = bg_reserve_carved(&ctx->aux, &ctx->aux_bytes, [&](bg_carve& cv) {
+        d_keys_out = cv.take<uint64_t>(n), d_len = cv.take<uint64_t>(n + 1), d_list = cv.take<uint64_t>(n), d_count = cv.take<uint64_t>(1);
+        d_tmp = cv.take<uint8_t>(std::max(t_sort, t_scan));
+    }))) return rc;
     hipEvent_t ev[3] = {};
     if (ctx->timing) {
         for (hipEvent_t& e : ev) BG_HIP(hipEventCreate(&e));

@@ -458,7 +458,7 @@ int se_candidates(SeedRun& R, SeedPassRun& p, bool* any_panic, bool* any_truncat
     if ((rc = R.need(kUpper, nq * 8))) return rc;
     if ((rc = R.need(kVotes, nq * 4))) return rc;
     if ((rc = R.need(kHitOff, (nq + 1) * 8))) return rc;
-    if ((rc = R.need(kScanPartials, 2 * (nq / 2048 + 2) * 8))) return rc;
+    if ((rc = R.need(kScanPartials, bg_scan_sums_words(nq) * 8))) return rc;
     if ((rc = R.need(kFlags, 64))) return rc;
     uint8_t* d_tag = R.buf<uint8_t>(kTag);
     uint64_t *d_lo = R.buf<uint64_t>(kLower), *d_hi = R.buf<uint64_t>(kUpper), *d_sums = R.buf<uint64_t>(kScanPartials);
@@ -711,7 +711,7 @@ int se_reseed(SeedRun& R, const SeedPassRun& p, uint8_t* strand1, uint64_t n_ind
     const uint64_t nr = p.nr;
     if ((rc = R.need(kReseedCounts, 2 * nr * 4))) return rc;
     if ((rc = R.need(kReseedOffsets, 2 * (nr + 1) * 8))) return rc;
-    if ((rc = R.need(kScanPartials, 2 * (nr / 2048 + 2) * 8))) return rc;
+    if ((rc = R.need(kScanPartials, bg_scan_sums_words(nr) * 8))) return rc;
     Carve counts{R.buf<uint8_t>(kReseedCounts)}, offsets{R.buf<uint8_t>(kReseedOffsets)};
     uint32_t *d_flag = counts.take<uint32_t>(nr), *d_bytes = counts.take<uint32_t>(nr);
     uint64_t *d_idx = offsets.take<uint64_t>(nr + 1), *d_boff = offsets.take<uint64_t>(nr + 1);
