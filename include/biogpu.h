@@ -1577,8 +1577,8 @@ int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, con
  * and the tiles; the number of sites); the records are then written asynchronously on `stream`.  A tile's share of its
  * region's summary is parked in scratch and a pass of its own sums a region's tiles (integer sums and maxima: exact, whatever
  * the order).  Scratch is the ctx's: the pileup's and 12 bytes a tile, 48 more a tile where d_summary is given.
- * Not covered: genotype likelihoods, overlapping mates, BAQ, the CG tag, VCF text (deletion events and inserted sequences:
- * bg_bam_indels below). */
+ * Not covered: genotype likelihoods, overlapping mates, BAQ, the CG tag (deletion events and inserted sequences:
+ * bg_bam_indels below; VCF text: bg_vcf_emit below that). */
 enum { BG_SITE_SNV = 0, BG_SITE_DEL = 1, BG_SITE_INS = 2 };
 typedef struct {
     uint32_t flags;             /* 0 */
@@ -1657,7 +1657,7 @@ int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const
  * sums of the strand bits give every event's counts without an atomic.  Scratch is the ctx's: the pileup's, 12 bytes a tile and
  * 88 a raw event plus the sort's own.
  * Not covered: left-alignment or normalisation against the reference, merging adjacent operations, genotype likelihoods,
- * overlapping mates, BAQ, the CG tag, VCF text. */
+ * overlapping mates, BAQ, the CG tag (VCF text: bg_vcf_emit below). */
 typedef struct {
     uint32_t flags;             /* 0 */
     uint16_t require;           /* FLAG bits a kept record has */
@@ -1686,6 +1686,71 @@ int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, con
                   const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
                   bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq, uint64_t seq_cap, uint64_t* event_off,
                   uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad);
+
+/* ---- VCF text from candidate sites and indel events (vcf_emit.hip; the bodies in csrc/vcf_rule.h) ----
+ * One VCF v4.3 data line for every SNV site and every indel event, in one contiguous buffer, formatted from exactly what
+ * bg_bam_sites[_dev] and bg_bam_indels[_dev] leave behind: (d_sites, n_sites) the sites, (d_events, n_events) the events,
+ * (d_seq, n_seq) the inserted bases, (d_contigs, n_contigs, d_names) and (d_text, n_text) the contig table and the index text
+ * those calls take.  Eight columns, no sample columns.
+ * THE RULE.  The bytes are a function of the inputs alone (integer arithmetic; no float, no order of arrival).
+ *   lines      a site of kind BG_SITE_SNV gives one line; sites of kind BG_SITE_DEL and BG_SITE_INS give none (the events name
+ *              them) and are still checked; every event gives one line.  One line per allele: the alleles of a position are
+ *              not joined.
+ *   order      by region, then pos, then the SNVs of a (region, pos) in front of its events, each kind in the order of its
+ *              own list (bg_bam_indels returns an anchor's deletions in front of its insertions, so SNV, DEL, INS).  Both lists
+ *              arrive non-decreasing in (region, pos), as the two calls return them, so a line's index is the element's rank in
+ *              its own list (the sites compacted to the SNVs) plus one binary search in the other list: no sort and no atomic
+ *              places a line.  Regions are not reordered: a sorted file takes ascending regions that do not overlap.
+ *   columns    CHROM POS ID REF ALT QUAL FILTER INFO, separated by tabs, ended by '\n'.  CHROM the contig's name bytes, POS =
+ *              pos + 1, ID, QUAL and FILTER ".".
+ *   R(p)       the reference byte text[contigs[ref].start + p] with a-z folded to A-Z, then: A, C, G, T, N as they are; M, R, W,
+ *              D, H, V -> A; Y, S, B -> C; K -> G; anything else -> N (VCF v4.3: an IUPAC code in REF becomes the first base,
+ *              alphabetically, that it stands for).
+ *   S(b)       an inserted byte of d_seq: A, C, G, T as they are, anything else ('=', N, IUPAC) -> N.
+ *   REF, ALT   SNV: REF = R(pos), ALT = alt.  DEL of len: REF = R(pos) .. R(pos + len), ALT = R(pos).  INS of len: REF = R(pos),
+ *              ALT = R(pos) followed by S of the len bytes at d_seq[seq_off].
+ *   INFO       SNV: DP=<depth>;RO=<ref_count>;AO=<alt_fwd + alt_rev>;SAF=<alt_fwd>;SAR=<alt_rev>;TYPE=snp.  Events: the same
+ *              without RO, with TYPE=del or TYPE=ins.  AO is a 64-bit sum.  Numbers are decimal without padding.
+ *   checks     the combined list holds the sites at 0 .. n_sites - 1 and event j at n_sites + j.  The smallest index of an
+ *              element that fails a check is *first_bad (UINT64_MAX if none); the status is then BG_ERR_INVALID_ARG and nothing
+ *              is written.  ref outside [0, n_contigs); a contig that does not lie inside [0, n_text); pos outside [0,
+ *              contig.len); a kind the list may not hold (sites: SNV, DEL, INS; events: DEL, INS); a non-zero reserved byte; an
+ *              SNV whose ref_base is not the folded text byte, or whose alt is not one of A, C, G, T, or equals ref_base; an
+ *              event with len == 0; a DEL with pos + len >= contig.len (a `$` is never read); an INS with seq_off + len >
+ *              n_seq; an element whose (region, pos) is smaller than its predecessor's in its list.
+ *   sizing     a null d_out with out_cap == 0 sizes the call: *n_lines and *out_bytes, every check still made, nothing written,
+ *              d_line_off included.  out_cap < out_bytes: BG_ERR_OPS_CAP with both totals set and nothing written.
+ *   offsets    d_line_off (optional, n_lines + 1 entries): where every line starts and the last one ends.
+ *   empty      no element at all is BG_OK with 0 lines.  A null array with a count of 0 is accepted; every other null (the
+ *              result pointers included) is BG_ERR_INVALID_ARG, as are flags != 0 and reserved != 0.
+ *   limits     offsets are 64-bit and a line is measured in 64 bits (a deletion may be longer than any staging buffer).
+ *              BG_ERR_TOO_LARGE: 2^32 elements or more, a single line of 2^32 bytes or more (a deletion of 4 Gbp: pos is 32-bit,
+ *              and no contig of a BAM header is that long).
+ * d_out, d_text, d_seq and d_names may sit at any address; d_sites is 4-byte aligned, d_events and d_line_off 8-byte aligned.
+ * ONE read-back with one stream synchronisation (the refused index, the number of lines, the bytes); the sizing call ends
+ * there, the text is then written asynchronously on `stream`.  A line of at most 256 bytes is put together in LDS by eight
+ * lanes and leaves in 16-byte stores where the destination allows; a longer one is formatted in place.  Scratch is the ctx's:
+ * at most 32 bytes an element.  bg_vcf_emit stages host arrays through it (names: up to the last contig's last byte).
+ * bg_vcf_header (host only, no GPU) writes "##fileformat=VCFv4.3\n##source=biogpu\n", one "##contig=<ID=name,length=len>\n" a
+ * contig, an ##INFO line for each of DP, RO, AO, SAF, SAR and TYPE and the "#CHROM ... INFO" line; *out_bytes receives the
+ * length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if out_cap is too small (nothing written).
+ * Not covered: left-alignment or normalisation of indels, joining alleles into multi-allelic lines, genotypes and sample
+ * columns, QUAL and FILTER values, tabix or CSI indexes, BCF, reading VCF. */
+typedef struct {
+    uint32_t flags;             /* 0 */
+    uint32_t reserved;          /* 0 */
+} bg_vcf_params_t;              /* 8 bytes */
+int bg_vcf_header(const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, char* out, uint64_t out_cap,
+                  uint64_t* out_bytes);
+int bg_vcf_emit_dev(bg_ctx* ctx, const bg_vcf_params_t* prm, const bg_bam_site_t* d_sites, uint64_t n_sites,
+                    const bg_bam_indel_t* d_events, uint64_t n_events, const uint8_t* d_seq, uint64_t n_seq,
+                    const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const char* d_names, const uint8_t* d_text,
+                    uint64_t n_text, char* d_out, uint64_t out_cap, uint64_t* d_line_off, uint64_t* n_lines, uint64_t* out_bytes,
+                    uint64_t* first_bad, void* stream);
+int bg_vcf_emit(bg_ctx* ctx, const bg_vcf_params_t* prm, const bg_bam_site_t* sites, uint64_t n_sites,
+                const bg_bam_indel_t* events, uint64_t n_events, const uint8_t* seq, uint64_t n_seq,
+                const bg_sam_contig_t* contigs, uint64_t n_contigs, const char* names, const uint8_t* text, uint64_t n_text,
+                char* out, uint64_t out_cap, uint64_t* line_off, uint64_t* n_lines, uint64_t* out_bytes, uint64_t* first_bad);
 
 /* ---- the reference text from parsed FASTA records (fasta_ingest.hip) --------------------------------------
  * The index text of n_records parsed records (bg_fasta_parse[_dev] above), with the contig table and names bg_sam_emit_batch[_dev] and bg_sam_header
