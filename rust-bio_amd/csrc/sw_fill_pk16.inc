@@ -66,6 +66,34 @@ __device__ __forceinline__ void scan_first_max(int ll, int64_t& v, uint32_t& idx
     }
 }
 
+// v with the lanes of its row of 16 permuted by a DPP control (every lane of the wavefront active)
+template <int CTRL>
+__device__ __forceinline__ pk dpp_row(pk v) {
+    return (pk)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false);
+}
+// Packed first maximum over the LP lanes of a pair, in every lane: each half of v is score | 15 - (lane % 16) with the score a
+// multiple of 16, so the signed packed maximum over a row of 16 lanes keeps the earliest lane of the largest score.  Four
+// DPP steps (lane ^ 1, lane ^ 2, mirror within 8, mirror within 16), no LDS round trip.  LP == 32 has no room for a fifth
+// priority bit in a half: the two rows of 16 are reduced on their own and combined by one more packed maximum in which the
+// lower row's score carries a 1 below the score bits, so it keeps ties; hi gets 16 in the halves the upper row won.
+template <int LP>
+__device__ __forceinline__ pk group_first_max(pk v, int ll, pk& hi) {
+    constexpr pk CLEAN = 0xfff0fff0u, ONE = 0x00010001u;
+    v = pk_max(v, dpp_row<0xb1>(v));   // quad_perm [1, 0, 3, 2]
+    v = pk_max(v, dpp_row<0x4e>(v));   // quad_perm [2, 3, 0, 1]
+    v = pk_max(v, dpp_row<0x141>(v));  // row_half_mirror
+    v = pk_max(v, dpp_row<0x140>(v));  // row_mirror
+    hi = 0;
+    if (LP == 32) {
+        const pk o = (pk)__shfl_xor((int)v, 16);
+        const pk lo_v = ll < 16 ? v : o, up_v = ll < 16 ? o : v;
+        const pk lowwin = nz_mask(pk_max((lo_v & CLEAN) | ONE, up_v & CLEAN) & ONE, ONE);
+        v = bfi(lowwin, lo_v, up_v);
+        hi = ~lowwin & 0x00100010u;
+    }
+    return v;
+}
+
 constexpr int32_t kFloor16 = -2048;  // 'minus infinity' of the 12-bit score range (scaled: 0x8000)
 
 // FAST: the wavefronts whose pairs all end on the last row of a lane (m % R == 0, the usual equal-length
@@ -84,7 +112,7 @@ enum { CZ = 0, CF = 1, CI = 2 };
 // from a fold of a column before n is <= the best cell of the rows above, which the last column's folds offer to (m, n)
 // anyway, with priority, and a gap on top makes it strictly smaller — so no cell of row m needs the candidate, and no
 // Lx[j < n] is ever asked for; the fold of column n itself (over the fill's S(1..m-1, n), before the y-suffix clip:
-// mod.rs:793-796 at j == n) is one more first-maximum scan of the epilogue (sw_epilogue.inc, EPI_FOLD_PRE), which has
+// mod.rs:793-796 at j == n) is one more first maximum of the LF flavours' own last-column epilogue (below), which has
 // those values in hand.  That takes two instructions out of every cell, the fold's carry, Lx and the clip candidate
 // of row m out of every step, and makes every wavefront a "fast" one (row m is nothing special during the fill: one
 // launch).  The local floor 0 (the x-prefix-clip candidate, mod.rs:765-768) comes out of the unsigned saturation of the
@@ -140,7 +168,8 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     // lane's 64 bytes per pair, kTileStride dwords apart: 8-byte writes, 16-byte aligned reads); after it, the
     // packed rows parked for the epilogue
     constexpr int kTileStride = 20;
-    constexpr int kParkDw = 64 * (4 * R + NH + 1), kTileDw = 2 * 64 * kTileStride;  // per wavefront
+    // (LF parks S, Sn, Ly and the last column's cells; the others I and Lx[n] as well)
+    constexpr int kParkDw = LF ? 64 * (3 * R + NH) : 64 * (4 * R + NH + 1), kTileDw = 2 * 64 * kTileStride;  // per wavefront
     constexpr int kWaveDw = kParkDw > kTileDw ? kParkDw : kTileDw;
     __shared__ __align__(16) pk s_lds[4 * kWaveDw];
     pk* const wave_lds = s_lds + (threadIdx.x >> 6) * kWaveDw;  // wavefronts of a block run unsynchronised
@@ -191,6 +220,9 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
     constexpr bool SYMHI = FR == 2 && !(PK16_CELL_KO & 2);    // symbols in the high byte, match term by one saturating subtract
     constexpr bool ROWMAX2 = FR == 2 && !(PK16_CELL_KO & 4);  // row maxima of a two-step trip by one maximum of three
     constexpr int SYM_SH = SYMHI ? 8 : 0;
+    // ceilings of the once-per-wavefront code of the LF flavours (timing only, WRONG results): bit 4 leaves right after the last
+    // tile store (no last-column epilogue), bit 5 starts every row from constants (no col0_cell set-up)
+    constexpr bool KO_EPILOGUE = LF && (PK16_CELL_KO & 16), KO_SETUP = LF && (PK16_CELL_KO & 32);
     // the traceback cells are put together with v_pk_mad_u16; the factors are hidden from the compiler, which
     // otherwise rewrites every multiply-add by a power of two into a shift and an add (two instructions for one)
     pk C16 = dup16(16), C32 = dup16(32), C1024 = dup16(1024);
@@ -265,7 +297,12 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
 
         int32_t fold0;
         uint32_t lx0;
-        col0_fold(sc, m, fold0, lx0);
+        if (KO_SETUP) {
+            fold0 = NEG;
+            lx0 = 0;
+        } else {
+            col0_fold(sc, m, fold0, lx0);
+        }
         // row 0 (mod.rs:678-717), kept by group lane 0.  ROW0_ZERO (yclip_prefix == yclip_suffix == 0): S(0,j) = 0
         // by YCLIP_PREFIX, Sn[0] stays 0 and Ly[0] = n
         int32_t Sn0 = sc.ys;
@@ -310,7 +347,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                 px[r] = packed ? (((uint32_t)(xw0 >> (2 * r)) & 3u) | (((uint32_t)(xw1 >> (2 * r)) & 3u) << 16))
                                : ((uint32_t)x0[i - 1] | ((uint32_t)x1[i - 1] << 16));
                 px[r] <<= SYM_SH;
-                const Col0 c = col0_cell(sc, i, m, fold0);
+                const Col0 c = KO_SETUP ? Col0{0, kFloor16, (uint32_t)TB_XCLIP_PREFIX, (uint32_t)TB_START} : col0_cell(sc, i, m, fold0);
                 Sl[r] = dup16(scl(c.S));
                 Il[r] = dup16(scl(c.I) | K_INS);
                 nib0S |= (uint64_t)c.sbits << (4 * r);
@@ -321,7 +358,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                 }
             }
         }
-        pk diag0 = dup16((pair_ok && rb < m) ? scl(col0_S(sc, rb, m, fold0)) : NEGS);  // S(rb, 0)
+        pk diag0 = dup16((pair_ok && rb < m) ? (KO_SETUP ? 0 : scl(col0_S(sc, rb, m, fold0))) : NEGS);  // S(rb, 0)
         if (FR) {
             // into the frame: column 0 is step ll - 1 of this lane, its diagonal step ll - 2 of row -1.  Exact modular adds, undone
             // when the rows are parked (a lane that computes nothing gets back what it started with); rows past m start at
@@ -334,7 +371,7 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
                 Il[r] += o;
                 Dl[r] = 0;
             }
-            diag0 = fr(off0 - gF) + ((pair_ok && rb < m) ? dup16(scl(col0_S(sc, rb, m, fold0))) : 0u);
+            diag0 = fr(off0 - gF) + ((pair_ok && rb < m) ? dup16((KO_SETUP ? 0 : scl(col0_S(sc, rb, m, fold0)))) : 0u);
         }
 
         pk S_out = FLOORK, I_out = FLOORK, cm_out = FLOORK, ca_out = 0, q_out = 0;
@@ -607,68 +644,189 @@ __device__ __forceinline__ void sw_fill_pk16_body(const SwArgs& a) {
         run_steps(std::integral_constant<int, (FAST && !LF) ? R - 1 : -1>{});
         if (nsteps_w % tsteps) store_tile(nsteps_w - 1);  // the last, partial tile
         if (YS != CI && nsteps_w) merge_rows((nsteps_w - 1) & ~15u);
-
-        // =========== epilogue of the last column (mod.rs:808-843), one pair of the couple at a time ===========
-        // The packed rows are parked in LDS (thread-private slots, stride 64: conflict-free) so that the
-        // epilogue's 64-bit scans do not have to share the register file with them.
-        pk* park = wave_lds + lane;
-        // FR: out of the frame of the lane's last column, step n - 1 + ll (n == 0: the frame of column 0 it started in)
-        const pk offl = FR ? fr(BF + gF * ((int32_t)ll + (int32_t)n - 1)) : 0u;
+        if (KO_EPILOGUE) {  // what the epilogue reads stays computed
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-            park[(0 * R + r) * 64] = FR ? Sl[r] - (offl + (uint32_t)r * GF) : Sl[r];
-            park[(1 * R + r) * 64] = FR ? Il[r] - (offl + (uint32_t)r * GF) : Il[r];
-            park[(2 * R + r) * 64] = SnR[r];
-            park[(3 * R + r) * 64] = Ly[r];
+            for (int r = 0; r < R; r++) asm volatile("" ::"v"(Sl[r]), "v"(Il[r]), "v"(SnR[r]), "v"(Ly[r]));
+#pragma unroll
+            for (int k = 0; k < NH; k++) asm volatile("" ::"v"(hwlast[k]));
+            asm volatile("" ::"v"(lx_n));
+            return;
         }
+
+        if constexpr (LF) {
+            // =========== last column of a local alignment (mod.rs:808-821), both pairs of the couple at once ===========
+            // Only what K2 reads of column n is computed and published (DESIGN.md §4.1): the score, Lx[n] and the S nibble
+            // of (m, n), the row i* the x-suffix clip of (m, n) jumps to (aux[3]; m if it does not) with its S nibble and
+            // Ly, and row 0.  The second pass (mod.rs:825-843) offers max S1(i' < i) + go + ge k with go < 0: strictly below a
+            // value the first pass already offered, so it changes neither (m, n) nor the cell the clip lands on.
+            // Everything stays in the packed 16-bit halves: scores are multiples of 16, the low nibble of a key holds the
+            // priority ("equal keeps the earlier row" == a larger nibble), and one signed packed maximum compares both pairs.
+            const bool nz = n != 0;
+            const int32_t S0fin = nz ? scl(S0n) : 0;
+            const uint32_t sb0fin = nz ? sb0n : (uint32_t)TB_START;
+            const bool has_row0 = pair_ok && ll == 0;
+            pk* park = wave_lds + lane;  // thread-private slots, stride 64: the rows are indexed at run time below
+            // FR: out of the frame of the lane's last column, step n - 1 + ll (n == 0: the frame of column 0 it started in)
+            const pk offl = FR ? fr(BF + gF * ((int32_t)ll + (int32_t)n - 1)) : 0u;
+            // per lane: first maximum over its rows below m (r < mrow) of S(i, n) (the fold the fill did not keep) and of
+            // S1(i) = max(S(i, n), Sn[i]); row r carries priority 14 - r, row 0 of the matrix 15
+            pk KF = FLOORK, KC = FLOORK;
 #pragma unroll
-        for (int k = 0; k < NH; k++) park[(4 * R + k) * 64] = hwlast[k];
-        park[(4 * R + NH) * 64] = lx_n;
-        const int nhalf = (pair_ok && P1 != P0) ? 2 : 1;
-        const int nhalf_w = __any(nhalf == 2) ? 2 : 1;
+            for (int r = 0; r < R; r++) {
+                const pk sl = FR ? Sl[r] - (offl + (uint32_t)r * GF) : Sl[r];
+                park[(0 * R + r) * 64] = sl;
+                park[(1 * R + r) * 64] = SnR[r];
+                park[(2 * R + r) * 64] = Ly[r];
+                if (r < mrow) {
+                    const pk pr = dup16(14 - r);
+                    KF = pk_max(KF, sl | pr);
+                    KC = pk_max(KC, pk_max(sl, SnR[r]) | pr);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NH; k++) park[(3 * R + k) * 64] = hwlast[k];
+            if (has_row0 && m != 0) KC = pk_max(KC, dup16(S0fin) | 0x000f000fu);
+            // across the lanes of the pair: score | 15 - lane, one packed maximum over each row of 16 lanes (LP == 32: the two
+            // rows are combined, the lower one keeps ties, see group_first_max)
+            const pk lprio = dup16(15 - (ll & 15));
+            pk HF, HC;
+            const pk RF = group_first_max<LP>((KF & CLEAN) | lprio, ll, HF), RC = group_first_max<LP>((KC & CLEAN) | lprio, ll, HC);
+            // row m: its owner's S(m, n) and Sn[m] go to every lane of the pair, which all resolve (m, n) the same way
+            const bool own_m = pair_ok && m != 0 && mrow >= 0 && mrow < R;
+            const bool own_m0 = pair_ok && m == 0 && ll == 0;
+            const int mr = own_m ? mrow : 0;
+            pk Sm = park[(0 * R + mr) * 64], Snm = park[(1 * R + mr) * 64];
+            if (!own_m) {  // m == 0: (0, n) is row 0 itself, Sn[0] > S(0, n) never holds (mod.rs:706-714)
+                Sm = dup16(S0fin);
+                Snm = FLOORK;
+            }
+            const int ol = m ? (int)((m - 1) / (uint32_t)R) : 0;
+            Sm = (pk)__shfl((int)Sm, ol, LP);
+            Snm = (pk)__shfl((int)Snm, ol, LP);
+            // in the reference's order: the cell's own candidates against the fold (the fold was there first: it keeps ties),
+            // then rows 0 .. m - 1 of the first loop (strictly greater only), then Sn[m]
+            const pk Fs = RF & CLEAN, Cs = RC & CLEAN;
+            const pk v1 = nz ? pk_max(Sm, Fs) : Sm;
+            const pk foldwin = nz ? ~nz_mask(v1 ^ Fs, ONE) : 0u;
+            const pk v2 = pk_max(v1, Cs);
+            const pk c1win = nz_mask(v2 ^ v1, ONE);
+            const pk v3 = pk_max(v2, Snm);
+            const pk ywin = nz_mask(v3 ^ v2, ONE);
+            const pk xswon = foldwin | c1win;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                if (!pair_ok || (h == 1 && P1 == P0)) continue;  // (A, A) / (B, B): one record
+                const uint32_t hs = 16u * (uint32_t)h;
+                int32_t* aux = h ? aux1 : aux0;
+                int32_t* gLy = aux + geo.off_Ly();
+                uint8_t* gBits = (uint8_t*)(aux + geo.off_bits());
+                const bool xs = (xswon >> hs) & 1u, c1 = (c1win >> hs) & 1u, yw = (ywin >> hs) & 1u;
+                // the S nibble of (rb + r + 1, n) as the fill left it
+                auto fillnib = [&](int r) -> uint32_t {
+                    if (!nz) return (uint32_t)(nib0S >> (4 * r)) & 15u;
+                    const uint32_t mv = (park[(3 * R + r / 3) * 64] >> (hs + 5u * (uint32_t)(r % 3) + 1u)) & 7u;
+                    return s_nibble_of_code(mv == 0 ? (uint32_t)C_XP : mv);
+                };
+                // the lane that holds i*: its own key knows the row
+                const uint32_t wl = 15u - (((c1 ? RC : RF) >> hs) & 15u) + (((c1 ? HC : HF) >> hs) & 16u);
+                if (xs && (uint32_t)ll == wl) {
+                    const uint32_t code = ((c1 ? KC : KF) >> hs) & 15u;
+                    uint32_t istar = 0;  // code 15: row 0, whose entries lane 0 writes below
+                    if (code != 15u) {
+                        const int r = min(max(14 - (int)code, 0), R - 1);
+                        istar = rb + (uint32_t)r + 1;
+                        const int32_t sl = (int32_t)(int16_t)(park[(0 * R + r) * 64] >> hs);
+                        const int32_t sn = (int32_t)(int16_t)(park[(1 * R + r) * 64] >> hs);
+                        gBits[istar] = (uint8_t)(sn > sl ? (uint32_t)TB_YCLIP_SUFFIX : fillnib(r));  // mod.rs:812-815
+                        gLy[istar] = (int32_t)((park[(2 * R + r) * 64] >> hs) & 0xffffu);
+                    }
+                    aux[2] = (int32_t)(m - istar);
+                    aux[3] = (int32_t)istar;
+                }
+                if (own_m || own_m0) {
+                    aux[1] = (int32_t)(int16_t)(v3 >> hs) >> SH;  // exact: every scaled value is a multiple of 16
+                    const uint32_t sbm = yw ? (uint32_t)TB_YCLIP_SUFFIX : xs ? (uint32_t)TB_XCLIP_SUFFIX : own_m ? fillnib(mr) : sb0fin;
+                    gBits[m] = (uint8_t)sbm;
+                    if (own_m) gLy[m] = (int32_t)((park[(2 * R + mr) * 64] >> hs) & 0xffffu);
+                    if (!xs) {
+                        uint32_t istar = m;
+                        if (sbm == (uint32_t)TB_XCLIP_SUFFIX) {  // n == 0, m >= 2: column 0's own fold (mod.rs:658-661) jumps to row m - lx0
+                            istar = m - lx0;
+                            gBits[istar] = (uint8_t)col0_cell(sc, istar, m, fold0).sbits;
+                            gLy[istar] = (int32_t)n;  // mod.rs:667-670
+                        }
+                        aux[2] = (int32_t)lx0;
+                        aux[3] = (int32_t)istar;
+                    }
+                }
+                if (has_row0) {
+                    gLy[0] = (int32_t)Ly0;
+                    if (m != 0) gBits[0] = (uint8_t)(sb0fin | (TB_START << 4));
+                }
+            }
+        } else {
+            // =========== epilogue of the last column (mod.rs:808-843), one pair of the couple at a time ===========
+            // The packed rows are parked in LDS (thread-private slots, stride 64: conflict-free) so that the
+            // epilogue's 64-bit scans do not have to share the register file with them.
+            pk* park = wave_lds + lane;
+            // FR: out of the frame of the lane's last column, step n - 1 + ll (n == 0: the frame of column 0 it started in)
+            const pk offl = FR ? fr(BF + gF * ((int32_t)ll + (int32_t)n - 1)) : 0u;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                park[(0 * R + r) * 64] = FR ? Sl[r] - (offl + (uint32_t)r * GF) : Sl[r];
+                park[(1 * R + r) * 64] = FR ? Il[r] - (offl + (uint32_t)r * GF) : Il[r];
+                park[(2 * R + r) * 64] = SnR[r];
+                park[(3 * R + r) * 64] = Ly[r];
+            }
+#pragma unroll
+            for (int k = 0; k < NH; k++) park[(4 * R + k) * 64] = hwlast[k];
+            park[(4 * R + NH) * 64] = lx_n;
+            const int nhalf = (pair_ok && P1 != P0) ? 2 : 1;
+            const int nhalf_w = __any(nhalf == 2) ? 2 : 1;
 #pragma unroll 1
-        for (int h = 0; h < nhalf_w; h++) {
-            if (h >= nhalf) continue;  // the shuffles below only pair lanes of one group, whose nhalf agree
-            const uint32_t hs = 16u * (uint32_t)h;
-            int32_t* aux = h ? aux1 : aux0;
-            int32_t* gLy = aux + geo.off_Ly();
-            uint8_t* gBits = (uint8_t*)(aux + geo.off_bits());
-            const uint32_t strip = 0;
-            // unpacked (sign-extended, still scaled by 16) views of this pair's half
-            struct HalfS {
-                const pk* p;
-                uint32_t hs;
-                __device__ int32_t operator[](int r) const { return (int32_t)(int16_t)(p[r * 64] >> hs); }
-            };
-            struct HalfU {
-                const pk* p;
-                uint32_t hs;
-                __device__ uint32_t operator[](int r) const { return (p[r * 64] >> hs) & 0xffffu; }
-            };
-            int32_t Sl_u[R];  // the epilogue overwrites S(i, n)
+            for (int h = 0; h < nhalf_w; h++) {
+                if (h >= nhalf) continue;  // the shuffles below only pair lanes of one group, whose nhalf agree
+                const uint32_t hs = 16u * (uint32_t)h;
+                int32_t* aux = h ? aux1 : aux0;
+                int32_t* gLy = aux + geo.off_Ly();
+                uint8_t* gBits = (uint8_t*)(aux + geo.off_bits());
+                const uint32_t strip = 0;
+                // unpacked (sign-extended, still scaled by 16) views of this pair's half
+                struct HalfS {
+                    const pk* p;
+                    uint32_t hs;
+                    __device__ int32_t operator[](int r) const { return (int32_t)(int16_t)(p[r * 64] >> hs); }
+                };
+                struct HalfU {
+                    const pk* p;
+                    uint32_t hs;
+                    __device__ uint32_t operator[](int r) const { return (p[r * 64] >> hs) & 0xffffu; }
+                };
+                int32_t Sl_u[R];  // the epilogue overwrites S(i, n)
 #pragma unroll
-            for (int r = 0; r < R; r++) Sl_u[r] = (int32_t)(int16_t)(park[r * 64] >> hs);
-            const HalfS Il_u{park + 1 * R * 64, hs}, Sn_u{park + 2 * R * 64, hs};
-            const HalfU Ly_u{park + 3 * R * 64, hs};
-            const uint32_t lx_n_u = (park[(4 * R + NH) * 64] >> hs) & 0xffffu;
-            int64_t e_carry = INT64_MIN;
-            uint32_t sbf_carry = TB_START, sb2_carry = TB_START;
-            int64_t c1v = INT64_MIN, c2v = INT64_MIN;
-            uint32_t c1i = 0, c2i = 0;
-            auto cell_of = [&](int r) -> uint32_t {  // K1's bit order: move | I extends << 3 | D extends << 4
-                const uint32_t c = (park[(4 * R + r / 3) * 64] >> (hs + 5 * (r % 3))) & 31u;
-                const uint32_t mv = (c >> 1) & 7u;
-                return ((LF && mv == 0) ? (uint32_t)C_XP : mv) | ((c & 1u) << 3) | (c & 16u);
-            };
-            {
-                constexpr bool EPI_FOLD_PRE = LF;  // the fill kept no fold: column n's comes from here
-                // the names the shared body expects
-                int32_t(&Sl)[R] = Sl_u;
-                const HalfS& Il = Il_u;
-                const HalfS& Sn = Sn_u;
-                const HalfU& Ly = Ly_u;
-                const uint32_t lx_n = lx_n_u;
+                for (int r = 0; r < R; r++) Sl_u[r] = (int32_t)(int16_t)(park[r * 64] >> hs);
+                const HalfS Il_u{park + 1 * R * 64, hs}, Sn_u{park + 2 * R * 64, hs};
+                const HalfU Ly_u{park + 3 * R * 64, hs};
+                const uint32_t lx_n_u = (park[(4 * R + NH) * 64] >> hs) & 0xffffu;
+                int64_t e_carry = INT64_MIN;
+                uint32_t sbf_carry = TB_START, sb2_carry = TB_START;
+                int64_t c1v = INT64_MIN, c2v = INT64_MIN;
+                uint32_t c1i = 0, c2i = 0;
+                auto cell_of = [&](int r) -> uint32_t {  // K1's bit order: move | I extends << 3 | D extends << 4
+                    const uint32_t c = (park[(4 * R + r / 3) * 64] >> (hs + 5 * (r % 3))) & 31u;
+                    const uint32_t mv = (c >> 1) & 7u;
+                    return ((LF && mv == 0) ? (uint32_t)C_XP : mv) | ((c & 1u) << 3) | (c & 16u);
+                };
+                {
+                    constexpr bool EPI_FOLD_PRE = false;  // (K1's LF flavour; K1p's has the epilogue above)
+                    // the names the shared body expects
+                    int32_t(&Sl)[R] = Sl_u;
+                    const HalfS& Il = Il_u;
+                    const HalfS& Sn = Sn_u;
+                    const HalfU& Ly = Ly_u;
+                    const uint32_t lx_n = lx_n_u;
 #include "sw_epilogue.inc"
+                }
             }
         }
     };

@@ -100,7 +100,10 @@ enum : uint32_t {
 
 // aux record of one pair (int32 words):
 //   [0] S nibble of (m,0)   [1] score = S[n%2][m] after the epilogue   [2] Lx[n] after the epilogue
+//   [3] TBF_K1P_LF only: i*, the row the x-suffix clip of (m,n) jumps to (m if it does not clip); unused otherwise
 //   Ly[m_cap+1]  Lx[n_cap+1]  colBits[m_cap+1 bytes]: (S nibble | I nibble << 4) of column n
+// TBF_K1P_LF publishes of column n only what a local traceback reads: Ly and the S nibble of rows 0, i* and m
+// (no I nibbles); the other entries hold whatever an earlier batch left there, and K2 refuses to read them.
 struct SwGeom {
     uint32_t lp, r, nsteps, nstrips, m_cap, n_cap, aux_stride;
     uint32_t tb_fmt;    // TBF_*

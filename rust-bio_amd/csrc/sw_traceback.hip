@@ -165,6 +165,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
             }
         }
         have_c = false;
+        // TBF_K1P_LF publishes of column n the S nibbles and Ly of rows 0, i* (aux[3]) and m only, and no I nibbles
+        // (sw_kernels.h).  A walk that asks for anything else there — layer I or D in column n, the entry of another row —
+        // would decode what an earlier batch left in the scratch: it ends with BG_ERR_TRACEBACK.  No local alignment does.
+        if (geo.tb_fmt == TBF_K1P_LF && j == n) {
+            const bool reads_row = layer == TB_XCLIP_SUFFIX || layer == TB_YCLIP_SUFFIX || (layer == TB_YCLIP_PREFIX && n == 0);
+            const uint32_t row = layer == TB_XCLIP_SUFFIX ? i - lxn : i;  // the row whose column-n entry this move reads
+            if (layer == TB_INS || layer == TB_DEL || (reads_row && row <= m && row != 0 && row != m && row != (uint32_t)aux[3])) {
+                status = BG_ERR_TRACEBACK;
+                break;
+            }
+        }
         uint32_t next;
         switch (layer) {
             case TB_INS:
