@@ -113,8 +113,9 @@ const char* bg_last_error(void); /* text of the last HIP failure on this thread 
  *                      text does not depend on it)
  *   fq_emit_mode       bg_fastq_emit_dev's text pass: 1 byte stores straight to the output, 2 lines staged in LDS and stored 16
  *                      bytes wide (0 = default, which is 1; tests, A/B: the text does not depend on it)
- *   indels_stop_after  bg_bam_indels_dev returns BG_OK with no event after 1 its count pass, 2 its emit pass, 3 its sort (0 = default:
- *                      it runs through; A/B only: timing tells the passes apart by differences of whole calls)
+ *   indels_stop_after  bg_bam_indels_dev and bg_bam_indels_left_dev return BG_OK with no event after 1 the count pass, 2 the emit
+ *                      pass, 3 the sort (0 = default: they run through; A/B only: timing tells the passes apart by differences
+ *                      of whole calls)
  *   sa_chunk_symbols   suffixes sorted per pass of round 0 of bg_suffix_array_dev[64] (0 = derived from free device memory;
  *                      tests use small values so that short texts take several passes)
  *   band_budget_gb     traceback + aux bytes per scratch set of the banded pipeline, in GB (0 = default: 40, and never more
@@ -1578,7 +1579,7 @@ int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, con
  * region's summary is parked in scratch and a pass of its own sums a region's tiles (integer sums and maxima: exact, whatever
  * the order).  Scratch is the ctx's: the pileup's and 12 bytes a tile, 48 more a tile where d_summary is given.
  * Not covered: genotype likelihoods, overlapping mates, BAQ, the CG tag (deletion events and inserted sequences:
- * bg_bam_indels below; VCF text: bg_vcf_emit below that). */
+ * bg_bam_indels below, left-aligned against the reference: bg_bam_indels_left behind it; VCF text: bg_vcf_emit below that). */
 enum { BG_SITE_SNV = 0, BG_SITE_DEL = 1, BG_SITE_INS = 2 };
 typedef struct {
     uint32_t flags;             /* 0 */
@@ -1656,8 +1657,8 @@ int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const
  * key (the comparator reads the inserted codes from the records: exact at any length, no hashing), heads of runs and prefix
  * sums of the strand bits give every event's counts without an atomic.  Scratch is the ctx's: the pileup's, 12 bytes a tile and
  * 88 a raw event plus the sort's own.
- * Not covered: left-alignment or normalisation against the reference, merging adjacent operations, genotype likelihoods,
- * overlapping mates, BAQ, the CG tag (VCF text: bg_vcf_emit below). */
+ * Not covered: left-alignment against the reference (bg_bam_indels_left below does it), merging adjacent operations, genotype
+ * likelihoods, overlapping mates, BAQ, the CG tag (VCF text: bg_vcf_emit below). */
 typedef struct {
     uint32_t flags;             /* 0 */
     uint16_t require;           /* FLAG bits a kept record has */
@@ -1686,6 +1687,67 @@ int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, con
                   const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
                   bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq, uint64_t seq_cap, uint64_t* event_off,
                   uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad);
+
+/* ---- indel events, left-aligned against the reference (bam_pileup.hip; the bodies in csrc/bam_indels_left_rule.h) ----
+ * bg_bam_indels counts an event exactly as the records spell it, and in a homopolymer or a tandem repeat one indel has as many
+ * spellings as the repeat has positions: its records then fall apart into shares that are judged alone.  bg_bam_indels_left
+ * shifts every raw event to the left against the reference text BEFORE events are merged, so that the spellings of one indel
+ * meet in one event.  The arguments are those of bg_bam_indels[_dev] with (d_text, n_text), the index text bg_bam_sites reads,
+ * behind n_contigs; the outputs are those of bg_bam_indels[_dev], and bg_vcf_emit[_dev] takes them unchanged.
+ * THE RULE.  The result is a function of the inputs alone (integer arithmetic; no float, no order of arrival).
+ *   shared     slots, checks, order, kept records, regions, the raw events of a record and every refusal are those of
+ *              bg_bam_indels, word for word (the same bodies): an operation with r == pos or of length 0 is dropped, and so are
+ *              the insertions of a record without bases.  The regions' contigs are held against the text as bg_bam_sites holds
+ *              them: contig.start + contig.len > n_text is a region error (BG_ERR_INVALID_ARG, *first_bad = UINT64_MAX); a null
+ *              d_text with n_text > 0 is BG_ERR_INVALID_ARG, as are flags != 0, reserved != 0 and min_alt_permille > 1000.
+ *   text       F(p) = text[contigs[ref].start + p] with a-z folded to A-Z.  A text byte or an inserted byte is a BASE only if
+ *              it is A, C, G or T.  Only positions pos < p < contig.len of the record's contig are read: a `$` never is.
+ *   deletion   a raw deletion (a, n) deletes a + 1 .. a + n.  One step takes a to a - 1.  A step is allowed while fewer than
+ *              max_shift steps have been taken, a > pos (the new anchor stays >= pos: an event never moves in front of the
+ *              record that carries it), a + n < contig.len, and F(a) == F(a + n) is a base.
+ *   insertion  a raw insertion (a, n, s[0 .. n)): s is the 4-bit codes read as ASCII through "=ACMGRSVTWYHKDBN".  Step j (j =
+ *              0, 1, ...) is allowed while j < max_shift, a - j > pos, and c_j == F(a - j) is a base, where c_j = s[n - 1 - j]
+ *              for j < n and F(a - j + n) beyond.  With k steps taken the anchor is a' = a - k and byte i of the sequence is
+ *              F(a' + 1 + i) for i < min(k, n) and s[i - k] behind (which is s rotated right by k mod n: every step compared
+ *              the text byte that enters with the byte that leaves; no rotated copy is ever materialised).
+ *   after      everything else is bg_bam_indels' rule applied to the shifted events: an event belongs to every region whose
+ *              [beg, end) holds the SHIFTED anchor; shifted events with equal (anchor, kind, len and every byte of the shifted
+ *              sequence) are ONE event; counts per strand; depth is bg_bam_sites' depth of the shifted anchor under min_baseq;
+ *              the four conditions; the order (region, anchor, DEL before INS, len, then the shifted sequence as 4-bit codes
+ *              left to right, a text base taking the code of its letter); seq_off, sizing, BG_ERR_OPS_CAP, limits and
+ *              alignment requirements.
+ *   therefore  max_shift == 0 gives the bytes of bg_bam_indels[_dev] wherever the text check passes; UINT32_MAX never binds.
+ *              Two operations of one record that normalise to one event count twice.  A record that begins inside a repeat
+ *              stops at its own pos, so its event may stay apart from the others (GATK's per-read left-alignment behaves the
+ *              same way).  alt <= depth may fail only as it can in bg_bam_indels.
+ * d_text may sit at any address.  Read-backs, passes and scratch (88 bytes a raw event: k rides in a word that was spare) are
+ * those of bg_bam_indels_dev.  The two tile passes walk a candidate record's operations beyond the tile's end, as far as
+ * max_shift allows, because an event anchored behind a tile may land in it; a' >= pos is what keeps a tile's candidates (the
+ * records that overlap it) complete.  A long record's later operations are therefore shifted again by every tile it spans.
+ * Not covered: merging adjacent operations, trimming shared bases, joining alleles, shifting in front of a record's pos. */
+typedef struct {
+    uint32_t flags;             /* 0 */
+    uint16_t require;           /* FLAG bits a kept record has */
+    uint16_t exclude;           /* FLAG bits a kept record lacks */
+    uint8_t min_mapq;           /* a kept record has mapq >= this */
+    uint8_t min_baseq;          /* enters the depth only, never an event */
+    uint16_t reserved;          /* 0 */
+    uint32_t min_depth;         /* a kept event's shifted anchor has depth >= this */
+    uint32_t min_alt;           /* a kept event has alt >= max(this, 1) */
+    uint32_t min_alt_permille;  /* ... and alt * 1000 >= this * depth; at most 1000 */
+    uint32_t min_alt_strand;    /* ... and alt_fwd, alt_rev >= this */
+    uint32_t max_shift;         /* the steps an event may take; 0: none (bg_bam_indels' events), UINT32_MAX: no limit */
+} bg_bam_indels_left_t;         /* 32 bytes: bg_bam_indels_t, then max_shift */
+int bg_bam_indels_left_dev(bg_ctx* ctx, const bg_bam_indels_left_t* prm, uint64_t n_slots, const uint8_t* d_recs,
+                           const uint64_t* d_off, const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const uint8_t* d_text,
+                           uint64_t n_text, const bg_bam_region_t* d_regions, uint64_t n_regions, bg_bam_indel_t* d_events,
+                           uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events,
+                           uint64_t* n_seq, uint64_t* first_bad, void* stream);
+int bg_bam_indels_left(bg_ctx* ctx, const bg_bam_indels_left_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
+                       const bg_sam_contig_t* contigs, uint64_t n_contigs, const uint8_t* text, uint64_t n_text,
+                       const bg_bam_region_t* regions, uint64_t n_regions, bg_bam_indel_t* events, uint64_t events_cap,
+                       uint8_t* seq, uint64_t seq_cap, uint64_t* event_off, uint64_t* n_events, uint64_t* n_seq,
+                       uint64_t* first_bad);
 
 /* ---- VCF text from candidate sites and indel events (vcf_emit.hip; the bodies in csrc/vcf_rule.h) ----
  * One VCF v4.3 data line for every SNV site and every indel event, in one contiguous buffer, formatted from exactly what
@@ -1734,7 +1796,8 @@ int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, con
  * bg_vcf_header (host only, no GPU) writes "##fileformat=VCFv4.3\n##source=biogpu\n", one "##contig=<ID=name,length=len>\n" a
  * contig, an ##INFO line for each of DP, RO, AO, SAF, SAR and TYPE and the "#CHROM ... INFO" line; *out_bytes receives the
  * length, out == NULL with out_cap == 0 sizes, BG_ERR_OPS_CAP if out_cap is too small (nothing written).
- * Not covered: left-alignment or normalisation of indels, joining alleles into multi-allelic lines, genotypes and sample
+ * Not covered: left-alignment of indels (bg_bam_indels_left hands over events that are left-aligned already; the writer
+ * shifts nothing), trimming of shared bases, joining alleles into multi-allelic lines, genotypes and sample
  * columns, QUAL and FILTER values, tabix or CSI indexes, BCF, reading VCF. */
 typedef struct {
     uint32_t flags;             /* 0 */

@@ -207,6 +207,9 @@ assert BAM_INDELS_DTYPE.itemsize == 28, BAM_INDELS_DTYPE.itemsize
 BAM_INDEL_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<i4"), ("region", "<u4"), ("kind", "u1"), ("reserved", "u1", (3,)), ("len", "<u4"), ("depth", "<u4"),
                             ("alt_fwd", "<u4"), ("alt_rev", "<u4"), ("seq_off", "<u8")])
 assert BAM_INDEL_DTYPE.itemsize == 40, BAM_INDEL_DTYPE.itemsize
+# bg_bam_indels_left_t (bg_bam_indels_left[_dev]): bg_bam_indels_t, then max_shift
+BAM_INDELS_LEFT_DTYPE = np.dtype(BAM_INDELS_DTYPE.descr + [("max_shift", "<u4")])
+assert BAM_INDELS_LEFT_DTYPE.itemsize == 32, BAM_INDELS_LEFT_DTYPE.itemsize
 # bg_vcf_params_t (bg_vcf_emit[_dev])
 VCF_PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("reserved", "<u4")])
 assert VCF_PARAMS_DTYPE.itemsize == 8, VCF_PARAMS_DTYPE.itemsize
@@ -266,7 +269,7 @@ SYMBOLS = ["bg_device_count", "bg_init", "bg_free", "bg_strerror", "bg_last_erro
            "bg_bgzf_blocks", "bg_bgzf_blocks_dev", "bg_bgzf_inflate", "bg_bgzf_inflate_dev",
            "bg_bam_header_parse", "bg_bam_records", "bg_bam_records_dev", "bg_bam_reads", "bg_bam_reads_dev",
            "bg_bam_sort_keys", "bg_bam_sort_keys_dev", "bg_bam_index_blocks", "bg_bam_index_blocks_dev",
-           "bg_bam_pileup", "bg_bam_pileup_dev", "bg_bam_sites", "bg_bam_sites_dev", "bg_bam_indels", "bg_bam_indels_dev",
+           "bg_bam_pileup", "bg_bam_pileup_dev", "bg_bam_sites", "bg_bam_sites_dev", "bg_bam_indels", "bg_bam_indels_dev", "bg_bam_indels_left", "bg_bam_indels_left_dev",
            "bg_vcf_header", "bg_vcf_emit", "bg_vcf_emit_dev",
            "bg_fasta_parse", "bg_fasta_parse_dev", "bg_fasta_reference", "bg_fasta_reference_dev",
            "bg_pack2_dev", "bg_unpack2_dev", "bg_fm_pattern_codes", "bg_fm_backward_search_packed_dev",
@@ -468,6 +471,8 @@ def lib():
         L.bg_bam_sites.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
         L.bg_bam_indels_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_bam_indels.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.bg_bam_indels_left_dev.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+        L.bg_bam_indels_left.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.bg_vcf_header.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
         L.bg_vcf_emit_dev.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
         L.bg_vcf_emit.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]

@@ -782,6 +782,69 @@ def indels_bam(data, regions, ctx=None, **params):
     return indels_arrays(stream, off, contigs, reg, ctx=ctx, **params)
 
 
+def indels_left_params(max_shift=0xFFFFFFFF, **thresholds):
+    """bg_bam_indels_left_t: `indels_params` and the steps a raw event may take to the left (0: none, 0xFFFFFFFF: no limit)"""
+    p = np.zeros(1, dtype=_lib.BAM_INDELS_LEFT_DTYPE)
+    p.view(np.uint8)[:28] = indels_params(**thresholds).view(np.uint8)
+    p["max_shift"] = max_shift
+    return p
+
+
+def indels_left_arrays(stream, off, contigs, text, regions, ctx=None, **params):
+    """bg_bam_indels_left, host buffers: `indels_arrays` with every raw event shifted to the left against the index text `text`
+    (the one `sites_arrays` takes) before events are merged, so that the spellings of one indel inside a repeat are one event.
+    params: those of `indels_left_params`.  Returns what `indels_arrays` returns; the anchors are the shifted ones."""
+    ctx = ctx or _lib.default_context()
+    src = _lib.as_u8(stream)
+    src = src if len(src) else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1 if len(off) else 0
+    table = np.ascontiguousarray(contigs.table)
+    ref_text = _lib.as_u8(text)
+    reg = pileup_regions(regions)
+    prm = indels_left_params(**params)
+    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(events, cap, seq, seq_cap, event_off):
+        return _lib.lib().bg_bam_indels_left(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None,
+                                             table.ctypes.data if len(table) else None, len(table), ref_text.ctypes.data if len(ref_text) else None,
+                                             len(ref_text), reg.ctypes.data if len(reg) else None, len(reg), events, cap, seq, seq_cap, event_off,
+                                             C.byref(total), C.byref(n_seq), C.byref(bad))
+    _pileup_check(call(None, 0, None, 0, None), "bg_bam_indels_left", bad)
+    events = np.zeros(max(total.value, 1), dtype=INDEL_DTYPE)
+    seq = np.zeros(max(n_seq.value, 1), dtype=np.uint8)
+    event_off = np.zeros(len(reg) + 1, dtype=np.uint64)
+    _pileup_check(call(events.ctypes.data, len(events), seq.ctypes.data, len(seq), event_off.ctypes.data), "bg_bam_indels_left", bad)
+    return events[:total.value], seq[:n_seq.value], event_off
+
+
+def indels_left_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_text, n_text, d_regions, n_regions, d_events=0, events_cap=0, d_seq=0, seq_cap=0,
+                    d_event_off=0, stream=0, ctx=None, **params):
+    """bg_bam_indels_left_dev: `indels_dev` with (d_text, n_text) behind n_contigs and `indels_left_params`; sizing, the returned
+    totals and the errors are `indels_dev`'s."""
+    ctx = ctx or _lib.default_context()
+    prm = indels_left_params(**params)
+    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.lib().bg_bam_indels_left_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_text or None, n_text,
+                                           d_regions or None, n_regions, d_events or None, events_cap, d_seq or None, seq_cap, d_event_off or None,
+                                           C.byref(total), C.byref(n_seq), C.byref(bad), stream)
+    try:
+        _pileup_check(rc, "bg_bam_indels_left_dev", bad)
+    except _lib.BiogpuError as e:
+        e.totals = (int(total.value), int(n_seq.value))
+        raise
+    return int(total.value), int(n_seq.value)
+
+
+def indels_left_bam(data, reference, regions, ctx=None, **params):
+    """The left-aligned indel events of a coordinate-sorted BAM file (bytes) against `reference`, FASTA text or a ready index
+    text, as `sites_bam` takes it: `read_bam`, then `indels_left_arrays`.  Returns (events, seq, event_off)."""
+    _, contigs, stream, off = read_bam(data, ctx=ctx)
+    reg = resolve_regions(contigs, regions)
+    text = _reference_text(reference, contigs, ctx)
+    return indels_left_arrays(stream, off, contigs, text, reg, ctx=ctx, **params)
+
+
 def indel_sequences(events, seq):
     """the inserted strings of `events` (bytes each; b"" for a deletion)"""
     raw = _lib.as_u8(seq).tobytes()

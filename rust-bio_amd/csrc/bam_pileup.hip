@@ -25,6 +25,9 @@
 // reads and drops, an operation's length and the inserted bases: a count pass and an emit pass over the tiles leave the raw
 // events in scratch, a merge sort orders them by the full key, heads of runs and prefix sums of the strand bits make them events
 // (the steps are listed at the entry point).
+// bg_bam_indels_left[_dev] (the bodies in bam_indels_left_rule.h) is that call with a shift of every raw event against the
+// reference text between the walk and the window (inl_tile_kernel), the sort and the placement through the shifted codes; its
+// merge sort is instantiated in bam_indels_left_sort.hip.
 #include <algorithm>
 
 #include <rocprim/device/device_merge_sort.hpp>
@@ -35,9 +38,14 @@
 #include "bam_pileup_rule.h"
 #include "bam_sites_rule.h"
 #include "bam_indels_rule.h"
+#include "bam_indels_left_rule.h"
 
 static_assert(sizeof(bg_bam_region_t) == 12 && sizeof(bg_bam_pileup_t) == 12, "the boundary's structs");
 static_assert(2 * BG_PILEUP_COLS * BG_PILEUP_TILE * 4 * 2 <= 160 * 1024, "two workgroups of the 16-column form must fit a CU's LDS");
+
+// bam_indels_left_sort.hip: the merge sort of the left-aligned raw events by inl_cmp, kept out of this file so that the kernels of
+// bg_bam_indels_dev's sort are compiled as they were (the reason is written there)
+int inl_sort_raw(void* d_tmp, size_t tmp_bytes, const ind_raw_t* raw, const uint8_t* recs, const uint64_t* off, uint32_t* order, uint64_t n, hipStream_t st);
 
 namespace {
 
@@ -399,6 +407,100 @@ __global__ __launch_bounds__(256) void ind_region_off_kernel(uint64_t n_regions,
     event_off[r] = v;
 }
 
+// ---- indel events, left-aligned --------------------------------------------------------------------------------------------
+struct InlArgs {
+    const uint8_t* text;
+    uint32_t max_shift;
+};
+
+// ind_tile_kernel with the shift between the walk and the window: one workgroup per tile, one thread per candidate record.
+// A thread walks its record's operations from t0 on (inl_walk: not only up to t1, an event anchored behind the tile may land in
+// it), shifts every raw event against the contig's text and keeps the one whose SHIFTED anchor a' lies in [t0, t1).  The
+// candidate range [lo, hi) of the tile is still complete, and that is what the rule's bound a' >= pos is for: a record whose
+// event lands in the tile has pos <= a' < t1 and end > a >= a' >= t0, so it overlaps the tile and lies in front of hi and not in
+// front of lo.  The first step fails for most events, and it is the first thing the shift tests (two byte loads).  The emit pass
+// takes the depth of a' from the tile's counters; k rides in the raw event's reserved word.
+template <bool EMIT>
+__global__ __launch_bounds__(kThreads) void inl_tile_kernel(const PlpArgs a, const PlpWork w, const IndWork x, const InlArgs L) {
+    __shared__ uint32_t cnt[EMIT ? BG_PILEUP_COLS * BG_PILEUP_TILE : 1];
+    __shared__ uint64_t range[2];
+    __shared__ uint32_t wave_sum[kWaves];
+    __shared__ uint32_t next;
+    uint64_t first = 0;
+    uint32_t room = 0;
+    if (EMIT) {
+        first = x.tile_raw_off[blockIdx.x];
+        room = (uint32_t)(x.tile_raw_off[blockIdx.x + 1] - first);
+        if (!room) return;  // (uniform)
+    }
+    const plp_tile_t t = plp_tile(blockIdx.x, a.regions, a.n_regions, w.tile_off, w.row_off);
+    if (EMIT) {
+        plp_count_tile<BG_PILEUP_COLS>(cnt, range, a, w, t);
+        if (threadIdx.x == 0) next = 0;
+    } else {
+        if (threadIdx.x == 0) range[0] = plp_lo(w.end_max, a.n, t);
+        if (threadIdx.x == 64) range[1] = plp_hi(w.pos_max, a.n, t);
+    }
+    __syncthreads();
+    const uint64_t lo = range[0], hi = range[1];
+    const bg_sam_contig_t contig = a.contigs[t.ref];
+    const uint8_t* text = L.text + contig.start;
+    uint32_t mine = 0;
+    for (uint64_t s = lo + threadIdx.x; s < hi; s += kThreads) {
+        if (!w.kept[s]) continue;
+        const uint8_t* rec = a.recs + a.off[s];
+        const uint32_t flag = bai_get16(rec + 18);
+        inl_walk(rec, t.ref, t.t0, t.t1, L.max_shift, [&](uint32_t kind, uint32_t anchor, uint32_t len, uint32_t q, int64_t pos) {
+            const uint32_t k = kind == BG_SITE_DEL ? inl_shift_del(text, (int64_t)contig.len, pos, anchor, len, L.max_shift)
+                                                   : inl_shift_ins(text, pos, anchor, len, ind_seq_of(rec), q, L.max_shift);
+            const int64_t at = (int64_t)anchor - k;
+            if (at < t.t0 || at >= t.t1) return;
+            if (EMIT) {
+                const uint32_t place = atomicAdd(&next, 1u);
+                if (place < room) {
+                    ind_raw_t e = ind_raw(blockIdx.x, kind, (uint32_t)at, len, q, flag, ind_depth(cnt, (uint32_t)(at - t.t0)), s);
+                    e.reserved = k;
+                    x.raw[first + place] = e;
+                }
+            } else {
+                mine++;
+            }
+        });
+    }
+    if (EMIT) return;
+    for (int d = 32; d; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if (threadIdx.x % 64 == 0) wave_sum[threadIdx.x / 64] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t k = 0; k < kWaves; k++) all += wave_sum[k];
+        x.tile_raw[blockIdx.x] = all;
+    }
+}
+
+// ind_head_kernel and ind_place_kernel through the shifted comparison and the shifted bytes
+__global__ __launch_bounds__(256) void inl_head_kernel(uint64_t n_raw, const PlpArgs a, const IndWork x) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_raw) return;
+    const ind_raw_t e = x.raw[x.order[i]];
+    x.head[i] = i == 0 || inl_cmp(x.raw[x.order[i - 1]], e, a.recs, a.off) != 0;
+    x.rev[i] = ind_rev(e);
+}
+__global__ __launch_bounds__(256) void inl_place_kernel(uint64_t n_raw, const PlpArgs a, const PlpWork w, const IndWork x, bg_bam_indel_t* __restrict__ events,
+                                                        uint8_t* __restrict__ seq) {
+    const uint64_t k = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / PLP_G;
+    const uint32_t lane = threadIdx.x % PLP_G;
+    if (k >= n_raw || !x.keep[k]) return;
+    const uint32_t s = x.run_start[k], e = x.run_start[k + 1];
+    const uint32_t rev = (uint32_t)(x.rev_off[e] - x.rev_off[s]);
+    ind_raw_t v = x.raw[x.order[s]];
+    if (lane == 0) {
+        const plp_tile_t t = plp_tile(v.tile, a.regions, a.n_regions, w.tile_off, w.row_off);
+        ind_store(ind_event(v, t.ref, t.region, e - s - rev, rev, x.seq_off[k]), events + x.keep_off[k]);
+    }
+    if (ind_kind(v) == BG_SITE_INS) inl_seq_lane(v, a.recs, a.off, seq + x.seq_off[k], lane, PLP_G);
+}
+
 int plp_check(const bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, const void* recs, const void* off, const void* contigs, uint64_t n_contigs,
               const void* regions, uint64_t n_regions, const void* rows, uint64_t rows_cap, uint64_t* n_rows, uint64_t* first_bad) {
     if (first_bad) *first_bad = UINT64_MAX;
@@ -660,9 +762,8 @@ int ind_check(const bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, c
     return BG_OK;
 }
 
-}  // namespace
-
-// bg_bam_indels_dev: the front (steps 1 to 3 of the pileup), then
+// bg_bam_indels_dev and bg_bam_indels_left_dev behind their checks (LEFT: the inl_* kernels in steps 4 to 6 and 8, the regions'
+// contigs held against the text, L the text and max_shift): the front (steps 1 to 3 of the pileup), then
 //   4. the count pass, one workgroup per tile: the raw events anchored in the tile; a scan places the tiles; the SECOND
 //      read-back gives the raw events;
 //   5. the emit pass over the tiles that have raw events: the depth counters, the raw events into the tile's range of scratch;
@@ -672,19 +773,17 @@ int ind_check(const bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, c
 //   8. the records, the sequences and the regions' offsets out.
 // Scratch: the front's lies in ctx->aux and must survive; 12 bytes a tile in ctx->tb; 88 bytes a raw event and the sort's own
 // in ctx->bnd.
-extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
-                                 const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions,
-                                 bg_bam_indel_t* d_events, uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events,
-                                 uint64_t* n_seq, uint64_t* first_bad, void* stream) {
-    int rc = ind_check(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, events_cap, d_seq, seq_cap, n_events, n_seq,
-                       first_bad);
-    if (rc) return rc;
-    if (((uintptr_t)d_events | (uintptr_t)d_event_off) & 7u) return bg_refuse("bg_bam_indels_dev: d_events or d_event_off is not 8-byte aligned");
+template <bool LEFT>
+int ind_events_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, const InlArgs& L, uint64_t n_text, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                   const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions, bg_bam_indel_t* d_events,
+                   uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad,
+                   void* stream) {
+    int rc;
     hipStream_t st = (hipStream_t)stream;
     BG_HIP(hipSetDevice(ctx->device));
     bg_scratch_guard guard(ctx, st);
     const uint64_t nr = n_regions;
-    const PlpArgs a = {n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, nr, ind_pileup_params(*prm), false, 0};
+    const PlpArgs a = {n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, nr, ind_pileup_params(*prm), LEFT, LEFT ? n_text : 0};
     PlpFront f;
     if ((rc = plp_front(ctx, st, a, &f, first_bad))) return rc;
     const uint64_t tiles = f.tiles;
@@ -699,7 +798,8 @@ extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64
             d_sums = cv.take<uint64_t>(bg_scan_sums_words(tiles));
         }))) return rc;
         // 4. the count pass
-        ind_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
+        if (LEFT) inl_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x, L);
+        else ind_tile_kernel<false><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
         BG_HIP(hipGetLastError());
         if ((rc = bg_scan_u32(x.tile_raw, tiles, d_roff, d_sums, st))) return rc;
         BG_HIP(hipMemcpyAsync(&n_raw, x.tile_raw_off + tiles, 8, hipMemcpyDeviceToHost, st));
@@ -728,14 +828,20 @@ extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64
             d_tmp = cv.take<uint8_t>(t_sort);
         }))) return rc;
         // 5. the emit pass
-        ind_tile_kernel<true><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
+        if (LEFT) inl_tile_kernel<true><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x, L);
+        else ind_tile_kernel<true><<<dim3((uint32_t)tiles), dim3(kThreads), 0, st>>>(a, f.w, x);
         BG_HIP(hipGetLastError());
         if (stop == 2) return BG_OK;
         // 6. the order, the runs
         size_t t = t_sort;
-        BG_HIP(rocprim::merge_sort(d_tmp, t, iota, x.order, n, IndOrder{x.raw, d_recs, d_off}, st));
+        if (LEFT) {
+            if ((rc = inl_sort_raw(d_tmp, t, x.raw, d_recs, d_off, x.order, n, st))) return rc;
+        } else {
+            BG_HIP(rocprim::merge_sort(d_tmp, t, iota, x.order, n, IndOrder{x.raw, d_recs, d_off}, st));
+        }
         if (stop == 3) return BG_OK;
-        ind_head_kernel<<<lanes(n), dim3(256), 0, st>>>(n, a, x);
+        if (LEFT) inl_head_kernel<<<lanes(n), dim3(256), 0, st>>>(n, a, x);
+        else ind_head_kernel<<<lanes(n), dim3(256), 0, st>>>(n, a, x);
         BG_HIP(hipGetLastError());
         if ((rc = bg_scan_u32(x.head, n, x.head_off, d_sums, st))) return rc;
         if ((rc = bg_scan_u32(x.rev, n, x.rev_off, d_sums, st))) return rc;
@@ -761,10 +867,26 @@ extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64
         BG_HIP(hipGetLastError());
     }
     if (totals[0]) {
-        ind_place_kernel<<<lanes(n_raw * PLP_G), dim3(256), 0, st>>>(n_raw, a, f.w, x, d_events, d_seq);
+        if (LEFT) inl_place_kernel<<<lanes(n_raw * PLP_G), dim3(256), 0, st>>>(n_raw, a, f.w, x, d_events, d_seq);
+        else ind_place_kernel<<<lanes(n_raw * PLP_G), dim3(256), 0, st>>>(n_raw, a, f.w, x, d_events, d_seq);
         BG_HIP(hipGetLastError());
     }
     return BG_OK;
+}
+
+
+}  // namespace
+
+extern "C" int bg_bam_indels_dev(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                                 const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const bg_bam_region_t* d_regions, uint64_t n_regions,
+                                 bg_bam_indel_t* d_events, uint64_t events_cap, uint8_t* d_seq, uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events,
+                                 uint64_t* n_seq, uint64_t* first_bad, void* stream) {
+    int rc = ind_check(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, events_cap, d_seq, seq_cap, n_events, n_seq,
+                       first_bad);
+    if (rc) return rc;
+    if (((uintptr_t)d_events | (uintptr_t)d_event_off) & 7u) return bg_refuse("bg_bam_indels_dev: d_events or d_event_off is not 8-byte aligned");
+    return ind_events_dev<false>(ctx, prm, InlArgs{nullptr, 0}, 0, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, events_cap, d_seq,
+                                 seq_cap, d_event_off, n_events, n_seq, first_bad, stream);
 }
 
 extern "C" int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off, const bg_sam_contig_t* contigs,
@@ -786,6 +908,67 @@ extern "C" int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n
     if (s.rc) return s.rc;
     if ((rc = bg_bam_indels_dev(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, cap, d_seq, cap_seq, d_event_off,
                                 n_events, n_seq, first_bad, s.st)))
+        return rc;
+    if (events) {
+        s.down(events, d_events, *n_events);
+        if (seq) s.down(seq, d_seq, *n_seq);
+        if (event_off) s.down(event_off, d_event_off, n_regions + 1);
+    }
+    return s.sync();
+}
+
+namespace {
+
+int inl_check(const bg_ctx* ctx, const bg_bam_indels_left_t* prm, const void* text, uint64_t n_text, bg_bam_indels_t* shared, uint64_t* n_events,
+              uint64_t* n_seq, uint64_t* first_bad) {
+    if (first_bad) *first_bad = UINT64_MAX;
+    if (!ctx || !prm || !n_events || !n_seq || (n_text && !text)) return BG_ERR_INVALID_ARG;
+    *shared = inl_indels_params(*prm);
+    return BG_OK;
+}
+
+}  // namespace
+
+// bg_bam_indels_left_dev: the checks of bg_bam_indels_dev and the text's, then ind_events_dev<true>
+extern "C" int bg_bam_indels_left_dev(bg_ctx* ctx, const bg_bam_indels_left_t* prm, uint64_t n_slots, const uint8_t* d_recs, const uint64_t* d_off,
+                                      const bg_sam_contig_t* d_contigs, uint64_t n_contigs, const uint8_t* d_text, uint64_t n_text,
+                                      const bg_bam_region_t* d_regions, uint64_t n_regions, bg_bam_indel_t* d_events, uint64_t events_cap, uint8_t* d_seq,
+                                      uint64_t seq_cap, uint64_t* d_event_off, uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad, void* stream) {
+    bg_bam_indels_t shared;
+    int rc = inl_check(ctx, prm, d_text, n_text, &shared, n_events, n_seq, first_bad);
+    if (rc) return rc;
+    if ((rc = ind_check(ctx, &shared, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events, events_cap, d_seq, seq_cap, n_events, n_seq,
+                        first_bad)))
+        return rc;
+    if (((uintptr_t)d_events | (uintptr_t)d_event_off) & 7u) return bg_refuse("bg_bam_indels_left_dev: d_events or d_event_off is not 8-byte aligned");
+    return ind_events_dev<true>(ctx, &shared, InlArgs{d_text, prm->max_shift}, n_text, n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events,
+                                events_cap, d_seq, seq_cap, d_event_off, n_events, n_seq, first_bad, stream);
+}
+
+extern "C" int bg_bam_indels_left(bg_ctx* ctx, const bg_bam_indels_left_t* prm, uint64_t n_slots, const uint8_t* recs, const uint64_t* off,
+                                  const bg_sam_contig_t* contigs, uint64_t n_contigs, const uint8_t* text, uint64_t n_text, const bg_bam_region_t* regions,
+                                  uint64_t n_regions, bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq, uint64_t seq_cap, uint64_t* event_off,
+                                  uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad) {
+    bg_bam_indels_t shared;
+    int rc = inl_check(ctx, prm, text, n_text, &shared, n_events, n_seq, first_bad);
+    if (rc) return rc;
+    if ((rc = ind_check(ctx, &shared, n_slots, recs, off, contigs, n_contigs, regions, n_regions, events, events_cap, seq, seq_cap, n_events, n_seq, first_bad)))
+        return rc;
+    // the bounds of bg_bam_indels: a shift moves an event and makes none
+    const uint64_t bytes = n_slots ? off[n_slots] : 0;
+    const uint64_t cap = events ? std::min(events_cap, n_regions * (bytes / 4)) : 0, cap_seq = seq ? std::min(seq_cap, n_regions * bytes * 2) : 0;
+    bg_stage s(ctx, ctx->stream);
+    const uint8_t* d_recs = s.up(recs, bytes);
+    const uint64_t* d_off = s.up(off, n_slots ? n_slots + 1 : 0);
+    const bg_sam_contig_t* d_contigs = s.up(contigs, n_contigs);
+    const uint8_t* d_text = s.up(text, n_text);
+    const bg_bam_region_t* d_regions = s.up(regions, n_regions);
+    bg_bam_indel_t* d_events = events ? s.out<bg_bam_indel_t>(cap) : nullptr;
+    uint8_t* d_seq = seq ? s.out<uint8_t>(cap_seq) : nullptr;
+    uint64_t* d_event_off = events && event_off ? s.out<uint64_t>(n_regions + 1) : nullptr;
+    if (s.rc) return s.rc;
+    if ((rc = bg_bam_indels_left_dev(ctx, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, d_text, n_text, d_regions, n_regions, d_events, cap, d_seq, cap_seq,
+                                     d_event_off, n_events, n_seq, first_bad, s.st)))
         return rc;
     if (events) {
         s.down(events, d_events, *n_events);

@@ -91,13 +91,15 @@ def emit_arrays(sites, events, seq, contigs, text, ctx=None):
     return out[:total.value].tobytes(), line_off
 
 
-def vcf_bam(data, text, regions=None, compress=False, ctx=None, **thresholds):
+def vcf_bam(data, text, regions=None, compress=False, ctx=None, left_align=None, **thresholds):
     """The VCF file of a coordinate-sorted BAM file (bytes) against `text`, FASTA text or a ready index text, as bytes: the header
     of `header`, then a line for every SNV site and every indel event of `regions` ((name or index, beg, end); None: every
     contig, whole).  `bam.read_bam`, `bam.resolve_regions`, then on the device `bam.sites_dev`, `bam.indels_dev` and `emit_dev`
     behind one another: sites, events and lines stay there, only their totals come back.  compress: the file as BGZF blocks
     with deflate-compressed payloads and the end-of-file block (`bam.bgzf_deflate_dev` over header plus body).  thresholds:
-    those `bam.sites_params` and `bam.indels_params` share."""
+    those `bam.sites_params` and `bam.indels_params` share.  left_align: None takes the events as the records spell them
+    (`bam.indels_dev`); an integer is the `max_shift` of `bam.indels_left_dev`, which shifts every indel to the left against the
+    text before events are merged; True shifts without a limit."""
     import torch
     for k in thresholds:
         if k not in THRESHOLDS:
@@ -126,9 +128,17 @@ def vcf_bam(data, text, regions=None, compress=False, ctx=None, **thresholds):
     n_sites = bam.sites_dev(*front, *text_args, *regs, stream=st, ctx=ctx, **thresholds)
     d_sites = room(32 * n_sites)
     bam.sites_dev(*front, *text_args, *regs, d_sites.data_ptr(), n_sites, stream=st, ctx=ctx, **thresholds)
-    n_events, n_seq = bam.indels_dev(*front, *regs, stream=st, ctx=ctx, **thresholds)
+    if left_align is None:
+        def indels(*out):
+            return bam.indels_dev(*front, *regs, *out, stream=st, ctx=ctx, **thresholds)
+    else:
+        max_shift = 0xFFFFFFFF if left_align is True else int(left_align)
+
+        def indels(*out):
+            return bam.indels_left_dev(*front, *text_args, *regs, *out, stream=st, ctx=ctx, max_shift=max_shift, **thresholds)
+    n_events, n_seq = indels()
     d_events, d_seq = room(40 * n_events), room(n_seq)
-    bam.indels_dev(*front, *regs, d_events.data_ptr(), n_events, d_seq.data_ptr(), n_seq, stream=st, ctx=ctx, **thresholds)
+    indels(d_events.data_ptr(), n_events, d_seq.data_ptr(), n_seq)
     lists = (n_sites, d_sites.data_ptr() if n_sites else 0, n_events, d_events.data_ptr() if n_events else 0, d_seq.data_ptr() if n_seq else 0, n_seq,
              d_contigs.data_ptr() if n_contigs else 0, n_contigs, d_names.data_ptr() if n_contigs else 0, *text_args)
     _, body = emit_dev(*lists, stream=st, ctx=ctx)
