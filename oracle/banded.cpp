@@ -205,6 +205,7 @@ struct BandedAligner {
     std::vector<size_t> v_path;
     int v_allowed_mismatches = -1;
     bool v_use_lcskpp_union = false;
+    Band v_band;
 
     // banded.rs:406-869
     Alignment compute_alignment(const uint8_t* x, size_t m, const uint8_t* y, size_t n) {
@@ -606,8 +607,10 @@ struct BandedAligner {
             filter = true;
         }
         // variant: 0 create (282-285), 1 custom_with_matches (313-321), 2 custom_with_match_path (391-401),
-        //          3 custom_with_expanded_matches (338-389)
-        if (variant == 0) {
+        //          3 custom_with_expanded_matches (338-389), 4 the caller's own band (v_band)
+        if (variant == 4) {
+            band = v_band;
+        } else if (variant == 0) {
             band = Band::create(x, m, y, n, k, w, scoring);
         } else if (variant == 1) {
             band = Band::create_with_matches(m, n, k, w, scoring, v_matches);
@@ -735,6 +738,30 @@ extern "C" int orc_banded_align_with(const orc_scoring_t* sc, int mode, uint32_t
                 band_start[j] = (uint32_t)al.band.start[j];
                 band_end[j] = (uint32_t)al.band.end[j];
             }
+        return orc::export_alignment(a, out, ops, ops_cap);
+    } catch (const std::exception&) {
+        return -2;
+    }
+}
+
+// compute_alignment over the caller's band: n + 1 half-open row ranges start[j]..end[j].  The mode wrappers' clips,
+// filter_clip_operations and band_cells as in orc_banded_align_with; -2 where the reference would panic (a range that
+// reaches past row m indexes its rolling arrays out of bounds).
+extern "C" int orc_banded_align_bands(const orc_scoring_t* sc, int mode, const uint8_t* x, uint64_t m, const uint8_t* y,
+                                      uint64_t n, const uint32_t* band_start, const uint32_t* band_end, orc_alignment_t* out,
+                                      uint64_t* ops, uint64_t ops_cap, uint64_t* band_cells) {
+    try {
+        orc::BandedAligner al(orc::scoring_from_c(sc), 0, 0);
+        al.variant = 4;
+        al.v_band = orc::Band(m, n);
+        for (uint64_t j = 0; j <= n; j++) {
+            if (band_end[j] > band_start[j] && band_end[j] > m + 1) throw orc::OracleError("index out of bounds");
+            al.v_band.start[j] = band_start[j];
+            al.v_band.end[j] = band_end[j];
+        }
+        size_t cells = 0;
+        orc::Alignment a = al.run(mode, x, m, y, n, &cells);
+        if (band_cells) *band_cells = cells;
         return orc::export_alignment(a, out, ops, ops_cap);
     } catch (const std::exception&) {
         return -2;

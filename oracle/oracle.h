@@ -76,6 +76,11 @@ int orc_banded_align_batch(const orc_scoring_t* sc, int mode, uint32_t k, uint32
 /* Band::create (banded.rs:1278): writes n+1 half-open row ranges; returns num_cells */
 uint64_t orc_band_create(const orc_scoring_t* sc, uint32_t k, uint32_t w, const uint8_t* x,
                          uint64_t m, const uint8_t* y, uint64_t n, uint32_t* start, uint32_t* end);
+/* compute_alignment (banded.rs:406-869) over the caller's band, n+1 half-open row ranges start[j]..end[j], under the
+ * mode's clips; -2 where the reference would panic (a range reaching past row m included) */
+int orc_banded_align_bands(const orc_scoring_t* sc, int mode, const uint8_t* x, uint64_t m, const uint8_t* y,
+                           uint64_t n, const uint32_t* band_start, const uint32_t* band_end,
+                           orc_alignment_t* out, uint64_t* ops, uint64_t ops_cap, uint64_t* band_cells);
 /* sparse::find_kmer_matches (sparse.rs:337) → pairs (x_pos,y_pos); returns count (≤cap written) */
 uint64_t orc_find_kmer_matches(const uint8_t* x, uint64_t m, const uint8_t* y, uint64_t n,
                                uint32_t k, uint32_t* out_xy, uint64_t cap);

@@ -117,6 +117,9 @@ def lib():
              [C.POINTER(Scoring), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
               C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(AlignmentRec),
               C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p]),
+            ("orc_banded_align_bands", C.c_int,
+             [C.POINTER(Scoring), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+              C.POINTER(AlignmentRec), C.c_void_p, C.c_uint64, u64p]),
             ("orc_fmd_check", C.c_int, [C.c_void_p, C.c_uint64]),
             ("orc_fmd_ext_calls", C.c_uint64, [C.c_int]),
             ("orc_fmd_smems", C.c_int64,
@@ -507,6 +510,28 @@ def banded_align_with(scoring, mode, k, w, x, y, matches, path=None, expanded=Fa
     d["band_cells"] = int(cells.value)
     if want_band:
         d["band"] = (bs, be)
+    return d
+
+
+def banded_align_bands(scoring, mode, x, y, start, end):
+    """compute_alignment (banded.rs:406-869) over the caller's band — len(y) + 1 half-open row ranges start[j]..end[j]
+    — in any mode.  Returns the alignment dict (+ 'band_cells')."""
+    sc = scoring[0] if isinstance(scoring, tuple) else scoring
+    xb, yb = _buf(x), _buf(y)
+    bs = np.ascontiguousarray(start, dtype=np.uint32)
+    be = np.ascontiguousarray(end, dtype=np.uint32)
+    assert len(bs) == len(be) == len(yb) + 1, "a band has one row range per column 0..n"
+    rec = AlignmentRec()
+    cap = len(xb) + len(yb) + 8
+    ops = np.zeros(cap, dtype=np.uint64)
+    cells = C.c_uint64(0)
+    rc = lib().orc_banded_align_bands(C.byref(sc), MODES[mode] if isinstance(mode, str) else mode, xb.ctypes.data, len(xb),
+                                      yb.ctypes.data, len(yb), bs.ctypes.data, be.ctypes.data, C.byref(rec),
+                                      ops.ctypes.data, cap, C.byref(cells))
+    if rc:
+        raise RuntimeError(f"oracle banded_align_bands failed rc={rc}")
+    d = _rec_to_dict(rec, decode_ops(ops[:rec.n_ops]))
+    d["band_cells"] = int(cells.value)
     return d
 
 
