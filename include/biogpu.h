@@ -1536,7 +1536,7 @@ int bg_bam_pileup(bg_ctx* ctx, const bg_bam_pileup_t* prm, uint64_t n_slots, con
                   const bg_sam_contig_t* contigs, uint64_t n_contigs, const bg_bam_region_t* regions, uint64_t n_regions,
                   uint32_t* rows, uint64_t rows_cap, uint64_t* row_off, uint64_t* n_rows, uint64_t* first_bad);
 
-/* ---- candidate variant sites and region summaries: the pileup held against the reference (bam_pileup.hip; the bodies in
+/* ---- candidate variant sites and region summaries: the pileup held against the reference (bam_sites.hip; the bodies in
  * csrc/bam_sites_rule.h) ----
  * The counters of bg_bam_pileup compared with the reference text where they are counted: one compact record for every
  * candidate variant site and one summary for every region.  No row goes to HBM, so the regions may be whole genomes.
@@ -1615,7 +1615,7 @@ int bg_bam_sites(bg_ctx* ctx, const bg_bam_sites_t* prm, uint64_t n_slots, const
                  const bg_bam_region_t* regions, uint64_t n_regions, bg_bam_site_t* sites, uint64_t sites_cap,
                  uint64_t* site_off, bg_bam_region_summary_t* summary, uint64_t* n_sites, uint64_t* first_bad);
 
-/* ---- indel events: deletions by length and insertions by sequence, per anchor (bam_pileup.hip; the bodies in
+/* ---- indel events: deletions by length and insertions by sequence, per anchor (bam_indels.hip; the bodies in
  * csrc/bam_indels_rule.h) ----
  * What bg_bam_sites cannot name: one record for every distinct indel event of a batch of regions — a deletion of a given
  * length, or an insertion of a given sequence, behind a given anchor — with counts per strand and the depth of the anchor,
@@ -1688,7 +1688,7 @@ int bg_bam_indels(bg_ctx* ctx, const bg_bam_indels_t* prm, uint64_t n_slots, con
                   bg_bam_indel_t* events, uint64_t events_cap, uint8_t* seq, uint64_t seq_cap, uint64_t* event_off,
                   uint64_t* n_events, uint64_t* n_seq, uint64_t* first_bad);
 
-/* ---- indel events, left-aligned against the reference (bam_pileup.hip; the bodies in csrc/bam_indels_left_rule.h) ----
+/* ---- indel events, left-aligned against the reference (bam_indels.hip; the bodies in csrc/bam_indels_left_rule.h) ----
  * bg_bam_indels counts an event exactly as the records spell it, and in a homopolymer or a tandem repeat one indel has as many
  * spellings as the repeat has positions: its records then fall apart into shares that are judged alone.  bg_bam_indels_left
  * shifts every raw event to the left against the reference text BEFORE events are merged, so that the spellings of one indel

@@ -1,5 +1,5 @@
 """BAM records, BGZF framing and reading, and the BAI index — host mirror of `bg_bam_header`, `bg_bam_emit_batch[_dev]`, `bg_bgzf_frame[_dev]`,
-`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip) and of the pileup over sorted records and its candidate variant sites (`bg_bam_pileup[_dev]`, `bg_bam_sites[_dev]`; rust-bio_amd/csrc/bam_pileup.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
+`bg_bgzf_deflate[_dev]`, `bg_bgzf_blocks[_dev]`, `bg_bgzf_inflate[_dev]`, `bg_bam_index[_dev]` and of reading BAM back (`bg_bam_header_parse`, `bg_bam_records[_dev]`, `bg_bam_reads[_dev]`, `bg_bam_sort_keys[_dev]`, `bg_bam_index_blocks[_dev]`; rust-bio_amd/csrc/bam_read.hip) and of the pileup over sorted records, its candidate variant sites and its indel events (`bg_bam_pileup[_dev]`, `bg_bam_sites[_dev]`, `bg_bam_indels[_dev]`, `bg_bam_indels_left[_dev]`; rust-bio_amd/csrc/bam_pileup.hip, bam_sites.hip, bam_indels.hip); `sorted_bam` chains them with `sam.markdup_*`, `sam.sort_keys_*` and `sam.sort_*` into a complete coordinate-sorted BAM file.
 
 rust-bio has no BAM writer; the record is defined in include/biogpu.h as the BAM encoding (SAM v1.6, section 4.2) of the line
 the SAM writer gives a slot and is written by HIP kernels (rust-bio_amd/csrc/bam_emit.hip) out of the same arguments; the
@@ -726,12 +726,8 @@ def indels_params(require=0, exclude=0x704, min_mapq=0, min_baseq=0, min_depth=0
     return p
 
 
-def indels_arrays(stream, off, contigs, regions, ctx=None, **params):
-    """bg_bam_indels, host buffers: the indel events of `regions` ((ref, beg, end), 0-based, half-open) from the coordinate-sorted
-    records stream[off[i] .. off[i + 1]).  params: those of `indels_params`.  Returns (events: INDEL_DTYPE[], in region order,
-    then by anchor, deletions before insertions, then by length, insertions of one length by their codes; seq: uint8[], the
-    inserted bases as ASCII, an insertion's at seq[seq_off : seq_off + len]; event_off: uint64[n_regions + 1]).  Raises
-    BamPileupError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+def _indels_arrays(where, prm, stream, off, contigs, text, regions, ctx):
+    """bg_bam_indels (text None) or bg_bam_indels_left behind `indels_arrays` / `indels_left_arrays`: a sizing call, then the call"""
     ctx = ctx or _lib.default_context()
     src = _lib.as_u8(stream)
     src = src if len(src) else np.zeros(1, np.uint8)
@@ -739,19 +735,45 @@ def indels_arrays(stream, off, contigs, regions, ctx=None, **params):
     n = len(off) - 1 if len(off) else 0
     table = np.ascontiguousarray(contigs.table)
     reg = pileup_regions(regions)
-    prm = indels_params(**params)
+    ref_text = None if text is None else _lib.as_u8(text)
+    with_text = () if text is None else (ref_text.ctypes.data if len(ref_text) else None, len(ref_text))
     total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
 
     def call(events, cap, seq, seq_cap, event_off):
-        return _lib.lib().bg_bam_indels(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
-                                        len(table), reg.ctypes.data if len(reg) else None, len(reg), events, cap, seq, seq_cap, event_off, C.byref(total),
-                                        C.byref(n_seq), C.byref(bad))
-    _pileup_check(call(None, 0, None, 0, None), "bg_bam_indels", bad)
+        return getattr(_lib.lib(), where)(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None, table.ctypes.data if len(table) else None,
+                                          len(table), *with_text, reg.ctypes.data if len(reg) else None, len(reg), events, cap, seq, seq_cap, event_off,
+                                          C.byref(total), C.byref(n_seq), C.byref(bad))
+    _pileup_check(call(None, 0, None, 0, None), where, bad)
     events = np.zeros(max(total.value, 1), dtype=INDEL_DTYPE)
     seq = np.zeros(max(n_seq.value, 1), dtype=np.uint8)
     event_off = np.zeros(len(reg) + 1, dtype=np.uint64)
-    _pileup_check(call(events.ctypes.data, len(events), seq.ctypes.data, len(seq), event_off.ctypes.data), "bg_bam_indels", bad)
+    _pileup_check(call(events.ctypes.data, len(events), seq.ctypes.data, len(seq), event_off.ctypes.data), where, bad)
     return events[:total.value], seq[:n_seq.value], event_off
+
+
+def indels_arrays(stream, off, contigs, regions, ctx=None, **params):
+    """bg_bam_indels, host buffers: the indel events of `regions` ((ref, beg, end), 0-based, half-open) from the coordinate-sorted
+    records stream[off[i] .. off[i + 1]).  params: those of `indels_params`.  Returns (events: INDEL_DTYPE[], in region order,
+    then by anchor, deletions before insertions, then by length, insertions of one length by their codes; seq: uint8[], the
+    inserted bases as ASCII, an insertion's at seq[seq_off : seq_off + len]; event_off: uint64[n_regions + 1]).  Raises
+    BamPileupError (status -1 INVALID_ARG, -11 UNSUPPORTED) with the offending slot."""
+    return _indels_arrays("bg_bam_indels", indels_params(**params), stream, off, contigs, None, regions, ctx)
+
+
+def _indels_dev(where, prm, n_slots, d_recs, d_off, d_contigs, n_contigs, with_text, d_regions, n_regions, d_events, events_cap, d_seq, seq_cap, d_event_off,
+                stream, ctx):
+    """bg_bam_indels_dev (with_text empty) or bg_bam_indels_left_dev (with_text: d_text, n_text) behind `indels_dev` / `indels_left_dev`"""
+    ctx = ctx or _lib.default_context()
+    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = getattr(_lib.lib(), where)(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, *with_text, d_regions or None,
+                                    n_regions, d_events or None, events_cap, d_seq or None, seq_cap, d_event_off or None, C.byref(total), C.byref(n_seq),
+                                    C.byref(bad), stream)
+    try:
+        _pileup_check(rc, where, bad)
+    except _lib.BiogpuError as e:
+        e.totals = (int(total.value), int(n_seq.value))
+        raise
+    return int(total.value), int(n_seq.value)
 
 
 def indels_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_regions, d_events=0, events_cap=0, d_seq=0, seq_cap=0, d_event_off=0, stream=0,
@@ -760,18 +782,8 @@ def indels_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_regions, n_region
     0).  Returns (n_events, n_seq), read back with the third synchronisation of `stream`; the records and sequences are then
     written asynchronously.  Raises BamPileupError with the offending slot, BiogpuError with status -9 (OPS_CAP) when a
     capacity is too small (`totals` then holds both totals)."""
-    ctx = ctx or _lib.default_context()
-    prm = indels_params(**params)
-    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    rc = _lib.lib().bg_bam_indels_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_regions or None,
-                                      n_regions, d_events or None, events_cap, d_seq or None, seq_cap, d_event_off or None, C.byref(total),
-                                      C.byref(n_seq), C.byref(bad), stream)
-    try:
-        _pileup_check(rc, "bg_bam_indels_dev", bad)
-    except _lib.BiogpuError as e:
-        e.totals = (int(total.value), int(n_seq.value))
-        raise
-    return int(total.value), int(n_seq.value)
+    return _indels_dev("bg_bam_indels_dev", indels_params(**params), n_slots, d_recs, d_off, d_contigs, n_contigs, (), d_regions, n_regions, d_events, events_cap,
+                       d_seq, seq_cap, d_event_off, stream, ctx)
 
 
 def indels_bam(data, regions, ctx=None, **params):
@@ -794,46 +806,15 @@ def indels_left_arrays(stream, off, contigs, text, regions, ctx=None, **params):
     """bg_bam_indels_left, host buffers: `indels_arrays` with every raw event shifted to the left against the index text `text`
     (the one `sites_arrays` takes) before events are merged, so that the spellings of one indel inside a repeat are one event.
     params: those of `indels_left_params`.  Returns what `indels_arrays` returns; the anchors are the shifted ones."""
-    ctx = ctx or _lib.default_context()
-    src = _lib.as_u8(stream)
-    src = src if len(src) else np.zeros(1, np.uint8)
-    off = np.ascontiguousarray(off, dtype=np.uint64)
-    n = len(off) - 1 if len(off) else 0
-    table = np.ascontiguousarray(contigs.table)
-    ref_text = _lib.as_u8(text)
-    reg = pileup_regions(regions)
-    prm = indels_left_params(**params)
-    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-
-    def call(events, cap, seq, seq_cap, event_off):
-        return _lib.lib().bg_bam_indels_left(ctx.h, prm.ctypes.data, n, src.ctypes.data, off.ctypes.data if n else None,
-                                             table.ctypes.data if len(table) else None, len(table), ref_text.ctypes.data if len(ref_text) else None,
-                                             len(ref_text), reg.ctypes.data if len(reg) else None, len(reg), events, cap, seq, seq_cap, event_off,
-                                             C.byref(total), C.byref(n_seq), C.byref(bad))
-    _pileup_check(call(None, 0, None, 0, None), "bg_bam_indels_left", bad)
-    events = np.zeros(max(total.value, 1), dtype=INDEL_DTYPE)
-    seq = np.zeros(max(n_seq.value, 1), dtype=np.uint8)
-    event_off = np.zeros(len(reg) + 1, dtype=np.uint64)
-    _pileup_check(call(events.ctypes.data, len(events), seq.ctypes.data, len(seq), event_off.ctypes.data), "bg_bam_indels_left", bad)
-    return events[:total.value], seq[:n_seq.value], event_off
+    return _indels_arrays("bg_bam_indels_left", indels_left_params(**params), stream, off, contigs, text, regions, ctx)
 
 
 def indels_left_dev(n_slots, d_recs, d_off, d_contigs, n_contigs, d_text, n_text, d_regions, n_regions, d_events=0, events_cap=0, d_seq=0, seq_cap=0,
                     d_event_off=0, stream=0, ctx=None, **params):
     """bg_bam_indels_left_dev: `indels_dev` with (d_text, n_text) behind n_contigs and `indels_left_params`; sizing, the returned
     totals and the errors are `indels_dev`'s."""
-    ctx = ctx or _lib.default_context()
-    prm = indels_left_params(**params)
-    total, n_seq, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    rc = _lib.lib().bg_bam_indels_left_dev(ctx.h, prm.ctypes.data, n_slots, d_recs or None, d_off or None, d_contigs or None, n_contigs, d_text or None, n_text,
-                                           d_regions or None, n_regions, d_events or None, events_cap, d_seq or None, seq_cap, d_event_off or None,
-                                           C.byref(total), C.byref(n_seq), C.byref(bad), stream)
-    try:
-        _pileup_check(rc, "bg_bam_indels_left_dev", bad)
-    except _lib.BiogpuError as e:
-        e.totals = (int(total.value), int(n_seq.value))
-        raise
-    return int(total.value), int(n_seq.value)
+    return _indels_dev("bg_bam_indels_left_dev", indels_left_params(**params), n_slots, d_recs, d_off, d_contigs, n_contigs, (d_text or None, n_text), d_regions,
+                       n_regions, d_events, events_cap, d_seq, seq_cap, d_event_off, stream, ctx)
 
 
 def indels_left_bam(data, reference, regions, ctx=None, **params):

@@ -1,5 +1,5 @@
-// The bodies behind the left-aligned indel events (bam_pileup.hip: bg_bam_indels_left[_dev]; THE RULE is in include/biogpu.h) as
-// __host__ __device__ functions, so that the kernels and tests/bam_indels_left_host_bodies.cpp, which runs them on the CPU under
+// The bodies behind the left-aligned indel events (bam_indels.hip: bg_bam_indels_left[_dev]; THE RULE is in include/biogpu.h) as
+// __host__ __device__ functions, so that the kernels and tests/bam_indels_host_bodies.cpp (its left flavour), which runs them on the CPU under
 // AddressSanitizer, share ONE definition of how far a raw event moves and of what its bytes are behind the move.  Everything in
 // front of the shift and behind it is bam_indels_rule.h's (ind_raw_t, ind_depth, ind_is_kept, ind_event, ind_store).
 //   * the walk:   inl_walk: ind_walk without the window's upper end: every raw event of a kept record whose RAW anchor is at or
@@ -31,31 +31,7 @@ SAM_HD bg_bam_indels_t inl_indels_params(const bg_bam_indels_left_t& p) {
 // t0 <= a < t1 + max_shift.  One in front of t0 cannot land in [t0, t1) and costs no text read; one at or behind t1 may.
 template <class Emit>
 SAM_HD void inl_walk(const uint8_t* rec, uint32_t ref, int64_t t0, int64_t t1, uint32_t max_shift, Emit emit) {
-    if (bai_get32(rec + 4) != ref) return;
-    const int64_t pos = (int32_t)bai_get32(rec + 8);
-    const uint32_t l_name = rec[12], n_cigar = bai_get16(rec + 16), l_seq = bai_get32(rec + 20);
-    const uint8_t* cig = rec + BAM_FIXED + l_name;
-    const int64_t last = t1 + (int64_t)max_shift;  // raw anchors at or behind it stay at or behind t1
-    int64_t r = pos, q = 0;
-    for (uint32_t k = 0; k < n_cigar && r <= last; k++) {
-        const uint32_t w = bai_get32(cig + 4ull * k), op = w & 15u;
-        const int64_t n = w >> 4;
-        const bool here = n >= 1 && r > pos && r - 1 >= t0 && r - 1 < last;
-        if (op == BAM_CIGAR_M || op == BAM_CIGAR_EQ || op == BAM_CIGAR_X) {
-            r += n;
-            q += n;
-        } else if (op == BAM_CIGAR_D) {
-            if (here) emit((uint32_t)BG_SITE_DEL, (uint32_t)(r - 1), (uint32_t)n, 0u, pos);
-            r += n;
-        } else if (op == BAM_CIGAR_N) {
-            r += n;
-        } else if (op == BAM_CIGAR_I) {
-            if (here && l_seq) emit((uint32_t)BG_SITE_INS, (uint32_t)(r - 1), (uint32_t)n, (uint32_t)q, pos);
-            q += n;
-        } else if (op == BAM_CIGAR_S) {
-            q += n;
-        }
-    }
+    ind_walk_pos(rec, ref, t0, t1 + (int64_t)max_shift, emit);  // raw anchors at or behind t1 + max_shift stay at or behind t1
 }
 
 // ---- the shift --------------------------------------------------------------------------------------------------------------

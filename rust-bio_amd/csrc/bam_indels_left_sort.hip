@@ -1,4 +1,4 @@
-// The merge sort of bg_bam_indels_left_dev (bam_pileup.hip), in a translation unit of its own.  Its kernels are rocPRIM's with the
+// The merge sort of bg_bam_indels_left_dev (bam_indels.hip), in a translation unit of its own.  Its kernels are rocPRIM's with the
 // comparator inl_cmp (bam_indels_left_rule.h): tile, shifted anchor, kind, len, then the shifted codes left to right.  It stands
 // apart because of what the compiler did with it beside the sort of bg_bam_indels_dev: with both comparators instantiated in
 // one file the block-sort kernel of THAT call went from 168 to 184 VGPRs and from 3 to 2 waves a SIMD (kernel-resource-usage

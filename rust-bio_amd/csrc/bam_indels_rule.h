@@ -1,7 +1,8 @@
-// The bodies behind the indel events (bam_pileup.hip: bg_bam_indels[_dev]; THE RULE is in include/biogpu.h) as __host__
+// The bodies behind the indel events (bam_indels.hip: bg_bam_indels[_dev]; THE RULE is in include/biogpu.h) as __host__
 // __device__ functions, so that the kernels and tests/bam_indels_host_bodies.cpp, which runs them on the CPU under
 // AddressSanitizer, share ONE definition of what a record yields and of how raw events become events.
-//   * the walk:    ind_walk: the raw events of a kept record anchored inside a window, in the pileup's walk (r = pos, q = 0)
+//   * the walk:    ind_walk: the raw events of a kept record anchored inside a window, in the pileup's walk (r = pos, q = 0);
+//                  ind_walk_pos: the same with the record's pos handed on, which bam_indels_left_rule.h's inl_walk is made of
 //   * a raw event: ind_raw_t, 32 bytes in scratch: the tile, the anchor, kind, length, strand, the anchor's depth, and where
 //                  the inserted codes lie (slot, q); ind_depth: the depth of a position from the 8-column counters of a tile
 //   * the order:   ind_code: a 4-bit code of a record's bases; ind_cmp: the full key (tile, anchor, kind, len, codes left to
@@ -20,34 +21,39 @@ SAM_HD bg_bam_pileup_t ind_pileup_params(const bg_bam_indels_t& p) {
 }
 
 // ---- the walk ---------------------------------------------------------------------------------------------------------------
-// The kept record rec (one that passed plp_slot): emit(kind, anchor, len, q) for every raw event anchored in [t0, t1) of `ref`.
-// q is the index of an insertion's first base (0 for a deletion).  Every byte read lies inside the record.
+// The kept record rec (one that passed plp_slot): emit(kind, anchor, len, q, pos) for every raw event anchored in [t0, last) of
+// `ref`.  q is the index of an insertion's first base (0 for a deletion), pos the record's.  Every byte read lies inside the record.
 template <class Emit>
-SAM_HD void ind_walk(const uint8_t* rec, uint32_t ref, int64_t t0, int64_t t1, Emit emit) {
+SAM_HD void ind_walk_pos(const uint8_t* rec, uint32_t ref, int64_t t0, int64_t last, Emit emit) {
     if (bai_get32(rec + 4) != ref) return;
     const int64_t pos = (int32_t)bai_get32(rec + 8);
     const uint32_t l_name = rec[12], n_cigar = bai_get16(rec + 16), l_seq = bai_get32(rec + 20);
     const uint8_t* cig = rec + BAM_FIXED + l_name;
     int64_t r = pos, q = 0;
-    for (uint32_t k = 0; k < n_cigar && r <= t1; k++) {  // (an event at r == t1 is anchored at t1 - 1)
+    for (uint32_t k = 0; k < n_cigar && r <= last; k++) {  // (an event at r == last is anchored at last - 1)
         const uint32_t w = bai_get32(cig + 4ull * k), op = w & 15u;
         const int64_t n = w >> 4;
-        const bool here = n >= 1 && r > pos && r - 1 >= t0 && r - 1 < t1;
+        const bool here = n >= 1 && r > pos && r - 1 >= t0 && r - 1 < last;
         if (op == BAM_CIGAR_M || op == BAM_CIGAR_EQ || op == BAM_CIGAR_X) {
             r += n;
             q += n;
         } else if (op == BAM_CIGAR_D) {
-            if (here) emit((uint32_t)BG_SITE_DEL, (uint32_t)(r - 1), (uint32_t)n, 0u);
+            if (here) emit((uint32_t)BG_SITE_DEL, (uint32_t)(r - 1), (uint32_t)n, 0u, pos);
             r += n;
         } else if (op == BAM_CIGAR_N) {
             r += n;
         } else if (op == BAM_CIGAR_I) {
-            if (here && l_seq) emit((uint32_t)BG_SITE_INS, (uint32_t)(r - 1), (uint32_t)n, (uint32_t)q);
+            if (here && l_seq) emit((uint32_t)BG_SITE_INS, (uint32_t)(r - 1), (uint32_t)n, (uint32_t)q, pos);
             q += n;
         } else if (op == BAM_CIGAR_S) {
             q += n;
         }
     }
+}
+// emit(kind, anchor, len, q) for every raw event anchored in [t0, t1) of `ref`
+template <class Emit>
+SAM_HD void ind_walk(const uint8_t* rec, uint32_t ref, int64_t t0, int64_t t1, Emit emit) {
+    ind_walk_pos(rec, ref, t0, t1, [&](uint32_t kind, uint32_t anchor, uint32_t len, uint32_t q, int64_t) { emit(kind, anchor, len, q); });
 }
 
 // ---- a raw event ------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// The bodies behind the candidate sites and region summaries (bam_pileup.hip: bg_bam_sites[_dev]; THE RULE is in
+// The bodies behind the candidate sites and region summaries (bam_sites.hip: bg_bam_sites[_dev]; THE RULE is in
 // include/biogpu.h) as __host__ __device__ functions, so that the kernels and tests/bam_sites_host_bodies.cpp, which runs them
 // on the CPU under AddressSanitizer, share ONE definition of what a position yields.  The counters are the pileup's
 // (bam_pileup_rule.h), column-major in a tile: counter c of position p at c * BG_PILEUP_TILE + p.

@@ -2,7 +2,7 @@
 the pileup's corpus (tests/bam_pileup_cases.py, by import) with the thresholds rotated over it, cases of the events' own at tile
 borders, at the word borders of the inserted codes and at the operations the rule drops, the pileup's refusals with what the
 Python restatement (tests/bam_indels_oracle.py) says of each, and the stand-alone program that runs the kernels' bodies on the
-CPU (tests/bam_indels_host_bodies.cpp).  T is the product's tile; the expected events know nothing of it."""
+CPU (tests/bam_indels_host_bodies.cpp, for tests/bam_indels_left_cases.py as well).  T is the product's tile; the expected events know nothing of it."""
 import os
 import struct
 import subprocess
@@ -154,22 +154,22 @@ def refusals():
 
 # ---- the program ------------------------------------------------------------------------------------------------------------
 def build_program(exe, sanitize):
-    """the program of bam_indels_host_bodies.cpp, built as bam_pileup_cases.build_program builds its own"""
-    flags = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.check_call(["hipcc", "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + _lib.CSRC] + flags + [os.path.join(ROOT, "tests", "bam_indels_host_bodies.cpp"), "-o", exe])
-    return exe
+    """the program of bam_indels_host_bodies.cpp, which serves both flavours"""
+    return pc.build_program("bam_indels_host_bodies.cpp", exe, sanitize)
 
 
 def params_array(p):
-    a = np.zeros(1, dtype=_lib.BAM_INDELS_DTYPE)
-    a[0] = (0, p["require"], p["exclude"], p["min_mapq"], p["min_baseq"], 0, p["min_depth"], p["min_alt"], p["min_alt_permille"], p["min_alt_strand"])
+    """bg_bam_indels_t, or bg_bam_indels_left_t where p has a max_shift"""
+    shared = (0, p["require"], p["exclude"], p["min_mapq"], p["min_baseq"], 0, p["min_depth"], p["min_alt"], p["min_alt_permille"], p["min_alt_strand"])
+    a = np.zeros(1, dtype=_lib.BAM_INDELS_LEFT_DTYPE if "max_shift" in p else _lib.BAM_INDELS_DTYPE)
+    a[0] = shared + (p["max_shift"],) if "max_shift" in p else shared
     return a
 
 
 def run_program(exe, tmp, cases):
     """cases: [dict(slots, contigs, regions, params)] -> [(rc, first_bad, n_events, n_seq, events: BAM_INDEL_DTYPE[] or None, seq: bytes or
-    None, event_off or None)]"""
+    None, event_off or None)].  A case with a `text` runs the left-aligned flavour: the program gets the first n_text bytes of it
+    and not one more (fewer where a refusal's text is only claimed)"""
     inp, outp = os.path.join(str(tmp), "in.bin"), os.path.join(str(tmp), "out.bin")
     with open(inp, "wb") as f:
         f.write(struct.pack("<Q", len(cases)))
@@ -178,8 +178,10 @@ def run_program(exe, tmp, cases):
             off = bam_oracle.offsets(slots)
             table = rc.contig_table(c["contigs"])
             regions = np.array([tuple(r) for r in c["regions"]], dtype=_lib.BAM_REGION_DTYPE) if c["regions"] else np.zeros(0, _lib.BAM_REGION_DTYPE)
-            f.write(struct.pack("<4Q", len(slots), int(off[-1]), len(table), len(regions)))
-            f.write(params_array(c["params"]).tobytes() + b"".join(slots) + off.tobytes() + table.tobytes() + regions.tobytes())
+            left = "text" in c
+            n_text, text = (c["n_text"], c["text"][:c["n_text"]]) if left else (0, b"")
+            f.write(struct.pack("<7Q", len(slots), int(off[-1]), len(table), len(regions), left, n_text, len(text)))
+            f.write(params_array(c["params"]).tobytes() + b"".join(slots) + off.tobytes() + table.tobytes() + regions.tobytes() + text)
     subprocess.check_call([exe, inp, outp])
     b = open(outp, "rb").read()
     at, got = 0, []

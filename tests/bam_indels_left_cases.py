@@ -4,22 +4,14 @@ that land one and two tiles in front of their raw anchor, regions that hold only
 at the word borders of the packed bases with k below, at and above their length, spellings that meet only behind the shift, more
 records than four strides of a workgroup on one event, and the whole corpus of tests/bam_indels_cases.py with max_shift 0, where
 the expected result is the older oracle's.  The refusals with what the Python restatement (tests/bam_indels_left_oracle.py) says
-of each, and the stand-alone program that runs the kernels' bodies on the CPU (tests/bam_indels_left_host_bodies.cpp).  The
-expected events know nothing of tiles."""
-import os
-import struct
-import subprocess
-
+of each, and the stand-alone program that runs the kernels' bodies on the CPU (tests/bam_indels_host_bodies.cpp, its left
+flavour).  The expected events know nothing of tiles."""
 import numpy as np
 
 import bam_indels_cases as ic
 import bam_indels_left_oracle as lo
-import bam_indels_oracle as io
-import bam_oracle
 import bam_pileup_cases as pc
-import bam_read_cases as rc
 import bam_sites_cases as sc
-from rust_bio_amd import _lib
 
 ROOT = pc.ROOT
 T = pc.T
@@ -235,49 +227,6 @@ def want_of(c):
     return lo.indels(c["slots"], c["contigs"], c["text"], c["regions"], n_text=c["n_text"], **c["params"])
 
 
-# ---- the program ------------------------------------------------------------------------------------------------------------
-def build_program(exe, sanitize):
-    """the program of bam_indels_left_host_bodies.cpp, built as bam_indels_cases.build_program builds its own"""
-    flags = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.check_call(["hipcc", "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + _lib.CSRC] + flags + [os.path.join(ROOT, "tests", "bam_indels_left_host_bodies.cpp"), "-o", exe])
-    return exe
-
-
-def params_array(p):
-    a = np.zeros(1, dtype=_lib.BAM_INDELS_LEFT_DTYPE)
-    a[0] = (0, p["require"], p["exclude"], p["min_mapq"], p["min_baseq"], 0, p["min_depth"], p["min_alt"], p["min_alt_permille"], p["min_alt_strand"],
-            p["max_shift"])
-    return a
-
-
-def run_program(exe, tmp, cases):
-    """cases -> [(rc, first_bad, n_events, n_seq, events: BAM_INDEL_DTYPE[] or None, seq: bytes or None, event_off or None)]; the
-    program gets the first n_text bytes of a case's text and not one more (fewer where a refusal's text is only claimed)"""
-    inp, outp = os.path.join(str(tmp), "in.bin"), os.path.join(str(tmp), "out.bin")
-    with open(inp, "wb") as f:
-        f.write(struct.pack("<Q", len(cases)))
-        for c in cases:
-            slots = c["slots"]
-            off = bam_oracle.offsets(slots)
-            table = rc.contig_table(c["contigs"])
-            regions = np.array([tuple(r) for r in c["regions"]], dtype=_lib.BAM_REGION_DTYPE) if c["regions"] else np.zeros(0, _lib.BAM_REGION_DTYPE)
-            f.write(struct.pack("<6Q", len(slots), int(off[-1]), len(table), len(regions), c["n_text"], len(c["text"][:c["n_text"]])))
-            f.write(params_array(c["params"]).tobytes() + b"".join(slots) + off.tobytes() + table.tobytes() + regions.tobytes() + c["text"][:c["n_text"]])
-    subprocess.check_call([exe, inp, outp])
-    b = open(outp, "rb").read()
-    at, got = 0, []
-    for c in cases:
-        rcode, bad, n_events, n_seq = struct.unpack_from("<qQQQ", b, at)
-        at += 32
-        events = seq = event_off = None
-        if rcode == 0:
-            events = np.frombuffer(b, _lib.BAM_INDEL_DTYPE, n_events, at)
-            at += events.nbytes
-            seq = b[at:at + n_seq]
-            at += n_seq
-            event_off = np.frombuffer(b, np.uint64, len(c["regions"]) + 1, at).tolist()
-            at += 8 * (len(c["regions"]) + 1)
-        got.append((rcode, bad, n_events, n_seq, events, seq, event_off))
-    assert at == len(b)
-    return got
+# ---- the program: bam_indels_cases' own, which takes a case's text -----------------------------------------------------------
+build_program = ic.build_program
+run_program = ic.run_program

@@ -236,11 +236,12 @@ def refusals():
 
 
 # ---- the program ------------------------------------------------------------------------------------------------------------
-def build_program(exe, sanitize):
-    """the program of bam_pileup_host_bodies.cpp, built as bam_read_cases.build_program builds its own"""
+def build_program(source, exe, sanitize):
+    """the stand-alone program of tests/<source> (the pileup's, the sites' or the indel events' host bodies), built as
+    bam_read_cases.build_program builds its own"""
     flags = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else []
     subprocess.check_call(["hipcc", "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + _lib.CSRC] + flags + [os.path.join(ROOT, "tests", "bam_pileup_host_bodies.cpp"), "-o", exe])
+                           "-I" + _lib.CSRC] + flags + [os.path.join(ROOT, "tests", source), "-o", exe])
     return exe
 
 

@@ -142,11 +142,8 @@ def synthetic():
 
 # ---- the program ------------------------------------------------------------------------------------------------------------
 def build_program(exe, sanitize):
-    """the program of bam_sites_host_bodies.cpp, built as bam_pileup_cases.build_program builds its own"""
-    flags = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.check_call(["hipcc", "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + _lib.CSRC] + flags + [os.path.join(ROOT, "tests", "bam_sites_host_bodies.cpp"), "-o", exe])
-    return exe
+    """the program of bam_sites_host_bodies.cpp"""
+    return pc.build_program("bam_sites_host_bodies.cpp", exe, sanitize)
 
 
 def params_array(p):

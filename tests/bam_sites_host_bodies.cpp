@@ -1,6 +1,6 @@
 // Stand-alone CPU program for tests/test_bam_sites_host_bodies.py: the __host__ __device__ bodies of csrc/bam_sites_rule.h (and
-// those of csrc/bam_pileup_rule.h they stand on) run on the host, in the steps the kernels of csrc/bam_pileup.hip take for
-// bg_bam_sites_dev.  The front as tests/bam_pileup_host_bodies.cpp runs it, with sit_region_ok for the regions.  The count
+// those of csrc/bam_pileup_rule.h they stand on) run on the host, in the steps the kernels of csrc/bam_sites.hip take for
+// bg_bam_sites_dev.  The front of tests/bam_pileup_host_front.h, with sit_region_ok for the regions.  The count
 // pass, tile by tile: the counters by plp_walk_lane, then threads 0 .. 255 in turn judge positions tid and tid + 256
 // (sit_judge) into a share each (sit_share_pos), the shares joined (sit_share_join), the tile's sites from the packed word, the
 // share parked as a record (sit_share_summary); a region's tiles summed by strided threads (sit_summary_stride, sit_summary_join)
@@ -14,24 +14,7 @@
 // per tile bg_bam_sites_t, 16 uint32 counters, the reference byte: positions 0 and T - 1 of a tile get the counters.
 // Output per case: int64 rc, uint64 first_bad, n_sites; if rc == 0 the sites, n_regions + 1 offsets, n_regions summaries.  Per
 // synthetic tile: uint64 n, the sites.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../rust-bio_amd/csrc/bam_sites_rule.h"
-
-template <typename T>
-static T* make(size_t count) {
-    return (T*)calloc(count ? count : 1, sizeof(T));
-}
-template <typename T>
-static T* load(FILE* f, size_t count) {
-    T* p = (T*)malloc(count * sizeof(T) ? count * sizeof(T) : 1);
-    if (count && fread(p, sizeof(T), count, f) != count) exit(2);
-    return p;
-}
-static const uint32_t THREADS = 256;
+#include "bam_pileup_host_front.h"
 
 // the tail of the count pass over a counted tile: the tile's share
 static sit_share_t count_tail(const uint32_t* cnt, uint32_t n_pos, const uint8_t* ref, const bg_bam_sites_t& prm) {
@@ -103,78 +86,25 @@ int main(int argc, char** argv) {
         bg_bam_sites_t* sp = load<bg_bam_sites_t>(f, 1);
         const bg_bam_sites_t sprm = *sp;
         const bg_bam_pileup_t prm = sit_pileup_params(sprm);
-        uint8_t* all = load<uint8_t>(f, rec_bytes);
-        uint64_t* off = load<uint64_t>(f, n + 1);
-        bg_sam_contig_t* contigs = load<bg_sam_contig_t>(f, n_contigs);
-        bg_bam_region_t* regions = load<bg_bam_region_t>(f, n_regions);
+        const HostTables tb(f, n, rec_bytes, n_contigs, n_regions);
         uint8_t* text = load<uint8_t>(f, text_bytes);
-        std::vector<uint8_t*> rec(n);  // every slot a buffer of its own
-        for (uint64_t i = 0; i < n; i++) {
-            rec[i] = (uint8_t*)malloc(off[i + 1] - off[i] ? off[i + 1] - off[i] : 1);
-            memcpy(rec[i], all + off[i], off[i + 1] - off[i]);
-        }
-
         // ---- the front
-        uint64_t bad = BAI_NONE;
-        uint64_t* pos_key = make<uint64_t>(n);
-        uint64_t* end_key = make<uint64_t>(n);
-        uint64_t* pos_max = make<uint64_t>(n);
-        uint64_t* end_max = make<uint64_t>(n);
-        uint8_t* kept = make<uint8_t>(n);
-        for (uint64_t i = 0; i < n; i++) {
-            plp_slot_t s = {0, 0, 0};
-            if (off[i + 1] > off[i]) {
-                const int kind = plp_slot(rec[i], off[i + 1] - off[i], contigs, n_contigs, prm, &s);
-                if (kind && ((i << 2) | (uint64_t)kind) < bad) bad = (i << 2) | (uint64_t)kind;
-            }
-            pos_key[i] = s.pos_key;
-            end_key[i] = s.end_key;
-            kept[i] = s.kept;
-        }
-        for (uint64_t i = 0; i < n; i++) {
-            pos_max[i] = i && pos_max[i - 1] > pos_key[i] ? pos_max[i - 1] : pos_key[i];
-            end_max[i] = i && end_max[i - 1] > end_key[i] ? end_max[i - 1] : end_key[i];
-        }
-        for (uint64_t i = 0; i < n; i++)
-            if (off[i + 1] > off[i] && pos_max[i] != pos_key[i] && ((i << 2) | BAI_INVALID) < bad) bad = (i << 2) | BAI_INVALID;
-        bool region_bad = false;
-        uint64_t* row_off = make<uint64_t>(n_regions + 1);
-        uint64_t* tile_off = make<uint64_t>(n_regions + 1);
-        for (uint64_t r = 0; r < n_regions; r++) {
-            uint32_t len = 0;
-            if (sit_region_ok(regions[r], contigs, n_contigs, n_text)) len = (uint32_t)(regions[r].end - regions[r].beg);
-            else region_bad = true;
-            row_off[r + 1] = row_off[r] + len;
-            tile_off[r + 1] = tile_off[r] + plp_tiles(len);
-        }
-        int64_t rc = BG_OK;
-        uint64_t first_bad = UINT64_MAX, n_sites = 0;
-        if (sprm.flags || sprm.reserved || sprm.min_alt_permille > 1000 || region_bad) rc = BG_ERR_INVALID_ARG;
-        else if (bad != BAI_NONE) {
-            first_bad = bad >> 2;
-            rc = (bad & 3) == BAI_UNSUPPORTED ? BG_ERR_UNSUPPORTED : BG_ERR_INVALID_ARG;
-        }
-        if (!rc && text_bytes != n_text) return 4;  // only a refusal may be told of a text it does not get
+        const HostFront fr(tb, prm, sprm.flags || sprm.reserved || sprm.min_alt_permille > 1000,
+                           [&](const bg_bam_region_t& g) { return sit_region_ok(g, tb.contigs, n_contigs, n_text); });
+        uint64_t n_sites = 0;
+        auto count = [&](const plp_tile_t& t) { return fr.count(tb, prm, SIT_W, t); };
+        if (!fr.rc && text_bytes != n_text) return 4;  // only a refusal may be told of a text it does not get
 
-        if (!rc) {
-            const uint64_t tiles = tile_off[n_regions];
-            auto count = [&](const plp_tile_t& t) {
-                uint32_t* cnt = make<uint32_t>((size_t)SIT_W * BG_PILEUP_TILE);
-                const uint64_t lo = plp_lo(end_max, n, t), hi = plp_hi(pos_max, n, t);
-                for (uint64_t s = lo; s < hi; s++) {
-                    if (!kept[s]) continue;
-                    for (uint32_t lane = 0; lane < PLP_G; lane++) plp_walk_lane(rec[s], prm, t.ref, t.t0, t.t1, lane, [&](uint32_t i) { cnt[i]++; });
-                }
-                return cnt;
-            };
+        if (!fr.rc) {
+            const uint64_t tiles = fr.tile_off[n_regions];
             // ---- the count pass
             uint32_t* tile_sites = make<uint32_t>(tiles);
             uint64_t* tile_site_off = make<uint64_t>(tiles + 1);
             bg_bam_region_summary_t* tile_share = make<bg_bam_region_summary_t>(tiles);
             for (uint64_t tile = 0; tile < tiles; tile++) {
-                const plp_tile_t t = plp_tile(tile, regions, n_regions, tile_off, row_off);
+                const plp_tile_t t = plp_tile(tile, tb.regions, n_regions, fr.tile_off, fr.row_off);
                 uint32_t* cnt = count(t);
-                const sit_share_t share = count_tail(cnt, (uint32_t)(t.t1 - t.t0), text + contigs[t.ref].start + t.t0, sprm);
+                const sit_share_t share = count_tail(cnt, (uint32_t)(t.t1 - t.t0), text + tb.contigs[t.ref].start + t.t0, sprm);
                 tile_sites[tile] = sit_share_sites(share);
                 tile_share[tile] = sit_share_summary(share);
                 free(cnt);
@@ -186,27 +116,27 @@ int main(int argc, char** argv) {
             uint8_t* summary_raw = make<uint8_t>(n_regions * sizeof(bg_bam_region_summary_t) + 4);
             bg_bam_region_summary_t* summary = (bg_bam_region_summary_t*)(summary_raw + 4);
             for (uint64_t r = 0; r < n_regions; r++) {
-                bg_bam_region_summary_t a = sit_summary_stride(tile_share, tile_off[r], tile_off[r + 1], 0, THREADS);
-                for (uint32_t th = 1; th < THREADS; th++) sit_summary_join(a, sit_summary_stride(tile_share, tile_off[r], tile_off[r + 1], th, THREADS));
+                bg_bam_region_summary_t a = sit_summary_stride(tile_share, fr.tile_off[r], fr.tile_off[r + 1], 0, THREADS);
+                for (uint32_t th = 1; th < THREADS; th++) sit_summary_join(a, sit_summary_stride(tile_share, fr.tile_off[r], fr.tile_off[r + 1], th, THREADS));
                 sit_summary_store(a, summary + r);
             }
             // ---- the emit pass
             bg_bam_site_t* sites = aligned16<bg_bam_site_t>(n_sites);
             bg_bam_site_t* narrow = aligned16<bg_bam_site_t>(n_sites);
             uint64_t* site_off = make<uint64_t>(n_regions + 1);
-            for (uint64_t r = 0; r <= n_regions; r++) site_off[r] = tiles ? tile_site_off[tile_off[r]] : 0;
+            for (uint64_t r = 0; r <= n_regions; r++) site_off[r] = tiles ? tile_site_off[fr.tile_off[r]] : 0;
             for (uint64_t tile = 0; tile < tiles; tile++) {
                 if (tile_site_off[tile + 1] == tile_site_off[tile]) continue;
-                const plp_tile_t t = plp_tile(tile, regions, n_regions, tile_off, row_off);
+                const plp_tile_t t = plp_tile(tile, tb.regions, n_regions, fr.tile_off, fr.row_off);
                 uint32_t* cnt = count(t);
-                if (!emit_tail(cnt, (uint32_t)(t.t1 - t.t0), text + contigs[t.ref].start + t.t0, sprm, t.ref, t.t0, t.region, sites + tile_site_off[tile],
+                if (!emit_tail(cnt, (uint32_t)(t.t1 - t.t0), text + tb.contigs[t.ref].start + t.t0, sprm, t.ref, t.t0, t.region, sites + tile_site_off[tile],
                                narrow + tile_site_off[tile], tile_sites[tile]))
                     return 3;
                 free(cnt);
             }
             if (n_sites && memcmp(sites, narrow, n_sites * sizeof(bg_bam_site_t))) return 3;
-            fwrite(&rc, 8, 1, o);
-            fwrite(&first_bad, 8, 1, o);
+            fwrite(&fr.rc, 8, 1, o);
+            fwrite(&fr.first_bad, 8, 1, o);
             fwrite(&n_sites, 8, 1, o);
             if (n_sites) fwrite(sites, sizeof(bg_bam_site_t), n_sites, o);
             fwrite(site_off, 8, n_regions + 1, o);
@@ -219,23 +149,11 @@ int main(int argc, char** argv) {
             free(tile_site_off);
             free(tile_sites);
         } else {
-            fwrite(&rc, 8, 1, o);
-            fwrite(&first_bad, 8, 1, o);
+            fwrite(&fr.rc, 8, 1, o);
+            fwrite(&fr.first_bad, 8, 1, o);
             fwrite(&n_sites, 8, 1, o);
         }
-        free(tile_off);
-        free(row_off);
-        free(kept);
-        free(end_max);
-        free(pos_max);
-        free(end_key);
-        free(pos_key);
-        for (uint64_t i = 0; i < n; i++) free(rec[i]);
         free(text);
-        free(regions);
-        free(contigs);
-        free(off);
-        free(all);
         free(sp);
         free(hd);
     }

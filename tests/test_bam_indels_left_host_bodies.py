@@ -1,6 +1,6 @@
 """The `__host__ __device__` bodies behind the left-aligned indel events (csrc/bam_indels_left_rule.h: the walk beyond the tile's
 end, the shift of a deletion and of an insertion against the text, the shifted codes, the full-key comparison, the shifted bytes)
-run on the CPU by a stand-alone program (tests/bam_indels_left_host_bodies.cpp: the kernels' steps; the places of a tile's raw
+run on the CPU by a stand-alone program (tests/bam_indels_host_bodies.cpp, its left flavour: the kernels' steps; the places of a tile's raw
 events handed out in another order than they were counted in; an unstable sort; every buffer an exact-size heap buffer, the text
 of every contig included, so that a read of F(-1) or of the `$` stops it) built with AddressSanitizer and UBSan.  Nothing is
 loaded into Python.  Everything is held to the Python restatement (tests/bam_indels_left_oracle.py), which shares no code with

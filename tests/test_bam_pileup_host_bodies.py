@@ -13,7 +13,7 @@ import bam_pileup_oracle as po
 @pytest.fixture(scope="module")
 def ran(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("bampileup")
-    exe = pc.build_program(str(tmp / "bodies"), sanitize=True)
+    exe = pc.build_program("bam_pileup_host_bodies.cpp", str(tmp / "bodies"), sanitize=True)
     corpus = pc.corpus()
     refusals = [dict(name=name, slots=slots, contigs=contigs, regions=regions, params=dict(pc.DEFAULT), want=(status, slot))
                 for name, slots, contigs, regions, status, slot in pc.refusals()]
